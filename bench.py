@@ -328,6 +328,70 @@ class HostFeed:
         self.h2d.synchronize(); self.d2h.synchronize()
 
 
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 20261015
+DUMP_SAMPLE = {"seedext": 262144, "global": 262144, "rescue": 131072}
+
+
+def dump_outputs(out_dir, torch, pkg, kswlib, chunks, swb, d_cig, gtasks_last):
+    """--dump-outputs DIR: what the last timed step handed back, as float64 .npy files (every field is a 32-bit integer, exact in
+    float64).  A fixed, seeded sample of the records of each stage, `<stage>_index.npy` holding the sampled records' indices over
+    the step (chunks concatenated): the finished seed regions, the global scores and CIGAR lengths, the mate-rescue results.  The
+    CIGAR words live in one buffer that every chunk reuses, so after the step only the last chunk's are there: `global_cigar.npy`
+    holds the words of the sampled global tasks of that chunk, `global_cigar_task.npy` the task each word belongs to."""
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(n, k):
+        return np.sort(rng.choice(n, size=min(n, k), replace=False)) if n else np.zeros(0, np.int64)
+
+    def gather(bufs, counts, dtype, idx):
+        """records idx (over the concatenation of bufs) of a structured record type, as an (n, fields) int32 array"""
+        nf = dtype.itemsize // 4
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        rows = []
+        for b, s0, s1 in zip(bufs, starts[:-1], starts[1:]):
+            loc = idx[(idx >= s0) & (idx < s1)] - s0
+            if len(loc):
+                t = b.view(torch.int32).view(-1, nf)[torch.from_numpy(loc).to(b.device)]
+                rows.append(t.cpu().numpy())
+        return np.concatenate(rows) if rows else np.zeros((0, nf), np.int32)
+
+    arrays = {}
+
+    def put(stage, dtype, fields, bufs, counts):
+        n = int(sum(counts))
+        idx = sample(n, DUMP_SAMPLE[stage])
+        recs = gather(bufs, counts, dtype, idx)
+        arrays[f"{stage}_index"] = idx.astype(np.float64)
+        for f in fields:
+            arrays[f"{stage}_{f}"] = recs[:, dtype.names.index(f)].astype(np.float64)
+        return idx, recs
+
+    put("seedext", pkg.SEED_RES, pkg.SEED_RES.names, [c["sres"] for c in chunks], [c["n"] for c in chunks])
+    gidx, grec = put("global", pkg.GLB_RES, pkg.GLB_RES.names, [c["gres"] for c in chunks], [c["ng"] for c in chunks])
+    put("rescue", pkg.SW_RES, kswlib.SW_FIELDS, [b["swres"] for b in swb], [b["ns"] for b in swb])
+
+    # CIGAR words of the sampled global tasks of the last chunk, whole tasks, as many as the byte budget leaves room for
+    last0 = sum(c["ng"] for c in chunks[:-1])
+    sel = np.nonzero(gidx >= last0)[0]
+    ncig = grec[sel, pkg.GLB_RES.names.index("n_cigar")].astype(np.int64)
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // 16  # two float64 per word: the word and its task
+    keep = int(np.searchsorted(np.cumsum(ncig), room, side="right"))
+    sel, ncig = sel[:keep], ncig[:keep]
+    cig = d_cig.cpu().numpy().view(np.uint32)
+    offs = gtasks_last["cigar_off"][gidx[sel] - last0].astype(np.int64)
+    words = [cig[o:o + n] for o, n in zip(offs, ncig)]
+    arrays["global_cigar"] = (np.concatenate(words) if words else np.zeros(0, np.uint32)).astype(np.float64)
+    arrays["global_cigar_task"] = np.repeat(gidx[sel], ncig).astype(np.float64)
+
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_BYTES} budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": int(total), "sample_seed": DUMP_SEED}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -362,12 +426,19 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true",
                     help="rehearsal on a box with fewer GPUs than ranks: rank r uses device r %% (visible devices), the barrier and the report "
                          "go over gloo (RCCL refuses two ranks on one device).  Never for a reported number.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed, seeded sample of each stage's results, float64) "
+                         "as DIR/<name>.npy, at most 64 MB in all (rank 0)")
     ap.add_argument("--rank-echo", action="store_true", help=argparse.SUPPRESS)  # launcher self-test: print this rank's environment, touch no GPU
     args, rest = ap.parse_known_args()
     if args.rank_echo and "RANK" in os.environ:
         if os.environ["RANK"] == "0":
             print(json.dumps({k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}))
         return 0
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "pe10m":
+        ap.error("--dump-outputs is implemented for the pe10m workload")
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])  # before anything here has touched a GPU
     if args.workload == "se1m":
@@ -516,6 +587,10 @@ def main():
     elapsed = time.perf_counter() - t_start
     for c in ctxs:
         c.sync()  # surfaces any BMH_E_RANGE / BMH_E_CIGAR_CAP flagged by a kernel
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs a kernel into these buffers
+        dumped = dump_outputs(args.dump_outputs, torch, pkg, kswlib, chunks, swb, d_cig, host[-1][3])
+        note(f"dumped {len(dumped['files'])} arrays ({dumped['bytes']} bytes) of the last timed step to {args.dump_outputs}")
     if use_dist:
         dist.barrier()
     rank_ms = elapsed / args.steps * 1e3
@@ -800,6 +875,7 @@ def main():
             "cpu_baseline": cpu,
             "cpu_baseline_pipeline": pipe,
             "setup": {"taskgen_s": gen_s, "upload_s": upload_s, "host_threads_for_generation": workers},
+            "dumped_outputs": dumped,
         }
         # what `value` covers, so that it cannot be read as an end-to-end figure: the DP path only, on generator tasks
         out["value_scope"] = ("DP-path reads/s (seed extension + global alignment + mate rescue) on synthetic generator tasks, inputs resident in HBM; "

@@ -91,3 +91,21 @@ def test_bench_two_ranks_on_one_device_and_the_host_fed_step():
     assert d["value_streamed"] == st["value_streamed"] > 0 and st["h2d_bytes_per_step"] > 0 and st["d2h_bytes_per_step"] > 0
     assert st["h2d_GBps_copy_stream"] and st["h2d_GBps_copy_stream"] > 0.1
     assert d["value_streamed"] <= d["value"] * 1.25  # the fed step cannot be meaningfully faster than the resident one
+
+
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: float arrays of what the timed path computed, inside 64 MB, the same from one run to the next."""
+    import numpy as np
+    base = ["--gpus", "1", "--warmup", "1", "--pairs", "60000", "--chunk-reads", "40000", "--feed", "resident", "--no-cpu-baseline",
+            "--no-pipeline-baseline"]
+    d1 = _run(base + ["--steps", "2", "--dump-outputs", str(tmp_path / "a")])
+    d2 = _run(base + ["--steps", "3", "--dump-outputs", str(tmp_path / "b")])
+    assert d1["steps"] == 2 and d2["steps"] == 3 and d1["ms_per_step"] > 0 and d1["parity"].startswith("bit-exact")
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == d1["dumped_outputs"]["files"] == sorted(os.listdir(tmp_path / "b"))
+    assert {"seedext_score.npy", "global_score.npy", "global_cigar.npy", "rescue_score.npy"} <= set(files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    assert len(np.load(tmp_path / "a" / "global_cigar.npy")) > 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
