@@ -92,6 +92,33 @@ class _Read(C.Structure):
     _fields_ = [("l_seq", C.c_int32), ("seq", C.c_void_p)]
 
 
+class _ChainStats(C.Structure):  # bmh_chain_stats_t
+    _fields_ = [("reads", C.c_int64), ("chains_in", C.c_int64), ("chains_out", C.c_int64), ("seeds", C.c_int64), ("equal_keys", C.c_int64),
+                ("kernel_ms", C.c_float)]
+
+
+CHAIN_OPT = np.dtype([("w", "<i4"), ("max_chain_gap", "<i4"), ("min_seed_len", "<i4"), ("max_occ", "<i4"), ("split_len", "<i4"),
+                      ("split_width", "<i4"), ("mask_level", "<f4"), ("chain_drop_ratio", "<f4")])
+
+
+def _take_chains(out, n):
+    """bmh_chain_v[n] -> per read a list of SEED arrays in chain order; frees the C allocations."""
+    res = []
+    for k in range(n):
+        chains = []
+        for ci in range(out[k].n):
+            c = out[k].a[ci]
+            sd = np.zeros(c.n, dtype=SEED)
+            if c.n:
+                C.memmove(sd.ctypes.data, c.seeds, c.n * SEED.itemsize)
+            chains.append(sd)
+            _libc.free(c.seeds)
+        if out[k].a:
+            _libc.free(C.cast(out[k].a, C.c_void_p))
+        res.append(chains)
+    return res
+
+
 class _DriverStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("rounds", "ext_tasks", "seeds_extended", "seeds_skipped", "pool_bytes", "seeds_speculated", "short_sw")]
 
@@ -135,6 +162,10 @@ def lib():
         L.bmh_smem_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                      C.c_void_p, C.c_size_t]
         L.bmh_sa_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.bmh_chain_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.bmh_seed_chain_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.bmh_chain_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_matesw_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_sw_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p]
@@ -391,6 +422,54 @@ class Context:
             out.append((calls[call_off[r]:call_off[r + 1]].copy(), intv[lo:hi].copy()))
             offs.append(sa_off[lo:hi].copy())
         return out, offs, sa_pos[:n_pos.value].copy()
+
+    def chain_batch(self, opt, l_pac, reads, calls, intvs, sa_off, sa_pos):
+        """bmh_chain_batch: chaining on the GPU over per-read seeding tables (calls[r], intvs[r], sa_off[r] as seed_batch returns
+        them, sa_pos the positions).  Returns per read a list of SEED arrays in chain order (what bmh_chain_reads gives)."""
+        n = len(reads)
+        o = np.ascontiguousarray(np.asarray(opt, dtype=CHAIN_OPT).reshape(()))
+        keep = []
+        c_reads = (_Read * max(n, 1))()
+        for k, r in enumerate(reads):
+            r = np.ascontiguousarray(r, dtype=np.uint8)
+            keep.append(r)
+            c_reads[k].l_seq, c_reads[k].seq = len(r), r.ctypes.data
+        call_off = np.concatenate([[0], np.cumsum([len(c) for c in calls])]).astype(np.uint32)
+        intv_off = np.concatenate([[0], np.cumsum([len(v) for v in intvs])]).astype(np.uint64)
+        fc = np.ascontiguousarray(np.concatenate(list(calls) + [np.zeros(1, SMEM_CALL)]), dtype=SMEM_CALL)
+        fi = np.ascontiguousarray(np.concatenate(list(intvs) + [np.zeros(1, SMEM_INTV)]), dtype=SMEM_INTV)
+        fo = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in sa_off] + [np.zeros(1, np.uint64)]))
+        pos = np.ascontiguousarray(np.concatenate([np.asarray(sa_pos, dtype=np.uint64), np.zeros(1, np.uint64)]))
+        out = (_ChainV * max(n, 1))()
+        self._check(lib().bmh_chain_batch(self._h, _ptr(o), C.c_int64(int(l_pac)), n, C.cast(c_reads, C.c_void_p), _ptr(call_off), _ptr(fc),
+                                          _ptr(intv_off), _ptr(fi), _ptr(fo), _ptr(pos), C.c_uint64(len(pos) - 1), C.cast(out, C.c_void_p)))
+        return _take_chains(out, n)
+
+    def seed_chain_batch(self, smem_opt, chain_opt, l_pac, reads):
+        """bmh_seed_chain_batch: seeding and chaining in one device round trip.  Returns per read a list of SEED arrays in chain
+        order."""
+        n = len(reads)
+        o_in, so = np.asarray(smem_opt), np.zeros((), dtype=SMEM_OPT)
+        for k in o_in.dtype.names:
+            so[k] = o_in[k]
+        co = np.ascontiguousarray(np.asarray(chain_opt, dtype=CHAIN_OPT).reshape(()))
+        keep = []
+        c_reads = (_Read * max(n, 1))()
+        for k, r in enumerate(reads):
+            r = np.ascontiguousarray(r, dtype=np.uint8)
+            keep.append(r)
+            c_reads[k].l_seq, c_reads[k].seq = len(r), r.ctypes.data
+        out = (_ChainV * max(n, 1))()
+        self._check(lib().bmh_seed_chain_batch(self._h, _ptr(so), _ptr(co), C.c_int64(int(l_pac)), n, C.cast(c_reads, C.c_void_p),
+                                               C.cast(out, C.c_void_p)))
+        return _take_chains(out, n)
+
+    def chain_stats(self):
+        """bmh_chain_stats of the last chaining call: dict of reads, chains_in / chains_out (around mem_chain_flt), seeds, equal_keys,
+        kernel_ms."""
+        st = _ChainStats()
+        self._check(lib().bmh_chain_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ChainStats._fields_}
 
     def sa_batch(self, ks):
         """N x bwt_sa (reference bwt.c:85)."""

@@ -243,7 +243,9 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	if (ctx->stream) (void)stream_wait(ctx, ctx->stream);
 	free_buf(ctx->d_pool), free_buf(ctx->d_tasks), free_buf(ctx->d_res), free_buf(ctx->d_order);
 	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
-	free_buf(ctx->d_seedws), free_buf(ctx->d_region);
+	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain);
+	for (auto &e : ctx->ev_chain)
+		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
 		if (h.ev) (void)hipEventDestroy(h.ev);
 		if (h.h) (void)hipHostFree(h.h);

@@ -88,6 +88,9 @@ struct bmh_ctx {
 	DevBuf d_region; // region records, their results, CIGAR and MD slots (bmh_region_cigar_batch)
 	bmh_seedext_stats_t sstats{};
 	int64_t seed_pending_n = -1; // tasks of the bmh_seedext_submit() in flight, -1 = none
+	DevBuf d_chain;                // device chainer (chain.hip): per-read bounds, arena, compact output
+	hipEvent_t ev_chain[2] = {};   // around its chain kernel (timing mode)
+	bmh_chain_stats_t cstats{-1, -1, -1, -1, -1, -1.f};
 };
 
 namespace bmh {
@@ -109,6 +112,22 @@ struct GateGuard {
 };
 
 int set_hip_error(bmh_ctx *ctx, hipError_t e, const char *what);
+
+// bmh_seed_batch's per-read tables where they lie on the device after its kernels (fmindex.hip), for a consumer that stays there
+struct DevSeedTables {
+	int n_reads;
+	const int *len;               // read lengths
+	const uint32_t *coff;         // n_reads + 1 call offsets
+	const bmh_smem_call_t *calls; // in per-read call order, .first relative to the read's intervals
+	const uint64_t *ioff;         // n_reads + 1 interval offsets
+	const bmh_smem_intv_t *intv;
+	const uint64_t *sa_off, *sa_pos; // per interval: where its positions start (UINT64_MAX: none); the positions
+	uint64_t n_calls, n_intv, n_pos;
+};
+typedef int (*SeedTablesFn)(bmh_ctx *ctx, const DevSeedTables &t, void *user);
+// bmh_seed_batch up to its device tables, then fn on them (on the context's stream, inside the same gate); returns fn's result.
+// Capacities grow inside; env BMH_CHAIN_INIT_CAP (test knob) starts them at that many entries.
+int seed_tables_device(bmh_ctx *ctx, const bmh_smem_opt_t *o, int max_occ, int n_reads, const bmh_read_t *reads, SeedTablesFn fn, void *user);
 // every host wait for a stream goes through here (bmh_set_wait_mode)
 extern int g_wait_blocking;
 inline hipError_t stream_wait(bmh_ctx *ctx, hipStream_t s)

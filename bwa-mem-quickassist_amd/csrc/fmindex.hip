@@ -662,6 +662,8 @@ struct SeedPos {
 	uint64_t *sa_off, *sa_pos; // sa_off[k] for interval k of the output, UINT64_MAX = never looked up
 	size_t sa_cap;
 	uint64_t n_pos;            // out: positions written
+	SeedTablesFn fn = nullptr; // seed_tables_device: the tables stay on the device and go to fn instead of the caller's arrays
+	void *user = nullptr;
 };
 
 static int smem_impl(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int n_reads, const bmh_read_t *reads, uint32_t *call_off,
@@ -708,7 +710,7 @@ static int smem_impl(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int n_reads, const
 	// 105 VGPRs -> 4 waves per SIMD; the 94-register build fits 5: worth it once the batch has more waves than 4 per SIMD
 	// (500 k reads: 20.4 -> 18.9 ms), not below (200 k: 10.0 -> 10.3 ms)
 	static const bool host_order = getenv("BMH_SMEM_HOST_ORDER") && atoi(getenv("BMH_SMEM_HOST_ORDER")) != 0; // (A/B: the per-read order made on the host)
-	const bool dev_order = !host_order;
+	const bool dev_order = !host_order || (sp && sp->fn);
 	int emit_min = 16;
 	if (const char *e = getenv("BMH_SMEM_EMIT")) emit_min = atoi(e) >= 1 && atoi(e) <= 64 ? atoi(e) : 16; // (tuning knob)
 	// Two kernels, same results.  smem_conv_kernel (one extension site, 46 % of the VALU lanes active against 25 %, but about
@@ -729,6 +731,9 @@ static int smem_impl(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int n_reads, const
 	size_t d_pos = sp ? std::max<size_t>((size_t)(ctx->smem_pos_per_base * 1.25 * (double)bytes) + 4096, 4096) : 0;
 	if (const char *e = getenv("BMH_SMEM_INIT_CAP")) // (test knob: start with arrays this small, so that the first attempt overflows)
 		if (atoll(e) > 0) d_calls = d_intv = (size_t)atoll(e), d_pos = sp ? (size_t)atoll(e) : 0;
+	if (sp && sp->fn)
+		if (const char *e = getenv("BMH_CHAIN_INIT_CAP")) // (test knob of the fused seeding + chaining call: the same for its tables)
+			if (atoll(e) > 0) d_calls = d_intv = d_pos = (size_t)atoll(e);
 	const bmh_smem_call_t *h_calls = nullptr; // (in the pinned download buffer)
 	const uint32_t *h_read = nullptr;
 	const Intv *h_intv = nullptr;
@@ -807,6 +812,13 @@ static int smem_impl(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int n_reads, const
 		tt[2] = now();
 		if (totals[0] <= d_calls && totals[1] <= d_intv && (!sp || totals[4] <= d_pos)) {
 			n_calls = (size_t)totals[0];
+			if (sp && sp->fn) { // the per-read tables, where they are
+				const DevSeedTables t{n_reads, (const int *)(d + o_len), (const uint32_t *)(d + o_coff), (const bmh_smem_call_t *)(d + o_calls2),
+				                      (const uint64_t *)(d + o_ioff), (const bmh_smem_intv_t *)(d + o_intv2), (const uint64_t *)(d + o_pb2),
+				                      (const uint64_t *)(d + o_pos), (uint64_t)totals[0], (uint64_t)totals[1], (uint64_t)totals[4]};
+				sp->n_pos = totals[4];
+				return sp->fn(ctx, t, sp->user);
+			}
 			if (dev_order) { // everything is in its final order: offsets, calls, intervals, position bases, positions
 				if (totals[0] > call_cap || totals[1] > intv_cap || (totals[0] && (!calls || (!intv && totals[1]))) || (sp && totals[4] > sp->sa_cap)) break;
 				const size_t b_coff = (((size_t)n_reads + 1) * 4 + 63) & ~(size_t)63, b_ioff = ((size_t)n_reads + 1) * 8;
@@ -909,3 +921,12 @@ int bmh_seed_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int max_occ, int n_r
 }
 
 } // extern "C"
+
+int bmh::seed_tables_device(bmh_ctx *ctx, const bmh_smem_opt_t *o, int max_occ, int n_reads, const bmh_read_t *reads, SeedTablesFn fn, void *user)
+{
+	if (!o || max_occ < 0 || !fn) return BMH_E_ARG;
+	SeedPos sp{o->min_seed_len, max_occ, nullptr, nullptr, 0, 0, fn, user};
+	std::vector<uint32_t> call_off((size_t)n_reads + 1);
+	std::vector<uint64_t> intv_off((size_t)n_reads + 1);
+	return smem_impl(ctx, o, n_reads, reads, call_off.data(), nullptr, 0, intv_off.data(), nullptr, 0, &sp);
+}

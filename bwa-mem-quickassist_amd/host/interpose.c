@@ -219,23 +219,37 @@ static double g_seed_density[3] = {0.06, 0.02, 0.03}; /* calls, intervals, suffi
 static long long g_seed_us[3]; /* thread-microseconds: bmh_smem_batch, building the look-up keys, bmh_sa_batch */
 static __thread qa_seed_t *qa_seed; /* the batch this thread is chaining */
 
-static void qa_seed_batch_begin(bmh_ctx_t *ctx, const ref_mem_opt_t *opt, const ref_bwt_t *bwt, int n, const bmh_read_t *reads)
+/* the index on the context's device, and the seeding options of mem_opt_t */
+static void qa_seed_setup(bmh_ctx_t *ctx, const ref_mem_opt_t *opt, const ref_bwt_t *bwt, bmh_smem_opt_t *so)
 {
 	bmh_bwt_t ib;
+	int i, rc;
+	ib.primary = bwt->primary, ib.seq_len = bwt->seq_len, ib.bwt_size = bwt->bwt_size, ib.bwt = bwt->bwt;
+	for (i = 0; i < 5; ++i) ib.L2[i] = bwt->L2[i];
+	ib.sa_intv = bwt->sa_intv, ib.n_sa = bwt->n_sa, ib.sa = bwt->sa;
+	if ((rc = bmh_ctx_set_bwt(ctx, &ib))) bmh_tls_die(bmh_last_error(ctx), rc);
+	so->min_seed_len = opt->min_seed_len, so->split_len = (int)(opt->min_seed_len * opt->split_factor + .499); /* bwamem.c:211 */
+	so->split_width = opt->split_width, so->start_width = (opt->flag & REF_MEM_F_NO_EXACT) ? 2 : 1;           /* bwamem.c:212 */
+	so->min_emit_len = opt->min_seed_len; /* shorter intervals are never turned into seeds (bwamem.c:219): they stay on the device */
+}
+
+static void qa_chain_opt(const ref_mem_opt_t *opt, bmh_chain_opt_t *co)
+{
+	co->w = opt->w, co->max_chain_gap = opt->max_chain_gap, co->min_seed_len = opt->min_seed_len, co->max_occ = opt->max_occ;
+	co->split_len = (int)(opt->min_seed_len * opt->split_factor + .499), co->split_width = opt->split_width;
+	co->mask_level = opt->mask_level, co->chain_drop_ratio = opt->chain_drop_ratio;
+}
+
+static void qa_seed_batch_begin(bmh_ctx_t *ctx, const ref_mem_opt_t *opt, const ref_bwt_t *bwt, int n, const bmh_read_t *reads)
+{
 	bmh_smem_opt_t so;
 	qa_seed_t *S;
 	size_t tot = 0, call_cap, intv_cap, nk = 0;
 	uint64_t *keys = 0;
 	double ts[4];
-	int r, rc, i;
+	int r, rc;
 	qa_seed = 0;
-	ib.primary = bwt->primary, ib.seq_len = bwt->seq_len, ib.bwt_size = bwt->bwt_size, ib.bwt = bwt->bwt;
-	for (i = 0; i < 5; ++i) ib.L2[i] = bwt->L2[i];
-	ib.sa_intv = bwt->sa_intv, ib.n_sa = bwt->n_sa, ib.sa = bwt->sa;
-	if ((rc = bmh_ctx_set_bwt(ctx, &ib))) bmh_tls_die(bmh_last_error(ctx), rc);
-	so.min_seed_len = opt->min_seed_len, so.split_len = (int)(opt->min_seed_len * opt->split_factor + .499); /* bwamem.c:211 */
-	so.split_width = opt->split_width, so.start_width = (opt->flag & REF_MEM_F_NO_EXACT) ? 2 : 1;           /* bwamem.c:212 */
-	so.min_emit_len = opt->min_seed_len; /* shorter intervals are never turned into seeds (bwamem.c:219): they stay on the device */
+	qa_seed_setup(ctx, opt, bwt, &so);
 	for (r = 0; r < n; ++r) tot += (size_t)reads[r].l_seq;
 	S = (qa_seed_t *)calloc(1, sizeof(*S));
 	S->bwt = bwt, S->n_reads = n, S->reads = reads;
@@ -312,7 +326,20 @@ static void qa_seed_batch_end(void)
 }
 
 static long long g_p1_cnt[4]; /* chains, seeds extended, seeds speculated in vain, short-chain Smith-Watermans */
-static long long g_p1_us[5]; /* phase 1, thread-microseconds: wait for a GPU slot, seeding batch, chaining (host), wait, extension batch */
+static long long g_p1_us[5]; /* phase 1, thread-microseconds: wait for a GPU slot, seeding batch (with BMH_CHAIN_DEVICE=1: seeding + chaining),
+                              * chaining on the host (0 with BMH_CHAIN_DEVICE=1), wait, extension batch */
+static long long g_seedchain_us; /* thread-microseconds in bmh_seed_chain_batch (BMH_CHAIN_DEVICE=1) */
+
+/* BMH_CHAIN_DEVICE=1: chaining on the device, fused with seeding (bmh_seed_chain_batch); unset or 0: bmh_chain_reads on the host */
+static int qa_chain_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_CHAIN_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
 
 /* (a static body behind both exported names: inside a process that also holds the reference's own definitions -- the tests load
  * libbwa_ref.so next to this library -- a call through the exported name would bind to whichever was loaded first) */
@@ -338,25 +365,34 @@ static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, cons
 	memcpy(p.mat, opt->mat, 25);
 	tq[0] = tq[1] = stage_now();
 	ctx = bmh_pool_get(&p);
-	qa_seed_batch_begin(ctx, opt, (const ref_bwt_t *)bwt, batch_size, reads); /* SMEMs + suffix-array look-ups of the batch on the GPU */
-	bmh_pool_put(ctx);
-	tq[2] = stage_now();
-	{ /* chaining: mem_chain + mem_chain_flt (bwamem.c:1095-1097) over the batch's tables */
-		const qa_seed_t *S = qa_seed;
+	if (qa_chain_device()) { /* mem_chain + mem_chain_flt (bwamem.c:1095-1097) on the device behind the seeding: only chains come back */
+		bmh_smem_opt_t so;
 		bmh_chain_opt_t co;
-		co.w = opt->w, co.max_chain_gap = opt->max_chain_gap, co.min_seed_len = opt->min_seed_len, co.max_occ = opt->max_occ;
-		co.split_len = (int)(opt->min_seed_len * opt->split_factor + .499), co.split_width = opt->split_width;
-		co.mask_level = opt->mask_level, co.chain_drop_ratio = opt->chain_drop_ratio;
-		if ((rc = bmh_chain_reads(&co, bns->l_pac, batch_size, reads, S->call_off, S->calls, S->intv_off, S->intv, S->sa_k, S->sa_pos, chn)))
-			bmh_tls_die("the batch's seeding tables do not cover its chaining", rc);
-		{
-			long long nc = 0;
-			for (b = 0; b < batch_size; ++b) nc += (long long)chn[b].n;
-			__sync_fetch_and_add(&g_p1_cnt[0], nc);
+		qa_seed_setup(ctx, opt, (const ref_bwt_t *)bwt, &so);
+		qa_chain_opt(opt, &co);
+		if ((rc = bmh_seed_chain_batch(ctx, &so, &co, bns->l_pac, batch_size, reads, chn))) bmh_tls_die(bmh_last_error(ctx), rc);
+		bmh_pool_put(ctx);
+		tq[2] = tq[3] = stage_now();
+		__sync_fetch_and_add(&g_seedchain_us, (long long)((tq[2] - tq[1]) * 1e6));
+	} else {
+		qa_seed_batch_begin(ctx, opt, (const ref_bwt_t *)bwt, batch_size, reads); /* SMEMs + suffix-array look-ups of the batch on the GPU */
+		bmh_pool_put(ctx);
+		tq[2] = stage_now();
+		{ /* chaining: mem_chain + mem_chain_flt (bwamem.c:1095-1097) over the batch's tables */
+			const qa_seed_t *S = qa_seed;
+			bmh_chain_opt_t co;
+			qa_chain_opt(opt, &co);
+			if ((rc = bmh_chain_reads(&co, bns->l_pac, batch_size, reads, S->call_off, S->calls, S->intv_off, S->intv, S->sa_k, S->sa_pos, chn)))
+				bmh_tls_die("the batch's seeding tables do not cover its chaining", rc);
 		}
+		qa_seed_batch_end();
+		tq[3] = stage_now();
 	}
-	qa_seed_batch_end();
-	tq[3] = stage_now();
+	{
+		long long nc = 0;
+		for (b = 0; b < batch_size; ++b) nc += (long long)chn[b].n;
+		__sync_fetch_and_add(&g_p1_cnt[0], nc);
+	}
 	tq[4] = stage_now();
 	ctx = bmh_pool_get(&p);
 	{ /* reference resident in HBM, shared by all contexts: the kernels do bns_get_seq themselves.  BMH_PAC_RESIDENT=0
@@ -617,12 +653,20 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	t_[3] = realtime();
 	free(reads);
 	if (getenv("BMH_VERBOSE")) {
-		fprintf(stderr, "[bwamem_hip] seeding batch thread-seconds so far: bmh_smem_batch %.3f, look-up keys %.3f, bmh_sa_batch %.3f\n",
-		        g_seed_us[0] * 1e-6, g_seed_us[1] * 1e-6, g_seed_us[2] * 1e-6);
-		fprintf(stderr, "[bwamem_hip] phase 1 thread-seconds so far: wait %.3f, seeding batch %.3f, chaining on the host %.3f, wait %.3f, extension batch %.3f\n",
-		        g_p1_us[0] * 1e-6, g_p1_us[1] * 1e-6, g_p1_us[2] * 1e-6, g_p1_us[3] * 1e-6, g_p1_us[4] * 1e-6);
-		fprintf(stderr, "[bwamem_hip] phase 1 so far: %lld chains from bmh_chain_reads, %lld seeds extended (+%lld speculated in vain), %lld short-chain Smith-Watermans batched\n",
-		        g_p1_cnt[0], g_p1_cnt[1], g_p1_cnt[2], g_p1_cnt[3]);
+		if (qa_chain_device()) {
+			fprintf(stderr, "[bwamem_hip] seeding batch thread-seconds so far: bmh_seed_chain_batch (seeding + chaining on the device) %.3f\n",
+			        g_seedchain_us * 1e-6);
+			fprintf(stderr, "[bwamem_hip] phase 1 thread-seconds so far: wait %.3f, seeding + chaining batch %.3f, chaining on the host %.3f, wait %.3f, extension batch %.3f\n",
+			        g_p1_us[0] * 1e-6, g_p1_us[1] * 1e-6, g_p1_us[2] * 1e-6, g_p1_us[3] * 1e-6, g_p1_us[4] * 1e-6);
+		} else {
+			fprintf(stderr, "[bwamem_hip] seeding batch thread-seconds so far: bmh_smem_batch %.3f, look-up keys %.3f, bmh_sa_batch %.3f\n",
+			        g_seed_us[0] * 1e-6, g_seed_us[1] * 1e-6, g_seed_us[2] * 1e-6);
+			fprintf(stderr, "[bwamem_hip] phase 1 thread-seconds so far: wait %.3f, seeding batch %.3f, chaining on the host %.3f, wait %.3f, extension batch %.3f\n",
+			        g_p1_us[0] * 1e-6, g_p1_us[1] * 1e-6, g_p1_us[2] * 1e-6, g_p1_us[3] * 1e-6, g_p1_us[4] * 1e-6);
+		}
+		fprintf(stderr, "[bwamem_hip] phase 1 so far: %lld chains from %s, %lld seeds extended (+%lld speculated in vain), %lld short-chain Smith-Watermans batched\n",
+		        g_p1_cnt[0], qa_chain_device() ? "bmh_seed_chain_batch on the device" : "bmh_chain_reads", g_p1_cnt[1], g_p1_cnt[2],
+		        g_p1_cnt[3]);
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
 		fprintf(stderr, "[bwamem_hip] chunk of %d reads: phase 1 %.3f s, pestat %.3f s + mate rescue %.3f s, phase 2 (marking, pairing, global alignments, SAM) %.3f s\n", n,
 		        t_[1] - t_[0], t_pes - t_[1], t_[2] - t_pes, t_[3] - t_[2]);

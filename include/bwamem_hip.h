@@ -526,8 +526,9 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
  * Replaces: bwt_smem1 (reference bwa-0.7.8/bwt.c:288-347; over bwt_extend :261-274 and bwt_2occ4 :191-219), called in the
  *           order smem_next2 calls it for one read (bwamem.c:118-162 as driven by mem_insert_seed, bwamem.c:208-214), and
  *           bwt_sa (bwt.c:85-95; over bwt_invPsi :52-58 and bwt_occ :107-129).
- * Chaining (mem_insert_seed's B-tree, mem_chain_flt) stays host code; INTEGRATION.md shows how the reference's
- * mem_chain consumes these results unchanged. */
+ * Chaining (mem_insert_seed's B-tree, mem_chain_flt) is bmh_chain_reads on the host or bmh_chain_batch /
+ * bmh_seed_chain_batch on the device (below); INTEGRATION.md shows how the reference's mem_chain consumes these results
+ * unchanged. */
 typedef struct bmh_bwt { /* the fields of bwt_t the queries read (bwt.h:45-57); arrays are borrowed, never modified */
 	uint64_t primary, L2[5], seq_len, bwt_size; /* bwt_size in 32-bit words */
 	const uint32_t *bwt;                        /* BWT with the interleaved occurrence counts (bwt.h:63-64 layout) */
@@ -594,7 +595,8 @@ int bmh_seed_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int max_occ, int n_r
 int bmh_sa_batch(bmh_ctx_t *ctx, const uint64_t *k, int64_t n, uint64_t *pos);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Seeds to chains (the rest of SURVEY.md §8(f) row 3): host code over the results of bmh_smem_batch / bmh_sa_batch.
+ * Seeds to chains (the rest of SURVEY.md §8(f) row 3): host code over the results of bmh_smem_batch / bmh_sa_batch,
+ * and the same on the device (bmh_chain_batch, bmh_seed_chain_batch at the end of this section).
  * Replaces: mem_chain (reference bwamem.c:283-306) = smem_next2's rounds (:118-157) + mem_insert_seed (:208-243, over
  *           test_and_merge :186-206 and klib's B-tree of chains) + the in-order read-out, followed by mem_chain_flt
  *           (:319-380) -- lines bwamem.c:1096-1097 of mem_align1_core_batched.
@@ -618,6 +620,25 @@ uint64_t bmh_chain_sa_keys(const bmh_chain_opt_t *o, uint64_t n_intv, const bmh_
 int bmh_chain_reads(const bmh_chain_opt_t *o, int64_t l_pac, int n_reads, const bmh_read_t *reads, const uint32_t *call_off,
                     const bmh_smem_call_t *calls, const uint64_t *intv_off, const bmh_smem_intv_t *intv, const uint64_t *sa_off,
                     const uint64_t *sa_pos, bmh_chain_v *chains);
+/* bmh_chain_reads on the GPU: same inputs, same output form (chains[r].a and every seed array malloc'd, caller frees).
+ * One lane per read simulates the same B-tree node for node, so chains, seeds and their order are bmh_chain_reads'.
+ * n_pos: entries of sa_pos.  BMH_E_ARG (and no chains) when the tables are inconsistent: a re-seeding call out of
+ * smem_next2's order, a long and rare interval without positions, offsets outside the arrays. */
+int bmh_chain_batch(bmh_ctx_t *ctx, const bmh_chain_opt_t *o, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                    const uint32_t *call_off, const bmh_smem_call_t *calls, const uint64_t *intv_off,
+                    const bmh_smem_intv_t *intv, const uint64_t *sa_off, const uint64_t *sa_pos, uint64_t n_pos,
+                    bmh_chain_v *chains);
+/* bmh_seed_batch + chaining in ONE device round trip: reads up, chains down; nothing else crosses PCIe.
+ * Needs bmh_ctx_set_bwt.  so->min_seed_len / split_len / split_width must equal co's, so->min_emit_len <= co->min_seed_len
+ * (BMH_E_ARG otherwise).  Capacities grow inside the call. */
+int bmh_seed_chain_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac,
+                         int n_reads, const bmh_read_t *reads, bmh_chain_v *chains);
+typedef struct bmh_chain_stats { /* of the last successful bmh_chain_batch / bmh_seed_chain_batch (-1: none yet) */
+	int64_t reads, chains_in, chains_out, seeds; /* chains before / after mem_chain_flt; seeds of the chains kept */
+	int64_t equal_keys; /* look-ups of the B-tree of chains that met an equal key (their answer depends on its splits) */
+	float kernel_ms;    /* the chain kernel's duration with kernel timing on, else -1 */
+} bmh_chain_stats_t;
+int bmh_chain_stats(bmh_ctx_t *ctx, bmh_chain_stats_t *st);
 
 #ifdef __cplusplus
 }

@@ -71,9 +71,12 @@ def sim_pairs_fast(rng, ref, n, L, noisy_frac):
     return a, b
 
 
-def run(fa, fq, threads, batch, preload, out, ksw_dropin=True):
+def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=False):
     env = dict(os.environ)
+    env.pop("BMH_CHAIN_DEVICE", None)
     if preload:
+        if chain_device:
+            env["BMH_CHAIN_DEVICE"] = "1"
         env["LD_PRELOAD"] = load_package().DROPIN_PATH
         env["BMH_KSW_DROPIN"] = "1" if ksw_dropin else "0"
         env["BMH_VERBOSE"] = "1"
@@ -106,6 +109,7 @@ def main():
     ap.add_argument("--noisy", type=float, default=0.3, help="--pe: fraction of second mates that need rescue")
     ap.add_argument("--repeats", type=int, default=0, help="plant this many diverged repeats (200-3000 bp) in the genome")
     ap.add_argument("--full", action="store_true", help="also time the per-call ksw_global2 GPU drop-in (slow by design)")
+    ap.add_argument("--chain-device", action="store_true", help="DUT chains on the device, fused with seeding (BMH_CHAIN_DEVICE=1)")
     a = ap.parse_args()
     rng = np.random.default_rng(20261007)
     tmp = tempfile.mkdtemp(prefix="bmh_pipe_")
@@ -127,18 +131,19 @@ def main():
     else:
         reads = sim_reads_fast(rng, ref, a.reads, 150)
         reflib.write_fastq(fq, list(reads))
-    res = {"genome_bp": a.genome, "repeats": a.repeats, "reads": a.reads, "paired": bool(a.pe), "index_s": t_index, "runs": []}
+    res = {"genome_bp": a.genome, "repeats": a.repeats, "reads": a.reads, "paired": bool(a.pe), "index_s": t_index, "chain_device": bool(a.chain_device),
+           "runs": []}
     # one untimed DUT run first: on a fresh box the first process to load the HIP runtime and the library's code objects
     # pays for reading them from disk (seconds), which has nothing to do with the pipeline
     run(fa, fq, 8, a.batch, True, os.path.join(tmp, "warm.sam"), ksw_dropin=False)
     for t in [int(x) for x in a.threads.split(",")]:
         r = run(fa, fq, t, a.batch, False, os.path.join(tmp, "ref.sam"))
         refsam = [l for l in open(os.path.join(tmp, "ref.sam")) if not l.startswith("@PG")]
-        d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False)
+        d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False, chain_device=a.chain_device)
         same1 = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         d2 = None
         if a.full:
-            d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True)
+            d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True, chain_device=a.chain_device)
             d2["sam_identical"] = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         res["runs"].append({"threads": t, "batch": a.batch, "ref": r, "dut_phase1_gpu": d1, "sam_identical": same1,
                             "dut_phase1_gpu_plus_percall_global": d2})
