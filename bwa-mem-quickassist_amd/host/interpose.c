@@ -4,10 +4,12 @@
  * It provides mem_align1_core_batched() with the fork's exact signature
  * (reference bwa-0.7.8/bwamem.c:1086) so that, preloaded in front of a build of the
  * reference (oracle/_ref/bwa + libbwa_ref.so), phase 1 of mem_process_seqs
- * (bwamem.c:1313 -> worker1_batched :1264) runs seeding/chaining on the CPU exactly
- * as before and hands every batch's chains to bmh_chain2aln_batch() -- the hook the
- * fork left commented out at bwamem.c:1110.  Run `bwa mem -b <batch>` to choose the
- * batch size.  INTEGRATION.md shows the same code as a patch to bwamem.c.
+ * (bwamem.c:1313 -> worker1_batched :1264) runs on the library: seeding as one device
+ * batch (bmh_seed_batch), chaining on the host (bmh_chain_reads) or, with
+ * BMH_CHAIN_DEVICE=1, fused with seeding on the device (bmh_seed_chain_batch), then
+ * every batch's chains go to bmh_chains2regs_batch() -- the hook the fork left
+ * commented out at bwamem.c:1110.  Run `bwa mem -b <batch>` to choose the batch size.
+ * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
  * Everything declared `extern` below is the reference's own symbol, resolved at load
  * time from libbwa_ref.so; nothing of the reference is compiled into this library.

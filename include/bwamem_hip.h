@@ -605,7 +605,10 @@ int bmh_sa_batch(bmh_ctx_t *ctx, const uint64_t *k, int64_t n, uint64_t *pos);
  * x[2] <= max_occ), its suffix-array indices x[0]..x[0]+x[2]-1 and records in sa_off[k] where interval k's run starts
  * (UINT64_MAX = never looked up); the caller resolves the list with ONE bmh_sa_batch and passes the positions as sa_pos
  * -- no sorting, no searching.  chains[r] is filled like mem_chain's return value: a malloc'd array of chains in the
- * reference's order, each with a malloc'd seed array; the caller frees both.
+ * reference's order, each with a malloc'd seed array; the caller frees both.  bmh_chain_reads returns BMH_E_ARG when the
+ * tables are inconsistent (a re-seeding record out of smem_next2's order, a long and rare interval without positions, a
+ * call or read range outside the tables) and BMH_E_NOMEM when an allocation fails; either way no read keeps chains:
+ * every chains[r] is {0, 0, NULL} and nothing is left allocated.
  * Precondition: the intervals come from a bmh_smem_batch / bmh_seed_batch run with min_emit_len <= o->min_seed_len (0
  * included): with a larger filter the longest match of a call and the re-seeding decision derived from it would be
  * computed from a truncated list and chains would silently differ. */
