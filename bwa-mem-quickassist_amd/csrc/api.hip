@@ -638,8 +638,12 @@ static int validate_seeds(bmh_ctx *ctx, const bmh_seed_task_t *t, int64_t n, siz
 			ctx->last_error = "seed " + std::to_string(k) + " reads outside the sequence pool";
 			return BMH_E_ARG;
 		}
-		if (x.qbeg > 65535 || rq > 65535 || x.rbeg > 65535 || rt > 65535 || (int64_t)x.l_query * smax > kScoreLimit) {
-			ctx->last_error = "seed " + std::to_string(k) + ": flank longer than 65535 or scores beyond the 16-bit range";
+		if (x.qbeg > 65535 || rq > 65535 || x.rbeg > 65535 || rt > 65535) {
+			ctx->last_error = "seed " + std::to_string(k) + ": flank longer than 65535";
+			return BMH_E_RANGE;
+		}
+		if ((int64_t)x.l_query * smax > kScoreLimit) {
+			ctx->last_error = "seed " + std::to_string(k) + ": l_query*max(max(mat), a) exceeds the 16-bit score range";
 			return BMH_E_RANGE;
 		}
 		qm = std::max(qm, std::max(x.qbeg, (int)rq));
@@ -877,6 +881,7 @@ int bmh_sw_batch_device(bmh_ctx_t *ctx, const uint8_t *d_pool, const bmh_sw_task
 static int validate_sw(bmh_ctx *ctx, const bmh_sw_task_t *tasks, int64_t n, size_t pool_bytes, int *qmax_, int *tmax_, int *qmin_)
 {
 	int qmax = 1, tmax = 1, qmin = 65535;
+	const bool wraps = sw_byte_gaps_wrap(ctx->params);
 	for (int64_t k = 0; k < n; ++k) {
 		const bmh_sw_task_t &x = tasks[k];
 		qmin = std::min(qmin, (int)x.qlen);
@@ -895,6 +900,10 @@ static int validate_sw(bmh_ctx *ctx, const bmh_sw_task_t *tasks, int64_t n, size
 		}
 		if (x.qlen < 1 || (int64_t)x.qlen * ctx->dev.max_mat >= kScoreLimit) {
 			ctx->last_error = "Smith-Waterman task " + std::to_string(k) + ": qlen must be >= 1 and qlen*max(mat) below the 16-bit score range";
+			return BMH_E_RANGE;
+		}
+		if (wraps && (x.xtra & BMH_SW_XBYTE)) {
+			ctx->last_error = "Smith-Waterman task " + std::to_string(k) + ": byte mode needs o_del+e_del and o_ins+e_ins below 256";
 			return BMH_E_RANGE;
 		}
 		qmax = std::max(qmax, (int)x.qlen), tmax = std::max(tmax, (int)x.tlen);

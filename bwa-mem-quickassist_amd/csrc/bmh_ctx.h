@@ -150,6 +150,13 @@ int ensure_host(bmh_ctx *ctx, DevBuf &b, size_t bytes); // same, pinned host mem
 // each block walks its bin with a grid stride
 constexpr long long kPersistentGrid = 256LL * 32 * 4;
 
+// gap costs the extension kernels are exact for: o+e within 16 bits and e below 2^14.  The bound is empirical:
+// e = 25535 and 65535, and o_ins+e_ins = 70000, gave other extensions than the reference in every family, and
+// tests/test_score_domain_gpu.py pins e = 16383 as exact; the cause is not established
+inline bool ext_gaps_too_large(const bmh_params_t &p)
+{
+	return (long long)p.o_del + p.e_del > 65535 || (long long)p.o_ins + p.e_ins > 65535 || p.e_del > 16383 || p.e_ins > 16383;
+}
 // dispatcher: classifies the tasks by query length on the device and runs each bin on its kernel
 // d_n (nullable): device-side count <= n of the entries of d_order (or of d_tasks) that are tasks; kind: which
 // BinHint slot the launch reads and refreshes
@@ -176,6 +183,9 @@ int launch_extend_lanex(bmh_ctx *ctx, int lpt, const uint8_t *d_pool, const bmh_
                         bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int min_count);
 int launch_sw(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n, bmh_sw_result_t *d_res,
               int qcap, int tcap, int qmin);
+// ksw_u8 holds o+e in 8-bit lanes (reference ksw.c:125-128), where 256 and more wrap; the kernels do not restate that,
+// so byte-mode tasks under such penalties are refused (BMH_E_RANGE)
+inline bool sw_byte_gaps_wrap(const bmh_params_t &p) { return p.o_del + p.e_del > 255 || p.o_ins + p.e_ins > 255; }
 int launch_sw_lane(bmh_ctx *ctx, int b, bool corr, bool word, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n,
                    bmh_sw_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, uint16_t *d_rm, int rows_cap,
                    int grid, int pass2, uint32_t *d_next);

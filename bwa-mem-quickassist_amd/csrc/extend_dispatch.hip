@@ -200,6 +200,10 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
                   bmh_ext_result_t *d_res, const uint32_t *d_order, int qmax, const uint32_t *d_n, int kind)
 {
 	if (n <= 0) return BMH_OK;
+	if (ext_gaps_too_large(ctx->params)) {
+		ctx->last_error = "the extension kernels need o_del+e_del, o_ins+e_ins <= 65535 and e_del, e_ins <= 16383";
+		return BMH_E_RANGE;
+	}
 	int rc;
 	if (kind < 0 || kind >= bmh_ctx::kHintKinds) kind = 0;
 	hint_poll(ctx, kind);

@@ -211,6 +211,10 @@ int launch_seedext(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_seed_task_t *d
                    int qmax)
 {
 	if (n <= 0) return BMH_OK;
+	if (ext_gaps_too_large(ctx->params)) {
+		ctx->last_error = "the extension kernels need o_del+e_del, o_ins+e_ins <= 65535 and e_del, e_ins <= 16383";
+		return BMH_E_RANGE;
+	}
 	if (ctx->params.w < 1 || (ctx->params.w << 1) > 32767) {
 		ctx->last_error = "the fused per-seed extension needs 1 <= w and 2*w <= 32767";
 		return BMH_E_RANGE;

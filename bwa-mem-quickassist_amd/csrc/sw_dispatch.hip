@@ -8,14 +8,16 @@
 namespace bmh {
 
 // largest padded query and target length of a device-resident batch (the *_device entry point has no host view)
+// (and caps[3] = 1 if any task is in byte mode)
 __global__ void sw_caps_kernel(const bmh_sw_task_t *__restrict__ tasks, long long n, int *caps)
 {
-	int q = 0, t = 0, qi = 0; // qi = 65535 - shortest query
+	int q = 0, t = 0, qi = 0, by = 0; // qi = 65535 - shortest query
 	for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
 		q = max(q, (int)tasks[k].qlen), t = max(t, (int)min(tasks[k].tlen, 0x7fffffffu)), qi = max(qi, 65535 - (int)tasks[k].qlen);
+		by |= (tasks[k].xtra & BMH_SW_XBYTE) != 0;
 	}
-	q = wave_reduce_max(q), t = wave_reduce_max(t), qi = wave_reduce_max(qi);
-	if ((threadIdx.x & 63) == 0) atomicMax(&caps[0], q), atomicMax(&caps[1], t), atomicMax(&caps[2], qi);
+	q = wave_reduce_max(q), t = wave_reduce_max(t), qi = wave_reduce_max(qi), by = wave_reduce_max(by);
+	if ((threadIdx.x & 63) == 0) atomicMax(&caps[0], q), atomicMax(&caps[1], t), atomicMax(&caps[2], qi), atomicMax(&caps[3], by);
 }
 
 // ---- batches of up to 32 768 tasks: sw_wave_kernel (one wave per task, sw_wave.hip) takes every task the register kernels
@@ -102,13 +104,17 @@ int launch_sw(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks,
 	int rc;
 	if (qcap < 0 || tcap < 0) { // one small reduction + read-back
 		if ((rc = ensure(ctx, ctx->d_scratch, 256))) return rc;
-		int *caps = (int *)ctx->d_scratch.p, h[3] = {0, 0, 0};
-		BMH_HIP(ctx, hipMemsetAsync(caps, 0, 12, ctx->stream));
+		int *caps = (int *)ctx->d_scratch.p, h[4] = {0, 0, 0, 0};
+		BMH_HIP(ctx, hipMemsetAsync(caps, 0, 16, ctx->stream));
 		hipLaunchKernelGGL(sw_caps_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024)), dim3(256), 0,
 		                   ctx->stream, d_tasks, (long long)n, caps);
-		BMH_HIP(ctx, hipMemcpyAsync(h, caps, 12, hipMemcpyDeviceToHost, ctx->stream));
+		BMH_HIP(ctx, hipMemcpyAsync(h, caps, 16, hipMemcpyDeviceToHost, ctx->stream));
 		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
 		qcap = h[0], tcap = h[1], qmin = 65535 - h[2];
+		if (h[3] && sw_byte_gaps_wrap(ctx->params)) { // the host entry points check this per task (validate_sw)
+			ctx->last_error = "Smith-Waterman byte mode needs o_del+e_del and o_ins+e_ins below 256";
+			return BMH_E_RANGE;
+		}
 	}
 	const int qfine = (qmin >= 1 && qcap - qmin < 64) ? qmin : -1; // see sw_hist_kernel
 	// a batch that cannot fill the chip with one lane per task goes to one wave per task (sw_wave.hip): the register

@@ -103,7 +103,8 @@ typedef struct bmh_glb_result {
 
 /* Supported range (checked on the host, BMH_E_RANGE otherwise):
  *   extend: 0 <= qlen,tlen <= 65535; scores must fit int16 lanes:
- *           h0 + qlen*max(mat) <= 32000; o_ins >= 0 (SURVEY.md §7 hard part 1).
+ *           h0 + qlen*max(mat) <= 32000; o_ins >= 0 (SURVEY.md §7 hard part 1);
+ *           o_del+e_del, o_ins+e_ins <= 65535, e_del, e_ins <= 16383 (also for bmh_seedext_batch).
  *   global: qlen,tlen <= 65535. */
 
 typedef struct bmh_ctx bmh_ctx_t;
@@ -402,8 +403,9 @@ int bmh_ctx_reserve_kernels(bmh_ctx_t *ctx, int seed_reads, int seed_read_len, i
  * and the result is field for field kswr_t (ksw.h:14-19), including the byte-mode (16 columns per vector) versus
  * word-mode (8) differences of the striped reference, which are visible in score2/te2 and, rarely, the scores.
  * m = 5 and the matrix / gap penalties come from bmh_params_t.  Inputs outside the exact domain are refused with
- * BMH_E_RANGE: qlen*max(mat) >= 32000, and byte-mode tasks that can overflow (qlen*max(mat) + shift >= 255) combined
- * with KSW_XSTART, for which the reference reads uninitialised memory (ksw.c:355-357). */
+ * BMH_E_RANGE: qlen*max(mat) >= 32000, gap penalties above 255, byte-mode tasks that can overflow (qlen*max(mat) + shift
+ * >= 255) combined with KSW_XSTART, for which the reference reads uninitialised memory (ksw.c:355-357), and byte-mode
+ * tasks when o_del+e_del or o_ins+e_ins reaches 256, which ksw_u8 wraps in its 8-bit lanes (ksw.c:125-128). */
 #define BMH_SW_XBYTE 0x10000u
 #define BMH_SW_XSTOP 0x20000u
 #define BMH_SW_XSUBO 0x40000u

@@ -27,7 +27,9 @@ static core_out_t sw_core(int size, int qlen, const uint8_t *query, int tlen, co
 	const int p = size == 1 ? 16 : 8;      /* values per vector, ksw.c:68 */
 	const int slen = (qlen + p - 1) / p;   /* segment length, ksw.c:69 */
 	const int Q = slen * p;                /* padded query length */
-	const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
+	/* ksw_u8 broadcasts each penalty into 8-bit lanes (_mm_set1_epi8, ksw.c:125-128): o+e of 256 or more wraps there */
+	const int msk = size == 1 ? 0xff : 0xffff;
+	const int oe_del = (o_del + e_del) & msk, oe_ins = (o_ins + e_ins) & msk;
 	const int minsc = (xtra & ORC_XSUBO) ? (xtra & 0xffff) : 0x10000; /* ksw.c:131-132 */
 	const int endsc = (xtra & ORC_XSTOP) ? (xtra & 0xffff) : 0x10000;
 	uint8_t shift = 127, mdiff = 0;
@@ -38,6 +40,7 @@ static core_out_t sw_core(int size, int qlen, const uint8_t *query, int tlen, co
 	int f[16], h[16];
 	core_out_t r = {0, -1, -1, -1, -1};
 
+	e_del &= msk, e_ins &= msk;
 	for (a = 0; a < m * m; ++a) { /* ksw.c:78-85: bias and largest score */
 		if (mat[a] < (int8_t)shift) shift = (uint8_t)mat[a];
 		if (mat[a] > (int8_t)mdiff) mdiff = (uint8_t)mat[a];
