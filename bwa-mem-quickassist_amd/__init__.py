@@ -142,6 +142,8 @@ def lib():
         L.bmh_ctx_set_params.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_ctx_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_ctx_set_qcap.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_ctx_set_wide_extension.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_extend_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_ctx_reserve_staging.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
         L.bmh_ctx_set_pac.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -241,6 +243,17 @@ class Context:
 
     def set_qcap(self, q):
         self._check(lib().bmh_ctx_set_qcap(self._h, int(q)))
+
+    def set_wide_extension(self, on=True):
+        """Opt in to the int32 extension kernel: scores past 32000, queries past 13 632 and gap costs past 16 bits go to it
+        instead of being refused (bmh_ctx_set_wide_extension)."""
+        self._check(lib().bmh_ctx_set_wide_extension(self._h, 1 if on else 0))
+
+    def extend_wide_stats(self):
+        """(tasks, ms) the last extension launch sent to the int32 kernel; ms is -1 with timing off (bmh_extend_wide_stats)."""
+        n, ms = C.c_int64(0), C.c_float(-1)
+        self._check(lib().bmh_extend_wide_stats(self._h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
 
     def reserve_staging(self, upload_bytes, download_bytes):
         """Pinned staging buffers of the host-buffer entry points, allocated ahead of the first batch."""

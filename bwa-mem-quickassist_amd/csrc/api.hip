@@ -222,7 +222,7 @@ int bmh_ctx_create(bmh_ctx_t **out, int device)
 	if (const char *m = getenv("BMH_EXT_GRID_MULT")) ctx->ext_grid_mult = atoi(m) > 0 ? atoi(m) : ctx->ext_grid_mult;
 	if (const char *m = getenv("BMH_EXT_SMALL")) ctx->small_batch = atoi(m) >= 0 ? atoi(m) : ctx->small_batch;
 	if (getenv("BMH_EXT_MODE")) ctx->ext_mode_forced = true;
-	if (const char *m = getenv("BMH_EXT_MODE")) ctx->force_kernel = !strcmp(m, "lds") ? 1 : !strcmp(m, "reg") ? 2 : !strcmp(m, "grp") ? 3 : !strcmp(m, "lanex4") ? 4 : 0;
+	if (const char *m = getenv("BMH_EXT_MODE")) ctx->force_kernel = !strcmp(m, "lds") ? 1 : !strcmp(m, "reg") ? 2 : !strcmp(m, "grp") ? 3 : !strcmp(m, "lanex4") ? 4 : !strcmp(m, "wide") ? 5 : 0;
 	if (const char *m = getenv("BMH_GLB_MODE")) ctx->glb_mode = !strcmp(m, "wave") ? 1 : 0;
 	if (const char *m = getenv("BMH_SW_MODE")) ctx->sw_mode = !strcmp(m, "generic") ? 1 : 0;
 	if (const char *m = getenv("BMH_SW_WAVE")) ctx->sw_wave = atoi(m) != 0;
@@ -243,7 +243,8 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	if (ctx->stream) (void)stream_wait(ctx, ctx->stream);
 	free_buf(ctx->d_pool), free_buf(ctx->d_tasks), free_buf(ctx->d_res), free_buf(ctx->d_order);
 	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
-	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain);
+	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab);
+	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	for (auto &e : ctx->ev_chain)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
@@ -382,6 +383,34 @@ int bmh_ctx_set_qcap(bmh_ctx_t *ctx, int qcap)
 	return BMH_OK;
 }
 
+int bmh_ctx_set_wide_extension(bmh_ctx_t *ctx, int enable)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (enable && !ctx->d_wide_stat) {
+		BMH_HIP(ctx, hipSetDevice(ctx->device));
+		BMH_HIP(ctx, hipMalloc((void **)&ctx->d_wide_stat, sizeof(unsigned long long)));
+		BMH_HIP(ctx, hipMemsetAsync(ctx->d_wide_stat, 0, sizeof(unsigned long long), ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	}
+	ctx->wide_ext = enable != 0;
+	return BMH_OK;
+}
+
+int bmh_extend_wide_stats(const bmh_ctx_t *cctx, int64_t *tasks, float *ms)
+{
+	if (!cctx || !tasks || !ms) return BMH_E_ARG;
+	bmh_ctx *ctx = const_cast<bmh_ctx *>(cctx); // (waits for the stream; the context's settings are not touched)
+	*tasks = 0, *ms = -1.f;
+	if (!ctx->wide_last) return BMH_OK;
+	unsigned long long c = 0;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, hipMemcpyAsync(&c, ctx->d_wide_stat, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	*tasks = (int64_t)c;
+	if (ctx->timing) *ms = (float)ctx->wide_ms_sum;
+	return BMH_OK;
+}
+
 int bmh_ctx_sync(bmh_ctx_t *ctx)
 {
 	if (!ctx) return BMH_E_ARG;
@@ -481,8 +510,12 @@ static int validate_ext(bmh_ctx *ctx, const bmh_ext_task_t *t, int64_t n, size_t
 			return BMH_E_ARG;
 		}
 		const int h0 = x.h0 < 0 ? 0 : x.h0;
-		if ((int64_t)h0 + (int64_t)x.qlen * ctx->dev.max_mat > kScoreLimit) {
+		if (!ctx->wide_ext && (int64_t)h0 + (int64_t)x.qlen * ctx->dev.max_mat > kScoreLimit) {
 			ctx->last_error = "task " + std::to_string(k) + ": h0 + qlen*max(mat) exceeds the 16-bit score range";
+			return BMH_E_RANGE;
+		}
+		if (ctx->wide_ext && (int64_t)h0 + (int64_t)x.qlen * ctx->dev.max_mat > kWideScoreLimit) {
+			ctx->last_error = "task " + std::to_string(k) + ": h0 + qlen*max(mat) exceeds the wide extension's score range (2^24)";
 			return BMH_E_RANGE;
 		}
 		qm = std::max(qm, (int)x.qlen);
@@ -524,6 +557,12 @@ int bmh_extend_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, con
 	if ((rc = st.d2h(results, ctx->d_res.p, (size_t)n * sizeof(bmh_ext_result_t)))) return rc;
 	rc = fetch_err(ctx); // synchronises
 	st.finish();
+	if (ctx->wide_last) {
+		unsigned long long c = 0;
+		BMH_HIP(ctx, hipMemcpyAsync(&c, ctx->d_wide_stat, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+		ctx->wide_total += (long long)c;
+	}
 	return rc;
 }
 
@@ -544,6 +583,8 @@ int bmh_upload_pool(bmh_ctx_t *ctx, const uint8_t *pool, size_t bytes)
 
 // internal hooks for host/chain2aln_batch.c (C cannot see inside bmh_ctx)
 const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx) { return ctx && ctx->have_params ? &ctx->params : nullptr; }
+// ... and for host/tls_ctx.c: tasks the int32 extension kernel received over this context's host-buffer calls
+int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx) { return ctx ? ctx->wide_total : 0; }
 void bmh_ctx_set_driver_stats_(bmh_ctx_t *ctx, const bmh_driver_stats_t *st)
 {
 	if (ctx && st) ctx->dstats = *st;
@@ -642,8 +683,12 @@ static int validate_seeds(bmh_ctx *ctx, const bmh_seed_task_t *t, int64_t n, siz
 			ctx->last_error = "seed " + std::to_string(k) + ": flank longer than 65535";
 			return BMH_E_RANGE;
 		}
-		if ((int64_t)x.l_query * smax > kScoreLimit) {
+		if (!ctx->wide_ext && (int64_t)x.l_query * smax > kScoreLimit) {
 			ctx->last_error = "seed " + std::to_string(k) + ": l_query*max(max(mat), a) exceeds the 16-bit score range";
+			return BMH_E_RANGE;
+		}
+		if (ctx->wide_ext && (int64_t)x.l_query * smax > kWideScoreLimit) {
+			ctx->last_error = "seed " + std::to_string(k) + ": l_query*max(max(mat), a) exceeds the wide extension's score range (2^24)";
 			return BMH_E_RANGE;
 		}
 		qm = std::max(qm, std::max(x.qbeg, (int)rq));
@@ -672,6 +717,9 @@ int bmh_seedext_submit(bmh_ctx_t *ctx, const bmh_seed_task_t *tasks, int64_t n)
 		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_down.p, ctx->d_res.p, rb, hipMemcpyDeviceToHost, ctx->stream));
 		BMH_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->h_down.p + ((rb + 63) & ~(size_t)63), seedext_counters(ctx), 16, hipMemcpyDeviceToHost,
 		                            ctx->stream));
+		if (ctx->wide_last) // (behind the four list lengths: what the wide bin received over the four rounds)
+			BMH_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->h_down.p + ((rb + 63) & ~(size_t)63) + 16, ctx->d_wide_stat, 8, hipMemcpyDeviceToHost,
+			                            ctx->stream));
 	}
 	ctx->seed_pending_n = n;
 	return BMH_OK;
@@ -690,6 +738,11 @@ int bmh_seedext_wait(bmh_ctx_t *ctx, bmh_seed_result_t *results)
 	const uint32_t *c = (const uint32_t *)((const uint8_t *)ctx->h_down.p + ((rb + 63) & ~(size_t)63));
 	ctx->sstats.seeds = n, ctx->sstats.left_tasks = c[0], ctx->sstats.left_retries = c[1], ctx->sstats.right_tasks = c[2],
 	ctx->sstats.right_retries = c[3];
+	if (ctx->wide_last) {
+		unsigned long long w;
+		memcpy(&w, c + 4, sizeof(w));
+		ctx->wide_total += (long long)w;
+	}
 	return rc;
 }
 

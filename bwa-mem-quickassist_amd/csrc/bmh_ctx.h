@@ -91,6 +91,13 @@ struct bmh_ctx {
 	DevBuf d_chain;                // device chainer (chain.hip): per-read bounds, arena, compact output
 	hipEvent_t ev_chain[2] = {};   // around its chain kernel (timing mode)
 	bmh_chain_stats_t cstats{-1, -1, -1, -1, -1, -1.f};
+	// int32 extension kernel (extend_wide.hip), opt-in: bmh_ctx_set_wide_extension
+	bool wide_ext = false;
+	bool wide_last = false;           // the last extension launch (a flat batch, or the four rounds of a fused call) ran with it on
+	unsigned long long *d_wide_stat = nullptr; // device: tasks the wide bin received since the launch began
+	double wide_ms_sum = 0.0;         // timing mode: the wide kernels' time over the same span
+	long long wide_total = 0;         // tasks the wide bin received over the host-buffer extension calls so far (preload shim log)
+	DevBuf d_wide_slab;               // per-block state slices of its HBM variant
 };
 
 namespace bmh {
@@ -166,6 +173,14 @@ int launch_seedext(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_seed_task_t *d
                    bmh_seed_result_t *d_res, int qmax);
 const uint32_t *seedext_counters(const bmh_ctx *ctx); // the four list lengths of the last launch_seedext, on the device
 inline long long ext_resident_waves(const bmh_ctx *ctx, int waves_per_simd) { return (long long)ctx->ncu * 4 * waves_per_simd; }
+// the LDS kernel holds 12 bytes per query column in 160 KiB: queries up to this many columns (launch_extend_lds)
+constexpr int kLdsQcap = 13632;
+// the wide kernel's LDS variant holds 13 bytes per column: up to this many; longer queries use its HBM slab (extend_wide.hip)
+constexpr int kWideLdsQcap = 12544;
+int launch_extend_wide(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
+                       const uint32_t *d_order, const uint32_t *d_count, int qmax, long long grid_cap = 0);
+// starts the span bmh_extend_wide_stats reports on: one flat extension batch, or the four rounds of a fused per-seed call
+int wide_stats_begin(bmh_ctx *ctx);
 int launch_extend_lds(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int qmax, long long grid_cap = 0);
 constexpr int kSortKeysHost = 2048; // == kSortKeys in extend_dispatch.hip
@@ -174,7 +189,8 @@ int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned
 int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                        bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, const uint32_t *d_count,
                        int rows_cap);
-constexpr int kExtBins = 6;        // length bins of the extension dispatcher
+constexpr int kExtBins = 6;        // length bins of the extension dispatcher (the 16-bit kernels)
+constexpr int kWideBin = 6;        // ... and the int32 kernel's bin, used only with bmh_ctx_set_wide_extension on
 constexpr int kSortBins = 8;       // bins the shared counting sort can tell apart (extension 6, global 6, Smith-Waterman 8)
 constexpr int kGrpTcapHost = 1024; // == kGrpTcap in extend_grp.hip
 int launch_extend_grp(bmh_ctx *ctx, int nv, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,

@@ -20,6 +20,7 @@ struct DevParams {
 };
 
 constexpr int kScoreLimit = 32000; // h0 + qlen*max_mat must stay below this (16-bit lanes)
+constexpr int kWideScoreLimit = 1 << 24; // ... and below this in the int32 kernel (extend_wide.hip: 64*e of its scan stays in int32)
 constexpr int kNegInf16 = -16384;  // scan identity for 16-bit-ranged values held in int32
 
 // ---- DPP controls (GFX9 encoding) ----

@@ -7,8 +7,11 @@
 //   bin 4: qlen <= 512   extend_lanex_kernel<4>   (16 tasks per wave; only with BMH_EXT_MODE=lanex4: with the few
 //                        such tasks a 150-300 bp run produces, one wave per task keeps more of the chip busy)
 //   bin 5: longer or qlen == 0                     extend_lds_kernel  (one wave per task)
+//   bin 6: only with bmh_ctx_set_wide_extension on: what the 16-bit kernels cannot take -- h0 + qlen*max(mat) > 32000 or
+//          qlen > kLdsQcap, or every task when the gap costs fail ext_gaps_too_large -> extend_wide_kernel (int32)
 // BMH_EXT_MODE=reg | grp | lds in the environment selects the one-task-per-wave register kernels, the
-// four-tasks-per-wave group kernels, or the LDS kernel for bins 0-2 instead (A/B runs, profiles/).
+// four-tasks-per-wave group kernels, or the LDS kernel for bins 0-2 instead (A/B runs, profiles/); BMH_EXT_MODE=wide sends every
+// task of a context with the switch on to bin 6 (A/B against the 16-bit kernels; no effect with the switch off).
 //
 // The bins are built ON THE DEVICE (a counting sort by bin and expected row count), and every
 // extension kernel reads its bin size from device memory, so a launch needs no
@@ -33,6 +36,12 @@ __device__ __forceinline__ int ext_bin_of(int qlen, int tlen, int mode)
 	return qlen <= 32 ? 0 : qlen <= 64 ? 1 : qlen <= 128 ? 2 : qlen <= 256 ? 3 : (qlen <= 512 && mode == 4) ? 4 : 5;
 }
 
+// bin 6: the task leaves the 16-bit kernels' domain (with the switch on; the gap costs are checked per batch on the host)
+__device__ __forceinline__ bool ext_goes_wide(int qlen, int h0, int max_mat)
+{
+	return (long long)max(h0, 0) + (long long)qlen * max_mat > kScoreLimit || qlen > kLdsQcap;
+}
+
 // sort key inside a bin: query-length bucket (major; lanes of a wave then share the unused leading columns,
 // which the lane kernels skip), h0 bucket, and expected row count (minor; lanes of a wave then finish together).
 // rows run at most to tlen, and the band leaves the query after ~qlen+w <= 2*qlen rows (ksw.c:418).
@@ -54,7 +63,7 @@ __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_t
                                                                  const uint32_t *__restrict__ order, long long n,
                                                                  uint32_t *__restrict__ hist,
                                                                  uint16_t *__restrict__ binkey, int mode,
-                                                                 const uint32_t *__restrict__ dn)
+                                                                 const uint32_t *__restrict__ dn, int wide, int max_mat)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeys];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kSortThreads) lh[t] = 0;
@@ -64,8 +73,10 @@ __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_t
 	for (long long k = lo + threadIdx.x; k < hi; k += kSortThreads) {
 		const uint32_t idx = order ? order[k] : (uint32_t)k;
 		const int qlen = tasks[idx].qlen, tlen = tasks[idx].tlen;
-		const int bin = ext_bin_of(qlen, tlen, mode);
-		const int bk = bin * kSortKeys + ext_sort_key(bin, qlen, tlen, tasks[idx].h0);
+		const int h0 = tasks[idx].h0;
+		// wide: 0 switch off, 1 per task, 2 every task
+		const int bin = wide && (wide == 2 || ext_goes_wide(qlen, h0, max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, mode);
+		const int bk = bin * kSortKeys + ext_sort_key(bin, qlen, tlen, h0);
 		binkey[k] = (uint16_t)bk;
 		atomicAdd(&lh[bk], 1u);
 	}
@@ -196,19 +207,30 @@ static int launch_extend_tiny(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext
 
 constexpr int64_t kForkMinTasks = 131072; // batches below this run their bins on one stream (see launch_extend)
 
+int wide_stats_begin(bmh_ctx *ctx)
+{
+	ctx->wide_last = ctx->wide_ext, ctx->wide_ms_sum = 0.0;
+	if (ctx->wide_ext) BMH_HIP(ctx, hipMemsetAsync(ctx->d_wide_stat, 0, sizeof(unsigned long long), ctx->stream));
+	return BMH_OK;
+}
+
 int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                   bmh_ext_result_t *d_res, const uint32_t *d_order, int qmax, const uint32_t *d_n, int kind)
 {
 	if (n <= 0) return BMH_OK;
-	if (ext_gaps_too_large(ctx->params)) {
+	if (kind < 0 || kind >= bmh_ctx::kHintKinds) kind = 0;
+	int rc;
+	if (kind == 0 && (rc = wide_stats_begin(ctx))) return rc; // (the fused per-seed call begins its span itself)
+	const bool gaps_wide = ext_gaps_too_large(ctx->params);
+	if (gaps_wide && !ctx->wide_ext) {
 		ctx->last_error = "the extension kernels need o_del+e_del, o_ins+e_ins <= 65535 and e_del, e_ins <= 16383";
 		return BMH_E_RANGE;
 	}
-	int rc;
-	if (kind < 0 || kind >= bmh_ctx::kHintKinds) kind = 0;
+	// bin 6 (switch on only): 1 the tasks outside the 16-bit domain, 2 every task (gap costs past 16 bits, or BMH_EXT_MODE=wide)
+	const int wide = !ctx->wide_ext ? 0 : gaps_wide || (ctx->ext_mode_forced && ctx->force_kernel == 5) ? 2 : 1;
 	hint_poll(ctx, kind);
 	const bmh_ctx::BinHint &hint = ctx->hint[kind];
-	if (d_n && hint.valid && !ctx->ext_mode_forced) {
+	if (d_n && hint.valid && !ctx->ext_mode_forced && !wide) { // (the tiny path's one LDS launch cannot take bin 6's tasks)
 		uint32_t tot = 0;
 		for (int b = 0; b < kExtBins; ++b) tot += hint.cnt[b];
 		if (tot <= kTinyList) return launch_extend_tiny(ctx, d_pool, d_tasks, n, d_res, d_order, qmax, d_n, kind);
@@ -226,7 +248,7 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 	// wants latency: one task per wave finishes in tens of microseconds (8 153 tasks: 0.76 -> 0.26 ms per call, 32 647:
 	// 0.84 -> 0.51 ms; level at 65 k).  With a device-side count (d_n) the decision uses the hinted size.
 	const int64_t n_eff = d_n ? std::min<int64_t>(n, est_total + (est_total >> 2) + 64) : n;
-	const int mode = ctx->ext_mode_forced ? ctx->force_kernel : n_eff <= ctx->small_batch ? 2 : 0;
+	const int mode = ctx->ext_mode_forced ? (ctx->force_kernel == 5 ? 0 : ctx->force_kernel) : n_eff <= ctx->small_batch ? 2 : 0;
 	const size_t N = (size_t)n;
 	uint32_t *counts, *lists;
 	if ((rc = sort_tasks_begin(ctx, n, &counts, &lists))) return rc;
@@ -236,7 +258,7 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 	if (cg > kSortBlocks) cg = kSortBlocks;
 	if (cg < 1) cg = 1;
 	hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)cg), dim3(kSortThreads), 0, ctx->stream, d_tasks, d_order, (long long)n,
-	                   hist, binkey, mode, d_n);
+	                   hist, binkey, mode, d_n, wide, ctx->dev.max_mat);
 	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg, d_n))) return rc;
 	if ((rc = hint_post(ctx, kind, counts))) return rc;
 	const bool tm = ctx->timing;
@@ -279,7 +301,7 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 		// correct); a bin the hint calls empty still gets a few hundred waves in case the batch differs from the last one
 		const int64_t eb = std::max<int64_t>(est[b], 16384);
 		rc = BMH_OK;
-		if (b < 5 && (mode == 1 || (qmax <= qlo && !(mode == 3 && b == 3)))) { // (mode 3 routes long targets of short queries to bin 3)
+		if (wide == 2 || (b < 5 && (mode == 1 || (qmax <= qlo && !(mode == 3 && b == 3))))) { // (mode 3 routes long targets of short queries to bin 3)
 			// provably empty bin
 		} else if (b <= 2) {
 			if ((mode == 0 || mode == 4) && b == 2 && ctx->ext_split96) {
@@ -306,8 +328,19 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 				}
 			} else rc = launch_extend_reg(ctx, 4, d_pool, d_tasks, n, d_res, lst, cnt, 0, est[b]);
 		} else if (b == 4 && mode == 4) rc = launch_extend_lanex(ctx, 4, d_pool, d_tasks, eb, d_res, lst, cnt, 0);
-		else if (b == 5) rc = launch_extend_lds(ctx, d_pool, d_tasks, n, d_res, lst, cnt, qmax, hint.valid ? std::max<int64_t>(est[5], 512) : (mode != 1 && qmax <= 256 ? 4096 : 0));
+		else if (b == 5) // (with the switch on, longer queries are bin 6's: the LDS kernel is sized for what it can hold)
+			rc = launch_extend_lds(ctx, d_pool, d_tasks, n, d_res, lst, cnt, wide ? std::min(qmax, kLdsQcap) : qmax,
+			                       hint.valid ? std::max<int64_t>(est[5], 512) : (mode != 1 && qmax <= 256 ? 4096 : 0));
 		if (!rc && tm) rc = (int)hipEventRecord(ctx->ev_bin_end[b], ctx->stream) ? BMH_E_HIP : BMH_OK;
+		if (rc) { ctx->stream = main_s; return rc; }
+	}
+	if (wide) { // bin 6 beside the long bins; its time goes to bmh_extend_wide_stats, not to the six bins' arrays
+		ctx->stream = side_s;
+		rc = BMH_OK;
+		if (tm) rc = (int)hipEventRecord(ctx->ev_bin[kWideBin], side_s) ? BMH_E_HIP : BMH_OK;
+		const int64_t ew = hint.valid ? std::min<int64_t>(n, (int64_t)hint.cnt[kWideBin] + (hint.cnt[kWideBin] >> 4) + 64) : n;
+		if (!rc) rc = launch_extend_wide(ctx, d_pool, d_tasks, n, d_res, lists + (size_t)kWideBin * N, counts + kWideBin, qmax, std::max<int64_t>(ew, 512));
+		if (!rc && tm) rc = (int)hipEventRecord(ctx->ev_bin_end[kWideBin], side_s) ? BMH_E_HIP : BMH_OK;
 		if (rc) { ctx->stream = main_s; return rc; }
 	}
 	ctx->stream = main_s;
@@ -328,6 +361,11 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 		for (int b = 0; b < kExtBins; ++b) {
 			float ms = 0.f;
 			if (hipEventElapsedTime(&ms, ctx->ev_bin[b], ctx->ev_bin_end[b]) == hipSuccess && ms > 0.f) ctx->ext_bin_ms_sum[b] += ms;
+			else (void)hipGetLastError();
+		}
+		if (wide) {
+			float ms = 0.f;
+			if (hipEventElapsedTime(&ms, ctx->ev_bin[kWideBin], ctx->ev_bin_end[kWideBin]) == hipSuccess && ms > 0.f) ctx->wide_ms_sum += ms;
 			else (void)hipGetLastError();
 		}
 		++ctx->ext_bin_launches;

@@ -42,6 +42,28 @@ static int pool_device(int nth)
 /* Workspaces of a context that will see the shim's batches -- up to 64 k reads of phase 1 (reads, windows, SMEM tables
  * coming back), a slice of a chunk in phase 2 -- sized once, so that no batch in the middle of a run has to grow them
  * ($BMH_RESERVE_MB scales the figures; 0 turns the reservation off). */
+int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx); /* internal hook of api.hip */
+
+int bmh_pool_wide(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_WIDE_EXT");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+
+long long bmh_pool_wide_tasks(void)
+{
+	long long t = 0;
+	int i;
+	pthread_mutex_lock(&g_mu);
+	for (i = 0; i < g_n; ++i) t += g_slots[i].ctx ? (long long)bmh_ctx_wide_tasks_(g_slots[i].ctx) : 0;
+	pthread_mutex_unlock(&g_mu);
+	return t;
+}
+
 static void pool_reserve(bmh_ctx_t *ctx)
 {
 	const char *e = getenv("BMH_RESERVE_MB");
@@ -79,6 +101,7 @@ bmh_ctx_t *bmh_pool_get(const bmh_params_t *p)
 	pthread_mutex_unlock(&g_mu);
 	if (!s->ctx) {
 		if ((rc = bmh_ctx_create(&s->ctx, pool_device((int)(s - g_slots))))) bmh_tls_die("cannot create a GPU context", rc);
+		if (bmh_pool_wide() && (rc = bmh_ctx_set_wide_extension(s->ctx, 1))) bmh_tls_die("cannot turn on the wide extension", rc);
 		pool_reserve(s->ctx);
 	}
 	if (!s->have || memcmp(&s->params, p, sizeof(*p)) != 0) {
@@ -110,6 +133,7 @@ void bmh_pool_prewarm(int n)
 		bmh_ctx_t *ctx = 0;
 		slot_t *s = 0;
 		if (bmh_ctx_create(&ctx, pool_device(k))) return; /* no GPU: the first real call will say so loudly */
+		if (bmh_pool_wide() && bmh_ctx_set_wide_extension(ctx, 1)) { bmh_ctx_destroy(ctx); return; }
 		pool_reserve(ctx);
 		pthread_mutex_lock(&g_mu);
 		if (g_n < BMH_POOL_MAX) s = &g_slots[g_n++], s->ctx = ctx, s->have = 0, s->busy = 0;

@@ -104,7 +104,15 @@ typedef struct bmh_glb_result {
 /* Supported range (checked on the host, BMH_E_RANGE otherwise):
  *   extend: 0 <= qlen,tlen <= 65535; scores must fit int16 lanes:
  *           h0 + qlen*max(mat) <= 32000; o_ins >= 0 (SURVEY.md §7 hard part 1);
- *           o_del+e_del, o_ins+e_ins <= 65535, e_del, e_ins <= 16383 (also for bmh_seedext_batch).
+ *           o_del+e_del, o_ins+e_ins <= 65535, e_del, e_ins <= 16383 (also for bmh_seedext_batch);
+ *           queries up to 13 632 columns (the LDS kernel's 160 KiB).
+ *   extend with bmh_ctx_set_wide_extension(ctx, 1): what the range above refuses goes to an int32 kernel instead:
+ *           h0 + qlen*max(mat) <= 2^24 (bmh_seedext_batch: l_query*max(max(mat), a) <= 2^24), any query up to 65535
+ *           (with *_device calls: up to bmh_ctx_set_qcap), any gap costs >= the minimums of bmh_ctx_set_params.  The
+ *           fused record keeps its flank bound of 65535 and 2*w <= 32767.  Tasks inside the range above keep their kernels.
+ *           Not covered: mate rescue (bmh_sw_batch / bmh_matesw_batch, qlen*max(mat) < 32000) and the 65535 limits of
+ *           bmh_global_batch and bmh_reg2cigar_batch, so paired-end long reads can still stop there; and the global wave kernel
+ *           holds 16 bytes per query column in LDS, so regions past 10 176 query columns are refused in phase 2.
  *   global: qlen,tlen <= 65535. */
 
 typedef struct bmh_ctx bmh_ctx_t;
@@ -125,6 +133,9 @@ int bmh_ctx_set_stream(bmh_ctx_t *ctx, void *hip_stream);
  * BMH_F_TPAC tasks and lets the L3 drivers skip the host-side bns_get_seq.  hg38: 0.78 GB, uploaded once. */
 int bmh_ctx_set_pac(bmh_ctx_t *ctx, const uint8_t *pac, int64_t l_pac);
 int bmh_ctx_sync(bmh_ctx_t *ctx); /* waits for the stream; returns a pending BMH_E_RANGE/CIGAR_CAP of a *_device call */
+/* Opt-in int32 extension kernel (see "Supported range"): with enable != 0, extension and fused per-seed batches accept scores up
+ * to 2^24, queries up to 65535 and gap costs past 16 bits.  Off by default; the default context refuses them as before. */
+int bmh_ctx_set_wide_extension(bmh_ctx_t *ctx, int enable);
 /* Capacity hint for the *_device entry points, which cannot look at the tasks on the host:
  * the longest query the launch must handle (default 512).  Longer tasks fail with BMH_E_RANGE. */
 int bmh_ctx_set_qcap(bmh_ctx_t *ctx, int max_qlen);
@@ -239,6 +250,9 @@ int bmh_last_extend_bin_ms(bmh_ctx_t *ctx, float ms[6]);
 /* With timing on, every dispatcher launch (a fused per-seed call makes four) waits for its kernels and adds their per-bin durations
  * to running sums: ms[b] = the sum for bin b, *launches (nullable) = dispatcher launches counted; reset != 0 clears the sums. */
 int bmh_extend_bin_ms_sum(bmh_ctx_t *ctx, double ms[6], long long *launches, int reset);
+/* What the last extension launch (a flat batch, or the four rounds of a fused per-seed call) sent to the int32 kernel:
+ * *tasks = its tasks (0 with the wide extension off), *ms = its kernel time (-1 when timing is off).  Waits for the stream. */
+int bmh_extend_wide_stats(const bmh_ctx_t *ctx, int64_t *tasks, float *ms);
 /* Per-kernel duration of the last global-alignment launch: the 64-slot lane kernel (w <= 31), the 128-slot one (w <= 63),
  * the one-wave-per-task kernel (everything else).  -1 when timing was off. */
 int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3]);
