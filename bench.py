@@ -19,7 +19,13 @@ reference pipeline; per-read DP work does not depend on the genome.  A STEP is o
 seeding, chaining, SAM text (host stages either side of the path); their cost shows in `cpu_baseline_pipeline`, which
 times the reference's own `bwa mem` (all host cores) and the same binary with this library preloaded, SAM-identical.
 
-`--workload se1m` runs round 1's line (tools/bench_se1m.py: one flat ksw_extend2 batch over configs[1]-shaped tasks).
+A plain run does what the headline needs and nothing more: it generates and uploads the tasks, warms up, times the steps,
+writes --dump-outputs and prints the line.  `--full` adds everything around it: the whole-pipeline baseline, the host-fed
+steps (`value_streamed`), the instrumented per-kernel pass with the roofline, the bit-exact check of chunk 0 against the
+oracle (a mismatch sets `value` to 0) and the oracle-port CPU baseline.
+
+`--workload se1m` runs round 1's line (tools/bench_se1m.py: one flat ksw_extend2 batch over configs[1]-shaped tasks), whole
+with or without `--full`.
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -410,16 +416,19 @@ def main():
     ap.add_argument("--streams", type=int, default=3, choices=[1, 3],
                     help="3: one context and HIP stream per stage, so chunk k's global alignments run beside chunk k+1's extensions "
                          "(measured +10 %% reads/s); 1: the stages back to back on one stream (every kernel alone on the chip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the whole-pipeline and oracle-port CPU baselines, the host-fed steps, "
+                         "the instrumented per-kernel pass and roofline, the oracle check of chunk 0; the options below refine these")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the oracle-port CPU baseline (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline-baseline", action="store_true")
     ap.add_argument("--pipeline-reads", type=int, default=6_400_000, help="reads of the whole-pipeline baseline (six chunks of bwa's at 16 threads)")
     ap.add_argument("--pipeline-batch", type=int, default=32768, help="the fork's -b: reads per phase-1 batch")
     ap.add_argument("--pipeline-genome", type=int, default=4_600_000)
-    ap.add_argument("--feed", default="both", choices=["resident", "host", "both"],
-                    help="resident: inputs in HBM when the timed region starts (`value`, the contract's definition); host: also time the same steps "
-                         "with every chunk uploaded from pinned host memory one chunk ahead of compute and every result downloaded "
-                         "(`value_streamed`); both (default): the two timed regions one after the other")
+    ap.add_argument("--feed", default=None, choices=["resident", "host", "both"],
+                    help="resident: inputs in HBM when the timed region starts (`value`, the contract's definition; the only one without --full); "
+                         "host: also time the same steps with every chunk uploaded from pinned host memory one chunk ahead of compute and every "
+                         "result downloaded (`value_streamed`); both (the default with --full): the two timed regions one after the other")
     ap.add_argument("--feed-global-windows", action="store_true",
                     help="host-fed steps: ship the global tasks' target windows as well (the CIGAR driver before the region record); default: they stay "
                          "resident like the seeds' windows")
@@ -439,6 +448,10 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload != "pe10m":
         ap.error("--dump-outputs is implemented for the pe10m workload")
+    if args.feed is None:
+        args.feed = "both" if args.full else "resident"
+    elif args.feed != "resident" and not args.full and args.workload == "pe10m":
+        ap.error(f"--feed {args.feed}: the host-fed steps are part of --full")
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])  # before anything here has touched a GPU
     if args.workload == "se1m":
@@ -456,7 +469,7 @@ def main():
 
     # ---- whole-pipeline CPU baseline FIRST: it starts child processes, and this process has not touched the GPU yet
     pipe = None
-    if world == 1 and rank == 0 and not args.no_pipeline_baseline and args.pipeline_reads > 0:
+    if args.full and world == 1 and rank == 0 and not args.no_pipeline_baseline and args.pipeline_reads > 0:
         try:
             pipe = pipeline_baseline(args.pipeline_reads, args.pipeline_genome, ncores, batch=args.pipeline_batch)
             pipe["cores_note"] = cores_note
@@ -474,49 +487,50 @@ def main():
     if world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world} (start it as `python bench.py --gpus N`, which launches its own ranks, "
                  f"or under torch.distributed.run with --nproc-per-node N)")
-    dev_index = local_rank
-    if args.oversubscribe:
-        dev_index = local_rank % max(1, torch.cuda.device_count())  # device_count() does not initialise the GPU on this image
-    if use_dist:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29511")
-        if args.oversubscribe:
-            dist.init_process_group("gloo")
-        else:
-            dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
-    torch.cuda.set_device(dev_index)
-    dev = torch.device("cuda", dev_index)
-    rdev = torch.device("cpu") if args.oversubscribe else dev  # where the report's reductions live
     pkg = load_package()
     tg = importlib.import_module("bwa_mem_quickassist_amd.taskgen")
     sh = importlib.import_module("bwa_mem_quickassist_amd.shard")
     params = kswlib.make_params()  # bwa mem defaults, reference bwamem.c:45-75
 
-    # ---- this rank's shard (weak scaling: same size, distinct seeds), generated chunk by chunk on host threads
+    # ---- this rank's shard (weak scaling: same size, distinct seeds), generated on host threads: every chunk's seed records,
+    # every chunk's global tasks and every rescue batch is a job of its own (the generator runs in C, outside the GIL), and the
+    # GPU side starts up while they run
     n_reads_step = 2 * args.pairs
     n_chunks = max(1, (n_reads_step + args.chunk_reads - 1) // args.chunk_reads)
     sizes = [n_reads_step * (k + 1) // n_chunks - n_reads_step * k // n_chunks for k in range(n_chunks)]
-    t0 = time.time()
-
-    def gen(k):
-        s0 = sh.shard_seed(7, rank) * 131 + 17 * k
-        nr = sizes[k]
-        pool, seeds = tg.generate_seeds(params, nr, args.shape, seed=s0)
-        gpool, gtasks, gwords = tg.generate_global(max(1, int(round(nr * args.global_per_read))), args.shape, seed=s0 + 5)
-        return pool, seeds, gpool, gtasks, gwords
-
     n_sw_step = max(1, int(round(args.pairs * args.rescue_rate)))
     n_swb = max(1, (n_sw_step + args.rescue_batch - 1) // args.rescue_batch)
     sw_sizes = [n_sw_step * (k + 1) // n_swb - n_sw_step * k // n_swb for k in range(n_swb)]
+    t0 = time.time()
 
-    def gen_sw(k):
-        return tg.generate_sw(params, sw_sizes[k], args.shape, seed=sh.shard_seed(7, rank) * 131 + 9 + 1000 * k)
+    def chunk_seed(k):
+        return sh.shard_seed(7, rank) * 131 + 17 * k
 
-    workers = max(1, min(16, ncores, n_chunks))
+    workers = max(1, min(16, ncores, 2 * n_chunks + n_swb))
     note(f"generating {n_reads_step} reads' worth of tasks in {n_chunks} chunks on {workers} threads")
     with ThreadPoolExecutor(max_workers=workers) as ex:
-        host = list(ex.map(gen, range(n_chunks)))
-        host_sw = list(ex.map(gen_sw, range(n_swb)))
+        seed_jobs = [ex.submit(tg.generate_seeds, params, sizes[k], args.shape, seed=chunk_seed(k)) for k in range(n_chunks)]
+        glb_jobs = [ex.submit(tg.generate_global, max(1, int(round(sizes[k] * args.global_per_read))), args.shape, seed=chunk_seed(k) + 5)
+                    for k in range(n_chunks)]
+        sw_jobs = [ex.submit(tg.generate_sw, params, sw_sizes[k], args.shape, seed=sh.shard_seed(7, rank) * 131 + 9 + 1000 * k) for k in range(n_swb)]
+
+        dev_index = local_rank
+        if args.oversubscribe:
+            dev_index = local_rank % max(1, torch.cuda.device_count())  # device_count() does not initialise the GPU
+        if use_dist:
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            os.environ.setdefault("MASTER_PORT", "29511")
+            if args.oversubscribe:
+                dist.init_process_group("gloo")
+            else:
+                dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
+        torch.cuda.set_device(dev_index)
+        torch.cuda.init()
+        dev = torch.device("cuda", dev_index)
+        rdev = torch.device("cpu") if args.oversubscribe else dev  # where the report's reductions live
+
+        host = [s.result() + g.result() for s, g in zip(seed_jobs, glb_jobs)]  # (pool, seeds, gpool, gtasks, gwords) per chunk
+        host_sw = [j.result() for j in sw_jobs]
     gen_s = time.time() - t0
 
     note(f"generated in {gen_s:.1f} s; uploading")
@@ -638,40 +652,43 @@ def main():
                             "(16 words of room per task) / rescue results downloaded to pinned host memory (third stream), all inside the timed "
                             "region; the seed records' reference windows are resident in HBM, as the reference is in the preload shim"}
 
-    note(f"timed: {rank_ms:.1f} ms per step" + (f", host-fed {streamed['rank_ms_per_step']:.1f} ms" if streamed else "") + "; instrumented pass")
-    # ---- one more, instrumented pass (untimed): HIP events on the launch streams around every stage and every kernel
-    # of the dominant stage, chunk by chunk
-    stage_ms = {"seed_extension": 0.0, "global_alignment": 0.0, "mate_rescue_sw": 0.0}
-    round_ms = np.zeros(4)
-    gbin_ms = np.zeros(3)
-    for c in ctxs:
-        c.set_kernel_timing(True)
-    cx_ext.extend_bin_ms_sum(reset=True)
-    evs = []
-    for c in chunks:
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        e[0].record(streams[0]); cx_ext.seedext_batch_device(c["pool"].data_ptr(), c["seeds"].data_ptr(), c["n"], c["sres"].data_ptr()); e[1].record(streams[0])
-        sg = streams[1 % len(streams)]
-        e[2].record(sg); cx_glb.global_batch_device(c["gpool"].data_ptr(), c["gtasks"].data_ptr(), c["ng"], c["gres"].data_ptr(), d_cig.data_ptr()); e[3].record(sg)
-        sync_all()
-        round_ms += np.array(cx_ext.last_seedext_round_ms())
-        gbin_ms += np.maximum(np.array(cx_glb.last_global_bin_ms()), 0.0)
-        evs.append(e)
-    for e in evs:
-        stage_ms["seed_extension"] += e[0].elapsed_time(e[1])
-        stage_ms["global_alignment"] += e[2].elapsed_time(e[3])
-    ss = streams[2 % len(streams)]
-    for b in swb:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(ss); run_sw(b); e1.record(ss)
-        sync_all()
-        stage_ms["mate_rescue_sw"] += e0.elapsed_time(e1)
-    ext_bin_ms, ext_bin_launches = cx_ext.extend_bin_ms_sum(reset=True)  # per extension kernel, summed over the fused rounds of all chunks
-    for c in ctxs:
-        c.set_kernel_timing(False)
+    note(f"timed: {rank_ms:.1f} ms per step" + (f", host-fed {streamed['rank_ms_per_step']:.1f} ms" if streamed else "") + ("; instrumented pass" if args.full else ""))
+    if args.full:
+        # ---- one more, instrumented pass (untimed): HIP events on the launch streams around every stage and every kernel
+        # of the dominant stage, chunk by chunk
+        stage_ms = {"seed_extension": 0.0, "global_alignment": 0.0, "mate_rescue_sw": 0.0}
+        round_ms = np.zeros(4)
+        gbin_ms = np.zeros(3)
+        for c in ctxs:
+            c.set_kernel_timing(True)
+        cx_ext.extend_bin_ms_sum(reset=True)
+        evs = []
+        for c in chunks:
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record(streams[0]); cx_ext.seedext_batch_device(c["pool"].data_ptr(), c["seeds"].data_ptr(), c["n"], c["sres"].data_ptr()); e[1].record(streams[0])
+            sg = streams[1 % len(streams)]
+            e[2].record(sg); cx_glb.global_batch_device(c["gpool"].data_ptr(), c["gtasks"].data_ptr(), c["ng"], c["gres"].data_ptr(), d_cig.data_ptr()); e[3].record(sg)
+            sync_all()
+            round_ms += np.array(cx_ext.last_seedext_round_ms())
+            gbin_ms += np.maximum(np.array(cx_glb.last_global_bin_ms()), 0.0)
+            evs.append(e)
+        for e in evs:
+            stage_ms["seed_extension"] += e[0].elapsed_time(e[1])
+            stage_ms["global_alignment"] += e[2].elapsed_time(e[3])
+        ss = streams[2 % len(streams)]
+        for b in swb:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ss); run_sw(b); e1.record(ss)
+            sync_all()
+            stage_ms["mate_rescue_sw"] += e0.elapsed_time(e1)
+        ext_bin_ms, ext_bin_launches = cx_ext.extend_bin_ms_sum(reset=True)  # per extension kernel, summed over the fused rounds of all chunks
+        for c in ctxs:
+            c.set_kernel_timing(False)
 
     out = None
-    if rank == 0:
+    full = {}  # what --full adds to the line
+    value_ok = True  # --full: the oracle check of chunk 0 passed
+    if rank == 0 and args.full:
         note("parity check and CPU baseline")
         # ---- parity on chunk 0 (its results are still on the device; CIGARs: run its global batch once more) + CPU baseline
         c0, h0 = chunks[0], host[0]
@@ -754,8 +771,6 @@ def main():
                    "cores_note": cores_note,
                    "stage_seconds": {"seed_extension": t_e, "global_alignment": t_g, "mate_rescue_sw": t_s}}
 
-        ms_per_step = elapsed / args.steps * 1e3
-        value = reads_all * args.steps / elapsed
         # ---- kernels of the step (instrumented pass): the fused extension's four rounds, the three global kernels, the SW stage
         ql, tl, gw = (np.concatenate([h[3][f].astype(np.int64) for h in host]) for f in ("qlen", "tlen", "w"))
         worst = int(params["o_del"]) + int(params["o_ins"]) + max(int(params["e_del"]), int(params["e_ins"])) * (ql + tl) + \
@@ -835,28 +850,11 @@ def main():
                                 "in a stream that is not pure vector code (profiles/r03_valu_pairing.md, DESIGN.md 4.2)"}
             elif mk:
                 valu = {"skipped": f"profiles/r03_valu_mix.json is from kernel sources {mj.get('csrc_sha')}, this tree is {tree_sha} (python tools/make_valu_mix_profile.py)"}
-        metric = "aligned reads/sec (150 bp PE vs hg38) at 1/2/4/8 MI355X; SAM bit-exact vs CPU"
-        bpath = os.path.join(ROOT, "BASELINE.json")
-        if os.path.exists(bpath):
-            metric = json.load(open(bpath)).get("metric", metric)
         step_cells = cells_per_seed * n_seeded
-        out = {
-            "metric": metric,
-            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "int16", "data": "synthetic",
-            "config": {"workload": f"pe10m -- BASELINE.json configs[2]: {args.pairs} x 2 x {args.shape} read pairs per GPU per step through the whole DP path "
-                                   f"(fused seed extension with the right extension started from the device's left score, ksw_global2 + traceback, "
-                                   f"mate-rescue ksw_align2), task generator in place of the hg38 index (SURVEY.md §8d), streamed in {n_chunks} chunks, "
-                                   f"inputs resident in HBM; seeding, chaining and SAM text are host stages outside the step (see cpu_baseline_pipeline)",
-                       "pairs_per_gpu": args.pairs, "reads_per_gpu": n_reads_step, "chunks": n_chunks, "seeded_reads_per_gpu": n_seeded,
-                       "ksw_extend2_calls_per_gpu": int(round(calls_per_seed * n_seeded)), "global_tasks_per_gpu": n_glb, "rescue_tasks_per_gpu": n_sw,
-                       "rescue_batches": n_swb, "mean_global_w": float(gw.mean()), "streams": args.streams,
-                       "parallelism": f"static shard x{world}, one process per GPU, no collective on the data path"},
-            "tasks_per_s": tasks_all * args.steps / elapsed,
-            "value_streamed": streamed["value_streamed"] if streamed else None,
+        value_ok = parity_ok
+        full = {
+            "value_streamed": (streamed["value_streamed"] if parity_ok and ok_feed else 0.0) if streamed else None,
             "streamed": streamed,
-            "per_rank_ms_per_step": per_rank_ms,
             "parity": ("bit-exact vs oracle: fused seed extensions, global alignments (scores, n_cigar, sampled CIGARs), mate-rescue SW"
                        if parity_ok else f"MISMATCH vs oracle (ext {ok_ext}, global {ok_glb}, sw {ok_sw})"),
             "parity_streamed": (None if feed is None else "host-fed results identical to the resident ones (finished regions, global scores, every 11th CIGAR, rescue results)"
@@ -874,18 +872,46 @@ def main():
                                  "events on the launch stream); integer DP is VALU-issue bound, GCUPS / tasks/s are the honest figures"},
             "cpu_baseline": cpu,
             "cpu_baseline_pipeline": pipe,
+            "value_end_to_end": (pipe or {}).get("dut_value") if (pipe or {}).get("sam_identical") else None,
+        }
+
+    if rank == 0:
+        ms_per_step = elapsed / args.steps * 1e3
+        value = reads_all * args.steps / elapsed
+        metric = "aligned reads/sec (150 bp PE vs hg38) at 1/2/4/8 MI355X; SAM bit-exact vs CPU"
+        bpath = os.path.join(ROOT, "BASELINE.json")
+        if os.path.exists(bpath):
+            metric = json.load(open(bpath)).get("metric", metric)
+        config = {"workload": f"pe10m -- BASELINE.json configs[2]: {args.pairs} x 2 x {args.shape} read pairs per GPU per step through the whole DP path "
+                              f"(fused seed extension with the right extension started from the device's left score, ksw_global2 + traceback, "
+                              f"mate-rescue ksw_align2), task generator in place of the hg38 index (SURVEY.md §8d), streamed in {n_chunks} chunks, "
+                              f"inputs resident in HBM; seeding, chaining and SAM text are host stages outside the step (see cpu_baseline_pipeline)",
+                  "pairs_per_gpu": args.pairs, "reads_per_gpu": n_reads_step, "chunks": n_chunks, "seeded_reads_per_gpu": n_seeded}
+        if args.full:  # counted by the oracle's replay of chunk 0
+            config["ksw_extend2_calls_per_gpu"] = int(round(calls_per_seed * n_seeded))
+        config.update({"global_tasks_per_gpu": n_glb, "rescue_tasks_per_gpu": n_sw, "rescue_batches": n_swb,
+                       "mean_global_w": float(np.concatenate([h[3]["w"].astype(np.int64) for h in host]).mean()), "streams": args.streams,
+                       "parallelism": f"static shard x{world}, one process per GPU, no collective on the data path"})
+        out = {
+            "metric": metric,
+            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "int16", "data": "synthetic",
+            "config": config,
+            "tasks_per_s": tasks_all * args.steps / elapsed,
+            "per_rank_ms_per_step": per_rank_ms,
             "setup": {"taskgen_s": gen_s, "upload_s": upload_s, "host_threads_for_generation": workers},
             "dumped_outputs": dumped,
+            "full": bool(args.full),
         }
         # what `value` covers, so that it cannot be read as an end-to-end figure: the DP path only, on generator tasks
-        out["value_scope"] = ("DP-path reads/s (seed extension + global alignment + mate rescue) on synthetic generator tasks, inputs resident in HBM; "
-                              "value_streamed = the same steps fed over PCIe from pinned host memory with results downloaded; "
-                              "value_end_to_end = whole `bwa mem` (seeding, chaining, DP, SAM text) through the preload shim, SAM identical to the reference")
-        out["value_end_to_end"] = (pipe or {}).get("dut_value") if (pipe or {}).get("sam_identical") else None
-        if not parity_ok:
+        out["value_scope"] = ("DP-path reads/s (seed extension + global alignment + mate rescue) on synthetic generator tasks, inputs resident in HBM" +
+                              ("; value_streamed = the same steps fed over PCIe from pinned host memory with results downloaded; "
+                               "value_end_to_end = whole `bwa mem` (seeding, chaining, DP, SAM text) through the preload shim, SAM identical to the reference"
+                               if args.full else ""))
+        out.update(full)
+        if not value_ok:
             out["value"] = 0.0  # a fast kernel with different results is not done
-        if streamed and not (parity_ok and ok_feed):
-            out["value_streamed"] = 0.0
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,4 +1,4 @@
-"""The driver's contract for bench.py: ONE JSON line with the agreed keys, the metric string of BASELINE.json, the roofline
+"""The driver's contract for bench.py: ONE JSON line with the agreed keys, the metric string of BASELINE.json, and with --full the roofline
 and cpu_baseline objects, bit-exact parity.  Run small here; the driver runs the default sizes (10 M pairs per step)."""
 import json
 import os
@@ -41,7 +41,7 @@ def _contract(d, steps, warmup):
 
 def test_bench_prints_one_contract_line_on_the_metric_config():
     """configs[2] shape, whole DP path in the step (fused seed extension -> global -> rescue), scaled down."""
-    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "60000", "--chunk-reads", "40000", "--cpu-seconds", "1",
+    d = _run(["--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "60000", "--chunk-reads", "40000", "--cpu-seconds", "1",
               "--pipeline-reads", "20000", "--pipeline-genome", "500000"])
     _contract(d, 3, 1)
     assert "configs[2]" in d["config"]["workload"] and d["config"]["chunks"] == 3
@@ -77,7 +77,7 @@ def test_bench_two_ranks_on_one_device_and_the_host_fed_step():
     and the host-fed steps (uploads one chunk ahead on a copy stream, results downloaded, inside the timed region) report `value_streamed`
     with the same results as the resident steps (the line's parity covers host-fed == resident)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "2", "--warmup", "1", "--pairs", "60000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--oversubscribe", "--steps", "2", "--warmup", "1", "--pairs", "60000",
                         "--chunk-reads", "40000", "--no-cpu-baseline", "--no-pipeline-baseline"], capture_output=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -94,11 +94,12 @@ def test_bench_two_ranks_on_one_device_and_the_host_fed_step():
 
 
 def test_bench_dumps_the_last_timed_step(tmp_path):
-    """--dump-outputs DIR: float arrays of what the timed path computed, inside 64 MB, the same from one run to the next."""
+    """--dump-outputs DIR: float arrays of what the timed path computed, inside 64 MB, the same from one run to the next -- and the same
+    from a plain run as from a --full one, whose oracle check covers them."""
     import numpy as np
     base = ["--gpus", "1", "--warmup", "1", "--pairs", "60000", "--chunk-reads", "40000", "--feed", "resident", "--no-cpu-baseline",
             "--no-pipeline-baseline"]
-    d1 = _run(base + ["--steps", "2", "--dump-outputs", str(tmp_path / "a")])
+    d1 = _run(base + ["--full", "--steps", "2", "--dump-outputs", str(tmp_path / "a")])
     d2 = _run(base + ["--steps", "3", "--dump-outputs", str(tmp_path / "b")])
     assert d1["steps"] == 2 and d2["steps"] == 3 and d1["ms_per_step"] > 0 and d1["parity"].startswith("bit-exact")
     files = sorted(os.listdir(tmp_path / "a"))
@@ -109,3 +110,24 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     for f in files:
         a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
         assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full a run sets up, warms up, times the steps, dumps and prints: the headline keys with their meaning, none of the
+    baselines, host-fed steps, per-kernel figures or oracle check, and little time outside the steps."""
+    import time
+    t0 = time.perf_counter()
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--pairs", "60000", "--chunk-reads", "40000", "--dump-outputs", str(tmp_path / "d")])
+    wall = time.perf_counter() - t0
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "per_rank_ms_per_step", "dumped_outputs"):
+        assert k in d, k
+    if os.path.exists(os.path.join(ROOT, "BASELINE.json")):
+        assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert d["unit"] == "reads/s" and d["higher_is_better"] is True and d["dtype"] == "int16" and d["steps"] == 3 and d["warmup"] == 2
+    assert d["full"] is False and d["config"]["chunks"] == 3 and d["dumped_outputs"]["files"] == sorted(os.listdir(tmp_path / "d"))
+    per_step = d["config"]["reads_per_gpu"] / (d["ms_per_step"] * 1e-3)
+    assert d["value"] > 0 and abs(d["value"] - per_step) <= 1e-6 * per_step
+    for k in ("cpu_baseline", "cpu_baseline_pipeline", "streamed", "value_streamed", "roofline", "stages_ms_per_step", "parity", "value_end_to_end"):
+        assert k not in d, k
+    assert wall - (3 + 2) * d["ms_per_step"] * 1e-3 < 30.0

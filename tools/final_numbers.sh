@@ -2,13 +2,13 @@
 # The round's measurement set (run on the GPU box via gpurun): the default bench line (resident + host-fed steps, both CPU baselines),
 # one stream, the two other read shapes, round 1's flat batch, and the two-rank rehearsal on one device.  Files under gpurun_out/.
 O=gpurun_out
-python bench.py > $O/r03_final_default.json 2> $O/r03_final_default.err
+python bench.py --full > $O/r03_final_default.json 2> $O/r03_final_default.err
 tail -2 $O/r03_final_default.err
-python bench.py --streams 1 --no-pipeline-baseline --no-cpu-baseline --feed resident > $O/r03_final_s1.json 2>/dev/null
-python bench.py --shape mixed100-300 --no-pipeline-baseline --no-cpu-baseline --feed resident > $O/r03_final_mixed.json 2>/dev/null
-python bench.py --shape 250bp --no-pipeline-baseline --no-cpu-baseline --feed resident > $O/r03_final_250.json 2>/dev/null
+python bench.py --full --streams 1 --no-pipeline-baseline --no-cpu-baseline --feed resident > $O/r03_final_s1.json 2>/dev/null
+python bench.py --full --shape mixed100-300 --no-pipeline-baseline --no-cpu-baseline --feed resident > $O/r03_final_mixed.json 2>/dev/null
+python bench.py --full --shape 250bp --no-pipeline-baseline --no-cpu-baseline --feed resident > $O/r03_final_250.json 2>/dev/null
 python bench.py --workload se1m --no-cpu-baseline > $O/r03_final_se1m.json 2>/dev/null
-python bench.py --gpus 2 --oversubscribe --no-pipeline-baseline --no-cpu-baseline --pairs 4000000 > $O/r03_final_2ranks.json 2>/dev/null
+python bench.py --full --gpus 2 --oversubscribe --no-pipeline-baseline --no-cpu-baseline --pairs 4000000 > $O/r03_final_2ranks.json 2>/dev/null
 python - <<PY
 import json
 for f in ("default","s1","mixed","250","se1m","2ranks"):
