@@ -603,14 +603,7 @@ class Context:
 
 def extend_batch_sharded(ctxs, pool, tasks):
     """Static contiguous shard of one host batch over several contexts (one per GPU)."""
-    pool = np.ascontiguousarray(pool, dtype=np.uint8)
-    tasks = np.ascontiguousarray(tasks, dtype=EXT_TASK)
-    res = np.zeros(len(tasks), dtype=EXT_RES)
-    arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
-    rc = lib().bmh_extend_batch_sharded(arr, len(ctxs), _ptr(pool), pool.nbytes, _ptr(tasks), len(tasks), _ptr(res))
-    if rc:
-        raise BmhError(rc, lib().bmh_strerror(rc).decode())
-    return res
+    return _sharded("bmh_extend_batch_sharded", ctxs, pool, tasks, EXT_TASK, EXT_RES)
 
 
 def _sharded(fn, ctxs, pool, tasks, tdtype, rdtype, *more):

@@ -64,11 +64,12 @@ static void free_buf(DevBuf &b)
 	b.p = nullptr, b.cap = 0;
 }
 
-// read-and-clear the device error flag; the stream must be idle
+// wait for the context's stream, then read and clear the device error flag
 static int fetch_err(bmh_ctx *ctx)
 {
-	BMH_HIP(ctx, hipMemcpyAsync(ctx->h_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	const hipError_t c = hipMemcpyAsync(ctx->h_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream)); // (also when the copy could not be enqueued)
+	if (c != hipSuccess) return set_hip_error(ctx, c, "hipMemcpyAsync(error flag)");
 	int e = *ctx->h_err;
 	if (e != 0) {
 		BMH_HIP(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream));
@@ -80,10 +81,12 @@ static int fetch_err(bmh_ctx *ctx)
 
 // The callers' host buffers are pageable.  Up to kStageMax bytes per direction and call they travel through the
 // context's pinned staging buffers -- one memcpy on the host, then a DMA that does not depend on the runtime's own
-// (slow, process-wide serialised) path for pageable memory; larger transfers go the direct way.
+// (slow, process-wide serialised) path for pageable memory; larger transfers go the direct way, and so do all the
+// transfers of a Stager that stage() was not called for.
 constexpr size_t kStageMax = (size_t)64 << 20;
 struct Stager {
 	bmh_ctx *ctx;
+	bool wide; // an extension batch: end() adds what the int32 kernel received to ctx->wide_total
 	bool up = false, down = false;
 	size_t up_used = 0, down_used = 0;
 	struct Pending {
@@ -91,13 +94,13 @@ struct Stager {
 		size_t off, bytes;
 	} pend[4];
 	int n_pend = 0;
-	int begin(bmh_ctx *c, size_t up_bytes, size_t down_bytes)
+	explicit Stager(bmh_ctx *c = nullptr, bool count_wide = false) : ctx(c), wide(count_wide) {}
+	int stage(size_t up_bytes, size_t down_bytes)
 	{
-		ctx = c;
 		int rc;
 		up = up_bytes <= kStageMax, down = down_bytes <= kStageMax;
-		if (up && (rc = ensure_host(c, c->h_up, up_bytes + 256))) return rc;
-		if (down && (rc = ensure_host(c, c->h_down, down_bytes + 256))) return rc;
+		if (up && (rc = ensure_host(ctx, ctx->h_up, up_bytes + 256))) return rc;
+		if (down && (rc = ensure_host(ctx, ctx->h_down, down_bytes + 256))) return rc;
 		return BMH_OK;
 	}
 	int h2d(void *d_dst, const void *src, size_t bytes)
@@ -121,12 +124,60 @@ struct Stager {
 		BMH_HIP(ctx, hipMemcpyAsync(to, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
 		return BMH_OK;
 	}
-	void finish() // after the stream has been synchronised
+	// The one way out of a call that has enqueued work on ctx's stream, rc being how far it got: wait for the stream and read
+	// and clear the device error flag whatever happened, then -- only if everything was enqueued -- copy what was staged to
+	// the caller and count the int32 kernel's tasks.  Returns rc, else the device's verdict.
+	int end(int rc)
 	{
+		if (rc) { // (the flag's text must not replace why the call failed)
+			std::string why = std::move(ctx->last_error);
+			(void)fetch_err(ctx);
+			ctx->last_error = std::move(why);
+			return rc;
+		}
+		rc = fetch_err(ctx);
 		for (int k = 0; k < n_pend; ++k) memcpy(pend[k].dst, (const uint8_t *)ctx->h_down.p + pend[k].off, pend[k].bytes);
-		n_pend = 0;
+		if (wide && ctx->wide_last) {
+			unsigned long long c = 0;
+			BMH_HIP(ctx, hipMemcpyAsync(&c, ctx->d_wide_stat, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+			BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+			ctx->wide_total += (long long)c;
+		}
+		return rc;
 	}
 };
+
+// A global batch's CIGAR pool: the device copy holds `words` words at the caller's offsets, words [lo, lo + n) come back to dst
+struct CigarDown {
+	size_t words;
+	uint32_t *dst;
+	size_t lo, n;
+};
+
+// One host-buffer batch on st.ctx up to its last download, leaving through st.end(): the pool (unless null: the one
+// bmh_upload_pool() left on the device) and the tasks up, launch(ctx, d_pool, d_tasks, d_res), the results and the CIGAR
+// words down.  Through the pinned staging buffers if `staged`, else copied directly (the sharded calls).
+template <class Task, class Result, class Launch>
+static int enqueue_batch(Stager &st, bool staged, const uint8_t *pool, size_t pool_bytes, const Task *tasks, int64_t n, Result *results,
+                         Launch launch, const CigarDown *cig = nullptr)
+{
+	bmh_ctx *c = st.ctx;
+	const size_t tb = (size_t)n * sizeof(Task), rb = (size_t)n * sizeof(Result);
+	int rc;
+	if (pool) {
+		c->pool_resident = false;
+		if ((rc = ensure(c, c->d_pool, pool_bytes + 16))) return rc;
+	}
+	if ((rc = ensure(c, c->d_tasks, tb)) || (rc = ensure(c, c->d_res, rb)) || (cig && (rc = ensure(c, c->d_cigar, (cig->words + 4) * 4))))
+		return rc;
+	if (staged && (rc = st.stage((pool ? pool_bytes + 64 : 0) + tb, rb + (cig ? 64 + cig->n * 4 : 0)))) return rc;
+	if (pool && (rc = st.h2d(c->d_pool.p, pool, pool_bytes))) return rc;
+	if ((rc = st.h2d(c->d_tasks.p, tasks, tb))) return rc;
+	if ((rc = launch(c, (const uint8_t *)c->d_pool.p, (const Task *)c->d_tasks.p, (Result *)c->d_res.p))) return rc;
+	if ((rc = st.d2h(results, c->d_res.p, rb))) return rc;
+	if (cig && cig->n && (rc = st.d2h(cig->dst, (const uint32_t *)c->d_cigar.p + cig->lo, cig->n * 4))) return rc;
+	return BMH_OK;
+}
 
 } // namespace bmh
 
@@ -531,39 +582,16 @@ int bmh_extend_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, con
 	if (!ctx->have_params) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
 	if (n > 0xffffffffLL) return BMH_E_ARG;
-	const bool resident = pool == nullptr; // use the pool left on the device by bmh_upload_pool()
-	if (resident) {
-		if (!ctx->pool_resident) return BMH_E_ARG;
-		pool_bytes = ctx->pool_bytes;
-	}
+	if (!pool && !ctx->pool_resident) return BMH_E_ARG; // (null: the pool left on the device by bmh_upload_pool())
 	int qmax = 1, rc;
-	if ((rc = validate_ext(ctx, tasks, n, pool_bytes, &qmax))) return rc;
+	if ((rc = validate_ext(ctx, tasks, n, pool ? pool_bytes : ctx->pool_bytes, &qmax))) return rc;
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	if (!resident) {
-		ctx->pool_resident = false;
-		if ((rc = ensure(ctx, ctx->d_pool, pool_bytes + 16))) return rc;
-	}
-	if ((rc = ensure(ctx, ctx->d_tasks, (size_t)n * sizeof(bmh_ext_task_t)))) return rc;
-	if ((rc = ensure(ctx, ctx->d_res, (size_t)n * sizeof(bmh_ext_result_t)))) return rc;
-	Stager st;
-	if ((rc = st.begin(ctx, (resident ? 0 : pool_bytes + 64) + (size_t)n * sizeof(bmh_ext_task_t), (size_t)n * sizeof(bmh_ext_result_t)))) return rc;
-	if (!resident && (rc = st.h2d(ctx->d_pool.p, pool, pool_bytes))) return rc;
-	if ((rc = st.h2d(ctx->d_tasks.p, tasks, (size_t)n * sizeof(bmh_ext_task_t)))) return rc;
+	Stager st(ctx, true);
 	// launch order: the dispatcher sorts the tasks on the device (bin, length bucket, row estimate)
-	if ((rc = launch_extend(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_ext_task_t *)ctx->d_tasks.p, n,
-	                        (bmh_ext_result_t *)ctx->d_res.p, nullptr, qmax)))
-		return rc;
-	if ((rc = st.d2h(results, ctx->d_res.p, (size_t)n * sizeof(bmh_ext_result_t)))) return rc;
-	rc = fetch_err(ctx); // synchronises
-	st.finish();
-	if (ctx->wide_last) {
-		unsigned long long c = 0;
-		BMH_HIP(ctx, hipMemcpyAsync(&c, ctx->d_wide_stat, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-		ctx->wide_total += (long long)c;
-	}
-	return rc;
+	return st.end(enqueue_batch(st, true, pool, pool_bytes, tasks, n, results, [&](bmh_ctx *c, auto p, auto t, auto r) {
+		return launch_extend(c, p, t, n, r, nullptr, qmax);
+	}));
 }
 
 int bmh_upload_pool(bmh_ctx_t *ctx, const uint8_t *pool, size_t bytes)
@@ -574,8 +602,8 @@ int bmh_upload_pool(bmh_ctx_t *ctx, const uint8_t *pool, size_t bytes)
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	ctx->pool_resident = false;
 	if ((rc = ensure(ctx, ctx->d_pool, bytes + 16))) return rc;
-	Stager st;
-	if ((rc = st.begin(ctx, bytes, 0)) || (rc = st.h2d(ctx->d_pool.p, pool, bytes))) return rc;
+	Stager st(ctx);
+	if ((rc = st.stage(bytes, 0)) || (rc = st.h2d(ctx->d_pool.p, pool, bytes))) return rc;
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream)); // `pool` may be freed by the caller on return
 	ctx->pool_resident = true, ctx->pool_bytes = bytes;
 	return BMH_OK;
@@ -588,62 +616,6 @@ int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx) { return ctx ? ctx->wide_total
 void bmh_ctx_set_driver_stats_(bmh_ctx_t *ctx, const bmh_driver_stats_t *st)
 {
 	if (ctx && st) ctx->dstats = *st;
-}
-
-int bmh_extend_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *pool, size_t pool_bytes,
-                             const bmh_ext_task_t *tasks, int64_t n, bmh_ext_result_t *results)
-{
-	if (!ctxs || n_ctx < 1 || n < 0) return BMH_E_ARG;
-	for (int g = 0; g < n_ctx; ++g)
-		if (!ctxs[g] || !ctxs[g]->have_params) return BMH_E_ARG;
-	if (n == 0) return BMH_OK;
-	// contiguous static split; every shard gets the whole pool (offsets stay valid), its own task slice
-	std::vector<int64_t> lo((size_t)n_ctx + 1);
-	for (int g = 0; g <= n_ctx; ++g) lo[(size_t)g] = n * g / n_ctx;
-	int rc;
-	for (int g = 0; g < n_ctx; ++g) { // enqueue everything on every device before waiting on any
-		bmh_ctx *c = ctxs[g];
-		const int64_t m = lo[(size_t)g + 1] - lo[(size_t)g];
-		if (m == 0) continue;
-		const bmh_ext_task_t *t = tasks + lo[(size_t)g];
-		int qmax = 1;
-		if ((rc = validate_ext(c, t, m, pool_bytes, &qmax))) {
-			for (int h = 0; h < g; ++h) {
-				(void)hipSetDevice(ctxs[h]->device);
-				(void)stream_wait(ctxs[h], ctxs[h]->stream);
-			}
-			return rc;
-		}
-		BMH_HIP(c, hipSetDevice(c->device));
-		c->pool_resident = false; // the context's pool is overwritten below
-		rc = BMH_OK;
-		if (!rc) rc = ensure(c, c->d_pool, pool_bytes + 16);
-		if (!rc) rc = ensure(c, c->d_tasks, (size_t)m * sizeof(bmh_ext_task_t));
-		if (!rc) rc = ensure(c, c->d_res, (size_t)m * sizeof(bmh_ext_result_t));
-		if (!rc && hipMemcpyAsync(c->d_pool.p, pool, pool_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = BMH_E_HIP;
-		if (!rc && hipMemcpyAsync(c->d_tasks.p, t, (size_t)m * sizeof(bmh_ext_task_t), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = BMH_E_HIP;
-		if (!rc)
-			rc = launch_extend(c, (const uint8_t *)c->d_pool.p, (const bmh_ext_task_t *)c->d_tasks.p, m, (bmh_ext_result_t *)c->d_res.p, nullptr,
-			                   qmax);
-		if (!rc && hipMemcpyAsync(results + lo[(size_t)g], c->d_res.p, (size_t)m * sizeof(bmh_ext_result_t), hipMemcpyDeviceToHost, c->stream) !=
-		               hipSuccess)
-			rc = BMH_E_HIP;
-		if (rc) { // copies into the caller's `results` may be in flight on the devices already served: drain them first
-			for (int h = 0; h <= g; ++h) {
-				(void)hipSetDevice(ctxs[h]->device);
-				(void)stream_wait(ctxs[h], ctxs[h]->stream);
-			}
-			return rc;
-		}
-	}
-	int first = BMH_OK;
-	for (int g = 0; g < n_ctx; ++g) {
-		if (lo[(size_t)g + 1] == lo[(size_t)g]) continue;
-		BMH_HIP(ctxs[g], hipSetDevice(ctxs[g]->device));
-		rc = fetch_err(ctxs[g]);
-		if (rc && !first) first = rc;
-	}
-	return first;
 }
 
 // ------------------------------------------------------------------ fused per-seed extension (row a5)
@@ -710,16 +682,16 @@ int bmh_seedext_submit(bmh_ctx_t *ctx, const bmh_seed_task_t *tasks, int64_t n)
 	if ((rc = ensure_host(ctx, ctx->h_up, tb + 256)) || (rc = ensure_host(ctx, ctx->h_down, rb + 256))) return rc;
 	if (n > 0) {
 		memcpy(ctx->h_up.p, tasks, tb);
-		BMH_HIP(ctx, hipMemcpyAsync(ctx->d_tasks.p, ctx->h_up.p, tb, hipMemcpyHostToDevice, ctx->stream));
-		if ((rc = launch_seedext(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_seed_task_t *)ctx->d_tasks.p, n,
-		                         (bmh_seed_result_t *)ctx->d_res.p, qmax)))
-			return rc;
-		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_down.p, ctx->d_res.p, rb, hipMemcpyDeviceToHost, ctx->stream));
-		BMH_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->h_down.p + ((rb + 63) & ~(size_t)63), seedext_counters(ctx), 16, hipMemcpyDeviceToHost,
-		                            ctx->stream));
-		if (ctx->wide_last) // (behind the four list lengths: what the wide bin received over the four rounds)
-			BMH_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->h_down.p + ((rb + 63) & ~(size_t)63) + 16, ctx->d_wide_stat, 8, hipMemcpyDeviceToHost,
-			                            ctx->stream));
+		uint8_t *cnt = (uint8_t *)ctx->h_down.p + ((rb + 63) & ~(size_t)63);
+		Stager st(ctx); // (not staged: both ends are pinned already)
+		rc = st.h2d(ctx->d_tasks.p, ctx->h_up.p, tb);
+		if (!rc)
+			rc = launch_seedext(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_seed_task_t *)ctx->d_tasks.p, n, (bmh_seed_result_t *)ctx->d_res.p,
+			                    qmax);
+		if (!rc) rc = st.d2h(ctx->h_down.p, ctx->d_res.p, rb);
+		if (!rc) rc = st.d2h(cnt, seedext_counters(ctx), 16);
+		if (!rc && ctx->wide_last) rc = st.d2h(cnt + 16, ctx->d_wide_stat, 8); // (behind the four list lengths: what the wide bin received)
+		if (rc) return st.end(rc); // (on success bmh_seedext_wait waits)
 	}
 	ctx->seed_pending_n = n;
 	return BMH_OK;
@@ -810,38 +782,18 @@ int bmh_global_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, con
 	if (!ctx->have_params) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
 	if (n > 0xffffffffLL) return BMH_E_ARG;
-	const bool resident = pool == nullptr; // use the pool left on the device by bmh_upload_pool()
-	if (resident) {
-		if (!ctx->pool_resident) return BMH_E_ARG;
-		pool_bytes = ctx->pool_bytes;
-	}
+	if (!pool && !ctx->pool_resident) return BMH_E_ARG; // (null: the pool left on the device by bmh_upload_pool())
 	GlbShape gs;
 	int rc;
-	if ((rc = validate_glb(ctx, tasks, n, pool_bytes, cigar_pool != nullptr, cigar_words, &gs))) return rc;
-	const int qmax = gs.qmax, tmax = gs.tmax, wmax = gs.wmax, wraw = gs.wraw;
+	if ((rc = validate_glb(ctx, tasks, n, pool ? pool_bytes : ctx->pool_bytes, cigar_pool != nullptr, cigar_words, &gs))) return rc;
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	if (!resident) {
-		ctx->pool_resident = false;
-		if ((rc = ensure(ctx, ctx->d_pool, pool_bytes + 16))) return rc;
-	}
-	if ((rc = ensure(ctx, ctx->d_tasks, (size_t)n * sizeof(bmh_glb_task_t)))) return rc;
-	if ((rc = ensure(ctx, ctx->d_res, (size_t)n * sizeof(bmh_glb_result_t)))) return rc;
-	if ((rc = ensure(ctx, ctx->d_cigar, (cigar_words + 4) * 4))) return rc;
-	Stager st;
-	if ((rc = st.begin(ctx, (resident ? 0 : pool_bytes + 64) + (size_t)n * sizeof(bmh_glb_task_t),
-	                   (size_t)n * sizeof(bmh_glb_result_t) + 64 + cigar_words * 4)))
-		return rc;
-	if (!resident && (rc = st.h2d(ctx->d_pool.p, pool, pool_bytes))) return rc;
-	if ((rc = st.h2d(ctx->d_tasks.p, tasks, (size_t)n * sizeof(bmh_glb_task_t)))) return rc;
-	if ((rc = launch_global(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_glb_task_t *)ctx->d_tasks.p, n,
-	                        (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr, qmax, tmax, wmax, wraw)))
-		return rc;
-	if ((rc = st.d2h(results, ctx->d_res.p, (size_t)n * sizeof(bmh_glb_result_t)))) return rc;
-	if (cigar_words && (rc = st.d2h(cigar_pool, ctx->d_cigar.p, cigar_words * 4))) return rc;
-	rc = fetch_err(ctx);
-	st.finish();
-	return rc;
+	Stager st(ctx);
+	const CigarDown cig{cigar_words, cigar_pool, 0, cigar_words};
+	return st.end(enqueue_batch(
+	    st, true, pool, pool_bytes, tasks, n, results,
+	    [&](bmh_ctx *c, auto p, auto t, auto r) { return launch_global(c, p, t, n, r, (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw); },
+	    &cig));
 }
 
 // ------------------------------------------------------------------ the region record (bwa_gen_cigar2 around ksw_global2)
@@ -880,42 +832,42 @@ int bmh_region_cigar_batch(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readp
 	if (n_tasks > 0 && (rc = validate_glb(ctx, tasks, n_tasks, opool_bytes, true, task_cigar_words, &gs))) return rc;
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	// device pool = [oriented copies | the query windows as uploaded]
-	const size_t rpool_off = (opool_bytes + 16 + 63) & ~(size_t)63;
-	ctx->pool_resident = false;
-	if ((rc = ensure(ctx, ctx->d_pool, rpool_off + readpool_bytes + 16))) return rc;
-	if ((rc = ensure(ctx, ctx->d_tasks, (size_t)std::max<int64_t>(n_tasks, 1) * sizeof(bmh_glb_task_t)))) return rc;
-	if ((rc = ensure(ctx, ctx->d_res, (size_t)std::max<int64_t>(n_tasks, 1) * sizeof(bmh_glb_result_t)))) return rc;
-	if ((rc = ensure(ctx, ctx->d_cigar, (task_cigar_words + 4) * 4))) return rc;
-	const size_t req_b = ((size_t)n_req * sizeof(bmh_region_req_t) + 255) & ~(size_t)255;
-	const size_t res_b = ((size_t)n_req * sizeof(bmh_region_res_t) + 255) & ~(size_t)255;
-	const size_t cig_b = ((size_t)n_req * (size_t)cig_cap * 4 + 255) & ~(size_t)255;
-	const size_t md_b = ((size_t)n_req * (size_t)md_cap + 255) & ~(size_t)255;
-	if ((rc = ensure(ctx, ctx->d_region, req_b + res_b + cig_b + md_b))) return rc;
-	uint8_t *d_reg = (uint8_t *)ctx->d_region.p;
-	bmh_region_req_t *d_reqs = (bmh_region_req_t *)d_reg;
-	bmh_region_res_t *d_rres = (bmh_region_res_t *)(d_reg + req_b);
-	uint32_t *d_cout = (uint32_t *)(d_reg + req_b + res_b);
-	char *d_md = (char *)(d_reg + req_b + res_b + cig_b);
-	Stager st;
-	if ((rc = st.begin(ctx, readpool_bytes + 64 + (size_t)n_req * sizeof(bmh_region_req_t) + 64 + (size_t)n_tasks * sizeof(bmh_glb_task_t) + 64,
-	                   res_b + cig_b + md_b)))
-		return rc;
-	if ((rc = st.h2d((uint8_t *)ctx->d_pool.p + rpool_off, readpool, readpool_bytes))) return rc;
-	if ((rc = st.h2d(d_reqs, reqs, (size_t)n_req * sizeof(bmh_region_req_t)))) return rc;
-	if (n_tasks > 0 && (rc = st.h2d(ctx->d_tasks.p, tasks, (size_t)n_tasks * sizeof(bmh_glb_task_t)))) return rc;
-	if ((rc = launch_region_orient(ctx, (uint8_t *)ctx->d_pool.p, rpool_off, d_reqs, n_req))) return rc;
-	if (n_tasks > 0 && (rc = launch_global(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_glb_task_t *)ctx->d_tasks.p, n_tasks,
-	                                       (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw)))
-		return rc;
-	if ((rc = launch_region_finish(ctx, (const uint8_t *)ctx->d_pool.p, d_reqs, n_req, (const bmh_glb_task_t *)ctx->d_tasks.p,
-	                               (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p, d_rres, d_cout, cig_cap, d_md, md_cap)))
-		return rc;
-	if ((rc = st.d2h(results, d_rres, (size_t)n_req * sizeof(bmh_region_res_t)))) return rc;
-	if ((rc = st.d2h(cigar_out, d_cout, (size_t)n_req * (size_t)cig_cap * 4))) return rc;
-	if ((rc = st.d2h(md_out, d_md, (size_t)n_req * (size_t)md_cap))) return rc;
-	rc = fetch_err(ctx);
-	st.finish();
+	Stager st(ctx);
+	rc = st.end([&]() -> int {
+		// device pool = [oriented copies | the query windows as uploaded]
+		const size_t rpool_off = (opool_bytes + 16 + 63) & ~(size_t)63;
+		ctx->pool_resident = false;
+		if ((rc = ensure(ctx, ctx->d_pool, rpool_off + readpool_bytes + 16))) return rc;
+		if ((rc = ensure(ctx, ctx->d_tasks, (size_t)std::max<int64_t>(n_tasks, 1) * sizeof(bmh_glb_task_t)))) return rc;
+		if ((rc = ensure(ctx, ctx->d_res, (size_t)std::max<int64_t>(n_tasks, 1) * sizeof(bmh_glb_result_t)))) return rc;
+		if ((rc = ensure(ctx, ctx->d_cigar, (task_cigar_words + 4) * 4))) return rc;
+		const size_t req_b = ((size_t)n_req * sizeof(bmh_region_req_t) + 255) & ~(size_t)255;
+		const size_t res_b = ((size_t)n_req * sizeof(bmh_region_res_t) + 255) & ~(size_t)255;
+		const size_t cig_b = ((size_t)n_req * (size_t)cig_cap * 4 + 255) & ~(size_t)255;
+		const size_t md_b = ((size_t)n_req * (size_t)md_cap + 255) & ~(size_t)255;
+		if ((rc = ensure(ctx, ctx->d_region, req_b + res_b + cig_b + md_b))) return rc;
+		uint8_t *d_reg = (uint8_t *)ctx->d_region.p;
+		bmh_region_req_t *d_reqs = (bmh_region_req_t *)d_reg;
+		bmh_region_res_t *d_rres = (bmh_region_res_t *)(d_reg + req_b);
+		uint32_t *d_cout = (uint32_t *)(d_reg + req_b + res_b);
+		char *d_md = (char *)(d_reg + req_b + res_b + cig_b);
+		if ((rc = st.stage(readpool_bytes + 64 + (size_t)n_req * sizeof(bmh_region_req_t) + 64 + (size_t)n_tasks * sizeof(bmh_glb_task_t) + 64,
+		                   res_b + cig_b + md_b)))
+			return rc;
+		if ((rc = st.h2d((uint8_t *)ctx->d_pool.p + rpool_off, readpool, readpool_bytes))) return rc;
+		if ((rc = st.h2d(d_reqs, reqs, (size_t)n_req * sizeof(bmh_region_req_t)))) return rc;
+		if (n_tasks > 0 && (rc = st.h2d(ctx->d_tasks.p, tasks, (size_t)n_tasks * sizeof(bmh_glb_task_t)))) return rc;
+		if ((rc = launch_region_orient(ctx, (uint8_t *)ctx->d_pool.p, rpool_off, d_reqs, n_req))) return rc;
+		if (n_tasks > 0 && (rc = launch_global(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_glb_task_t *)ctx->d_tasks.p, n_tasks,
+		                                       (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw)))
+			return rc;
+		if ((rc = launch_region_finish(ctx, (const uint8_t *)ctx->d_pool.p, d_reqs, n_req, (const bmh_glb_task_t *)ctx->d_tasks.p,
+		                               (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p, d_rres, d_cout, cig_cap, d_md, md_cap)))
+			return rc;
+		if ((rc = st.d2h(results, d_rres, (size_t)n_req * sizeof(bmh_region_res_t)))) return rc;
+		if ((rc = st.d2h(cigar_out, d_cout, (size_t)n_req * (size_t)cig_cap * 4))) return rc;
+		return st.d2h(md_out, d_md, (size_t)n_req * (size_t)md_cap);
+	}());
 	return rc == BMH_E_CIGAR_CAP ? BMH_OK : rc; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
 }
 
@@ -972,120 +924,104 @@ int bmh_sw_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, const b
 	if (!ctx->have_params) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
 	if (n > 0xffffffffLL) return BMH_E_ARG;
-	const bool resident = pool == nullptr; // use the pool left on the device by bmh_upload_pool()
-	if (resident) {
-		if (!ctx->pool_resident) return BMH_E_ARG;
-		pool_bytes = ctx->pool_bytes;
-	}
+	if (!pool && !ctx->pool_resident) return BMH_E_ARG; // (null: the pool left on the device by bmh_upload_pool())
 	int qmax = 1, tmax = 1, qmin = 65535, rc;
-	if ((rc = validate_sw(ctx, tasks, n, pool_bytes, &qmax, &tmax, &qmin))) return rc;
+	if ((rc = validate_sw(ctx, tasks, n, pool ? pool_bytes : ctx->pool_bytes, &qmax, &tmax, &qmin))) return rc;
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	if (!resident) {
-		ctx->pool_resident = false;
-		if ((rc = ensure(ctx, ctx->d_pool, pool_bytes + 16))) return rc;
-	}
-	if ((rc = ensure(ctx, ctx->d_tasks, (size_t)n * sizeof(bmh_sw_task_t)))) return rc;
-	if ((rc = ensure(ctx, ctx->d_res, (size_t)n * sizeof(bmh_sw_result_t)))) return rc;
-	Stager st;
-	if ((rc = st.begin(ctx, (resident ? 0 : pool_bytes + 64) + (size_t)n * sizeof(bmh_sw_task_t), (size_t)n * sizeof(bmh_sw_result_t)))) return rc;
-	if (!resident && (rc = st.h2d(ctx->d_pool.p, pool, pool_bytes))) return rc;
-	if ((rc = st.h2d(ctx->d_tasks.p, tasks, (size_t)n * sizeof(bmh_sw_task_t)))) return rc;
-	if ((rc = launch_sw(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_sw_task_t *)ctx->d_tasks.p, n,
-	                    (bmh_sw_result_t *)ctx->d_res.p, qmax, tmax, qmin)))
-		return rc;
-	if ((rc = st.d2h(results, ctx->d_res.p, (size_t)n * sizeof(bmh_sw_result_t)))) return rc;
-	rc = fetch_err(ctx); // synchronises
-	st.finish();
-	return rc;
+	Stager st(ctx);
+	return st.end(enqueue_batch(st, true, pool, pool_bytes, tasks, n, results, [&](bmh_ctx *c, auto p, auto t, auto r) {
+		return launch_sw(c, p, t, n, r, qmax, tmax, qmin);
+	}));
 }
 
-// ------------------------------------------------------------------ static shards of the other batches
+// ------------------------------------------------------------------ static shards of one batch over several contexts
 // One contiguous slice of the tasks per context (one context per GPU), every device given the whole sequence pool (offsets stay
-// valid), everything -- uploads, kernels, downloads -- enqueued on every device's stream before any of them is waited for; no
-// collective, no device-to-device traffic.  The same split as kt_for_batch's ranges (reference kthread_batch.c:44-56, bwamem.c:1313).
+// valid); no collective, no device-to-device traffic.  The same split as kt_for_batch's ranges (reference kthread_batch.c:44-56,
+// bwamem.c:1313).  Every shard is validated on the host before anything is enqueued anywhere, so a refused call has no effect;
+// then, inside one device gate, each shard's batch is enqueued with direct copies on its context's stream before any of them is
+// waited for, and every context served leaves through Stager::end, whatever happened.  Returns the first error.
 } // extern "C"
-static void drain_shards(bmh_ctx_t *const *ctxs, int upto)
-{
-	for (int h = 0; h <= upto; ++h) {
-		(void)hipSetDevice(ctxs[h]->device);
-		(void)stream_wait(ctxs[h], ctxs[h]->stream);
-	}
-}
-template <class Enqueue> static int run_sharded(bmh_ctx_t *const *ctxs, int n_ctx, int64_t n, Enqueue enqueue)
+template <class Validate, class Enqueue>
+static int run_sharded(bmh_ctx_t *const *ctxs, int n_ctx, int64_t n, Validate validate, Enqueue enqueue)
 {
 	if (!ctxs || n_ctx < 1 || n < 0) return BMH_E_ARG;
 	for (int g = 0; g < n_ctx; ++g)
 		if (!ctxs[g] || !ctxs[g]->have_params) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
-	for (int g = 0; g < n_ctx; ++g) {
-		const int64_t lo = n * g / n_ctx, m = n * (g + 1) / n_ctx - lo;
-		if (m == 0) continue;
-		bmh_ctx *c = ctxs[g];
-		int rc = hipSetDevice(c->device) == hipSuccess ? BMH_OK : BMH_E_HIP;
-		if (!rc) rc = enqueue(c, g, lo, m);
-		if (rc) { // copies into the caller's arrays may be in flight on the devices already served: drain them first
-			drain_shards(ctxs, g);
-			return rc;
+	const auto lo = [=](int g) { return n * g / n_ctx; };
+	int rc;
+	for (int g = 0; g < n_ctx; ++g)
+		if (lo(g + 1) > lo(g) && (rc = validate(ctxs[g], (size_t)g, lo(g), lo(g + 1) - lo(g)))) return rc;
+	GateGuard gate;
+	std::vector<Stager> st((size_t)n_ctx);
+	int failed = BMH_OK, g = 0;
+	for (; g < n_ctx && !failed; ++g)
+		if (lo(g + 1) > lo(g)) {
+			st[(size_t)g] = Stager(ctxs[g]);
+			const hipError_t e = hipSetDevice(ctxs[g]->device);
+			failed = e != hipSuccess ? set_hip_error(ctxs[g], e, "hipSetDevice") : enqueue(st[(size_t)g], (size_t)g, lo(g), lo(g + 1) - lo(g));
 		}
-	}
-	int first = BMH_OK;
-	for (int g = 0; g < n_ctx; ++g) {
-		if (n * (g + 1) / n_ctx == n * g / n_ctx) continue;
-		BMH_HIP(ctxs[g], hipSetDevice(ctxs[g]->device));
-		const int rc = fetch_err(ctxs[g]); // synchronises
-		if (rc && !first) first = rc;
-	}
+	int first = failed;
+	for (int h = 0; h < g; ++h) // (g - 1: the context whose enqueue failed, if one did)
+		if (lo(h + 1) > lo(h)) {
+			const hipError_t e = hipSetDevice(ctxs[h]->device);
+			rc = st[(size_t)h].end(h == g - 1 ? failed : BMH_OK);
+			if (!first) first = e != hipSuccess ? set_hip_error(ctxs[h], e, "hipSetDevice") : rc;
+		}
 	return first;
 }
-#define SH_TRY(expr)                                                                                                   \
-	do {                                                                                                               \
-		if ((expr) != hipSuccess) {                                                                                    \
-			c->last_error = std::string(#expr) + ": " + hipGetErrorString(hipGetLastError());                          \
-			return BMH_E_HIP;                                                                                          \
-		}                                                                                                              \
-	} while (0)
 
 extern "C" {
+int bmh_extend_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *pool, size_t pool_bytes, const bmh_ext_task_t *tasks, int64_t n,
+                             bmh_ext_result_t *results)
+{
+	if (n > 0 && (!pool || !tasks || !results)) return BMH_E_ARG;
+	std::vector<int> qmax((size_t)std::max(n_ctx, 0));
+	return run_sharded(
+	    ctxs, n_ctx, n, [&](bmh_ctx *c, size_t g, int64_t lo, int64_t m) { return validate_ext(c, tasks + lo, m, pool_bytes, &qmax[g]); },
+	    [&](Stager &st, size_t g, int64_t lo, int64_t m) {
+		    st.wide = true;
+		    return enqueue_batch(st, false, pool, pool_bytes, tasks + lo, m, results + lo, [&](bmh_ctx *c, auto p, auto t, auto r) {
+			    return launch_extend(c, p, t, m, r, nullptr, qmax[g]);
+		    });
+	    });
+}
+
 int bmh_seedext_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *pool, size_t pool_bytes, const bmh_seed_task_t *tasks,
                               int64_t n, bmh_seed_result_t *results)
 {
 	if (n > 0 && (!pool || !tasks || !results)) return BMH_E_ARG;
-	return run_sharded(ctxs, n_ctx, n, [&](bmh_ctx *c, int, int64_t lo, int64_t m) -> int {
-		int qmax = 1, rc;
-		if (m > 0x7fffffffLL) return BMH_E_ARG;
-		if ((rc = validate_seeds(c, tasks + lo, m, pool_bytes, &qmax))) return rc;
-		c->pool_resident = false;
-		if ((rc = ensure(c, c->d_pool, pool_bytes + 16)) || (rc = ensure(c, c->d_tasks, (size_t)m * sizeof(bmh_seed_task_t) + 64)) ||
-		    (rc = ensure(c, c->d_res, (size_t)m * sizeof(bmh_seed_result_t) + 64)))
-			return rc;
-		SH_TRY(hipMemcpyAsync(c->d_pool.p, pool, pool_bytes, hipMemcpyHostToDevice, c->stream));
-		SH_TRY(hipMemcpyAsync(c->d_tasks.p, tasks + lo, (size_t)m * sizeof(bmh_seed_task_t), hipMemcpyHostToDevice, c->stream));
-		if ((rc = launch_seedext(c, (const uint8_t *)c->d_pool.p, (const bmh_seed_task_t *)c->d_tasks.p, m, (bmh_seed_result_t *)c->d_res.p, qmax)))
-			return rc;
-		SH_TRY(hipMemcpyAsync(results + lo, c->d_res.p, (size_t)m * sizeof(bmh_seed_result_t), hipMemcpyDeviceToHost, c->stream));
-		return BMH_OK;
-	});
+	std::vector<int> qmax((size_t)std::max(n_ctx, 0));
+	return run_sharded(
+	    ctxs, n_ctx, n,
+	    [&](bmh_ctx *c, size_t g, int64_t lo, int64_t m) { return m > 0x7fffffffLL ? BMH_E_ARG : validate_seeds(c, tasks + lo, m, pool_bytes, &qmax[g]); },
+	    [&](Stager &st, size_t g, int64_t lo, int64_t m) {
+		    return enqueue_batch(st, false, pool, pool_bytes, tasks + lo, m, results + lo, [&](bmh_ctx *c, auto p, auto t, auto r) {
+			    return launch_seedext(c, p, t, m, r, qmax[g]);
+		    });
+	    });
 }
 
 int bmh_sw_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *pool, size_t pool_bytes, const bmh_sw_task_t *tasks, int64_t n,
                          bmh_sw_result_t *results)
 {
 	if (n > 0 && (!pool || !tasks || !results)) return BMH_E_ARG;
-	return run_sharded(ctxs, n_ctx, n, [&](bmh_ctx *c, int, int64_t lo, int64_t m) -> int {
-		int qmax = 1, tmax = 1, qmin = 65535, rc;
-		if ((rc = validate_sw(c, tasks + lo, m, pool_bytes, &qmax, &tmax, &qmin))) return rc;
-		c->pool_resident = false;
-		if ((rc = ensure(c, c->d_pool, pool_bytes + 16)) || (rc = ensure(c, c->d_tasks, (size_t)m * sizeof(bmh_sw_task_t))) ||
-		    (rc = ensure(c, c->d_res, (size_t)m * sizeof(bmh_sw_result_t))))
-			return rc;
-		SH_TRY(hipMemcpyAsync(c->d_pool.p, pool, pool_bytes, hipMemcpyHostToDevice, c->stream));
-		SH_TRY(hipMemcpyAsync(c->d_tasks.p, tasks + lo, (size_t)m * sizeof(bmh_sw_task_t), hipMemcpyHostToDevice, c->stream));
-		if ((rc = launch_sw(c, (const uint8_t *)c->d_pool.p, (const bmh_sw_task_t *)c->d_tasks.p, m, (bmh_sw_result_t *)c->d_res.p, qmax, tmax, qmin)))
-			return rc;
-		SH_TRY(hipMemcpyAsync(results + lo, c->d_res.p, (size_t)m * sizeof(bmh_sw_result_t), hipMemcpyDeviceToHost, c->stream));
-		return BMH_OK;
-	});
+	struct SwShape {
+		int qmax = 1, tmax = 1, qmin = 65535;
+	};
+	std::vector<SwShape> shape((size_t)std::max(n_ctx, 0));
+	return run_sharded(
+	    ctxs, n_ctx, n,
+	    [&](bmh_ctx *c, size_t g, int64_t lo, int64_t m) {
+		    SwShape &s = shape[g];
+		    return validate_sw(c, tasks + lo, m, pool_bytes, &s.qmax, &s.tmax, &s.qmin);
+	    },
+	    [&](Stager &st, size_t g, int64_t lo, int64_t m) {
+		    return enqueue_batch(st, false, pool, pool_bytes, tasks + lo, m, results + lo, [&](bmh_ctx *c, auto p, auto t, auto r) {
+			    return launch_sw(c, p, t, m, r, shape[g].qmax, shape[g].tmax, shape[g].qmin);
+		    });
+	    });
 }
 
 int bmh_global_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *pool, size_t pool_bytes, const bmh_glb_task_t *tasks, int64_t n,
@@ -1096,27 +1032,20 @@ int bmh_global_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *p
 	// device only holds what its own tasks wrote
 	std::vector<std::vector<uint32_t>> back((size_t)std::max(n_ctx, 0));
 	std::vector<GlbShape> shape((size_t)std::max(n_ctx, 0));
-	const int rc = run_sharded(ctxs, n_ctx, n, [&](bmh_ctx *c, int g, int64_t lo, int64_t m) -> int {
-		int rc;
-		GlbShape &gs = shape[(size_t)g];
-		if (m > 0xffffffffLL) return BMH_E_ARG;
-		if ((rc = validate_glb(c, tasks + lo, m, pool_bytes, cigar_pool != nullptr, cigar_words, &gs))) return rc;
-		c->pool_resident = false;
-		if ((rc = ensure(c, c->d_pool, pool_bytes + 16)) || (rc = ensure(c, c->d_tasks, (size_t)m * sizeof(bmh_glb_task_t))) ||
-		    (rc = ensure(c, c->d_res, (size_t)m * sizeof(bmh_glb_result_t))) || (rc = ensure(c, c->d_cigar, (cigar_words + 4) * 4)))
-			return rc;
-		SH_TRY(hipMemcpyAsync(c->d_pool.p, pool, pool_bytes, hipMemcpyHostToDevice, c->stream));
-		SH_TRY(hipMemcpyAsync(c->d_tasks.p, tasks + lo, (size_t)m * sizeof(bmh_glb_task_t), hipMemcpyHostToDevice, c->stream));
-		if ((rc = launch_global(c, (const uint8_t *)c->d_pool.p, (const bmh_glb_task_t *)c->d_tasks.p, m, (bmh_glb_result_t *)c->d_res.p,
-		                        (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw)))
-			return rc;
-		SH_TRY(hipMemcpyAsync(results + lo, c->d_res.p, (size_t)m * sizeof(bmh_glb_result_t), hipMemcpyDeviceToHost, c->stream));
-		if (gs.cig_hi > gs.cig_lo) {
-			back[(size_t)g].resize(gs.cig_hi - gs.cig_lo);
-			SH_TRY(hipMemcpyAsync(back[(size_t)g].data(), (const uint32_t *)c->d_cigar.p + gs.cig_lo, (gs.cig_hi - gs.cig_lo) * 4, hipMemcpyDeviceToHost, c->stream));
-		}
-		return BMH_OK;
-	});
+	const int rc = run_sharded(
+	    ctxs, n_ctx, n,
+	    [&](bmh_ctx *c, size_t g, int64_t lo, int64_t m) {
+		    return m > 0xffffffffLL ? BMH_E_ARG : validate_glb(c, tasks + lo, m, pool_bytes, cigar_pool != nullptr, cigar_words, &shape[g]);
+	    },
+	    [&](Stager &st, size_t g, int64_t lo, int64_t m) {
+		    const GlbShape &gs = shape[g];
+		    back[g].resize(gs.cig_hi > gs.cig_lo ? gs.cig_hi - gs.cig_lo : 0);
+		    const CigarDown cig{cigar_words, back[g].data(), gs.cig_lo, back[g].size()};
+		    return enqueue_batch(
+		        st, false, pool, pool_bytes, tasks + lo, m, results + lo,
+		        [&](bmh_ctx *c, auto p, auto t, auto r) { return launch_global(c, p, t, m, r, (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw); },
+		        &cig);
+	    });
 	if (rc && rc != BMH_E_CIGAR_CAP && rc != BMH_E_RANGE) return rc; // (a flagged task: the other tasks' results are still delivered)
 	for (int g = 0; g < n_ctx && n > 0; ++g) {
 		const int64_t lo = n * g / n_ctx, hi = n * (g + 1) / n_ctx;
@@ -1129,7 +1058,6 @@ int bmh_global_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *p
 	}
 	return rc;
 }
-#undef SH_TRY
 
 int bmh_ctx_reserve_staging(bmh_ctx_t *ctx, size_t upload_bytes, size_t download_bytes)
 {

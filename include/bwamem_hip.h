@@ -184,8 +184,10 @@ int bmh_extend_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *s
                              bmh_ext_result_t *results);
 /* The same static split for the other three batches of the DP path (declared here, records defined below): the fused per-seed
  * records, ksw_global2 + traceback, ksw_align2.  Contiguous task ranges like kt_for_batch's (reference kthread_batch.c:44-56,
- * bwamem.c:1313), every device gets the whole pool, everything is enqueued on every device before any is waited for, results
- * land at their task index; a shard's CIGAR words are copied into the caller's pool task by task. */
+ * bwamem.c:1313), every device gets the whole pool, results land at their task index; a shard's CIGAR words are copied into the
+ * caller's pool task by task.  All four validate every shard before anything is enqueued on any device, so a refused call has
+ * no effect (nothing run, nothing written to the caller's arrays); then, inside the device gate, everything is enqueued on every
+ * device before any is waited for, and every device is waited for before the call returns, on an error too. */
 struct bmh_seed_task; struct bmh_seed_result; struct bmh_sw_task; struct bmh_sw_result;
 int bmh_seedext_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *seqpool, size_t pool_bytes,
                               const struct bmh_seed_task *tasks, int64_t n, struct bmh_seed_result *results);
