@@ -144,6 +144,7 @@ def lib():
         L.bmh_ctx_set_qcap.argtypes = [C.c_void_p, C.c_int]
         L.bmh_ctx_set_wide_extension.argtypes = [C.c_void_p, C.c_int]
         L.bmh_extend_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.bmh_global_long_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_ctx_reserve_staging.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
         L.bmh_ctx_set_pac.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -253,6 +254,13 @@ class Context:
         """(tasks, ms) the last extension launch sent to the int32 kernel; ms is -1 with timing off (bmh_extend_wide_stats)."""
         n, ms = C.c_int64(0), C.c_float(-1)
         self._check(lib().bmh_extend_wide_stats(self._h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
+
+    def global_long_stats(self):
+        """(tasks, ms) this context's global-alignment launches have sent to the band-ring kernel so far (queries past 10 176
+        columns); ms sums its kernel time over the launches made with timing on, -1 with timing off (bmh_global_long_stats)."""
+        n, ms = C.c_int64(0), C.c_float(-1)
+        self._check(lib().bmh_global_long_stats(self._h, C.byref(n), C.byref(ms)))
         return int(n.value), float(ms.value)
 
     def reserve_staging(self, upload_bytes, download_bytes):

@@ -239,7 +239,7 @@ int bmh_ctx_create(bmh_ctx_t **out, int device)
 		if (hipSetDeviceFlags(hipDeviceScheduleBlockingSync) != hipSuccess) (void)hipGetLastError();
 	}
 	if (e != hipSuccess || (e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess ||
-	    (e = hipMalloc((void **)&ctx->d_err, sizeof(int))) != hipSuccess || (e = hipMemset(ctx->d_err, 0, sizeof(int))) != hipSuccess ||
+	    (e = hipMalloc((void **)&ctx->d_err, 16)) != hipSuccess || (e = hipMemset(ctx->d_err, 0, 16)) != hipSuccess ||
 	    (e = hipHostMalloc((void **)&ctx->h_err, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
 	    (e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess ||
 	    (e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)) != hipSuccess ||
@@ -317,6 +317,8 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	}
 	for (int b = 0; b < 4; ++b)
 		if (ctx->ev_gbin[b]) (void)hipEventDestroy(ctx->ev_gbin[b]);
+	for (int b = 0; b < 2; ++b)
+		if (ctx->ev_glong[b]) (void)hipEventDestroy(ctx->ev_glong[b]);
 	for (int b = 0; b < 5; ++b)
 		if (ctx->ev_sround[b]) (void)hipEventDestroy(ctx->ev_sround[b]);
 	if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -459,6 +461,18 @@ int bmh_extend_wide_stats(const bmh_ctx_t *cctx, int64_t *tasks, float *ms)
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
 	*tasks = (int64_t)c;
 	if (ctx->timing) *ms = (float)ctx->wide_ms_sum;
+	return BMH_OK;
+}
+
+int bmh_global_long_stats(const bmh_ctx_t *cctx, int64_t *tasks, float *ms)
+{
+	if (!cctx || !tasks || !ms) return BMH_E_ARG;
+	bmh_ctx *ctx = const_cast<bmh_ctx *>(cctx); // (waits for the stream; the context's settings are not touched)
+	unsigned long long c = 0;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, hipMemcpyAsync(&c, ctx->d_err + 2, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	*tasks = (int64_t)c, *ms = ctx->timing ? (float)ctx->glong_ms_sum : -1.f;
 	return BMH_OK;
 }
 
@@ -613,6 +627,12 @@ int bmh_upload_pool(bmh_ctx_t *ctx, const uint8_t *pool, size_t bytes)
 const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx) { return ctx && ctx->have_params ? &ctx->params : nullptr; }
 // ... and for host/tls_ctx.c: tasks the int32 extension kernel received over this context's host-buffer calls
 int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx) { return ctx ? ctx->wide_total : 0; }
+int64_t bmh_ctx_glong_tasks_(const bmh_ctx_t *ctx)
+{
+	int64_t t = 0;
+	float ms;
+	return ctx && bmh_global_long_stats(ctx, &t, &ms) == BMH_OK ? t : 0;
+}
 void bmh_ctx_set_driver_stats_(bmh_ctx_t *ctx, const bmh_driver_stats_t *st)
 {
 	if (ctx && st) ctx->dstats = *st;
@@ -741,7 +761,8 @@ int bmh_seedext_stats(const bmh_ctx_t *ctx, bmh_seedext_stats_t *st)
 // ------------------------------------------------------------------ global
 
 struct GlbShape {
-	int qmax = 1, tmax = 1, wmax = 0, wraw = 0;
+	int qmax = 1, tmax = 1, wmax = 0, wraw = 0; // (qmax, tmax, wmax: of the tasks with qlen <= kGlbLdsQcap)
+	GlbLongShape lg;                            // ... and of the longer ones, bin 4's
 	size_t cig_lo = ~(size_t)0, cig_hi = 0; // the words of the CIGAR pool the tasks may write
 };
 static int validate_glb(bmh_ctx *ctx, const bmh_glb_task_t *tasks, int64_t n, size_t pool_bytes, bool have_cigar_pool, size_t cigar_words, GlbShape *o)
@@ -754,9 +775,14 @@ static int validate_glb(bmh_ctx *ctx, const bmh_glb_task_t *tasks, int64_t n, si
 			ctx->last_error = "global task " + std::to_string(k) + " has out-of-range offsets";
 			return BMH_E_ARG;
 		}
-		g.qmax = std::max(g.qmax, (int)x.qlen), g.tmax = std::max(g.tmax, (int)x.tlen);
-		g.wmax = std::max(g.wmax, std::min(x.w, (int)x.qlen)); // only min(qlen,2w+1) columns are ever stored
-		g.wraw = std::max(g.wraw, x.w);                        // ... but the device bins the tasks by their w as given
+		if (x.qlen <= kGlbLdsQcap) {
+			g.qmax = std::max(g.qmax, (int)x.qlen), g.tmax = std::max(g.tmax, (int)x.tlen);
+			g.wmax = std::max(g.wmax, std::min(x.w, (int)x.qlen)); // only min(qlen,2w+1) columns are ever stored
+		} else { // (a superset of what the device sends to bin 4: it only sizes that launch)
+			g.lg.qmax = std::max(g.lg.qmax, (int)x.qlen), g.lg.tmax = std::max(g.lg.tmax, (int)x.tlen);
+			g.lg.wmax = std::max(g.lg.wmax, std::min(x.w, (int)x.qlen)), ++g.lg.n;
+		}
+		g.wraw = std::max(g.wraw, x.w); // ... but the device bins the tasks by their w as given
 		if (x.cigar_cap) g.cig_lo = std::min(g.cig_lo, (size_t)x.cigar_off), g.cig_hi = std::max(g.cig_hi, (size_t)x.cigar_off + x.cigar_cap);
 	}
 	*o = g;
@@ -770,9 +796,12 @@ int bmh_global_batch_device(bmh_ctx_t *ctx, const uint8_t *d_pool, const bmh_glb
 	if (!ctx->have_params) return BMH_E_ARG;
 	if (n > 0xffffffffLL) return BMH_E_ARG;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	// no host view of the tasks: size for the context's capacity hint (square band-limited matrix)
-	return launch_global(ctx, d_pool, d_tasks, n, d_res, d_cigar, d_order, ctx->qcap, ctx->qcap + 2 * ctx->params.w + 64,
-	                     std::max(ctx->params.w * 4, 100), std::max(ctx->params.w * 4, 100));
+	// no host view of the tasks: size for the context's capacity hint (square band-limited matrix); a capacity past the LDS
+	// row's sends the longer tasks to bin 4, sized by the same hints
+	const int whint = std::max(ctx->params.w * 4, 100), q2 = std::min(ctx->qcap, kGlbLdsQcap);
+	GlbLongShape lg;
+	if (ctx->qcap > kGlbLdsQcap) lg.qmax = ctx->qcap, lg.tmax = ctx->qcap + 2 * ctx->params.w + 64, lg.wmax = whint, lg.n = n;
+	return launch_global(ctx, d_pool, d_tasks, n, d_res, d_cigar, d_order, q2, q2 + 2 * ctx->params.w + 64, whint, whint, &lg);
 }
 
 int bmh_global_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, const bmh_glb_task_t *tasks, int64_t n,
@@ -792,7 +821,7 @@ int bmh_global_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, con
 	const CigarDown cig{cigar_words, cigar_pool, 0, cigar_words};
 	return st.end(enqueue_batch(
 	    st, true, pool, pool_bytes, tasks, n, results,
-	    [&](bmh_ctx *c, auto p, auto t, auto r) { return launch_global(c, p, t, n, r, (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw); },
+	    [&](bmh_ctx *c, auto p, auto t, auto r) { return launch_global(c, p, t, n, r, (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw, &gs.lg); },
 	    &cig));
 }
 
@@ -859,7 +888,7 @@ int bmh_region_cigar_batch(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readp
 		if (n_tasks > 0 && (rc = st.h2d(ctx->d_tasks.p, tasks, (size_t)n_tasks * sizeof(bmh_glb_task_t)))) return rc;
 		if ((rc = launch_region_orient(ctx, (uint8_t *)ctx->d_pool.p, rpool_off, d_reqs, n_req))) return rc;
 		if (n_tasks > 0 && (rc = launch_global(ctx, (const uint8_t *)ctx->d_pool.p, (const bmh_glb_task_t *)ctx->d_tasks.p, n_tasks,
-		                                       (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw)))
+		                                       (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw, &gs.lg)))
 			return rc;
 		if ((rc = launch_region_finish(ctx, (const uint8_t *)ctx->d_pool.p, d_reqs, n_req, (const bmh_glb_task_t *)ctx->d_tasks.p,
 		                               (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p, d_rres, d_cout, cig_cap, d_md, md_cap)))
@@ -1043,7 +1072,7 @@ int bmh_global_batch_sharded(bmh_ctx_t *const *ctxs, int n_ctx, const uint8_t *p
 		    const CigarDown cig{cigar_words, back[g].data(), gs.cig_lo, back[g].size()};
 		    return enqueue_batch(
 		        st, false, pool, pool_bytes, tasks + lo, m, results + lo,
-		        [&](bmh_ctx *c, auto p, auto t, auto r) { return launch_global(c, p, t, m, r, (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw); },
+		        [&](bmh_ctx *c, auto p, auto t, auto r) { return launch_global(c, p, t, m, r, (uint32_t *)c->d_cigar.p, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw, &gs.lg); },
 		        &cig);
 	    });
 	if (rc && rc != BMH_E_CIGAR_CAP && rc != BMH_E_RANGE) return rc; // (a flagged task: the other tasks' results are still delivered)

@@ -44,7 +44,7 @@ struct bmh_ctx {
 	// pinned staging of the entry points that move bulk data per call from many host threads at once (the runtime's own
 	// path for pageable memory was the slowest part of a seeding batch: 5-36 ms for 11 MB with eight threads in flight)
 	DevBuf h_up, h_down;
-	int *d_err = nullptr; // device error flag (BMH_E_* or 0)
+	int *d_err = nullptr; // device error flag (BMH_E_* or 0) in [0]; [2..3]: bin 4's running task count (global_kernel.hip)
 	int *h_err = nullptr; // pinned mirror
 	// kernel timing
 	bool timing = false;
@@ -98,6 +98,9 @@ struct bmh_ctx {
 	double wide_ms_sum = 0.0;         // timing mode: the wide kernels' time over the same span
 	long long wide_total = 0;         // tasks the wide bin received over the host-buffer extension calls so far (preload shim log)
 	DevBuf d_wide_slab;               // per-block state slices of its HBM variant
+	// bin 4 of the global path (the band ring, global_kernel.hip): its tasks are counted on the device in d_err[2..3]
+	hipEvent_t ev_glong[2] = {};      // around its kernel (timing mode)
+	double glong_ms_sum = 0.0;        // timing mode: its time over the context's life (bmh_global_long_stats)
 };
 
 namespace bmh {
@@ -214,11 +217,38 @@ int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext
                        bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip = nullptr);
 int launch_extend_reg(bmh_ctx *ctx, int ns, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int max_count = 0, long long grid_cap = 0);
-// wmax: the widest band in stored columns (min(w, qlen)), sizes the wave kernel's direction matrix; wgate: the largest w
-// as the tasks carry it -- the device bins by that, so it decides which lane kernels are launched
+// The global wave kernel (global_kernel.hip) in LDS: H and E int32 [qcap+2] each, the profile 8 bytes [qcap], smat; up to
+// 160 KiB.  Queries up to kGlbLdsQcap columns; bin 4's ring variant holds 10 bytes per slot (H, E, two query bytes) in
+// power-of-two rings of up to kGlbRingMax slots, so bands with 2*min(w,qlen)+2 <= kGlbRingMax.
+constexpr size_t kGlbLdsBytes = 160 * 1024;
+constexpr size_t glb_state_bytes(int qcap) { return (size_t)8 * (qcap + 2) + (size_t)8 * qcap + 32; }
+constexpr size_t glb_ring_bytes(int ring) { return (size_t)10 * ring + 32; }
+constexpr int glb_lds_qcap()
+{
+	int q = 65536;
+	while (glb_state_bytes(q) > kGlbLdsBytes) q -= 64; // (the launch rounds qmax up to a multiple of 64)
+	return q;
+}
+constexpr int glb_ring_max()
+{
+	int r = 65536;
+	while (glb_ring_bytes(r) > kGlbLdsBytes) r >>= 1;
+	return r;
+}
+constexpr int kGlbLdsQcap = glb_lds_qcap();
+constexpr int kGlbRingMax = glb_ring_max();
+static_assert(kGlbLdsQcap == 10176 && kGlbRingMax == 8192, "the header states these bounds");
+// bin 4's tasks (qlen > kGlbLdsQcap): maxima of qlen, tlen and min(w, qlen), and how many; qmax = 0: no bin 4 in this launch
+struct GlbLongShape {
+	int qmax = 0, tmax = 0, wmax = 0;
+	int64_t n = 0;
+};
+// qmax, tmax, wmax: the bin-2 tasks' (qlen <= kGlbLdsQcap) maxima; wmax: the widest band in stored columns (min(w, qlen)),
+// sizes the wave kernel's direction matrix; wgate: the largest w as the tasks carry it -- the device bins by that, so it
+// decides which lane kernels are launched; lg: bin 4's shape, or null
 int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                   bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, int qmax, int tmax,
-                  int wmax, int wgate);
+                  int wmax, int wgate, const GlbLongShape *lg);
 
 int launch_region_orient(bmh_ctx *ctx, uint8_t *d_pool, size_t rpool_off, const bmh_region_req_t *d_reqs, int64_t n);
 int launch_region_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_region_req_t *d_reqs, int64_t n, const bmh_glb_task_t *d_tasks,

@@ -14,6 +14,7 @@
 //     one iteration emits a whole CIGAR run instead of one cell.
 //   * CIGAR words are produced last-op-first and stored from the back of the task's slot
 //     range, which leaves them in forward order; they are then moved to the front.
+//   * queries past the LDS row (kGlbLdsQcap columns) run with RING: H and E in a ring of band slots (bin 4).
 #include "bmh_ctx.h"
 #include "bmh_device.h"
 
@@ -42,7 +43,14 @@ struct CigarSink { // wave-uniform run-length CIGAR builder writing backwards fr
 	}
 };
 
-template <bool ZLDS>
+// One DP body, two state layouts.  RING = false: H, E and the profile of every query column in LDS (global_kernel, qcap =
+// query capacity).  RING = true: H and E of column j in slot j mod qcap of a ring of qcap slots (a power of two >=
+// 2*min(w,qlen)+2), the query bytes in a ring of 2*qcap, the cell's score formed from the query byte and the target base's
+// row of smat.  Only the addressing of H, E and the profile differs; the F scan, the hand-over between
+// chunks, the direction bytes and the traceback are the same code.  RING is bin 4's kernel: the tasks of bin 2 whose query
+// rows do not fit LDS, direction bytes in the HBM slab; its block 0 adds the bin's size to the context's running count in
+// err_flag[2..3] (bmh_global_long_stats).
+template <bool ZLDS, bool RING = false>
 __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ pool,
                                                     const bmh_glb_task_t *__restrict__ tasks,
                                                     const uint32_t *__restrict__ order,
@@ -53,17 +61,26 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
                                                     int *__restrict__ err_flag)
 {
 	extern __shared__ __align__(16) unsigned char smem[];
-	int *H = (int *)smem;                   // [qcap+2] shifted H = eh[j].h
-	int *E = H + (qcap + 2);                // [qcap+2]
-	uint2 *PR = (uint2 *)(E + (qcap + 2));  // [qcap]  (8-byte aligned: 2*(qcap+2) ints precede)
-	int8_t *smat = (int8_t *)(PR + qcap);   // [32]
-	uint8_t *zl = (uint8_t *)(smat + 32);   // [zcap] when ZLDS
+	int *H = (int *)smem;                              // [qcap+2] shifted H = eh[j].h  (RING: [qcap] slots)
+	int *E = H + (RING ? qcap : qcap + 2);             // [qcap+2]                      (RING: [qcap] slots)
+	uint2 *PR = (uint2 *)(E + (qcap + 2));             // [qcap]  (8-byte aligned: 2*(qcap+2) ints precede)
+	uint8_t *Q = (uint8_t *)(E + qcap);                // RING: [2*qcap] query bytes, column j in j mod 2*qcap
+	int8_t *smat = RING ? (int8_t *)(Q + 2 * qcap) : (int8_t *)(PR + qcap); // [32]
+	uint8_t *zl = (uint8_t *)(smat + 32);              // [zcap] when ZLDS
 	uint8_t *z = ZLDS ? zl : zscratch + (size_t)blockIdx.x * (size_t)zcap;
+	const int rmask = qcap - 1, qmask = 2 * qcap - 1;
 	const int lane = threadIdx.x;
 	const int oe_del = P.o_del + P.e_del, oe_ins = P.o_ins + P.e_ins;
 	const int e_del = P.e_del, e_ins = P.e_ins;
 
 	if (lane < 25) smat[lane] = (int8_t)mat_at(P, lane);
+	uint32_t mrow = 0; // RING: lane r < 5 holds smat row r (target base r against query bases 0-3) and its column 4
+	int mrow4 = 0;
+	if (RING && lane < 5) {
+		for (int k = 0; k < 4; ++k) mrow |= (uint32_t)(uint8_t)smat[lane * 5 + k] << (8 * k);
+		mrow4 = smat[lane * 5 + 4];
+	}
+	if (RING && blockIdx.x == 0 && lane == 0) atomicAdd((unsigned long long *)(err_flag + 2), (unsigned long long)(count ? *count : n));
 
 	if (count) n = *count; // bin size produced on the device by the dispatcher
 	for (long long slot = blockIdx.x; slot < n; slot += gridDim.x) {
@@ -79,7 +96,7 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 		const int n_col = min(qlen, 2 * w + 1); // ksw.c:509
 		const bool want = cigar_cap > 0;
 
-		if (qlen > qcap || w < 0 || (want && (long long)n_col * tlen > zcap)) {
+		if ((RING ? 2 * min(w, qlen) + 2 > qcap : qlen > qcap) || w < 0 || (want && (long long)n_col * tlen > zcap)) {
 			if (lane == 0) {
 				out[idx].score = INT32_MIN, out[idx].n_cigar = 0;
 				atomicExch(err_flag, BMH_E_RANGE);
@@ -88,14 +105,25 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 		}
 
 		// first row, ksw.c:519-522, and profile, ksw.c:514-517
-		for (int j = lane; j <= qlen; j += 64) {
-			H[j] = j == 0 ? 0 : (j <= w ? -(P.o_ins + e_ins * j) : kNegInf);
-			E[j] = kNegInf;
-			if (j < qlen) {
-				const int qb = pool[q_off + (uint64_t)j];
-				uint32_t lo = 0;
-				for (int k = 0; k < 4; ++k) lo |= (uint32_t)(uint8_t)smat[k * 5 + qb] << (8 * k);
-				PR[j] = make_uint2(lo, (uint32_t)(uint8_t)smat[20 + qb]);
+		const int wq = min(w, qlen);
+		if (!RING) {
+			for (int j = lane; j <= qlen; j += 64) {
+				H[j] = j == 0 ? 0 : (j <= w ? -(P.o_ins + e_ins * j) : kNegInf);
+				E[j] = kNegInf;
+				if (j < qlen) {
+					const int qb = pool[q_off + (uint64_t)j];
+					uint32_t lo = 0;
+					for (int k = 0; k < 4; ++k) lo |= (uint32_t)(uint8_t)smat[k * 5 + qb] << (8 * k);
+					PR[j] = make_uint2(lo, (uint32_t)(uint8_t)smat[20 + qb]);
+				}
+			}
+		} else {
+			// column j > w enters the band at row j-w and is written one row earlier as H[end], E[end] (ksw.c:563): only
+			// columns 0..min(qlen,w) need their initial values; the query bytes of the first band, the rest as the band slides
+			for (int j = lane; j <= wq; j += 64) {
+				H[j] = j == 0 ? 0 : -(P.o_ins + e_ins * j);
+				E[j] = kNegInf;
+				if (j < qlen) Q[j] = pool[q_off + (uint64_t)j];
 			}
 		}
 
@@ -110,6 +138,14 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 			}
 			const int tw = __builtin_amdgcn_readlane((int)tv, (i >> 2) & 63);
 			const int t = (tw >> ((i & 3) * 8)) & 0xff;
+			int rlo = 0, r4 = 0;
+			if (RING) {
+				// every 64 rows: the query bytes of the next 64 columns to enter the band, i+w+1 .. i+w+64.  The columns 2*qcap
+				// before them, whose slots they take, left the band before this row (2*qcap >= 2*w + 66: qcap >= 64 and >= 2*w + 2)
+				const int c = i + wq + 1 + lane;
+				if ((i & 63) == 0 && c < qlen) Q[c & qmask] = pool[q_off + (uint64_t)c];
+				rlo = __builtin_amdgcn_readlane((int)mrow, t < 4 ? t : 4), r4 = __builtin_amdgcn_readlane(mrow4, t < 4 ? t : 4);
+			}
 			const int beg = i > w ? i - w : 0;
 			const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
 			int carry_h = beg == 0 ? -(P.o_del + e_del * (i + 1)) : kNegInf; // ksw.c:530
@@ -118,10 +154,16 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 			for (int cb = beg; cb < end; cb += 64) {
 				const int j = cb + lane;
 				const bool act = j < end;
-				int hs = 0, e = 0;
+				const int js = RING ? j & rmask : j;
+				int hs = 0, e = 0, qb = 0;
 				uint2 pr = make_uint2(0, 0);
-				if (act) hs = H[j], e = E[j], pr = PR[j];
-				const int s = t < 4 ? (int)(int8_t)(pr.x >> (t * 8)) : (int)(int8_t)pr.y;
+				if (act) {
+					hs = H[js], e = E[js];
+					if (RING) qb = Q[j & qmask];
+					else pr = PR[j];
+				}
+				const int s = RING ? (qb < 4 ? (int)(int8_t)((uint32_t)rlo >> (qb * 8)) : r4)
+				                   : t < 4 ? (int)(int8_t)(pr.x >> (t * 8)) : (int)(int8_t)pr.y;
 				const int mm = hs + s;
 				// F(i,j) = max(fin - (j-cb)*e_ins, max_{k<j}(mm_k - oe_ins - (j-1-k)*e_ins))
 				const int g = act ? mm - oe_ins + lane * e_ins : INT32_MIN / 2;
@@ -138,7 +180,7 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 				d |= f - e_ins > mm - oe_ins ? 2 << 4 : 0; // ksw.c:557-559
 				const int hprev = wave_shr1(h, carry_h);
 				if (act) {
-					H[j] = hprev, E[j] = en;
+					H[js] = hprev, E[js] = en;
 					if (want) zi[j - beg] = (uint8_t)d; // ksw.c:561
 				}
 				const int nact = end - cb;
@@ -147,9 +189,11 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 					fin = max(fin - 64 * e_ins, __builtin_amdgcn_readlane(pm, 63) - 63 * e_ins);
 				} else carry_h = __builtin_amdgcn_readlane(h, nact - 1);
 			}
-			if (lane == 0 && end >= 0) H[end] = carry_h, E[end] = kNegInf; // ksw.c:563
+			if (lane == 0 && end >= 0) H[RING ? end & rmask : end] = carry_h, E[RING ? end & rmask : end] = kNegInf; // ksw.c:563
 		}
-		const int score = uni(H[qlen]); // ksw.c:565
+		// ksw.c:565.  When the last row's band ends short of qlen (qlen > tlen + w) no row wrote eh[qlen]: the reference returns its
+		// initial value, -inf (qlen > w), which the whole-row layout still holds and the ring does not
+		const int score = RING ? (qlen > tlen + w ? kNegInf : uni(H[qlen & rmask])) : uni(H[qlen]);
 
 		int n_cigar = 0;
 		if (want) { // traceback, ksw.c:566-581
@@ -214,11 +258,13 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 //        49 registers: not used)
 // bin 2: wider bands, targets longer than the lane kernels' direction slab, or scores that could leave the
 //        16-bit range -> global_kernel (one wave per task, int32 in LDS)
+// bin 4: the tasks of bin 2 with more query columns than its LDS row holds (kGlbLdsQcap), when the launch has a bin 4 at all
+//        (lds_qcap < 65535) -> global_kernel<false, true> (the band ring)
 // Bins and the order inside them (by row count) come from the same device-side counting sort as the extension path.
 __global__ __launch_bounds__(256) void glb_sort_hist_kernel(const bmh_glb_task_t *__restrict__ tasks,
                                                             const uint32_t *__restrict__ order, long long n,
                                                             uint32_t *__restrict__ hist, uint16_t *__restrict__ binkey,
-                                                            DevParams P, int lane_ok, int rows_cap)
+                                                            DevParams P, int lane_ok, int rows_cap, int lds_qcap)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += 256) lh[t] = 0;
@@ -233,10 +279,11 @@ __global__ __launch_bounds__(256) void glb_sort_hist_kernel(const bmh_glb_task_t
 		// (the lane kernels take the sign of 16-bit differences such as m - e - o_del: with |m|, |e| < 12000 and the -16384 sentinel that
 		// stays inside +-32767 as long as the gap-open penalties are not absurd)
 		if (lane_ok && tlen <= rows_cap && worst < 12000 && P.o_del + P.o_ins < 4000 && w >= 0) bin = w <= 31 ? 0 : w <= 47 ? 3 : (w <= 63 ? 1 : 2);
+		if (bin == 2 && qlen > lds_qcap) bin = 4;
 		// inside a lane bin: rows first (lanes of a wave run until their longest target ends), then band width (a wave
 		// computes and stores the 8-slot blocks that ANY of its lanes needs, and its lanes' tracebacks share cache lines
 		// when they sit in the same block)
-		const int bk = bin * kSortKeysHost + (bin != 2 ? (min(tlen >> 3, 127) << 4 | (min(w, 63) >> (bin == 0 ? 1 : 2) & 15)) : 0);
+		const int bk = bin * kSortKeysHost + (bin != 2 && bin != 4 ? (min(tlen >> 3, 127) << 4 | (min(w, 63) >> (bin == 0 ? 1 : 2) & 15)) : 0);
 		binkey[k] = (uint16_t)bk;
 		atomicAdd(&lh[bk], 1u);
 	}
@@ -247,13 +294,46 @@ __global__ __launch_bounds__(256) void glb_sort_hist_kernel(const bmh_glb_task_t
 
 int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                   bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, int qmax, int tmax,
-                  int wmax, int wgate)
+                  int wmax, int wgate, const GlbLongShape *lg)
 {
 	if (n <= 0) return BMH_OK;
 	int rc;
 	const size_t N = (size_t)n;
 	const bool lane_ok = ctx->glb_mode == 0;
-	const int rows_cap = tmax < 512 ? tmax : 512; // rows of the lane kernels' direction slab
+	const bool longb = lg && lg->qmax > 0; // bin 4 is launched: the tasks of bin 2 past kGlbLdsQcap go to the ring
+	const int rows_cap = std::max(tmax, longb ? lg->tmax : 0) < 512 ? std::max(tmax, longb ? lg->tmax : 0) : 512; // rows of the lane kernels' direction slab
+	// plan both wave launches first: they share the HBM slab of direction bytes, which grows once, before either runs
+	const long long budget = 8LL << 30; // HBM scratch for direction bytes, one slab per resident block
+	const int qcap = (std::min(qmax, kGlbLdsQcap) + 63) & ~63;
+	const size_t state = glb_state_bytes(qcap);
+	const long long ncol = qmax < 2LL * wmax + 1 ? qmax : 2LL * wmax + 1;
+	long long zcap = ncol * (long long)tmax;
+	zcap = (zcap + 15) & ~15LL;
+	if (zcap < 16) zcap = 16;
+	if (state > kGlbLdsBytes) return BMH_E_RANGE;
+	const bool zlds = state + (size_t)zcap <= 64 * 1024; // keep >= 2 blocks per CU in the LDS variant
+	long long grid = n < (1LL << 20) ? n : (1LL << 20);
+	if (lane_ok && grid > 8192) grid = 8192; // normally (almost) empty when the lane kernels are on
+	if (!zlds) {
+		long long g = budget / zcap;
+		if (g < 1) return BMH_E_RANGE;
+		if (g > 8192) g = 8192;
+		if (grid > g) grid = g;
+	}
+	int ring = 64;
+	long long zcap4 = 16, grid4 = 0;
+	if (longb) { // bin 4: a ring of 2*min(w,qlen)+2 slots or more (up to kGlbRingMax) and its own slab, sized by the long tasks alone
+		const int wq = std::min(lg->wmax, lg->qmax);
+		while (ring < 2 * wq + 2 && ring < kGlbRingMax) ring <<= 1; // (a task past the largest ring is refused by the kernel)
+		zcap4 = (std::min<long long>(lg->qmax, 2LL * lg->wmax + 1) * (long long)lg->tmax + 15) & ~15LL;
+		if (zcap4 < 16) zcap4 = 16;
+		long long g = budget / zcap4;
+		if (g < 1) return BMH_E_RANGE;
+		grid4 = std::min<long long>({g, 8192, std::max<int64_t>(lg->n, 1)});
+	}
+	const size_t slab = std::max(zlds ? 0 : (size_t)grid * (size_t)zcap, longb ? (size_t)grid4 * (size_t)zcap4 : 0);
+	if (slab && (rc = ensure(ctx, ctx->d_scratch, slab))) return rc;
+
 	uint32_t *counts, *lists;
 	if ((rc = sort_tasks_begin(ctx, n, &counts, &lists))) return rc;
 	uint32_t *hist = counts + 16;
@@ -261,7 +341,7 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
 	long long cg = (n + 1023) / 1024;
 	if (cg > 512) cg = 512;
 	hipLaunchKernelGGL(glb_sort_hist_kernel, dim3((unsigned)cg), dim3(256), 0, ctx->stream, d_tasks, d_order, (long long)n, hist,
-	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap);
+	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap, longb ? kGlbLdsQcap : 65535);
 	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg))) return rc;
 	const bool tm = ctx->timing;
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -278,35 +358,37 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[2], ctx->stream));
 	{ // bin 2: the wave kernel
 		const uint32_t *lst = lists + 2 * N, *cnt = counts + 2;
-		const int qcap = (qmax + 63) & ~63;
-		const size_t state = (size_t)8 * (qcap + 2) + (size_t)8 * qcap + 32;
-		const long long ncol = qmax < 2LL * wmax + 1 ? qmax : 2LL * wmax + 1;
-		long long zcap = ncol * (long long)tmax;
-		zcap = (zcap + 15) & ~15LL;
-		if (zcap < 16) zcap = 16;
-		if (state > 160 * 1024) return BMH_E_RANGE;
-		const bool zlds = state + (size_t)zcap <= 64 * 1024; // keep >= 2 blocks per CU in the LDS variant
-		long long grid = n < (1LL << 20) ? n : (1LL << 20);
-		if (lane_ok && grid > 8192) grid = 8192; // normally (almost) empty when the lane kernels are on
 		if (zlds) {
 			hipLaunchKernelGGL(global_kernel<true>, dim3((unsigned)grid), dim3(64), state + (size_t)zcap, ctx->stream, d_pool,
 			                   d_tasks, lst, cnt, (long long)n, d_res, d_cigar, ctx->dev, qcap, zcap, (uint8_t *)nullptr, ctx->d_err);
 		} else {
-			long long budget = 8LL << 30; // HBM scratch for direction bytes, one slab per resident block
-			long long g = budget / zcap;
-			if (g < 1) return BMH_E_RANGE;
-			if (g > 8192) g = 8192;
-			if (grid > g) grid = g;
-			if ((rc = ensure(ctx, ctx->d_scratch, (size_t)grid * (size_t)zcap))) return rc;
 			hipLaunchKernelGGL(global_kernel<false>, dim3((unsigned)grid), dim3(64), state, ctx->stream, d_pool, d_tasks, lst, cnt,
 			                   (long long)n, d_res, d_cigar, ctx->dev, qcap, zcap, (uint8_t *)ctx->d_scratch.p, ctx->d_err);
 		}
 		BMH_HIP(ctx, hipGetLastError());
 	}
+	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[3], ctx->stream));
+	if (longb) { // bin 4: the band ring, after bin 2 on the same stream (the two share the slab)
+		if (tm && !ctx->ev_glong[0]) {
+			BMH_HIP(ctx, hipEventCreate(&ctx->ev_glong[0]));
+			BMH_HIP(ctx, hipEventCreate(&ctx->ev_glong[1]));
+		}
+		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_glong[0], ctx->stream));
+		hipLaunchKernelGGL((global_kernel<false, true>), dim3((unsigned)grid4), dim3(64), glb_ring_bytes(ring), ctx->stream, d_pool, d_tasks,
+		                   lists + 4 * N, counts + 4, (long long)n, d_res, d_cigar, ctx->dev, ring, zcap4, (uint8_t *)ctx->d_scratch.p,
+		                   ctx->d_err);
+		BMH_HIP(ctx, hipGetLastError());
+		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_glong[1], ctx->stream));
+	}
 	if (tm) {
-		BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[3], ctx->stream));
 		BMH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
 		ctx->ev_valid = true, ctx->ev_gbin_valid = lane_ok;
+		if (longb) { // (a measurement mode: wait, and add the ring's time to the running sum bmh_global_long_stats reports)
+			float ms = 0.f;
+			BMH_HIP(ctx, hipEventSynchronize(ctx->ev_glong[1]));
+			BMH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_glong[0], ctx->ev_glong[1]));
+			ctx->glong_ms_sum += ms;
+		}
 	}
 	return BMH_OK;
 }

@@ -42,7 +42,8 @@ static int pool_device(int nth)
 /* Workspaces of a context that will see the shim's batches -- up to 64 k reads of phase 1 (reads, windows, SMEM tables
  * coming back), a slice of a chunk in phase 2 -- sized once, so that no batch in the middle of a run has to grow them
  * ($BMH_RESERVE_MB scales the figures; 0 turns the reservation off). */
-int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx); /* internal hook of api.hip */
+int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx);  /* internal hook of api.hip */
+int64_t bmh_ctx_glong_tasks_(const bmh_ctx_t *ctx); /* internal hook of api.hip (waits for the context's stream) */
 
 int bmh_pool_wide(void)
 {
@@ -60,6 +61,16 @@ long long bmh_pool_wide_tasks(void)
 	int i;
 	pthread_mutex_lock(&g_mu);
 	for (i = 0; i < g_n; ++i) t += g_slots[i].ctx ? (long long)bmh_ctx_wide_tasks_(g_slots[i].ctx) : 0;
+	pthread_mutex_unlock(&g_mu);
+	return t;
+}
+
+long long bmh_pool_glong_tasks(void)
+{
+	long long t = 0;
+	int i;
+	pthread_mutex_lock(&g_mu);
+	for (i = 0; i < g_n; ++i) t += g_slots[i].ctx ? (long long)bmh_ctx_glong_tasks_(g_slots[i].ctx) : 0;
 	pthread_mutex_unlock(&g_mu);
 	return t;
 }

@@ -18,4 +18,6 @@ void bmh_tls_die(const char *msg, int code);
 int bmh_pool_wide(void);
 /* extension tasks the pool's contexts sent to the int32 kernel so far (host-buffer calls) */
 long long bmh_pool_wide_tasks(void);
+/* global alignments the pool's contexts have sent to the band-ring kernel so far (bmh_global_long_stats) */
+long long bmh_pool_glong_tasks(void);
 #endif

@@ -110,10 +110,16 @@ typedef struct bmh_glb_result {
  *           h0 + qlen*max(mat) <= 2^24 (bmh_seedext_batch: l_query*max(max(mat), a) <= 2^24), any query up to 65535
  *           (with *_device calls: up to bmh_ctx_set_qcap), any gap costs >= the minimums of bmh_ctx_set_params.  The
  *           fused record keeps its flank bound of 65535 and 2*w <= 32767.  Tasks inside the range above keep their kernels.
- *           Not covered: mate rescue (bmh_sw_batch / bmh_matesw_batch, qlen*max(mat) < 32000) and the 65535 limits of
- *           bmh_global_batch and bmh_reg2cigar_batch, so paired-end long reads can still stop there; and the global wave kernel
- *           holds 16 bytes per query column in LDS, so regions past 10 176 query columns are refused in phase 2.
- *   global: qlen,tlen <= 65535. */
+ *           Not covered: mate rescue (bmh_sw_batch / bmh_matesw_batch, qlen*max(mat) < 32000), so paired-end long reads can
+ *           still stop there; and the 65535 limits of bmh_global_batch and bmh_reg2cigar_batch below.
+ *   global: qlen,tlen <= 65535 (the uint16 fields of bmh_glb_task_t).  Tasks with up to 10 176 query columns keep H, E and the
+ *           profile of the whole row in LDS (16 bytes per column).  Longer ones that no lane kernel takes go to a band-ring
+ *           kernel, whose LDS holds 2*min(w,qlen)+2 columns or more, rounded up to a power of two, at 10 bytes each: bands
+ *           with min(w,qlen) <= 4 095 (bmh_global_long_stats counts its tasks).  The direction bytes of every wave-kernel task,
+ *           min(qlen,2w+1)*tlen, must fit an 8 GiB slab.  Past these, BMH_E_RANGE: for host-buffer calls the batch when a
+ *           direction slab does not fit, the task (the rest are delivered) when its band does not fit the ring; *_device calls
+ *           size both kernels from bmh_ctx_set_qcap and a band of max(4w,100) and flag the tasks beyond them.
+ *           A CIGAR task must let its band reach the end cell (tlen <= qlen + w, qlen <= tlen + w); score-only tasks may not. */
 
 typedef struct bmh_ctx bmh_ctx_t;
 
@@ -258,6 +264,10 @@ int bmh_extend_wide_stats(const bmh_ctx_t *ctx, int64_t *tasks, float *ms);
 /* Per-kernel duration of the last global-alignment launch: the 64-slot lane kernel (w <= 31), the 128-slot one (w <= 63),
  * the one-wave-per-task kernel (everything else).  -1 when timing was off. */
 int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3]);
+/* What the global-alignment launches of this context so far sent to bin 4, the band-ring kernel (tasks with more than 10 176
+ * query columns that no lane kernel takes): *tasks = their number, *ms = the ring kernel's time summed over the launches made
+ * with timing on (-1 when timing is off).  The counterpart of bmh_extend_wide_stats.  Waits for the stream. */
+int bmh_global_long_stats(const bmh_ctx_t *ctx, int64_t *tasks, float *ms);
 /* Duration of the four rounds of the last fused per-seed launch (left, left at 2w, right, right at 2w), each with the
  * small list-building kernel in front of it.  -1 when timing was off. */
 int bmh_last_seedext_round_ms(bmh_ctx_t *ctx, float ms[4]);
