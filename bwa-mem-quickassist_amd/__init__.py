@@ -146,6 +146,8 @@ def lib():
         L.bmh_extend_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_global_long_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_ctx_reserve_staging.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
+        L.bmh_ctx_reserve_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int64, C.c_size_t]
+        L.bmh_ctx_reserve_kernels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int]
         L.bmh_ctx_set_pac.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
         L.bmh_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -199,6 +201,10 @@ _libc.malloc.argtypes = [C.c_size_t]
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _nbytes(a):
+    return a.nbytes if a is not None else 0
 
 
 class Context:
@@ -267,6 +273,14 @@ class Context:
         """Pinned staging buffers of the host-buffer entry points, allocated ahead of the first batch."""
         self._check(lib().bmh_ctx_reserve_staging(self._h, int(upload_bytes), int(download_bytes)))
 
+    def reserve_device(self, pool_bytes, max_tasks, cigar_words):
+        """Device workspaces of the host-buffer entry points, allocated ahead of the first batch (bmh_ctx_reserve_device)."""
+        self._check(lib().bmh_ctx_reserve_device(self._h, int(pool_bytes), int(max_tasks), int(cigar_words)))
+
+    def reserve_kernels(self, seed_reads, seed_read_len, global_tasks, global_rows):
+        """Kernel scratch of the SMEM and global lane kernels, allocated ahead of the first batch (bmh_ctx_reserve_kernels)."""
+        self._check(lib().bmh_ctx_reserve_kernels(self._h, int(seed_reads), int(seed_read_len), int(global_tasks), int(global_rows)))
+
     def sync(self):
         self._check(lib().bmh_ctx_sync(self._h))
 
@@ -301,21 +315,42 @@ class Context:
         return [float(x) for x in ms]
 
     # ---- L2, host buffers
-    def extend_batch(self, pool, tasks):
-        """N x ksw_extend2 (reference ksw.c:379).  numpy in, numpy out."""
+    def upload_pool(self, pool):
+        """Leave a sequence pool resident on the device (bmh_upload_pool): extend_batch / global_batch / seedext_batch with
+        pool=None and seedext_submit run against it."""
         pool = np.ascontiguousarray(pool, dtype=np.uint8)
+        self._check(lib().bmh_upload_pool(self._h, _ptr(pool), pool.nbytes))
+
+    def extend_batch(self, pool, tasks):
+        """N x ksw_extend2 (reference ksw.c:379).  numpy in, numpy out; pool=None: the pool left by upload_pool()."""
+        pool = None if pool is None else np.ascontiguousarray(pool, dtype=np.uint8)
         tasks = np.ascontiguousarray(tasks, dtype=EXT_TASK)
         res = np.zeros(len(tasks), dtype=EXT_RES)
-        self._check(lib().bmh_extend_batch(self._h, _ptr(pool), pool.nbytes, _ptr(tasks), len(tasks), _ptr(res)))
+        self._check(lib().bmh_extend_batch(self._h, _ptr(pool), _nbytes(pool), _ptr(tasks), len(tasks), _ptr(res)))
         return res
 
     def seedext_batch(self, pool, tasks):
         """N x (left extension, clip decision, right extension from the left score): the fused per-seed record
-        (reference bwamem.c:810-866; ext_param_t / ext_res_t :553-577).  numpy in, numpy out."""
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
+        (reference bwamem.c:810-866; ext_param_t / ext_res_t :553-577).  numpy in, numpy out; pool=None: the pool left by
+        upload_pool()."""
+        pool = None if pool is None else np.ascontiguousarray(pool, dtype=np.uint8)
         tasks = np.ascontiguousarray(tasks, dtype=SEED_TASK)
         res = np.zeros(len(tasks), dtype=SEED_RES)
-        self._check(lib().bmh_seedext_batch(self._h, _ptr(pool), pool.nbytes, _ptr(tasks), len(tasks), _ptr(res)))
+        self._check(lib().bmh_seedext_batch(self._h, _ptr(pool), _nbytes(pool), _ptr(tasks), len(tasks), _ptr(res)))
+        return res
+
+    def seedext_submit(self, tasks):
+        """First half of the two-step fused per-seed call (bmh_seedext_submit): stages the seeds and enqueues everything
+        against the pool left by upload_pool(), then returns; seedext_wait() delivers the records."""
+        tasks = np.ascontiguousarray(tasks, dtype=SEED_TASK)
+        self._check(lib().bmh_seedext_submit(self._h, _ptr(tasks), len(tasks)))
+        self._seed_pending = len(tasks)
+
+    def seedext_wait(self):
+        """Second half (bmh_seedext_wait): blocks until the submitted seeds' records are there and returns them."""
+        n, self._seed_pending = getattr(self, "_seed_pending", None) or 0, None
+        res = np.zeros(n, dtype=SEED_RES)
+        self._check(lib().bmh_seedext_wait(self._h, _ptr(res) if n else None))
         return res
 
     def seedext_batch_device(self, d_pool, d_tasks, n, d_res):
@@ -327,12 +362,12 @@ class Context:
         return dict(zip(("seeds", "left_tasks", "left_retries", "right_tasks", "right_retries"), [int(x) for x in st]))
 
     def global_batch(self, pool, tasks, cigar_words):
-        """N x ksw_global2 (reference ksw.c:501).  Returns (results, cigar_pool)."""
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
+        """N x ksw_global2 (reference ksw.c:501).  Returns (results, cigar_pool); pool=None: the pool left by upload_pool()."""
+        pool = None if pool is None else np.ascontiguousarray(pool, dtype=np.uint8)
         tasks = np.ascontiguousarray(tasks, dtype=GLB_TASK)
         res = np.zeros(len(tasks), dtype=GLB_RES)
         cig = np.zeros(max(int(cigar_words), 1), dtype=np.uint32)
-        self._check(lib().bmh_global_batch(self._h, _ptr(pool), pool.nbytes, _ptr(tasks), len(tasks), _ptr(res),
+        self._check(lib().bmh_global_batch(self._h, _ptr(pool), _nbytes(pool), _ptr(tasks), len(tasks), _ptr(res),
                                            _ptr(cig), int(cigar_words)))
         return res, cig
 

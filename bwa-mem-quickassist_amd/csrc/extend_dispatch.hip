@@ -9,6 +9,8 @@
 //   bin 5: longer or qlen == 0                     extend_lds_kernel  (one wave per task)
 //   bin 6: only with bmh_ctx_set_wide_extension on: what the 16-bit kernels cannot take -- h0 + qlen*max(mat) > 32000 or
 //          qlen > kLdsQcap, or every task when the gap costs fail ext_gaps_too_large -> extend_wide_kernel (int32)
+//   bin 7: qlen > the launch's qmax (only a *_device call's qcap can be below a query length): no kernel; the sort writes the
+//          failure record and raises BMH_E_RANGE, so that the bins qmax calls empty can be left out
 // BMH_EXT_MODE=reg | grp | lds in the environment selects the one-task-per-wave register kernels, the
 // four-tasks-per-wave group kernels, or the LDS kernel for bins 0-2 instead (A/B runs, profiles/); BMH_EXT_MODE=wide sends every
 // task of a context with the switch on to bin 6 (A/B against the 16-bit kernels; no effect with the switch off).
@@ -58,12 +60,16 @@ __device__ __forceinline__ int ext_sort_key(int bin, int qlen, int tlen, int h0)
 constexpr int kSortBlocks = 512, kSortThreads = 256;
 constexpr int kLanexMinTasks = 4096; // below this many 129-256 bp flanks one wave per task fills the chip better
 
+constexpr int kCapBin = 7; // tasks past the launch's qmax: listed, never launched
+
 // pass 1: per-block histogram in LDS over a contiguous chunk, flushed with one global atomic per used key
 __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_task_t *__restrict__ tasks,
                                                                  const uint32_t *__restrict__ order, long long n,
                                                                  uint32_t *__restrict__ hist,
                                                                  uint16_t *__restrict__ binkey, int mode,
-                                                                 const uint32_t *__restrict__ dn, int wide, int max_mat)
+                                                                 const uint32_t *__restrict__ dn, int wide, int max_mat,
+                                                                 int qmax, bmh_ext_result_t *__restrict__ out,
+                                                                 int *__restrict__ err_flag)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeys];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kSortThreads) lh[t] = 0;
@@ -74,8 +80,15 @@ __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_t
 		const uint32_t idx = order ? order[k] : (uint32_t)k;
 		const int qlen = tasks[idx].qlen, tlen = tasks[idx].tlen;
 		const int h0 = tasks[idx].h0;
-		// wide: 0 switch off, 1 per task, 2 every task
-		const int bin = wide && (wide == 2 || ext_goes_wide(qlen, h0, max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, mode);
+		// wide: 0 switch off, 1 per task, 2 every task.  Past qmax: the failure record of the kernels, here, since the bins
+		// that qmax calls empty are not launched
+		const bool over = qlen > qmax;
+		const int bin = over ? kCapBin : wide && (wide == 2 || ext_goes_wide(qlen, h0, max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, mode);
+		if (over) {
+			int *p = (int *)(out + idx);
+			p[0] = INT32_MIN, p[1] = p[2] = p[3] = p[4] = p[5] = 0;
+			atomicExch(err_flag, BMH_E_RANGE);
+		}
 		const int bk = bin * kSortKeys + ext_sort_key(bin, qlen, tlen, h0);
 		binkey[k] = (uint16_t)bk;
 		atomicAdd(&lh[bk], 1u);
@@ -258,7 +271,7 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 	if (cg > kSortBlocks) cg = kSortBlocks;
 	if (cg < 1) cg = 1;
 	hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)cg), dim3(kSortThreads), 0, ctx->stream, d_tasks, d_order, (long long)n,
-	                   hist, binkey, mode, d_n, wide, ctx->dev.max_mat);
+	                   hist, binkey, mode, d_n, wide, ctx->dev.max_mat, qmax, d_res, ctx->d_err);
 	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg, d_n))) return rc;
 	if ((rc = hint_post(ctx, kind, counts))) return rc;
 	const bool tm = ctx->timing;

@@ -31,6 +31,7 @@ namespace bmh {
 struct SeedP { // the driver-level fields of bmh_params_t
 	int a, w, pen_clip5, pen_clip3, max_mat;
 	int limit; // bound of l_query*max(max(mat), a): kScoreLimit, or kWideScoreLimit with the wide extension on
+	int qmax;  // longest flank the launch takes (a *_device call's qcap)
 };
 
 struct SeedState { // what the left side leaves for the right side and the end (24 bytes)
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void seed_left_make(const bmh_seed_task_t *__r
 		const bmh_seed_task_t s = S[i];
 		const int rq = s.l_query - s.qbeg - s.len, rt = s.wlen - s.rbeg - s.len;
 		if (s.qbeg < 0 || s.len <= 0 || rq < 0 || s.rbeg < 0 || rt < 0 || s.qbeg > 65535 || rq > 65535 || s.rbeg > 65535 || rt > 65535 ||
-		    (long long)s.l_query * max(sp.max_mat, sp.a) > sp.limit) {
+		    (long long)s.l_query * max(sp.max_mat, sp.a) > sp.limit || s.qbeg > sp.qmax || rq > sp.qmax) {
 			atomicExch(err_flag, BMH_E_RANGE);
 			SeedState st = {0, 0, -1, -1, sp.w, 0xffffffffu}; // poisoned: later stages skip the seed
 			ST[i] = st;
@@ -225,7 +226,7 @@ int launch_seedext(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_seed_task_t *d
 	if (rc) return rc;
 	if ((rc = wide_stats_begin(ctx))) return rc; // the four rounds below add up in bmh_extend_wide_stats
 	const SeedP sp = {ctx->params.a, ctx->params.w, ctx->params.pen_clip5, ctx->params.pen_clip3, ctx->dev.max_mat,
-	                  ctx->wide_ext ? kWideScoreLimit : kScoreLimit};
+	                  ctx->wide_ext ? kWideScoreLimit : kScoreLimit, qmax};
 	const unsigned grid = (unsigned)((n + 255) / 256);
 	hipStream_t s = ctx->stream;
 	const bool tm = ctx->timing;

@@ -143,7 +143,11 @@ int bmh_ctx_sync(bmh_ctx_t *ctx); /* waits for the stream; returns a pending BMH
  * to 2^24, queries up to 65535 and gap costs past 16 bits.  Off by default; the default context refuses them as before. */
 int bmh_ctx_set_wide_extension(bmh_ctx_t *ctx, int enable);
 /* Capacity hint for the *_device entry points, which cannot look at the tasks on the host:
- * the longest query the launch must handle (default 512).  Longer tasks fail with BMH_E_RANGE. */
+ * the longest query the launch must handle (default 512).  bmh_extend_batch_device and bmh_seedext_batch_device fail longer
+ * queries with BMH_E_RANGE (bmh_ctx_sync returns it) and deliver the other tasks of the call: an extension task longer than
+ * qcap gets the failure record score = INT32_MIN, the other fields 0; a seed with a left or right flank longer than qcap gets
+ * the record of a seed outside the supported range, score = truesc = INT32_MIN, the other fields 0.  For
+ * bmh_global_batch_device see "Supported range" above.  The host-buffer entry points ignore qcap. */
 int bmh_ctx_set_qcap(bmh_ctx_t *ctx, int max_qlen);
 
 /* A process-wide gate around the DEVICE SECTIONS of the host-buffer entry points below (upload, kernels, download):
