@@ -145,6 +145,8 @@ def lib():
         L.bmh_ctx_set_wide_extension.argtypes = [C.c_void_p, C.c_int]
         L.bmh_extend_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_global_long_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.bmh_ctx_set_wide_sw.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_sw_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_ctx_reserve_staging.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
         L.bmh_ctx_reserve_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int64, C.c_size_t]
         L.bmh_ctx_reserve_kernels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int]
@@ -267,6 +269,19 @@ class Context:
         columns); ms sums its kernel time over the launches made with timing on, -1 with timing off (bmh_global_long_stats)."""
         n, ms = C.c_int64(0), C.c_float(-1)
         self._check(lib().bmh_global_long_stats(self._h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
+
+    def set_wide_sw(self, on=True):
+        """Opt in to the long-query Smith-Waterman kernel: word-mode ksw_align2 tasks past qlen*max(mat) >= 32000 are accepted
+        (saturating as the reference does), and every word-mode task the slab kernel would take runs on one wave per task
+        (bmh_ctx_set_wide_sw)."""
+        self._check(lib().bmh_ctx_set_wide_sw(self._h, 1 if on else 0))
+
+    def sw_wide_stats(self):
+        """(tasks, ms) this context's Smith-Waterman launches have sent to the long-query kernel so far; ms sums its kernel time
+        over the launches made with timing on, -1 with timing off (bmh_sw_wide_stats)."""
+        n, ms = C.c_int64(0), C.c_float(-1)
+        self._check(lib().bmh_sw_wide_stats(self._h, C.byref(n), C.byref(ms)))
         return int(n.value), float(ms.value)
 
     def reserve_staging(self, upload_bytes, download_bytes):

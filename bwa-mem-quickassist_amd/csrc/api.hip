@@ -296,6 +296,8 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
 	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
+	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
+	free_buf(ctx->d_swl);
 	for (auto &e : ctx->ev_chain)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
@@ -319,6 +321,8 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 		if (ctx->ev_gbin[b]) (void)hipEventDestroy(ctx->ev_gbin[b]);
 	for (int b = 0; b < 2; ++b)
 		if (ctx->ev_glong[b]) (void)hipEventDestroy(ctx->ev_glong[b]);
+	for (int b = 0; b < 2; ++b)
+		if (ctx->ev_swl[b]) (void)hipEventDestroy(ctx->ev_swl[b]);
 	for (int b = 0; b < 5; ++b)
 		if (ctx->ev_sround[b]) (void)hipEventDestroy(ctx->ev_sround[b]);
 	if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -446,6 +450,33 @@ int bmh_ctx_set_wide_extension(bmh_ctx_t *ctx, int enable)
 		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
 	}
 	ctx->wide_ext = enable != 0;
+	return BMH_OK;
+}
+
+int bmh_ctx_set_wide_sw(bmh_ctx_t *ctx, int enable)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (enable && !ctx->d_swl_stat) {
+		BMH_HIP(ctx, hipSetDevice(ctx->device));
+		BMH_HIP(ctx, hipMalloc((void **)&ctx->d_swl_stat, sizeof(unsigned long long)));
+		BMH_HIP(ctx, hipMemsetAsync(ctx->d_swl_stat, 0, sizeof(unsigned long long), ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	}
+	ctx->wide_sw = enable != 0;
+	return BMH_OK;
+}
+
+int bmh_sw_wide_stats(const bmh_ctx_t *cctx, int64_t *tasks, float *ms)
+{
+	if (!cctx || !tasks || !ms) return BMH_E_ARG;
+	bmh_ctx *ctx = const_cast<bmh_ctx *>(cctx); // (waits for the stream; the context's settings are not touched)
+	*tasks = 0, *ms = ctx->timing ? (float)ctx->swl_ms_sum : -1.f;
+	if (!ctx->d_swl_stat) return BMH_OK; // (never turned on)
+	unsigned long long c = 0;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, hipMemcpyAsync(&c, ctx->d_swl_stat, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	*tasks = (int64_t)c;
 	return BMH_OK;
 }
 
@@ -632,6 +663,12 @@ int64_t bmh_ctx_glong_tasks_(const bmh_ctx_t *ctx)
 	int64_t t = 0;
 	float ms;
 	return ctx && bmh_global_long_stats(ctx, &t, &ms) == BMH_OK ? t : 0;
+}
+int64_t bmh_ctx_swl_tasks_(const bmh_ctx_t *ctx)
+{
+	int64_t t = 0;
+	float ms;
+	return ctx && bmh_sw_wide_stats(ctx, &t, &ms) == BMH_OK ? t : 0;
 }
 void bmh_ctx_set_driver_stats_(bmh_ctx_t *ctx, const bmh_driver_stats_t *st)
 {
@@ -932,7 +969,9 @@ static int validate_sw(bmh_ctx *ctx, const bmh_sw_task_t *tasks, int64_t n, size
 			ctx->last_error = "Smith-Waterman task " + std::to_string(k) + " reads outside the sequence pool";
 			return BMH_E_ARG;
 		}
-		if (x.qlen < 1 || (int64_t)x.qlen * ctx->dev.max_mat >= kScoreLimit) {
+		// (with bmh_ctx_set_wide_sw on, word mode takes any query: sw_long_kernel restates ksw_i16's saturation)
+		const bool wide = ctx->wide_sw && !(x.xtra & BMH_SW_XBYTE);
+		if (x.qlen < 1 || (!wide && (int64_t)x.qlen * ctx->dev.max_mat >= kScoreLimit)) {
 			ctx->last_error = "Smith-Waterman task " + std::to_string(k) + ": qlen must be >= 1 and qlen*max(mat) below the 16-bit score range";
 			return BMH_E_RANGE;
 		}

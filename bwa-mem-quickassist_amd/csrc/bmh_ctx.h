@@ -101,6 +101,12 @@ struct bmh_ctx {
 	// bin 4 of the global path (the band ring, global_kernel.hip): its tasks are counted on the device in d_err[2..3]
 	hipEvent_t ev_glong[2] = {};      // around its kernel (timing mode)
 	double glong_ms_sum = 0.0;        // timing mode: its time over the context's life (bmh_global_long_stats)
+	// word-mode Smith-Waterman on one wave per task for long queries and saturating scores (sw_long.hip), opt-in: bmh_ctx_set_wide_sw
+	bool wide_sw = false;
+	unsigned long long *d_swl_stat = nullptr; // device: tasks its kernels took over the context's life
+	DevBuf d_swl;                             // its row-maximum slab, then the state slices of its HBM variant
+	hipEvent_t ev_swl[2] = {};                // around its kernels (timing mode)
+	double swl_ms_sum = 0.0;                  // timing mode: their time over the context's life (bmh_sw_wide_stats)
 };
 
 namespace bmh {
@@ -211,8 +217,16 @@ int launch_sw_lane(bmh_ctx *ctx, int b, bool corr, bool word, const uint8_t *d_p
 bool sw_wave_fits(int64_t n, int qcap, int tcap);
 int launch_sw_wave(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n, bmh_sw_result_t *d_res, int max_cols,
                    int tcap, const uint32_t *d_order = nullptr, const uint32_t *d_count = nullptr);
+// skip_long: sw_long_kernel has taken what sw_long_takes (bmh_ctx_set_wide_sw on)
 int launch_sw_generic(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n,
-                      bmh_sw_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int qcap, int tcap, int wave_cols = 0);
+                      bmh_sw_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int qcap, int tcap, int wave_cols = 0,
+                      bool skip_long = false);
+// the long-query Smith-Waterman kernel (sw_long.hip): 5 bytes of state per padded query column; padded queries up to kSwLongLdsCols
+// columns keep it in LDS (20 KiB: seven waves per CU at the cutoff, more for shorter batches), longer ones in an HBM slab
+constexpr int kSwLongLdsCols = 4096;
+constexpr long long sw_long_state_bytes(int cols) { return 5LL * cols; }
+int launch_sw_long(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n, bmh_sw_result_t *d_res,
+                   const uint32_t *d_order, const uint32_t *d_count, int qmax, int qmin, int tcap, int wave_cols);
 int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                        bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip = nullptr);
 int launch_extend_reg(bmh_ctx *ctx, int ns, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,

@@ -47,4 +47,12 @@ __device__ __forceinline__ bool sw_wave_takes(const DevParams &P, int qlen, uint
 	return byte_mode ? qlen * P.max_mat + P.sw_shift < 255 : qlen * P.max_mat + P.sw_shift < 512;
 }
 
+// Tasks sw_long_kernel takes (bmh_ctx_set_wide_sw on): every word-mode task the other kernels of launch_sw would leave to
+// sw_generic_kernel -- wave_cols > 0: sw_wave_kernel has served what it takes at that width.  Byte mode stays where it was.
+__device__ __forceinline__ bool sw_long_takes(const DevParams &P, int qlen, uint32_t xtra, int wave_cols)
+{
+	if (qlen < 1 || (xtra & BMH_SW_XBYTE)) return false;
+	return !(wave_cols > 0 && sw_wave_takes(P, qlen, xtra, wave_cols));
+}
+
 } // namespace bmh

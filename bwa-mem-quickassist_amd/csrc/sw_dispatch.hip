@@ -30,6 +30,8 @@ __global__ void sw_caps_kernel(const bmh_sw_task_t *__restrict__ tasks, long lon
 //   bin 5: nothing to do (second pass not wanted)
 //   bin 6: byte mode, cannot overflow, padded query <= 256 columns  sw_lane_kernel<128, CORR>
 //   bin 7: word mode, scores below 512, padded query <= 256 columns sw_lane_kernel<128, CORR, WORD> (250 bp reads)
+// With bmh_ctx_set_wide_sw on, bin 2's word-mode tasks that sw_wave_kernel does not take go to sw_long_kernel (one wave per task,
+// any query up to 65 535, scores past the 16-bit range: sw_long.hip) and sw_generic_kernel skips them; no bin of its own.
 __device__ __forceinline__ bool sw_lane_bin(int bin) { return bin < 2 || bin >= 6; }
 __device__ __forceinline__ int sw_bin_of(const DevParams &P, int qlen, uint32_t xtra, int mode)
 {
@@ -117,6 +119,7 @@ int launch_sw(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks,
 		}
 	}
 	const int qfine = (qmin >= 1 && qcap - qmin < 64) ? qmin : -1; // see sw_hist_kernel
+	const int qmax = std::max(qcap, 1), tmax = std::max(tcap, 1); // (the batch's own extremes, for sw_long_kernel)
 	// a batch that cannot fill the chip with one lane per task goes to one wave per task (sw_wave.hip): the register
 	// kernels' launches take as long as one lane's whole matrix, milliseconds however few the tasks.  What that kernel does
 	// not take (arithmetic that can saturate) still goes through the routing below, to sw_generic_kernel.
@@ -145,7 +148,9 @@ int launch_sw(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks,
 		                   d_res, ctx->dev, hist, binkey, mode, pass2, d_pool, qfine, wave_cols);
 		if ((rc = sort_tasks_finish(ctx, n, nullptr, (unsigned)cg))) return rc;
 		if (wave) { // every bin but sw_generic_kernel's is empty
-			if ((rc = launch_sw_generic(ctx, d_pool, d_tasks, n, d_res, lists + 2 * N, counts + 2, qcap, tcap))) return rc;
+			if (ctx->wide_sw && (rc = launch_sw_long(ctx, d_pool, d_tasks, n, d_res, lists + 2 * N, counts + 2, qmax, qmin, tmax, 0)))
+				return rc;
+			if ((rc = launch_sw_generic(ctx, d_pool, d_tasks, n, d_res, lists + 2 * N, counts + 2, qcap, tcap, 0, ctx->wide_sw))) return rc;
 			break;
 		}
 		// (counts[b] = size of bin b, counts[8 + b] = its chunk cursor; longest columns first)
@@ -161,7 +166,10 @@ int launch_sw(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks,
 			// serves the rest (it used to serve all of it: 37 ms per launch for a handful of 300 bp mates, however few)
 			const int wc = ctx->sw_mode == 0 && ctx->sw_wave && tcap <= 16384 && qcap - 16 > 256 ? 320 : 0;
 			if (wc && (rc = launch_sw_wave(ctx, d_pool, d_tasks, n, d_res, wc, tcap, lists + 2 * N, counts + 2))) return rc;
-			if ((rc = launch_sw_generic(ctx, d_pool, d_tasks, n, d_res, lists + 2 * N, counts + 2, qcap, tcap, wc))) return rc;
+			// with bmh_ctx_set_wide_sw on, the word-mode rest goes to one wave per task as well (sw_long.hip), whatever its length
+			if (ctx->wide_sw && (rc = launch_sw_long(ctx, d_pool, d_tasks, n, d_res, lists + 2 * N, counts + 2, qmax, qmin, tmax, wc)))
+				return rc;
+			if ((rc = launch_sw_generic(ctx, d_pool, d_tasks, n, d_res, lists + 2 * N, counts + 2, qcap, tcap, wc, ctx->wide_sw))) return rc;
 		}
 	}
 	if (ctx->timing) {

@@ -109,7 +109,8 @@ __global__ __launch_bounds__(64) void sw_generic_kernel(const uint8_t *__restric
                                                         const uint32_t *__restrict__ order,
                                                         const uint32_t *__restrict__ count, long long n,
                                                         bmh_sw_result_t *__restrict__ out, DevParams P, uint8_t *slab,
-                                                        long long slab_stride, int qcap, int tcap, int *err_flag, int wave_cols)
+                                                        long long slab_stride, int qcap, int tcap, int *err_flag, int wave_cols,
+                                                        int skip_long)
 {
 	__shared__ int smat[6 * 8];
 	const int lane = threadIdx.x;
@@ -134,6 +135,7 @@ __global__ __launch_bounds__(64) void sw_generic_kernel(const uint8_t *__restric
 		const int p = byte_mode ? 16 : 8;
 		const int Q = (qlen + p - 1) / p * p;
 		if (wave_cols > 0 && sw_wave_takes(P, qlen, xtra, wave_cols)) continue; // sw_wave_kernel has been through this list
+		if (skip_long && sw_long_takes(P, qlen, xtra, wave_cols)) continue;       // ... and sw_long_kernel
 		bmh_sw_result_t res;
 		res.score = 0, res.te = res.qe = res.score2 = res.te2 = res.tb = res.qb = -1, res.rsv = 0;
 		if (Q > qcap || tlen > tcap || sw_task_out_of_range(P, qlen, xtra)) {
@@ -168,7 +170,8 @@ __global__ __launch_bounds__(64) void sw_generic_kernel(const uint8_t *__restric
 }
 
 int launch_sw_generic(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n,
-                      bmh_sw_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int qcap, int tcap, int wave_cols)
+                      bmh_sw_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int qcap, int tcap, int wave_cols,
+                      bool skip_long)
 {
 	if (n <= 0) return BMH_OK;
 	qcap = (qcap + 15) / 16 * 16;
@@ -179,7 +182,7 @@ int launch_sw_generic(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *
 	if ((rc = ensure(ctx, ctx->d_sw, stride * (size_t)grid))) return rc;
 	hipLaunchKernelGGL(sw_generic_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, d_pool, d_tasks, d_order,
 	                   d_count, (long long)n, d_res, ctx->dev, (uint8_t *)ctx->d_sw.p, (long long)stride, qcap, tcap,
-	                   ctx->d_err, wave_cols);
+	                   ctx->d_err, wave_cols, skip_long ? 1 : 0);
 	BMH_HIP(ctx, hipGetLastError());
 	return BMH_OK;
 }

@@ -670,8 +670,10 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		        g_p1_cnt[0], qa_chain_device() ? "bmh_seed_chain_batch on the device" : "bmh_chain_reads", g_p1_cnt[1], g_p1_cnt[2],
 		        g_p1_cnt[3]);
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
-		if (bmh_pool_wide()) /* BMH_WIDE_EXT=1 */
+		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());
+			fprintf(stderr, "[bwamem_hip] wide Smith-Waterman so far: %lld ksw_align2 tasks on the long-query kernel\n", bmh_pool_swl_tasks());
+		}
 		fprintf(stderr, "[bwamem_hip] long global alignments so far: %lld ksw_global2 tasks on the band-ring kernel\n", bmh_pool_glong_tasks());
 		fprintf(stderr, "[bwamem_hip] chunk of %d reads: phase 1 %.3f s, pestat %.3f s + mate rescue %.3f s, phase 2 (marking, pairing, global alignments, SAM) %.3f s\n", n,
 		        t_[1] - t_[0], t_pes - t_[1], t_[2] - t_pes, t_[3] - t_[2]);

@@ -44,6 +44,7 @@ static int pool_device(int nth)
  * ($BMH_RESERVE_MB scales the figures; 0 turns the reservation off). */
 int64_t bmh_ctx_wide_tasks_(const bmh_ctx_t *ctx);  /* internal hook of api.hip */
 int64_t bmh_ctx_glong_tasks_(const bmh_ctx_t *ctx); /* internal hook of api.hip (waits for the context's stream) */
+int64_t bmh_ctx_swl_tasks_(const bmh_ctx_t *ctx);   /* ... likewise */
 
 int bmh_pool_wide(void)
 {
@@ -71,6 +72,16 @@ long long bmh_pool_glong_tasks(void)
 	int i;
 	pthread_mutex_lock(&g_mu);
 	for (i = 0; i < g_n; ++i) t += g_slots[i].ctx ? (long long)bmh_ctx_glong_tasks_(g_slots[i].ctx) : 0;
+	pthread_mutex_unlock(&g_mu);
+	return t;
+}
+
+long long bmh_pool_swl_tasks(void)
+{
+	long long t = 0;
+	int i;
+	pthread_mutex_lock(&g_mu);
+	for (i = 0; i < g_n; ++i) t += g_slots[i].ctx ? (long long)bmh_ctx_swl_tasks_(g_slots[i].ctx) : 0;
 	pthread_mutex_unlock(&g_mu);
 	return t;
 }
@@ -113,6 +124,7 @@ bmh_ctx_t *bmh_pool_get(const bmh_params_t *p)
 	if (!s->ctx) {
 		if ((rc = bmh_ctx_create(&s->ctx, pool_device((int)(s - g_slots))))) bmh_tls_die("cannot create a GPU context", rc);
 		if (bmh_pool_wide() && (rc = bmh_ctx_set_wide_extension(s->ctx, 1))) bmh_tls_die("cannot turn on the wide extension", rc);
+		if (bmh_pool_wide() && (rc = bmh_ctx_set_wide_sw(s->ctx, 1))) bmh_tls_die("cannot turn on the wide Smith-Waterman", rc);
 		pool_reserve(s->ctx);
 	}
 	if (!s->have || memcmp(&s->params, p, sizeof(*p)) != 0) {
@@ -144,7 +156,7 @@ void bmh_pool_prewarm(int n)
 		bmh_ctx_t *ctx = 0;
 		slot_t *s = 0;
 		if (bmh_ctx_create(&ctx, pool_device(k))) return; /* no GPU: the first real call will say so loudly */
-		if (bmh_pool_wide() && bmh_ctx_set_wide_extension(ctx, 1)) { bmh_ctx_destroy(ctx); return; }
+		if (bmh_pool_wide() && (bmh_ctx_set_wide_extension(ctx, 1) || bmh_ctx_set_wide_sw(ctx, 1))) { bmh_ctx_destroy(ctx); return; }
 		pool_reserve(ctx);
 		pthread_mutex_lock(&g_mu);
 		if (g_n < BMH_POOL_MAX) s = &g_slots[g_n++], s->ctx = ctx, s->have = 0, s->busy = 0;

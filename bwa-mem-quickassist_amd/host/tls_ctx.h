@@ -14,10 +14,12 @@ void bmh_pool_put(bmh_ctx_t *ctx);
 void bmh_pool_prewarm(int n);
 void bmh_pool_stop(void); /* makes a running bmh_pool_prewarm return after the context it is creating */
 void bmh_tls_die(const char *msg, int code);
-/* BMH_WIDE_EXT=1: every pool context runs with bmh_ctx_set_wide_extension on (default off) */
+/* BMH_WIDE_EXT=1: every pool context runs with bmh_ctx_set_wide_extension and bmh_ctx_set_wide_sw on (default off) */
 int bmh_pool_wide(void);
 /* extension tasks the pool's contexts sent to the int32 kernel so far (host-buffer calls) */
 long long bmh_pool_wide_tasks(void);
 /* global alignments the pool's contexts have sent to the band-ring kernel so far (bmh_global_long_stats) */
 long long bmh_pool_glong_tasks(void);
+/* ksw_align2 tasks the pool's contexts have sent to the long-query Smith-Waterman kernel so far (bmh_sw_wide_stats) */
+long long bmh_pool_swl_tasks(void);
 #endif

@@ -110,8 +110,10 @@ typedef struct bmh_glb_result {
  *           h0 + qlen*max(mat) <= 2^24 (bmh_seedext_batch: l_query*max(max(mat), a) <= 2^24), any query up to 65535
  *           (with *_device calls: up to bmh_ctx_set_qcap), any gap costs >= the minimums of bmh_ctx_set_params.  The
  *           fused record keeps its flank bound of 65535 and 2*w <= 32767.  Tasks inside the range above keep their kernels.
- *           Not covered: mate rescue (bmh_sw_batch / bmh_matesw_batch, qlen*max(mat) < 32000), so paired-end long reads can
- *           still stop there; and the 65535 limits of bmh_global_batch and bmh_reg2cigar_batch below.
+ *           Mate rescue (bmh_sw_batch / bmh_matesw_batch) has a switch of its own, bmh_ctx_set_wide_sw below; not covered
+ *           by either: the 65535 limits of bmh_global_batch and bmh_reg2cigar_batch below.
+ *   Smith-Waterman with bmh_ctx_set_wide_sw(ctx, 1): word-mode tasks (no BMH_SW_XBYTE) accept any qlen up to 65535 whatever
+ *           qlen*max(mat); scores saturate at 32 767 exactly as ksw_i16's 16-bit lanes do.  Byte mode keeps its limits.
  *   global: qlen,tlen <= 65535 (the uint16 fields of bmh_glb_task_t).  Tasks with up to 10 176 query columns keep H, E and the
  *           profile of the whole row in LDS (16 bytes per column).  Longer ones that no lane kernel takes go to a band-ring
  *           kernel, whose LDS holds 2*min(w,qlen)+2 columns or more, rounded up to a power of two, at 10 bytes each: bands
@@ -142,6 +144,12 @@ int bmh_ctx_sync(bmh_ctx_t *ctx); /* waits for the stream; returns a pending BMH
 /* Opt-in int32 extension kernel (see "Supported range"): with enable != 0, extension and fused per-seed batches accept scores up
  * to 2^24, queries up to 65535 and gap costs past 16 bits.  Off by default; the default context refuses them as before. */
 int bmh_ctx_set_wide_extension(bmh_ctx_t *ctx, int enable);
+/* Opt-in long-query Smith-Waterman kernel: with enable != 0, bmh_sw_batch / _device / _sharded and bmh_matesw_batch accept
+ * word-mode tasks with qlen*max(mat) >= 32000 (up to qlen 65535) and run every word-mode task that would otherwise go to the
+ * one-lane-per-task slab kernel -- queries past the register kernels, scores of 512 and more -- on one wave per task
+ * (bmh_sw_wide_stats counts them).  Results are those of the reference, saturation included: in-range tasks change kernel but
+ * not result.  Off by default; the default context refuses such tasks and routes every task as before. */
+int bmh_ctx_set_wide_sw(bmh_ctx_t *ctx, int enable);
 /* Capacity hint for the *_device entry points, which cannot look at the tasks on the host:
  * the longest query the launch must handle (default 512).  bmh_extend_batch_device and bmh_seedext_batch_device fail longer
  * queries with BMH_E_RANGE (bmh_ctx_sync returns it) and deliver the other tasks of the call: an extension task longer than
@@ -272,6 +280,10 @@ int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3]);
  * query columns that no lane kernel takes): *tasks = their number, *ms = the ring kernel's time summed over the launches made
  * with timing on (-1 when timing is off).  The counterpart of bmh_extend_wide_stats.  Waits for the stream. */
 int bmh_global_long_stats(const bmh_ctx_t *ctx, int64_t *tasks, float *ms);
+/* What the Smith-Waterman launches of this context so far sent to the long-query kernel (bmh_ctx_set_wide_sw): *tasks = their
+ * number, *ms = its time summed over the launches made with timing on (-1 when timing is off).  The counterpart of
+ * bmh_global_long_stats.  Waits for the stream. */
+int bmh_sw_wide_stats(const bmh_ctx_t *ctx, int64_t *tasks, float *ms);
 /* Duration of the four rounds of the last fused per-seed launch (left, left at 2w, right, right at 2w), each with the
  * small list-building kernel in front of it.  -1 when timing was off. */
 int bmh_last_seedext_round_ms(bmh_ctx_t *ctx, float ms[4]);
@@ -435,7 +447,10 @@ int bmh_ctx_reserve_kernels(bmh_ctx_t *ctx, int seed_reads, int seed_read_len, i
  * m = 5 and the matrix / gap penalties come from bmh_params_t.  Inputs outside the exact domain are refused with
  * BMH_E_RANGE: qlen*max(mat) >= 32000, gap penalties above 255, byte-mode tasks that can overflow (qlen*max(mat) + shift
  * >= 255) combined with KSW_XSTART, for which the reference reads uninitialised memory (ksw.c:355-357), and byte-mode
- * tasks when o_del+e_del or o_ins+e_ins reaches 256, which ksw_u8 wraps in its 8-bit lanes (ksw.c:125-128). */
+ * tasks when o_del+e_del or o_ins+e_ins reaches 256, which ksw_u8 wraps in its 8-bit lanes (ksw.c:125-128).
+ * With bmh_ctx_set_wide_sw on, word-mode tasks are accepted past qlen*max(mat) >= 32000 (qlen up to 65535) with ksw_i16's
+ * saturation at 32 767, and run on one wave per task; *_device calls flag a task that kernel cannot hold (BMH_E_RANGE,
+ * the others are delivered). */
 #define BMH_SW_XBYTE 0x10000u
 #define BMH_SW_XSTOP 0x20000u
 #define BMH_SW_XSUBO 0x40000u
@@ -481,7 +496,9 @@ int bmh_sw_batch_device(bmh_ctx_t *ctx, const uint8_t *d_pool, const bmh_sw_task
  * invocations (planned ahead against the current state, re-checked when folded), their ksw_align2 calls as one GPU
  * batch over all pairs.  The outcome is exactly the reference's; a call planned ahead may go unused.
  * With the reference resident (bmh_ctx_set_pac, same pac pointer) the windows are BMH_F_TPAC tasks and the
- * reverse-complemented mate is BMH_F_QREV|BMH_F_QCOMP: the pool holds every read once and nothing else. */
+ * reverse-complemented mate is BMH_F_QREV|BMH_F_QCOMP: the pool holds every read once and nothing else.
+ * Its ksw_align2 calls obey bmh_sw_batch's range: a mate with l_seq*max(mat) >= 32000 needs bmh_ctx_set_wide_sw on the context
+ * (word mode, the long-query kernel), and the call fails with BMH_E_RANGE otherwise. */
 typedef struct bmh_pestat { /* mem_pestat_t, bwamem.h:66-70 */
 	int32_t low, high;
 	int32_t failed;
