@@ -557,15 +557,23 @@ __global__ void smem_order_intervals(int n_reads, const uint32_t *__restrict__ c
 	}
 }
 
-// ---- host side: one resident copy of the index per (device, host arrays), shared by all contexts ----
+// ---- host side: one resident copy of the index per (device, host arrays, shape), shared by all contexts ----
+// The shape (every field of bmh_bwt_t) is part of the key: a freed index and a new one can get the same host addresses
+// (large buffers are mmapped, and mmap hands the same range back), and a copy matched on the pointers alone would then
+// be used with the old primary / L2 / seq_len -- wrong seeds, or reads past the old allocation when the new index is
+// larger.  Contents are not compared: the arrays must not change while an index is bound.
 struct BwtShare {
 	int device;
-	const uint32_t *h_bwt;
-	const uint64_t *h_sa;
+	bmh_bwt_t key;
 	void *d_bwt, *d_sa;
 	DevBwt dev;
 	int refs;
 };
+static bool same_bwt(const bmh_bwt_t &a, const bmh_bwt_t &b)
+{
+	return a.bwt == b.bwt && a.sa == b.sa && a.primary == b.primary && a.seq_len == b.seq_len && a.bwt_size == b.bwt_size &&
+	       a.n_sa == b.n_sa && a.sa_intv == b.sa_intv && !memcmp(a.L2, b.L2, sizeof a.L2);
+}
 static std::mutex g_bwt_mu;
 static std::vector<BwtShare> g_bwts;
 
@@ -575,7 +583,7 @@ using namespace bmh;
 
 struct bmh_bwt_binding { // hangs off the context (opaque pointer in bmh_ctx)
 	DevBwt dev;
-	const uint32_t *h_bwt;
+	bmh_bwt_t key;
 };
 
 extern "C" void free_bwt_binding(void *p) { delete (bmh_bwt_binding *)p; }
@@ -587,13 +595,13 @@ int bmh_ctx_set_bwt(bmh_ctx_t *ctx, const bmh_bwt_t *b)
 	if (!ctx || !b || !b->bwt || !b->sa || b->sa_intv < 1 || (b->sa_intv & (b->sa_intv - 1))) return BMH_E_ARG;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	std::lock_guard<std::mutex> lk(g_bwt_mu);
-	if (ctx->bwt_bind && ((bmh_bwt_binding *)ctx->bwt_bind)->h_bwt == b->bwt) return BMH_OK;
+	if (ctx->bwt_bind && same_bwt(((bmh_bwt_binding *)ctx->bwt_bind)->key, *b)) return BMH_OK;
 	BwtShare *s = nullptr;
 	for (auto &e : g_bwts)
-		if (e.device == ctx->device && e.h_bwt == b->bwt && e.h_sa == b->sa) s = &e;
+		if (e.device == ctx->device && same_bwt(e.key, *b)) s = &e;
 	if (!s) {
 		BwtShare n{};
-		n.device = ctx->device, n.h_bwt = b->bwt, n.h_sa = b->sa;
+		n.device = ctx->device, n.key = *b;
 		const size_t bw = (size_t)b->bwt_size * 4 + 64, sb = (size_t)b->n_sa * 8 + 64;
 		if (hipMalloc(&n.d_bwt, bw) != hipSuccess || hipMalloc(&n.d_sa, sb) != hipSuccess) {
 			(void)hipGetLastError();
@@ -617,7 +625,7 @@ int bmh_ctx_set_bwt(bmh_ctx_t *ctx, const bmh_bwt_t *b)
 	}
 	++s->refs; // (kept for the life of the process: the index is as immutable as the reference)
 	if (!ctx->bwt_bind) ctx->bwt_bind = new bmh_bwt_binding();
-	((bmh_bwt_binding *)ctx->bwt_bind)->dev = s->dev, ((bmh_bwt_binding *)ctx->bwt_bind)->h_bwt = b->bwt;
+	((bmh_bwt_binding *)ctx->bwt_bind)->dev = s->dev, ((bmh_bwt_binding *)ctx->bwt_bind)->key = *b;
 	return BMH_OK;
 }
 

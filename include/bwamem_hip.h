@@ -624,7 +624,11 @@ typedef struct bmh_index {
 int bmh_index_load(const char *prefix, bmh_index_t **out); /* BMH_E_ARG if a file is missing or inconsistent */
 void bmh_index_free(bmh_index_t *ix);
 
-/* Make the index resident on the context's device (one copy per device and host array, shared by all contexts). */
+/* Make the index resident on the context's device: one copy per device, host arrays and shape (every field of *bwt),
+ * shared by all contexts and kept for the life of the process.  The host arrays must not change while an index is
+ * bound: the library does not compare contents, so new contents at the same addresses and with the same shape would
+ * keep the old copy.  A different shape at the same addresses (an index freed and another built in its place) gets
+ * a fresh copy. */
 int bmh_ctx_set_bwt(bmh_ctx_t *ctx, const bmh_bwt_t *bwt);
 /* For every read: the bwt_smem1 calls of smem_next2's iteration, in order.  Read r's calls are
  * calls[call_off[r] .. call_off[r+1]) and their intervals lie in intv[intv_off[r] + call.first ...].  call_off and
