@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import kswlib
+import pacwin
 from kswlib import BMH_F_QREV, BMH_F_TREV, BMH_F_TPAC, EXT_TASK
 from test_kernel_families_gpu import _ctx_with
 
@@ -156,15 +157,7 @@ def test_region_records_against_oracle_global_and_md(l_pac):
     pac = rng.integers(0, 256, l_pac // 4 + 1, dtype=np.uint8)
 
     def window(pos, n):
-        """n bases of the doubled coordinate from pos on (bntseq.c:355-376), decoded from the 2-bit array"""
-        if pos >= l_pac:  # reverse strand: complement of the forward strand read backwards
-            f0 = 2 * l_pac - pos - n
-            return (3 - _fwd(f0, n))[::-1]
-        return _fwd(pos, n)
-
-    def _fwd(f0, n):
-        idx = np.arange(f0, f0 + n, dtype=np.int64)
-        return ((pac[idx >> 2] >> ((~idx & 3) << 1).astype(np.uint8)) & 3).astype(np.uint8)
+        return pacwin.window(pac, l_pac, pos, n)
 
     p = kswlib.make_params()
     ctx = _ctx_with({})
