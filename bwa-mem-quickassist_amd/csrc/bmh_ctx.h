@@ -194,7 +194,9 @@ int launch_extend_lds(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t 
                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int qmax, long long grid_cap = 0);
 constexpr int kSortKeysHost = 2048; // == kSortKeys in extend_dispatch.hip
 int sort_tasks_begin(bmh_ctx *ctx, int64_t n, uint32_t **counts, uint32_t **lists);
-int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n = nullptr);
+// d_total (nullable): receives the sum of the bin sizes
+int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n = nullptr,
+                      uint32_t *d_total = nullptr);
 int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                        bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, const uint32_t *d_count,
                        int rows_cap);
@@ -202,6 +204,80 @@ constexpr int kExtBins = 6;        // length bins of the extension dispatcher (t
 constexpr int kWideBin = 6;        // ... and the int32 kernel's bin, used only with bmh_ctx_set_wide_extension on
 constexpr int kSortBins = 8;       // bins the shared counting sort can tell apart (extension 6, global 6, Smith-Waterman 8)
 constexpr int kGrpTcapHost = 1024; // == kGrpTcap in extend_grp.hip
+
+// ---- the extension dispatcher's binning rule, for every kernel that fills binkey[] and the histogram: sort_hist_kernel over
+// tasks that exist (extend_dispatch.hip), and the fused per-seed record's kernels that bin a task while they make it (seedext.hip)
+constexpr int kCapBin = 7;          // tasks past the launch's qmax: listed, never launched
+constexpr int kSortBlocks = 512;    // most blocks a pass of the sort uses
+constexpr uint16_t kNoTask = 0xffff; // binkey of an entry that holds no task (a seed without the flank): counted and placed nowhere
+static_assert(kSortBins * kSortKeysHost <= kNoTask, "binkey is 16 bits wide and keeps one value for entries without a task");
+
+__device__ __forceinline__ int ext_bin_of(int qlen, int tlen, int mode)
+{
+	// mode 0: lane-per-task kernels (qlen <= 256); 1: LDS kernel only; 2: one task per wave; 3: four tasks per wave;
+	// 4: like 0 plus the four-lanes-per-task kernel for qlen <= 512
+	if (mode == 1 || qlen < 1) return 5;
+	if (mode == 3 && qlen <= 256 && tlen > kGrpTcapHost) return 3; // the group kernels stage the target in LDS
+	return qlen <= 32 ? 0 : qlen <= 64 ? 1 : qlen <= 128 ? 2 : qlen <= 256 ? 3 : (qlen <= 512 && mode == 4) ? 4 : 5;
+}
+
+// bin 6: the task leaves the 16-bit kernels' domain (with the switch on; the gap costs are checked per batch on the host)
+__device__ __forceinline__ bool ext_goes_wide(int qlen, int h0, int max_mat)
+{
+	return (long long)max(h0, 0) + (long long)qlen * max_mat > kScoreLimit || qlen > kLdsQcap;
+}
+
+// sort key inside a bin: query-length bucket (major; lanes of a wave then share the unused leading columns,
+// which the lane kernels skip), h0 bucket, and expected row count (minor; lanes of a wave then finish together).
+// rows run at most to tlen, and the band leaves the query after ~qlen+w <= 2*qlen rows (ksw.c:418).
+__device__ __forceinline__ int ext_sort_key(int bin, int qlen, int tlen, int h0)
+{
+	if (bin > 4) return 0;
+	const int qlo = bin == 0 ? 1 : (16 << bin) + 1, qsh = bin < 2 ? 1 : bin; // 16 query-length buckets per bin
+	const int rows = min(tlen, 2 * qlen + 8) >> (bin > 2 ? bin - 2 : 0);
+	// h0 decides how wide the live interval is (cells stay non-zero within ~h0-o-e of the diagonal), so lanes
+	// with a similar h0 need the same 8-column blocks
+	return ((max(qlen - qlo, 0) >> qsh) * 8 + min(max(h0, 0) >> 4, 7)) * 16 + min(rows >> 4, 15);
+}
+
+struct ExtBinRule { // what a launch fixes for all of its tasks
+	int mode;       // see ext_bin_of
+	int wide;       // 0 switch off, 1 per task, 2 every task
+	int max_mat, qmax;
+	bmh_ext_result_t *out; // results, for the failure record of a task past qmax
+	int *err_flag;
+};
+
+// bin and sort key of ONE task as binkey holds them (bin * kSortKeys + key).  Past qmax: the failure record of the kernels, here,
+// since the bins that qmax calls empty are not launched
+__device__ __forceinline__ int ext_binkey_of(const ExtBinRule &r, int qlen, int tlen, int h0, size_t idx)
+{
+	const bool over = qlen > r.qmax;
+	const int bin = over ? kCapBin : r.wide && (r.wide == 2 || ext_goes_wide(qlen, h0, r.max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, r.mode);
+	if (over) {
+		int *p = (int *)(r.out + idx);
+		p[0] = INT32_MIN, p[1] = p[2] = p[3] = p[4] = p[5] = 0;
+		atomicExch(r.err_flag, BMH_E_RANGE);
+	}
+	return bin * kSortKeysHost + ext_sort_key(bin, qlen, tlen, h0);
+}
+
+// The dispatcher in two halves, for a caller whose own kernel makes the tasks and bins them in the same pass (the fused
+// per-seed record).  Between the two calls the caller enqueues that kernel on ctx->stream with at most p.blocks blocks: for
+// entry i of 0..n-1 it writes p.binkey[i] = ext_binkey_of(p.rule, ...) and counts it in p.hist -- or kNoTask and nothing.
+struct ExtBinned {
+	ExtBinRule rule;
+	uint32_t *hist;   // kSortBins * kSortKeys counters, zeroed
+	uint16_t *binkey; // n entries
+	unsigned blocks;
+	bool tiny; // the bin-size hint calls the batch (almost) empty: rule.mode sends every task to bin 5, and one launch of the
+	           // any-length kernel walks that list (as launch_extend does for a device-counted list)
+};
+int extend_binned_begin(bmh_ctx *ctx, int64_t n, bmh_ext_result_t *d_res, int qmax, int kind, ExtBinned *p);
+// d_total (nullable): receives the number of tasks, i.e. the sum of the bin sizes
+int extend_binned_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
+                         int qmax, int kind, const ExtBinned &p, uint32_t *d_total);
+
 int launch_extend_grp(bmh_ctx *ctx, int nv, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count);
 int launch_extend_lanex(bmh_ctx *ctx, int lpt, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,

@@ -29,47 +29,17 @@ namespace bmh {
 // The lane-per-task kernels want neighbouring tasks to run for a similar number of rows.
 constexpr int kSortKeys = 2048;
 
-__device__ __forceinline__ int ext_bin_of(int qlen, int tlen, int mode)
-{
-	// mode 0: lane-per-task kernels (qlen <= 256); 1: LDS kernel only; 2: one task per wave; 3: four tasks per wave;
-	// 4: like 0 plus the four-lanes-per-task kernel for qlen <= 512
-	if (mode == 1 || qlen < 1) return 5;
-	if (mode == 3 && qlen <= 256 && tlen > kGrpTcapHost) return 3; // the group kernels stage the target in LDS
-	return qlen <= 32 ? 0 : qlen <= 64 ? 1 : qlen <= 128 ? 2 : qlen <= 256 ? 3 : (qlen <= 512 && mode == 4) ? 4 : 5;
-}
-
-// bin 6: the task leaves the 16-bit kernels' domain (with the switch on; the gap costs are checked per batch on the host)
-__device__ __forceinline__ bool ext_goes_wide(int qlen, int h0, int max_mat)
-{
-	return (long long)max(h0, 0) + (long long)qlen * max_mat > kScoreLimit || qlen > kLdsQcap;
-}
-
-// sort key inside a bin: query-length bucket (major; lanes of a wave then share the unused leading columns,
-// which the lane kernels skip), h0 bucket, and expected row count (minor; lanes of a wave then finish together).
-// rows run at most to tlen, and the band leaves the query after ~qlen+w <= 2*qlen rows (ksw.c:418).
-__device__ __forceinline__ int ext_sort_key(int bin, int qlen, int tlen, int h0)
-{
-	if (bin > 4) return 0;
-	const int qlo = bin == 0 ? 1 : (16 << bin) + 1, qsh = bin < 2 ? 1 : bin; // 16 query-length buckets per bin
-	const int rows = min(tlen, 2 * qlen + 8) >> (bin > 2 ? bin - 2 : 0);
-	// h0 decides how wide the live interval is (cells stay non-zero within ~h0-o-e of the diagonal), so lanes
-	// with a similar h0 need the same 8-column blocks
-	return ((max(qlen - qlo, 0) >> qsh) * 8 + min(max(h0, 0) >> 4, 7)) * 16 + min(rows >> 4, 15);
-}
-
-constexpr int kSortBlocks = 512, kSortThreads = 256;
+// (the binning rule itself -- ext_bin_of, ext_goes_wide, ext_sort_key, ext_binkey_of -- is in bmh_ctx.h: the fused per-seed record's
+// kernels apply it too)
+constexpr int kSortThreads = 256;
 constexpr int kLanexMinTasks = 4096; // below this many 129-256 bp flanks one wave per task fills the chip better
-
-constexpr int kCapBin = 7; // tasks past the launch's qmax: listed, never launched
 
 // pass 1: per-block histogram in LDS over a contiguous chunk, flushed with one global atomic per used key
 __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_task_t *__restrict__ tasks,
                                                                  const uint32_t *__restrict__ order, long long n,
                                                                  uint32_t *__restrict__ hist,
-                                                                 uint16_t *__restrict__ binkey, int mode,
-                                                                 const uint32_t *__restrict__ dn, int wide, int max_mat,
-                                                                 int qmax, bmh_ext_result_t *__restrict__ out,
-                                                                 int *__restrict__ err_flag)
+                                                                 uint16_t *__restrict__ binkey, ExtBinRule rule,
+                                                                 const uint32_t *__restrict__ dn)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeys];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kSortThreads) lh[t] = 0;
@@ -78,18 +48,7 @@ __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_t
 	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
 	for (long long k = lo + threadIdx.x; k < hi; k += kSortThreads) {
 		const uint32_t idx = order ? order[k] : (uint32_t)k;
-		const int qlen = tasks[idx].qlen, tlen = tasks[idx].tlen;
-		const int h0 = tasks[idx].h0;
-		// wide: 0 switch off, 1 per task, 2 every task.  Past qmax: the failure record of the kernels, here, since the bins
-		// that qmax calls empty are not launched
-		const bool over = qlen > qmax;
-		const int bin = over ? kCapBin : wide && (wide == 2 || ext_goes_wide(qlen, h0, max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, mode);
-		if (over) {
-			int *p = (int *)(out + idx);
-			p[0] = INT32_MIN, p[1] = p[2] = p[3] = p[4] = p[5] = 0;
-			atomicExch(err_flag, BMH_E_RANGE);
-		}
-		const int bk = bin * kSortKeys + ext_sort_key(bin, qlen, tlen, h0);
+		const int bk = ext_binkey_of(rule, tasks[idx].qlen, tasks[idx].tlen, tasks[idx].h0, idx);
 		binkey[k] = (uint16_t)bk;
 		atomicAdd(&lh[bk], 1u);
 	}
@@ -98,12 +57,14 @@ __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_t
 		if (lh[t]) atomicAdd(&hist[t], lh[t]);
 }
 
-// pass 2: exclusive scan of each bin's histogram (in place -> cursors) and the bin sizes
-__global__ __launch_bounds__(1024) void sort_scan_kernel(uint32_t *__restrict__ hist, uint32_t *__restrict__ counts)
+// pass 2: exclusive scan of each bin's histogram (in place -> cursors) and the bin sizes; total (nullable): their sum
+__global__ __launch_bounds__(1024) void sort_scan_kernel(uint32_t *__restrict__ hist, uint32_t *__restrict__ counts,
+                                                         uint32_t *__restrict__ total)
 {
 	static_assert(kSortKeys == 2048, "two keys per thread");
 	__shared__ uint32_t part[1024];
 	const int t = threadIdx.x;
+	uint32_t sum = 0;
 	for (int b = 0; b < kSortBins; ++b) {
 		const uint32_t v0 = hist[b * kSortKeys + 2 * t], v1 = hist[b * kSortKeys + 2 * t + 1];
 		part[t] = v0 + v1;
@@ -117,13 +78,15 @@ __global__ __launch_bounds__(1024) void sort_scan_kernel(uint32_t *__restrict__ 
 		const uint32_t excl = part[t] - (v0 + v1);
 		hist[b * kSortKeys + 2 * t] = excl;
 		hist[b * kSortKeys + 2 * t + 1] = excl + v0;
-		if (t == 1023) counts[b] = part[t];
+		if (t == 1023) counts[b] = part[t], sum += part[t];
 		__syncthreads();
 	}
+	if (t == 1023 && total) *total = sum;
 }
 
 // pass 3: every block re-counts its chunk, reserves one range per used key from the global cursors and
-// places its tasks inside those ranges with LDS atomics
+// places its tasks inside those ranges with LDS atomics.  Entries marked kNoTask (only a kernel that bins entries which may
+// hold no task writes them) are neither counted nor placed
 __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const uint32_t *__restrict__ order, long long n,
                                                                     uint32_t *__restrict__ cursor,
                                                                     const uint16_t *__restrict__ binkey,
@@ -135,13 +98,17 @@ __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const uint32
 	__syncthreads();
 	if (dn) n = min(n, (long long)*dn);
 	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
-	for (long long k = lo + threadIdx.x; k < hi; k += kSortThreads) atomicAdd(&lh[binkey[k]], 1u);
+	for (long long k = lo + threadIdx.x; k < hi; k += kSortThreads) {
+		const uint32_t bk = binkey[k];
+		if (bk != kNoTask) atomicAdd(&lh[bk], 1u);
+	}
 	__syncthreads();
 	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kSortThreads)
 		if (lh[t]) lh[t] = atomicAdd(&cursor[t], lh[t]); // count -> start of this block's range
 	__syncthreads();
 	for (long long k = lo + threadIdx.x; k < hi; k += kSortThreads) {
 		const uint32_t bk = binkey[k];
+		if (bk == kNoTask) continue;
 		const uint32_t pos = atomicAdd(&lh[bk], 1u);
 		lists[(size_t)(bk / kSortKeys) * (size_t)stride + pos] = order ? order[k] : (uint32_t)k;
 	}
@@ -160,13 +127,13 @@ int sort_tasks_begin(bmh_ctx *ctx, int64_t n, uint32_t **counts, uint32_t **list
 	return BMH_OK;
 }
 
-int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n)
+int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n, uint32_t *d_total)
 {
 	const size_t N = (size_t)n, hist_words = (size_t)kSortBins * kSortKeys;
 	uint32_t *counts = (uint32_t *)ctx->d_bins.p, *hist = counts + 16;
 	uint16_t *binkey = (uint16_t *)(hist + hist_words);
 	uint32_t *lists = hist + hist_words + (N + 1) / 2 + 1;
-	hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, hist, counts);
+	hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, hist, counts, d_total);
 	hipLaunchKernelGGL(sort_scatter_kernel, dim3(blocks), dim3(kSortThreads), 0, ctx->stream, d_order, (long long)n, hist, binkey,
 	                   lists, (long long)n, d_n);
 	BMH_HIP(ctx, hipGetLastError());
@@ -227,6 +194,51 @@ int wide_stats_begin(bmh_ctx *ctx)
 	return BMH_OK;
 }
 
+// ---- A dispatcher launch in two halves.  The first decides how the batch is binned and gets the bins built: extend_plan, then
+// either sort_hist_kernel over the caller's tasks (launch_extend) or the caller's own make-and-bin kernel (extend_binned_begin /
+// _finish), then the scan and scatter passes.  The second, extend_run_bins, runs every bin on its kernel.
+struct ExtPlan {
+	int wide; // bin 6 (switch on only): 1 the tasks outside the 16-bit domain, 2 every task (gap costs past 16 bits, or BMH_EXT_MODE=wide)
+	int mode; // see ext_bin_of
+	bool tiny; // the hint calls a device-counted batch (almost) empty: no bins, one launch of the any-length kernel
+	int64_t n_eff; // tasks expected: n, or what the hint says of a device-counted list
+};
+
+// device_count: how many of the n entries are tasks is known on the device only, so the hinted size stands in for it
+static int extend_plan(bmh_ctx *ctx, int64_t n, int kind, bool device_count, ExtPlan *pl)
+{
+	const bool gaps_wide = ext_gaps_too_large(ctx->params);
+	if (gaps_wide && !ctx->wide_ext) {
+		ctx->last_error = "the extension kernels need o_del+e_del, o_ins+e_ins <= 65535 and e_del, e_ins <= 16383";
+		return BMH_E_RANGE;
+	}
+	pl->wide = !ctx->wide_ext ? 0 : gaps_wide || (ctx->ext_mode_forced && ctx->force_kernel == 5) ? 2 : 1;
+	hint_poll(ctx, kind);
+	const bmh_ctx::BinHint &hint = ctx->hint[kind];
+	int64_t est_total = 0;
+	for (int b = 0; b < kExtBins; ++b) est_total += hint.valid ? hint.cnt[b] : 0;
+	// (the tiny path's one LDS launch cannot take bin 6's tasks)
+	pl->tiny = device_count && hint.valid && !ctx->ext_mode_forced && !pl->wide && est_total <= kTinyList;
+	if (!hint.valid) est_total = n;
+	// 0 lane-per-task, 1 lds, 2 reg (1 task/wave), 3 grp (4 tasks/wave).  The lane-per-task kernels are built for
+	// throughput: a wave walks ~100 rows x 128 columns for its 64 tasks, about half a millisecond however small the batch.
+	// A driver round of a few thousand tasks (bmh_chain2aln_batch: 8 192 reads per call) cannot fill the chip anyway and
+	// wants latency: one task per wave finishes in tens of microseconds (8 153 tasks: 0.76 -> 0.26 ms per call, 32 647:
+	// 0.84 -> 0.51 ms; level at 65 k).  With a device-side count the decision uses the hinted size.
+	const int64_t n_eff = pl->n_eff = device_count ? std::min<int64_t>(n, est_total + (est_total >> 2) + 64) : n;
+	pl->mode = ctx->ext_mode_forced ? (ctx->force_kernel == 5 ? 0 : ctx->force_kernel) : n_eff <= ctx->small_batch ? 2 : 0;
+	return BMH_OK;
+}
+
+static unsigned sort_blocks_for(int64_t n)
+{
+	const int64_t cg = (n + 1023) / 1024;
+	return (unsigned)std::min<int64_t>(std::max<int64_t>(cg, 1), kSortBlocks);
+}
+
+static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
+                           int qmax, int kind, const ExtPlan &pl);
+
 int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                   bmh_ext_result_t *d_res, const uint32_t *d_order, int qmax, const uint32_t *d_n, int kind)
 {
@@ -234,45 +246,65 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 	if (kind < 0 || kind >= bmh_ctx::kHintKinds) kind = 0;
 	int rc;
 	if (kind == 0 && (rc = wide_stats_begin(ctx))) return rc; // (the fused per-seed call begins its span itself)
-	const bool gaps_wide = ext_gaps_too_large(ctx->params);
-	if (gaps_wide && !ctx->wide_ext) {
-		ctx->last_error = "the extension kernels need o_del+e_del, o_ins+e_ins <= 65535 and e_del, e_ins <= 16383";
-		return BMH_E_RANGE;
-	}
-	// bin 6 (switch on only): 1 the tasks outside the 16-bit domain, 2 every task (gap costs past 16 bits, or BMH_EXT_MODE=wide)
-	const int wide = !ctx->wide_ext ? 0 : gaps_wide || (ctx->ext_mode_forced && ctx->force_kernel == 5) ? 2 : 1;
-	hint_poll(ctx, kind);
-	const bmh_ctx::BinHint &hint = ctx->hint[kind];
-	if (d_n && hint.valid && !ctx->ext_mode_forced && !wide) { // (the tiny path's one LDS launch cannot take bin 6's tasks)
-		uint32_t tot = 0;
-		for (int b = 0; b < kExtBins; ++b) tot += hint.cnt[b];
-		if (tot <= kTinyList) return launch_extend_tiny(ctx, d_pool, d_tasks, n, d_res, d_order, qmax, d_n, kind);
-	}
-	// expected size of bin b: the previous launch's count with a margin -- or, with no hint, the whole batch
-	int64_t est[kExtBins], est_total = 0;
-	for (int b = 0; b < kExtBins; ++b) {
-		est[b] = hint.valid ? std::min<int64_t>(n, (int64_t)hint.cnt[b] + (hint.cnt[b] >> 4) + 64) : n;
-		est_total += hint.valid ? hint.cnt[b] : 0;
-	}
-	if (!hint.valid) est_total = n;
-	// 0 lane-per-task, 1 lds, 2 reg (1 task/wave), 3 grp (4 tasks/wave).  The lane-per-task kernels are built for
-	// throughput: a wave walks ~100 rows x 128 columns for its 64 tasks, about half a millisecond however small the batch.
-	// A driver round of a few thousand tasks (bmh_chain2aln_batch: 8 192 reads per call) cannot fill the chip anyway and
-	// wants latency: one task per wave finishes in tens of microseconds (8 153 tasks: 0.76 -> 0.26 ms per call, 32 647:
-	// 0.84 -> 0.51 ms; level at 65 k).  With a device-side count (d_n) the decision uses the hinted size.
-	const int64_t n_eff = d_n ? std::min<int64_t>(n, est_total + (est_total >> 2) + 64) : n;
-	const int mode = ctx->ext_mode_forced ? (ctx->force_kernel == 5 ? 0 : ctx->force_kernel) : n_eff <= ctx->small_batch ? 2 : 0;
-	const size_t N = (size_t)n;
+	ExtPlan pl;
+	if ((rc = extend_plan(ctx, n, kind, d_n != nullptr, &pl))) return rc;
+	if (pl.tiny) return launch_extend_tiny(ctx, d_pool, d_tasks, n, d_res, d_order, qmax, d_n, kind);
 	uint32_t *counts, *lists;
 	if ((rc = sort_tasks_begin(ctx, n, &counts, &lists))) return rc;
 	uint32_t *hist = counts + 16;
 	uint16_t *binkey = (uint16_t *)(hist + (size_t)kSortBins * kSortKeys);
-	long long cg = (n_eff + 1023) / 1024;
-	if (cg > kSortBlocks) cg = kSortBlocks;
-	if (cg < 1) cg = 1;
-	hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)cg), dim3(kSortThreads), 0, ctx->stream, d_tasks, d_order, (long long)n,
-	                   hist, binkey, mode, d_n, wide, ctx->dev.max_mat, qmax, d_res, ctx->d_err);
-	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg, d_n))) return rc;
+	const unsigned cg = sort_blocks_for(pl.n_eff);
+	const ExtBinRule rule = {pl.mode, pl.wide, ctx->dev.max_mat, qmax, d_res, ctx->d_err};
+	hipLaunchKernelGGL(sort_hist_kernel, dim3(cg), dim3(kSortThreads), 0, ctx->stream, d_tasks, d_order, (long long)n, hist, binkey,
+	                   rule, d_n);
+	if ((rc = sort_tasks_finish(ctx, n, d_order, cg, d_n))) return rc;
+	return extend_run_bins(ctx, d_pool, d_tasks, n, d_res, qmax, kind, pl);
+}
+
+int extend_binned_begin(bmh_ctx *ctx, int64_t n, bmh_ext_result_t *d_res, int qmax, int kind, ExtBinned *p)
+{
+	ExtPlan pl;
+	int rc = extend_plan(ctx, n, kind, true, &pl);
+	if (rc) return rc;
+	uint32_t *counts, *lists;
+	if ((rc = sort_tasks_begin(ctx, n, &counts, &lists))) return rc;
+	// a batch the hint calls (almost) empty: every task to bin 5, whose list the any-length kernel then walks in ONE launch
+	p->tiny = pl.tiny;
+	p->rule = ExtBinRule{pl.tiny ? 1 : pl.mode, pl.wide, ctx->dev.max_mat, qmax, d_res, ctx->d_err};
+	p->hist = counts + 16;
+	p->binkey = (uint16_t *)(p->hist + (size_t)kSortBins * kSortKeys);
+	p->blocks = sort_blocks_for(n);
+	return BMH_OK;
+}
+
+int extend_binned_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
+                         int qmax, int kind, const ExtBinned &p, uint32_t *d_total)
+{
+	int rc = sort_tasks_finish(ctx, n, nullptr, p.blocks, nullptr, d_total); // (the position in binkey[] is the task index)
+	if (rc) return rc;
+	if (p.tiny) {
+		uint32_t *counts = (uint32_t *)ctx->d_bins.p;
+		const uint32_t *lists = counts + 16 + (size_t)kSortBins * kSortKeys + ((size_t)n + 1) / 2 + 1;
+		if ((rc = launch_extend_lds(ctx, d_pool, d_tasks, n, d_res, lists + (size_t)5 * (size_t)n, counts + 5, qmax, 2 * kTinyList))) return rc;
+		return hint_post(ctx, kind, counts); // (all of it in bin 5: the total is what the next decision needs)
+	}
+	const ExtPlan pl = {p.rule.wide, p.rule.mode, false, n};
+	return extend_run_bins(ctx, d_pool, d_tasks, n, d_res, qmax, kind, pl);
+}
+
+// the second half: the bins stand in ctx->d_bins (sizes, cursors, lists), enqueued on ctx->stream
+static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
+                           int qmax, int kind, const ExtPlan &pl)
+{
+	int rc;
+	const int wide = pl.wide, mode = pl.mode;
+	const size_t N = (size_t)n;
+	uint32_t *counts = (uint32_t *)ctx->d_bins.p, *hist = counts + 16;
+	const uint32_t *lists = hist + (size_t)kSortBins * kSortKeys + (N + 1) / 2 + 1;
+	const bmh_ctx::BinHint &hint = ctx->hint[kind];
+	// expected size of bin b: the previous launch's count with a margin -- or, with no hint, the whole batch
+	int64_t est[kExtBins];
+	for (int b = 0; b < kExtBins; ++b) est[b] = hint.valid ? std::min<int64_t>(n, (int64_t)hint.cnt[b] + (hint.cnt[b] >> 4) + 64) : n;
 	if ((rc = hint_post(ctx, kind, counts))) return rc;
 	const bool tm = ctx->timing;
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));

@@ -3,24 +3,26 @@
 //
 // The fork sketched this record as ext_param_t / ext_res_t (bwamem.c:553-577: both flanks of a seed in, the finished
 // region out) and never used it.  On the device it is FOUR dependent rounds of ksw_extend2 batches, each one a run of the
-// length-sorted lane-per-task kernels of extend_dispatch.hip over a task list that the previous round's results
+// length-sorted lane-per-task kernels of extend_dispatch.hip over the tasks that the previous round's results
 // produced -- built by the small kernels below, on the device:
 //
-//   seed_left_make    left task of every seed with qbeg > 0 (reversed flanks, h0 = len*a, end_bonus = pen_clip5,
-//                     band w), bwamem.c:810-826; seeds without a left flank get score = truesc = len*a (:839)
-//   round L1          ksw_extend2 x (#left tasks)
-//   seed_try<LEFT>    the retry rule of bwamem.c:828 (prev = -1, so: max_off >= 3w/4) -> compact list of tasks at 2w
-//   round L2          ksw_extend2 x (#retries), usually a handful
-//   seed_right_make   clip-or-reach-the-end decision of the left side (:831-837) from the LAST try's outputs; right
-//                     task (forward flanks, h0 = sc0 = the left score, end_bonus = pen_clip3), :841-854; seeds that
-//                     end at the read end are finished here (:866)
-//   round R1          ksw_extend2 x (#right tasks)
-//   seed_try<RIGHT>   retry rule of :856 (prev = sc0): score != sc0 && max_off >= 3w/4
+//   seed_left_make_bin   left task of every seed with qbeg > 0 (reversed flanks, h0 = len*a, end_bonus = pen_clip5,
+//                        band w), bwamem.c:810-826; seeds without a left flank get score = truesc = len*a (:839).
+//                        The same pass is the FIRST pass of the dispatcher's sort: bin and sort key of the task it made
+//   round L1             ksw_extend2 x (#left tasks)
+//   seed_try<LEFT>       the retry rule of bwamem.c:828 (prev = -1, so: max_off >= 3w/4) -> compact list of tasks at 2w
+//   round L2             ksw_extend2 x (#retries), usually a handful
+//   seed_right_make_bin  clip-or-reach-the-end decision of the left side (:831-837) from the LAST try's outputs; right
+//                        task (forward flanks, h0 = sc0 = the left score, end_bonus = pen_clip3), :841-854; seeds that
+//                        end at the read end are finished here (:866).  Again the sort's first pass as well
+//   round R1             ksw_extend2 x (#right tasks)
+//   seed_try<RIGHT>      retry rule of :856 (prev = sc0): score != sc0 && max_off >= 3w/4
 //   round R2
-//   seed_finish       the right side's decision (:859-865), a->w = max(aw0, aw1) (:875)
+//   seed_finish          the right side's decision (:859-865), a->w = max(aw0, aw1) (:875)
 //
-// Lists are appended with one atomic per wave (ballot + mbcnt); the dispatcher reads their lengths from device memory,
-// so the host never learns them and never waits.
+// The big rounds keep their tasks at the seeds' own indices (T[i], X[i]) and need no list: the sort places index i of
+// every seed that has the task.  The retry lists are appended with one atomic per wave (ballot + mbcnt); the dispatcher
+// reads their lengths, and every bin's size, from device memory, so the host never learns them and never waits.
 #include <algorithm>
 
 #include "bmh_ctx.h"
@@ -59,19 +61,52 @@ __device__ __forceinline__ void store_task(bmh_ext_task_t *t, uint64_t q_off, ui
 	p[1] = make_uint4((uint32_t)qlen | (uint32_t)tlen << 16, (uint32_t)h0, (uint32_t)(w & 0xffff) | (uint32_t)end_bonus << 16, flags);
 }
 
-__global__ __launch_bounds__(256) void seed_left_make(const bmh_seed_task_t *__restrict__ S, long long n, SeedP sp,
-                                                      bmh_ext_task_t *__restrict__ T, uint32_t *__restrict__ L,
-                                                      uint32_t *__restrict__ cnt, SeedState *__restrict__ ST,
-                                                      int *__restrict__ err_flag)
+// The two big rounds' tasks are made AND binned in one pass of the dispatcher sort's shape (extend_binned_begin / _finish): at most
+// kSortBlocks blocks, each over a contiguous range of seeds with the sort's LDS histogram.  A seed with the flank stores its task in
+// T[i] and its bin and sort key -- from the lengths and h0 it holds in registers, by the dispatcher's rule -- in binkey[i]; a seed
+// without one stores kNoTask, which the sort's last pass skips.  1024 threads: the histogram's 64 KiB allow two blocks per CU, and a
+// pass that streams ~100 bytes per seed wants all 32 wave slots of the CU.
+constexpr int kMakeThreads = 1024;
+
+struct MakeBin { // the LDS histogram around the per-seed body
+	uint32_t *lh;
+	__device__ __forceinline__ void begin()
+	{
+		for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += kMakeThreads) lh[t] = 0;
+		__syncthreads();
+	}
+	__device__ __forceinline__ void put(const ExtBinned &b, long long i, bool has, int qlen, int tlen, int h0)
+	{
+		uint16_t bk = kNoTask;
+		if (has) {
+			bk = (uint16_t)ext_binkey_of(b.rule, qlen, tlen, h0, (size_t)i);
+			atomicAdd(&lh[bk], 1u);
+		}
+		b.binkey[i] = bk;
+	}
+	__device__ __forceinline__ void end(const ExtBinned &b)
+	{
+		__syncthreads();
+		for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += kMakeThreads)
+			if (lh[t]) atomicAdd(&b.hist[t], lh[t]);
+	}
+};
+
+__global__ __launch_bounds__(kMakeThreads) void seed_left_make_bin(const bmh_seed_task_t *__restrict__ S, long long n, SeedP sp,
+                                                                   bmh_ext_task_t *__restrict__ T, SeedState *__restrict__ ST,
+                                                                   ExtBinned bin)
 {
-	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-	bool has = false;
-	if (i < n) {
+	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
+	MakeBin mb = {lh};
+	mb.begin();
+	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
+	for (long long i = lo + threadIdx.x; i < hi; i += kMakeThreads) {
 		const bmh_seed_task_t s = S[i];
 		const int rq = s.l_query - s.qbeg - s.len, rt = s.wlen - s.rbeg - s.len;
+		bool has = false;
 		if (s.qbeg < 0 || s.len <= 0 || rq < 0 || s.rbeg < 0 || rt < 0 || s.qbeg > 65535 || rq > 65535 || s.rbeg > 65535 || rt > 65535 ||
 		    (long long)s.l_query * max(sp.max_mat, sp.a) > sp.limit || s.qbeg > sp.qmax || rq > sp.qmax) {
-			atomicExch(err_flag, BMH_E_RANGE);
+			atomicExch(bin.rule.err_flag, BMH_E_RANGE);
 			SeedState st = {0, 0, -1, -1, sp.w, 0xffffffffu}; // poisoned: later stages skip the seed
 			ST[i] = st;
 		} else if (s.qbeg > 0) { // bwamem.c:810-826
@@ -85,9 +120,9 @@ __global__ __launch_bounds__(256) void seed_left_make(const bmh_seed_task_t *__r
 			SeedState st = {0, 0, s.len * sp.a, s.len * sp.a, sp.w, 0};
 			ST[i] = st;
 		}
+		mb.put(bin, i, has, s.qbeg, s.rbeg, s.len * sp.a);
 	}
-	const uint32_t pos = wave_append(has, &cnt[0]);
-	if (has) L[pos] = (uint32_t)i;
+	mb.end(bin);
 }
 
 // the band-doubling rule (bwamem.c:828 for the left side, :856 for the right): the tasks that must run again at 2w
@@ -119,17 +154,20 @@ __global__ __launch_bounds__(256) void seed_try(const bmh_seed_task_t *__restric
 	}
 }
 
-__global__ __launch_bounds__(256) void seed_right_make(const bmh_seed_task_t *__restrict__ S, long long n, SeedP sp,
-                                                       const bmh_ext_result_t *__restrict__ X, const bmh_ext_result_t *__restrict__ X2,
-                                                       bmh_ext_task_t *__restrict__ T, uint32_t *__restrict__ L,
-                                                       uint32_t *__restrict__ cnt, SeedState *__restrict__ ST,
-                                                       bmh_seed_result_t *__restrict__ R)
+// (X is read here and, for a task past qmax, written through bin.rule.out: no __restrict__ on it)
+__global__ __launch_bounds__(kMakeThreads) void seed_right_make_bin(const bmh_seed_task_t *__restrict__ S, long long n, SeedP sp,
+                                                                    const bmh_ext_result_t *X, const bmh_ext_result_t *__restrict__ X2,
+                                                                    bmh_ext_task_t *__restrict__ T, SeedState *__restrict__ ST,
+                                                                    bmh_seed_result_t *__restrict__ R, ExtBinned bin)
 {
-	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-	bool has = false;
-	if (i < n) {
+	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
+	MakeBin mb = {lh};
+	mb.begin();
+	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
+	for (long long i = lo + threadIdx.x; i < hi; i += kMakeThreads) {
 		const bmh_seed_task_t s = S[i];
 		SeedState st = ST[i];
+		bool has = false;
 		if (st.r2 == 0xffffffffu) {
 			bmh_seed_result_t r = {0, 0, 0, 0, INT32_MIN, INT32_MIN, 0, 0};
 			R[i] = r;
@@ -156,9 +194,9 @@ __global__ __launch_bounds__(256) void seed_right_make(const bmh_seed_task_t *__
 			}
 			ST[i] = st;
 		}
+		mb.put(bin, i, has, s.l_query - s.qbeg - s.len, s.wlen - s.rbeg - s.len, st.sc0);
 	}
-	const uint32_t pos = wave_append(has, &cnt[2]);
-	if (has) L[pos] = (uint32_t)i;
+	mb.end(bin);
 }
 
 __global__ __launch_bounds__(256) void seed_finish(const bmh_seed_task_t *__restrict__ S, long long n, SeedP sp,
@@ -184,7 +222,7 @@ __global__ __launch_bounds__(256) void seed_finish(const bmh_seed_task_t *__rest
 struct SeedWs {
 	bmh_ext_task_t *T, *T2;
 	bmh_ext_result_t *X, *X2;
-	uint32_t *L, *cnt;
+	uint32_t *cnt;
 	SeedState *ST;
 };
 
@@ -197,18 +235,19 @@ static int seed_workspace(bmh_ctx *ctx, int64_t n, SeedWs *w)
 		off = (off + bytes + a256) & ~a256;
 		return o;
 	};
-	const size_t oc = take(64), oT = take(N * 32), oT2 = take(N * 32), oX = take(N * 24), oX2 = take(N * 24), oL = take(N * 4),
+	const size_t oc = take(64), oT = take(N * 32), oT2 = take(N * 32), oX = take(N * 24), oX2 = take(N * 24),
 	             oS = take(N * sizeof(SeedState));
 	int rc = ensure(ctx, ctx->d_seedws, off);
 	if (rc) return rc;
 	uint8_t *b = (uint8_t *)ctx->d_seedws.p;
 	w->cnt = (uint32_t *)(b + oc), w->T = (bmh_ext_task_t *)(b + oT), w->T2 = (bmh_ext_task_t *)(b + oT2);
-	w->X = (bmh_ext_result_t *)(b + oX), w->X2 = (bmh_ext_result_t *)(b + oX2), w->L = (uint32_t *)(b + oL), w->ST = (SeedState *)(b + oS);
+	w->X = (bmh_ext_result_t *)(b + oX), w->X2 = (bmh_ext_result_t *)(b + oX2), w->ST = (SeedState *)(b + oS);
 	return BMH_OK;
 }
 
-// everything is enqueued on ctx->stream; the list lengths stay on the device (ws.cnt[0..3]: left, left retries, right,
-// right retries -- read back by the host-buffer entry point for its statistics only)
+// everything is enqueued on ctx->stream; the task counts stay on the device (ws.cnt[0..3]: left, left retries, right,
+// right retries -- read back by the host-buffer entry point for its statistics only; the two big rounds' are the sums of
+// their bin sizes, which the sort's scan pass leaves there)
 int launch_seedext(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_seed_task_t *d_tasks, int64_t n, bmh_seed_result_t *d_res,
                    int qmax)
 {
@@ -236,15 +275,18 @@ int launch_seedext(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_seed_task_t *d
 	} while (0)
 	BMH_HIP(ctx, hipMemsetAsync(ws.cnt, 0, 64, s));
 	BMH_SROUND(0);
-	hipLaunchKernelGGL(seed_left_make, dim3(grid), dim3(256), 0, s, d_tasks, (long long)n, sp, ws.T, ws.L, ws.cnt, ws.ST, ctx->d_err);
-	if ((rc = launch_extend(ctx, d_pool, ws.T, n, ws.X, ws.L, qmax, ws.cnt + 0, 1))) return rc;
+	ExtBinned bin;
+	if ((rc = extend_binned_begin(ctx, n, ws.X, qmax, 1, &bin))) return rc;
+	hipLaunchKernelGGL(seed_left_make_bin, dim3(bin.blocks), dim3(kMakeThreads), 0, s, d_tasks, (long long)n, sp, ws.T, ws.ST, bin);
+	if ((rc = extend_binned_finish(ctx, d_pool, ws.T, n, ws.X, qmax, 1, bin, ws.cnt + 0))) return rc;
 	BMH_SROUND(1);
 	hipLaunchKernelGGL(seed_try<false>, dim3(grid), dim3(256), 0, s, d_tasks, (long long)n, sp, ws.T, ws.X, ws.T2, ws.cnt, ws.ST);
 	if ((rc = launch_extend(ctx, d_pool, ws.T2, n, ws.X2, nullptr, qmax, ws.cnt + 1, 2))) return rc;
 	BMH_SROUND(2);
-	hipLaunchKernelGGL(seed_right_make, dim3(grid), dim3(256), 0, s, d_tasks, (long long)n, sp, ws.X, ws.X2, ws.T, ws.L, ws.cnt, ws.ST,
-	                   d_res);
-	if ((rc = launch_extend(ctx, d_pool, ws.T, n, ws.X, ws.L, qmax, ws.cnt + 2, 3))) return rc;
+	if ((rc = extend_binned_begin(ctx, n, ws.X, qmax, 3, &bin))) return rc;
+	hipLaunchKernelGGL(seed_right_make_bin, dim3(bin.blocks), dim3(kMakeThreads), 0, s, d_tasks, (long long)n, sp, ws.X, ws.X2, ws.T,
+	                   ws.ST, d_res, bin);
+	if ((rc = extend_binned_finish(ctx, d_pool, ws.T, n, ws.X, qmax, 3, bin, ws.cnt + 2))) return rc;
 	BMH_SROUND(3);
 	hipLaunchKernelGGL(seed_try<true>, dim3(grid), dim3(256), 0, s, d_tasks, (long long)n, sp, ws.T, ws.X, ws.T2, ws.cnt, ws.ST);
 	if ((rc = launch_extend(ctx, d_pool, ws.T2, n, ws.X2, nullptr, qmax, ws.cnt + 3, 4))) return rc;
