@@ -186,6 +186,9 @@ def lib():
         L.bmh_chain2aln_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_driver_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_chains2regs_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.bmh_chains2regs_device.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.bmh_seed_chain_regs_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_region_cigar_batch.restype = C.c_int
@@ -631,6 +634,86 @@ class Context:
             out.append(a)
         self._check(rc)
         return out
+
+    @staticmethod
+    def _c_reads_chains(reads, chains):
+        """(keep-alive list, bmh_read_t[n], bmh_chain_v[n] or None) of lists of code arrays / per read lists of SEED arrays."""
+        n = len(reads)
+        keep = []
+        c_reads = (_Read * max(n, 1))()
+        c_chv = (_ChainV * max(n, 1))() if chains is not None else None
+        for r in range(n):
+            seq = np.ascontiguousarray(reads[r], dtype=np.uint8)
+            keep.append(seq)
+            c_reads[r].l_seq, c_reads[r].seq = len(seq), seq.ctypes.data
+            if chains is None:
+                continue
+            arr = (_Chain * max(len(chains[r]), 1))()
+            for ci, seeds in enumerate(chains[r]):
+                sd = np.ascontiguousarray(seeds, dtype=SEED)
+                keep.append(sd)
+                arr[ci].n = arr[ci].m = len(sd)
+                arr[ci].pos = int(sd["rbeg"][0]) if len(sd) else 0
+                arr[ci].seeds = sd.ctypes.data
+            keep.append(arr)
+            c_chv[r].n = c_chv[r].m = len(chains[r])
+            c_chv[r].a = C.cast(arr, C.POINTER(_Chain))
+        return keep, c_reads, c_chv
+
+    def _take_regs(self, c_regs, n, rc):
+        """bmh_alnreg_v[n] -> per read an ALNREG array; frees the C allocations, then raises on rc."""
+        out = []
+        for r in range(n):
+            k = c_regs[r].n
+            a = np.zeros(k, dtype=ALNREG)
+            if k:
+                C.memmove(a.ctypes.data, c_regs[r].a, k * ALNREG.itemsize)
+            if c_regs[r].a:
+                _libc.free(c_regs[r].a)
+            out.append(a)
+        self._check(rc)
+        return out
+
+    def chains2regs_batch(self, l_pac, pac, reads, chains, min_seed_len):
+        """bmh_chains2regs_batch, the host driver: mem_chain2aln_short + mem_chain2aln per chain (min_seed_len >= 1).
+        Returns per read an ALNREG array."""
+        n = len(reads)
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        keep, c_reads, c_chv = self._c_reads_chains(reads, chains)
+        c_regs = (_AlnregV * max(n, 1))()
+        rc = lib().bmh_chains2regs_batch(self._h, int(l_pac), _ptr(pac), n, C.cast(c_reads, C.c_void_p), C.cast(c_chv, C.c_void_p),
+                                         int(min_seed_len), C.cast(c_regs, C.c_void_p))
+        return self._take_regs(c_regs, n, rc)
+
+    def chains2regs_device(self, l_pac, reads, chains, min_seed_len=0, regs_in=None):
+        """bmh_chains2regs_device: the same driver as kernels, against the resident reference (set_pac).  min_seed_len = 0: no
+        short-chain pre-step.  regs_in (test hook): per read an ALNREG array the call finds in regs[r]; it must refuse them."""
+        n = len(reads)
+        keep, c_reads, c_chv = self._c_reads_chains(reads, chains)
+        c_regs = (_AlnregV * max(n, 1))()
+        for r, a in enumerate(regs_in or []):
+            a = np.ascontiguousarray(a, dtype=ALNREG)
+            if len(a):
+                c_regs[r].n = c_regs[r].m = len(a)
+                c_regs[r].a = _libc.malloc(len(a) * ALNREG.itemsize)
+                C.memmove(c_regs[r].a, a.ctypes.data, len(a) * ALNREG.itemsize)
+        rc = lib().bmh_chains2regs_device(self._h, int(l_pac), n, C.cast(c_reads, C.c_void_p), C.cast(c_chv, C.c_void_p),
+                                          int(min_seed_len), C.cast(c_regs, C.c_void_p))
+        return self._take_regs(c_regs, n, rc)
+
+    def seed_chain_regs_batch(self, smem_opt, chain_opt, l_pac, reads, min_seed_len=0):
+        """bmh_seed_chain_regs_batch: seeding, chaining and the chains-to-regions driver in one call; only regions come back.
+        Returns per read an ALNREG array."""
+        n = len(reads)
+        o_in, so = np.asarray(smem_opt), np.zeros((), dtype=SMEM_OPT)
+        for k in o_in.dtype.names:
+            so[k] = o_in[k]
+        co = np.ascontiguousarray(np.asarray(chain_opt, dtype=CHAIN_OPT).reshape(()))
+        keep, c_reads, _ = self._c_reads_chains(reads, None)
+        c_regs = (_AlnregV * max(n, 1))()
+        rc = lib().bmh_seed_chain_regs_batch(self._h, _ptr(so), _ptr(co), C.c_int64(int(l_pac)), n, C.cast(c_reads, C.c_void_p),
+                                             int(min_seed_len), C.cast(c_regs, C.c_void_p))
+        return self._take_regs(c_regs, n, rc)
 
     def reg2cigar_batch(self, l_pac, pac, reads, reqs):
         """Batched mem_reg2aln band/retry loop over bwa_gen_cigar2 (reference bwamem.c:1187-1201, bwa.c:89-172).

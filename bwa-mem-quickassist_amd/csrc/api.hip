@@ -294,7 +294,7 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	if (ctx->stream) (void)stream_wait(ctx, ctx->stream);
 	free_buf(ctx->d_pool), free_buf(ctx->d_tasks), free_buf(ctx->d_res), free_buf(ctx->d_order);
 	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
-	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab);
+	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab), free_buf(ctx->d_c2r);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
 	free_buf(ctx->d_swl);

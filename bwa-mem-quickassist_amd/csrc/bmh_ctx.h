@@ -91,6 +91,7 @@ struct bmh_ctx {
 	DevBuf d_chain;                // device chainer (chain.hip): per-read bounds, arena, compact output
 	hipEvent_t ev_chain[2] = {};   // around its chain kernel (timing mode)
 	bmh_chain_stats_t cstats{-1, -1, -1, -1, -1, -1.f};
+	DevBuf d_c2r; // chains to regions on the device (chain2reg.hip): status words, chain records, keys, tasks, results, regions
 	// int32 extension kernel (extend_wide.hip), opt-in: bmh_ctx_set_wide_extension
 	bool wide_ext = false;
 	bool wide_last = false;           // the last extension launch (a flat batch, or the four rounds of a fused call) ran with it on
@@ -139,7 +140,25 @@ struct DevSeedTables {
 	const bmh_smem_intv_t *intv;
 	const uint64_t *sa_off, *sa_pos; // per interval: where its positions start (UINT64_MAX: none); the positions
 	uint64_t n_calls, n_intv, n_pos;
+	const uint8_t *pool;      // the reads as the seeding stage uploaded them, base codes, ...
+	const uint64_t *read_off; // ... read r at pool + read_off[r]; at least 16 bytes of padding behind the last one
+	// Everything here points into ctx->d_scratch (the chainer's output into ctx->d_chain): a consumer must neither grow nor write
+	// d_scratch while it reads them.  The chains-to-regions driver relies on that: it gives launch_sw explicit caps, so that its
+	// cap reduction in d_scratch is not taken, and calls nothing else that uses d_scratch (today: launch_global's slab only).
 };
+// the device chainer's compact output where chain_place_kernel leaves it (in ctx->d_chain): per read the exclusive sums of its chains
+// and kept seeds, per chain its seed count, the seeds; n_keys: per read its chains before the filter
+struct DevChains {
+	int n_reads;
+	const unsigned long long *coff, *soff; // n_reads + 1 each
+	const uint32_t *cn;
+	const bmh_seed_t *seeds;
+	const uint32_t *n_keys;
+	unsigned long long tc, ts; // chains and seeds of the batch
+	unsigned long long n_equal; // look-ups that met an equal key
+	float kernel_ms;            // the chain kernel's duration with kernel timing on, else -1
+};
+int chain_compact_device(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const DevSeedTables &t, DevChains *out);
 typedef int (*SeedTablesFn)(bmh_ctx *ctx, const DevSeedTables &t, void *user);
 // bmh_seed_batch up to its device tables, then fn on them (on the context's stream, inside the same gate); returns fn's result.
 // Capacities grow inside; env BMH_CHAIN_INIT_CAP (test knob) starts them at that many entries.

@@ -111,9 +111,10 @@ using namespace bmh;
 
 namespace {
 
-// device tables -> chains on the host (the rest of both entry points)
+// device tables -> compact chains on the device (what every entry point starts with): sizes, arena, chain_kernel, count -> scan -> place,
+// then the error flag and the totals.  The chain statistics are the caller's to set, once its call has succeeded.
 // seed_bound: the batch's sum of the per-read seed bounds (positions of the long and rare intervals) -- the arena's size
-int chain_device(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const ChainIn &in, uint64_t seed_bound, bmh_chain_v *chains)
+int chain_compact(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const ChainIn &in, uint64_t seed_bound, DevChains *out)
 {
 	const int n = in.n_reads;
 	const unsigned long long seed_cap = std::max<unsigned long long>(seed_bound, 1);
@@ -182,14 +183,30 @@ int chain_device(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const Ch
 		ctx->last_error = "chaining: the seeding tables are inconsistent (call list out of smem_next2's order, or an interval without its positions)";
 		return BMH_E_ARG;
 	}
+	*out = DevChains{n, (const unsigned long long *)(d + o_coff), (const unsigned long long *)(d + o_soff), (const uint32_t *)(d + o_outn),
+	                 (const bmh_seed_t *)(d + o_outs), (const uint32_t *)(d + o_nkeys), tc, ts, n_equal, -1.f};
+	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&out->kernel_ms, ctx->ev_chain[0], ctx->ev_chain[1]));
+	return BMH_OK;
+}
+
+// device tables -> chains on the host (the rest of bmh_chain_batch and bmh_seed_chain_batch)
+int chain_device(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const ChainIn &in, uint64_t seed_bound, bmh_chain_v *chains)
+{
+	const int n = in.n_reads;
+	const size_t nr1 = (size_t)n + 1;
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	DevChains dc;
+	int rc;
+	if ((rc = chain_compact(ctx, o, l_pac, in, seed_bound, &dc))) return rc;
+	const unsigned long long tc = dc.tc, ts = dc.ts;
 	const size_t b_off = al(nr1 * 8), b_keys = al(nr1 * 4), b_n = al(tc * 4), b_s = tc ? ts * sizeof(bmh_seed_t) : 0;
 	if ((rc = ensure_host(ctx, ctx->h_down, 2 * b_off + b_keys + b_n + b_s + 64))) return rc;
-	h = (uint8_t *)ctx->h_down.p;
-	BMH_HIP(ctx, hipMemcpyAsync(h, d + o_coff, nr1 * 8, hipMemcpyDeviceToHost, ctx->stream));
-	BMH_HIP(ctx, hipMemcpyAsync(h + b_off, d + o_soff, nr1 * 8, hipMemcpyDeviceToHost, ctx->stream));
-	BMH_HIP(ctx, hipMemcpyAsync(h + 2 * b_off, d + o_nkeys, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-	if (tc) BMH_HIP(ctx, hipMemcpyAsync(h + 2 * b_off + b_keys, d + o_outn, tc * 4, hipMemcpyDeviceToHost, ctx->stream));
-	if (b_s) BMH_HIP(ctx, hipMemcpyAsync(h + 2 * b_off + b_keys + b_n, d + o_outs, b_s, hipMemcpyDeviceToHost, ctx->stream));
+	uint8_t *h = (uint8_t *)ctx->h_down.p;
+	BMH_HIP(ctx, hipMemcpyAsync(h, dc.coff, nr1 * 8, hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, hipMemcpyAsync(h + b_off, dc.soff, nr1 * 8, hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, hipMemcpyAsync(h + 2 * b_off, dc.n_keys, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	if (tc) BMH_HIP(ctx, hipMemcpyAsync(h + 2 * b_off + b_keys, dc.cn, tc * 4, hipMemcpyDeviceToHost, ctx->stream));
+	if (b_s) BMH_HIP(ctx, hipMemcpyAsync(h + 2 * b_off + b_keys + b_n, dc.seeds, b_s, hipMemcpyDeviceToHost, ctx->stream));
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
 	const unsigned long long *coff = (const unsigned long long *)h, *soff = (const unsigned long long *)(h + b_off);
 	const uint32_t *nkeys = (const uint32_t *)(h + 2 * b_off), *cn = (const uint32_t *)(h + 2 * b_off + b_keys);
@@ -204,22 +221,32 @@ int chain_device(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const Ch
 		}
 	}
 	ctx->cstats.reads = n, ctx->cstats.chains_in = before, ctx->cstats.chains_out = (int64_t)tc, ctx->cstats.seeds = (int64_t)ts;
-	ctx->cstats.equal_keys = (int64_t)n_equal;
-	ctx->cstats.kernel_ms = -1.f;
-	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->cstats.kernel_ms, ctx->ev_chain[0], ctx->ev_chain[1]));
+	ctx->cstats.equal_keys = (int64_t)dc.n_equal;
+	ctx->cstats.kernel_ms = dc.kernel_ms;
 	return BMH_OK;
+}
+
+ChainIn chain_in_of(const DevSeedTables &t)
+{
+	return ChainIn{t.n_reads, t.len, {t.coff, t.calls, t.ioff, t.intv, t.sa_off, t.sa_pos, t.n_calls, t.n_intv, t.n_pos}};
 }
 
 int seed_chain_cb(bmh_ctx *ctx, const DevSeedTables &t, void *user)
 {
 	const auto *u = (const std::pair<const bmh_chain_opt_t *, std::pair<int64_t, bmh_chain_v *>> *)user;
-	const ChainIn in{t.n_reads, t.len, {t.coff, t.calls, t.ioff, t.intv, t.sa_off, t.sa_pos, t.n_calls, t.n_intv, t.n_pos}};
-	return chain_device(ctx, u->first, u->second.first, in, t.n_pos, u->second.second); // (sa_of_intervals_kernel used the same two filters)
+	return chain_device(ctx, u->first, u->second.first, chain_in_of(t), t.n_pos, u->second.second); // (sa_of_intervals_kernel used the same two filters)
 }
 
 bool chain_opt_ok(const bmh_chain_opt_t *o) { return o && o->min_seed_len >= 0 && o->max_occ >= 0; }
 
 } // namespace
+
+// the fused seeding -> chaining -> regions call (chain2reg.hip) stops here: the compact chains stay in ctx->d_chain
+int bmh::chain_compact_device(bmh_ctx *ctx, const bmh_chain_opt_t *o, int64_t l_pac, const DevSeedTables &t, DevChains *out)
+{
+	if (!chain_opt_ok(o)) return BMH_E_ARG;
+	return chain_compact(ctx, o, l_pac, chain_in_of(t), t.n_pos, out);
+}
 
 extern "C" {
 

@@ -1,0 +1,582 @@
+// chain2reg.hip -- chains to regions on the device: the per-read driver of mem_chain2aln (reference bwa-0.7.8/bwamem.c:730-878) and
+// mem_chain2aln_short (:495-542), i.e. everything chains2regs() of host/chain2aln_batch.c does, without the chains, tasks, results or
+// regions ever visiting the host.  The arithmetic both drivers must agree on is one text, host/chain2aln_core.h.
+//
+// Input: the device chainer's compact output where chain_place_kernel leaves it (DevChains: per read coff / soff, per chain its seed
+// count, the seeds) and the reads as a pool with per-read offsets and lengths.  One lane per read throughout, like chain_kernel.
+//
+//   c2r_window_kernel   per chain: the window [rmax0, rmax1) (bwamem.c:740-755), the short-chain qualifying test and the bmh_sw_task_t
+//                       of its ksw_align2 (appended with an atomic counter: results are addressed through the index kept in the
+//                       chain's record, so append order never reaches the output), the chain's (len, index) keys in ascending order,
+//                       and the round-1 bmh_seed_task_t of the seed the reference extends first -- the task of flat chain c at
+//                       index c, so round 1 has exactly tc tasks, which the host knows
+//   launch_sw           the short chains' Smith-Watermans
+//   loop                launch_seedext on the new tail of the task array, then c2r_replay_kernel: run_read()'s state machine
+//                       {st, ci, k} kept in device memory between launches.  A read that needs a result that is not there stops and
+//                       appends what the host driver requests (the seed it stopped at, the rest of its chain, the later chains, all
+//                       but the provably skipped seeds) behind the earlier rounds' tasks: ONE task array and ONE result array of ts
+//                       entries (every kept seed is requested at most once), so "the result is there" is index < tasks finished so far.
+//                       A per-seed word (task index + 1, 0 = never requested) is the host driver's have[].
+//                       The host reads back {tasks appended, reads stopped, error flag, short-chain tasks}: 16 bytes per round trip.
+//   gather              count -> scan -> place of the regions (each read wrote into its slice of the region arena, the soff prefix
+//                       sums: a read yields at most as many regions as it has kept seeds), then the counts and the compact records down.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "bmh_ctx.h"
+#include "bmh_device.h"
+#include "../host/chain2aln_core.h"
+
+namespace bmh {
+
+enum { C2R_NEXT_CHAIN = 0, C2R_NEXT_SEED = 1, C2R_DONE = 2 };
+// status words (uint32 index).  0..3 are what the host reads in the loop
+enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_STATUS_BYTES = 64 };
+
+struct C2rChain { // one chain's record, 64 bytes
+	int64_t rmax0, rmax1;
+	uint64_t seed_base; // flat index of its seed 0 (into seeds, keys and task words)
+	int64_t srb, sre;   // mem_chain2aln_short's reference interval ...
+	int32_t n;
+	int32_t sw_idx;     // ... and the index of its ksw_align2 in the short-chain tasks, -1 = it returns without one
+	int32_t sqb, sqe, seedcov, rsv;
+};
+static_assert(sizeof(C2rChain) == 64, "chain record");
+
+struct C2rState { // run_read()'s state between launches
+	int st, ci, k, rsv;
+};
+
+struct C2rIn {
+	int n_reads;
+	const uint64_t *read_off; // q_off of read r in the pool the extension kernels are given
+	const int *len;
+	const unsigned long long *coff, *soff; // n_reads + 1 each
+	const uint32_t *cn;
+	const bmh_seed_t *seeds;
+	unsigned long long tc, ts;
+	const uint32_t *n_keys; // per read its chains before the filter, summed for bmh_chain_stats; null: chains from the host
+};
+
+struct C2rWs {
+	uint32_t *status;
+	C2rChain *chn;           // tc
+	C2rState *state;         // n_reads
+	uint64_t *srt;           // ts: per chain its keys, 0 where the replay skipped a seed
+	uint32_t *slot;          // ts: task index + 1 of the seed's extension, 0 = not requested
+	bmh_seed_task_t *tasks;  // ts
+	bmh_seed_result_t *res;  // ts
+	bmh_sw_task_t *swt;      // tc
+	bmh_sw_result_t *swr;    // tc
+	bmh_alnreg_t *reg;       // ts: the region arena, read r's slice at soff[r]
+	unsigned long long *nreg, *roff; // n_reads + 1: regions per read, their exclusive sums
+	bmh_alnreg_t *out;       // ts: the compact regions
+};
+
+struct C2rSwRule { // what validate_sw (api.hip) checks per task of a host-fed batch
+	int msl;       // opt->min_seed_len, 0 = no short-chain pre-step
+	int max_mat;
+	int wide_sw, wraps;
+};
+
+__device__ __forceinline__ void c2r_fail(uint32_t *status, int code) { atomicCAS((int *)&status[C2R_ERR], 0, code); }
+
+// keys are unique, so any sort gives the reference's order: heapsort in place, no stack
+__device__ __forceinline__ void c2r_sort(uint64_t *a, int n)
+{
+	for (int start = n / 2 - 1, end = n; end > 1;) {
+		uint64_t v;
+		int root;
+		if (start >= 0) v = a[start], root = start--;
+		else v = a[--end], a[end] = a[0], root = 0;
+		for (;;) {
+			int ch = 2 * root + 1;
+			if (ch >= end) break;
+			if (ch + 1 < end && a[ch + 1] > a[ch]) ++ch;
+			if (a[ch] <= v) break;
+			a[root] = a[ch], root = ch;
+		}
+		a[root] = v;
+	}
+}
+
+// request() of the host driver without its bookkeeping: the fused record of seed s of chain c.  BMH_E_RANGE as there, BMH_E_ARG for a
+// seed that does not lie inside its read (what validate_seeds answers the host driver)
+__device__ __forceinline__ int c2r_task(const C2rChain &c, const bmh_seed_t &s, uint64_t q_off, int l_query, bmh_seed_task_t *t)
+{
+	if (l_query < 1 || s.qbeg < 0 || s.len < 1 || s.qbeg + s.len > l_query) return BMH_E_ARG; // (validate_seeds of the host-fed call)
+	if (s.rbeg < c.rmax0 || s.rbeg + s.len > c.rmax1 || c.rmax1 - c.rmax0 > 0x7fffffff) return BMH_E_RANGE;
+	t->q_off = q_off, t->t_off = (uint64_t)c.rmax0; // rseq[0], bwamem.c:757: the window is read from the resident reference
+	t->l_query = l_query, t->qbeg = s.qbeg, t->len = s.len;
+	t->rbeg = (int32_t)(s.rbeg - c.rmax0), t->wlen = (int32_t)(c.rmax1 - c.rmax0);
+	t->flags = BMH_F_TPAC, t->rsv_ = 0;
+	return 0;
+}
+
+__global__ __launch_bounds__(64) void c2r_window_kernel(bmh_params_t p, int64_t l_pac, C2rIn in, C2rWs ws, C2rSwRule sw)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r == 0) ws.status[C2R_N_TASKS] = (uint32_t)in.tc; // later rounds append behind round 1
+	if (r >= in.n_reads) return;
+	const C2rState st0 = {C2R_NEXT_CHAIN, -1, 0, 0};
+	ws.state[r] = st0, ws.nreg[r] = 0;
+	if (in.n_keys && in.n_keys[r]) atomicAdd((unsigned long long *)&ws.status[C2R_CHAINS_IN], (unsigned long long)in.n_keys[r]);
+	const int l_query = in.len[r];
+	const uint64_t q_off = in.read_off[r];
+	const unsigned long long c0 = in.coff[r], c1 = in.coff[r + 1], s1 = in.soff[r + 1];
+	unsigned long long sb = in.soff[r];
+	if (c1 > in.tc || s1 > in.ts || c0 > c1 || sb > s1) { c2r_fail(ws.status, BMH_E_ARG); ws.state[r].st = C2R_DONE; return; }
+	for (unsigned long long c = c0; c < c1; ++c) {
+		const int n = (int)in.cn[c];
+		C2rChain w = {0, 0, sb, 0, 0, n, -1, 0, 0, 0, 0};
+		if (n < 1 || sb + (unsigned long long)n > s1) { // (the compact form holds no empty chain)
+			c2r_fail(ws.status, BMH_E_ARG);
+			w.n = 0, ws.chn[c] = w;
+			continue;
+		}
+		const bmh_seed_t *sd = in.seeds + sb;
+		if (bmh_c2a_window(&p, l_pac, l_query, n, sd, &w.rmax0, &w.rmax1)) c2r_fail(ws.status, BMH_E_ARG);
+		bmh_c2a_short_t sc;
+		if (sw.msl > 0 && bmh_c2a_short_candidate(&p, l_pac, l_query, n, sd, &sc)) {
+			const uint32_t idx = atomicAdd(&ws.status[C2R_N_SHORT], 1u);
+			const int qlen = sc.sqe - sc.sqb;
+			const bool xbyte = qlen * p.a < 250;
+			w.sw_idx = (int32_t)idx, w.sqb = sc.sqb, w.sqe = sc.sqe, w.srb = sc.srb, w.sre = sc.sre, w.seedcov = sc.seedcov;
+			if ((!(sw.wide_sw && !xbyte) && (long long)qlen * sw.max_mat >= kScoreLimit) || (sw.wraps && xbyte)) c2r_fail(ws.status, BMH_E_RANGE);
+			if (idx < in.tc) { // bwamem.c:529-531
+				bmh_sw_task_t t;
+				t.q_off = q_off + (uint64_t)sc.sqb, t.t_off = (uint64_t)sc.srb;
+				t.tlen = (uint32_t)(sc.sre - sc.srb), t.qlen = (uint16_t)qlen, t.flags = BMH_F_TPAC;
+				t.xtra = BMH_SW_XSUBO | BMH_SW_XSTART | (xbyte ? BMH_SW_XBYTE : 0) | (uint32_t)(sw.msl * p.a);
+				t.rsv = 0;
+				ws.swt[idx] = t;
+			} else c2r_fail(ws.status, BMH_E_ARG);
+		}
+		ws.chn[c] = w;
+		// the (len, index) keys in the reference's order, bwamem.c:760-763; the last one is the seed it extends first
+		uint64_t *srt = ws.srt + sb;
+		for (int i = 0; i < n; ++i) srt[i] = (uint64_t)sd[i].len << 32 | (uint32_t)i, ws.slot[sb + i] = 0;
+		c2r_sort(srt, n);
+		const uint32_t top = (uint32_t)srt[n - 1];
+		bmh_seed_task_t t;
+		if (const int e = c2r_task(w, sd[top], q_off, l_query, &t)) {
+			c2r_fail(ws.status, e);
+			memset(&t, 0, sizeof(t));
+		}
+		ws.tasks[c] = t, ws.slot[sb + top] = (uint32_t)c + 1;
+		sb += (unsigned long long)n;
+	}
+}
+
+// appends the extension of seed si of chain c unless it was requested before
+__device__ __forceinline__ void c2r_request(const C2rIn &in, const C2rWs &ws, const C2rChain &c, int si, uint64_t q_off, int l_query)
+{
+	uint32_t *slot = &ws.slot[c.seed_base + (uint64_t)si];
+	if (*slot) return;
+	bmh_seed_task_t t;
+	if (const int e = c2r_task(c, in.seeds[c.seed_base + (uint64_t)si], q_off, l_query, &t)) { c2r_fail(ws.status, e); return; }
+	const uint32_t idx = atomicAdd(&ws.status[C2R_N_TASKS], 1u);
+	if (idx >= in.ts) { c2r_fail(ws.status, BMH_E_ARG); return; } // cannot happen: every seed is requested at most once
+	ws.tasks[idx] = t, *slot = idx + 1;
+}
+
+// run_read() of the host driver for every unfinished read, with the results of tasks [0, n_done).  ext_cnt: the four list lengths
+// of the launch_seedext just finished (null: none), added up for the statistics; ext_err: the extension kernels' error flag, moved
+// into the status words so that one read-back carries everything.
+__global__ __launch_bounds__(64) void c2r_replay_kernel(bmh_params_t p, C2rIn in, C2rWs ws, uint32_t n_done, const uint32_t *ext_cnt, int *ext_err)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r == 0) {
+		if (ext_cnt) *(unsigned long long *)&ws.status[C2R_EXT_TASKS] += (unsigned long long)ext_cnt[0] + ext_cnt[1] + ext_cnt[2] + ext_cnt[3];
+		const int e = *ext_err;
+		if (e) c2r_fail(ws.status, e), *ext_err = 0;
+	}
+	if (r >= in.n_reads) return;
+	C2rState s = ws.state[r];
+	if (s.st == C2R_DONE) return;
+	const unsigned long long c0 = in.coff[r], s0 = in.soff[r];
+	const int nc = (int)(in.coff[r + 1] - c0);
+	const size_t cap = (size_t)(in.soff[r + 1] - s0);
+	bmh_alnreg_t *av = ws.reg + s0;
+	size_t nav = (size_t)ws.nreg[r];
+	const int l_query = in.len[r];
+	const uint64_t q_off = in.read_off[r];
+	unsigned long long n_ext = 0, n_skip = 0;
+	bool stopped = false;
+	C2rChain c = ws.chn[c0 + (unsigned long long)(s.ci < 0 ? 0 : s.ci)]; // (a read without chains is done before it is looked at)
+	for (;;) {
+		if (s.st == C2R_NEXT_CHAIN) {
+			if (++s.ci >= nc) { s.st = C2R_DONE; break; }
+			c = ws.chn[c0 + (unsigned long long)s.ci];
+			if (c.sw_idx >= 0) { // the second half of mem_chain2aln_short, bwamem.c:533-541
+				const bmh_sw_result_t x = ws.swr[c.sw_idx];
+				if (!(x.tb < BMH_MEM_SHORT_EXT >> 1 || x.te > c.sre - c.srb - (BMH_MEM_SHORT_EXT >> 1))) {
+					if (nav >= cap) { c2r_fail(ws.status, BMH_E_ARG); s.st = C2R_DONE; break; }
+					bmh_alnreg_t a = {};
+					a.rb = c.srb + x.tb, a.re = c.srb + x.te + 1;
+					a.qb = c.sqb + x.qb, a.qe = c.sqb + x.qe + 1;
+					a.score = x.score, a.csub = x.score2, a.seedcov = c.seedcov;
+					av[nav++] = a;
+					continue; // the chain is settled
+				}
+			}
+			if (c.n == 0) continue; // bwamem.c:738
+			s.k = c.n - 1, s.st = C2R_NEXT_SEED;
+		} else {
+			if (s.k < 0) { s.st = C2R_NEXT_CHAIN; continue; }
+			uint64_t *srt = ws.srt + c.seed_base;
+			const bmh_seed_t *sd = in.seeds + c.seed_base;
+			const uint32_t si = (uint32_t)srt[s.k];
+			const bmh_seed_t sdk = sd[si];
+			if (bmh_c2a_seed_near_region(&p, &sdk, av, nav) && !bmh_c2a_has_conflicting_seed(sd, c.n, srt, s.k, &sdk)) {
+				srt[s.k] = 0; // bwamem.c:796-799
+				--s.k, ++n_skip;
+				continue;
+			}
+			const uint32_t tix = ws.slot[c.seed_base + si];
+			if (tix == 0 || tix - 1 >= n_done) { stopped = true; break; } // the device has not extended this seed yet
+			if (nav >= cap) { c2r_fail(ws.status, BMH_E_ARG); s.st = C2R_DONE; break; }
+			const bmh_seed_result_t x = ws.res[tix - 1];
+			bmh_alnreg_t a = {}; // bwamem.c:804-807
+			a.qb = x.qb, a.qe = x.qe, a.rb = c.rmax0 + x.rb, a.re = c.rmax0 + x.re; // bwamem.c:831-866
+			a.score = x.score, a.truesc = x.truesc, a.w = x.w;                      // ... and :875
+			a.seedcov = bmh_c2a_seedcov(sd, c.n, &a);
+			av[nav++] = a;
+			--s.k, ++n_ext;
+		}
+	}
+	if (stopped) { // what this read may still need: the seed it stopped at, the rest of its chain, the later chains
+		const uint64_t *srt = ws.srt + c.seed_base;
+		const bmh_seed_t *sd = in.seeds + c.seed_base;
+		c2r_request(in, ws, c, (int)(uint32_t)srt[s.k], q_off, l_query);
+		for (int kk = s.k - 1; kk >= 0; --kk) {
+			const int si = (int)(uint32_t)srt[kk];
+			if (bmh_c2a_seed_near_region(&p, &sd[si], av, nav) && !bmh_c2a_may_conflict(sd, c.n, si)) continue; // provably skipped
+			c2r_request(in, ws, c, si, q_off, l_query);
+		}
+		for (int ci = s.ci + 1; ci < nc; ++ci) {
+			const C2rChain c2 = ws.chn[c0 + (unsigned long long)ci];
+			const bmh_seed_t *sd2 = in.seeds + c2.seed_base;
+			for (int si = 0; si < c2.n; ++si) {
+				if (bmh_c2a_seed_near_region(&p, &sd2[si], av, nav) && !bmh_c2a_may_conflict(sd2, c2.n, si)) continue;
+				c2r_request(in, ws, c2, si, q_off, l_query);
+			}
+		}
+		atomicAdd(&ws.status[C2R_N_STOPPED], 1u);
+	}
+	ws.state[r] = s, ws.nreg[r] = nav;
+	if (n_ext) atomicAdd((unsigned long long *)&ws.status[C2R_EXTENDED], n_ext);
+	if (n_skip) atomicAdd((unsigned long long *)&ws.status[C2R_SKIPPED], n_skip);
+}
+
+// exclusive sums of one count array, n + 1 outputs (the last one is the total); one block of 1024 threads
+__global__ __launch_bounds__(1024) void c2r_scan(const unsigned long long *__restrict__ a, int n, unsigned long long *__restrict__ pa)
+{
+	__shared__ unsigned long long sa[1024];
+	const int t = threadIdx.x, per = (n + 1023) / 1024, lo = min(t * per, n), hi = min(lo + per, n);
+	unsigned long long xa = 0;
+	for (int k = lo; k < hi; ++k) xa += a[k];
+	sa[t] = xa;
+	__syncthreads();
+	for (int d = 1; d < 1024; d <<= 1) {
+		const unsigned long long ya = t >= d ? sa[t - d] : 0;
+		__syncthreads();
+		sa[t] += ya;
+		__syncthreads();
+	}
+	unsigned long long ca = sa[t] - xa;
+	for (int k = lo; k < hi; ++k) {
+		pa[k] = ca;
+		ca += a[k];
+	}
+	if (t == 1023) pa[n] = sa[1023];
+}
+
+// one lane per read copies its regions from its arena slice to the compact output
+static_assert(sizeof(bmh_alnreg_t) == 64, "c2r_place_kernel copies a region as four uint4");
+__global__ __launch_bounds__(64) void c2r_place_kernel(C2rIn in, C2rWs ws)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= in.n_reads) return;
+	const unsigned long long n = ws.nreg[r], o = ws.roff[r], s0 = in.soff[r];
+	if (o + n > in.ts || n > in.soff[r + 1] - s0) { c2r_fail(ws.status, BMH_E_ARG); return; }
+	const uint4 *src = (const uint4 *)(ws.reg + s0);
+	uint4 *dst = (uint4 *)(ws.out + o);
+	for (unsigned long long k = 0; k < n * 4; ++k) dst[k] = src[k];
+}
+
+} // namespace bmh
+
+using namespace bmh;
+
+namespace {
+
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct C2rLayout {
+	size_t status, chn, state, srt, slot, tasks, res, swt, swr, reg, nreg, roff, out, total;
+	C2rLayout(size_t n, size_t tc, size_t ts)
+	{
+		size_t o = 0;
+		auto take = [&](size_t bytes) {
+			const size_t at = o;
+			o += al256(bytes);
+			return at;
+		};
+		status = take(C2R_STATUS_BYTES), chn = take((tc + 1) * sizeof(C2rChain)), state = take(n * sizeof(C2rState)), srt = take(ts * 8);
+		slot = take(ts * 4), tasks = take(ts * sizeof(bmh_seed_task_t)), res = take(ts * sizeof(bmh_seed_result_t));
+		swt = take(tc * sizeof(bmh_sw_task_t)), swr = take(tc * sizeof(bmh_sw_result_t)), reg = take(ts * sizeof(bmh_alnreg_t));
+		nreg = take((n + 1) * 8), roff = take((n + 1) * 8), out = take(ts * sizeof(bmh_alnreg_t)), total = o;
+	}
+};
+
+// reads the extension kernels' error flag after a call that was refused on the host, and clears it; the refusal stays the answer
+int c2r_abandon(bmh_ctx *ctx, int rc)
+{
+	std::string why = std::move(ctx->last_error);
+	int e = 0;
+	if (hipMemcpyAsync(ctx->h_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+	    stream_wait(ctx, ctx->stream) == hipSuccess)
+		e = *ctx->h_err;
+	if (e) {
+		(void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream);
+		(void)stream_wait(ctx, ctx->stream);
+	}
+	ctx->last_error = std::move(why);
+	return rc;
+}
+
+// The driver proper, on the context's stream.  The workspace lies at the start of ctx->d_c2r (a caller that keeps its own input there
+// puts it behind C2rLayout::total and has made the buffer large enough).  regs[r] receive malloc'd arrays with n == m.
+int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in, int lmax, int msl, bmh_alnreg_v *regs, bmh_driver_stats_t *st,
+            long long *chains_in = nullptr)
+{
+	const int n = in.n_reads;
+	const C2rLayout L((size_t)n, (size_t)in.tc, (size_t)in.ts);
+	int rc;
+	if ((rc = ensure(ctx, ctx->d_c2r, L.total))) return rc;
+	if ((rc = ensure_host(ctx, ctx->h_down, 256))) return rc;
+	uint8_t *d = (uint8_t *)ctx->d_c2r.p;
+	const C2rWs ws{(uint32_t *)(d + L.status), (C2rChain *)(d + L.chn), (C2rState *)(d + L.state), (uint64_t *)(d + L.srt), (uint32_t *)(d + L.slot),
+	               (bmh_seed_task_t *)(d + L.tasks), (bmh_seed_result_t *)(d + L.res), (bmh_sw_task_t *)(d + L.swt), (bmh_sw_result_t *)(d + L.swr),
+	               (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (bmh_alnreg_t *)(d + L.out)};
+	const bmh_params_t &p = ctx->params;
+	const C2rSwRule sw{msl, ctx->dev.max_mat, ctx->wide_sw ? 1 : 0, sw_byte_gaps_wrap(p) ? 1 : 0};
+	const unsigned rb = (unsigned)((n + 63) / 64);
+	uint32_t *h = (uint32_t *)ctx->h_down.p;
+	hipStream_t s = ctx->stream;
+	BMH_HIP(ctx, hipMemsetAsync(ws.status, 0, C2R_STATUS_BYTES, s)); // the error flag starts clean on every call
+	hipLaunchKernelGGL(c2r_window_kernel, dim3(rb), dim3(64), 0, s, p, l_pac, in, ws, sw);
+	BMH_HIP(ctx, hipGetLastError());
+	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, 16, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, stream_wait(ctx, s));
+	if ((int)h[C2R_ERR]) {
+		ctx->last_error = (int)h[C2R_ERR] == BMH_E_RANGE ? "chains to regions: a seed outside its chain's window, a window over 2^31, or a short-chain task outside the Smith-Waterman range"
+		                                                 : "chains to regions: the chains are inconsistent (a seed outside its read, offsets outside the arrays, or a chain off the doubled coordinate)";
+		return (int)h[C2R_ERR];
+	}
+	const uint32_t n_short = h[C2R_N_SHORT];
+	st->short_sw = n_short;
+	// mem_chain2aln_short's bounds (bmh_c2a_short_candidate): qlen, tlen < MEM_SHORT_LEN, and qlen > 2 * MEM_SHORT_EXT.
+	// The caps are given, and must stay given: in the fused call d_pool lies in ctx->d_scratch, which launch_sw's own reduction of
+	// the caps (qcap < 0) would reallocate or overwrite.  Nothing else between here and the gather touches d_scratch.
+	if (n_short && (rc = launch_sw(ctx, d_pool, ws.swt, n_short, ws.swr, BMH_MEM_SHORT_LEN - 1, BMH_MEM_SHORT_LEN - 1, 2 * BMH_MEM_SHORT_EXT + 1)))
+		return c2r_abandon(ctx, rc);
+	const int qmax = std::max(lmax, 1); // no flank is longer than its read
+	uint32_t n_done = 0, n_tasks = (uint32_t)in.tc; // round 1: the task of chain c at index c (the window kernel set the counter to tc)
+	for (;;) {
+		const bool ext = n_tasks > n_done;
+		if (ext) {
+			++st->rounds;
+			if ((rc = launch_seedext(ctx, d_pool, ws.tasks + n_done, (int64_t)(n_tasks - n_done), ws.res + n_done, qmax))) return c2r_abandon(ctx, rc);
+			n_done = n_tasks;
+		}
+		BMH_HIP(ctx, hipMemsetAsync(&ws.status[C2R_N_STOPPED], 0, 4, s));
+		hipLaunchKernelGGL(c2r_replay_kernel, dim3(rb), dim3(64), 0, s, p, in, ws, n_done, ext ? seedext_counters(ctx) : nullptr, ctx->d_err);
+		BMH_HIP(ctx, hipGetLastError());
+		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, 16, hipMemcpyDeviceToHost, s));
+		BMH_HIP(ctx, stream_wait(ctx, s));
+		if ((int)h[C2R_ERR]) {
+			ctx->last_error = (int)h[C2R_ERR] == BMH_E_RANGE ? "chains to regions: a task was outside the supported range (see bwamem_hip.h)"
+			                                                 : "chains to regions: a seed outside its read, or a read's regions do not fit its arena slice";
+			return (int)h[C2R_ERR];
+		}
+		n_tasks = h[C2R_N_TASKS];
+		if (h[C2R_N_STOPPED] == 0) break;
+		if (n_tasks == n_done) { // cannot happen: a stopped read always asks for its seed
+			ctx->last_error = "chains to regions: a read is stopped and nothing was requested";
+			return BMH_E_ARG;
+		}
+	}
+	// gather: count -> scan -> place, then the counts and the compact records
+	hipLaunchKernelGGL(c2r_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long *)ws.nreg, n, ws.roff);
+	hipLaunchKernelGGL(c2r_place_kernel, dim3(rb), dim3(64), 0, s, in, ws);
+	BMH_HIP(ctx, hipGetLastError());
+	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, stream_wait(ctx, s));
+	unsigned long long tr, u64s[4];
+	memcpy(&tr, h + 16, 8), memcpy(u64s, h + C2R_EXT_TASKS, 32);
+	if (chains_in) *chains_in = (long long)u64s[3];
+	if ((int)h[C2R_ERR] || tr > in.ts) {
+		ctx->last_error = "chains to regions: the region counts are inconsistent";
+		return BMH_E_ARG;
+	}
+	st->ext_tasks = (int64_t)u64s[0], st->seeds_extended = (int64_t)u64s[1], st->seeds_skipped = (int64_t)u64s[2];
+	st->seeds_speculated = (int64_t)n_tasks - st->seeds_extended; // extended on the device but never used
+	const size_t b_off = al256(((size_t)n + 1) * 8), b_reg = (size_t)tr * sizeof(bmh_alnreg_t);
+	if ((rc = ensure_host(ctx, ctx->h_down, b_off + b_reg + 64))) return rc;
+	uint8_t *hb = (uint8_t *)ctx->h_down.p;
+	BMH_HIP(ctx, hipMemcpyAsync(hb, ws.roff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+	if (b_reg) BMH_HIP(ctx, hipMemcpyAsync(hb + b_off, ws.out, b_reg, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, stream_wait(ctx, s));
+	const unsigned long long *roff = (const unsigned long long *)hb;
+	const bmh_alnreg_t *ra = (const bmh_alnreg_t *)(hb + b_off);
+	for (int r = 0; r < n; ++r) {
+		const size_t k = (size_t)(roff[r + 1] - roff[r]);
+		if (!k) continue;
+		bmh_alnreg_t *a = (bmh_alnreg_t *)malloc(k * sizeof(bmh_alnreg_t));
+		if (!a) {
+			for (int q = 0; q < r; ++q) free(regs[q].a), regs[q].a = nullptr, regs[q].n = regs[q].m = 0;
+			ctx->last_error = "chains to regions: out of host memory for the regions";
+			return BMH_E_NOMEM;
+		}
+		memcpy(a, ra + roff[r], k * sizeof(bmh_alnreg_t));
+		regs[r].a = a, regs[r].n = regs[r].m = k;
+	}
+	return BMH_OK;
+}
+
+int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads, int min_seed_len, const bmh_alnreg_v *regs, const char *who)
+{
+	if (!ctx || n_reads < 0 || l_pac < 0 || min_seed_len < 0 || (n_reads > 0 && (!reads || !regs))) return BMH_E_ARG;
+	if (!ctx->have_params) return BMH_E_ARG;
+	if (!ctx->dev.pac || ctx->dev.l_pac != l_pac) {
+		ctx->last_error = std::string(who) + ": needs the 2-bit reference of this l_pac resident on the device (bmh_ctx_set_pac)";
+		return BMH_E_ARG;
+	}
+	for (int r = 0; r < n_reads; ++r)
+		if (reads[r].l_seq > 65535) {
+			ctx->last_error = std::string(who) + ": read " + std::to_string(r) + " is longer than 65535 bases";
+			return BMH_E_RANGE;
+		}
+	for (int r = 0; r < n_reads; ++r)
+		if (regs[r].n) {
+			ctx->last_error = std::string(who) + ": regs[" + std::to_string(r) + "] is not empty";
+			return BMH_E_ARG;
+		}
+	return BMH_OK;
+}
+
+struct FusedArgs {
+	const bmh_chain_opt_t *co;
+	int64_t l_pac;
+	int lmax, msl;
+	bmh_alnreg_v *regs;
+	bmh_driver_stats_t *st;
+};
+
+// seeding's tables -> compact chains -> regions, all where they lie on the device; the reads are the pool seeding uploaded
+int fused_cb(bmh_ctx *ctx, const DevSeedTables &t, void *user)
+{
+	const FusedArgs *u = (const FusedArgs *)user;
+	DevChains dc;
+	int rc;
+	if ((rc = chain_compact_device(ctx, u->co, u->l_pac, t, &dc))) return rc;
+	const int n = t.n_reads;
+	// (the chains before the filter, for bmh_chain_stats, are summed on the device and come back in the status words)
+	const C2rIn in{n, t.read_off, t.len, dc.coff, dc.soff, dc.cn, dc.seeds, dc.tc, dc.ts, dc.n_keys};
+	long long before = 0;
+	if ((rc = c2r_run(ctx, u->l_pac, t.pool, in, u->lmax, u->msl, u->regs, u->st, &before))) return rc;
+	ctx->cstats = bmh_chain_stats_t{n, before, (int64_t)dc.tc, (int64_t)dc.ts, (int64_t)dc.n_equal, dc.kernel_ms}; // of a successful call only
+	return BMH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads, const bmh_chain_v *chains, int min_seed_len,
+                           bmh_alnreg_v *regs)
+{
+	int rc;
+	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, regs, "bmh_chains2regs_device"))) return rc;
+	if (n_reads > 0 && !chains) return BMH_E_ARG;
+	bmh_driver_stats_t st{};
+	ctx->dstats = st;
+	if (n_reads == 0) return BMH_OK;
+	// the compact form of the chains (empty chains do nothing in the reference's loop and are left out), and the reads
+	size_t tc = 0, ts = 0, bytes = 0;
+	int lmax = 1;
+	for (int r = 0; r < n_reads; ++r) {
+		if (reads[r].l_seq < 0 || (reads[r].l_seq > 0 && !reads[r].seq) || (chains[r].n && !chains[r].a)) return BMH_E_ARG;
+		bytes += (size_t)reads[r].l_seq, lmax = std::max(lmax, reads[r].l_seq);
+		for (size_t c = 0; c < chains[r].n; ++c)
+			if (chains[r].a[c].n > 0) {
+				if (!chains[r].a[c].seeds) return BMH_E_ARG;
+				++tc, ts += (size_t)chains[r].a[c].n;
+			}
+	}
+	if (tc > 0x7fffffffu || ts > 0x7fffffffu) return BMH_E_ARG;
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	const size_t nr1 = (size_t)n_reads + 1;
+	const size_t i_pool = 0, i_off = al256(bytes + 16), i_len = i_off + al256(nr1 * 8), i_coff = i_len + al256(nr1 * 4), i_soff = i_coff + al256(nr1 * 8),
+	             i_cn = i_soff + al256(nr1 * 8), i_seed = i_cn + al256((tc + 1) * 4), i_total = i_seed + al256((ts + 1) * sizeof(bmh_seed_t));
+	const C2rLayout L((size_t)n_reads, tc, ts);
+	if ((rc = ensure(ctx, ctx->d_c2r, L.total + i_total)) || (rc = ensure_host(ctx, ctx->h_up, i_total))) return rc;
+	uint8_t *h = (uint8_t *)ctx->h_up.p;
+	uint64_t *off = (uint64_t *)(h + i_off);
+	int *len = (int *)(h + i_len);
+	unsigned long long *coff = (unsigned long long *)(h + i_coff), *soff = (unsigned long long *)(h + i_soff);
+	uint32_t *cn = (uint32_t *)(h + i_cn);
+	bmh_seed_t *sd = (bmh_seed_t *)(h + i_seed);
+	size_t at = 0, c_at = 0, s_at = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		off[r] = at, len[r] = reads[r].l_seq, coff[r] = c_at, soff[r] = s_at;
+		if (reads[r].l_seq) memcpy(h + i_pool + at, reads[r].seq, (size_t)reads[r].l_seq);
+		at += (size_t)reads[r].l_seq;
+		for (size_t c = 0; c < chains[r].n; ++c) {
+			const bmh_chain_t &ch = chains[r].a[c];
+			if (ch.n <= 0) continue;
+			cn[c_at++] = (uint32_t)ch.n;
+			memcpy(sd + s_at, ch.seeds, (size_t)ch.n * sizeof(bmh_seed_t));
+			s_at += (size_t)ch.n;
+		}
+	}
+	off[n_reads] = at, coff[n_reads] = c_at, soff[n_reads] = s_at;
+	memset(h + i_pool + bytes, 0, i_off - bytes);
+	uint8_t *d = (uint8_t *)ctx->d_c2r.p + L.total;
+	BMH_HIP(ctx, hipMemcpyAsync(d, h, i_total, hipMemcpyHostToDevice, ctx->stream));
+	st.pool_bytes = (int64_t)bytes + 16; // the reads and the 16 bytes of padding behind them, as the host driver counts its pool
+	const C2rIn in{n_reads, (const uint64_t *)(d + i_off), (const int *)(d + i_len), (const unsigned long long *)(d + i_coff),
+	               (const unsigned long long *)(d + i_soff), (const uint32_t *)(d + i_cn), (const bmh_seed_t *)(d + i_seed), tc, ts, nullptr};
+	rc = c2r_run(ctx, l_pac, d + i_pool, in, lmax, min_seed_len, regs, &st);
+	ctx->dstats = st;
+	return rc;
+}
+
+int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads,
+                              const bmh_read_t *reads, int min_seed_len, bmh_alnreg_v *regs)
+{
+	int rc;
+	if (!so || !co) return BMH_E_ARG;
+	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, regs, "bmh_seed_chain_regs_batch"))) return rc;
+	if (co->min_seed_len < 0 || co->max_occ < 0) return BMH_E_ARG;
+	if (so->min_seed_len != co->min_seed_len || so->split_len != co->split_len || so->split_width != co->split_width || so->min_emit_len < 0 ||
+	    so->min_emit_len > co->min_seed_len) {
+		ctx->last_error = "bmh_seed_chain_regs_batch: min_seed_len / split_len / split_width must agree and min_emit_len <= min_seed_len";
+		return BMH_E_ARG;
+	}
+	bmh_driver_stats_t st{}; // (pool_bytes stays 0: the reads are where seeding uploaded them)
+	ctx->dstats = st;
+	int lmax = 1;
+	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
+	FusedArgs u{co, l_pac, lmax, min_seed_len, regs, &st};
+	rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
+	ctx->dstats = st;
+	return rc;
+}
+
+} // extern "C"

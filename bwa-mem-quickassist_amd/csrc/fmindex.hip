@@ -823,7 +823,8 @@ static int smem_impl(bmh_ctx_t *ctx, const bmh_smem_opt_t *o, int n_reads, const
 			if (sp && sp->fn) { // the per-read tables, where they are
 				const DevSeedTables t{n_reads, (const int *)(d + o_len), (const uint32_t *)(d + o_coff), (const bmh_smem_call_t *)(d + o_calls2),
 				                      (const uint64_t *)(d + o_ioff), (const bmh_smem_intv_t *)(d + o_intv2), (const uint64_t *)(d + o_pb2),
-				                      (const uint64_t *)(d + o_pos), (uint64_t)totals[0], (uint64_t)totals[1], (uint64_t)totals[4]};
+				                      (const uint64_t *)(d + o_pos), (uint64_t)totals[0], (uint64_t)totals[1], (uint64_t)totals[4],
+				                      (const uint8_t *)(d + o_pool), (const uint64_t *)(d + o_off)};
 				sp->n_pos = totals[4];
 				return sp->fn(ctx, t, sp->user);
 			}

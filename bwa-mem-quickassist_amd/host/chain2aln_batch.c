@@ -44,6 +44,7 @@
 #include <time.h>
 
 #include "../../include/bwamem_hip.h"
+#include "chain2aln_core.h"
 
 int bmh_upload_pool(bmh_ctx_t *ctx, const uint8_t *pool, size_t bytes);
 const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx);
@@ -52,17 +53,8 @@ void bmh_ctx_set_driver_stats_(bmh_ctx_t *ctx, const bmh_driver_stats_t *st);
 
 #define MAX_BAND_TRY 2 /* bwamem.c:493 */
 
-static inline int imin(int a, int b) { return a < b ? a : b; }
-static inline int imax(int a, int b) { return a > b ? a : b; }
-
-/* bwamem.c:544-551 */
-static int cal_max_gap(const bmh_params_t *p, int qlen)
-{
-	int l_del = (int)((double)(qlen * p->a - p->o_del) / p->e_del + 1.);
-	int l_ins = (int)((double)(qlen * p->a - p->o_ins) / p->e_ins + 1.);
-	int l = imax(imax(l_del, l_ins), 1);
-	return imin(l, p->w << 1);
-}
+/* internal hook for the tests: the shared header's cal_max_gap as this library compiled it */
+int bmh_cal_max_gap_(const bmh_params_t *p, int qlen) { return p ? bmh_c2a_cal_max_gap(p, qlen) : 0; }
 
 /* 2-bit reference -> one code per byte over the doubled coordinate (bntseq.c:355-376).
  * The caller guarantees [beg,end) does not straddle l_pac (bwamem.c:752-755). */
@@ -88,8 +80,7 @@ typedef struct {
 	uint64_t swin_off; /* pool offset of [srb,sre) when the reference is not resident */
 } chain_win_t;
 
-#define MEM_SHORT_EXT 50  /* bwamem.c:491-492 */
-#define MEM_SHORT_LEN 200
+#define MEM_SHORT_EXT BMH_MEM_SHORT_EXT /* bwamem.c:491-492 */
 
 enum { ST_NEXT_CHAIN, ST_NEXT_SEED, ST_DONE };
 
@@ -115,62 +106,6 @@ static int cmp_u64(const void *a, const void *b)
 	return (x > y) - (x < y);
 }
 
-/* bwamem.c:769-784 */
-static int seed_near_region(const bmh_params_t *p, const bmh_seed_t *s, const bmh_alnreg_v *av)
-{
-	size_t i;
-	for (i = 0; i < av->n; ++i) {
-		const bmh_alnreg_t *r = &av->a[i];
-		int64_t rd;
-		int qd, w, g;
-		if (s->rbeg < r->rb || s->rbeg + s->len > r->re || s->qbeg < r->qb || s->qbeg + s->len > r->qe) continue;
-		qd = s->qbeg - r->qb, rd = s->rbeg - r->rb;
-		g = cal_max_gap(p, qd < rd ? qd : (int)rd);
-		w = imin(g, p->w);
-		if (qd - rd < w && rd - qd < w) return 1;
-		qd = r->qe - (s->qbeg + s->len), rd = r->re - (s->rbeg + s->len);
-		g = cal_max_gap(p, qd < rd ? qd : (int)rd);
-		w = imin(g, p->w);
-		if (qd - rd < w && rd - qd < w) return 1;
-	}
-	return 0;
-}
-
-/* the overlap test of bwamem.c:793-794 */
-static inline int seeds_conflict(const bmh_seed_t *s, const bmh_seed_t *t)
-{
-	if (t->len < s->len * .95) return 0; /* double compare, bwamem.c:792 */
-	if (s->qbeg <= t->qbeg && s->qbeg + s->len - t->qbeg >= s->len >> 2 && t->qbeg - s->qbeg != t->rbeg - s->rbeg) return 1;
-	if (t->qbeg <= s->qbeg && t->qbeg + t->len - s->qbeg >= s->len >> 2 && s->qbeg - t->qbeg != s->rbeg - t->rbeg) return 1;
-	return 0;
-}
-
-/* bwamem.c:788-799: does another, not-skipped, long-enough seed overlap s off-diagonal? */
-static int has_conflicting_seed(const bmh_chain_t *c, const uint64_t *srt, int k, const bmh_seed_t *s)
-{
-	int i;
-	for (i = k + 1; i < c->n; ++i) {
-		if (srt[i] == 0) continue;
-		if (seeds_conflict(s, &c->seeds[(uint32_t)srt[i]])) return 1;
-	}
-	return 0;
-}
-
-/* the same question asked BEFORE the chain's earlier seeds have been decided: every seed that sorts after `si`
- * (longer, or as long with a larger index) counts, skipped or not -- a superset of the conflicts the reference will see */
-static int may_conflict(const bmh_chain_t *c, int si)
-{
-	const bmh_seed_t *s = &c->seeds[si];
-	const uint64_t key = (uint64_t)s->len << 32 | (uint32_t)si;
-	int i;
-	for (i = 0; i < c->n; ++i) {
-		const uint64_t ki = (uint64_t)c->seeds[i].len << 32 | (uint32_t)i;
-		if (ki <= key || ki == 0) continue;
-		if (seeds_conflict(s, &c->seeds[i])) return 1;
-	}
-	return 0;
-}
-
 typedef struct {
 	const bmh_params_t *p;
 	const bmh_read_t *reads;
@@ -187,38 +122,6 @@ typedef struct {
 	int short_msl; /* > 0: mem_chain2aln_short is the driver's own pre-step, with this opt->min_seed_len */
 	const bmh_sw_result_t *sw_res;
 } drv_t;
-
-/* The part of mem_chain2aln_short before its ksw_align2 (bwamem.c:504-527): does the chain qualify, and for which
- * query / reference intervals?  Returns 1 and fills cw->s* if a Smith-Waterman is to be run. */
-static int short_candidate(const bmh_params_t *p, int64_t l_pac, int l_query, const bmh_chain_t *c, chain_win_t *cw)
-{
-	int i, qb = l_query, qe = 0, cov = 0;
-	int64_t rb = l_pac << 1, re = 0;
-	cw->sw_idx = -1;
-	if (c->n <= 0) return 0;
-	for (i = 0; i < c->n; ++i) {
-		const bmh_seed_t *s = &c->seeds[i];
-		qb = qb < s->qbeg ? qb : s->qbeg;
-		qe = qe > s->qbeg + s->len ? qe : s->qbeg + s->len;
-		rb = rb < s->rbeg ? rb : s->rbeg;
-		re = re > s->rbeg + s->len ? re : s->rbeg + s->len;
-		cov += s->len;
-	}
-	qb -= MEM_SHORT_EXT, qe += MEM_SHORT_EXT;
-	if (qb <= 10 || qe >= l_query - 10) return 0; /* ksw_align2 cannot align to the ends */
-	rb -= MEM_SHORT_EXT, re += MEM_SHORT_EXT;
-	rb = rb > 0 ? rb : 0;
-	re = re < l_pac << 1 ? re : l_pac << 1;
-	if (rb < l_pac && l_pac < re) {
-		if (c->seeds[0].rbeg < l_pac) re = l_pac;
-		else rb = l_pac;
-	}
-	if ((re - rb) - (qe - qb) > MEM_SHORT_EXT || (qe - qb) - (re - rb) > MEM_SHORT_EXT) return 0;
-	if (qe - qb >= p->w * 4 || re - rb >= p->w * 4) return 0;
-	if (qe - qb >= MEM_SHORT_LEN || re - rb >= MEM_SHORT_LEN) return 0;
-	cw->sqb = qb, cw->sqe = qe, cw->srb = rb, cw->sre = re, cw->seedcov = cov;
-	return 1;
-}
 
 /* Runs read r with the reference's control flow (bwamem.c:1101-1107 over :760-876) for as long as the extension results
  * it needs are cached.  Returns 0 when the read is finished, 1 when it stopped at a seed whose result is missing. */
@@ -263,7 +166,6 @@ static int run_read(drv_t *d, int r, rstate_t *rs)
 			const bmh_seed_result_t *x;
 			bmh_alnreg_t *a;
 			uint32_t si;
-			int i;
 			if (rs->k < 0) {
 				free(rs->srt);
 				rs->srt = 0;
@@ -272,7 +174,7 @@ static int run_read(drv_t *d, int r, rstate_t *rs)
 			}
 			si = (uint32_t)rs->srt[rs->k];
 			s = &c->seeds[si];
-			if (seed_near_region(d->p, s, &d->regs[r]) && !has_conflicting_seed(c, rs->srt, rs->k, s)) {
+			if (bmh_c2a_seed_near_region(d->p, s, d->regs[r].a, d->regs[r].n) && !bmh_c2a_has_conflicting_seed(c->seeds, c->n, rs->srt, rs->k, s)) {
 				rs->srt[rs->k] = 0; /* bwamem.c:796-799 */
 				--rs->k;
 				++d->st.seeds_skipped;
@@ -285,11 +187,7 @@ static int run_read(drv_t *d, int r, rstate_t *rs)
 			memset(a, 0, sizeof(*a));
 			a->qb = x->qb, a->qe = x->qe, a->rb = cw->rmax0 + x->rb, a->re = cw->rmax0 + x->re; /* bwamem.c:831-866 */
 			a->score = x->score, a->truesc = x->truesc, a->w = x->w;                          /* ... and :875 */
-			for (i = 0, a->seedcov = 0; i < c->n; ++i) { /* bwamem.c:870-874 */
-				const bmh_seed_t *t = &c->seeds[i];
-				if (t->qbeg >= a->qb && t->qbeg + t->len <= a->qe && t->rbeg >= a->rb && t->rbeg + t->len <= a->re)
-					a->seedcov += t->len;
-			}
+			a->seedcov = bmh_c2a_seedcov(c->seeds, c->n, a); /* bwamem.c:870-874 */
 			--rs->k;
 		} else return 0;
 	}
@@ -391,27 +289,15 @@ static int chains2regs(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_
 			const bmh_chain_t *c = &chains[r].a[ci];
 			chain_win_t *cw = &wins[ci_flat];
 			const int l_query = reads[r].l_seq;
-			int i;
+			bmh_c2a_short_t sc;
 			cw->seed_base = n_seeds, cw->sw_idx = -1;
 			if (c->n <= 0) continue;
-			if (short_msl > 0 && short_candidate(d.p, l_pac, l_query, c, cw)) cw->sw_idx = (int32_t)n_short++;
+			if (short_msl > 0 && bmh_c2a_short_candidate(d.p, l_pac, l_query, c->n, c->seeds, &sc)) {
+				cw->sw_idx = (int32_t)n_short++;
+				cw->sqb = sc.sqb, cw->sqe = sc.sqe, cw->srb = sc.srb, cw->sre = sc.sre, cw->seedcov = sc.seedcov;
+			}
 			n_seeds += (size_t)c->n;
-			cw->rmax0 = l_pac << 1, cw->rmax1 = 0;
-			for (i = 0; i < c->n; ++i) {
-				const bmh_seed_t *t = &c->seeds[i];
-				const int rest = l_query - t->qbeg - t->len;
-				const int64_t b = t->rbeg - (t->qbeg + cal_max_gap(d.p, t->qbeg));
-				const int64_t e = t->rbeg + t->len + (rest + cal_max_gap(d.p, rest));
-				if (b < cw->rmax0) cw->rmax0 = b;
-				if (e > cw->rmax1) cw->rmax1 = e;
-			}
-			if (cw->rmax0 < 0) cw->rmax0 = 0;
-			if (cw->rmax1 > l_pac << 1) cw->rmax1 = l_pac << 1;
-			if (cw->rmax0 < l_pac && l_pac < cw->rmax1) {
-				if (c->seeds[0].rbeg < l_pac) cw->rmax1 = l_pac;
-				else cw->rmax0 = l_pac;
-			}
-			if (cw->rmax1 < cw->rmax0) { rc = BMH_E_ARG; goto done; }
+			if (bmh_c2a_window(d.p, l_pac, l_query, c->n, c->seeds, &cw->rmax0, &cw->rmax1)) { rc = BMH_E_ARG; goto done; }
 		}
 	}
 	/* with the reference resident on the device (bmh_ctx_set_pac) the tasks address it directly and no window is
@@ -509,14 +395,14 @@ static int chains2regs(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_
 				if ((rc = request(&d, &q, r, &rs[r], rs[r].ci, (int)(uint32_t)rs[r].srt[rs[r].k]))) goto done;
 				for (kk = rs[r].k - 1; kk >= 0; --kk) {
 					const int si = (int)(uint32_t)rs[r].srt[kk];
-					if (seed_near_region(d.p, &c->seeds[si], &regs[r]) && !may_conflict(c, si)) continue; /* provably skipped */
+					if (bmh_c2a_seed_near_region(d.p, &c->seeds[si], regs[r].a, regs[r].n) && !bmh_c2a_may_conflict(c->seeds, c->n, si)) continue; /* provably skipped */
 					if ((rc = request(&d, &q, r, &rs[r], rs[r].ci, si))) goto done;
 				}
 				for (ci = (size_t)rs[r].ci + 1; ci < chains[r].n; ++ci) {
 					const bmh_chain_t *c2 = &chains[r].a[ci];
 					int si;
 					for (si = 0; si < c2->n; ++si) {
-						if (seed_near_region(d.p, &c2->seeds[si], &regs[r]) && !may_conflict(c2, si)) continue;
+						if (bmh_c2a_seed_near_region(d.p, &c2->seeds[si], regs[r].a, regs[r].n) && !bmh_c2a_may_conflict(c2->seeds, c2->n, si)) continue;
 						if ((rc = request(&d, &q, r, &rs[r], (int)ci, si))) goto done;
 					}
 				}

@@ -4,11 +4,19 @@
  * It provides mem_align1_core_batched() with the fork's exact signature
  * (reference bwa-0.7.8/bwamem.c:1086) so that, preloaded in front of a build of the
  * reference (oracle/_ref/bwa + libbwa_ref.so), phase 1 of mem_process_seqs
- * (bwamem.c:1313 -> worker1_batched :1264) runs on the library: seeding as one device
- * batch (bmh_seed_batch), chaining on the host (bmh_chain_reads) or, with
- * BMH_CHAIN_DEVICE=1, fused with seeding on the device (bmh_seed_chain_batch), then
- * every batch's chains go to bmh_chains2regs_batch() -- the hook the fork left
- * commented out at bwamem.c:1110.  Run `bwa mem -b <batch>` to choose the batch size.
+ * (bwamem.c:1313 -> worker1_batched :1264) runs on the library, in one of three forms:
+ *   default              seeding as one device batch (bmh_seed_batch), chaining on the host
+ *                        (bmh_chain_reads), then the batch's chains go to bmh_chains2regs_batch()
+ *                        -- the hook the fork left commented out at bwamem.c:1110: short-chain
+ *                        Smith-Watermans and fused per-seed extensions on the device, the
+ *                        per-read control flow replayed on the host;
+ *   BMH_CHAIN_DEVICE=1   chaining fused with seeding on the device (bmh_seed_chain_batch), the
+ *                        chains come back and go to bmh_chains2regs_batch() as above;
+ *   BMH_REGS_DEVICE=1    ONE call, bmh_seed_chain_regs_batch(): seeding, chaining and the
+ *                        chains-to-regions driver on the device, only regions come back.  Needs
+ *                        the reference resident on the device (BMH_PAC_RESIDENT not 0).
+ * After it the host sorts and de-duplicates each read's regions (bmh_sort_and_dedup).
+ * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
  * Everything declared `extern` below is the reference's own symbol, resolved at load
@@ -332,13 +340,36 @@ static long long g_p1_us[5]; /* phase 1, thread-microseconds: wait for a GPU slo
                               * chaining on the host (0 with BMH_CHAIN_DEVICE=1), wait, extension batch */
 static long long g_seedchain_us; /* thread-microseconds in bmh_seed_chain_batch (BMH_CHAIN_DEVICE=1) */
 
-/* BMH_CHAIN_DEVICE=1: chaining on the device, fused with seeding (bmh_seed_chain_batch); unset or 0: bmh_chain_reads on the host */
+/* BMH_REGS_DEVICE=1 extends from the reference resident on the device, so BMH_PAC_RESIDENT=0 contradicts it.  Checked once when the
+ * library is loaded, before anything has opened the GPU, and left with a plain exit status: no context to tear down, no core. */
+__attribute__((constructor)) static void qa_check_regs_device_env(void)
+{
+	const char *e = getenv("BMH_REGS_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_REGS_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+
+/* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
+static int qa_regs_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_REGS_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+
+/* BMH_CHAIN_DEVICE=1 (implied by BMH_REGS_DEVICE=1): chaining on the device, fused with seeding (bmh_seed_chain_batch); unset or 0:
+ * bmh_chain_reads on the host */
 static int qa_chain_device(void)
 {
 	static int on = -1;
 	if (on < 0) {
 		const char *e = getenv("BMH_CHAIN_DEVICE");
-		on = e && e[0] && strcmp(e, "0") != 0;
+		on = (e && e[0] && strcmp(e, "0") != 0) || qa_regs_device();
 	}
 	return on;
 }
@@ -367,6 +398,27 @@ static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, cons
 	memcpy(p.mat, opt->mat, 25);
 	tq[0] = tq[1] = stage_now();
 	ctx = bmh_pool_get(&p);
+	if (qa_regs_device()) { /* bwamem.c:1095-1110 in one call: reads up, regions down */
+		bmh_smem_opt_t so;
+		bmh_chain_opt_t co;
+		bmh_driver_stats_t st;
+		bmh_chain_stats_t cs;
+		/* (BMH_PAC_RESIDENT=0 was refused when the library was loaded) */
+		if ((rc = bmh_ctx_set_pac(ctx, pac, bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
+		qa_seed_setup(ctx, opt, (const ref_bwt_t *)bwt, &so);
+		qa_chain_opt(opt, &co);
+		if ((rc = bmh_seed_chain_regs_batch(ctx, &so, &co, bns->l_pac, batch_size, reads, opt->min_seed_len, regs))) bmh_tls_die(bmh_last_error(ctx), rc);
+		bmh_driver_stats(ctx, &st);
+		bmh_chain_stats(ctx, &cs);
+		bmh_pool_put(ctx);
+		__sync_fetch_and_add(&g_p1_cnt[0], (long long)cs.chains_out);
+		__sync_fetch_and_add(&g_p1_cnt[1], st.seeds_extended), __sync_fetch_and_add(&g_p1_cnt[2], st.seeds_speculated);
+		__sync_fetch_and_add(&g_p1_cnt[3], st.short_sw);
+		tq[2] = tq[3] = tq[4] = tq[5] = stage_now();
+		__sync_fetch_and_add(&g_seedchain_us, (long long)((tq[2] - tq[1]) * 1e6));
+		for (b = 0; b < batch_size; ++b) chn[b].n = chn[b].m = 0, chn[b].a = 0;
+		goto folded;
+	}
 	if (qa_chain_device()) { /* mem_chain + mem_chain_flt (bwamem.c:1095-1097) on the device behind the seeding: only chains come back */
 		bmh_smem_opt_t so;
 		bmh_chain_opt_t co;
@@ -412,6 +464,7 @@ static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, cons
 	}
 	bmh_pool_put(ctx);
 	tq[5] = stage_now();
+folded:
 	{ /* thread-seconds per stage, summed over the run (BMH_VERBOSE prints them per chunk) */
 		static const int a_[5] = {0, 1, 2, 3, 4};
 		int k;
@@ -655,7 +708,12 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	t_[3] = realtime();
 	free(reads);
 	if (getenv("BMH_VERBOSE")) {
-		if (qa_chain_device()) {
+		if (qa_regs_device()) {
+			fprintf(stderr, "[bwamem_hip] seeding batch thread-seconds so far: bmh_seed_chain_regs_batch (seeding + chaining + regions on the device) %.3f\n",
+			        g_seedchain_us * 1e-6);
+			fprintf(stderr, "[bwamem_hip] phase 1 thread-seconds so far: wait %.3f, seeding + chaining + regions batch %.3f\n", g_p1_us[0] * 1e-6,
+			        g_p1_us[1] * 1e-6);
+		} else if (qa_chain_device()) {
 			fprintf(stderr, "[bwamem_hip] seeding batch thread-seconds so far: bmh_seed_chain_batch (seeding + chaining on the device) %.3f\n",
 			        g_seedchain_us * 1e-6);
 			fprintf(stderr, "[bwamem_hip] phase 1 thread-seconds so far: wait %.3f, seeding + chaining batch %.3f, chaining on the host %.3f, wait %.3f, extension batch %.3f\n",
@@ -666,9 +724,12 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 			fprintf(stderr, "[bwamem_hip] phase 1 thread-seconds so far: wait %.3f, seeding batch %.3f, chaining on the host %.3f, wait %.3f, extension batch %.3f\n",
 			        g_p1_us[0] * 1e-6, g_p1_us[1] * 1e-6, g_p1_us[2] * 1e-6, g_p1_us[3] * 1e-6, g_p1_us[4] * 1e-6);
 		}
-		fprintf(stderr, "[bwamem_hip] phase 1 so far: %lld chains from %s, %lld seeds extended (+%lld speculated in vain), %lld short-chain Smith-Watermans batched\n",
-		        g_p1_cnt[0], qa_chain_device() ? "bmh_seed_chain_batch on the device" : "bmh_chain_reads", g_p1_cnt[1], g_p1_cnt[2],
-		        g_p1_cnt[3]);
+		fprintf(stderr, "[bwamem_hip] phase 1 so far: %lld chains %s, %lld seeds extended (+%lld speculated in vain), %lld short-chain Smith-Watermans batched\n",
+		        g_p1_cnt[0],
+		        qa_regs_device()    ? "and regions from bmh_seed_chain_regs_batch on the device"
+		        : qa_chain_device() ? "from bmh_seed_chain_batch on the device"
+		                            : "from bmh_chain_reads",
+		        g_p1_cnt[1], g_p1_cnt[2], g_p1_cnt[3]);
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());

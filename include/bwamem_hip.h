@@ -689,12 +689,31 @@ int bmh_chain_batch(bmh_ctx_t *ctx, const bmh_chain_opt_t *o, int64_t l_pac, int
  * (BMH_E_ARG otherwise).  Capacities grow inside the call. */
 int bmh_seed_chain_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac,
                          int n_reads, const bmh_read_t *reads, bmh_chain_v *chains);
-typedef struct bmh_chain_stats { /* of the last successful bmh_chain_batch / bmh_seed_chain_batch (-1: none yet) */
+typedef struct bmh_chain_stats { /* of the last successful bmh_chain_batch / bmh_seed_chain_batch / bmh_seed_chain_regs_batch (-1: none yet) */
 	int64_t reads, chains_in, chains_out, seeds; /* chains before / after mem_chain_flt; seeds of the chains kept */
 	int64_t equal_keys; /* look-ups of the B-tree of chains that met an equal key (their answer depends on its splits) */
 	float kernel_ms;    /* the chain kernel's duration with kernel timing on, else -1 */
 } bmh_chain_stats_t;
 int bmh_chain_stats(bmh_ctx_t *ctx, bmh_chain_stats_t *st);
+
+/* ---- chains to regions on the device: the per-read driver of bmh_chains2regs_batch (windows, the short-chain pre-step, the replay of
+ * the reference's control flow, the tasks of every round) as kernels, one lane per read.  Inside a call only 16-byte status words
+ * cross PCIe between the launches; the regions come back compacted at the end.  Both calls need the 2-bit reference resident on the
+ * device (bmh_ctx_set_pac with this l_pac; BMH_E_ARG otherwise) and reads of at most 65 535 bases (a longer one: BMH_E_RANGE before
+ * anything runs, where the host driver looks at the flanks only).  BMH_E_RANGE where the host driver gives it (a seed outside its
+ * window, a window over 2^31, the fused per-seed record's own limits); BMH_E_ARG for a caller's seed that does not lie inside its
+ * read (len < 1, qbeg < 0, qbeg + len > l_seq), found on the device.  bmh_ctx_set_wide_extension is honoured.  bmh_driver_stats reports the call as it does the host driver's; pool_bytes is the sequence this call uploaded: the reads
+ * plus 16 bytes of padding for bmh_chains2regs_device, 0 for bmh_seed_chain_regs_batch (seeding's copy of the reads is used).
+ *
+ * mem_chain2aln [+ mem_chain2aln_short when min_seed_len > 0] for n_reads reads, the whole driver on the device.
+ * chains: as bmh_chain_reads / bmh_seed_chain_batch return them; uploaded in compact form.  regs[r] must be empty.
+ * min_seed_len == 0: no short-chain pre-step (bmh_chain2aln_batch with pre == NULL); < 0: BMH_E_ARG. */
+int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                           const bmh_chain_v *chains, int min_seed_len, bmh_alnreg_v *regs);
+/* seeding -> chaining -> regions; nothing but regions (and the statistics) comes back.  Arguments as bmh_seed_chain_batch's;
+ * bmh_chain_stats is valid afterwards. */
+int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac,
+                              int n_reads, const bmh_read_t *reads, int min_seed_len, bmh_alnreg_v *regs);
 
 #ifdef __cplusplus
 }
