@@ -189,6 +189,9 @@ def lib():
         L.bmh_chains2regs_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.bmh_chains2regs_device.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.bmh_seed_chain_regs_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.bmh_sort_dedup_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float]
+        L.bmh_ctx_set_regs_dedup.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        L.bmh_last_dedup_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_region_cigar_batch.restype = C.c_int
@@ -714,6 +717,29 @@ class Context:
         rc = lib().bmh_seed_chain_regs_batch(self._h, _ptr(so), _ptr(co), C.c_int64(int(l_pac)), n, C.cast(c_reads, C.c_void_p),
                                              int(min_seed_len), C.cast(c_regs, C.c_void_p))
         return self._take_regs(c_regs, n, rc)
+
+    def sort_dedup_batch(self, vectors, mask_level_redun):
+        """bmh_sort_dedup_batch: mem_sort_and_dedup for every vector of a batch in one device call.
+        vectors: per read an ALNREG array (left as it is).  Returns per read the ALNREG array of the survivors, in order."""
+        n = len(vectors)
+        bufs = [np.array(v, dtype=ALNREG, copy=True).reshape(-1) for v in vectors]
+        c_regs = (_AlnregV * max(n, 1))()
+        for r, a in enumerate(bufs):
+            c_regs[r].n = c_regs[r].m = len(a)
+            c_regs[r].a = a.ctypes.data if len(a) else None
+        self._check(lib().bmh_sort_dedup_batch(self._h, n, C.cast(c_regs, C.c_void_p), float(mask_level_redun)))
+        return [a[:c_regs[r].n].copy() for r, a in enumerate(bufs)]
+
+    def set_regs_dedup(self, on=True, mask_level_redun=0.95):
+        """bmh_ctx_set_regs_dedup: while on, chains2regs_device and seed_chain_regs_batch return what mem_sort_and_dedup
+        leaves of their regions (sorted and filtered on the device, before the download)."""
+        self._check(lib().bmh_ctx_set_regs_dedup(self._h, 1 if on else 0, float(mask_level_redun)))
+
+    def last_dedup_stats(self):
+        """(regions in, regions kept, kernel ms or -1) of the last call that ran the de-duplication kernel; -1 each before it."""
+        a, b, ms = C.c_int64(0), C.c_int64(0), C.c_float(0)
+        self._check(lib().bmh_last_dedup_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
+        return a.value, b.value, ms.value
 
     def reg2cigar_batch(self, l_pac, pac, reads, reqs):
         """Batched mem_reg2aln band/retry loop over bwa_gen_cigar2 (reference bwamem.c:1187-1201, bwa.c:89-172).

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <numeric>
 #include <vector>
 
@@ -297,8 +298,10 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab), free_buf(ctx->d_c2r);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
-	free_buf(ctx->d_swl);
+	free_buf(ctx->d_swl), free_buf(ctx->d_dedup);
 	for (auto &e : ctx->ev_chain)
+		if (e) (void)hipEventDestroy(e);
+	for (auto &e : ctx->ev_dedup)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
 		if (h.ev) (void)hipEventDestroy(h.ev);
@@ -1162,6 +1165,93 @@ int bmh_ctx_reserve_kernels(bmh_ctx_t *ctx, int seed_reads, int seed_read_len, i
 		const size_t grid = std::min<size_t>(((size_t)global_tasks + 63) / 64, (size_t)std::max(ctx->ncu, 1) * 4 * 2);
 		if ((rc = ensure(ctx, ctx->d_zslab, grid * (size_t)std::min(global_rows, 512) * 8 * 256))) return rc;
 	}
+	return BMH_OK;
+}
+
+// ------------------------------------------------------------------ mem_sort_and_dedup
+
+int bmh_sort_dedup_batch(bmh_ctx_t *ctx, int n_reads, bmh_alnreg_v *regs, float mask_level_redun)
+{
+	if (!ctx || n_reads < 0 || (n_reads > 0 && !regs)) return BMH_E_ARG;
+	size_t total = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		if (regs[r].n && !regs[r].a) return BMH_E_ARG;
+		if (regs[r].n > 0x7fffffffu - total) {
+			ctx->last_error = "bmh_sort_dedup_batch: more than 2^31-1 regions in the batch";
+			return BMH_E_ARG;
+		}
+		total += regs[r].n;
+	}
+	if (total == 0) { // nothing to launch
+		ctx->dedup_in = ctx->dedup_out = 0, ctx->dedup_ms = -1.f;
+		return BMH_OK;
+	}
+	// one upload: [removed, padding | off[n_reads + 1] | cnt[n_reads] | the regions], laid out the same on both sides
+	const size_t nr = (size_t)n_reads, o_off = 64, o_cnt = o_off + (nr + 1) * 8, o_reg = (o_cnt + nr * 8 + 63) & ~(size_t)63;
+	const size_t b_reg = total * sizeof(bmh_alnreg_t), b_up = o_reg + b_reg, b_down = b_up - o_cnt;
+	std::vector<uint8_t> up, down;
+	try {
+		up.resize(b_up), down.resize(b_down);
+	} catch (const std::bad_alloc &) {
+		ctx->last_error = "bmh_sort_dedup_batch: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	memset(up.data(), 0, o_off);
+	unsigned long long *off = (unsigned long long *)(up.data() + o_off), *cnt = (unsigned long long *)(up.data() + o_cnt);
+	size_t at = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		off[r] = at, cnt[r] = regs[r].n;
+		if (regs[r].n) memcpy(up.data() + o_reg + at * sizeof(bmh_alnreg_t), regs[r].a, regs[r].n * sizeof(bmh_alnreg_t));
+		at += regs[r].n;
+	}
+	off[n_reads] = at;
+	memset(up.data() + o_cnt + nr * 8, 0, o_reg - (o_cnt + nr * 8));
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	Stager st(ctx);
+	unsigned long long removed = 0;
+	int rc = [&]() -> int {
+		int e;
+		if ((e = ensure(ctx, ctx->d_dedup, b_up)) || (e = st.stage(b_up, b_down + 64))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_dedup.p;
+		if ((e = st.h2d(d, up.data(), b_up))) return e;
+		if ((e = launch_region_dedup(ctx, (bmh_alnreg_t *)(d + o_reg), (const unsigned long long *)(d + o_off), (unsigned long long *)(d + o_cnt), n_reads,
+		                             (unsigned long long)total, mask_level_redun, (unsigned long long *)d, ctx->d_err)))
+			return e;
+		if ((e = st.d2h(down.data(), d + o_cnt, b_down)) || (e = st.d2h(&removed, d, 8))) return e;
+		return BMH_OK;
+	}();
+	if ((rc = st.end(rc))) return rc;
+	// the survivors lie at the start of each slice; a and m stay the caller's
+	const unsigned long long *kept = (const unsigned long long *)down.data();
+	const uint8_t *ra = down.data() + (o_reg - o_cnt);
+	for (int r = 0; r < n_reads; ++r) {
+		if (regs[r].n <= 1) continue;
+		if (kept[r] > regs[r].n) { // cannot happen
+			ctx->last_error = "bmh_sort_dedup_batch: the device's counts are inconsistent";
+			return BMH_E_ARG;
+		}
+		memcpy(regs[r].a, ra + (size_t)off[r] * sizeof(bmh_alnreg_t), (size_t)kept[r] * sizeof(bmh_alnreg_t));
+		regs[r].n = (size_t)kept[r];
+	}
+	ctx->dedup_in = (long long)total, ctx->dedup_out = (long long)(total - removed), ctx->dedup_ms = -1.f;
+	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->dedup_ms, ctx->ev_dedup[0], ctx->ev_dedup[1]));
+	return BMH_OK;
+}
+
+int bmh_ctx_set_regs_dedup(bmh_ctx_t *ctx, int on, float mask_level_redun)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->regs_dedup = on != 0, ctx->regs_dedup_mask = mask_level_redun;
+	return BMH_OK;
+}
+
+int bmh_last_dedup_stats(const bmh_ctx_t *ctx, int64_t *regions_in, int64_t *regions_out, float *kernel_ms)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (regions_in) *regions_in = ctx->dedup_in;
+	if (regions_out) *regions_out = ctx->dedup_out;
+	if (kernel_ms) *kernel_ms = ctx->dedup_ms;
 	return BMH_OK;
 }
 

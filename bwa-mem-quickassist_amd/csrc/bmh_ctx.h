@@ -108,6 +108,14 @@ struct bmh_ctx {
 	DevBuf d_swl;                             // its row-maximum slab, then the state slices of its HBM variant
 	hipEvent_t ev_swl[2] = {};                // around its kernels (timing mode)
 	double swl_ms_sum = 0.0;                  // timing mode: their time over the context's life (bmh_sw_wide_stats)
+	// mem_sort_and_dedup on the device (region_dedup_kernel, chain2reg.hip): bmh_sort_dedup_batch, and with the switch on
+	// (bmh_ctx_set_regs_dedup) the chains-to-regions calls before their gather
+	bool regs_dedup = false;
+	float regs_dedup_mask = 0.95f;            // mask_level_redun the switch was set with
+	DevBuf d_dedup;                           // bmh_sort_dedup_batch: removed-regions counter, offsets, counts, regions
+	hipEvent_t ev_dedup[2] = {};              // around the kernel (timing mode)
+	long long dedup_in = -1, dedup_out = -1;  // regions in / kept of the last call that ran it (bmh_last_dedup_stats), -1 = none yet
+	float dedup_ms = -1.f;                    // ... and the kernel's duration with kernel timing on, else -1
 };
 
 namespace bmh {
@@ -358,6 +366,12 @@ struct GlbLongShape {
 int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                   bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, int qmax, int tmax,
                   int wmax, int wgate, const GlbLongShape *lg);
+
+// mem_sort_and_dedup, one lane per read, in place on read r's slice [off[r], off[r] + cnt[r]) of reg (total records in all); rewrites
+// cnt[r] and adds the regions it removed to *removed.  A slice outside the array: BMH_E_ARG into *err (atomicCAS from 0), nothing touched.
+// In timing mode ctx->ev_dedup are recorded around the kernel.
+int launch_region_dedup(bmh_ctx *ctx, bmh_alnreg_t *d_reg, const unsigned long long *d_off, unsigned long long *d_cnt, int n_reads,
+                        unsigned long long total, float mask_level_redun, unsigned long long *d_removed, int *d_err);
 
 int launch_region_orient(bmh_ctx *ctx, uint8_t *d_pool, size_t rpool_off, const bmh_region_req_t *d_reqs, int64_t n);
 int launch_region_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_region_req_t *d_reqs, int64_t n, const bmh_glb_task_t *d_tasks,

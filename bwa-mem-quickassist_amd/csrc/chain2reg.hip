@@ -18,6 +18,9 @@
 //                       entries (every kept seed is requested at most once), so "the result is there" is index < tasks finished so far.
 //                       A per-seed word (task index + 1, 0 = never requested) is the host driver's have[].
 //                       The host reads back {tasks appended, reads stopped, error flag, short-chain tasks}: 16 bytes per round trip.
+//   region_dedup_kernel with bmh_ctx_set_regs_dedup on: mem_sort_and_dedup (bwamem.c:395-436, the text of host/dedup_core.h) in place on
+//                       every read's arena slice, so that the gather below moves the survivors only.  Also what bmh_sort_dedup_batch
+//                       (api.hip) runs on a caller's vectors.
 //   gather              count -> scan -> place of the regions (each read wrote into its slice of the region arena, the soff prefix
 //                       sums: a read yields at most as many regions as it has kept seeds), then the counts and the compact records down.
 #include <algorithm>
@@ -27,12 +30,13 @@
 #include "bmh_ctx.h"
 #include "bmh_device.h"
 #include "../host/chain2aln_core.h"
+#include "../host/dedup_core.h"
 
 namespace bmh {
 
 enum { C2R_NEXT_CHAIN = 0, C2R_NEXT_SEED = 1, C2R_DONE = 2 };
 // status words (uint32 index).  0..3 are what the host reads in the loop
-enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_STATUS_BYTES = 64 };
+enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_DEDUP_REMOVED = 12, C2R_STATUS_BYTES = 64 };
 
 struct C2rChain { // one chain's record, 64 bytes
 	int64_t rmax0, rmax1;
@@ -306,6 +310,38 @@ __global__ __launch_bounds__(64) void c2r_place_kernel(C2rIn in, C2rWs ws)
 	for (unsigned long long k = 0; k < n * 4; ++k) dst[k] = src[k];
 }
 
+// mem_sort_and_dedup (host/dedup_core.h, the text bmh_sort_and_dedup runs) on read r's slice of a region array, one lane per read.
+// The range stack of the two introsorts is the lane's own: bmh_sort_stack_len(n) <= 33 entries for n < 2^31.
+constexpr int kDedupStk = 34;
+__global__ __launch_bounds__(64) void region_dedup_kernel(bmh_alnreg_t *reg, const unsigned long long *__restrict__ off, unsigned long long *cnt, int n_reads,
+                                                          unsigned long long total, float mask_level_redun, unsigned long long *removed, int *err)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= n_reads) return;
+	const unsigned long long n = cnt[r], o = off[r];
+	if (n <= 1) return;
+	if (n > 0x7fffffffull || o > total || n > total - o) { atomicCAS(err, 0, BMH_E_ARG); return; }
+	bmh_sort_stk_t stk[kDedupStk];
+	const unsigned long long m = (unsigned long long)bmh_dedup_core((int)n, reg + o, mask_level_redun, stk);
+	if (m != n) cnt[r] = m, atomicAdd(removed, n - m);
+}
+
+int launch_region_dedup(bmh_ctx *ctx, bmh_alnreg_t *d_reg, const unsigned long long *d_off, unsigned long long *d_cnt, int n_reads,
+                        unsigned long long total, float mask_level_redun, unsigned long long *d_removed, int *d_err)
+{
+	if (n_reads <= 0) return BMH_OK;
+	if (ctx->timing) {
+		if (!ctx->ev_dedup[0]) BMH_HIP(ctx, hipEventCreate(&ctx->ev_dedup[0]));
+		if (!ctx->ev_dedup[1]) BMH_HIP(ctx, hipEventCreate(&ctx->ev_dedup[1]));
+		BMH_HIP(ctx, hipEventRecord(ctx->ev_dedup[0], ctx->stream));
+	}
+	hipLaunchKernelGGL(region_dedup_kernel, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, ctx->stream, d_reg, d_off, d_cnt, n_reads, total,
+	                   mask_level_redun, d_removed, d_err);
+	BMH_HIP(ctx, hipGetLastError());
+	if (ctx->timing) BMH_HIP(ctx, hipEventRecord(ctx->ev_dedup[1], ctx->stream));
+	return BMH_OK;
+}
+
 } // namespace bmh
 
 using namespace bmh;
@@ -409,6 +445,11 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 			return BMH_E_ARG;
 		}
 	}
+	// with the switch on: mem_sort_and_dedup on every read's arena slice, so that the gather places and downloads the survivors only
+	const bool dedup = ctx->regs_dedup;
+	if (dedup && (rc = launch_region_dedup(ctx, ws.reg, in.soff, ws.nreg, n, in.ts, ctx->regs_dedup_mask,
+	                                       (unsigned long long *)&ws.status[C2R_DEDUP_REMOVED], (int *)&ws.status[C2R_ERR])))
+		return rc;
 	// gather: count -> scan -> place, then the counts and the compact records
 	hipLaunchKernelGGL(c2r_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long *)ws.nreg, n, ws.roff);
 	hipLaunchKernelGGL(c2r_place_kernel, dim3(rb), dim3(64), 0, s, in, ws);
@@ -416,8 +457,8 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, stream_wait(ctx, s));
-	unsigned long long tr, u64s[4];
-	memcpy(&tr, h + 16, 8), memcpy(u64s, h + C2R_EXT_TASKS, 32);
+	unsigned long long tr, u64s[4], removed;
+	memcpy(&tr, h + 16, 8), memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&removed, h + C2R_DEDUP_REMOVED, 8);
 	if (chains_in) *chains_in = (long long)u64s[3];
 	if ((int)h[C2R_ERR] || tr > in.ts) {
 		ctx->last_error = "chains to regions: the region counts are inconsistent";
@@ -425,6 +466,10 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	}
 	st->ext_tasks = (int64_t)u64s[0], st->seeds_extended = (int64_t)u64s[1], st->seeds_skipped = (int64_t)u64s[2];
 	st->seeds_speculated = (int64_t)n_tasks - st->seeds_extended; // extended on the device but never used
+	if (dedup) { // (the driver's statistics are about extensions and stay what they are without the switch)
+		ctx->dedup_in = (long long)(tr + removed), ctx->dedup_out = (long long)tr, ctx->dedup_ms = -1.f;
+		if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->dedup_ms, ctx->ev_dedup[0], ctx->ev_dedup[1]));
+	}
 	const size_t b_off = al256(((size_t)n + 1) * 8), b_reg = (size_t)tr * sizeof(bmh_alnreg_t);
 	if ((rc = ensure_host(ctx, ctx->h_down, b_off + b_reg + 64))) return rc;
 	uint8_t *hb = (uint8_t *)ctx->h_down.p;

@@ -15,7 +15,9 @@
  *   BMH_REGS_DEVICE=1    ONE call, bmh_seed_chain_regs_batch(): seeding, chaining and the
  *                        chains-to-regions driver on the device, only regions come back.  Needs
  *                        the reference resident on the device (BMH_PAC_RESIDENT not 0).
- * After it the host sorts and de-duplicates each read's regions (bmh_sort_and_dedup).
+ * After it the host sorts and de-duplicates each read's regions (bmh_sort_and_dedup) -- or, with
+ *   BMH_DEDUP_DEVICE=1   (needs BMH_REGS_DEVICE=1) the same call does that on the device before the regions come down
+ *                        (bmh_ctx_set_regs_dedup) and phase 1 makes no host bmh_sort_and_dedup call.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -351,6 +353,17 @@ __attribute__((constructor)) static void qa_check_regs_device_env(void)
 	}
 }
 
+/* BMH_DEDUP_DEVICE=1 de-duplicates the regions where bmh_seed_chain_regs_batch leaves them, so it means nothing without
+ * BMH_REGS_DEVICE=1.  Checked like the one above: once at load, before the GPU is opened. */
+__attribute__((constructor)) static void qa_check_dedup_device_env(void)
+{
+	const char *d = getenv("BMH_DEDUP_DEVICE"), *e = getenv("BMH_REGS_DEVICE");
+	if (d && d[0] && strcmp(d, "0") != 0 && !(e && e[0] && strcmp(e, "0") != 0)) {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_DEDUP_DEVICE=1 de-duplicates the regions of the device driver: it needs BMH_REGS_DEVICE=1\n");
+		exit(1);
+	}
+}
+
 /* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
 static int qa_regs_device(void)
 {
@@ -361,6 +374,19 @@ static int qa_regs_device(void)
 	}
 	return on;
 }
+
+/* BMH_DEDUP_DEVICE=1 (with BMH_REGS_DEVICE=1): mem_sort_and_dedup behind the regions on the device (bmh_ctx_set_regs_dedup);
+ * phase 1 then makes no host bmh_sort_and_dedup call */
+static int qa_dedup_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_DEDUP_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0 && qa_regs_device();
+	}
+	return on;
+}
+static long long g_dedup_cnt[3]; /* regions de-duplicated on the device, regions kept, host bmh_sort_and_dedup calls of phase 1 */
 
 /* BMH_CHAIN_DEVICE=1 (implied by BMH_REGS_DEVICE=1): chaining on the device, fused with seeding (bmh_seed_chain_batch); unset or 0:
  * bmh_chain_reads on the host */
@@ -407,7 +433,13 @@ static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, cons
 		if ((rc = bmh_ctx_set_pac(ctx, pac, bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
 		qa_seed_setup(ctx, opt, (const ref_bwt_t *)bwt, &so);
 		qa_chain_opt(opt, &co);
+		if ((rc = bmh_ctx_set_regs_dedup(ctx, qa_dedup_device(), opt->mask_level_redun))) bmh_tls_die(bmh_last_error(ctx), rc); /* bwamem.c:1114 behind the call */
 		if ((rc = bmh_seed_chain_regs_batch(ctx, &so, &co, bns->l_pac, batch_size, reads, opt->min_seed_len, regs))) bmh_tls_die(bmh_last_error(ctx), rc);
+		if (qa_dedup_device()) {
+			int64_t din = 0, dout = 0;
+			bmh_last_dedup_stats(ctx, &din, &dout, 0);
+			__sync_fetch_and_add(&g_dedup_cnt[0], (long long)din), __sync_fetch_and_add(&g_dedup_cnt[1], (long long)dout);
+		}
 		bmh_driver_stats(ctx, &st);
 		bmh_chain_stats(ctx, &cs);
 		bmh_pool_put(ctx);
@@ -478,7 +510,10 @@ folded:
 	for (b = 0; b < batch_size; ++b) { /* host stages after the path: bwamem.c:1106,1112-1117 */
 		for (i = 0; i < (int)chn[b].n; ++i) free(chn[b].a[i].seeds);
 		free(chn[b].a);
-		regs[b].n = (size_t)bmh_sort_and_dedup((int)regs[b].n, regs[b].a, opt->mask_level_redun); /* bwamem.c:1114 */
+		if (!qa_dedup_device()) { /* (BMH_DEDUP_DEVICE=1: the device call returned the survivors) */
+			regs[b].n = (size_t)bmh_sort_and_dedup((int)regs[b].n, regs[b].a, opt->mask_level_redun); /* bwamem.c:1114 */
+			__sync_fetch_and_add(&g_dedup_cnt[2], 1);
+		}
 		if ((opt->flag & REF_MEM_F_NO_EXACT) && regs[b].n && regs[b].a[0].truesc == seqs[start + b].l_seq * opt->a) { /* mem_test_and_remove_exact, bwamem.c:438-443 */
 			memmove(regs[b].a, regs[b].a + 1, (regs[b].n - 1) * sizeof(bmh_alnreg_t));
 			--regs[b].n;
@@ -730,6 +765,9 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		        : qa_chain_device() ? "from bmh_seed_chain_batch on the device"
 		                            : "from bmh_chain_reads",
 		        g_p1_cnt[1], g_p1_cnt[2], g_p1_cnt[3]);
+		if (qa_dedup_device())
+			fprintf(stderr, "[bwamem_hip] region de-duplication so far: %lld regions de-duplicated on the device, %lld kept, %lld host bmh_sort_and_dedup calls in phase 1\n",
+			        g_dedup_cnt[0], g_dedup_cnt[1], g_dedup_cnt[2]);
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());

@@ -27,6 +27,7 @@
 #include <time.h>
 
 #include "../../include/bwamem_hip.h"
+#include "dedup_core.h"
 #include "sort_exact.h"
 
 static double now_s(void) /* the clock of the BMH_DRIVER_TRACE lines: wall time, or with BMH_TRACE_CPU this thread's CPU time */
@@ -62,13 +63,7 @@ static inline uint64_t hash_64(uint64_t key) /* utils.h:98-109 */
 	return key;
 }
 
-/* ---- orders (bwamem.c:386-393, utils.c:45) */
-static int lt_re(const void *x, const void *y) { return ((const bmh_alnreg_t *)x)->re < ((const bmh_alnreg_t *)y)->re; }
-static int lt_score_pos(const void *x, const void *y)
-{
-	const bmh_alnreg_t *a = (const bmh_alnreg_t *)x, *b = (const bmh_alnreg_t *)y;
-	return a->score > b->score || (a->score == b->score && (a->rb < b->rb || (a->rb == b->rb && a->qb < b->qb)));
-}
+/* ---- orders (bwamem.c:386-393, utils.c:45); those of mem_sort_and_dedup are in dedup_core.h */
 static int lt_score_hash(const void *x, const void *y)
 {
 	const bmh_alnreg_t *a = (const bmh_alnreg_t *)x, *b = (const bmh_alnreg_t *)y;
@@ -98,46 +93,11 @@ static int lt_pair64(const void *p, const void *q)
 	return a->x < b->x || (a->x == b->x && a->y < b->y);
 }
 
-/* ---- bwamem.c:395-436 */
+/* ---- bwamem.c:395-436: the routine is dedup_core.h's, shared with the device kernel; here only its range stack */
 int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun)
 {
-	int m, i, j;
-	if (n <= 1) return n;
-	bmh_sort_exact(a, (size_t)n, sizeof(*a), lt_re);
-	for (i = 1; i < n; ++i) {
-		bmh_alnreg_t *p = &a[i];
-		if (p->rb >= a[i - 1].re) continue;
-		for (j = i - 1; j >= 0 && p->rb < a[j].re; --j) {
-			bmh_alnreg_t *q = &a[j];
-			int64_t orr, oq, mr, mq;
-			if (q->qe == q->qb) continue; /* already excluded */
-			orr = q->re - p->rb;                                  /* overlap on the reference */
-			oq = q->qb < p->qb ? q->qe - p->qb : p->qe - q->qb;   /* overlap on the query */
-			mr = q->re - q->rb < p->re - p->rb ? q->re - q->rb : p->re - p->rb;
-			mq = q->qe - q->qb < p->qe - p->qb ? q->qe - q->qb : p->qe - p->qb;
-			if (orr > mask_level_redun * mr && oq > mask_level_redun * mq) { /* one of the two is redundant */
-				if (p->score < q->score) {
-					p->qe = p->qb;
-					break;
-				} else q->qe = q->qb;
-			}
-		}
-	}
-	for (i = 0, m = 0; i < n; ++i)
-		if (a[i].qe > a[i].qb) {
-			if (m != i) a[m++] = a[i];
-			else ++m;
-		}
-	n = m;
-	bmh_sort_exact(a, (size_t)n, sizeof(*a), lt_score_pos);
-	for (i = 1; i < n; ++i) /* identical hits */
-		if (a[i].score == a[i - 1].score && a[i].rb == a[i - 1].rb && a[i].qb == a[i - 1].qb) a[i].qe = a[i].qb;
-	for (i = 1, m = 1; i < n; ++i)
-		if (a[i].qe > a[i].qb) {
-			if (m != i) a[m++] = a[i];
-			else ++m;
-		}
-	return m;
+	bmh_sort_stk_t stk[8 * sizeof(size_t) + 2]; /* >= bmh_sort_stack_len(n) for any n */
+	return bmh_dedup_core(n, a, mask_level_redun, stk);
 }
 
 static inline int gap_tmp(const bmh_sam_opt_t *o) /* the largest single-event penalty, bwamem.c:455-457 */

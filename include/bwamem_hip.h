@@ -552,7 +552,7 @@ typedef struct bmh_seq { /* == bseq1_t, bwa.h:19-22; seq holds base codes (after
 	char *name, *comment, *seq, *qual, *sam;
 } bmh_seq_t;
 
-int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun);                       /* mem_sort_and_dedup  */
+int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun);                       /* mem_sort_and_dedup; on the device: bmh_sort_dedup_batch */
 void bmh_mark_primary_se(const bmh_sam_opt_t *o, int n, bmh_alnreg_t *a, int64_t id);         /* mem_mark_primary_se */
 int bmh_approx_mapq_se(const bmh_sam_opt_t *o, const bmh_alnreg_t *a);                         /* mem_approx_mapq_se  */
 /* mem_pestat; with verbose >= 3 it prints the reference's "[M::mem_pestat] ..." lines to stderr */
@@ -714,6 +714,26 @@ int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh
  * bmh_chain_stats is valid afterwards. */
 int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac,
                               int n_reads, const bmh_read_t *reads, int min_seed_len, bmh_alnreg_v *regs);
+
+/* ---- mem_sort_and_dedup on the device (reference bwamem.c:395-436): the text of bmh_sort_and_dedup (host/dedup_core.h) as a kernel,
+ * one lane per read, in place on the read's regions.  Bit-exact with the host routine, including which of two tied records survives:
+ * both sorts are the same restatement of klib's introsort, and the redundancy test is the same single-precision expression.
+ *
+ * mem_sort_and_dedup for every vector of a batch in one device call: regions up, kernel, survivors back into the same regs[r].a.
+ * regs[r].n is updated; a and m are untouched.  Needs neither parameters nor a resident reference.  BMH_E_ARG (and the vectors as
+ * they were) for a NULL context, n_reads < 0, regs == NULL with n_reads > 0, a vector with n > 0 and a == NULL, or more than
+ * 2^31-1 regions in all.  n_reads == 0 and batches of empty vectors: BMH_OK without a launch. */
+int bmh_sort_dedup_batch(bmh_ctx_t *ctx, int n_reads, bmh_alnreg_v *regs, float mask_level_redun);
+/* Per context, off by default.  While on, bmh_chains2regs_device and bmh_seed_chain_regs_batch run the kernel on the reads' region
+ * slices after the last replay and before the gather, so only the survivors are placed, downloaded and malloc'd: regs[r] is what
+ * bmh_sort_and_dedup(regs[r].n, regs[r].a, mask_level_redun) leaves of the switch-off result, record for record and in order.
+ * bmh_driver_stats reports the same numbers either way (they are about extensions, not survivors).  A refused call leaves the
+ * switch as set. */
+int bmh_ctx_set_regs_dedup(bmh_ctx_t *ctx, int on, float mask_level_redun);
+/* Of the last successful call on this context that ran the kernel (bmh_sort_dedup_batch, or a chains-to-regions call with the switch
+ * on): regions in, regions kept, and the kernel's milliseconds with bmh_set_kernel_timing on (else -1).  -1 each before the first such
+ * call.  Any of the three pointers may be NULL. */
+int bmh_last_dedup_stats(const bmh_ctx_t *ctx, int64_t *regions_in, int64_t *regions_out, float *kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -71,15 +71,18 @@ def sim_pairs_fast(rng, ref, n, L, noisy_frac):
     return a, b
 
 
-def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=False, regs_device=False):
+def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=False, regs_device=False, dedup_device=False):
     env = dict(os.environ)
     env.pop("BMH_CHAIN_DEVICE", None)
     env.pop("BMH_REGS_DEVICE", None)
+    env.pop("BMH_DEDUP_DEVICE", None)
     if preload:
         if chain_device:
             env["BMH_CHAIN_DEVICE"] = "1"
-        if regs_device:
+        if regs_device or dedup_device:
             env["BMH_REGS_DEVICE"] = "1"
+        if dedup_device:
+            env["BMH_DEDUP_DEVICE"] = "1"
         env["LD_PRELOAD"] = load_package().DROPIN_PATH
         env["BMH_KSW_DROPIN"] = "1" if ksw_dropin else "0"
         env["BMH_VERBOSE"] = "1"
@@ -115,7 +118,10 @@ def main():
     ap.add_argument("--chain-device", action="store_true", help="DUT chains on the device, fused with seeding (BMH_CHAIN_DEVICE=1)")
     ap.add_argument("--regs-device", action="store_true",
                     help="DUT seeds, chains and turns chains into regions in one device call (BMH_REGS_DEVICE=1)")
+    ap.add_argument("--dedup-device", action="store_true",
+                    help="... and sorts and de-duplicates the regions there too (BMH_DEDUP_DEVICE=1); implies --regs-device")
     a = ap.parse_args()
+    a.regs_device = a.regs_device or a.dedup_device
     rng = np.random.default_rng(20261007)
     tmp = tempfile.mkdtemp(prefix="bmh_pipe_")
     ref = kswgen.rand_seq(rng, a.genome)
@@ -137,6 +143,7 @@ def main():
         reads = sim_reads_fast(rng, ref, a.reads, 150)
         reflib.write_fastq(fq, list(reads))
     res = {"genome_bp": a.genome, "repeats": a.repeats, "reads": a.reads, "paired": bool(a.pe), "index_s": t_index, "chain_device": bool(a.chain_device), "regs_device": bool(a.regs_device),
+           "dedup_device": bool(a.dedup_device),
            "runs": []}
     # one untimed DUT run first: on a fresh box the first process to load the HIP runtime and the library's code objects
     # pays for reading them from disk (seconds), which has nothing to do with the pipeline
@@ -144,11 +151,13 @@ def main():
     for t in [int(x) for x in a.threads.split(",")]:
         r = run(fa, fq, t, a.batch, False, os.path.join(tmp, "ref.sam"))
         refsam = [l for l in open(os.path.join(tmp, "ref.sam")) if not l.startswith("@PG")]
-        d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False, chain_device=a.chain_device, regs_device=a.regs_device)
+        d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False, chain_device=a.chain_device, regs_device=a.regs_device,
+                 dedup_device=a.dedup_device)
         same1 = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         d2 = None
         if a.full:
-            d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True, chain_device=a.chain_device, regs_device=a.regs_device)
+            d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True, chain_device=a.chain_device, regs_device=a.regs_device,
+                 dedup_device=a.dedup_device)
             d2["sam_identical"] = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         res["runs"].append({"threads": t, "batch": a.batch, "ref": r, "dut_phase1_gpu": d1, "sam_identical": same1,
                             "dut_phase1_gpu_plus_percall_global": d2})
