@@ -175,6 +175,8 @@ def lib():
         L.bmh_chain_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_matesw_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmh_matesw_device.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                        C.c_void_p]
         L.bmh_sw_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p]
         L.bmh_sw_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.bmh_extend_batch_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -589,6 +591,44 @@ class Context:
                 _libc.free(c_regs[k].a)
             out.append(a)
         self._check(rc)
+        return out, n_sw[:n_pairs].tolist()
+
+    def matesw_device(self, l_pac, reads, regs, pes, opt, mask_level_redun):
+        """bmh_matesw_device: the same driver as kernels, against the resident reference (set_pac); mem_sort_and_dedup runs on the
+        device at mask_level_redun.  Arguments as matesw_batch's.  Returns (regs after rescue, n per pair).  A refused call raises
+        BmhError with the vectors as the call left them in its `regs` attribute."""
+        n_pairs = len(reads) // 2
+        pes = np.ascontiguousarray(pes, dtype=PESTAT)
+        opt = np.ascontiguousarray(opt, dtype=MATESW_OPT)
+        keep = []
+        c_reads = (_Read * max(len(reads), 1))()
+        for k, r in enumerate(reads):
+            r = np.ascontiguousarray(r, dtype=np.uint8)
+            keep.append(r)
+            c_reads[k].l_seq, c_reads[k].seq = len(r), r.ctypes.data
+        c_regs = (_AlnregV * max(len(regs), 1))()
+        for k, r in enumerate(regs):
+            r = np.ascontiguousarray(r, dtype=ALNREG)
+            c_regs[k].n = c_regs[k].m = len(r)
+            if len(r):
+                c_regs[k].a = _libc.malloc(len(r) * ALNREG.itemsize)
+                C.memmove(c_regs[k].a, r.ctypes.data, len(r) * ALNREG.itemsize)
+        n_sw = np.zeros(max(n_pairs, 1), dtype=np.int32)
+        rc = lib().bmh_matesw_device(self._h, C.c_int64(l_pac), n_pairs, C.cast(c_reads, C.c_void_p), C.cast(c_regs, C.c_void_p),
+                                     _ptr(pes), _ptr(opt), C.c_float(mask_level_redun), _ptr(n_sw))
+        out = []
+        for k in range(len(regs)):
+            a = np.zeros(c_regs[k].n, dtype=ALNREG)
+            if c_regs[k].n:
+                C.memmove(a.ctypes.data, c_regs[k].a, c_regs[k].n * ALNREG.itemsize)
+            if c_regs[k].a:
+                _libc.free(c_regs[k].a)
+            out.append(a)
+        try:
+            self._check(rc)
+        except BmhError as e:
+            e.regs = out
+            raise
         return out, n_sw[:n_pairs].tolist()
 
     def extend_batch_device(self, d_pool, d_tasks, n, d_res, d_order=0):

@@ -298,7 +298,7 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab), free_buf(ctx->d_c2r);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
-	free_buf(ctx->d_swl), free_buf(ctx->d_dedup);
+	free_buf(ctx->d_swl), free_buf(ctx->d_dedup), free_buf(ctx->d_msw);
 	for (auto &e : ctx->ev_chain)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_dedup)

@@ -116,6 +116,7 @@ struct bmh_ctx {
 	hipEvent_t ev_dedup[2] = {};              // around the kernel (timing mode)
 	long long dedup_in = -1, dedup_out = -1;  // regions in / kept of the last call that ran it (bmh_last_dedup_stats), -1 = none yet
 	float dedup_ms = -1.f;                    // ... and the kernel's duration with kernel timing on, else -1
+	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 
 namespace bmh {

@@ -18,6 +18,9 @@
  * After it the host sorts and de-duplicates each read's regions (bmh_sort_and_dedup) -- or, with
  *   BMH_DEDUP_DEVICE=1   (needs BMH_REGS_DEVICE=1) the same call does that on the device before the regions come down
  *                        (bmh_ctx_set_regs_dedup) and phase 1 makes no host bmh_sort_and_dedup call.
+ * Mate rescue (bmh_matesw_batch per slice of the chunk) has a switch of its own:
+ *   BMH_MATESW_DEVICE=1  mate rescue's driver (planning, folding, mem_sort_and_dedup) as kernels, bmh_matesw_device(): no host
+ *                        callback, 16 bytes per round back.  Needs BMH_PAC_RESIDENT not 0; independent of BMH_REGS_DEVICE.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -364,6 +367,28 @@ __attribute__((constructor)) static void qa_check_dedup_device_env(void)
 	}
 }
 
+/* BMH_MATESW_DEVICE=1 rescues mates against the reference resident on the device, so BMH_PAC_RESIDENT=0 contradicts it as well.
+ * Checked like the two above; it does not depend on BMH_REGS_DEVICE. */
+__attribute__((constructor)) static void qa_check_matesw_device_env(void)
+{
+	const char *e = getenv("BMH_MATESW_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_MATESW_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+
+/* BMH_MATESW_DEVICE=1: the mate-rescue driver as kernels (bmh_matesw_device), mem_sort_and_dedup included: no host callback */
+static int qa_matesw_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_MATESW_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+
 /* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
 static int qa_regs_device(void)
 {
@@ -584,8 +609,10 @@ static void qa_worker1_batched(void *data, int start, int batch_size, int tid) /
 	free(ret);
 }
 
+static long long g_msw_dedup_calls, g_msw_active; /* host callbacks of mate rescue; with BMH_MATESW_DEVICE=1: pairs that needed rescue */
 static int qa_dedup(void *user, int n, bmh_alnreg_t *a) /* bmh_dedup_fn of the mate-rescue driver */
 {
+	__sync_fetch_and_add(&g_msw_dedup_calls, 1);
 	return bmh_sort_and_dedup(n, a, ((const ref_mem_opt_t *)user)->mask_level_redun);
 }
 
@@ -614,8 +641,10 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 
 /* mate rescue, one slice of pairs per host thread */
 static long long g_msw_calls, g_msw_rounds_max, g_msw_bytes;
+static long long g_msw_us; /* thread-microseconds in the driver call, over the run (stage_now's clock) */
 static void qa_matesw_slice(void *data, int k, int tid)
 {
+	double t0;
 	const qa_slice_job_t *J = (const qa_slice_job_t *)data;
 	const int np = J->n >> 1, lo = (int)((int64_t)np * k / J->n_slices), hi = (int)((int64_t)np * (k + 1) / J->n_slices);
 	bmh_matesw_opt_t mo;
@@ -626,9 +655,19 @@ static void qa_matesw_slice(void *data, int k, int tid)
 	if (hi <= lo) return;
 	ctx = qa_slice_ctx(J);
 	mo.pen_unpaired = J->opt->pen_unpaired, mo.max_matesw = J->opt->max_matesw, mo.min_seed_len = J->opt->min_seed_len, mo.rsv = 0;
-	if ((rc = bmh_matesw_batch(ctx, J->bns->l_pac, J->pac, hi - lo, J->reads + 2 * lo, J->regs + 2 * lo, J->pes, &mo, qa_dedup,
-	                           (void *)J->opt, 0)))
+	t0 = stage_now();
+	if (qa_matesw_device()) { /* (the reference is resident: BMH_PAC_RESIDENT=0 was refused when the library was loaded) */
+		int *n_sw = (int *)calloc((size_t)(hi - lo), sizeof(int)), p, act = 0;
+		if (!n_sw) bmh_tls_die("out of memory", BMH_E_NOMEM);
+		if ((rc = bmh_matesw_device(ctx, J->bns->l_pac, hi - lo, J->reads + 2 * lo, J->regs + 2 * lo, J->pes, &mo, J->opt->mask_level_redun, n_sw)))
+			bmh_tls_die(bmh_last_error(ctx), rc);
+		for (p = 0; p < hi - lo; ++p) act += n_sw[p] > 0; /* pairs with at least one ksw_align2 call */
+		free(n_sw);
+		__sync_fetch_and_add(&g_msw_active, act);
+	} else if ((rc = bmh_matesw_batch(ctx, J->bns->l_pac, J->pac, hi - lo, J->reads + 2 * lo, J->regs + 2 * lo, J->pes, &mo, qa_dedup,
+	                                  (void *)J->opt, 0)))
 		bmh_tls_die(bmh_last_error(ctx), rc);
+	__sync_fetch_and_add(&g_msw_us, (long long)((stage_now() - t0) * 1e6));
 	bmh_driver_stats(ctx, &st);
 	bmh_pool_put(ctx);
 	__sync_fetch_and_add(&g_msw_calls, st.ext_tasks), __sync_fetch_and_add(&g_msw_bytes, st.pool_bytes);
@@ -732,11 +771,14 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	nt2 = qa_threads("BMH_P2_THREADS", opt->n_threads + opt->n_threads / 2);
 	J.n_slices = qa_threads("BMH_P2_SLICES", nt2);
 	if (rescue) { /* the whole chunk's mate rescue (the block of mem_sam_pe at bwamem_pair.c:251-263), one bmh_matesw_batch per slice */
-		g_msw_calls = g_msw_rounds_max = g_msw_bytes = 0;
+		g_msw_calls = g_msw_rounds_max = g_msw_bytes = g_msw_dedup_calls = g_msw_active = 0;
 		kt_for(nt2, qa_matesw_slice, &J, J.n_slices);
-		if (getenv("BMH_VERBOSE"))
+		if (getenv("BMH_VERBOSE")) {
 			fprintf(stderr, "[bwamem_hip] mate rescue: %d pairs, %lld ksw_align2 calls in %lld GPU rounds, %lld pool bytes\n", n >> 1,
 			        g_msw_calls, g_msw_rounds_max, g_msw_bytes);
+			if (qa_matesw_device()) /* (active: pairs rescue made at least one ksw_align2 call for) */
+				fprintf(stderr, "[bwamem_hip] mate rescue on the device: %lld active pairs, %lld host dedup callbacks\n", g_msw_active, g_msw_dedup_calls);
+		}
 	}
 	t_[2] = realtime();
 	kt_for(nt2, qa_sam_slice, &J, J.n_slices); /* bwamem.c:1318-1319 */
@@ -768,6 +810,7 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		if (qa_dedup_device())
 			fprintf(stderr, "[bwamem_hip] region de-duplication so far: %lld regions de-duplicated on the device, %lld kept, %lld host bmh_sort_and_dedup calls in phase 1\n",
 			        g_dedup_cnt[0], g_dedup_cnt[1], g_dedup_cnt[2]);
+		if (rescue) fprintf(stderr, "[bwamem_hip] mate rescue driver so far: %.3f thread-s in %s\n", g_msw_us * 1e-6, qa_matesw_device() ? "bmh_matesw_device" : "bmh_matesw_batch");
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());

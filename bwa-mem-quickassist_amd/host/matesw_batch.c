@@ -24,41 +24,13 @@ const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx);
 int bmh_ctx_has_pac_(const bmh_ctx_t *ctx, const uint8_t *pac, int64_t l_pac);
 void bmh_ctx_set_driver_stats_(bmh_ctx_t *ctx, const bmh_driver_stats_t *st);
 
-enum { LOOKAHEAD = 8 }; /* invocations planned per pair and round */
-
-typedef struct { /* one planned mem_matesw invocation: hit j of end i against the mate !i */
-	int i, j;
-	int plan[4]; /* per orientation: 0 not computed (was skipped when planned), -2 call on an empty window, -3 no call
-	                (window inverted / bridging), > 0 index+1 of its ksw_align2 result */
-	int64_t rb[4], re[4];
-} inv_t;
+#include "matesw_core.h" /* the rules both drivers share: skip test, windows, tasks, regions, planning, folding */
 
 typedef struct {
-	bmh_alnreg_v b[2];  /* hits of each end within pen_unpaired of its best, copied up front (bwamem_pair.c:252-257) */
-	int i, j;           /* next invocation to fold */
-	int n;              /* sum of mem_matesw's return values */
-	int done;
-	int n_inv;
-	inv_t inv[LOOKAHEAD];
+	bmh_alnreg_t *b[2]; /* hits of each end within pen_unpaired of its best, the first max_matesw of them, copied up front (bwamem_pair.c:252-259) */
+	int nb[2];
+	bmh_msw_pair_t s;
 } pair_t;
-
-/* mem_infer_dir, bwamem_pair.c:23-30 */
-static int infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist)
-{
-	const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-	const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
-	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
-static void push_reg(bmh_alnreg_v *v, const bmh_alnreg_t *x) /* kv_push, kvec.h:68-74 */
-{
-	if (v->n == v->m) {
-		v->m = v->m ? v->m << 1 : 2;
-		v->a = (bmh_alnreg_t *)realloc(v->a, sizeof(bmh_alnreg_t) * v->m);
-	}
-	v->a[v->n++] = *x;
-}
 
 static void fetch_window(int64_t l_pac, const uint8_t *pac, int64_t beg, int64_t end, uint8_t *dst) /* bntseq.c:355-376 */
 {
@@ -68,6 +40,17 @@ static void fetch_window(int64_t l_pac, const uint8_t *pac, int64_t beg, int64_t
 		for (k = hi; k > lo; --k) dst[l++] = (uint8_t)(3 - (pac[k >> 2] >> ((~k & 3) << 1) & 3));
 	} else
 		for (k = beg; k < end; ++k) dst[l++] = (uint8_t)(pac[k >> 2] >> ((~k & 3) << 1) & 3);
+}
+
+/* pair q as matesw_core.h sees it, over the caller's vectors as they are now */
+static void view(const pair_t *ps, const bmh_read_t *reads, bmh_alnreg_v *regs, bmh_msw_io_t *io)
+{
+	int i;
+	for (i = 0; i < 2; ++i) {
+		io->b[i] = ps->b[i], io->nb[i] = ps->nb[i];
+		io->a[i] = regs[i].a, io->n[i] = (int32_t)regs[i].n, io->cap[i] = (int32_t)regs[i].m;
+		io->l_seq[i] = reads[i].l_seq;
+	}
 }
 
 int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pairs, const bmh_read_t *reads,
@@ -100,19 +83,13 @@ int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pa
 		int i, busy = 0;
 		for (i = 0; i < 2 && !busy; ++i) {
 			const bmh_alnreg_v *a = &regs[2 * p + i], *ma = &regs[2 * p + !i];
-			size_t j, k;
+			size_t j;
 			int nb = 0;
 			for (j = 0; j < a->n && !busy; ++j) { /* the hits copied to b[i] (:252-257), the first max_matesw of them (:258-259) */
 				int skip[4];
 				if (a->a[j].score < a->a[0].score - o->pen_unpaired) continue;
 				if (nb++ >= o->max_matesw) break;
-				for (r = 0; r < 4; ++r) skip[r] = pes[r].failed ? 1 : 0;
-				for (k = 0; k < ma->n; ++k) {
-					int64_t dist;
-					r = infer_dir(l_pac, a->a[j].rb, ma->a[k].rb, &dist);
-					if (dist >= pes[r].low && dist <= pes[r].high) skip[r] = 1;
-				}
-				if (skip[0] + skip[1] + skip[2] + skip[3] != 4) busy = 1;
+				if (bmh_msw_skip(l_pac, pes, a->a[j].rb, ma->a, (int32_t)ma->n, skip) != 4) busy = 1;
 			}
 		}
 		if (busy) act[n_act++] = p;
@@ -130,68 +107,28 @@ int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pa
 			const bmh_alnreg_v *a = &regs[2 * p + i];
 			if (reads[2 * p + i].l_seq < 1 || reads[2 * p + i].l_seq > 65535) { rc = BMH_E_RANGE; goto done; }
 			read_off[2 * q + i] = reads_bytes, reads_bytes += (size_t)reads[2 * p + i].l_seq;
-			for (j = 0; j < a->n; ++j) /* bwamem_pair.c:252-257 */
-				if (a->a[j].score >= a->a[0].score - o->pen_unpaired) push_reg(&ps[q].b[i], &a->a[j]);
+			if (a->n && o->max_matesw > 0 && !(ps[q].b[i] = (bmh_alnreg_t *)malloc(sizeof(bmh_alnreg_t) * (a->n < (size_t)o->max_matesw ? a->n : (size_t)o->max_matesw)))) {
+				rc = BMH_E_NOMEM;
+				goto done;
+			}
+			for (j = 0; j < a->n && ps[q].nb[i] < o->max_matesw; ++j) /* bwamem_pair.c:252-259 */
+				if (a->a[j].score >= a->a[0].score - o->pen_unpaired) ps[q].b[i][ps[q].nb[i]++] = a->a[j];
 		}
 	}
 
 	for (;;) {
 		size_t n_tasks = 0, win_bytes = 0, used, want_tasks = 0;
 		int active = 0;
-		/* ---- plan: from each unfinished pair's cursor on, the next invocations that (as things stand) need ksw_align2.
-		 * The first of them is planned against exactly the state it will be folded in; the later ones are planned AHEAD
-		 * against the current state of the mate's vector, which earlier folds may still change -- ksw_align2 is pure and
-		 * its inputs (hit, orientation, mate) do not depend on that state, so a result computed ahead is THE result; the
-		 * fold below re-derives skip[] and only uses what it then really needs.  Without this, a pair with h candidate
-		 * hits would cost h GPU round trips. */
+		/* ---- plan (bmh_msw_plan): from each unfinished pair's cursor on, the next invocations that (as things stand) need
+		 * ksw_align2, the later ones planned ahead.  Without this, a pair with h candidate hits would cost h GPU round trips. */
 		for (q = 0; q < n_act; ++q) {
-			pair_t *s = &ps[q];
-			int ii, jj;
+			bmh_msw_io_t io;
+			uint64_t wb;
 			p = act[q];
-			if (s->done) continue;
-			s->n_inv = 0;
-			for (ii = s->i, jj = s->j; ii < 2 && s->n_inv < LOOKAHEAD;) {
-				const bmh_alnreg_t *a;
-				const bmh_alnreg_v *ma;
-				inv_t *e;
-				int l_ms, skip[4];
-				size_t k;
-				if (!((size_t)jj < s->b[ii].n && jj < o->max_matesw)) { ++ii, jj = 0; continue; } /* :258-259 */
-				a = &s->b[ii].a[jj], ma = &regs[2 * p + !ii], l_ms = reads[2 * p + !ii].l_seq;
-				for (r = 0; r < 4; ++r) skip[r] = pes[r].failed ? 1 : 0; /* :112-121 */
-				for (k = 0; k < ma->n; ++k) {
-					int64_t dist;
-					r = infer_dir(l_pac, a->rb, ma->a[k].rb, &dist);
-					if (dist >= pes[r].low && dist <= pes[r].high) skip[r] = 1;
-				}
-				if (skip[0] + skip[1] + skip[2] + skip[3] == 4) { ++jj; continue; } /* :122, returns 0 */
-				e = &s->inv[s->n_inv++];
-				e->i = ii, e->j = jj;
-				for (r = 0; r < 4; ++r) { /* :123-142 */
-					int is_rev, is_larger;
-					int64_t rb, re;
-					e->plan[r] = 0;
-					if (skip[r]) continue;
-					is_rev = (r >> 1 != (r & 1)), is_larger = !(r >> 1);
-					if (!is_rev) {
-						rb = is_larger ? a->rb + pes[r].low : a->rb - pes[r].high;
-						re = (is_larger ? a->rb + pes[r].high : a->rb - pes[r].low) + l_ms;
-					} else {
-						rb = (is_larger ? a->rb + pes[r].low : a->rb - pes[r].high) - l_ms;
-						re = is_larger ? a->rb + pes[r].high : a->rb - pes[r].low;
-					}
-					if (rb < 0) rb = 0;
-					if (re > l_pac << 1) re = l_pac << 1;
-					e->rb[r] = rb, e->re[r] = re;
-					/* bns_get_seq hands back re-rb bases unless the interval is inverted or bridges the two strands
-					 * (bntseq.c:358-375); only then does mem_matesw call ksw_align2 (:144).  An empty window is still a call:
-					 * it scores 0, inserts nothing and counts (no GPU work) */
-					if (re == rb) e->plan[r] = -2;
-					else if (re > rb && (rb >= l_pac || re <= l_pac)) e->plan[r] = 1, ++want_tasks, win_bytes += (size_t)(re - rb);
-					else e->plan[r] = -3;
-				}
-				++jj;
-			}
+			if (ps[q].s.done) continue;
+			view(&ps[q], reads + 2 * p, regs + 2 * p, &io);
+			want_tasks += (size_t)bmh_msw_plan(l_pac, pes, &io, &ps[q].s, &wb);
+			win_bytes += (size_t)wb;
 			++active;
 		}
 		if (!active) break;
@@ -220,29 +157,23 @@ int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pa
 				}
 		}
 		for (q = 0; q < n_act; ++q) {
-			pair_t *s = &ps[q];
+			bmh_msw_pair_t *s = &ps[q].s;
 			int v;
 			p = act[q];
 			if (s->done) continue;
 			for (v = 0; v < s->n_inv; ++v) {
-				inv_t *e = &s->inv[v];
+				bmh_msw_inv_t *e = &s->inv[v];
 				const int mate = 2 * q + !e->i, l_ms = reads[2 * p + !e->i].l_seq; /* `mate` indexes read_off */
 				for (r = 0; r < 4; ++r) {
 					bmh_sw_task_t *t;
-					const int is_rev = (r >> 1 != (r & 1));
-					if (e->plan[r] <= 0) continue;
+					if (e->plan[r] != BMH_MSW_CALL) continue;
 					t = &tasks[n_tasks];
-					memset(t, 0, sizeof(*t));
-					t->qlen = (uint16_t)l_ms, t->tlen = (uint32_t)(e->re[r] - e->rb[r]);
-					t->q_off = is_rev ? read_off[mate] + (uint64_t)l_ms - 1 : read_off[mate]; /* :130-133 without the copy */
-					t->flags = is_rev ? BMH_F_QREV | BMH_F_QCOMP : 0;
-					if (tpac) t->t_off = (uint64_t)e->rb[r], t->flags |= BMH_F_TPAC;
-					else {
+					bmh_msw_task(P->a, o->min_seed_len, l_ms, r, read_off[mate], e->rb[r], e->re[r], t);
+					if (!tpac) { /* the window decoded on the host, behind the reads */
 						fetch_window(l_pac, pac, e->rb[r], e->re[r], pool + used);
-						t->t_off = used, used += (size_t)(e->re[r] - e->rb[r]);
+						t->t_off = used, used += (size_t)(e->re[r] - e->rb[r]), t->flags &= (uint16_t)~BMH_F_TPAC;
 					}
-					t->xtra = BMH_SW_XSUBO | BMH_SW_XSTART | (l_ms * P->a < 250 ? BMH_SW_XBYTE : 0) | (uint32_t)(o->min_seed_len * P->a); /* :147 */
-					e->plan[r] = (int)n_tasks + 1; /* 1-based index of its result */
+					e->plan[r] = (int32_t)n_tasks + 1; /* 1-based index of its result */
 					++n_tasks;
 				}
 			}
@@ -258,71 +189,37 @@ int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pa
 			if ((rc = bmh_sw_batch(ctx, 0, 0, tasks, (int64_t)n_tasks, res))) goto done;
 		}
 
-		/* ---- fold, invocation by invocation in the reference's order (:109-175), as far as the planned results reach */
+		/* ---- fold (bmh_msw_fold_step), invocation by invocation in the reference's order, as far as the planned results reach */
 		for (q = 0; q < n_act; ++q) {
-			pair_t *s = &ps[q];
+			const bmh_msw_dedup_t dd = {dedup, dedup_user, 0.f, 0};
 			p = act[q];
-			if (s->done) continue;
+			if (ps[q].s.done) continue;
 			for (;;) {
-				const bmh_alnreg_t *a;
-				bmh_alnreg_v *ma;
-				const inv_t *e = 0;
-				int skip[4], n = 0, l_ms, v, ok = 1;
-				size_t k;
-				while (s->i < 2 && !((size_t)s->j < s->b[s->i].n && s->j < o->max_matesw)) ++s->i, s->j = 0; /* :258-259 */
-				if (s->i == 2) { s->done = 1; break; }
-				a = &s->b[s->i].a[s->j], ma = &regs[2 * p + !s->i], l_ms = reads[2 * p + !s->i].l_seq;
-				for (r = 0; r < 4; ++r) skip[r] = pes[r].failed ? 1 : 0; /* :112-121, against the vector as it is NOW */
-				for (k = 0; k < ma->n; ++k) {
-					int64_t dist;
-					r = infer_dir(l_pac, a->rb, ma->a[k].rb, &dist);
-					if (dist >= pes[r].low && dist <= pes[r].high) skip[r] = 1;
-				}
-				if (skip[0] + skip[1] + skip[2] + skip[3] == 4) { ++s->j; continue; } /* :122, returns 0 */
-				for (v = 0; v < s->n_inv; ++v)
-					if (s->inv[v].i == s->i && s->inv[v].j == s->j) e = &s->inv[v];
-				if (!e) break; /* beyond this round's plan */
-				for (r = 0; r < 4; ++r)
-					if (!skip[r] && e->plan[r] == 0) ok = 0; /* an orientation that was skipped when planned is needed after all */
-				if (!ok) break;    /* (a dedup removed the region that covered it): planned afresh in the next round */
-				for (r = 0; r < 4; ++r) {
-					if (skip[r]) continue;
-					if (e->plan[r] > 0) {
-						const bmh_sw_result_t *aln = &res[e->plan[r] - 1];
-						const int is_rev = (r >> 1 != (r & 1));
-						const int64_t rb = e->rb[r];
-						if (aln->score >= o->min_seed_len && aln->qb >= 0) { /* :150-166 */
-							bmh_alnreg_t b;
-							size_t i, tmp;
-							memset(&b, 0, sizeof(b));
-							b.qb = is_rev ? l_ms - (aln->qe + 1) : aln->qb;
-							b.qe = is_rev ? l_ms - aln->qb : aln->qe + 1;
-							b.rb = is_rev ? (l_pac << 1) - (rb + aln->te + 1) : rb + aln->tb;
-							b.re = is_rev ? (l_pac << 1) - (rb + aln->tb) : rb + aln->te + 1;
-							b.score = aln->score, b.csub = aln->score2, b.secondary = -1;
-							b.seedcov = (int32_t)((b.re - b.rb < b.qe - b.qb ? b.re - b.rb : b.qe - b.qb) >> 1);
-							push_reg(ma, &b); /* make room, then move b so that ma stays sorted by score */
-							for (i = 0; i < ma->n - 1; ++i)
-								if (ma->a[i].score < b.score) break;
-							tmp = i;
-							for (i = ma->n - 1; i > tmp; --i) ma->a[i] = ma->a[i - 1];
-							ma->a[i] = b;
-						}
-						++n;
-					} else if (e->plan[r] == -2) ++n;
-					if (n) ma->n = (size_t)dedup(dedup_user, (int)ma->n, ma->a); /* :168 */
-				}
-				s->n += n;
-				++s->j;
+				bmh_msw_io_t io;
+				int c;
+				view(&ps[q], reads + 2 * p, regs + 2 * p, &io);
+				c = bmh_msw_fold_step(l_pac, pes, o->min_seed_len, &io, &ps[q].s, res, (uint32_t)n_tasks, &dd);
+				regs[2 * p].n = (size_t)io.n[0], regs[2 * p + 1].n = (size_t)io.n[1];
+				if (c == BMH_MSW_FULL) { /* kv_push's growth (kvec.h:68-74) until the invocation's regions fit */
+					bmh_alnreg_v *ma = &regs[2 * p + !ps[q].s.i];
+					bmh_alnreg_t *na;
+					size_t m = ma->m;
+					while (m < ma->n + 4) m = m ? m << 1 : 2;
+					if (!(na = (bmh_alnreg_t *)realloc(ma->a, sizeof(bmh_alnreg_t) * m))) { rc = BMH_E_NOMEM; goto done; }
+					ma->a = na, ma->m = m;
+				} else if (c == BMH_MSW_BAD) {
+					rc = BMH_E_ARG;
+					goto done;
+				} else if (c != BMH_MSW_FOLDED) break;
 			}
 		}
 	}
 	if (n_sw)
-		for (q = 0; q < n_act; ++q) n_sw[act[q]] = ps[q].n;
+		for (q = 0; q < n_act; ++q) n_sw[act[q]] = ps[q].s.n;
 done:
 	bmh_ctx_set_driver_stats_(ctx, &st);
 	if (ps)
-		for (q = 0; q < n_act; ++q) free(ps[q].b[0].a), free(ps[q].b[1].a);
+		for (q = 0; q < n_act; ++q) free(ps[q].b[0]), free(ps[q].b[1]);
 	free(ps), free(read_off), free(pool), free(tasks), free(res), free(act);
 	return rc;
 }

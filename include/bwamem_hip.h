@@ -511,6 +511,24 @@ typedef int (*bmh_dedup_fn)(void *user, int n, bmh_alnreg_t *a);
 int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pairs, const bmh_read_t *reads,
                      bmh_alnreg_v *regs, const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, bmh_dedup_fn dedup,
                      void *dedup_user, int *n_sw);
+/* The same driver as kernels (csrc/matesw.hip): the planning, the folding and mem_sort_and_dedup run on the device, one lane per
+ * pair that needs rescue, over the rules the host driver uses (one text, host/matesw_core.h) -- so both make the same ksw_align2
+ * calls in the same number of rounds.  Inside a call only 16-byte status words cross PCIe between the launches, and no host
+ * callback remains: mem_sort_and_dedup is bmh_sort_and_dedup's text at mask_level_redun.
+ *   result       regs and n_sw exactly as bmh_matesw_batch leaves them when its dedup is bmh_sort_and_dedup(n, a, mask_level_redun).
+ *                Only the vectors of pairs that need rescue are written: regs[k].a is realloc'd where m is too small, n is updated;
+ *                every other vector is not touched.  n_sw (nullable) is 0 for the other pairs.
+ *   BMH_E_ARG    a NULL ctx, reads, regs, pes or o; n_pairs < 0; l_pac <= 0; no parameters set; no 2-bit reference of this l_pac
+ *                resident on the device (bmh_ctx_set_pac); a vector with n > 0 and a == NULL
+ *   BMH_E_RANGE  a pair that needs rescue with a read outside 1..65535 bases, or whose ksw_align2 calls bmh_sw_batch would refuse
+ *                (they depend on the read's length and the parameters only): byte mode under gap penalties that wrap, and
+ *                l_seq*max(mat) >= 32000 without bmh_ctx_set_wide_sw.  Checked on the host before anything is uploaded.
+ *   BMH_OK       without a launch for n_pairs == 0 and for a batch in which no pair needs rescue
+ * On any error the caller's vectors are as they were: they are written after the last kernel has finished, all or none.
+ * bmh_driver_stats reports the host driver's numbers with the host driver's meanings: rounds that launched Smith-Waterman,
+ * ksw_align2 tasks, and as pool_bytes the reads of the pairs that need rescue plus 16 bytes of padding (0 if no round launched). */
+int bmh_matesw_device(bmh_ctx_t *ctx, int64_t l_pac, int n_pairs, const bmh_read_t *reads, bmh_alnreg_v *regs,
+                      const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, int *n_sw);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Region post-processing and SAM text: everything mem_process_seqs does with a read's region
