@@ -65,6 +65,13 @@ BMH_REGION_CIGAR_CUT, BMH_REGION_MD_CUT = 1, 2
 REGION_REQ = np.dtype([("q_src", "<u8"), ("rb", "<i8"), ("o_off", "<u8"), ("ql", "<i4"), ("tl", "<i4"), ("truesc", "<i4"),
                        ("task", "<i4", (3,))])
 REGION_RES = np.dtype([("score", "<i4"), ("n_cigar", "<i4"), ("tries", "<i4"), ("NM", "<i4"), ("md_len", "<i4"), ("flags", "<u4")])
+SAM_OPT = np.dtype([("a", "<i4"), ("b", "<i4"), ("o_del", "<i4"), ("e_del", "<i4"), ("o_ins", "<i4"), ("e_ins", "<i4"),
+                    ("pen_unpaired", "<i4"), ("w", "<i4"), ("T", "<i4"), ("flag", "<i4"), ("min_seed_len", "<i4"), ("max_ins", "<i4"),
+                    ("mapQ_coef_fac", "<i4"), ("max_matesw", "<i4"), ("mask_level", "<f4"), ("mask_level_redun", "<f4"),
+                    ("mapQ_coef_len", "<f4"), ("mat", "i1", (25,)), ("pad", "i1", (3,))])  # bmh_sam_opt_t
+MEM_F_PE, MEM_F_NOPAIRING, MEM_F_ALL = 0x2, 0x4, 0x8
+PAIRDEC = np.dtype([("paired", "<i4"), ("z", "<i4", (2,)), ("q_se", "<i4", (2,)), ("extra_flag", "<i4"), ("score", "<i4"), ("sub", "<i4"),
+                    ("n_sub", "<i4"), ("q_pe", "<i4"), ("rsv", "<i4", (2,))])  # bmh_pairdec_t
 ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
                    ("truesc", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"),
                    ("w", "<i4"), ("seedcov", "<i4"), ("secondary", "<i4"), ("hash", "<u8")])
@@ -194,6 +201,10 @@ def lib():
         L.bmh_sort_dedup_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float]
         L.bmh_ctx_set_regs_dedup.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.bmh_last_dedup_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.bmh_decide_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6
+        L.bmh_decide_device.argtypes = [C.c_void_p] + L.bmh_decide_batch.argtypes
+        L.bmh_ctx_set_decide_device.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_last_decide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_region_cigar_batch.restype = C.c_int
@@ -781,6 +792,20 @@ class Context:
         self._check(lib().bmh_last_dedup_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
         return a.value, b.value, ms.value
 
+    def decide_device(self, opt, l_pac, pes, id0, vectors, roff=None, inplace=False):
+        """bmh_decide_device: pass A of phase 2 as a kernel.  Arguments and result as decide_batch()."""
+        return _decide(self, opt, l_pac, pes, id0, vectors, roff, inplace)
+
+    def set_decide_device(self, on=True):
+        """bmh_ctx_set_decide_device: while on, bmh_sam_batch takes its pass A from bmh_decide_device."""
+        self._check(lib().bmh_ctx_set_decide_device(self._h, 1 if on else 0))
+
+    def last_decide_stats(self):
+        """(units decided on the device, 1 if the call answered BMH_E_RANGE else 0, kernel ms or -1) of the last bmh_decide_device call."""
+        a, b, ms = C.c_int64(0), C.c_int64(0), C.c_float(0)
+        self._check(lib().bmh_last_decide_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
+        return a.value, b.value, ms.value
+
     def reg2cigar_batch(self, l_pac, pac, reads, reqs):
         """Batched mem_reg2aln band/retry loop over bwa_gen_cigar2 (reference bwamem.c:1187-1201, bwa.c:89-172).
         reads: list of uint8 code arrays; reqs: CIGAR_REQ array.  Returns (results, cigar_pool, md_bytes)."""
@@ -806,6 +831,41 @@ class Context:
         st = _DriverStats()
         self._check(lib().bmh_driver_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in _DriverStats._fields_}
+
+
+def _decide(ctx, opt, l_pac, pes, id0, vectors, roff, inplace):
+    n = len(vectors)
+    o = np.array(opt, dtype=SAM_OPT).reshape(1)
+    bufs = list(vectors) if inplace else [np.array(v, dtype=ALNREG, copy=True).reshape(-1) for v in vectors]
+    c_regs = (_AlnregV * max(n, 1))()
+    for r, a in enumerate(bufs):
+        assert a.dtype == ALNREG and a.flags.c_contiguous
+        c_regs[r].n = c_regs[r].m = len(a)
+        c_regs[r].a = a.ctypes.data if len(a) else None
+    if roff is None:
+        roff = np.concatenate([[0], np.cumsum([len(a) for a in bufs])])
+    roff = np.ascontiguousarray(roff, dtype=np.int64)
+    total = int(sum(len(a) for a in bufs))
+    pe = bool(int(o["flag"][0]) & MEM_F_PE)
+    pd = np.zeros(n // 2 if pe else 0, dtype=PAIRDEC)
+    reg_mapq, want_k, n_want = np.full(total, -1, dtype=np.int32), np.full(total, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    pes_p = _ptr(np.ascontiguousarray(pes, dtype=PESTAT)) if pes is not None else None
+    args = (_ptr(o), C.c_int64(int(l_pac)), pes_p, C.c_int64(int(id0)), n, C.cast(c_regs, C.c_void_p), _ptr(roff), _ptr(pd) if pe else None,
+            _ptr(reg_mapq), _ptr(n_want), _ptr(want_k))
+    rc = lib().bmh_decide_batch(*args) if ctx is None else lib().bmh_decide_device(ctx._h, *args)
+    if rc:
+        raise BmhError(rc, lib().bmh_strerror(rc).decode() if ctx is None else lib().bmh_last_error(ctx._h).decode())
+    want = [want_k[int(roff[i]):int(roff[i]) + int(n_want[i])].copy() for i in range(n)]
+    return {"regs": bufs, "pd": pd, "reg_mapq": reg_mapq, "n_want": n_want, "want_k": want_k, "want": want}
+
+
+def decide_batch(opt, l_pac, pes, id0, vectors, roff=None, inplace=False):
+    """bmh_decide_batch: pass A of phase 2 on the host -- primary marking, pairing (opt.flag has MEM_F_PE: vectors 2p, 2p+1 are
+    mates, pes = PESTAT[4]), mapQ and the list of regions that get printed.  vectors: per read an ALNREG array (left as it is, or
+    with inplace=True worked on where it lies).
+    Returns a dict: regs (per read the vector as pass A leaves it), pd (PAIRDEC per pair), reg_mapq, n_want, want_k (flat, at the
+    regions' offsets; entries past n_want stay -1) and want (per read the printed regions' indices)."""
+    return _decide(None, opt, l_pac, pes, id0, vectors, roff, inplace)
 
 
 def extend_batch_sharded(ctxs, pool, tasks):

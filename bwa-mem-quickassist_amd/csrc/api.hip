@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "bmh_ctx.h"
+#include "decide.h"
 
 namespace bmh {
 
@@ -298,7 +299,10 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab), free_buf(ctx->d_c2r);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
-	free_buf(ctx->d_swl), free_buf(ctx->d_dedup), free_buf(ctx->d_msw);
+	free_buf(ctx->d_swl), free_buf(ctx->d_dedup), free_buf(ctx->d_msw), free_buf(ctx->d_decide), free_buf(ctx->d_logk);
+	free(ctx->h_logk);
+	for (auto &e : ctx->ev_decide)
+		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_chain)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_dedup)
@@ -1253,6 +1257,174 @@ int bmh_last_dedup_stats(const bmh_ctx_t *ctx, int64_t *regions_in, int64_t *reg
 	if (regions_out) *regions_out = ctx->dedup_out;
 	if (kernel_ms) *kernel_ms = ctx->dedup_ms;
 	return BMH_OK;
+}
+
+// ------------------------------------------------------------------ pass A of phase 2 (decide.hip)
+
+// the tables' entries, made by the compiler and libm of the host routines (host/sam_post.c)
+void bmh_pp_fill_log_(double *logk, int64_t k0, int64_t k1);
+void bmh_pp_fill_term_(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const int64_t term_off[4], double *term);
+
+int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs,
+                      const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k)
+{
+	constexpr long long kTabMax = 1LL << 20;
+	if (!ctx) return BMH_E_ARG;
+	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	if (rc) return rc;
+	if (n == 0) {
+		ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+		return BMH_OK;
+	}
+	const bool pe = (o->flag & BMH_MEM_F_PE) != 0, pairing = pe && !(o->flag & BMH_MEM_F_NOPAIRING);
+	const size_t total = (size_t)roff[n];
+	// what the tables must reach (bwamem_hip.h), before anything is uploaded
+	auto refuse = [&](const char *why) {
+		ctx->last_error = why;
+		ctx->decide_units = 0, ctx->decide_fallbacks = 1, ctx->decide_ms = -1.f;
+		return BMH_E_RANGE;
+	};
+	long long kmax = 1, n_term = 0;
+	int64_t term_off[4] = {0, 0, 0, 0};
+	for (int i = 0; i < n; ++i) {
+		const long long nv = (long long)regs[i].n;
+		for (long long j = 0; j < nv; ++j) {
+			const bmh_alnreg_t *a = &regs[i].a[j];
+			long long idx = 0;
+			if (o->mapQ_coef_len > 0) {
+				const int l = bmh_pp_len(a);
+				if (!(l < o->mapQ_coef_len)) idx = l;
+			} else idx = a->seedcov;
+			if (idx < 0) return refuse("bmh_decide_device: a region asks for the logarithm of a negative number");
+			kmax = std::max(kmax, std::max(idx, (long long)std::max(a->sub_n, 0) + nv + 1));
+		}
+		if (pe && (i & 1)) {
+			const long long m = (long long)regs[i - 1].n + nv;
+			kmax = std::max(kmax, m > 1024 ? kTabMax : m * m + 1); // (past 1024 the square is out of the table anyway, and of long long at 2^32)
+		}
+	}
+	if (kmax + 1 > kTabMax) return refuse("bmh_decide_device: the log table would pass 2^20 entries");
+	if (pairing)
+		for (int d = 0; d < 4; ++d) {
+			term_off[d] = n_term, n_term += bmh_pp_term_len(&pes[d]);
+			if (n_term > kTabMax) return refuse("bmh_decide_device: the pair table would pass 2^20 entries");
+		}
+	// the log table: resident, grown in powers of two
+	long long want_log = ctx->logk_n;
+	if (kmax + 1 > ctx->logk_n) {
+		for (want_log = 1 << 17; want_log < kmax + 1; want_log <<= 1) {}
+		if (want_log > ctx->logk_host_n) {
+			double *t = (double *)realloc(ctx->h_logk, sizeof(double) * (size_t)want_log);
+			if (!t) {
+				ctx->last_error = "bmh_decide_device: out of host memory";
+				return BMH_E_NOMEM;
+			}
+			bmh_pp_fill_log_(t, ctx->logk_host_n, want_log);
+			ctx->h_logk = t, ctx->logk_host_n = want_log;
+		}
+	}
+	// the device block: [offsets | opt + pes | pair table | regions] up, [regions | reg_mapq | want_k | n_want | pd] down (the regions
+	// come last in the upload so that the download is one copy), then the two scratch arrays
+	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+	const size_t nr = (size_t)n, o_hdr = al((nr + 1) * 8), o_term = o_hdr + al(sizeof(DecideHdr)), o_reg = o_term + al((size_t)n_term * 8);
+	const size_t o_mq = o_reg + al(total * sizeof(bmh_alnreg_t)), o_wk = o_mq + al(total * 4), o_nw = o_wk + al(total * 4), o_pd = o_nw + al(nr * 4);
+	const size_t o_z = o_pd + al(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0), o_v = o_z + al(total * 4), o_end = o_v + al(pe ? total * sizeof(bmh_pair64_t) : 0);
+	const size_t b_up = o_mq, b_down = o_z - o_reg;
+	uint8_t *up = (uint8_t *)malloc(b_up), *down = (uint8_t *)malloc(b_down);
+	struct Free {
+		uint8_t *a, *b;
+		~Free() { free(a), free(b); }
+	} guard{up, down};
+	if (!up || !down) {
+		ctx->last_error = "bmh_decide_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	memcpy(up, roff, (nr + 1) * 8);
+	DecideHdr *hdr = (DecideHdr *)(up + o_hdr);
+	memset(hdr, 0, sizeof(*hdr));
+	hdr->opt = *o;
+	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
+	if (n_term) bmh_pp_fill_term_(o, pes, term_off, (double *)(up + o_term));
+	for (int i = 0; i < n; ++i)
+		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	Stager st(ctx);
+	rc = [&]() -> int {
+		int e;
+		const bool grow = want_log > ctx->logk_n;
+		if (grow) ctx->logk_n = 0; // (ensure may drop the old table)
+		if ((e = ensure(ctx, ctx->d_decide, o_end)) || (e = ensure(ctx, ctx->d_logk, (size_t)std::max(want_log, 1LL) * 8))) return e;
+		if ((e = st.stage(b_up + (grow ? (size_t)want_log * 8 + 64 : 0), b_down + 64))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_decide.p;
+		if (grow && (e = st.h2d(ctx->d_logk.p, ctx->h_logk, (size_t)want_log * 8))) return e;
+		if ((e = st.h2d(d, up, b_up))) return e;
+		DecideArgs A{};
+		A.roff = (const unsigned long long *)d, A.hdr = (const DecideHdr *)(d + o_hdr);
+		A.tab.logk = (const double *)ctx->d_logk.p, A.tab.term = (const double *)(d + o_term);
+		memcpy(A.tab.term_off, term_off, sizeof(term_off));
+		A.tab.n_log = want_log, A.tab.n_term = n_term;
+		A.reg = (bmh_alnreg_t *)(d + o_reg), A.total = total;
+		A.reg_mapq = (int32_t *)(d + o_mq), A.want_k = (int32_t *)(d + o_wk), A.n_want = (int32_t *)(d + o_nw), A.pd = (bmh_pairdec_t *)(d + o_pd);
+		A.z = (int *)(d + o_z), A.v = (bmh_pair64_t *)(d + o_v);
+		A.l_pac = l_pac, A.id0 = id0, A.n = n, A.pe = pe, A.err = ctx->d_err;
+		if ((e = launch_decide(ctx, A))) return e;
+		return st.d2h(down, d + o_reg, b_down);
+	}();
+	if ((rc = st.end(rc))) return rc;
+	ctx->logk_n = want_log;
+	const int32_t *nw = (const int32_t *)(down + (o_nw - o_reg)), *wk = (const int32_t *)(down + (o_wk - o_reg));
+	for (int i = 0; i < n; ++i)
+		if (nw[i] < 0 || (size_t)nw[i] > regs[i].n) { // cannot happen
+			ctx->last_error = "bmh_decide_device: the device's counts are inconsistent";
+			return BMH_E_ARG;
+		}
+	// all or nothing: the caller's vectors and outputs only now
+	for (int i = 0; i < n; ++i)
+		if (regs[i].n) memcpy(regs[i].a, down + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].n * sizeof(bmh_alnreg_t));
+	memcpy(reg_mapq, down + (o_mq - o_reg), total * 4), memcpy(n_want, nw, nr * 4);
+	for (int i = 0; i < n; ++i) // (entries of want_k past a read's n_want stay the caller's)
+		if (nw[i]) memcpy(want_k + roff[i], wk + roff[i], (size_t)nw[i] * 4);
+	if (pe) memcpy(pd, down + (o_pd - o_reg), (nr >> 1) * sizeof(bmh_pairdec_t));
+	ctx->decide_units = pe ? n >> 1 : n, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
+	return BMH_OK;
+}
+
+int bmh_ctx_set_decide_device(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->decide_device = on != 0;
+	return BMH_OK;
+}
+
+int bmh_last_decide_stats(const bmh_ctx_t *ctx, int64_t *units, int64_t *fallbacks, float *kernel_ms)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (units) *units = ctx->decide_units;
+	if (fallbacks) *fallbacks = ctx->decide_fallbacks;
+	if (kernel_ms) *kernel_ms = ctx->decide_ms;
+	return BMH_OK;
+}
+
+// bmh_sam_batch at its entry, before any check of its own: with the switch on the statistics are this call's from here on
+__attribute__((visibility("hidden"))) void bmh_decide_stats_reset_(bmh_ctx_t *ctx)
+{
+	if (ctx && ctx->decide_device) ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+}
+
+// bmh_sam_batch's pass A (host/sam_post.c; not part of the interface)
+__attribute__((visibility("hidden"))) int bmh_decide_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0,
+                                                             int n, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq,
+                                                             int32_t *n_want, int32_t *want_k)
+{
+	if (ctx && ctx->decide_device) {
+		// (statistics of THIS call: a slice that never reaches the device call must not leave an earlier slice's on the context)
+		ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+		const int rc = bmh_decide_device(ctx, o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k);
+		if (rc != BMH_E_RANGE) return rc;
+	}
+	return bmh_decide_batch(o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k);
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

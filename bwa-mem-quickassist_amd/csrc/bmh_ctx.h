@@ -116,6 +116,16 @@ struct bmh_ctx {
 	hipEvent_t ev_dedup[2] = {};              // around the kernel (timing mode)
 	long long dedup_in = -1, dedup_out = -1;  // regions in / kept of the last call that ran it (bmh_last_dedup_stats), -1 = none yet
 	float dedup_ms = -1.f;                    // ... and the kernel's duration with kernel timing on, else -1
+	// pass A of phase 2 on the device (decide_kernel, decide.hip): bmh_decide_device, and bmh_sam_batch with the switch on
+	bool decide_device = false;               // bmh_ctx_set_decide_device
+	DevBuf d_decide;                          // a call's block: offsets, parameters, pair table, regions, outputs, scratch
+	DevBuf d_logk;                            // log(k), k = 0..logk_n-1, resident; grown when a call needs more
+	long long logk_n = 0;
+	double *h_logk = nullptr;                 // the host's copy (malloc), logk_host_n entries
+	long long logk_host_n = 0;
+	hipEvent_t ev_decide[2] = {};             // around the kernel (timing mode)
+	long long decide_units = -1, decide_fallbacks = 0; // of the last bmh_decide_device call (bmh_last_decide_stats)
+	float decide_ms = -1.f;
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 

@@ -21,6 +21,10 @@
  * Mate rescue (bmh_matesw_batch per slice of the chunk) has a switch of its own:
  *   BMH_MATESW_DEVICE=1  mate rescue's driver (planning, folding, mem_sort_and_dedup) as kernels, bmh_matesw_device(): no host
  *                        callback, 16 bytes per round back.  Needs BMH_PAC_RESIDENT not 0; independent of BMH_REGS_DEVICE.
+ * Phase 2 (bmh_sam_batch per slice) has one too:
+ *   BMH_DECIDE_DEVICE=1  its pass A -- primary marking, pairing, mapQ, the list of regions that get printed -- as a kernel
+ *                        (bmh_ctx_set_decide_device); a slice the device call refuses as out of range is decided on the host.
+ *                        Independent of the other switches; needs no resident reference.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -389,6 +393,20 @@ static int qa_matesw_device(void)
 	return on;
 }
 
+/* BMH_DECIDE_DEVICE=1: phase 2's pass A (primary marking, pairing, mapQ, the selection of what gets printed) on the device
+ * (bmh_ctx_set_decide_device on every pooled context phase 2 uses).  Independent of the other device switches; needs no resident
+ * reference. */
+static int qa_decide_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_DECIDE_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_decide_cnt[2]; /* reads or pairs decided on the device, slices that fell back to the host */
+
 /* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
 static int qa_regs_device(void)
 {
@@ -636,6 +654,7 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 	bmh_ctx_t *ctx = bmh_pool_get(J->params);
 	int rc;
 	if (J->resident && (rc = bmh_ctx_set_pac(ctx, J->pac, J->bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
+	if ((rc = bmh_ctx_set_decide_device(ctx, qa_decide_device()))) bmh_tls_die(bmh_last_error(ctx), rc); /* per pooled context */
 	return ctx;
 }
 
@@ -691,6 +710,11 @@ static void qa_sam_slice(void *data, int k, int tid)
 	if ((rc = bmh_sam_batch(ctx, J->sopt, (const bmh_refidx_t *)J->bns, J->pac, J->pes, J->n_processed + lo, hi - lo, (bmh_seq_t *)(J->seqs + lo),
 	                        J->regs + lo, bwa_rg_id)))
 		bmh_tls_die(rc == BMH_E_ARG ? "a region could not be turned into an alignment (the reference aborts here too, bwamem.c:1183-1186)" : bmh_last_error(ctx), rc);
+	if (qa_decide_device()) {
+		int64_t du = 0, df = 0;
+		bmh_last_decide_stats(ctx, &du, &df, 0);
+		__sync_fetch_and_add(&g_decide_cnt[0], (long long)(du > 0 ? du : 0)), __sync_fetch_and_add(&g_decide_cnt[1], (long long)df);
+	}
 	bmh_pool_put(ctx);
 	t2 = stage_now();
 	for (i = lo; i < hi; ++i) free(J->regs[i].a);
@@ -812,6 +836,8 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 			        g_dedup_cnt[0], g_dedup_cnt[1], g_dedup_cnt[2]);
 		if (rescue) fprintf(stderr, "[bwamem_hip] mate rescue driver so far: %.3f thread-s in %s\n", g_msw_us * 1e-6, qa_matesw_device() ? "bmh_matesw_device" : "bmh_matesw_batch");
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
+		if (qa_decide_device())
+			fprintf(stderr, "[bwamem_hip] phase 2 decisions on the device: %lld units, %lld host fall-backs\n", g_decide_cnt[0], g_decide_cnt[1]);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());
 			fprintf(stderr, "[bwamem_hip] wide Smith-Waterman so far: %lld ksw_align2 tasks on the long-query kernel\n", bmh_pool_swl_tasks());

@@ -28,6 +28,7 @@
 
 #include "../../include/bwamem_hip.h"
 #include "dedup_core.h"
+#include "postproc_core.h"
 #include "sort_exact.h"
 
 static double now_s(void) /* the clock of the BMH_DRIVER_TRACE lines: wall time, or with BMH_TRACE_CPU this thread's CPU time */
@@ -45,30 +46,11 @@ static double now_s(void) /* the clock of the BMH_DRIVER_TRACE lines: wall time,
 #define OUTLIER_BOUND 2.0
 #define MAPPING_BOUND 3.0
 #define MAX_STDDEV 4.0
-#define MEM_MAPQ_COEF 30.0 /* bwamem.h:11 */
 
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
 
-static inline uint64_t hash_64(uint64_t key) /* utils.h:98-109 */
-{
-	key += ~(key << 32);
-	key ^= (key >> 22);
-	key += ~(key << 13);
-	key ^= (key >> 8);
-	key += (key << 3);
-	key ^= (key >> 15);
-	key += ~(key << 27);
-	key ^= (key >> 31);
-	return key;
-}
-
-/* ---- orders (bwamem.c:386-393, utils.c:45); those of mem_sort_and_dedup are in dedup_core.h */
-static int lt_score_hash(const void *x, const void *y)
-{
-	const bmh_alnreg_t *a = (const bmh_alnreg_t *)x, *b = (const bmh_alnreg_t *)y;
-	return a->score > b->score || (a->score == b->score && a->hash < b->hash);
-}
+/* ---- orders (utils.c:45); those of mem_sort_and_dedup are in dedup_core.h, those of marking and pairing in postproc_core.h */
 static int lt_u64(const void *x, const void *y) { return *(const uint64_t *)x < *(const uint64_t *)y; }
 static void sort_u64(uint64_t *a, size_t n, uint64_t max) /* insert sizes: 1..max_ins -> a counting sort where that is small */
 {
@@ -86,12 +68,6 @@ static void sort_u64(uint64_t *a, size_t n, uint64_t max) /* insert sizes: 1..ma
 	}
 	bmh_sort_exact(a, n, 8, lt_u64);
 }
-typedef struct { uint64_t x, y; } pair64_t;
-static int lt_pair64(const void *p, const void *q)
-{
-	const pair64_t *a = (const pair64_t *)p, *b = (const pair64_t *)q;
-	return a->x < b->x || (a->x == b->x && a->y < b->y);
-}
 
 /* ---- bwamem.c:395-436: the routine is dedup_core.h's, shared with the device kernel; here only its range stack */
 int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun)
@@ -100,81 +76,26 @@ int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun)
 	return bmh_dedup_core(n, a, mask_level_redun, stk);
 }
 
-static inline int gap_tmp(const bmh_sam_opt_t *o) /* the largest single-event penalty, bwamem.c:455-457 */
-{
-	int tmp = o->a + o->b;
-	tmp = o->o_del + o->e_del > tmp ? o->o_del + o->e_del : tmp;
-	return o->o_ins + o->e_ins > tmp ? o->o_ins + o->e_ins : tmp;
-}
+#define SORT_STK_LEN (8 * sizeof(size_t) + 2) /* >= bmh_sort_stack_len(n) for any n */
 
-/* ---- bwamem.c:445-475 */
+/* ---- bwamem.c:445-475: the routine is postproc_core.h's, shared with the device kernel; here its z[] list and range stack */
 void bmh_mark_primary_se(const bmh_sam_opt_t *o, int n, bmh_alnreg_t *a, int64_t id)
 {
-	int i, k, nz = 0, tmp, zs[64], *z = zs, zcap = 64;
-	if (n == 0) return;
-	for (i = 0; i < n; ++i) a[i].sub = 0, a[i].secondary = -1, a[i].hash = hash_64((uint64_t)(id + i));
-	bmh_sort_exact(a, (size_t)n, sizeof(*a), lt_score_hash);
-	tmp = gap_tmp(o);
-	z[nz++] = 0;
-	for (i = 1; i < n; ++i) {
-		for (k = 0; k < nz; ++k) {
-			const int j = z[k];
-			const int b_max = imax(a[j].qb, a[i].qb), e_min = imin(a[j].qe, a[i].qe);
-			if (e_min > b_max) { /* overlap on the query */
-				const int min_l = imin(a[i].qe - a[i].qb, a[j].qe - a[j].qb);
-				if (e_min - b_max >= min_l * o->mask_level) { /* significant */
-					if (a[j].sub == 0) a[j].sub = a[i].score;
-					if (a[j].score - a[i].score <= tmp) ++a[j].sub_n;
-					break;
-				}
-			}
-		}
-		if (k == nz) {
-			if (nz == zcap) {
-				int *z2 = (int *)malloc(sizeof(int) * (size_t)zcap * 2);
-				memcpy(z2, z, sizeof(int) * (size_t)nz);
-				if (z != zs) free(z);
-				z = z2, zcap *= 2;
-			}
-			z[nz++] = i;
-		} else a[i].secondary = z[k];
+	bmh_sort_stk_t stk[SORT_STK_LEN];
+	int zs[64], *z = zs;
+	if (n <= 0) return;
+	/* (the reference aborts when its z vector cannot grow; a void routine cannot report it, so say it and leave the vector as it
+	 * came -- bmh_decide_batch, which bmh_sam_batch uses, answers BMH_E_NOMEM instead) */
+	if (n > 64 && !(z = (int *)malloc(sizeof(int) * (size_t)n))) {
+		fprintf(stderr, "[bwamem_hip] bmh_mark_primary_se: out of memory, %d regions left unmarked\n", n);
+		return;
 	}
+	bmh_pp_mark(o, n, a, id, z, stk);
 	if (z != zs) free(z);
 }
 
 /* ---- bwamem.c:1023-1047 */
-int bmh_approx_mapq_se(const bmh_sam_opt_t *o, const bmh_alnreg_t *a)
-{
-	int mapq, l, sub = a->sub ? a->sub : o->min_seed_len * o->a;
-	double identity;
-	sub = a->csub > sub ? a->csub : sub;
-	if (sub >= a->score) return 0;
-	l = a->qe - a->qb > a->re - a->rb ? a->qe - a->qb : (int)(a->re - a->rb);
-	identity = 1. - (double)(l * o->a - a->score) / (o->a + o->b) / l;
-	if (a->score == 0) mapq = 0;
-	else if (o->mapQ_coef_len > 0) {
-		double tmp;
-		tmp = l < o->mapQ_coef_len ? 1. : o->mapQ_coef_fac / log(l);
-		tmp *= identity * identity;
-		mapq = (int)(6.02 * (a->score - sub) / o->a * tmp * tmp + .499);
-	} else {
-		mapq = (int)(MEM_MAPQ_COEF * (1. - (double)sub / a->score) * log(a->seedcov) + .499);
-		mapq = identity < 0.95 ? (int)(mapq * identity * identity + .499) : mapq;
-	}
-	if (a->sub_n > 0) mapq -= (int)(4.343 * log(a->sub_n + 1) + .499);
-	if (mapq > 60) mapq = 60;
-	if (mapq < 0) mapq = 0;
-	return mapq;
-}
-
-/* ---- bwamem_pair.c:25-32 */
-static inline int infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist)
-{
-	const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-	const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2; /* read 2 on the strand of read 1 */
-	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
-	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
+int bmh_approx_mapq_se(const bmh_sam_opt_t *o, const bmh_alnreg_t *a) { return bmh_pp_mapq(o, a, 0); }
 
 /* ---- bwamem_pair.c:34-44 */
 static int cal_sub(const bmh_sam_opt_t *o, const bmh_alnreg_v *r)
@@ -207,7 +128,7 @@ void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v
 		if (r0->n == 0 || r1->n == 0) continue;
 		if (cal_sub(o, r0) > MIN_RATIO * r0->a[0].score) continue;
 		if (cal_sub(o, r1) > MIN_RATIO * r1->a[0].score) continue;
-		dir = infer_dir(l_pac, r0->a[0].rb, r1->a[0].rb, &is);
+		dir = bmh_pp_infer_dir(l_pac, r0->a[0].rb, r1->a[0].rb, &is);
 		if (is && is <= o->max_ins) {
 			if (isize[dir].n == isize[dir].m) {
 				isize[dir].m = isize[dir].m ? isize[dir].m << 1 : 2;
@@ -265,84 +186,70 @@ void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v
 	}
 }
 
-/* ---- bwamem_pair.c:177-238.  Scratch vectors are the caller's (reused across pairs). */
-typedef struct { size_t n, m; pair64_t *a; } pair64_v;
-static pair64_t *pv_push(pair64_v *v)
-{
-	if (v->n == v->m) {
-		v->m = v->m ? v->m << 1 : 16;
-		v->a = (pair64_t *)realloc(v->a, sizeof(pair64_t) * v->m);
-	}
-	return &v->a[v->n++];
-}
-
-static int pair_ends(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], const bmh_alnreg_v a[2], uint64_t id, int *sub,
-                     int *n_sub, int z[2], pair64_v *v, pair64_v *u)
-{
-	int r, y[4], ret;
-	size_t i;
-	v->n = u->n = 0;
-	for (r = 0; r < 2; ++r)
-		for (i = 0; i < a[r].n; ++i) {
-			const bmh_alnreg_t *e = &a[r].a[i];
-			pair64_t *key = pv_push(v);
-			key->x = (uint64_t)(e->rb < l_pac ? e->rb : (l_pac << 1) - 1 - e->rb); /* forward position */
-			key->y = (uint64_t)e->score << 32 | (uint64_t)(i << 2) | (uint64_t)((e->rb >= l_pac) << 1) | (uint64_t)r;
-		}
-	bmh_sort_exact(v->a, v->n, sizeof(pair64_t), lt_pair64);
-	y[0] = y[1] = y[2] = y[3] = -1;
-	for (i = 0; i < v->n; ++i) {
-		for (r = 0; r < 2; ++r) { /* direction */
-			const int dir = r << 1 | (int)(v->a[i].y >> 1 & 1);
-			int which, k;
-			if (pes[dir].failed) continue;
-			which = r << 1 | (int)((v->a[i].y & 1) ^ 1);
-			if (y[which] < 0) continue; /* no earlier hit of that kind */
-			for (k = y[which]; k >= 0; --k) {
-				int64_t dist;
-				int q;
-				double ns;
-				pair64_t *p;
-				if ((int)(v->a[k].y & 3) != which) continue;
-				dist = (int64_t)v->a[i].x - (int64_t)v->a[k].x;
-				if (dist > pes[dir].high) break;
-				if (dist < pes[dir].low) continue;
-				ns = (dist - pes[dir].avg) / pes[dir].std;
-				q = (int)((v->a[i].y >> 32) + (v->a[k].y >> 32) + .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * o->a + .499); /* .721 = 1/log(4) */
-				if (q < 0) q = 0;
-				p = pv_push(u);
-				p->y = (uint64_t)k << 32 | i;
-				/* the reference's mem_pair takes the pair id as an `int` (bwamem_pair.c:177) and shifts it as one */
-				p->x = (uint64_t)q << 32 | (hash_64(p->y ^ (uint64_t)(int64_t)(int32_t)((uint32_t)(int32_t)id << 8)) & 0xffffffffU);
-			}
-		}
-		y[v->a[i].y & 3] = (int)i;
-	}
-	if (u->n) { /* at least one proper pair */
-		const int tmp = gap_tmp(o);
-		long k2;
-		size_t bi, bk;
-		bmh_sort_exact(u->a, u->n, sizeof(pair64_t), lt_pair64);
-		bi = (size_t)(u->a[u->n - 1].y >> 32), bk = (size_t)(u->a[u->n - 1].y << 32 >> 32);
-		z[v->a[bi].y & 1] = (int)(v->a[bi].y << 32 >> 34); /* index of the best pair */
-		z[v->a[bk].y & 1] = (int)(v->a[bk].y << 32 >> 34);
-		ret = (int)(u->a[u->n - 1].x >> 32);
-		*sub = u->n > 1 ? (int)(u->a[u->n - 2].x >> 32) : 0;
-		for (k2 = (long)u->n - 2, *n_sub = 0; k2 >= 0; --k2)
-			if (*sub - (int)(u->a[k2].x >> 32) <= tmp) ++*n_sub;
-	} else ret = 0, *sub = 0, *n_sub = 0;
-	return ret;
-}
-
+/* ---- bwamem_pair.c:177-238: the routine is postproc_core.h's; here its key vector and range stack */
 int bmh_pair(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], const bmh_alnreg_v a[2], uint64_t id, int *sub, int *n_sub, int z[2])
 {
-	pair64_v v = {0, 0, 0}, u = {0, 0, 0};
-	const int ret = pair_ends(o, l_pac, pes, a, id, sub, n_sub, z, &v, &u);
-	free(v.a), free(u.a);
+	bmh_sort_stk_t stk[SORT_STK_LEN];
+	bmh_pair64_t *v = (bmh_pair64_t *)malloc(sizeof(bmh_pair64_t) * (a[0].n + a[1].n + 1));
+	int ret;
+	*sub = *n_sub = 0;
+	if (!v) return 0;
+	ret = bmh_pp_pair(o, l_pac, pes, 0, (int)a[0].n, a[0].a, (int)a[1].n, a[1].a, id, sub, n_sub, z, v, stk);
+	free(v);
 	return ret;
 }
 
-#define raw_mapq(diff, a) ((int)(6.02 * (diff) / (a) + .499)) /* bwamem_pair.c:238 */
+/* ---- pass A of bmh_sam_batch: the decisions, per read or pair, over postproc_core.h (on the device: bmh_decide_device) */
+int bmh_decide_batch(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs, const int64_t *roff,
+                     bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k)
+{
+	bmh_sort_stk_t stk[SORT_STK_LEN];
+	const int pe = o && (o->flag & BMH_MEM_F_PE) != 0;
+	size_t zmax = 1, vmax = 1;
+	int *z = 0;
+	bmh_pair64_t *v = 0;
+	int i, rc;
+	if ((rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k))) return rc;
+	if (n == 0) return BMH_OK;
+	for (i = 0; i < n; ++i) {
+		zmax = regs[i].n > zmax ? regs[i].n : zmax;
+		if (pe && (i & 1)) vmax = regs[i - 1].n + regs[i].n > vmax ? regs[i - 1].n + regs[i].n : vmax;
+	}
+	z = (int *)malloc(sizeof(int) * zmax * 2);
+	if (pe) v = (bmh_pair64_t *)malloc(sizeof(bmh_pair64_t) * vmax);
+	if (!z || (pe && !v)) {
+		free(z), free(v);
+		return BMH_E_NOMEM;
+	}
+	if (!pe) {
+		for (i = 0; i < n; ++i) { /* worker2's SE branch, bwamem.c:1285-1289 */
+			if (i + 8 < n) __builtin_prefetch(regs[i + 8].a);
+			bmh_pp_unit_se(o, 0, id0 + i, (int)regs[i].n, regs[i].a, z, stk, reg_mapq + roff[i], &n_want[i], want_k + roff[i]);
+		}
+	} else {
+		for (i = 0; i < n >> 1; ++i) { /* mem_sam_pe after its rescue block, bwamem_pair.c:264-331 */
+			const bmh_alnreg_v *a = &regs[i << 1];
+			const uint64_t id = (uint64_t)(id0 >> 1) + (uint64_t)i;
+			const int nn[2] = {(int)a[0].n, (int)a[1].n};
+			bmh_alnreg_t *const aa[2] = {a[0].a, a[1].a};
+			int *const zz[2] = {z, z + zmax};
+			int32_t *const mq[2] = {reg_mapq + roff[i << 1], reg_mapq + roff[i << 1 | 1]};
+			int32_t *const wk[2] = {want_k + roff[i << 1], want_k + roff[i << 1 | 1]};
+			if (i + 6 < n >> 1) __builtin_prefetch(regs[(i + 6) << 1].a), __builtin_prefetch(regs[(i + 6) << 1 | 1].a);
+			bmh_pp_unit_pe(o, l_pac, pes, 0, id, nn, aa, zz, v, stk, &pd[i], mq, &n_want[i << 1], wk);
+		}
+	}
+	free(z), free(v);
+	return BMH_OK;
+}
+
+/* the device call's tables, made HERE so that they come from the compiler and the libm the host routines above use
+ * (csrc/api.hip calls these; not part of the interface) */
+__attribute__((visibility("hidden"))) void bmh_pp_fill_log_(double *logk, int64_t k0, int64_t k1) { bmh_pp_fill_log(logk, k0, k1); }
+__attribute__((visibility("hidden"))) void bmh_pp_fill_term_(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const int64_t term_off[4], double *term)
+{
+	bmh_pp_fill_term(o, pes, term_off, term);
+}
 
 /* ================================================================================================ alignments and text */
 
@@ -563,10 +470,6 @@ typedef struct { /* one region that gets an alignment */
 	int64_t cb, ce;   /* ... and the interval it has to be cut to */
 } want_t;
 
-typedef struct { /* pass A's verdict on a pair */
-	int paired, z[2], q_se[2], extra_flag;
-} pairdec_t;
-
 static void unmapped(aln_t *a) /* mem_reg2aln(..., 0), bwamem.c:1171-1175 */
 {
 	memset(a, 0, sizeof(*a));
@@ -590,21 +493,11 @@ static int want_push(want_v *w, int read, int k, const bmh_alnreg_t *ar)
 	return 0;
 }
 
-/* the regions mem_reg2sam_se prints, bwamem.c:1057-1062 (k = 0 first: it is also the `h` of mem_sam_pe's no_pairing) */
-static int want_se(const bmh_sam_opt_t *o, want_v *w, int read, const bmh_alnreg_v *a)
-{
-	size_t k;
-	int rc;
-	for (k = 0; k < a->n; ++k) {
-		const bmh_alnreg_t *p = &a->a[k];
-		if (p->score < o->T) continue;
-		if (p->secondary >= 0 && !(o->flag & BMH_MEM_F_ALL)) continue;
-		if (p->secondary >= 0 && p->score < a->a[p->secondary].score * .5) continue;
-		if (p->rb < 0 || p->re < 0) continue; /* mem_reg2aln then writes an unmapped record, bwamem.c:1172 */
-		if ((rc = want_push(w, read, (int)k, p))) return rc;
-	}
-	return 0;
-}
+/* pass A behind the context's switch (csrc/api.hip): bmh_decide_device while bmh_ctx_set_decide_device is on, falling back to
+ * bmh_decide_batch where that answers BMH_E_RANGE; bmh_decide_batch otherwise */
+void bmh_decide_stats_reset_(bmh_ctx_t *ctx);
+int bmh_decide_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs,
+                       const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k);
 
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id)
@@ -612,7 +505,9 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	const int pe = (o->flag & BMH_MEM_F_PE) != 0;
 	const int64_t l_pac = bns ? bns->l_pac : 0;
 	want_v W = {0, 0, 0};
-	pairdec_t *pd = 0;
+	bmh_pairdec_t *pd = 0;
+	int64_t *roff = 0;
+	int32_t *reg_mapq = 0, *n_want = 0, *want_k = 0;
 	bmh_read_t *reads = 0;
 	bmh_cigar_req_t *reqs = 0;
 	bmh_cigar_res_t *res = 0;
@@ -620,86 +515,39 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	char *md = 0;
 	size_t *first = 0; /* first entry of W per read (+1 sentinel) */
 	aln_t *alns = 0;
-	pair64_v pv = {0, 0, 0}, pu = {0, 0, 0};
 	str_t str = {0, 0, 0};
 	size_t j, cw = 8, mb = 16, n_fix = 0, arena_words = 0;
 	int i, rc = BMH_OK;
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0;
 	double tt[4] = {0, 0, 0, 0};
 
+	bmh_decide_stats_reset_(ctx);
 	if (!ctx || !o || !bns || !pac || n < 0 || (n > 0 && (!seqs || !regs)) || (pe && ((n & 1) || !pes))) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
 	first = (size_t *)calloc((size_t)n + 1, sizeof(size_t));
 	reads = (bmh_read_t *)malloc(sizeof(bmh_read_t) * (size_t)n);
-	if (pe) pd = (pairdec_t *)calloc((size_t)(n >> 1), sizeof(pairdec_t));
-	if (!first || !reads || (pe && !pd)) { rc = BMH_E_NOMEM; goto done; }
+	roff = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+	n_want = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
+	if (pe) pd = (bmh_pairdec_t *)calloc((size_t)(n >> 1), sizeof(bmh_pairdec_t));
+	if (!first || !reads || !roff || !n_want || (pe && !pd)) { rc = BMH_E_NOMEM; goto done; }
 	for (i = 0; i < n; ++i) reads[i].l_seq = seqs[i].l_seq, reads[i].seq = (const uint8_t *)seqs[i].seq;
+	for (i = 0, roff[0] = 0; i < n; ++i) {
+		if (regs[i].n && !regs[i].a) { rc = BMH_E_ARG; goto done; }
+		roff[i + 1] = roff[i] + (int64_t)regs[i].n;
+	}
+	reg_mapq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)roff[n] + 1));
+	want_k = (int32_t *)malloc(sizeof(int32_t) * ((size_t)roff[n] + 1));
+	if (!reg_mapq || !want_k) { rc = BMH_E_NOMEM; goto done; }
 
 	if (trace) tt[0] = now_s();
-	/* ---- pass A: decisions */
-	if (!pe) {
-		for (i = 0; i < n; ++i) { /* worker2's SE branch, bwamem.c:1285-1289 */
-			if (i + 8 < n) __builtin_prefetch(regs[i + 8].a);
-			bmh_mark_primary_se(o, (int)regs[i].n, regs[i].a, id0 + i);
-			first[i] = W.n;
-			if ((rc = want_se(o, &W, i, &regs[i]))) goto done;
-		}
-	} else {
-		for (i = 0; i < n >> 1; ++i) { /* mem_sam_pe after its rescue block, bwamem_pair.c:264-331 */
-			bmh_alnreg_v *a = &regs[i << 1];
-			if (i + 6 < n >> 1) __builtin_prefetch(regs[(i + 6) << 1].a), __builtin_prefetch(regs[(i + 6) << 1 | 1].a);
-			const uint64_t id = (uint64_t)(id0 >> 1) + (uint64_t)i;
-			pairdec_t *d = &pd[i];
-			int sub_o = 0, n_sub = 0, oo, r, go_pair = 0;
-			bmh_mark_primary_se(o, (int)a[0].n, a[0].a, (int64_t)(id << 1 | 0));
-			bmh_mark_primary_se(o, (int)a[1].n, a[1].a, (int64_t)(id << 1 | 1));
-			d->extra_flag = 1;
-			if (!(o->flag & BMH_MEM_F_NOPAIRING) && a[0].n && a[1].n &&
-			    (oo = pair_ends(o, l_pac, pes, a, id, &sub_o, &n_sub, d->z, &pv, &pu)) > 0) {
-				int is_multi[2], q_pe, score_un;
-				size_t jj;
-				for (r = 0; r < 2; ++r) { /* more than one good hit at an end even after rescue? */
-					for (jj = 1; jj < a[r].n; ++jj)
-						if (a[r].a[jj].secondary < 0 && a[r].a[jj].score >= o->T) break;
-					is_multi[r] = jj < a[r].n;
-				}
-				if (!is_multi[0] && !is_multi[1]) {
-					go_pair = 1;
-					score_un = a[0].a[0].score + a[1].a[0].score - o->pen_unpaired;
-					sub_o = sub_o > score_un ? sub_o : score_un;
-					q_pe = raw_mapq(oo - sub_o, o->a);
-					if (n_sub > 0) q_pe -= (int)(4.343 * log(n_sub + 1) + .499);
-					if (q_pe < 0) q_pe = 0;
-					if (q_pe > 60) q_pe = 60;
-					if (oo > score_un) { /* the pair wins */
-						bmh_alnreg_t *c[2];
-						c[0] = &a[0].a[d->z[0]], c[1] = &a[1].a[d->z[1]];
-						for (r = 0; r < 2; ++r) {
-							if (c[r]->secondary >= 0) c[r]->sub = a[r].a[c[r]->secondary].score, c[r]->secondary = -2;
-							d->q_se[r] = bmh_approx_mapq_se(o, c[r]);
-						}
-						for (r = 0; r < 2; ++r) d->q_se[r] = d->q_se[r] > q_pe ? d->q_se[r] : q_pe < d->q_se[r] + 40 ? q_pe : d->q_se[r] + 40;
-						d->extra_flag |= 2;
-						for (r = 0; r < 2; ++r) { /* cap at the tandem-repeat score */
-							const int cap = raw_mapq(c[r]->score - c[r]->csub, o->a);
-							d->q_se[r] = d->q_se[r] < cap ? d->q_se[r] : cap;
-						}
-					} else { /* the two best single-end hits win */
-						d->z[0] = d->z[1] = 0;
-						d->q_se[0] = bmh_approx_mapq_se(o, &a[0].a[0]);
-						d->q_se[1] = bmh_approx_mapq_se(o, &a[1].a[0]);
-					}
-				}
-			}
-			d->paired = go_pair;
-			for (r = 0; r < 2; ++r) {
-				const int rd = i << 1 | r;
-				first[rd] = W.n;
-				if (go_pair) {
-					const bmh_alnreg_t *ar = &a[r].a[d->z[r]];
-					if (ar->rb >= 0 && ar->re >= 0 && (rc = want_push(&W, rd, d->z[r], ar))) goto done;
-				} else if ((rc = want_se(o, &W, rd, &a[r]))) goto done;
-			}
+	/* ---- pass A: decisions (bmh_decide_batch, or bmh_decide_device behind the context's switch), then the want list as records */
+	if ((rc = bmh_decide_routed_(ctx, o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k))) goto done;
+	for (i = 0; i < n; ++i) {
+		int q;
+		first[i] = W.n;
+		for (q = 0; q < n_want[i]; ++q) {
+			const int k = want_k[roff[i] + q];
+			if ((rc = want_push(&W, i, k, &regs[i].a[k]))) goto done;
 		}
 	}
 	first[n] = W.n;
@@ -814,7 +662,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 		int64_t pos;
 		if (res[j].NM < 0) { rc = BMH_E_ARG; goto done; } /* bwa_gen_cigar2 refused the region (bwa.c:99): cannot happen after the fix */
 		memset(a, 0, sizeof(*a));
-		a->mapq = ar->secondary < 0 ? bmh_approx_mapq_se(o, ar) : 0;
+		a->mapq = ar->secondary < 0 ? reg_mapq[roff[x->read] + x->k] : 0;
 		if (ar->secondary >= 0) a->flag |= 0x100;
 		a->NM = res[j].NM, a->md = md + res[j].md_off;
 		pos = depos(l_pac, x->rb < l_pac ? x->rb : x->re - 1, &is_rev);
@@ -852,7 +700,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 		}
 		unmapped(&un);
 		if (pe) {
-			const pairdec_t *d = &pd[i >> 1];
+			const bmh_pairdec_t *d = &pd[i >> 1];
 			extra = d->extra_flag;
 			if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) {
 				fprintf(stderr, "[bwamem_hip] paired reads have different names: \"%s\", \"%s\"\n", seqs[i].name, seqs[i + 1].name);
@@ -880,7 +728,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 			}
 			if (!(o->flag & BMH_MEM_F_NOPAIRING) && h[0].rid == h[1].rid && h[0].rid >= 0) { /* the two top hits make a proper pair? */
 				int64_t dist;
-				const int dd = infer_dir(l_pac, regs[i].a[0].rb, regs[i + 1].a[0].rb, &dist);
+				const int dd = bmh_pp_infer_dir(l_pac, regs[i].a[0].rb, regs[i + 1].a[0].rb, &dist);
 				if (!pes[dd].failed && dist >= pes[dd].low && dist <= pes[dd].high) extra |= 2;
 			}
 		}
@@ -915,7 +763,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 		fprintf(stderr, "[bwamem_hip] bmh_sam_batch %d reads, %zu alignments: marking + pairing %.1f ms, global alignments (bmh_reg2cigar_batch) %.1f ms, coordinates + text %.1f ms\n",
 		        n, W.n, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3);
 done:
-	free(W.a), free(pd), free(reads), free(reqs), free(res), free(cig), free(md), free(first), free(alns), free(arena), free(pv.a), free(pu.a),
-	    free(str.s);
+	free(W.a), free(pd), free(reads), free(reqs), free(res), free(cig), free(md), free(first), free(alns), free(arena), free(roff), free(reg_mapq),
+	    free(n_want), free(want_k), free(str.s);
 	return rc;
 }

@@ -573,6 +573,7 @@ typedef struct bmh_seq { /* == bseq1_t, bwa.h:19-22; seq holds base codes (after
 int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun);                       /* mem_sort_and_dedup; on the device: bmh_sort_dedup_batch */
 void bmh_mark_primary_se(const bmh_sam_opt_t *o, int n, bmh_alnreg_t *a, int64_t id);         /* mem_mark_primary_se */
 int bmh_approx_mapq_se(const bmh_sam_opt_t *o, const bmh_alnreg_t *a);                         /* mem_approx_mapq_se  */
+/* (the three above and bmh_pair below as one batch call, on the host or the device: bmh_decide_batch / bmh_decide_device) */
 /* mem_pestat; with verbose >= 3 it prints the reference's "[M::mem_pestat] ..." lines to stderr */
 void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, bmh_pestat_t pes[4], int verbose);
 /* mem_pair (bwamem_pair.c:177-238): the best-scoring properly oriented pair of hits of the two ends; returns its score
@@ -583,9 +584,53 @@ int bmh_pair(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], c
  * and 2p+1 are mates, pes = the four insert-size models, mate rescue already done or off), runs the global alignments
  * of exactly the regions that get printed as GPU batches, and writes seqs[i].sam (malloc'd, the caller frees it as
  * fastmap.c:201 does).  id0 = n_processed + index of read 0 (the reference's per-read id, bwamem.c:1287,1291).
- * rg_id: the reference's bwa_rg_id ("" = none).  regs[i].a is left sorted/marked as the reference leaves it. */
+ * rg_id: the reference's bwa_rg_id ("" = none).  regs[i].a is left sorted/marked as the reference leaves it.
+ * The decisions (everything before the global alignments) are bmh_decide_batch's, or with bmh_ctx_set_decide_device on
+ * bmh_decide_device's: the same text either way (below). */
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id);
+
+/* ---- Pass A of bmh_sam_batch on its own: what gets printed, and with which mapQ (mem_mark_primary_se, mem_pair, the tail of
+ * mem_sam_pe, the selection of mem_reg2sam_se, mem_approx_mapq_se of every region), for reads [0,n) of a chunk slice.  One text,
+ * host/postproc_core.h, compiled by gcc for the host call and by hipcc for the device call: both give the same bytes.
+ *   regs      regs[i] is read i's vector as phase 1 or mate rescue left it; on return sorted and marked as the reference leaves
+ *             it, with sub / secondary = -2 of a winning pair's hits
+ *   roff      n + 1 entries: roff[i] = regions before read i
+ *   pd        with BMH_MEM_F_PE in o->flag (n even, pes the four insert-size models): pd[p] is the verdict on reads 2p, 2p+1, whose
+ *             pair id is (id0>>1)+p and read ids id<<1|r.  score, sub, n_sub are mem_pair's (0 where it was not asked); q_pe is 0
+ *             where it is not computed; z[] and q_se[] mean something for paired != 0.  NULL (like pes) for single-end reads.
+ *   reg_mapq  reg_mapq[roff[i]+j] = mem_approx_mapq_se of region j of read i in its final state, for every region
+ *   n_want, want_k   want_k[roff[i] .. roff[i]+n_want[i]) are the indices of read i's regions that get printed, in the order
+ *             mem_reg2sam_se visits them; for a paired decision that is z[r] alone (or nothing, for a region off the reference)
+ * BMH_E_ARG: a NULL argument with n > 0, n < 0, odd n or no pes with PE, a vector with n > 0 and no array, roff that does not
+ * match the vectors.  n == 0: BMH_OK. */
+typedef struct bmh_pairdec { int32_t paired, z[2], q_se[2], extra_flag, score, sub, n_sub, q_pe, rsv[2]; } bmh_pairdec_t; /* 48 B */
+int bmh_decide_batch(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                     bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq,
+                     int32_t *n_want, int32_t *want_k);
+/* The same as a kernel (csrc/decide.hip), one lane per read or pair: one upload, decide_kernel, one download.  log and erfc do
+ * not run on the device: the host tabulates log(k) for k = 0..K (resident per context, grown on demand) and, per call, mem_pair's
+ * insert-size term for every distance of every orientation that has not failed.  Needs neither parameters nor a resident
+ * reference.  Refused on the host before anything is uploaded:
+ *   BMH_E_ARG    a NULL ctx, and what bmh_decide_batch refuses
+ *   BMH_E_RANGE  a table would pass 1 << 20 entries: the log table must reach max(qe-qb, re-rb) (mapQ_coef_len > 0) or seedcov
+ *                (otherwise) of every region, a vector's n + 1 (plus the sub_n it came with), a pair's (n0 + n1)^2 + 1; a negative
+ *                index is refused too; the pair table needs the sum of high - low + 1 over the orientations that have not failed
+ *                (not with BMH_MEM_F_NOPAIRING, which never pairs)
+ *   BMH_OK       without a launch for n == 0
+ * The caller's vectors and outputs are written only after the kernel has finished: all or nothing. */
+int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                      bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq,
+                      int32_t *n_want, int32_t *want_k);
+/* Per context, off by default.  While on, bmh_sam_batch takes its pass A from bmh_decide_device; a slice that call answers
+ * BMH_E_RANGE for goes through bmh_decide_batch instead.  The text is the same either way. */
+int bmh_ctx_set_decide_device(bmh_ctx_t *ctx, int on);
+/* Of the last bmh_decide_device call on this context, direct or from bmh_sam_batch with the switch on: the reads (single-end) or
+ * pairs the kernel decided, 1 if the call answered BMH_E_RANGE (bmh_sam_batch then fell back to the host) else 0, and the kernel's
+ * milliseconds with bmh_set_kernel_timing on (else -1).  -1, 0, -1 before the first such call.  With the switch on bmh_sam_batch
+ * sets them to 0, 0, -1 at its entry, so that after it they are that call's even where it returned before its decisions (n == 0, a
+ * refused argument).  Any pointer may be NULL. */
+int bmh_last_decide_stats(const bmh_ctx_t *ctx, int64_t *units, int64_t *fallbacks, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------------------
  * FM-index queries of the seeding stage (first slice): super-maximal exact matches and suffix-
