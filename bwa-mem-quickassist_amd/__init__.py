@@ -72,6 +72,10 @@ SAM_OPT = np.dtype([("a", "<i4"), ("b", "<i4"), ("o_del", "<i4"), ("e_del", "<i4
 MEM_F_PE, MEM_F_NOPAIRING, MEM_F_ALL = 0x2, 0x4, 0x8
 PAIRDEC = np.dtype([("paired", "<i4"), ("z", "<i4", (2,)), ("q_se", "<i4", (2,)), ("extra_flag", "<i4"), ("score", "<i4"), ("sub", "<i4"),
                     ("n_sub", "<i4"), ("q_pe", "<i4"), ("rsv", "<i4", (2,))])  # bmh_pairdec_t
+WANTED_RES = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("n_cigar", "<i4"), ("NM", "<i4"),
+                       ("tries", "<i4"), ("cigar_off", "<u4"), ("md_off", "<u4"), ("md_len", "<u4"), ("flags", "<u4"), ("band", "<i4", (3,)),
+                       ("rsv", "<i4")])  # bmh_wanted_res_t, 72 bytes
+WANTED_MOVED, WANTED_HOST = 4, 8
 ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
                    ("truesc", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"),
                    ("w", "<i4"), ("seedcov", "<i4"), ("secondary", "<i4"), ("hash", "<u8")])
@@ -97,6 +101,24 @@ class _AlnregV(C.Structure):
 
 class _Read(C.Structure):
     _fields_ = [("l_seq", C.c_int32), ("seq", C.c_void_p)]
+
+
+class _RefAnn(C.Structure):  # bmh_refann_t
+    _fields_ = [("offset", C.c_int64), ("len", C.c_int32), ("n_ambs", C.c_int32), ("gi", C.c_uint32), ("name", C.c_char_p), ("anno", C.c_char_p)]
+
+
+class _RefIdx(C.Structure):  # bmh_refidx_t
+    _fields_ = [("l_pac", C.c_int64), ("n_seqs", C.c_int32), ("seed", C.c_uint32), ("anns", C.POINTER(_RefAnn))]
+
+
+def make_refidx(contigs, l_pac=None):
+    """bmh_refidx_t over contigs = [(offset, len), ...] (names seq0, seq1, ...); l_pac defaults to the end of the last one."""
+    anns = (_RefAnn * max(len(contigs), 1))()
+    for i, (off, ln) in enumerate(contigs):
+        anns[i] = _RefAnn(int(off), int(ln), 0, 0, b"seq%d" % i, b"")
+    idx = _RefIdx(int(l_pac if l_pac is not None else contigs[-1][0] + contigs[-1][1]), len(contigs), 11, anns)
+    idx._keep = anns
+    return idx
 
 
 class _ChainStats(C.Structure):  # bmh_chain_stats_t
@@ -205,6 +227,11 @@ def lib():
         L.bmh_decide_device.argtypes = [C.c_void_p] + L.bmh_decide_batch.argtypes
         L.bmh_ctx_set_decide_device.argtypes = [C.c_void_p, C.c_int]
         L.bmh_last_decide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.bmh_wanted_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p, C.c_size_t]
+        L.bmh_wanted_cigar_device.argtypes = L.bmh_wanted_cigar_batch.argtypes
+        L.bmh_ctx_set_refidx.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_ctx_set_wanted_device.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_region_cigar_batch.restype = C.c_int
@@ -805,6 +832,55 @@ class Context:
         a, b, ms = C.c_int64(0), C.c_int64(0), C.c_float(0)
         self._check(lib().bmh_last_decide_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
         return a.value, b.value, ms.value
+
+    def set_refidx(self, refidx):
+        """bmh_ctx_set_refidx: (offset, len) of every reference sequence resident on the device; None drops it."""
+        self._check(lib().bmh_ctx_set_refidx(self._h, C.byref(refidx) if refidx is not None else None))
+
+    def set_wanted_device(self, on=True):
+        """bmh_ctx_set_wanted_device: while on, bmh_sam_batch takes its pass B from bmh_wanted_cigar_device."""
+        self._check(lib().bmh_ctx_set_wanted_device(self._h, 1 if on else 0))
+
+    def last_wanted_stats(self):
+        """(wanted regions, regions fixed, regions redone on the host, planning-kernel ms or -1) of the last bmh_wanted_cigar_device call."""
+        a, b, c, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
+        self._check(lib().bmh_last_wanted_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)))
+        return a.value, b.value, c.value, ms.value
+
+    def wanted_cigar_batch(self, refidx, pac, w, reads, vectors, want, device=False, out=None):
+        """bmh_wanted_cigar_batch (device=True: bmh_wanted_cigar_device): pass B of phase 2.  reads: uint8 code arrays; vectors: per read an
+        ALNREG array; want: per read the indices of its wanted regions.  Returns (WANTED_RES records, CIGAR pool, MD bytes); out: the three
+        arrays to write into (a test's sentinels)."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        n = len(reads)
+        keep = []
+        c_reads = (_Read * max(n, 1))()
+        c_regs = (_AlnregV * max(n, 1))()
+        for r, (seq, v) in enumerate(zip(reads, vectors)):
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            v = np.ascontiguousarray(v, dtype=ALNREG).reshape(-1)
+            keep += [seq, v]
+            c_reads[r].l_seq, c_reads[r].seq = len(seq), seq.ctypes.data
+            c_regs[r].n = c_regs[r].m = len(v)
+            c_regs[r].a = v.ctypes.data if len(v) else None
+        roff = np.concatenate([[0], np.cumsum([len(v) for v in vectors])]).astype(np.int64)
+        n_want = np.array([len(x) for x in want], dtype=np.int32).reshape(-1)
+        want_k = np.full(int(roff[-1]) + 1, -1, dtype=np.int32)
+        span = 0
+        for i, ks in enumerate(want):
+            want_k[int(roff[i]):int(roff[i]) + len(ks)] = ks
+            for k in ks:
+                if 0 <= k < len(vectors[i]):
+                    a = vectors[i][k]
+                    span += max(int(a["qe"]) - int(a["qb"]), 0) + max(int(a["re"]) - int(a["rb"]), 0)
+        n_w = int(n_want.sum())
+        if out is None:
+            out = (np.zeros(n_w, dtype=WANTED_RES), np.zeros(span + 2 * n_w + 8, dtype=np.uint32), np.zeros(3 * span + 16 * n_w + 16, dtype=np.uint8))
+        res, cig, md = out
+        fn = lib().bmh_wanted_cigar_device if device else lib().bmh_wanted_cigar_batch
+        self._check(fn(self._h, C.byref(refidx), _ptr(pac), int(w), n, C.cast(c_reads, C.c_void_p), C.cast(c_regs, C.c_void_p), _ptr(roff),
+                       _ptr(n_want), _ptr(want_k), _ptr(res), _ptr(cig), C.c_size_t(len(cig)), _ptr(md), C.c_size_t(len(md))))
+        return res, cig, md
 
     def reg2cigar_batch(self, l_pac, pac, reads, reqs):
         """Batched mem_reg2aln band/retry loop over bwa_gen_cigar2 (reference bwamem.c:1187-1201, bwa.c:89-172).

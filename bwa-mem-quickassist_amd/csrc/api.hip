@@ -12,6 +12,7 @@
 
 #include "bmh_ctx.h"
 #include "decide.h"
+#include "wanted.h"
 
 namespace bmh {
 
@@ -301,6 +302,10 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
 	free_buf(ctx->d_swl), free_buf(ctx->d_dedup), free_buf(ctx->d_msw), free_buf(ctx->d_decide), free_buf(ctx->d_logk);
 	free(ctx->h_logk);
+	free_buf(ctx->d_refidx), free_buf(ctx->d_wanted);
+	if (ctx->h_wstat) (void)hipHostFree(ctx->h_wstat);
+	for (auto &e : ctx->ev_wanted)
+		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_decide)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_chain)
@@ -1411,6 +1416,7 @@ int bmh_last_decide_stats(const bmh_ctx_t *ctx, int64_t *units, int64_t *fallbac
 __attribute__((visibility("hidden"))) void bmh_decide_stats_reset_(bmh_ctx_t *ctx)
 {
 	if (ctx && ctx->decide_device) ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+	if (ctx && ctx->wanted_device) ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
 }
 
 // bmh_sam_batch's pass A (host/sam_post.c; not part of the interface)
@@ -1425,6 +1431,324 @@ __attribute__((visibility("hidden"))) int bmh_decide_routed_(bmh_ctx_t *ctx, con
 		if (rc != BMH_E_RANGE) return rc;
 	}
 	return bmh_decide_batch(o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k);
+}
+
+// ------------------------------------------------------------------ pass B of phase 2 planned on the device (wanted.hip)
+
+// the host form and its helpers (host/sam_post.c; not part of the interface)
+int bmh_wanted_host_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                     const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t n_w, int bands, bmh_wanted_res_t *wr, uint32_t **cig,
+                     char **md, int64_t *n_fixed);
+int bmh_wanted_deliver_(int64_t n_w, const bmh_wanted_res_t *wr, const uint32_t *cig, const char *md, bmh_wanted_res_t *results, uint32_t *cigar_pool,
+                        size_t cigar_words, char *md_pool, size_t md_bytes);
+int bmh_wanted_check_args_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                           const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t *n_w);
+
+int bmh_ctx_set_refidx(bmh_ctx_t *ctx, const bmh_refidx_t *bns)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (!bns) {
+		ctx->refidx_n = 0, ctx->refidx_l_pac = 0, ctx->h_refidx.clear();
+		return BMH_OK;
+	}
+	if (bns->n_seqs <= 0 || !bns->anns || bns->l_pac <= 0) return BMH_E_ARG;
+	std::vector<bmh_refspan_t> t((size_t)bns->n_seqs);
+	for (int i = 0; i < bns->n_seqs; ++i) t[(size_t)i] = bmh_refspan_t{bns->anns[i].offset, bns->anns[i].len, 0};
+	if (ctx->refidx_n == bns->n_seqs && ctx->refidx_l_pac == bns->l_pac && ctx->h_refidx.size() == t.size() &&
+	    memcmp(ctx->h_refidx.data(), t.data(), t.size() * sizeof(bmh_refspan_t)) == 0)
+		return BMH_OK; // already resident: the same records (16 bytes per sequence to compare, per slice)
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream)); // (nothing in flight reads the table while it is replaced)
+	ctx->refidx_n = 0, ctx->h_refidx.clear();
+	int rc;
+	if ((rc = ensure(ctx, ctx->d_refidx, t.size() * sizeof(bmh_refspan_t)))) return rc;
+	BMH_HIP(ctx, hipMemcpy(ctx->d_refidx.p, t.data(), t.size() * sizeof(bmh_refspan_t), hipMemcpyHostToDevice));
+	ctx->refidx_n = bns->n_seqs, ctx->refidx_l_pac = bns->l_pac, ctx->h_refidx = std::move(t);
+	return BMH_OK;
+}
+
+// bytes of MD coming back per region (BMH_RP_MD_SLOT, host/regplan_core.h); round 0's MD is not read
+enum { kWantMdSlot = BMH_RP_MD_SLOT, kWantFixMdSlot = 4 };
+
+// the device form up to its own records and pools (*cig_ / *md_: malloc'd, the caller frees them), for the public call and bmh_sam_batch
+static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                             const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t n_w, bmh_wanted_res_t *wr, uint32_t **cig_, char **md_)
+{
+	*cig_ = nullptr, *md_ = nullptr;
+	ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
+	if (!ctx->have_params) return BMH_E_ARG;
+	if (!ctx->dev.pac || ctx->h_pac != pac || ctx->dev.l_pac != bns->l_pac) {
+		ctx->last_error = "bmh_wanted_cigar_device needs the resident reference (bmh_ctx_set_pac)";
+		return BMH_E_ARG;
+	}
+	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
+		ctx->last_error = "bmh_wanted_cigar_device needs the resident sequence table (bmh_ctx_set_refidx)";
+		return BMH_E_ARG;
+	}
+	if (n_w == 0) return BMH_OK;
+	if (n_w > (1 << 28) || n > (1 << 28)) return BMH_E_ARG;
+	const int64_t l_pac = bns->l_pac;
+	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = (size_t)n_w;
+	// every buffer the kernels write, sized before the first launch: the oriented pool from the lengths a region the kernels accept can have
+	size_t reads_bytes = 0, opool_cap = 0;
+	for (int i = 0; i < n; ++i) {
+		reads_bytes += (size_t)reads[i].l_seq;
+		for (int q = 0; q < n_want[i]; ++q) {
+			const int k = want_k[roff[i] + q];
+			if (k < 0 || (size_t)k >= regs[i].n) continue; // (the kernel refuses it)
+			const bmh_alnreg_t *a = &regs[i].a[k];
+			opool_cap += (size_t)std::clamp<int64_t>((int64_t)a->qe - a->qb, 0, 65535) + (size_t)std::clamp<int64_t>(a->re - a->rb, 0, 65535);
+		}
+	}
+	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+	// the device block: [offsets | read offsets | parameters | n_want | want_k | regions] up, then work arrays, then what comes down
+	const size_t o_soff = al((nr + 1) * 8), o_hdr = o_soff + al((nr + 1) * 8), o_nw = o_hdr + al(sizeof(WantedHdr)), o_wk = o_nw + al(nr * 4);
+	const size_t o_reg = o_wk + al(total * 4), b_up = o_reg + al(total * sizeof(bmh_alnreg_t));
+	size_t at = b_up;
+	auto take = [&](size_t bytes) {
+		const size_t o = at;
+		at += al(bytes);
+		return o;
+	};
+	const size_t o_first = take((nr + 1) * 8), o_rec = take(wc * sizeof(WantRec));
+	size_t o_key[4], o_sum[4];
+	for (int c = 0; c < 4; ++c) o_key[c] = take(wc * 4);
+	for (int c = 0; c < 4; ++c) o_sum[c] = take(wc * 8);
+	const size_t o_req0 = take(wc * sizeof(bmh_region_req_t)), o_req1 = take(wc * sizeof(bmh_region_req_t)), o_stat = take(2 * sizeof(WantedStatus));
+	const size_t o_res0 = take(wc * sizeof(bmh_region_res_t)), o_cig0 = take(wc * BMH_RP_SMALL_CAP * 4), o_md0 = take(wc * kWantFixMdSlot);
+	const size_t o_res1 = take(wc * sizeof(bmh_region_res_t)), o_cig1 = take(wc * BMH_RP_SMALL_CAP * 4), o_md1 = take(wc * kWantMdSlot), o_end = at;
+	uint8_t *up = (uint8_t *)malloc(b_up), *rpool = (uint8_t *)malloc(reads_bytes + 16);
+	WantRec *rec = (WantRec *)malloc(wc * sizeof(WantRec));
+	uint8_t *down = (uint8_t *)malloc(o_end - o_res1);
+	struct Free {
+		void *a, *b, *c, *d;
+		~Free() { free(a), free(b), free(c), free(d); }
+	} guard{up, rpool, rec, down};
+	if (!up || !rpool || !rec || !down) {
+		ctx->last_error = "bmh_wanted_cigar_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	memcpy(up, roff, (nr + 1) * 8);
+	{
+		uint64_t *so = (uint64_t *)(up + o_soff);
+		size_t b = 0;
+		for (int i = 0; i < n; ++i) {
+			so[i] = b;
+			if (reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
+			b += (size_t)reads[i].l_seq;
+		}
+		so[n] = b;
+		memset(rpool + b, 0, 16);
+	}
+	WantedHdr *hdr = (WantedHdr *)(up + o_hdr);
+	const bmh_params_t &p = ctx->params;
+	hdr->opt = bmh_rp_opt_t{p.a, p.mat[0], p.o_del, p.e_del, p.o_ins, p.e_ins, p.w};
+	hdr->fix_w = w;
+	memcpy(up + o_nw, n_want, nr * 4);
+	for (int i = 0; i < n; ++i) {
+		if (n_want[i]) memcpy(up + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
+		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+	}
+	int64_t n_rec1 = 0, n_fix = 0;
+	int rc = BMH_OK;
+	{ // the device section, inside the caller's gate (the redo below enters it again through the host form)
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	if (!ctx->h_wstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_wstat, 2 * sizeof(WantedStatus), hipHostMallocDefault));
+	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
+	Stager st(ctx);
+	rc = [&]() -> int {
+		int e;
+		// device pool = [oriented copies | the reads as uploaded], as bmh_region_cigar_batch lays it out
+		const size_t rpool_off = (opool_cap + 16 + 63) & ~(size_t)63;
+		ctx->pool_resident = false;
+		if ((e = ensure(ctx, ctx->d_pool, rpool_off + reads_bytes + 16))) return e;
+		if ((e = ensure(ctx, ctx->d_tasks, 4 * wc * sizeof(bmh_glb_task_t))) || (e = ensure(ctx, ctx->d_res, 3 * wc * sizeof(bmh_glb_result_t)))) return e;
+		if ((e = ensure(ctx, ctx->d_cigar, (3 * wc * BMH_RP_SMALL_CAP + 4) * 4)) || (e = ensure(ctx, ctx->d_wanted, o_end))) return e;
+		if ((e = st.stage(b_up + reads_bytes + 256, wc * sizeof(WantRec) + (o_end - o_res1) + 256))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_wanted.p, *d_pool = (uint8_t *)ctx->d_pool.p;
+		BMH_HIP(ctx, hipMemsetAsync(d + o_stat, 0, 2 * sizeof(WantedStatus), ctx->stream));
+		if ((e = st.h2d(d, up, b_up)) || (e = st.h2d(d_pool + rpool_off, rpool, reads_bytes + 16))) return e;
+		WantedArgs A{};
+		A.roff = (const unsigned long long *)d, A.seq_off = (const unsigned long long *)(d + o_soff), A.hdr = (const WantedHdr *)(d + o_hdr);
+		A.n_want = (const int32_t *)(d + o_nw), A.want_k = (const int32_t *)(d + o_wk), A.reg = (const bmh_alnreg_t *)(d + o_reg);
+		A.total = total, A.reads_bytes = reads_bytes, A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.n_seqs = ctx->refidx_n, A.n = n, A.l_pac = l_pac;
+		A.first = (unsigned long long *)(d + o_first), A.rec = (WantRec *)(d + o_rec);
+		for (int c = 0; c < 4; ++c) A.key[c] = (uint32_t *)(d + o_key[c]), A.sum[c] = (unsigned long long *)(d + o_sum[c]);
+		A.req[0] = (bmh_region_req_t *)(d + o_req0), A.req[1] = (bmh_region_req_t *)(d + o_req1);
+		A.task[0] = (bmh_glb_task_t *)ctx->d_tasks.p, A.task[1] = A.task[0] + wc;
+		A.fix_res = (const bmh_region_res_t *)(d + o_res0), A.fix_cig = (const uint32_t *)(d + o_cig0);
+		A.status = (WantedStatus *)(d + o_stat), A.w_cap = wc, A.opool_cap = opool_cap, A.err = ctx->d_err;
+		// one round of the region kernels over what a status record describes
+		auto run_round = [&](int r, size_t o_res, size_t o_cig, size_t o_md, int md_cap) -> int {
+			const WantedStatus &s = hs[r];
+			int e2;
+			if (s.n_rec <= 0) return BMH_OK;
+			GlbLongShape lg;
+			lg.qmax = s.lqmax, lg.tmax = s.ltmax, lg.wmax = s.lwmax, lg.n = s.ln;
+			if ((e2 = launch_region_orient(ctx, d_pool, rpool_off, A.req[r], s.n_rec))) return e2;
+			if (s.n_tasks > 0 && (e2 = launch_global(ctx, d_pool, A.task[r], s.n_tasks, (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr,
+			                                         std::max(s.qmax, 1), std::max(s.tmax, 1), s.wmax, s.wraw, &lg)))
+				return e2;
+			return launch_region_finish(ctx, d_pool, A.req[r], s.n_rec, A.task[r], (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p,
+			                            (bmh_region_res_t *)(d + o_res), (uint32_t *)(d + o_cig), BMH_RP_SMALL_CAP, (char *)(d + o_md), md_cap);
+		};
+		// the status records: the only thing the host reads between launches
+		auto read_status = [&]() -> int {
+			BMH_HIP(ctx, hipMemcpyAsync(ctx->h_wstat, d + o_stat, 2 * sizeof(WantedStatus), hipMemcpyDeviceToHost, ctx->stream));
+			BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+			if (hs[0].err || hs[1].err) {
+				ctx->last_error = "bmh_wanted_cigar_device: a wanted region is outside its read, its vector or the reference, or nothing is left of it";
+				return hs[0].err ? hs[0].err : hs[1].err;
+			}
+			if (hs[0].n_w != n_w || hs[1].n_rec > n_w || hs[0].n_rec > n_w) { // cannot happen
+				ctx->last_error = "bmh_wanted_cigar_device: the device's counts are inconsistent";
+				return BMH_E_ARG;
+			}
+			return BMH_OK;
+		};
+		if ((e = launch_wanted_begin(ctx, A)) || (e = read_status())) return e;
+		if ((e = run_round(0, o_res0, o_cig0, o_md0, kWantFixMdSlot))) return e;
+		if ((e = launch_wanted_main(ctx, A)) || (e = read_status())) return e;
+		if ((e = run_round(1, o_res1, o_cig1, o_md1, kWantMdSlot))) return e;
+		n_rec1 = hs[1].n_rec;
+		if ((e = st.d2h(rec, d + o_rec, wc * sizeof(WantRec)))) return e;
+		return n_rec1 ? st.d2h(down, d + o_res1, o_end - o_res1) : BMH_OK;
+	}();
+	rc = st.end(rc);
+	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
+	if (rc) return rc;
+	n_fix = hs[0].n_rec;
+	if (ctx->timing && ctx->ev_wanted[3]) {
+		float a = 0.f, b = 0.f;
+		BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
+		BMH_HIP(ctx, hipEventElapsedTime(&b, ctx->ev_wanted[2], ctx->ev_wanted[3]));
+		ctx->wanted_ms = a + b;
+	}
+	}
+	// ---- the records: the device's, and the few regions whose alignments outgrew their slots again through the host form
+	const bmh_region_res_t *rr = (const bmh_region_res_t *)down;
+	const uint32_t *cout = (const uint32_t *)(down + (o_cig1 - o_res1));
+	const char *mout = (const char *)(down + (o_md1 - o_res1));
+	std::vector<int64_t> redo;
+	size_t cu = 0, mu = 0;
+	for (int64_t j = 0; j < n_w; ++j) {
+		const WantRec &x = rec[j];
+		const bool ok = x.state == kWantOk && x.v >= 0 && x.v < n_rec1 && x.read >= 0 && x.read < n && x.k >= 0 && (size_t)x.k < regs[x.read].n;
+		if (!ok && x.state != kWantHost) {
+			ctx->last_error = "bmh_wanted_cigar_device: the device's records are inconsistent";
+			return BMH_E_ARG;
+		}
+		if (x.state == kWantHost || rr[x.v].flags) redo.push_back(j);
+		else cu += (size_t)rr[x.v].n_cigar, mu += (size_t)rr[x.v].md_len + 1;
+	}
+	std::vector<bmh_wanted_res_t> hw(redo.size());
+	uint32_t *hcig = nullptr;
+	char *hmd = nullptr;
+	struct Free2 {
+		uint32_t *&a;
+		char *&b;
+		~Free2() { free(a), free(b); }
+	} guard2{hcig, hmd};
+	if (!redo.empty()) { // one region per read of a small slice of its own: the fix again for a region whose fix outgrew its slot
+		const size_t m = redo.size();
+		std::vector<bmh_alnreg_t> ra(m);
+		std::vector<bmh_alnreg_v> rv(m);
+		std::vector<bmh_read_t> rd(m);
+		std::vector<int64_t> ro(m + 1);
+		std::vector<int32_t> nw(m, 1), wk(m, 0);
+		for (size_t t = 0; t < m; ++t) {
+			const WantRec &x = rec[redo[t]];
+			ra[t] = regs[x.read].a[x.k];
+			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe; // (as cut; a region whose fix is redone still has its own)
+			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[x.read], ro[t] = (int64_t)t;
+		}
+		ro[m] = (int64_t)m;
+		if ((rc = bmh_wanted_host_(ctx, bns, pac, w, (int)m, rd.data(), rv.data(), ro.data(), nw.data(), wk.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr)))
+			return rc;
+		for (size_t t = 0; t < m; ++t) cu += (size_t)hw[t].n_cigar, mu += (size_t)hw[t].md_len + 1;
+	}
+	uint32_t *cig = (uint32_t *)malloc(4 * (cu + 4));
+	char *md = (char *)malloc(mu + 4);
+	if (!cig || !md) {
+		free(cig), free(md);
+		ctx->last_error = "bmh_wanted_cigar_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	cu = mu = 0;
+	size_t t = 0;
+	for (int64_t j = 0; j < n_w; ++j) {
+		const WantRec &x = rec[j];
+		bmh_wanted_res_t o{};
+		const uint32_t *sc;
+		const char *sm;
+		if (t < redo.size() && redo[t] == j) {
+			o = hw[t], sc = hcig + o.cigar_off, sm = hmd + o.md_off;
+			o.flags |= x.flags | BMH_WANTED_HOST;
+			++t;
+		} else {
+			const bmh_region_res_t &r = rr[x.v];
+			o.rb = x.rb, o.re = x.re, o.qb = x.qb, o.qe = x.qe, o.score = r.score, o.n_cigar = r.n_cigar, o.NM = r.NM, o.tries = r.tries;
+			o.md_len = (uint32_t)r.md_len, o.flags = x.flags, o.band[0] = x.band[0], o.band[1] = x.band[1], o.band[2] = x.band[2];
+			sc = cout + (size_t)x.v * BMH_RP_SMALL_CAP, sm = mout + (size_t)x.v * kWantMdSlot;
+		}
+		memcpy(cig + cu, sc, 4 * (size_t)o.n_cigar), memcpy(md + mu, sm, o.md_len), md[mu + o.md_len] = 0;
+		o.cigar_off = (uint32_t)cu, o.md_off = (uint32_t)mu;
+		cu += (size_t)o.n_cigar, mu += (size_t)o.md_len + 1;
+		wr[j] = o;
+	}
+	ctx->wanted_n = n_w, ctx->wanted_fixed = n_fix, ctx->wanted_redone = (long long)redo.size();
+	*cig_ = cig, *md_ = md;
+	return BMH_OK;
+}
+
+int bmh_wanted_cigar_device(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                            const int64_t *roff, const int32_t *n_want, const int32_t *want_k, bmh_wanted_res_t *results, uint32_t *cigar_pool,
+                            size_t cigar_words, char *md_pool, size_t md_bytes)
+{
+	int64_t n_w = 0;
+	int rc = bmh_wanted_check_args_(ctx, bns, pac, n, reads, regs, roff, n_want, want_k, &n_w);
+	if (rc) return rc;
+	if (n_w > 0 && (!results || !cigar_pool || !md_pool)) return BMH_E_ARG;
+	std::vector<bmh_wanted_res_t> wr((size_t)n_w);
+	uint32_t *cig = nullptr;
+	char *md = nullptr;
+	rc = wanted_device_run(ctx, bns, pac, w, n, reads, regs, roff, n_want, want_k, n_w, wr.data(), &cig, &md);
+	if (!rc && n_w > 0) rc = bmh_wanted_deliver_(n_w, wr.data(), cig, md, results, cigar_pool, cigar_words, md_pool, md_bytes);
+	free(cig), free(md);
+	return rc;
+}
+
+int bmh_ctx_set_wanted_device(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->wanted_device = on != 0;
+	return BMH_OK;
+}
+
+int bmh_last_wanted_stats(const bmh_ctx_t *ctx, int64_t *wanted, int64_t *fixed, int64_t *redone, float *kernel_ms)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (wanted) *wanted = ctx->wanted_n;
+	if (fixed) *fixed = ctx->wanted_fixed;
+	if (redone) *redone = ctx->wanted_redone;
+	if (kernel_ms) *kernel_ms = ctx->wanted_ms;
+	return BMH_OK;
+}
+
+// bmh_sam_batch's pass B (host/sam_post.c; not part of the interface)
+__attribute__((visibility("hidden"))) int bmh_wanted_routed_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads,
+                                                             const bmh_alnreg_v *regs, const int64_t *roff, const int32_t *n_want, const int32_t *want_k,
+                                                             int64_t n_w, bmh_wanted_res_t *wr, uint32_t **cig, char **md)
+{
+	if (ctx && ctx->wanted_device) {
+		int64_t chk = 0;
+		int rc = bmh_wanted_check_args_(ctx, bns, pac, n, reads, regs, roff, n_want, want_k, &chk);
+		if (rc || chk != n_w) return rc ? rc : BMH_E_ARG;
+		return wanted_device_run(ctx, bns, pac, w, n, reads, regs, roff, n_want, want_k, n_w, wr, cig, md);
+	}
+	return bmh_wanted_host_(ctx, bns, pac, w, n, reads, regs, roff, n_want, want_k, n_w, 0, wr, cig, md, nullptr);
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 #include "../../include/bwamem_hip.h"
 #include "bmh_device.h"
+#include "../host/regplan_core.h"
 
 constexpr int kExtBinsMax = 6;
 
@@ -126,6 +128,17 @@ struct bmh_ctx {
 	hipEvent_t ev_decide[2] = {};             // around the kernel (timing mode)
 	long long decide_units = -1, decide_fallbacks = 0; // of the last bmh_decide_device call (bmh_last_decide_stats)
 	float decide_ms = -1.f;
+	// pass B's planning on the device (wanted.hip): bmh_wanted_cigar_device, and bmh_sam_batch with the switch on
+	bool wanted_device = false;               // bmh_ctx_set_wanted_device
+	DevBuf d_refidx;                          // (offset, len) of every reference sequence, resident (bmh_ctx_set_refidx)
+	int refidx_n = 0;                         // its records, 0 = none
+	std::vector<bmh_refspan_t> h_refidx;      // the host's copy of it: a table with the same records is not uploaded again
+	long long refidx_l_pac = 0;               // bns->l_pac it was set with
+	DevBuf d_wanted;                          // a call's block: offsets, parameters, want list, regions, records, keys, sums, status, results
+	void *h_wstat = nullptr;                  // pinned: the two status records as the host reads them between launches
+	hipEvent_t ev_wanted[4] = {};             // around the two groups of planning kernels (timing mode)
+	long long wanted_n = -1, wanted_fixed = -1, wanted_redone = -1; // of the last bmh_wanted_cigar_device call (bmh_last_wanted_stats)
+	float wanted_ms = -1.f;
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 

@@ -25,6 +25,9 @@
  *   BMH_DECIDE_DEVICE=1  its pass A -- primary marking, pairing, mapQ, the list of regions that get printed -- as a kernel
  *                        (bmh_ctx_set_decide_device); a slice the device call refuses as out of range is decided on the host.
  *                        Independent of the other switches; needs no resident reference.
+ *   BMH_WANTED_DEVICE=1  its pass B's planning -- the bwa_fix_xref2 test and cut, bands, region records and tasks of the regions that
+ *                        get printed -- as kernels (bmh_ctx_set_wanted_device).  Needs BMH_PAC_RESIDENT not 0; independent of the
+ *                        other switches.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -407,6 +410,28 @@ static int qa_decide_device(void)
 }
 static long long g_decide_cnt[2]; /* reads or pairs decided on the device, slices that fell back to the host */
 
+/* BMH_WANTED_DEVICE=1: phase 2's pass B planned on the device (bmh_ctx_set_wanted_device on every pooled context phase 2 uses,
+ * with the sequence table made resident where the reference is).  It aligns against the resident reference, so BMH_PAC_RESIDENT=0
+ * contradicts it: checked when the library is loaded, like BMH_MATESW_DEVICE. */
+__attribute__((constructor)) static void qa_check_wanted_device_env(void)
+{
+	const char *e = getenv("BMH_WANTED_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_WANTED_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+static int qa_wanted_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_WANTED_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_wanted_cnt[3]; /* regions planned on the device, fixed, redone on the host */
+
 /* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
 static int qa_regs_device(void)
 {
@@ -655,6 +680,11 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 	int rc;
 	if (J->resident && (rc = bmh_ctx_set_pac(ctx, J->pac, J->bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
 	if ((rc = bmh_ctx_set_decide_device(ctx, qa_decide_device()))) bmh_tls_die(bmh_last_error(ctx), rc); /* per pooled context */
+	if (qa_wanted_device()) { /* the sequence table where the reference is made resident; both stay */
+		if (!J->resident) bmh_tls_die("BMH_WANTED_DEVICE=1 needs the reference resident on the device", BMH_E_ARG);
+		if ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns))) bmh_tls_die(bmh_last_error(ctx), rc);
+	}
+	if ((rc = bmh_ctx_set_wanted_device(ctx, qa_wanted_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	return ctx;
 }
 
@@ -714,6 +744,12 @@ static void qa_sam_slice(void *data, int k, int tid)
 		int64_t du = 0, df = 0;
 		bmh_last_decide_stats(ctx, &du, &df, 0);
 		__sync_fetch_and_add(&g_decide_cnt[0], (long long)(du > 0 ? du : 0)), __sync_fetch_and_add(&g_decide_cnt[1], (long long)df);
+	}
+	if (qa_wanted_device()) {
+		int64_t ww = 0, wf = 0, wr = 0;
+		bmh_last_wanted_stats(ctx, &ww, &wf, &wr, 0);
+		__sync_fetch_and_add(&g_wanted_cnt[0], (long long)(ww > 0 ? ww : 0)), __sync_fetch_and_add(&g_wanted_cnt[1], (long long)(wf > 0 ? wf : 0));
+		__sync_fetch_and_add(&g_wanted_cnt[2], (long long)(wr > 0 ? wr : 0));
 	}
 	bmh_pool_put(ctx);
 	t2 = stage_now();
@@ -838,6 +874,9 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
 		if (qa_decide_device())
 			fprintf(stderr, "[bwamem_hip] phase 2 decisions on the device: %lld units, %lld host fall-backs\n", g_decide_cnt[0], g_decide_cnt[1]);
+		if (qa_wanted_device())
+			fprintf(stderr, "[bwamem_hip] phase 2 alignments planned on the device: %lld regions, %lld fixed, %lld redone on the host\n",
+			        g_wanted_cnt[0], g_wanted_cnt[1], g_wanted_cnt[2]);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());
 			fprintf(stderr, "[bwamem_hip] wide Smith-Waterman so far: %lld ksw_align2 tasks on the long-query kernel\n", bmh_pool_swl_tasks());

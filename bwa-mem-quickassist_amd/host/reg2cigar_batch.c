@@ -26,6 +26,7 @@
 #include <time.h>
 
 #include "../../include/bwamem_hip.h"
+#include "regplan_core.h"
 
 const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx);
 int bmh_upload_pool(bmh_ctx_t *ctx, const uint8_t *pool, size_t bytes);
@@ -66,7 +67,7 @@ static void pac_codes(const uint8_t *pac, int64_t beg, int64_t end, int comp, ui
 	for (; x < end; ++x) *dst++ = (uint8_t)(lut[pac[x >> 2]] >> ((x & 3) << 3));
 }
 
-enum { SMALL_CAP = 24 }; /* CIGAR slots reserved per task on the first attempt of a try */
+enum { SMALL_CAP = BMH_RP_SMALL_CAP }; /* CIGAR slots reserved per task on the first attempt of a try */
 
 static void put_num(char *s, size_t *l, int c) /* kputw, kstring.h:62-77, c >= 0 */
 {
@@ -117,13 +118,12 @@ static int nm_md(int n_cigar, const uint32_t *cigar, const uint8_t *q, const uin
 	return mismatches + gap_bases;
 }
 
-static int infer_bw(int l1, int l2, int score, int a, int q, int r) /* bwamem.c:884-891 */
+/* the scoring fields the bands read (regplan_core.h holds infer_bw, the first band and the band of a try) */
+static bmh_rp_opt_t rp_opt(const bmh_params_t *p)
 {
-	int w;
-	if (l1 == l2 && l1 * a - score < (q + r - a) << 1) return 0;
-	w = (int)((double)((l1 < l2 ? l1 : l2) * a - score - q) / r + 2.);
-	if (w < abs(l1 - l2)) w = abs(l1 - l2);
-	return w;
+	bmh_rp_opt_t o;
+	o.a = p->a, o.mat0 = p->mat[0], o.o_del = p->o_del, o.e_del = p->e_del, o.o_ins = p->o_ins, o.e_ins = p->e_ins, o.w = p->w;
+	return o;
 }
 
 typedef struct {
@@ -134,30 +134,6 @@ typedef struct {
 	int64_t final_task; /* ... and the one whose result the loop ends on */
 	const uint32_t *cig; /* the final try's CIGAR words (in one of the scratch arrays); NULL = the no-DP case, one M run */
 } cg_t;
-
-/* band of try t_ of a region whose inferred band is w2 (bwa.c:116-125) */
-static int try_band(const bmh_params_t *p, int ql, int tl, int w2)
-{
-	const int max_ins = (int)((double)(((ql + 1) >> 1) * p->mat[0] - p->o_ins) / p->e_ins + 1.);
-	const int max_del = (int)((double)(((ql + 1) >> 1) * p->mat[0] - p->o_del) / p->e_del + 1.);
-	int max_gap = max_ins > max_del ? max_ins : max_del, w, min_w;
-	max_gap = max_gap > 1 ? max_gap : 1;
-	w = (max_gap + abs(tl - ql) + 1) >> 1;
-	w = w < w2 ? w : w2;
-	min_w = abs(tl - ql) + 3;
-	return w > min_w ? w : min_w;
-}
-
-/* the band mem_reg2aln starts with (bwamem.c:1187-1191), or reg_w for bwa_fix_xref2's single call (bwa.c:198) */
-static int first_band(const bmh_params_t *p, const bmh_cigar_req_t *r, int ql, int tl)
-{
-	const int tmp = infer_bw(ql, tl, r->truesc, p->a, p->o_del, p->e_del);
-	int w2 = infer_bw(ql, tl, r->truesc, p->a, p->o_ins, p->e_ins);
-	w2 = w2 > tmp ? w2 : tmp;
-	if (w2 > p->w) w2 = w2 < r->reg_w ? w2 : r->reg_w;
-	if (r->truesc == INT32_MIN) w2 = r->reg_w;
-	return w2;
-}
 
 /* ---- the path with oriented copies made on the host.  Packs its CIGARs and MD strings from *cig_used_ / *md_used_ on. */
 static int reg2cigar_host_copies(bmh_ctx_t *ctx, const bmh_params_t *p, int64_t l_pac, const uint8_t *pac, const bmh_read_t *reads,
@@ -172,6 +148,7 @@ static int reg2cigar_host_copies(bmh_ctx_t *ctx, const bmh_params_t *p, int64_t 
 	int64_t *owner = 0, k, task_cap = 0;
 	size_t pool_bytes = 0, cig_used = *cig_used_, md_used = *md_used_;
 	int rc = BMH_OK;
+	const bmh_rp_opt_t po = rp_opt(p);
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0; /* where a call's time goes, on stderr */
 	double tt[4] = {0, 0, 0, 0}, t0 = 0;
 
@@ -224,7 +201,7 @@ static int reg2cigar_host_copies(bmh_ctx_t *ctx, const bmh_params_t *p, int64_t 
 			for (i = 0; i < c->ql; ++i) q[i] = rq[c->ql - 1 - i];
 			pac_codes(pac, lo + 1, lo + 1 + c->tl, 1, t);
 		}
-		c->w2 = first_band(p, r, c->ql, c->tl);
+		c->w2 = bmh_rp_first_band(&po, c->ql, c->tl, r->truesc, r->reg_w);
 		c->last_sc = -(1 << 30), c->active = 1;
 	}
 	memset(pool + pool_bytes, 0, 16);
@@ -252,11 +229,11 @@ static int reg2cigar_host_copies(bmh_ctx_t *ctx, const bmh_params_t *p, int64_t 
 				continue;
 			}
 			for (t_ = 0; t_ < (single ? 1 : 3); ++t_) { /* band of this try, bwa.c:116-125 */
-				const int w2 = c->w2 << t_;
+				const int w2 = bmh_rp_widen(c->w2, t_);
 				int w;
 				bmh_glb_task_t *t;
 				if (c->ql == c->tl && w2 == 0) break;
-				w = try_band(p, c->ql, c->tl, w2);
+				w = bmh_rp_try_band(&po, c->ql, c->tl, w2);
 				if (w == prev_w) { c->tidx[t_] = c->tidx[t_ - 1]; continue; }
 				prev_w = w;
 				if (n_tasks == task_cap) {
@@ -375,6 +352,7 @@ static int reg2cigar_region_records(bmh_ctx_t *ctx, const bmh_params_t *p, int64
 	int64_t k, v, n_v = 0, n_tasks = 0, task_cap, n_redo = 0;
 	size_t rbytes = 0, obytes = 0, slot = 0, cig_used = 0, md_used = 0;
 	int rc = BMH_OK;
+	const bmh_rp_opt_t po = rp_opt(p);
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0;
 	double tt[4] = {0, 0, 0, 0};
 
@@ -387,38 +365,23 @@ static int reg2cigar_region_records(bmh_ctx_t *ctx, const bmh_params_t *p, int64
 	if (!rq || !rr || !of || !tasks) { rc = BMH_E_NOMEM; goto done; }
 	for (k = 0; k < n_req; ++k) { /* records, pool layout, bands, tasks: arithmetic on coordinates only */
 		const bmh_cigar_req_t *r = &reqs[k];
-		const int ql = r->qe - r->qb, single = r->truesc == INT32_MIN;
+		const int ql = r->qe - r->qb;
 		const int64_t tl = r->re - r->rb;
-		bmh_region_req_t *q;
-		int t_, w2, prev_w = -1;
+		bmh_rp_plan_t pl;
 		memset(&res[k], 0, sizeof(res[k]));
 		res[k].NM = -1;
 		if (ql <= 0 || r->rb >= r->re || (r->rb < l_pac && r->re > l_pac) || r->rb < 0 || r->re > l_pac << 1) continue; /* bwa.c:99-101 */
 		if (ql > 65535 || tl > 65535) { rc = BMH_E_RANGE; goto done; }
-		q = &rq[n_v];
-		of[n_v++] = k;
-		q->q_src = rbytes, rbytes += (size_t)ql;
-		q->o_off = obytes, obytes += (size_t)ql + (size_t)tl;
-		q->rb = r->rb, q->ql = ql, q->tl = (int)tl, q->truesc = r->truesc;
-		q->task[0] = q->task[1] = q->task[2] = -1;
-		w2 = first_band(p, r, ql, (int)tl);
-		if (ql == tl && w2 == 0) continue; /* the no-gap case: bwa.c:108-114 */
-		for (t_ = 0; t_ < (single ? 1 : 3); ++t_) {
-			const int w = try_band(p, ql, (int)tl, w2 << t_);
-			bmh_glb_task_t *t;
-			if (w == prev_w) { q->task[t_] = q->task[t_ - 1]; continue; } /* the band saturates: the same alignment */
-			prev_w = w;
-			if (n_tasks == task_cap) {
-				task_cap = task_cap + task_cap / 2 + 1024;
-				tasks = (bmh_glb_task_t *)realloc(tasks, sizeof(*tasks) * (size_t)task_cap);
-				if (!tasks) { rc = BMH_E_NOMEM; goto done; }
-			}
-			t = &tasks[n_tasks];
-			t->q_off = q->o_off, t->t_off = q->o_off + (uint64_t)ql, t->qlen = (uint16_t)ql, t->tlen = (uint16_t)tl, t->w = w;
-			t->cigar_off = (uint32_t)slot, t->cigar_cap = (uint32_t)(ql + (int)tl + 2 < SMALL_CAP ? ql + (int)tl + 2 : SMALL_CAP);
-			slot += t->cigar_cap;
-			q->task[t_] = (int32_t)n_tasks++;
+		bmh_rp_plan(&po, ql, (int)tl, r->truesc, r->reg_w, &pl); /* bands, the no-gap case, equal bands sharing a task */
+		if (n_tasks + 3 > task_cap) {
+			task_cap = task_cap + task_cap / 2 + 1024;
+			tasks = (bmh_glb_task_t *)realloc(tasks, sizeof(*tasks) * (size_t)task_cap);
+			if (!tasks) { rc = BMH_E_NOMEM; goto done; }
 		}
+		of[n_v] = k;
+		bmh_rp_emit(&pl, rbytes, r->rb, obytes, ql, (int)tl, r->truesc, n_tasks, slot, &rq[n_v++], tasks + n_tasks);
+		rbytes += (size_t)ql, obytes += (size_t)ql + (size_t)tl;
+		n_tasks += pl.n_tasks, slot += (size_t)pl.n_tasks * pl.cap;
 	}
 	rpool = (uint8_t *)malloc(rbytes + 16);
 	cout = (uint32_t *)malloc(4 * ((size_t)n_v * SMALL_CAP + 4));

@@ -29,6 +29,7 @@
 #include "../../include/bwamem_hip.h"
 #include "dedup_core.h"
 #include "postproc_core.h"
+#include "regplan_core.h"
 #include "sort_exact.h"
 
 static double now_s(void) /* the clock of the BMH_DRIVER_TRACE lines: wall time, or with BMH_TRACE_CPU this thread's CPU time */
@@ -447,28 +448,15 @@ static void aln2sam(const bmh_refidx_t *bns, str_t *str, const bmh_seq_t *s, int
 
 /* ---- bntseq.h:83-86, bntseq.c:316-330 */
 static inline int64_t depos(int64_t l_pac, int64_t pos, int *is_rev) { return (*is_rev = pos >= l_pac) ? (l_pac << 1) - 1 - pos : pos; }
-static int pos2rid(const bmh_refidx_t *bns, int64_t pos_f)
+static bmh_rp_refv_t refv_of(const bmh_refidx_t *bns) /* the reference sequences as regplan_core.h walks them */
 {
-	int left = 0, mid = 0, right = bns->n_seqs;
-	if (pos_f >= bns->l_pac) return -1;
-	while (left < right) {
-		mid = (left + right) >> 1;
-		if (pos_f >= bns->anns[mid].offset) {
-			if (mid == bns->n_seqs - 1) break;
-			if (pos_f < bns->anns[mid + 1].offset) break;
-			left = mid + 1;
-		} else right = mid;
-	}
-	return mid;
+	bmh_rp_refv_t v;
+	v.off0 = bns->anns ? &bns->anns[0].offset : 0, v.len0 = bns->anns ? &bns->anns[0].len : 0, v.stride = sizeof(bmh_refann_t);
+	v.n_seqs = bns->n_seqs, v.l_pac = bns->l_pac;
+	return v;
 }
 
-typedef struct { /* one region that gets an alignment */
-	int read, k;      /* read of the slice, region index in its (sorted) vector */
-	int qb, qe;       /* after bwa_fix_xref2 */
-	int64_t rb, re;
-	int fix;          /* hangs over the end of its reference sequence: index into the fix batch, else -1 */
-	int64_t cb, ce;   /* ... and the interval it has to be cut to */
-} want_t;
+const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx);
 
 static void unmapped(aln_t *a) /* mem_reg2aln(..., 0), bwamem.c:1171-1175 */
 {
@@ -476,21 +464,199 @@ static void unmapped(aln_t *a) /* mem_reg2aln(..., 0), bwamem.c:1171-1175 */
 	a->rid = -1, a->pos = -1, a->flag |= 0x4;
 }
 
-typedef struct {
-	want_t *a;
-	size_t n, m;
-} want_v;
-static int want_push(want_v *w, int read, int k, const bmh_alnreg_t *ar)
+/* ================================================================================================ pass B: the alignments
+ * bwa_fix_xref2 (bwa.c:179-222) for the few regions that hang over the end of a reference sequence (one bwa_gen_cigar2 each), then
+ * mem_reg2aln's band loop (bwamem.c:1187-1201) for every wanted region, as GPU batches through bmh_reg2cigar_batch.  Everything that
+ * needs no sequence byte is regplan_core.h's, shared with the planning kernels of bmh_wanted_cigar_device (csrc/wanted.hip). */
+
+enum { MD_SLOT_ = BMH_RP_MD_SLOT };
+
+/* what both forms refuse before anything runs (host only) */
+static int wanted_check_args(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                             const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t *n_w)
 {
-	want_t *x;
-	if (w->n == w->m) {
-		w->m = w->m ? w->m << 1 : 1024;
-		w->a = (want_t *)realloc(w->a, sizeof(want_t) * w->m);
-		if (!w->a) return BMH_E_NOMEM;
+	int64_t at = 0, w = 0;
+	int i;
+	*n_w = 0;
+	if (!ctx || !bns || !pac || n < 0 || bns->l_pac <= 0 || bns->n_seqs <= 0 || !bns->anns) return BMH_E_ARG;
+	if (n > 0 && (!reads || !regs || !roff || !n_want || !want_k)) return BMH_E_ARG;
+	for (i = 0; i < n; ++i) {
+		if ((regs[i].n && !regs[i].a) || regs[i].n > 0x7fffffffu || roff[i] != at) return BMH_E_ARG;
+		if (n_want[i] < 0 || (size_t)n_want[i] > regs[i].n) return BMH_E_ARG;
+		if (reads[i].l_seq < 0 || (reads[i].l_seq > 0 && !reads[i].seq)) return BMH_E_ARG;
+		at += (int64_t)regs[i].n, w += n_want[i];
 	}
-	x = &w->a[w->n++];
-	x->read = read, x->k = k, x->qb = ar->qb, x->qe = ar->qe, x->rb = ar->rb, x->re = ar->re, x->fix = -1;
+	if (n > 0 && roff[n] != at) return BMH_E_ARG;
+	*n_w = w;
+	return BMH_OK;
+}
+
+/* a wanted region as the planning sees it: BMH_E_ARG / BMH_E_RANGE as the kernel gives them, else 0 */
+static int wanted_check_region(int64_t l_pac, int l_seq, const bmh_alnreg_t *a)
+{
+	if (!(0 <= a->qb && a->qb < a->qe && a->qe <= l_seq)) return BMH_E_ARG;
+	if (!(a->rb >= 0 && a->rb < a->re && a->re <= l_pac << 1)) return BMH_E_ARG;
+	if (a->rb < l_pac && a->re > l_pac) return BMH_E_ARG; /* bridges the strands: the reference gives up on the run (bwamem.c:1183-1186) */
+	if (a->qe - a->qb > 65535 || a->re - a->rb > 65535) return BMH_E_RANGE;
 	return 0;
+}
+
+/* The host form.  wr[0..n_w) in want order (n_w = sum of n_want); cigar_off / md_off address *cig_ / *md_, malloc'd here (the
+ * caller frees them), in bmh_reg2cigar_batch's packing.  bands: fill band[] (the public call; bmh_sam_batch has no use for it). */
+__attribute__((visibility("hidden"))) int bmh_wanted_host_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads,
+                                                           const bmh_alnreg_v *regs, const int64_t *roff, const int32_t *n_want, const int32_t *want_k,
+                                                           int64_t n_w, int bands, bmh_wanted_res_t *wr, uint32_t **cig_, char **md_, int64_t *n_fixed)
+{
+	const int64_t l_pac = bns->l_pac;
+	const bmh_rp_refv_t rv = refv_of(bns);
+	const bmh_params_t *p = bmh_ctx_params_(ctx);
+	bmh_cigar_req_t *reqs = 0, *fq = 0;
+	bmh_cigar_res_t *res = 0, *fr = 0;
+	int64_t *cbe = 0; /* cb, ce of fix f */
+	uint32_t *cig = 0, *fc = 0;
+	char *md = 0, *fmd = 0;
+	size_t j, n_fix = 0, cw = 8, mb = 16, fw = 8, fm_ = 16;
+	int i, q, rc = BMH_OK;
+
+	*cig_ = 0, *md_ = 0;
+	if (n_fixed) *n_fixed = 0;
+	if (!p) return BMH_E_ARG;
+	if (n_w == 0) return BMH_OK;
+	reqs = (bmh_cigar_req_t *)malloc(sizeof(*reqs) * (size_t)n_w);
+	res = (bmh_cigar_res_t *)malloc(sizeof(*res) * (size_t)n_w);
+	if (!reqs || !res) { rc = BMH_E_NOMEM; goto done; }
+	for (i = 0, j = 0; i < n; ++i) /* the want list as requests; the bwa_fix_xref2 test (bwa.c:184-197) */
+		for (q = 0; q < n_want[i]; ++q, ++j) {
+			const int k = want_k[roff[i] + q];
+			const bmh_alnreg_t *ar;
+			bmh_wanted_res_t *x = &wr[j];
+			int64_t cb, ce;
+			if (k < 0 || (size_t)k >= regs[i].n) { rc = BMH_E_ARG; goto done; }
+			ar = &regs[i].a[k];
+			if ((rc = wanted_check_region(l_pac, reads[i].l_seq, ar))) goto done;
+			memset(x, 0, sizeof(*x));
+			x->rb = ar->rb, x->re = ar->re, x->qb = ar->qb, x->qe = ar->qe;
+			x->band[0] = x->band[1] = x->band[2] = -1;
+			reqs[j].read = i, reqs[j].truesc = ar->truesc, reqs[j].reg_w = ar->w;
+			if (bmh_rp_xref_test(&rv, x->rb, x->re, &cb, &ce) > 0) {
+				int64_t *t = (int64_t *)realloc(cbe, sizeof(int64_t) * 2 * (n_fix + 1));
+				if (!t) { rc = BMH_E_NOMEM; goto done; }
+				cbe = t, cbe[2 * n_fix] = cb, cbe[2 * n_fix + 1] = ce;
+				x->flags = BMH_WANTED_MOVED, x->rsv_ = (int32_t)n_fix++; /* (rsv_ holds the fix index until the cut) */
+				fw += (size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb) + 2, fm_ += 3 * ((size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb)) + 16;
+			}
+		}
+	if (n_fix) { /* one bwa_gen_cigar2(w_ = opt->w) per such region, then walk its CIGAR to the cut points (bwa.c:198-219) */
+		size_t f = 0;
+		fq = (bmh_cigar_req_t *)malloc(sizeof(*fq) * n_fix), fr = (bmh_cigar_res_t *)malloc(sizeof(*fr) * n_fix);
+		fc = (uint32_t *)malloc(4 * fw), fmd = (char *)malloc(fm_);
+		if (!fq || !fr || !fc || !fmd) { rc = BMH_E_NOMEM; goto done; }
+		for (j = 0; j < (size_t)n_w; ++j) {
+			const bmh_wanted_res_t *x = &wr[j];
+			if (!(x->flags & BMH_WANTED_MOVED)) continue;
+			fq[f].read = reqs[j].read, fq[f].qb = x->qb, fq[f].qe = x->qe, fq[f].rb = x->rb, fq[f].re = x->re, fq[f].truesc = INT32_MIN, fq[f].reg_w = w;
+			++f;
+		}
+		if ((rc = bmh_reg2cigar_batch(ctx, l_pac, pac, reads, (int64_t)n_fix, fq, fr, fc, fw, fmd, fm_))) goto done;
+		for (j = 0; j < (size_t)n_w; ++j) {
+			bmh_wanted_res_t *x = &wr[j];
+			int f_;
+			if (!(x->flags & BMH_WANTED_MOVED)) continue;
+			f_ = x->rsv_, x->rsv_ = 0;
+			if (fr[f_].n_cigar > BMH_RP_SMALL_CAP) x->flags |= BMH_WANTED_HOST;
+			if (bmh_rp_xref_cut(fr[f_].n_cigar, fc + fr[f_].cigar_off, cbe[2 * f_], cbe[2 * f_ + 1], &x->qb, &x->qe, &x->rb, &x->re)) {
+				rc = BMH_E_ARG; /* bwa_fix_xref2 returns -2: the reference aborts */
+				goto done;
+			}
+		}
+	}
+	for (j = 0; j < (size_t)n_w; ++j) {
+		const bmh_wanted_res_t *x = &wr[j];
+		reqs[j].qb = x->qb, reqs[j].qe = x->qe, reqs[j].rb = x->rb, reqs[j].re = x->re;
+		cw += (size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb) + 2, mb += 3 * ((size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb)) + 16;
+	}
+	{ /* pools: a CIGAR may have ql+tl+1 operations and an MD 3 bytes per base, but they almost never have more than a
+	   * few -- try with 16 words / 48 bytes per region (plus one region's worst case) and only fall back to the sizes
+	   * that always suffice if the driver says BMH_E_CIGAR_CAP (hundreds of megabytes of untouched-but-mapped memory
+	   * per slice, mapped and unmapped by every host thread at once, cost more than the alignments) */
+		size_t cw2 = 16 * (size_t)n_w + 70000, mb2 = 48 * (size_t)n_w + 3 * 140000 + 64;
+		if (cw2 > cw) cw2 = cw;
+		if (mb2 > mb) mb2 = mb;
+		cig = (uint32_t *)malloc(4 * cw2), md = (char *)malloc(mb2);
+		if (!cig || !md) { rc = BMH_E_NOMEM; goto done; }
+		rc = bmh_reg2cigar_batch(ctx, l_pac, pac, reads, n_w, reqs, res, cig, cw2, md, mb2);
+		if (rc == BMH_E_CIGAR_CAP && (cw2 < cw || mb2 < mb)) {
+			free(cig), free(md);
+			cig = (uint32_t *)malloc(4 * cw), md = (char *)malloc(mb);
+			if (!cig || !md) { rc = BMH_E_NOMEM; goto done; }
+			rc = bmh_reg2cigar_batch(ctx, l_pac, pac, reads, n_w, reqs, res, cig, cw, md, mb);
+		}
+		if (rc) goto done;
+	}
+	for (j = 0; j < (size_t)n_w; ++j) {
+		bmh_wanted_res_t *x = &wr[j];
+		x->score = res[j].score, x->n_cigar = res[j].n_cigar, x->NM = res[j].NM, x->tries = res[j].tries;
+		x->cigar_off = res[j].cigar_off, x->md_off = res[j].md_off, x->md_len = res[j].md_len;
+		if (res[j].n_cigar > BMH_RP_SMALL_CAP || res[j].md_len > MD_SLOT_) x->flags |= BMH_WANTED_HOST;
+		if (bands) {
+			const bmh_rp_opt_t po = {p->a, p->mat[0], p->o_del, p->e_del, p->o_ins, p->e_ins, p->w};
+			bmh_rp_plan_t pl;
+			bmh_rp_plan(&po, x->qe - x->qb, (int)(x->re - x->rb), reqs[j].truesc, reqs[j].reg_w, &pl);
+			x->band[0] = pl.band[0], x->band[1] = pl.band[1], x->band[2] = pl.band[2];
+		}
+	}
+	if (n_fixed) *n_fixed = (int64_t)n_fix;
+	*cig_ = cig, *md_ = md, cig = 0, md = 0;
+done:
+	free(reqs), free(res), free(fq), free(fr), free(cbe), free(fc), free(fmd), free(cig), free(md);
+	return rc;
+}
+
+/* the caller's records and pools, in want order, from a form's own: written only here, after everything has succeeded */
+__attribute__((visibility("hidden"))) int bmh_wanted_deliver_(int64_t n_w, const bmh_wanted_res_t *wr, const uint32_t *cig, const char *md,
+                                                              bmh_wanted_res_t *results, uint32_t *cigar_pool, size_t cigar_words, char *md_pool, size_t md_bytes)
+{
+	size_t cu = 0, mu = 0;
+	int64_t j;
+	for (j = 0; j < n_w; ++j) cu += (size_t)wr[j].n_cigar, mu += (size_t)wr[j].md_len + 1;
+	if (cu > cigar_words || mu > md_bytes) return BMH_E_CIGAR_CAP;
+	for (j = 0, cu = mu = 0; j < n_w; ++j) {
+		bmh_wanted_res_t x = wr[j];
+		memcpy(cigar_pool + cu, cig + x.cigar_off, 4 * (size_t)x.n_cigar);
+		memcpy(md_pool + mu, md + x.md_off, (size_t)x.md_len);
+		md_pool[mu + x.md_len] = 0;
+		x.cigar_off = (uint32_t)cu, x.md_off = (uint32_t)mu;
+		results[j] = x;
+		cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+	}
+	return BMH_OK;
+}
+
+int bmh_wanted_cigar_batch(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                           const int64_t *roff, const int32_t *n_want, const int32_t *want_k, bmh_wanted_res_t *results, uint32_t *cigar_pool,
+                           size_t cigar_words, char *md_pool, size_t md_bytes)
+{
+	bmh_wanted_res_t *wr = 0;
+	uint32_t *cig = 0;
+	char *md = 0;
+	int64_t n_w;
+	int rc = wanted_check_args(ctx, bns, pac, n, reads, regs, roff, n_want, want_k, &n_w);
+	if (rc) return rc;
+	if (n_w == 0) return BMH_OK;
+	if (!results || !cigar_pool || !md_pool) return BMH_E_ARG;
+	if (!(wr = (bmh_wanted_res_t *)malloc(sizeof(*wr) * (size_t)n_w))) return BMH_E_NOMEM;
+	rc = bmh_wanted_host_(ctx, bns, pac, w, n, reads, regs, roff, n_want, want_k, n_w, 1, wr, &cig, &md, 0);
+	if (!rc) rc = bmh_wanted_deliver_(n_w, wr, cig, md, results, cigar_pool, cigar_words, md_pool, md_bytes);
+	free(wr), free(cig), free(md);
+	return rc;
+}
+
+/* the argument check of the two public forms, for csrc/api.hip */
+__attribute__((visibility("hidden"))) int bmh_wanted_check_args_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int n, const bmh_read_t *reads,
+                                                                 const bmh_alnreg_v *regs, const int64_t *roff, const int32_t *n_want, const int32_t *want_k,
+                                                                 int64_t *n_w)
+{
+	return wanted_check_args(ctx, bns, pac, n, reads, regs, roff, n_want, want_k, n_w);
 }
 
 /* pass A behind the context's switch (csrc/api.hip): bmh_decide_device while bmh_ctx_set_decide_device is on, falling back to
@@ -498,25 +664,30 @@ static int want_push(want_v *w, int read, int k, const bmh_alnreg_t *ar)
 void bmh_decide_stats_reset_(bmh_ctx_t *ctx);
 int bmh_decide_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs,
                        const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k);
+/* pass B behind the context's switch (csrc/api.hip): bmh_wanted_cigar_device's work while bmh_ctx_set_wanted_device is on, else
+ * bmh_wanted_host_ above; *cig / *md are malloc'd */
+int bmh_wanted_routed_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                       const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t n_w, bmh_wanted_res_t *wr, uint32_t **cig, char **md);
 
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id)
 {
 	const int pe = (o->flag & BMH_MEM_F_PE) != 0;
 	const int64_t l_pac = bns ? bns->l_pac : 0;
-	want_v W = {0, 0, 0};
+	bmh_rp_refv_t rv;
+	bmh_wanted_res_t *wr = 0; /* the wanted regions, in want order: final coordinates and alignments */
+	int32_t *wk = 0;          /* ... and the region index of each in its read's vector */
+	int64_t n_w = 0;
 	bmh_pairdec_t *pd = 0;
 	int64_t *roff = 0;
 	int32_t *reg_mapq = 0, *n_want = 0, *want_k = 0;
 	bmh_read_t *reads = 0;
-	bmh_cigar_req_t *reqs = 0;
-	bmh_cigar_res_t *res = 0;
 	uint32_t *cig = 0, *arena = 0;
 	char *md = 0;
 	size_t *first = 0; /* first entry of W per read (+1 sentinel) */
 	aln_t *alns = 0;
 	str_t str = {0, 0, 0};
-	size_t j, cw = 8, mb = 16, n_fix = 0, arena_words = 0;
+	size_t j, arena_words = 0;
 	int i, rc = BMH_OK;
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0;
 	double tt[4] = {0, 0, 0, 0};
@@ -524,6 +695,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	bmh_decide_stats_reset_(ctx);
 	if (!ctx || !o || !bns || !pac || n < 0 || (n > 0 && (!seqs || !regs)) || (pe && ((n & 1) || !pes))) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
+	rv = refv_of(bns);
 	first = (size_t *)calloc((size_t)n + 1, sizeof(size_t));
 	reads = (bmh_read_t *)malloc(sizeof(bmh_read_t) * (size_t)n);
 	roff = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
@@ -540,131 +712,47 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	if (!reg_mapq || !want_k) { rc = BMH_E_NOMEM; goto done; }
 
 	if (trace) tt[0] = now_s();
-	/* ---- pass A: decisions (bmh_decide_batch, or bmh_decide_device behind the context's switch), then the want list as records */
+	/* ---- pass A: decisions (bmh_decide_batch, or bmh_decide_device behind the context's switch) */
 	if ((rc = bmh_decide_routed_(ctx, o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k))) goto done;
-	for (i = 0; i < n; ++i) {
-		int q;
-		first[i] = W.n;
-		for (q = 0; q < n_want[i]; ++q) {
-			const int k = want_k[roff[i] + q];
-			if ((rc = want_push(&W, i, k, &regs[i].a[k]))) goto done;
-		}
-	}
-	first[n] = W.n;
+	for (i = 0; i < n; ++i) n_w += n_want[i];
 
 	if (trace) tt[1] = now_s();
-	/* ---- pass B: bwa_fix_xref2 (bwa.c:179-222), then the alignments */
-	for (j = 0; j < W.n; ++j) {
-		want_t *x = &W.a[j];
-		const bmh_refann_t *ra;
-		int is_rev;
-		int64_t fm, cb, ce;
-		if (x->rb < l_pac && x->re > l_pac) { /* bridges the strands: the reference gives up on the run (bwamem.c:1183-1186) */
-			rc = BMH_E_ARG;
-			goto done;
-		}
-		fm = depos(l_pac, (x->rb + x->re) >> 1, &is_rev);
-		ra = &bns->anns[pos2rid(bns, fm)];
-		cb = is_rev ? (l_pac << 1) - (ra->offset + ra->len) : ra->offset; /* its sequence, on the mapping strand */
-		ce = cb + ra->len;
-		if (cb > x->rb || ce < x->re) x->fix = (int)n_fix++, x->cb = cb > x->rb ? cb : x->rb, x->ce = ce < x->re ? ce : x->re;
+	/* ---- pass B: bwa_fix_xref2 (bwa.c:179-222), then the alignments: bmh_wanted_cigar_batch's work, or with
+	 * bmh_ctx_set_wanted_device on bmh_wanted_cigar_device's (the same records either way) */
+	if (n_w) {
+		wr = (bmh_wanted_res_t *)malloc(sizeof(*wr) * (size_t)n_w);
+		wk = (int32_t *)malloc(sizeof(*wk) * (size_t)n_w);
+		if (!wr || !wk) { rc = BMH_E_NOMEM; goto done; }
+		if ((rc = bmh_wanted_routed_(ctx, bns, pac, o->w, n, reads, regs, roff, n_want, want_k, n_w, wr, &cig, &md))) goto done;
+		for (j = 0; j < (size_t)n_w; ++j) arena_words += (size_t)wr[j].n_cigar + 2;
 	}
-	if (n_fix) { /* one bwa_gen_cigar2(w_ = opt->w) per such region, then walk its CIGAR to the cut points (bwa.c:198-219) */
-		size_t f = 0, fw = 8, fm_ = 16;
-		bmh_cigar_req_t *fq = (bmh_cigar_req_t *)malloc(sizeof(*fq) * n_fix);
-		bmh_cigar_res_t *fr = (bmh_cigar_res_t *)malloc(sizeof(*fr) * n_fix);
-		uint32_t *fc;
-		char *fmd;
-		for (j = 0; j < W.n; ++j) {
-			const want_t *x = &W.a[j];
-			if (x->fix < 0) continue;
-			fq[f].read = x->read, fq[f].qb = x->qb, fq[f].qe = x->qe, fq[f].rb = x->rb, fq[f].re = x->re, fq[f].truesc = INT32_MIN, fq[f].reg_w = o->w;
-			fw += (size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb) + 2, fm_ += 3 * ((size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb)) + 16;
-			++f;
-		}
-		fc = (uint32_t *)malloc(4 * fw), fmd = (char *)malloc(fm_);
-		rc = fq && fr && fc && fmd ? bmh_reg2cigar_batch(ctx, l_pac, pac, reads, (int64_t)n_fix, fq, fr, fc, fw, fmd, fm_) : BMH_E_NOMEM;
-		for (j = 0; j < W.n && !rc; ++j) {
-			want_t *x = &W.a[j];
-			const uint32_t *cg;
-			int64_t xx;
-			int k, y;
-			if (x->fix < 0) continue;
-			cg = fc + fr[x->fix].cigar_off;
-			for (k = 0, xx = x->rb, y = x->qb; k < fr[x->fix].n_cigar; ++k) {
-				const int op = (int)(cg[k] & 0xf), len = (int)(cg[k] >> 4);
-				if (op == 0) {
-					if (xx <= x->cb && x->cb < xx + len) x->qb = y + (int)(x->cb - xx), x->rb = x->cb;
-					if (xx < x->ce && x->ce <= xx + len) {
-						x->qe = y + (int)(x->ce - xx), x->re = x->ce;
-						break;
-					} else xx += len, y += len;
-				} else if (op == 1) y += len;
-				else if (op == 2) {
-					if (xx <= x->cb && x->cb < xx + len) x->qb = y, x->rb = xx + len;
-					if (xx < x->ce && x->ce <= xx + len) {
-						x->qe = y, x->re = xx;
-						break;
-					} else xx += len;
-				}
-			}
-			if (x->qb == x->qe || x->rb == x->re) rc = BMH_E_ARG; /* bwa_fix_xref2 returns -2: the reference aborts */
-		}
-		free(fq), free(fr), free(fc), free(fmd);
-		if (rc) goto done;
+	for (i = 0, j = 0; i < n; ++i) { /* first entry of the want list per read */
+		int q;
+		first[i] = j;
+		for (q = 0; q < n_want[i]; ++q) wk[j++] = want_k[roff[i] + q];
 	}
-	if (W.n) {
-		reqs = (bmh_cigar_req_t *)malloc(sizeof(*reqs) * W.n);
-		res = (bmh_cigar_res_t *)malloc(sizeof(*res) * W.n);
-		if (!reqs || !res) { rc = BMH_E_NOMEM; goto done; }
-		for (j = 0; j < W.n; ++j) {
-			const want_t *x = &W.a[j];
-			const bmh_alnreg_t *ar = &regs[x->read].a[x->k];
-			reqs[j].read = x->read, reqs[j].qb = x->qb, reqs[j].qe = x->qe, reqs[j].rb = x->rb, reqs[j].re = x->re;
-			reqs[j].truesc = ar->truesc, reqs[j].reg_w = ar->w;
-			cw += (size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb) + 2, mb += 3 * ((size_t)(x->qe - x->qb) + (size_t)(x->re - x->rb)) + 16;
-		}
-		{ /* pools: a CIGAR may have ql+tl+1 operations and an MD 3 bytes per base, but they almost never have more than a
-		   * few -- try with 16 words / 48 bytes per region (plus one region's worst case) and only fall back to the sizes
-		   * that always suffice if the driver says BMH_E_CIGAR_CAP (hundreds of megabytes of untouched-but-mapped memory
-		   * per slice, mapped and unmapped by every host thread at once, cost more than the alignments) */
-			size_t cw2 = 16 * W.n + 70000, mb2 = 48 * W.n + 3 * 140000 + 64;
-			if (cw2 > cw) cw2 = cw;
-			if (mb2 > mb) mb2 = mb;
-			cig = (uint32_t *)malloc(4 * cw2), md = (char *)malloc(mb2);
-			if (!cig || !md) { rc = BMH_E_NOMEM; goto done; }
-			rc = bmh_reg2cigar_batch(ctx, l_pac, pac, reads, (int64_t)W.n, reqs, res, cig, cw2, md, mb2);
-			if (rc == BMH_E_CIGAR_CAP && (cw2 < cw || mb2 < mb)) {
-				free(cig), free(md);
-				cig = (uint32_t *)malloc(4 * cw), md = (char *)malloc(mb);
-				if (!cig || !md) { rc = BMH_E_NOMEM; goto done; }
-				rc = bmh_reg2cigar_batch(ctx, l_pac, pac, reads, (int64_t)W.n, reqs, res, cig, cw, md, mb);
-			}
-			if (rc) goto done;
-		}
-		for (j = 0; j < W.n; ++j) arena_words += (size_t)res[j].n_cigar + 2;
-	}
+	first[n] = j;
 
 	if (trace) tt[2] = now_s();
 	/* ---- pass C: mem_reg2aln's second half (bwamem.c:1203-1235) for every wanted region, then the text */
-	alns = (aln_t *)malloc(sizeof(aln_t) * (W.n + 2));
+	alns = (aln_t *)malloc(sizeof(aln_t) * ((size_t)n_w + 2));
 	arena = (uint32_t *)malloc(4 * (arena_words + 4));
 	if (!alns || !arena) { rc = BMH_E_NOMEM; goto done; }
 	arena_words = 0;
-	for (j = 0; j < W.n; ++j) {
-		const want_t *x = &W.a[j];
-		const bmh_alnreg_t *ar = &regs[x->read].a[x->k];
-		const int l_query = seqs[x->read].l_seq;
+	for (i = 0, j = 0; i < n; ++i)
+	for (; j < first[i + 1]; ++j) {
+		const bmh_wanted_res_t *x = &wr[j];
+		const bmh_alnreg_t *ar = &regs[i].a[wk[j]];
+		const int l_query = seqs[i].l_seq;
 		aln_t *a = &alns[j];
-		const uint32_t *src = cig + res[j].cigar_off;
+		const uint32_t *src = cig + x->cigar_off;
 		uint32_t *dst = arena + arena_words;
-		int nc = res[j].n_cigar, is_rev, k, clip5, clip3;
+		int nc = x->n_cigar, is_rev, k, clip5, clip3;
 		int64_t pos;
-		if (res[j].NM < 0) { rc = BMH_E_ARG; goto done; } /* bwa_gen_cigar2 refused the region (bwa.c:99): cannot happen after the fix */
 		memset(a, 0, sizeof(*a));
-		a->mapq = ar->secondary < 0 ? reg_mapq[roff[x->read] + x->k] : 0;
+		a->mapq = ar->secondary < 0 ? reg_mapq[roff[i] + wk[j]] : 0;
 		if (ar->secondary >= 0) a->flag |= 0x100;
-		a->NM = res[j].NM, a->md = md + res[j].md_off;
+		a->NM = x->NM, a->md = md + x->md_off;
 		pos = depos(l_pac, x->rb < l_pac ? x->rb : x->re - 1, &is_rev);
 		a->is_rev = is_rev;
 		if (nc > 0) { /* squeeze out a leading or trailing deletion */
@@ -680,7 +768,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 			if (clip3) dst[k++] = (uint32_t)clip3 << 4 | 3;
 		} else memcpy(dst, src, 4 * (size_t)nc), k = nc;
 		a->n_cigar = k, arena_words += (size_t)k;
-		a->rid = pos2rid(bns, pos);
+		a->rid = bmh_rp_pos2rid(&rv, pos);
 		a->pos = pos - bns->anns[a->rid].offset;
 		a->score = ar->score, a->sub = ar->sub > ar->csub ? ar->sub : ar->csub;
 	}
@@ -713,7 +801,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 					if (f1 > f0) h[r] = alns[f0], h[r].mapq = d->q_se[r];
 					else unmapped(&h[r]);
 					h[r].flag |= (r ? 0x80 : 0x40) | extra;
-				} else if (f1 > f0 && W.a[f0].k == 0) h[r] = alns[f0]; /* regs[].a[0] with score >= T */
+				} else if (f1 > f0 && wk[f0] == 0) h[r] = alns[f0]; /* regs[].a[0] with score >= T */
 				else unmapped(&h[r]);
 			}
 			if (d->paired) {
@@ -740,7 +828,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 			size_t q;
 			str.l = 0;
 			for (q = f0; q < f1; ++q) { /* alns[f0..f1) is the reference's `aa` */
-				const int k = W.a[q].k;
+				const int k = wk[q];
 				const bmh_alnreg_t *p = &regs[rd].a[k];
 				aln_t *a = &alns[q];
 				a->flag |= extra_flag;
@@ -761,9 +849,9 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	}
 	if (trace)
 		fprintf(stderr, "[bwamem_hip] bmh_sam_batch %d reads, %zu alignments: marking + pairing %.1f ms, global alignments (bmh_reg2cigar_batch) %.1f ms, coordinates + text %.1f ms\n",
-		        n, W.n, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3);
+		        n, (size_t)n_w, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3);
 done:
-	free(W.a), free(pd), free(reads), free(reqs), free(res), free(cig), free(md), free(first), free(alns), free(arena), free(roff), free(reg_mapq),
+	free(wr), free(wk), free(pd), free(reads), free(cig), free(md), free(first), free(alns), free(arena), free(roff), free(reg_mapq),
 	    free(n_want), free(want_k), free(str.s);
 	return rc;
 }

@@ -632,6 +632,54 @@ int bmh_ctx_set_decide_device(bmh_ctx_t *ctx, int on);
  * refused argument).  Any pointer may be NULL. */
 int bmh_last_decide_stats(const bmh_ctx_t *ctx, int64_t *units, int64_t *fallbacks, float *kernel_ms);
 
+/* ---- Pass B of bmh_sam_batch on its own: the global alignments of exactly the regions pass A listed (mem_reg2aln's first half,
+ * bwamem.c:1164-1201, over bwa_fix_xref2, bwa.c:179-222), for reads [0,n) of a chunk slice.  regs, roff, n_want, want_k as
+ * bmh_decide_batch leaves them; w = opt->w (the band of bwa_fix_xref2's single alignment); the context's parameters give the scoring.
+ * Wanted region number j = (wanted regions of the reads before read i) + q stands for want_k[roff[i] + q]; results[j] is:
+ *   qb, qe, rb, re   the region's ends after bwa_fix_xref2
+ *   score, n_cigar, NM, tries, md_len   as bmh_cigar_res_t
+ *   cigar_off, md_off   into cigar_pool / md_pool, packed in want order (the MD strings NUL-terminated); BMH_E_CIGAR_CAP when a
+ *                    pool is too small -- the sums of qe-qb + re-rb + 2 words and of 3*(qe-qb + re-rb) + 16 bytes always suffice
+ *   band[3]          the band of each try as planned: -1 where there is no try, band[0] == -1 for the no-gap case (bwa.c:108-114)
+ *   flags            BMH_WANTED_MOVED: the region hung over an end of its reference sequence and bwa_fix_xref2 moved an end;
+ *                    BMH_WANTED_HOST: an alignment of the region outgrows the device's slots (a CIGAR of more than 24 operations,
+ *                    its own or that of bwa_fix_xref2's alignment, or an MD string of more than 128 bytes), so wherever the
+ *                    region records run it is redone with host copies; the BMH_REGION_* bits are cleared by then and never set here
+ * What the planning sees is checked per wanted region: 0 <= want_k < regs[i].n, 0 <= qb < qe <= l_seq, 0 <= rb < re <= 2*l_pac and no
+ * strand bridge (BMH_E_ARG, as for a region of which bwa_fix_xref2 leaves nothing), qe-qb and re-rb at most 65535 (BMH_E_RANGE).
+ * The caller's memory is written only after everything has succeeded.  n == 0 or no wanted region: BMH_OK, nothing runs. */
+#define BMH_WANTED_MOVED 4u
+#define BMH_WANTED_HOST 8u
+typedef struct bmh_wanted_res { /* 72 bytes */
+	int64_t rb, re;
+	int32_t qb, qe;
+	int32_t score, n_cigar, NM, tries;
+	uint32_t cigar_off, md_off, md_len, flags;
+	int32_t band[3];
+	int32_t rsv_;
+} bmh_wanted_res_t;
+int bmh_wanted_cigar_batch(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads,
+                           const bmh_alnreg_v *regs, const int64_t *roff, const int32_t *n_want, const int32_t *want_k,
+                           bmh_wanted_res_t *results, uint32_t *cigar_pool, size_t cigar_words, char *md_pool, size_t md_bytes);
+/* The same with the planning as kernels (csrc/wanted.hip over host/regplan_core.h, the text the host form uses): one upload of
+ * offsets, regions, the want list and the reads, the planning kernels and the region kernels of bmh_region_cigar_batch behind it,
+ * one download.  The host reads one status record between launches, at most twice.  The same bytes out as the host form.  Needs the
+ * 2-bit reference (bmh_ctx_set_pac with bns->l_pac) and the sequence table (bmh_ctx_set_refidx) resident: BMH_E_ARG otherwise.  The few
+ * regions flagged BMH_WANTED_HOST are redone on the host; the rest of the call is unaffected. */
+int bmh_wanted_cigar_device(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads,
+                            const bmh_alnreg_v *regs, const int64_t *roff, const int32_t *n_want, const int32_t *want_k,
+                            bmh_wanted_res_t *results, uint32_t *cigar_pool, size_t cigar_words, char *md_pool, size_t md_bytes);
+/* Copies (offset, len) of every reference sequence of bns to the device, where it stays like the 2-bit reference; NULL drops it. */
+int bmh_ctx_set_refidx(bmh_ctx_t *ctx, const bmh_refidx_t *bns);
+/* Per context, off by default.  While on, bmh_sam_batch takes its pass B from the device form (BMH_E_ARG without the two resident
+ * tables).  The text is the same either way. */
+int bmh_ctx_set_wanted_device(bmh_ctx_t *ctx, int on);
+/* Of the last bmh_wanted_cigar_device call on this context, direct or from bmh_sam_batch with the switch on: wanted regions, regions
+ * bwa_fix_xref2 moved, regions redone on the host, and the planning kernels' milliseconds with bmh_set_kernel_timing on (else -1).
+ * -1, -1, -1, -1 before the first such call.  Any pointer may be NULL.  (With bmh_ctx_set_decide_device also on, pass A and pass B
+ * are still two device sessions: the want list is downloaded and uploaded again between them.) */
+int bmh_last_wanted_stats(const bmh_ctx_t *ctx, int64_t *wanted, int64_t *fixed, int64_t *redone, float *kernel_ms);
+
 /* ------------------------------------------------------------------------------------------------------------
  * FM-index queries of the seeding stage (first slice): super-maximal exact matches and suffix-
  * array look-ups on the device, over the reference's own index arrays made resident in HBM.
