@@ -281,6 +281,8 @@ int bmh_ctx_create(bmh_ctx_t **out, int device)
 	if (const char *m = getenv("BMH_SW_MODE")) ctx->sw_mode = !strcmp(m, "generic") ? 1 : 0;
 	if (const char *m = getenv("BMH_SW_WAVE")) ctx->sw_wave = atoi(m) != 0;
 	if (const char *m = getenv("BMH_GL_FAST")) ctx->glb_fast = atoi(m) != 0;
+	if (const char *m = getenv("BMH_GLB_C32")) ctx->glb_c32 = atoi(m) != 0; // (A/B knob)
+	if (const char *m = getenv("BMH_GLB_NARROW")) ctx->glb_narrow = atoi(m) != 0; // (A/B knob)
 	if (const char *m = getenv("BMH_GRID_MULT")) ctx->grid_mult = atoi(m) > 0 ? atoi(m) : 1;
 	if (const char *m = getenv("BMH_EXT_SCHED")) ctx->ext_sched = atoi(m) >= 0 && atoi(m) <= 4 ? atoi(m) : -1;
 	*out = ctx;
@@ -296,7 +298,7 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)stream_wait(ctx, ctx->stream);
 	free_buf(ctx->d_pool), free_buf(ctx->d_tasks), free_buf(ctx->d_res), free_buf(ctx->d_order);
-	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
+	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_gband), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
 	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab), free_buf(ctx->d_c2r);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
@@ -1156,7 +1158,8 @@ int bmh_ctx_reserve_device(bmh_ctx_t *ctx, size_t pool_bytes, int64_t max_tasks,
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	if ((rc = ensure(ctx, ctx->d_pool, pool_bytes + 16)) || (rc = ensure(ctx, ctx->d_tasks, N * 40 + 64)) || (rc = ensure(ctx, ctx->d_res, N * 32 + 64)) ||
 	    (rc = ensure(ctx, ctx->d_cigar, (cigar_words + 4) * 4)) ||
-	    (rc = ensure(ctx, ctx->d_bins, (16 + (size_t)kSortBins * kSortKeysHost + (N + 1) / 2 + 1 + (size_t)kSortBins * N) * 4)))
+	    (rc = ensure(ctx, ctx->d_bins, (16 + (size_t)kSortBins * kSortKeysHost + (N + 1) / 2 + 1 + (size_t)kSortBins * N) * 4)) ||
+	    (ctx->glb_narrow && (rc = ensure(ctx, ctx->d_gband, (1 + (size_t)kSortBins) * N + 16))))
 		return rc;
 	return BMH_OK;
 }

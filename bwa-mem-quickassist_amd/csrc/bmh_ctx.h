@@ -34,6 +34,9 @@ struct bmh_ctx {
 	int glb_mode = 0; // 0 lane-per-task global kernels, 1 one wave per task only (env BMH_GLB_MODE=wave)
 	int sw_mode = 0;  // 0 register kernels where they fit, 1 slab kernel only (env BMH_SW_MODE=generic)
 	int glb_fast = 1;   // unmasked body for blocks inside every lane's band (env BMH_GL_FAST=0 turns it off)
+	int glb_narrow = 1; // lane kernels run each task on the band its result needs (host/glbband_core.h; env BMH_GLB_NARROW=0 turns it off)
+	int glb_c32 = 1;    // bands up to 15 run on the 32-slot instantiation, four waves per SIMD (env BMH_GLB_C32=0: on the 64-slot one)
+	DevBuf d_gband;     // ... those bands: n bytes by input position, then kSortBins x n bytes parallel to the sort's lists
 	int sw_wave = 1;  // batches of up to 32 k tasks: one wave per task (sw_wave.hip); env BMH_SW_WAVE=0 turns it off
 	DevBuf d_bins; // per-launch bin lists of the extension dispatcher: 4 counters + 4 x n task indices
 	int grid_mult = 1;    // env BMH_GRID_MULT: persistent grid = resident waves x this (tuning knob)
@@ -246,11 +249,12 @@ int launch_extend_lds(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t 
 constexpr int kSortKeysHost = 2048; // == kSortKeys in extend_dispatch.hip
 int sort_tasks_begin(bmh_ctx *ctx, int64_t n, uint32_t **counts, uint32_t **lists);
 // d_total (nullable): receives the sum of the bin sizes
+// d_payload (nullable): one byte per input position, placed in d_plists (kSortBins x n bytes) exactly as the index is in lists
 int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n = nullptr,
-                      uint32_t *d_total = nullptr);
+                      uint32_t *d_total = nullptr, const uint8_t *d_payload = nullptr, uint8_t *d_plists = nullptr);
 int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                        bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, const uint32_t *d_count,
-                       int rows_cap);
+                       int rows_cap, const uint8_t *d_band = nullptr);
 constexpr int kExtBins = 6;        // length bins of the extension dispatcher (the 16-bit kernels)
 constexpr int kWideBin = 6;        // ... and the int32 kernel's bin, used only with bmh_ctx_set_wide_extension on
 constexpr int kSortBins = 8;       // bins the shared counting sort can tell apart (extension 6, global 6, Smith-Waterman 8)

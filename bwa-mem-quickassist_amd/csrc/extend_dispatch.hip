@@ -91,7 +91,9 @@ __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const uint32
                                                                     uint32_t *__restrict__ cursor,
                                                                     const uint16_t *__restrict__ binkey,
                                                                     uint32_t *__restrict__ lists, long long stride,
-                                                                    const uint32_t *__restrict__ dn)
+                                                                    const uint32_t *__restrict__ dn,
+                                                                    const uint8_t *__restrict__ payload,
+                                                                    uint8_t *__restrict__ plists)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeys];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kSortThreads) lh[t] = 0;
@@ -110,7 +112,9 @@ __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const uint32
 		const uint32_t bk = binkey[k];
 		if (bk == kNoTask) continue;
 		const uint32_t pos = atomicAdd(&lh[bk], 1u);
-		lists[(size_t)(bk / kSortKeys) * (size_t)stride + pos] = order ? order[k] : (uint32_t)k;
+		const size_t at = (size_t)(bk / kSortKeys) * (size_t)stride + pos;
+		lists[at] = order ? order[k] : (uint32_t)k;
+		if (payload) plists[at] = payload[k]; // a byte that belongs to the input position travels with it (the global dispatcher's band)
 	}
 }
 
@@ -127,7 +131,8 @@ int sort_tasks_begin(bmh_ctx *ctx, int64_t n, uint32_t **counts, uint32_t **list
 	return BMH_OK;
 }
 
-int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n, uint32_t *d_total)
+int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned blocks, const uint32_t *d_n, uint32_t *d_total,
+                      const uint8_t *d_payload, uint8_t *d_plists)
 {
 	const size_t N = (size_t)n, hist_words = (size_t)kSortBins * kSortKeys;
 	uint32_t *counts = (uint32_t *)ctx->d_bins.p, *hist = counts + 16;
@@ -135,7 +140,7 @@ int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned
 	uint32_t *lists = hist + hist_words + (N + 1) / 2 + 1;
 	hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, hist, counts, d_total);
 	hipLaunchKernelGGL(sort_scatter_kernel, dim3(blocks), dim3(kSortThreads), 0, ctx->stream, d_order, (long long)n, hist, binkey,
-	                   lists, (long long)n, d_n);
+	                   lists, (long long)n, d_n, d_payload, d_plists);
 	BMH_HIP(ctx, hipGetLastError());
 	return BMH_OK;
 }

@@ -17,6 +17,7 @@
 //   * queries past the LDS row (kGlbLdsQcap columns) run with RING: H and E in a ring of band slots (bin 4).
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "../host/glbband_core.h"
 
 namespace bmh {
 
@@ -251,6 +252,8 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 }
 
 // ---- dispatcher -----------------------------------------------------------------------------------
+// (w below: the band the lane kernels run the task on -- the band pass's w_eff, or the task's own with BMH_GLB_NARROW=0)
+// bin 5: w <= 15  -> global_lane_kernel<32>   (four waves per SIMD; with BMH_GLB_C32=0 these stay in bin 0)
 // bin 0: w <= 31  -> global_lane_kernel<64>   (64 tasks per wave, band-relative registers)
 // bin 1: w <= 63  -> global_lane_kernel<128>
 // bin 3: 32 <= w <= 47 -> global_lane_kernel<96>
@@ -261,29 +264,84 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 // bin 4: the tasks of bin 2 with more query columns than its LDS row holds (kGlbLdsQcap), when the launch has a bin 4 at all
 //        (lds_qcap < 65535) -> global_kernel<false, true> (the band ring)
 // Bins and the order inside them (by row count) come from the same device-side counting sort as the extension path.
+// A task may run on a lane kernel when its rows fit the direction slab and no cell can leave the 16-bit range; which one, its band
+// decides.  (The lane kernels take the sign of 16-bit differences such as m - e - o_del: with |m|, |e| < 12000 and the -16384
+// sentinel that stays inside +-32767 as long as the gap-open penalties are not absurd.)
+__device__ __forceinline__ bool glb_lane_domain(const DevParams &P, int qlen, int tlen, int w, int lane_ok, int rows_cap)
+{
+	const int emax = max(P.e_del, P.e_ins), smax = max(P.bias, P.max_mat);
+	const int worst = P.o_del + P.o_ins + emax * (qlen + tlen) + smax * max(qlen, tlen); // |score| bound of any cell
+	return lane_ok && tlen <= rows_cap && worst < 12000 && P.o_del + P.o_ins < 4000 && w >= 0;
+}
+
+// The band pass, in front of the sort: band[k] = the band the result of the task at input position k needs (host/glbband_core.h,
+// DESIGN.md §4.6), for the tasks a lane kernel can take; 255 stands for "64 or wider", which no lane kernel runs.  By position and
+// not by task: the indices in a caller's d_order may be sparse.  EIGHT lanes per task, each an eighth of the pairs in eight-base
+// loads, joined in order: the eight lanes' loads fall into the task's two or three cache lines in the same instruction.  (One lane
+// per task had every lane walk lines of its own: with all resident waves' lines far beyond the caches each 8-byte load fetched a
+// whole line again, 8.6 ms for 8.5 M tasks, profiles/global_band.md.)  No LDS histogram here, so enough waves are resident to hide
+// the loads -- inside glb_sort_hist_kernel (64 KiB of LDS, two blocks per CU) they would be exposed.
+constexpr int kBandThreads = 256, kBandLanes = 8;
+__global__ __launch_bounds__(kBandThreads) void glb_band_kernel(const uint8_t *__restrict__ pool, const bmh_glb_task_t *__restrict__ tasks,
+                                                                const uint32_t *__restrict__ order, long long n, uint8_t *__restrict__ band,
+                                                                DevParams P, int lane_ok, int rows_cap)
+{
+	__shared__ int8_t smat[32];
+	if (threadIdx.x < 25) smat[threadIdx.x] = (int8_t)mat_at(P, threadIdx.x);
+	__syncthreads();
+	const int amax = bmh_glbband_amax(smat);
+	const bool rule = bmh_glbband_applies(amax, P.o_del, P.e_del, P.o_ins, P.e_ins);
+	const int g = threadIdx.x & (kBandLanes - 1);
+	constexpr int kPer = kBandThreads / kBandLanes;
+	for (long long k = (long long)blockIdx.x * kPer + threadIdx.x / kBandLanes; k < n; k += (long long)gridDim.x * kPer) { // (uniform in a group of eight)
+		const uint32_t idx = order ? order[k] : (uint32_t)k;
+		const uint4 *tp = (const uint4 *)(tasks + idx);
+		const uint4 ta = tp[0], tb = tp[1];
+		const int qlen = (int)(tb.x & 0xffff), tlen = (int)(tb.x >> 16);
+		int w = (int)tb.y;
+		if (rule && qlen >= 1 && tlen >= 1 && w >= abs(qlen - tlen) && glb_lane_domain(P, qlen, tlen, w, lane_ok, rows_cap)) {
+			const bmh_gb_walk_t wk = bmh_glbband_walk(P.o_del, P.e_del, P.o_ins, P.e_ins, pool + ((uint64_t)ta.y << 32 | ta.x), qlen,
+			                                          pool + ((uint64_t)ta.w << 32 | ta.z), tlen);
+			const int per = ((wk.n + 8 * kBandLanes - 1) / (8 * kBandLanes)) * 8; // pairs per lane, a multiple of the eight-base load
+			const int from = min(g * per, wk.n), to = min(from + per, wk.n);
+			const bmh_gb_part_t mine = bmh_glbband_part(smat, &wk, from, to);
+			bmh_gb_part_t acc = {0, 0, 0};
+#pragma unroll
+			for (int j = 0; j < kBandLanes; ++j) { // every lane joins the eight parts in order
+				const bmh_gb_part_t nx = {__shfl(mine.s1, j, kBandLanes), __shfl(mine.d, j, kBandLanes), __shfl(mine.b, j, kBandLanes)};
+				bmh_glbband_join(&acc, &nx);
+			}
+			w = bmh_glbband_from_lb(amax, P.o_del, P.e_del, P.o_ins, P.e_ins, qlen, tlen, w, acc.s1 + acc.b - wk.gap);
+		}
+		if (g == 0) band[k] = (uint8_t)(w < 0 || w > 255 ? 255 : w);
+	}
+}
+
 __global__ __launch_bounds__(256) void glb_sort_hist_kernel(const bmh_glb_task_t *__restrict__ tasks,
                                                             const uint32_t *__restrict__ order, long long n,
                                                             uint32_t *__restrict__ hist, uint16_t *__restrict__ binkey,
-                                                            DevParams P, int lane_ok, int rows_cap, int lds_qcap)
+                                                            DevParams P, int lane_ok, int rows_cap, int lds_qcap,
+                                                            const uint8_t *__restrict__ band, int c32)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += 256) lh[t] = 0;
 	__syncthreads();
 	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
-	const int emax = max(P.e_del, P.e_ins), smax = max(P.bias, P.max_mat);
 	for (long long k = lo + threadIdx.x; k < hi; k += 256) {
 		const uint32_t idx = order ? order[k] : (uint32_t)k;
-		const int qlen = tasks[idx].qlen, tlen = tasks[idx].tlen, w = tasks[idx].w;
-		const int worst = P.o_del + P.o_ins + emax * (qlen + tlen) + smax * max(qlen, tlen); // |score| bound of any cell
-		int bin = 2;
-		// (the lane kernels take the sign of 16-bit differences such as m - e - o_del: with |m|, |e| < 12000 and the -16384 sentinel that
-		// stays inside +-32767 as long as the gap-open penalties are not absurd)
-		if (lane_ok && tlen <= rows_cap && worst < 12000 && P.o_del + P.o_ins < 4000 && w >= 0) bin = w <= 31 ? 0 : w <= 47 ? 3 : (w <= 63 ? 1 : 2);
+		const int qlen = tasks[idx].qlen, tlen = tasks[idx].tlen;
+		int bin = 2, w = tasks[idx].w;
+		if (glb_lane_domain(P, qlen, tlen, w, lane_ok, rows_cap)) {
+			// the band pass has been here (band != null): the lane kernels run the task on band[k], so that picks the bin and the key.
+			// It only ever narrows, so the host's gates (which lane kernels are launched at all) still hold
+			if (band) w = band[k];
+			bin = c32 && w <= 15 ? 5 : w <= 31 ? 0 : w <= 47 ? 3 : (w <= 63 ? 1 : 2);
+		}
 		if (bin == 2 && qlen > lds_qcap) bin = 4;
 		// inside a lane bin: rows first (lanes of a wave run until their longest target ends), then band width (a wave
 		// computes and stores the 8-slot blocks that ANY of its lanes needs, and its lanes' tracebacks share cache lines
 		// when they sit in the same block)
-		const int bk = bin * kSortKeysHost + (bin != 2 && bin != 4 ? (min(tlen >> 3, 127) << 4 | (min(w, 63) >> (bin == 0 ? 1 : 2) & 15)) : 0);
+		const int bk = bin * kSortKeysHost + (bin != 2 && bin != 4 ? (min(tlen >> 3, 127) << 4 | (min(w, 63) >> (bin == 5 ? 0 : bin == 0 ? 1 : 2) & 15)) : 0);
 		binkey[k] = (uint16_t)bk;
 		atomicAdd(&lh[bk], 1u);
 	}
@@ -340,19 +398,33 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
 	uint16_t *binkey = (uint16_t *)(hist + (size_t)kSortBins * kSortKeysHost);
 	long long cg = (n + 1023) / 1024;
 	if (cg > 512) cg = 512;
+	// the bands the lane kernels will run on: by input position for the sort's first pass, then listed beside each bin's indices
+	uint8_t *band = nullptr, *blists = nullptr;
+	if (lane_ok && ctx->glb_narrow) {
+		if ((rc = ensure(ctx, ctx->d_gband, (1 + (size_t)kSortBins) * N + 16))) return rc;
+		band = (uint8_t *)ctx->d_gband.p, blists = band + ((N + 15) & ~(size_t)15);
+		const long long bg = std::min<long long>((n * kBandLanes + kBandThreads - 1) / kBandThreads, (long long)ctx->ncu * 8 * 4);
+		hipLaunchKernelGGL(glb_band_kernel, dim3((unsigned)bg), dim3(kBandThreads), 0, ctx->stream, d_pool, d_tasks, d_order, (long long)n,
+		                   band, ctx->dev, 1, rows_cap);
+	}
 	hipLaunchKernelGGL(glb_sort_hist_kernel, dim3((unsigned)cg), dim3(256), 0, ctx->stream, d_tasks, d_order, (long long)n, hist,
-	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap, longb ? kGlbLdsQcap : 65535);
-	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg))) return rc;
+	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap, longb ? kGlbLdsQcap : 65535, band, ctx->glb_c32);
+	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg, nullptr, nullptr, band, blists))) return rc;
 	const bool tm = ctx->timing;
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
 	if (lane_ok) {
 		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[0], ctx->stream));
-		if ((rc = launch_global_lane(ctx, 64, d_pool, d_tasks, n, d_res, d_cigar, lists, counts + 0, rows_cap))) return rc;
+		if (ctx->glb_c32 && (rc = launch_global_lane(ctx, 32, d_pool, d_tasks, n, d_res, d_cigar, lists + 5 * N, counts + 5, rows_cap,
+		                                             blists ? blists + 5 * N : nullptr)))
+			return rc;
+		if ((rc = launch_global_lane(ctx, 64, d_pool, d_tasks, n, d_res, d_cigar, lists, counts + 0, rows_cap, blists))) return rc;
 		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[1], ctx->stream));
 		// bands of 32..47 take the 96-slot instantiation (two waves per SIMD, three quarters of the slots), 48..63 the 128-slot one
-		if (wgate > 31 && (rc = launch_global_lane(ctx, 96, d_pool, d_tasks, n, d_res, d_cigar, lists + 3 * N, counts + 3, rows_cap)))
+		if (wgate > 31 && (rc = launch_global_lane(ctx, 96, d_pool, d_tasks, n, d_res, d_cigar, lists + 3 * N, counts + 3, rows_cap,
+		                                             blists ? blists + 3 * N : nullptr)))
 			return rc;
-		if (wgate > 47 && (rc = launch_global_lane(ctx, 128, d_pool, d_tasks, n, d_res, d_cigar, lists + N, counts + 1, rows_cap)))
+		if (wgate > 47 && (rc = launch_global_lane(ctx, 128, d_pool, d_tasks, n, d_res, d_cigar, lists + N, counts + 1, rows_cap,
+		                                             blists ? blists + N : nullptr)))
 			return rc;
 	}
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[2], ctx->stream));

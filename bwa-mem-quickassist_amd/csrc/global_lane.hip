@@ -41,6 +41,9 @@ __device__ __forceinline__ int sel3(int mask, int a, int b) { return __builtin_a
 #ifndef BMH_GL_WAVES64
 #define BMH_GL_WAVES64 3 /* round 3 (16-bit cell): 3 waves per SIMD hold the row loop without scratch traffic; 4 do not (100+ spills) */
 #endif
+#ifndef BMH_GL_WAVES32
+#define BMH_GL_WAVES32 4
+#endif
 #ifndef BMH_GL_WAVES128
 #define BMH_GL_WAVES128 2
 #endif
@@ -52,10 +55,10 @@ __device__ __forceinline__ int sel3(int mask, int a, int b) { return __builtin_a
 // SYM: o_del + e_del == o_ins + e_ins (bwa's defaults): m - oe is shared by the E and F updates.  A run-time test of that inside the cell was
 // compiled to a branch per cell.
 template <int C, bool FAST, bool SYM>
-__global__ __launch_bounds__(64, (C <= 64 ? BMH_GL_WAVES64 : C <= 96 ? BMH_GL_WAVES96 : BMH_GL_WAVES128)) void global_lane_kernel(
+__global__ __launch_bounds__(64, (C <= 32 ? BMH_GL_WAVES32 : C <= 64 ? BMH_GL_WAVES64 : C <= 96 ? BMH_GL_WAVES96 : BMH_GL_WAVES128)) void global_lane_kernel(
     const uint8_t *__restrict__ pool, const bmh_glb_task_t *__restrict__ tasks, const uint32_t *__restrict__ order,
-    const uint32_t *__restrict__ count, long long n, bmh_glb_result_t *__restrict__ out, uint32_t *__restrict__ cigar_pool,
-    DevParams P, uint32_t *__restrict__ zslab, int rows_cap, int *__restrict__ err_flag)
+    const uint8_t *__restrict__ band, const uint32_t *__restrict__ count, long long n, bmh_glb_result_t *__restrict__ out,
+    uint32_t *__restrict__ cigar_pool, DevParams P, uint32_t *__restrict__ zslab, int rows_cap, int *__restrict__ err_flag)
 {
 	constexpr int NW = (C + 31) / 32, NQ = C / 4, NB = C / 8;
 	__shared__ uint2 srow[8];
@@ -80,7 +83,8 @@ __global__ __launch_bounds__(64, (C <= 64 ? BMH_GL_WAVES64 : C <= 96 ? BMH_GL_WA
 		const uint4 ta = tp[0], tb = tp[1];
 		const uint64_t q_off = (uint64_t)ta.y << 32 | ta.x;
 		const int qlen = (int)(tb.x & 0xffff), tlen = (int)(tb.x >> 16);
-		const int w = (int)tb.y;
+		// the band the result needs (host/glbband_core.h), listed by the dispatcher beside order[]; without a list, the task's own
+		const int w = band ? (int)band[pos] : (int)tb.y;
 		const bool want = (int)tb.w > 0;
 		const bool bad = w < 0 || 2 * w + 2 > C || tlen > rows_cap;
 		if (valid && bad) {
@@ -357,10 +361,11 @@ __global__ __launch_bounds__(64, (C <= 64 ? BMH_GL_WAVES64 : C <= 96 ? BMH_GL_WA
 	}
 }
 
-// ---- launcher: tasks listed in d_order[0..*d_count) must have 2w+2 <= C and tlen <= rows_cap
+// ---- launcher: tasks listed in d_order[0..*d_count) must have 2w+2 <= C and tlen <= rows_cap; d_band (nullable): the band of
+// the task at each position of d_order, to be used in place of its w
 int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                        bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, const uint32_t *d_count,
-                       int rows_cap)
+                       int rows_cap, const uint8_t *d_band)
 {
 	if (n <= 0) return BMH_OK;
 	int ncu = 256;
@@ -369,7 +374,7 @@ int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb
 	// persistent grid = the waves that are resident at once: every wave owns a private direction slab for as long as it
 	// lives, so more blocks than that would only pin more HBM (2 048 waves x 170 rows x 8 blocks x 256 B = 0.7 GB at
 	// 150 bp; a grow-only workspace per context, and the preload shim keeps one context per host thread)
-	const long long resident = (long long)ncu * 4 * (c <= 64 ? BMH_GL_WAVES64 : c <= 96 ? BMH_GL_WAVES96 : BMH_GL_WAVES128);
+	const long long resident = (long long)ncu * 4 * (c <= 32 ? BMH_GL_WAVES32 : c <= 64 ? BMH_GL_WAVES64 : c <= 96 ? BMH_GL_WAVES96 : BMH_GL_WAVES128);
 	if (grid > resident) grid = resident;
 	// one slab serves both lane kernels of a launch (they run back to back on the stream): [block][row][lane] dwords of
 	// 8 cells, C/8 blocks per row
@@ -381,7 +386,7 @@ int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb
 	const size_t lds = (size_t)std::max(c, kStreamRows) * 64; // window staging (C/4 dwords per lane), then one byte per staged row and lane
 #define BMH_LAUNCH_GL2(CC, FF, SS)                                                                                             \
 	hipLaunchKernelGGL((global_lane_kernel<CC, FF, SS>), dim3((unsigned)grid), dim3(64), lds, ctx->stream, d_pool, d_tasks, d_order, \
-	                   d_count, (long long)n, d_res, d_cigar, ctx->dev, (uint32_t *)ctx->d_zslab.p, rows_cap, ctx->d_err)
+	                   d_band, d_count, (long long)n, d_res, d_cigar, ctx->dev, (uint32_t *)ctx->d_zslab.p, rows_cap, ctx->d_err)
 #define BMH_LAUNCH_GL(CC)                                                                                                      \
 	do {                                                                                                                       \
 		if (fast && sym) BMH_LAUNCH_GL2(CC, true, true);                                                                       \
@@ -389,7 +394,8 @@ int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb
 		else if (sym) BMH_LAUNCH_GL2(CC, false, true);                                                                         \
 		else BMH_LAUNCH_GL2(CC, false, false);                                                                                 \
 	} while (0)
-	if (c == 64) BMH_LAUNCH_GL(64);
+	if (c == 32) BMH_LAUNCH_GL(32);
+	else if (c == 64) BMH_LAUNCH_GL(64);
 	else if (c == 96) BMH_LAUNCH_GL(96);
 	else if (c == 128) BMH_LAUNCH_GL(128);
 	else return BMH_E_ARG;
