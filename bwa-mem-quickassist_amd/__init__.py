@@ -184,6 +184,7 @@ def lib():
         L.bmh_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_last_extend_bin_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_last_global_bin_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.bmh_last_global_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_last_seedext_round_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_extend_bin_ms_sum.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
         L.bmh_upload_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -374,6 +375,13 @@ class Context:
         ms = (C.c_float * 3)()
         self._check(lib().bmh_last_global_bin_ms(self._h, ms))
         return [float(x) for x in ms]
+
+    def last_global_bands(self, n):
+        """Diagnostic: the band the device computed for each of the n tasks of the most recent global launch, by input position
+        (uint8, 255 = wider than 254).  Raises when that launch ran no band pass or had another task count (bmh_last_global_bands)."""
+        bands = np.zeros(int(n), dtype=np.uint8)
+        self._check(lib().bmh_last_global_bands(self._h, _ptr(bands), int(n)))
+        return bands
 
     # ---- L2, host buffers
     def upload_pool(self, pool):

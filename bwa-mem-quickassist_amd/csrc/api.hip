@@ -353,9 +353,11 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 int bmh_ctx_set_params(bmh_ctx_t *ctx, const bmh_params_t *p)
 {
 	if (!ctx || !p) return BMH_E_ARG;
-	// e>=1: the reference divides by e (ksw.c:401,404); o_ins>=0: the scan form of F needs it
-	if (p->e_del < 1 || p->e_ins < 1 || p->o_ins < 0 || p->o_del < 0) {
-		ctx->last_error = "need e_del>=1, e_ins>=1, o_del>=0, o_ins>=0";
+	// o_ins>=0: the scan form of F needs it.  e>=1: the reference's extension divides by e (ksw.c:401,404); ksw_global2 does
+	// not, so a zero gap extension gives parameters that bmh_global_batch and bmh_global_batch_device alone take (glb_params without
+	// have_params: every other call finds the context as it is before the first bmh_ctx_set_params)
+	if (p->e_del < 0 || p->e_ins < 0 || p->o_ins < 0 || p->o_del < 0) {
+		ctx->last_error = "need e_del>=0, e_ins>=0, o_del>=0, o_ins>=0";
 		return BMH_E_RANGE;
 	}
 	ctx->params = *p;
@@ -373,7 +375,7 @@ int bmh_ctx_set_params(bmh_ctx_t *ctx, const bmh_params_t *p)
 	uint8_t bytes[28] = {0};
 	memcpy(bytes, p->mat, 25);
 	memcpy(d.matw, bytes, 28);
-	ctx->have_params = true;
+	ctx->have_params = p->e_del >= 1 && p->e_ins >= 1, ctx->glb_params = true;
 	return BMH_OK;
 }
 
@@ -586,6 +588,15 @@ int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3])
 	if (!ctx->ev_gbin_valid) return BMH_OK;
 	BMH_HIP(ctx, hipEventSynchronize(ctx->ev_gbin[3]));
 	for (int b = 0; b < 3; ++b) BMH_HIP(ctx, hipEventElapsedTime(&ms[b], ctx->ev_gbin[b], ctx->ev_gbin[b + 1]));
+	return BMH_OK;
+}
+
+int bmh_last_global_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n)
+{
+	if (!ctx || !bands || n <= 0 || n != ctx->gband_n || !ctx->d_gband.p) return BMH_E_ARG;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	BMH_HIP(ctx, hipMemcpy(bands, ctx->d_gband.p, (size_t)n, hipMemcpyDeviceToHost));
 	return BMH_OK;
 }
 
@@ -844,7 +855,7 @@ int bmh_global_batch_device(bmh_ctx_t *ctx, const uint8_t *d_pool, const bmh_glb
                             bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order)
 {
 	if (!ctx || n < 0 || (n > 0 && (!d_pool || !d_tasks || !d_res))) return BMH_E_ARG;
-	if (!ctx->have_params) return BMH_E_ARG;
+	if (!ctx->glb_params) return BMH_E_ARG;
 	if (n > 0xffffffffLL) return BMH_E_ARG;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	// no host view of the tasks: size for the context's capacity hint (square band-limited matrix); a capacity past the LDS
@@ -859,7 +870,7 @@ int bmh_global_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, con
                      bmh_glb_result_t *results, uint32_t *cigar_pool, size_t cigar_words)
 {
 	if (!ctx || n < 0 || (n > 0 && (!tasks || !results))) return BMH_E_ARG;
-	if (!ctx->have_params) return BMH_E_ARG;
+	if (!ctx->glb_params) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
 	if (n > 0xffffffffLL) return BMH_E_ARG;
 	if (!pool && !ctx->pool_resident) return BMH_E_ARG; // (null: the pool left on the device by bmh_upload_pool())
@@ -1156,6 +1167,7 @@ int bmh_ctx_reserve_device(bmh_ctx_t *ctx, size_t pool_bytes, int64_t max_tasks,
 	int rc;
 	const size_t N = (size_t)max_tasks;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	if (ctx->glb_narrow && (1 + (size_t)kSortBins) * N + 16 > ctx->d_gband.cap) ctx->gband_n = 0; // (growing drops the last launch's bands)
 	if ((rc = ensure(ctx, ctx->d_pool, pool_bytes + 16)) || (rc = ensure(ctx, ctx->d_tasks, N * 40 + 64)) || (rc = ensure(ctx, ctx->d_res, N * 32 + 64)) ||
 	    (rc = ensure(ctx, ctx->d_cigar, (cigar_words + 4) * 4)) ||
 	    (rc = ensure(ctx, ctx->d_bins, (16 + (size_t)kSortBins * kSortKeysHost + (N + 1) / 2 + 1 + (size_t)kSortBins * N) * 4)) ||

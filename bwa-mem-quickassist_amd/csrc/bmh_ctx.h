@@ -20,6 +20,7 @@ struct bmh_ctx {
 	int device = 0;
 	hipStream_t own_stream = nullptr, stream = nullptr;
 	bool have_params = false;
+	bool glb_params = false; // parameters are set, possibly with a zero gap extension: then have_params stays false and only the global calls run
 	bmh_params_t params{};
 	bmh::DevParams dev{};
 	int qcap = 512; // query-length capacity used to size the LDS kernel's window state for *_device calls
@@ -37,6 +38,7 @@ struct bmh_ctx {
 	int glb_narrow = 1; // lane kernels run each task on the band its result needs (host/glbband_core.h; env BMH_GLB_NARROW=0 turns it off)
 	int glb_c32 = 1;    // bands up to 15 run on the 32-slot instantiation, four waves per SIMD (env BMH_GLB_C32=0: on the 64-slot one)
 	DevBuf d_gband;     // ... those bands: n bytes by input position, then kSortBins x n bytes parallel to the sort's lists
+	int64_t gband_n = 0; // tasks of the last global launch if its band pass ran, else 0 (bmh_last_global_bands)
 	int sw_wave = 1;  // batches of up to 32 k tasks: one wave per task (sw_wave.hip); env BMH_SW_WAVE=0 turns it off
 	DevBuf d_bins; // per-launch bin lists of the extension dispatcher: 4 counters + 4 x n task indices
 	int grid_mult = 1;    // env BMH_GRID_MULT: persistent grid = resident waves x this (tuning knob)

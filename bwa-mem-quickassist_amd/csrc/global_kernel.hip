@@ -354,6 +354,7 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
                   bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, int qmax, int tmax,
                   int wmax, int wgate, const GlbLongShape *lg)
 {
+	ctx->gband_n = 0;
 	if (n <= 0) return BMH_OK;
 	int rc;
 	const size_t N = (size_t)n;
@@ -406,6 +407,7 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
 		const long long bg = std::min<long long>((n * kBandLanes + kBandThreads - 1) / kBandThreads, (long long)ctx->ncu * 8 * 4);
 		hipLaunchKernelGGL(glb_band_kernel, dim3((unsigned)bg), dim3(kBandThreads), 0, ctx->stream, d_pool, d_tasks, d_order, (long long)n,
 		                   band, ctx->dev, 1, rows_cap);
+		ctx->gband_n = n;
 	}
 	hipLaunchKernelGGL(glb_sort_hist_kernel, dim3((unsigned)cg), dim3(256), 0, ctx->stream, d_tasks, d_order, (long long)n, hist,
 	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap, longb ? kGlbLdsQcap : 65535, band, ctx->glb_c32);

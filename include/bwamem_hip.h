@@ -134,6 +134,9 @@ int bmh_device_count(int *n);
  * A context is used by one host thread at a time. */
 int bmh_ctx_create(bmh_ctx_t **ctx, int device);
 int bmh_ctx_destroy(bmh_ctx_t *ctx);
+/* Gap costs must not be negative (BMH_E_RANGE).  With e_del = 0 or e_ins = 0 the parameters serve bmh_global_batch and
+ * bmh_global_batch_device alone (ksw_global2 never divides by a gap extension; the reference's extension does, ksw.c:401,404):
+ * every other call then answers BMH_E_ARG, as on a context whose parameters were never set. */
 int bmh_ctx_set_params(bmh_ctx_t *ctx, const bmh_params_t *p);
 /* Run on a caller-owned hipStream_t (passed as void*); NULL restores the context's own. */
 int bmh_ctx_set_stream(bmh_ctx_t *ctx, void *hip_stream);
@@ -276,6 +279,13 @@ int bmh_extend_wide_stats(const bmh_ctx_t *ctx, int64_t *tasks, float *ms);
 /* Per-kernel duration of the last global-alignment launch: the 64-slot lane kernel (w <= 31), the 128-slot one (w <= 63),
  * the one-wave-per-task kernel (everything else).  -1 when timing was off. */
 int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3]);
+/* Diagnostic: the band the device computed for every task of the context's most recent global-alignment launch, in front of
+ * its sort (the lane kernels run each task on the band its result needs).  bands[k] belongs to the task at input position k --
+ * entry k of d_order where the launch had one, else task k; 255 stands for every band of 255 and more.  n must be that launch's task
+ * count.  BMH_E_ARG when it is not, or when the launch ran no band pass (BMH_GLB_NARROW=0, BMH_GLB_MODE=wave, nothing
+ * launched yet, or the workspace was grown since by bmh_ctx_reserve_device).  A call that makes several global launches leaves
+ * the last one's bands.  Waits for the stream and copies n bytes; the launches themselves do nothing for it. */
+int bmh_last_global_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n);
 /* What the global-alignment launches of this context so far sent to bin 4, the band-ring kernel (tasks with more than 10 176
  * query columns that no lane kernel takes): *tasks = their number, *ms = the ring kernel's time summed over the launches made
  * with timing on (-1 when timing is off).  The counterpart of bmh_extend_wide_stats.  Waits for the stream. */

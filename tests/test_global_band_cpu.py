@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import glbband_ref
 import kswgen
 import kswlib
 from __graft_entry__ import load_package
@@ -118,6 +119,11 @@ def cases(tmp_path_factory):
         sets.append((name + "/150bp", kw, 1, (g150[0], g150[1][:1500])))
         sets.append((name + "/low", kw, 1, (low[0], low[1][:1500])))
         sets.append((name + "/edges", kw, 1, (epool, etasks)))
+    # every pair of short sequences at every band, ties and zero costs included (glbband_ref.py): the sets the GPU test reads the bands of
+    small = (("A", glbband_ref.set_a()[:2]), ("B", glbband_ref.set_b()[:2]))
+    for name, kw in glbband_ref.SCORINGS.items():
+        for s, pt in small:
+            sets.append((f"small{s}/{name}", kw, 1, pt))
     # a matrix without a positive entry, and a negative gap cost: the rule must leave every w alone
     sets.append(("A<=0", dict(mat=np.minimum(kswlib.fill_scmat(1, 4), 0)), 0, (g150[0], g150[1][:300])))
     sets.append(("e<0", dict(e_del=-1), 0, (g150[0], g150[1][:300])))
@@ -161,6 +167,9 @@ def test_narrow_band_gives_the_oracles_result_and_the_rule_bites(cases, tmp_path
         _, n, applied, narrowed, _, _, c0, c1 = rows[name]
         assert applied == n and narrowed > n // 2 and c1 < c0, (name, rows[name])
     assert rows["mixed100-300"][3] > 200 and rows["low"][7] < rows["low"][6]
+    for name in glbband_ref.SCORINGS:  # the exhaustive sets: whole, the rule applied to all, and a good part narrowed (so compared with the oracle)
+        a, b = rows[f"smallA/{name}"], rows[f"smallB/{name}"]
+        assert a[1] == a[2] == 22732 and b[1] == b[2] == 6741 and 7000 < a[3] < 18000 and 1500 < b[3] < 5000, (name, a, b)
     for name in ("A<=0", "e<0"):
         assert rows[name][2] == 0 and rows[name][3] == 0 and rows[name][6] == rows[name][7], (name, rows[name])
     # the edges, value by value

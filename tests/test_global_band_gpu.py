@@ -8,9 +8,11 @@ import numpy as np
 import pytest
 
 import devcalls as dc
+import glbband_ref
 import kswgen
 import kswlib
 from __graft_entry__ import load_package
+from glbband_ref import w_eff  # the rule restated in Python
 from test_kernel_families_gpu import _ctx_with
 
 pytestmark = pytest.mark.gpu
@@ -18,28 +20,6 @@ pytestmark = pytest.mark.gpu
 
 def _tg():
     return importlib.import_module(load_package().__name__ + ".taskgen")
-
-
-def w_eff(p, q, t, w):
-    """The rule of host/glbband_core.h, restated (slowly) to say what the hand-made batch holds."""
-    mat = np.asarray(p["mat"], dtype=np.int64).reshape(5, 5)
-    od, ed, oi, ei = (int(p[k]) for k in ("o_del", "e_del", "o_ins", "e_ins"))
-    ql, tl, A = len(q), len(t), int(mat.max())
-    d = ql - tl
-    if w < abs(d) or ql < 1 or tl < 1 or A <= 0 or min(od, ed, oi, ei) < 0:
-        return w
-    q, t = np.minimum(q, 4).astype(np.int64), np.minimum(t, 4).astype(np.int64)
-    if d == 0:
-        lb = int(mat[t, q].sum())
-    elif d > 0:
-        s0, s1 = mat[t, q[:tl]], mat[t, q[d:]]
-        lb = int(s1.sum()) + max(0, int(np.cumsum(s0 - s1).max())) - (oi + ei * d)
-    else:
-        s0, s1 = mat[t[:ql], q], mat[t[-d:], q]
-        lb = int(s1.sum()) + max(0, int(np.cumsum(s0 - s1).max())) - (od + ed * -d)
-    K = A + ei + ed
-    xp, xm = A * ql - oi - od + ed * d - lb, A * tl - oi - od - ei * d - lb
-    return min(w, max(abs(d), xp // K if xp >= 0 else 0, xm // K if xm >= 0 else 0))
 
 
 def _both(pool, tasks, words, p=None):
@@ -126,7 +106,8 @@ def test_one_wave_with_every_corner_of_the_rule():
 
 
 def test_the_band_travels_with_the_position_in_a_sparse_order():
-    """bmh_global_batch_device with a permuted d_order of 3 000 entries over 10 000 records."""
+    """bmh_global_batch_device with a permuted d_order of 3 000 entries over 10 000 records: the results, and the bands the device
+    computed (bmh_last_global_bands), entry k of which belongs to tasks[order[k]]."""
     rng = np.random.default_rng(4712)
     p = kswlib.make_params()
     pool, tasks, words = _tg().generate_global(10000, "150bp", seed=940, wspread=32)
@@ -140,9 +121,17 @@ def test_the_band_travels_with_the_position_in_a_sparse_order():
     g.n = len(order)  # the launch covers the order's entries; the buffers hold all 10 000 records
     g.run(ctx)
     ctx.sync()
+    bands = ctx.last_global_bands(len(order))  # the device's bands, by position in the order
+    with pytest.raises(load_package().BmhError):
+        ctx.last_global_bands(len(tasks))  # (the launch had 3 000 tasks, not 10 000)
     g.n = len(tasks)
     res, cig = g.result()
     ctx.close()
+    rows_cap = min(int(tasks["qlen"].max()) + 2 * int(p["w"]) + 64, glbband_ref.ROWS_CAP)  # of a device-resident launch: from the capacity hint
+    expect = glbband_ref.expected_bands(p, pool, tasks[order], rows_cap)
+    bad = np.nonzero(bands != expect)[0]
+    assert len(bad) == 0, f"{len(bad)} bands differ from the rule; first at position {bad[0]}: device={bands[bad[0]]} rule={expect[bad[0]]}"
+    assert (expect != glbband_ref.expected_bands(p, pool, tasks[:len(order)], rows_cap)).sum() > 1000  # by task index it would be another list
     dc.assert_glb(res[order], cig, want[order], wcig, tasks[order], "sparse order: ")
     rest = np.setdiff1d(np.arange(len(tasks)), order)
     assert (res[rest].view(np.uint8) == res[rest].view(np.uint8)[0]).all(), "a record outside the order was written"

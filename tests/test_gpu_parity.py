@@ -85,8 +85,20 @@ def test_extend_rejects_out_of_range(ctx, pkg):
     with pytest.raises(pkg.BmhError) as e:
         ctx.extend_batch(pool, t)
     assert e.value.code == pkg.BMH_E_ARG
-    with pytest.raises(pkg.BmhError):
-        ctx.set_params(kswlib.make_params(e_ins=0))
+    with pytest.raises(pkg.BmhError) as e:
+        ctx.set_params(kswlib.make_params(e_ins=-1))
+    assert e.value.code == pkg.BMH_E_RANGE
+    # a zero gap extension: parameters for the global calls alone; the extension divides by it (ksw.c:401,404) and stays refused
+    t["q_off"] = 0
+    try:
+        for kw in (dict(e_ins=0), dict(e_del=0), dict(e_del=0, e_ins=0)):
+            ctx.set_params(kswlib.make_params(**kw))
+            with pytest.raises(pkg.BmhError) as e:
+                ctx.extend_batch(pool, t)
+            assert e.value.code == pkg.BMH_E_ARG
+    finally:
+        ctx.set_params(p)
+    assert len(ctx.extend_batch(pool, t)) == 1
 
 
 def test_extend_sharded_two_contexts_one_device(ctx, pkg):
