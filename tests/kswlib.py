@@ -584,6 +584,29 @@ def smem_opt(opt):
     return out
 
 
+# The seeding option sets the FM-index tests run: name -> (min_seed_len, split_len, split_width, start_width).  `fixture` is the
+# default of `bwa mem`; start_width 2 is what MEM_F_NO_EXACT sends; split_len 0 and split_width 0 turn re-seeding off by
+# two different tests of smem_next2 (bwamem.c:133); `eager` re-seeds from almost every match; start_width 3 is beyond
+# what mem_opt_t can express and is pinned through bwt_smem1 alone.
+SMEM_OPTION_SETS = {
+    "fixture": (19, 28, 10, 1),
+    "no_exact": (19, 28, 10, 2),
+    "short": (12, 20, 30, 2),
+    "split_off": (19, 0, 10, 1),
+    "width0": (19, 28, 0, 1),
+    "eager": (10, 12, 1000, 1),
+    "sw3": (19, 28, 10, 3),
+}
+
+
+def smem_option_set(name, emit=False):
+    """The bmh_smem_opt_t of a named set, with min_emit_len 0 or min_seed_len."""
+    o = np.zeros((), dtype=SMEM_OPT)
+    o["min_seed_len"], o["split_len"], o["split_width"], o["start_width"] = SMEM_OPTION_SETS[name]
+    o["min_emit_len"] = int(o["min_seed_len"]) if emit else 0
+    return o
+
+
 def orc_smem_calls(cb, opt, read):
     """OUR restatement of the bwt_smem1 call sequence of one read -> (SMEM_CALL[], SMEM_INTV[])."""
     lib = load_oracle()

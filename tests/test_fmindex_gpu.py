@@ -4,7 +4,7 @@ import pytest
 
 import kswgen
 import kswlib
-from test_fmindex_cpu import _same_calls
+from test_fmindex_cpu import _same_calls, option_matrix_reads_and_oracle
 from test_kernel_families_gpu import _ctx_with
 
 pytestmark = pytest.mark.gpu
@@ -166,4 +166,21 @@ def test_seed_batch_survives_an_overflowed_first_attempt(kernel, monkeypatch):
         for k in np.nonzero(look)[0]:
             x2 = int(gi["x2"][k])
             assert (pos[int(so[k]):int(so[k]) + x2] == wpos[int(wo[k]):int(wo[k]) + x2]).all()
+    ctx.close()
+
+
+@pytest.mark.parametrize("oname", list(kswlib.SMEM_OPTION_SETS))
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_smem_option_matrix_matches_oracle(kernel, oname, monkeypatch):
+    """Seeding options beyond the default set (start_width 2 and 3, re-seeding off by split_len 0 and by split_width 0, eager
+    re-seeding, a short min_seed_len), each with min_emit_len 0 and min_seed_len, both kernels, read by read."""
+    monkeypatch.setenv("BMH_SMEM_KERNEL", kernel)
+    cb, keep, raw, opt, reads, per, sa_k, sa_pos = kswlib.golden_fmindex()
+    more, want = option_matrix_reads_and_oracle()
+    ctx = _ctx_with({})
+    ctx.set_bwt(*raw)
+    for emit in (False, True):
+        got = ctx.smem_batch(kswlib.smem_option_set(oname, emit), more)
+        for r, (g, w) in enumerate(zip(got, want[oname, emit])):
+            assert _same_calls(g, w), f"{oname} emit {emit} read {r} (len {len(more[r])})"
     ctx.close()

@@ -10,34 +10,18 @@ import pytest
 import kswlib
 import periodic_index as pi
 import reflib
+import tinyindex
 
 NEED_REF = pytest.mark.skipif(not reflib.have_ref_bwa(), reason="oracle/_ref not built (no reference sources here)")
 
 
 def _brute(P, m):
-    """Suffix array, BWT rows and bwa's arrays of P^(2m)$ from a plain Python suffix sort and bwt_bwtupdate_core's loop."""
-    T = bytes(np.tile(P, 2 * m) + 1) + b"\0"
-    n = len(T) - 1
-    sa = sorted(range(n + 1), key=lambda i: T[i:])
-    primary = sa.index(0)
-    stream = [T[s - 1] - 1 for k, s in enumerate(sa) if k != primary]  # row 0 is the $ suffix: its symbol is T[n-1]
-    L2 = [0]
-    for c in range(4):
-        L2.append(L2[-1] + stream.count(c))
-    words, cnt = [], [0, 0, 0, 0]
-    for i in range(n):
-        if i % 128 == 0:
-            for c in range(4):
-                words += [cnt[c] & 0xffffffff, cnt[c] >> 32]
-        if i % 16 == 0:
-            words.append(0)
-        words[-1] |= stream[i] << (30 - 2 * (i % 16))
-        cnt[stream[i]] += 1
-    for c in range(4):
-        words += [cnt[c] & 0xffffffff, cnt[c] >> 32]
-    samp = [sa[k] for k in range(0, n + 1, 32)]
-    samp[0] = 0xffffffffffffffff
-    return sa, primary, L2, np.array(words, np.uint32), np.array(samp, np.uint64)
+    """Suffix array, BWT rows and bwa's arrays of P^(2m)$ from tests/tinyindex.py's plain suffix sort: P is its own reverse
+    complement, so P^(2m) is the doubled text of the forward genome P^m."""
+    assert (np.asarray(P) == 3 - np.asarray(P)[::-1]).all()
+    (primary, L2, n, words, sa_intv, samp), sa = tinyindex.build(np.tile(P, m))
+    assert n == 2 * m * len(P) and sa_intv == 32
+    return sa, primary, L2, words, samp
 
 
 @pytest.mark.parametrize("chunk", [1, 3, 1 << 18])
