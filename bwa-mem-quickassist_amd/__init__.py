@@ -75,6 +75,8 @@ PAIRDEC = np.dtype([("paired", "<i4"), ("z", "<i4", (2,)), ("q_se", "<i4", (2,))
 WANTED_RES = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("n_cigar", "<i4"), ("NM", "<i4"),
                        ("tries", "<i4"), ("cigar_off", "<u4"), ("md_off", "<u4"), ("md_len", "<u4"), ("flags", "<u4"), ("band", "<i4", (3,)),
                        ("rsv", "<i4")])  # bmh_wanted_res_t, 72 bytes
+PHASE2_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i8"), ("redone", "<i8"), ("fallbacks", "<i8"), ("h2d_bytes", "<i8"),
+                         ("d2h_bytes", "<i8"), ("waits", "<i4"), ("sessions", "<i4"), ("decide_ms", "<f4"), ("wanted_ms", "<f4")])  # bmh_phase2_stats_t, 72 bytes
 WANTED_MOVED, WANTED_HOST = 4, 8
 ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
                    ("truesc", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"),
@@ -232,6 +234,10 @@ def lib():
         L.bmh_wanted_cigar_device.argtypes = L.bmh_wanted_cigar_batch.argtypes
         L.bmh_ctx_set_refidx.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_ctx_set_wanted_device.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_phase2_device.argtypes = ([C.c_void_p] * 5 + [C.c_int64, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t])
+        L.bmh_ctx_set_phase2_device.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_last_phase2_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -889,6 +895,57 @@ class Context:
         self._check(fn(self._h, C.byref(refidx), _ptr(pac), int(w), n, C.cast(c_reads, C.c_void_p), C.cast(c_regs, C.c_void_p), _ptr(roff),
                        _ptr(n_want), _ptr(want_k), _ptr(res), _ptr(cig), C.c_size_t(len(cig)), _ptr(md), C.c_size_t(len(md))))
         return res, cig, md
+
+    def phase2_device(self, opt, refidx, pac, pes, id0, reads, vectors, inplace=False, out=None, results_cap=None):
+        """bmh_phase2_device: pass A and pass B of phase 2 as one device session.  opt: SAM_OPT (w = opt.w); reads: uint8 code arrays;
+        vectors: per read an ALNREG array (left as it is, or with inplace=True worked on where it lies).  Returns decide_batch()'s dict
+        with res (WANTED_RES records, n_wanted of them), cig, md and n_wanted added.  out: arrays to write into by name (pd, reg_mapq,
+        n_want, want_k, res, cig, md: a test's sentinels); results_cap: the capacity to state for res, else its length."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        n = len(reads)
+        o = np.array(opt, dtype=SAM_OPT).reshape(1)
+        bufs = list(vectors) if inplace else [np.array(v, dtype=ALNREG, copy=True).reshape(-1) for v in vectors]
+        keep = []
+        c_reads = (_Read * max(n, 1))()
+        c_regs = (_AlnregV * max(n, 1))()
+        for r, (seq, a) in enumerate(zip(reads, bufs)):
+            assert a.dtype == ALNREG and a.flags.c_contiguous
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            keep.append(seq)
+            c_reads[r].l_seq, c_reads[r].seq = len(seq), seq.ctypes.data
+            c_regs[r].n = c_regs[r].m = len(a)
+            c_regs[r].a = a.ctypes.data if len(a) else None
+        roff = np.concatenate([[0], np.cumsum([len(a) for a in bufs])]).astype(np.int64)
+        total = int(roff[-1])
+        span = sum(max(int(x["qe"]) - int(x["qb"]), 0) + max(int(x["re"]) - int(x["rb"]), 0) for a in bufs for x in a)
+        pe = bool(int(o["flag"][0]) & MEM_F_PE)
+        out = dict(out or {})
+        got = {"pd": np.zeros(n // 2 if pe else 0, dtype=PAIRDEC), "reg_mapq": np.full(total, -1, dtype=np.int32),
+               "want_k": np.full(total, -1, dtype=np.int32), "n_want": np.full(n, -1, dtype=np.int32), "res": np.zeros(total, dtype=WANTED_RES),
+               "cig": np.zeros(span + 2 * total + 8, dtype=np.uint32), "md": np.zeros(3 * span + 16 * total + 16, dtype=np.uint8)}
+        got.update(out)
+        n_wanted = C.c_int64(-1)
+        pes_p = _ptr(np.ascontiguousarray(pes, dtype=PESTAT)) if pes is not None else None
+        rc = lib().bmh_phase2_device(self._h, _ptr(o), C.byref(refidx), _ptr(pac), pes_p, C.c_int64(int(id0)), n, C.cast(c_reads, C.c_void_p),
+                                     C.cast(c_regs, C.c_void_p), _ptr(roff), _ptr(got["pd"]) if pe else None, _ptr(got["reg_mapq"]), _ptr(got["n_want"]),
+                                     _ptr(got["want_k"]), _ptr(got["res"]), C.c_int64(len(got["res"]) if results_cap is None else int(results_cap)),
+                                     C.cast(C.byref(n_wanted), C.c_void_p), _ptr(got["cig"]), C.c_size_t(len(got["cig"])), _ptr(got["md"]),
+                                     C.c_size_t(len(got["md"])))
+        self._check(rc)
+        got["regs"], got["n_wanted"] = bufs, n_wanted.value
+        got["res"] = got["res"][:n_wanted.value]
+        got["want"] = [got["want_k"][int(roff[i]):int(roff[i]) + int(got["n_want"][i])].copy() for i in range(n)]
+        return got
+
+    def set_phase2_device(self, on=True):
+        """bmh_ctx_set_phase2_device: while on, bmh_sam_batch takes pass A and pass B from bmh_phase2_device."""
+        self._check(lib().bmh_ctx_set_phase2_device(self._h, 1 if on else 0))
+
+    def last_phase2_stats(self):
+        """bmh_last_phase2_stats as a dict of PHASE2_STATS' fields: the last fused call on this context."""
+        st = np.zeros(1, dtype=PHASE2_STATS)
+        self._check(lib().bmh_last_phase2_stats(self._h, _ptr(st)))
+        return {k: st[0][k].item() for k in PHASE2_STATS.names}
 
     def reg2cigar_batch(self, l_pac, pac, reads, reqs):
         """Batched mem_reg2aln band/retry loop over bwa_gen_cigar2 (reference bwamem.c:1187-1201, bwa.c:89-172).

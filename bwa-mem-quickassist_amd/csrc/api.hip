@@ -91,6 +91,7 @@ struct Stager {
 	bmh_ctx *ctx;
 	bool wide; // an extension batch: end() adds what the int32 kernel received to ctx->wide_total
 	bool up = false, down = false;
+	bool p2 = false; // the fused phase 2 session: bytes and waits go to ctx->p2 (bmh_last_phase2_stats)
 	size_t up_used = 0, down_used = 0;
 	struct Pending {
 		void *dst;
@@ -113,6 +114,7 @@ struct Stager {
 			memcpy(h, src, bytes);
 			up_used += (bytes + 63) & ~(size_t)63, src = h;
 		}
+		if (p2) ctx->p2.h2d_bytes += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
 		return BMH_OK;
 	}
@@ -124,6 +126,7 @@ struct Stager {
 			pend[n_pend++] = Pending{dst, down_used, bytes};
 			down_used += (bytes + 63) & ~(size_t)63;
 		}
+		if (p2) ctx->p2.d2h_bytes += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(to, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
 		return BMH_OK;
 	}
@@ -132,6 +135,7 @@ struct Stager {
 	// the caller and count the int32 kernel's tasks.  Returns rc, else the device's verdict.
 	int end(int rc)
 	{
+		if (p2) ++ctx->p2.waits;
 		if (rc) { // (the flag's text must not replace why the call failed)
 			std::string why = std::move(ctx->last_error);
 			(void)fetch_err(ctx);
@@ -1285,27 +1289,18 @@ int bmh_last_dedup_stats(const bmh_ctx_t *ctx, int64_t *regions_in, int64_t *reg
 void bmh_pp_fill_log_(double *logk, int64_t k0, int64_t k1);
 void bmh_pp_fill_term_(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const int64_t term_off[4], double *term);
 
-int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs,
-                      const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k)
+// What the tables of a pass A on the device must reach (bwamem_hip.h), before anything is uploaded: BMH_E_RANGE and *why where one
+// would pass 2^20 entries or an index is negative
+static int decide_table_sizes(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, int n, const bmh_alnreg_v *regs, long long *kmax_, long long *n_term_,
+                              int64_t term_off[4], const char **why)
 {
 	constexpr long long kTabMax = 1LL << 20;
-	if (!ctx) return BMH_E_ARG;
-	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
-	if (rc) return rc;
-	if (n == 0) {
-		ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
-		return BMH_OK;
-	}
 	const bool pe = (o->flag & BMH_MEM_F_PE) != 0, pairing = pe && !(o->flag & BMH_MEM_F_NOPAIRING);
-	const size_t total = (size_t)roff[n];
-	// what the tables must reach (bwamem_hip.h), before anything is uploaded
-	auto refuse = [&](const char *why) {
-		ctx->last_error = why;
-		ctx->decide_units = 0, ctx->decide_fallbacks = 1, ctx->decide_ms = -1.f;
+	long long kmax = 1, n_term = 0;
+	auto refuse = [&](const char *w) {
+		*why = w;
 		return BMH_E_RANGE;
 	};
-	long long kmax = 1, n_term = 0;
-	int64_t term_off[4] = {0, 0, 0, 0};
 	for (int i = 0; i < n; ++i) {
 		const long long nv = (long long)regs[i].n;
 		for (long long j = 0; j < nv; ++j) {
@@ -1329,7 +1324,13 @@ int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, con
 			term_off[d] = n_term, n_term += bmh_pp_term_len(&pes[d]);
 			if (n_term > kTabMax) return refuse("bmh_decide_device: the pair table would pass 2^20 entries");
 		}
-	// the log table: resident, grown in powers of two
+	*kmax_ = kmax, *n_term_ = n_term;
+	return BMH_OK;
+}
+
+// the host's copy of the log table up to kmax, grown in powers of two; *want_log = the entries the device's copy must have
+static int decide_host_log(bmh_ctx *ctx, long long kmax, long long *want_log_)
+{
 	long long want_log = ctx->logk_n;
 	if (kmax + 1 > ctx->logk_n) {
 		for (want_log = 1 << 17; want_log < kmax + 1; want_log <<= 1) {}
@@ -1343,6 +1344,33 @@ int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, con
 			ctx->h_logk = t, ctx->logk_host_n = want_log;
 		}
 	}
+	*want_log_ = want_log;
+	return BMH_OK;
+}
+
+int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs,
+                      const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k)
+{
+	if (!ctx) return BMH_E_ARG;
+	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	if (rc) return rc;
+	if (n == 0) {
+		ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+		return BMH_OK;
+	}
+	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
+	const size_t total = (size_t)roff[n];
+	// what the tables must reach (bwamem_hip.h), before anything is uploaded
+	auto refuse = [&](const char *why) {
+		ctx->last_error = why;
+		ctx->decide_units = 0, ctx->decide_fallbacks = 1, ctx->decide_ms = -1.f;
+		return BMH_E_RANGE;
+	};
+	long long kmax = 1, n_term = 0, want_log = 0;
+	int64_t term_off[4] = {0, 0, 0, 0};
+	const char *why = nullptr;
+	if (decide_table_sizes(o, pes, n, regs, &kmax, &n_term, term_off, &why)) return refuse(why);
+	if ((rc = decide_host_log(ctx, kmax, &want_log))) return rc;
 	// the device block: [offsets | opt + pes | pair table | regions] up, [regions | reg_mapq | want_k | n_want | pd] down (the regions
 	// come last in the upload so that the download is one copy), then the two scratch arrays
 	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
@@ -1432,6 +1460,7 @@ __attribute__((visibility("hidden"))) void bmh_decide_stats_reset_(bmh_ctx_t *ct
 {
 	if (ctx && ctx->decide_device) ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
 	if (ctx && ctx->wanted_device) ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
+	if (ctx && ctx->phase2_device) ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
 }
 
 // bmh_sam_batch's pass A (host/sam_post.c; not part of the interface)
@@ -1485,6 +1514,41 @@ int bmh_ctx_set_refidx(bmh_ctx_t *ctx, const bmh_refidx_t *bns)
 
 // bytes of MD coming back per region (BMH_RP_MD_SLOT, host/regplan_core.h); round 0's MD is not read
 enum { kWantMdSlot = BMH_RP_MD_SLOT, kWantFixMdSlot = 4 };
+
+// one round of the region kernels over what a status record describes (the two device forms of pass B)
+static int wanted_run_round(bmh_ctx *ctx, const WantedArgs &A, const WantedStatus &s, int r, uint8_t *d_pool, size_t rpool_off, bmh_region_res_t *res,
+                            uint32_t *cig, char *md, int md_cap)
+{
+	int e2;
+	if (s.n_rec <= 0) return BMH_OK;
+	GlbLongShape lg;
+	lg.qmax = s.lqmax, lg.tmax = s.ltmax, lg.wmax = s.lwmax, lg.n = s.ln;
+	if ((e2 = launch_region_orient(ctx, d_pool, rpool_off, A.req[r], s.n_rec))) return e2;
+	if (s.n_tasks > 0 && (e2 = launch_global(ctx, d_pool, A.task[r], s.n_tasks, (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr,
+	                                         std::max(s.qmax, 1), std::max(s.tmax, 1), s.wmax, s.wraw, &lg)))
+		return e2;
+	return launch_region_finish(ctx, d_pool, A.req[r], s.n_rec, A.task[r], (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p, res, cig,
+	                            BMH_RP_SMALL_CAP, md, md_cap);
+}
+
+// the status records: the only thing the host reads between launches.  The wanted regions are n_lo..n_hi: the count where the host
+// knows it, 0..the capacity where pass A left the want list on the device.  st: the fused session's Stager, which counts the read.
+static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, Stager *st)
+{
+	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
+	BMH_HIP(ctx, hipMemcpyAsync(ctx->h_wstat, d_stat, 2 * sizeof(WantedStatus), hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	if (st && st->p2) ++ctx->p2.waits, ctx->p2.d2h_bytes += (int64_t)(2 * sizeof(WantedStatus));
+	if (hs[0].err || hs[1].err) {
+		ctx->last_error = "bmh_wanted_cigar_device: a wanted region is outside its read, its vector or the reference, or nothing is left of it";
+		return hs[0].err ? hs[0].err : hs[1].err;
+	}
+	if (hs[0].n_w < n_lo || hs[0].n_w > n_hi || hs[1].n_rec > hs[0].n_w || hs[0].n_rec > hs[0].n_w) { // cannot happen
+		ctx->last_error = "bmh_wanted_cigar_device: the device's counts are inconsistent";
+		return BMH_E_ARG;
+	}
+	return BMH_OK;
+}
 
 // the device form up to its own records and pools (*cig_ / *md_: malloc'd, the caller frees them), for the public call and bmh_sam_batch
 static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
@@ -1595,34 +1659,10 @@ static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_
 		A.task[0] = (bmh_glb_task_t *)ctx->d_tasks.p, A.task[1] = A.task[0] + wc;
 		A.fix_res = (const bmh_region_res_t *)(d + o_res0), A.fix_cig = (const uint32_t *)(d + o_cig0);
 		A.status = (WantedStatus *)(d + o_stat), A.w_cap = wc, A.opool_cap = opool_cap, A.err = ctx->d_err;
-		// one round of the region kernels over what a status record describes
-		auto run_round = [&](int r, size_t o_res, size_t o_cig, size_t o_md, int md_cap) -> int {
-			const WantedStatus &s = hs[r];
-			int e2;
-			if (s.n_rec <= 0) return BMH_OK;
-			GlbLongShape lg;
-			lg.qmax = s.lqmax, lg.tmax = s.ltmax, lg.wmax = s.lwmax, lg.n = s.ln;
-			if ((e2 = launch_region_orient(ctx, d_pool, rpool_off, A.req[r], s.n_rec))) return e2;
-			if (s.n_tasks > 0 && (e2 = launch_global(ctx, d_pool, A.task[r], s.n_tasks, (bmh_glb_result_t *)ctx->d_res.p, (uint32_t *)ctx->d_cigar.p, nullptr,
-			                                         std::max(s.qmax, 1), std::max(s.tmax, 1), s.wmax, s.wraw, &lg)))
-				return e2;
-			return launch_region_finish(ctx, d_pool, A.req[r], s.n_rec, A.task[r], (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p,
-			                            (bmh_region_res_t *)(d + o_res), (uint32_t *)(d + o_cig), BMH_RP_SMALL_CAP, (char *)(d + o_md), md_cap);
+		auto run_round = [&](int r, size_t o_res, size_t o_cig, size_t o_md, int md_cap) {
+			return wanted_run_round(ctx, A, hs[r], r, d_pool, rpool_off, (bmh_region_res_t *)(d + o_res), (uint32_t *)(d + o_cig), (char *)(d + o_md), md_cap);
 		};
-		// the status records: the only thing the host reads between launches
-		auto read_status = [&]() -> int {
-			BMH_HIP(ctx, hipMemcpyAsync(ctx->h_wstat, d + o_stat, 2 * sizeof(WantedStatus), hipMemcpyDeviceToHost, ctx->stream));
-			BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-			if (hs[0].err || hs[1].err) {
-				ctx->last_error = "bmh_wanted_cigar_device: a wanted region is outside its read, its vector or the reference, or nothing is left of it";
-				return hs[0].err ? hs[0].err : hs[1].err;
-			}
-			if (hs[0].n_w != n_w || hs[1].n_rec > n_w || hs[0].n_rec > n_w) { // cannot happen
-				ctx->last_error = "bmh_wanted_cigar_device: the device's counts are inconsistent";
-				return BMH_E_ARG;
-			}
-			return BMH_OK;
-		};
+		auto read_status = [&]() { return wanted_read_status(ctx, d + o_stat, n_w, n_w, nullptr); };
 		if ((e = launch_wanted_begin(ctx, A)) || (e = read_status())) return e;
 		if ((e = run_round(0, o_res0, o_cig0, o_md0, kWantFixMdSlot))) return e;
 		if ((e = launch_wanted_main(ctx, A)) || (e = read_status())) return e;
@@ -1764,6 +1804,380 @@ __attribute__((visibility("hidden"))) int bmh_wanted_routed_(bmh_ctx_t *ctx, con
 		return wanted_device_run(ctx, bns, pac, w, n, reads, regs, roff, n_want, want_k, n_w, wr, cig, md);
 	}
 	return bmh_wanted_host_(ctx, bns, pac, w, n, reads, regs, roff, n_want, want_k, n_w, 0, wr, cig, md, nullptr);
+}
+
+// ------------------------------------------------------------------ pass A and pass B of phase 2 as one device session
+
+// what bmh_wanted_check_args_ refuses without reading the want list (the vectors and offsets are bmh_pp_check_args's already)
+static int phase2_check_reads(const bmh_refidx_t *bns, const uint8_t *pac, int n, const bmh_read_t *reads)
+{
+	if (!bns || !pac || bns->l_pac <= 0 || bns->n_seqs <= 0 || !bns->anns || (n > 0 && !reads)) return BMH_E_ARG;
+	for (int i = 0; i < n; ++i)
+		if (reads[i].l_seq < 0 || (reads[i].l_seq > 0 && !reads[i].seq)) return BMH_E_ARG;
+	return BMH_OK;
+}
+
+// what a fused session holds on the host until everything has succeeded: nothing of the caller's is written before phase2_commit
+struct Phase2Run {
+	std::vector<uint8_t> down;        // pass A's block as downloaded: [regions | reg_mapq | want_k | n_want | pd], the regions sorted
+	size_t o_mq = 0, o_wk = 0, o_nw = 0, o_pd = 0;
+	int64_t n_w = 0;
+	std::vector<bmh_wanted_res_t> wr; // want order; cigar_off / md_off address cig / md
+	uint32_t *cig = nullptr;
+	char *md = nullptr;
+	~Phase2Run() { free(cig), free(md); }
+};
+
+static void phase2_commit(const Phase2Run &R, bool pe, int n, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq,
+                          int32_t *n_want, int32_t *want_k)
+{
+	const uint8_t *down = R.down.data();
+	const size_t nr = (size_t)n, total = (size_t)roff[n];
+	const int32_t *nw = (const int32_t *)(down + R.o_nw), *wk = (const int32_t *)(down + R.o_wk);
+	for (int i = 0; i < n; ++i)
+		if (regs[i].n) memcpy(regs[i].a, down + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].n * sizeof(bmh_alnreg_t));
+	memcpy(reg_mapq, down + R.o_mq, total * 4), memcpy(n_want, nw, nr * 4);
+	for (int i = 0; i < n; ++i) // (entries of want_k past a read's n_want stay the caller's)
+		if (nw[i]) memcpy(want_k + roff[i], wk + roff[i], (size_t)nw[i] * 4);
+	if (pe) memcpy(pd, down + R.o_pd, (nr >> 1) * sizeof(bmh_pairdec_t));
+}
+
+// The session up to its own records and pools, for the public call and bmh_sam_batch.  n > 0 and the arguments checked.  *tables: the
+// BMH_E_RANGE is bmh_decide_device's refusal before any upload, not a kernel's.
+static int phase2_device_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                             const bmh_read_t *reads, const bmh_alnreg_v *regs, const int64_t *roff, Phase2Run &R, bool *tables)
+{
+	*tables = false;
+	ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+	ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+	ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
+	if (!ctx->have_params) return BMH_E_ARG;
+	if (!ctx->dev.pac || ctx->h_pac != pac || ctx->dev.l_pac != bns->l_pac) {
+		ctx->last_error = "bmh_phase2_device needs the resident reference (bmh_ctx_set_pac)";
+		return BMH_E_ARG;
+	}
+	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
+		ctx->last_error = "bmh_phase2_device needs the resident sequence table (bmh_ctx_set_refidx)";
+		return BMH_E_ARG;
+	}
+	if (n > (1 << 28) || roff[n] > (1 << 28)) return BMH_E_ARG;
+	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
+	const int64_t l_pac = bns->l_pac;
+	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = total; // wc: the capacity of everything per wanted region, which bounds their number
+	long long kmax = 1, n_term = 0, want_log = 0;
+	int64_t term_off[4] = {0, 0, 0, 0};
+	const char *why = nullptr;
+	int rc;
+	if (decide_table_sizes(o, pes, n, regs, &kmax, &n_term, term_off, &why)) {
+		ctx->last_error = why;
+		ctx->decide_fallbacks = 1, ctx->p2.fallbacks = 1, *tables = true;
+		return BMH_E_RANGE;
+	}
+	if ((rc = decide_host_log(ctx, kmax, &want_log))) return rc;
+	// the oriented pool from the clamped lengths of every region: a sum the sort does not change, and a cut only shortens a region
+	size_t reads_bytes = 0, opool_cap = 0;
+	for (int i = 0; i < n; ++i) {
+		reads_bytes += (size_t)reads[i].l_seq;
+		for (size_t k = 0; k < regs[i].n; ++k) {
+			const bmh_alnreg_t *a = &regs[i].a[k];
+			opool_cap += (size_t)std::clamp<int64_t>((int64_t)a->qe - a->qb, 0, 65535) + (size_t)std::clamp<int64_t>(a->re - a->rb, 0, 65535);
+		}
+	}
+	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+	// pass A's block with pass B's inputs in it: [offsets | opt + pes | read offsets | WantedHdr | pair table | regions] up,
+	// [regions | reg_mapq | want_k | n_want | pd] down, then decide_kernel's two scratch arrays
+	const size_t o_hdr = al((nr + 1) * 8), o_soff = o_hdr + al(sizeof(DecideHdr)), o_whdr = o_soff + al((nr + 1) * 8), o_term = o_whdr + al(sizeof(WantedHdr));
+	const size_t o_reg = o_term + al((size_t)n_term * 8), o_mq = o_reg + al(total * sizeof(bmh_alnreg_t)), o_wk = o_mq + al(total * 4), o_nw = o_wk + al(total * 4);
+	const size_t o_pd = o_nw + al(nr * 4), o_z = o_pd + al(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0), o_v = o_z + al(total * 4);
+	const size_t o_endA = o_v + al(pe ? total * sizeof(bmh_pair64_t) : 0), b_up = o_mq, b_down = o_z - o_reg;
+	// pass B's block: work arrays, then what comes down
+	size_t at = 0;
+	auto take = [&](size_t bytes) {
+		const size_t o_ = at;
+		at += al(bytes);
+		return o_;
+	};
+	const size_t o_first = take((nr + 1) * 8), o_rec = take(wc * sizeof(WantRec));
+	size_t o_key[4], o_sum[4];
+	for (int c = 0; c < 4; ++c) o_key[c] = take(wc * 4);
+	for (int c = 0; c < 4; ++c) o_sum[c] = take(wc * 8);
+	const size_t o_req0 = take(wc * sizeof(bmh_region_req_t)), o_req1 = take(wc * sizeof(bmh_region_req_t)), o_stat = take(2 * sizeof(WantedStatus));
+	const size_t o_res0 = take(wc * sizeof(bmh_region_res_t)), o_cig0 = take(wc * BMH_RP_SMALL_CAP * 4), o_md0 = take(wc * kWantFixMdSlot);
+	const size_t o_res1 = take(wc * sizeof(bmh_region_res_t)), o_wres = take(wc * sizeof(bmh_wanted_res_t)), o_cig1 = take(wc * BMH_RP_SMALL_CAP * 4);
+	const size_t o_md1 = take(wc * kWantMdSlot), o_endB = at;
+	uint8_t *up = (uint8_t *)malloc(b_up), *rpool = (uint8_t *)malloc(reads_bytes + 16);
+	struct Free {
+		void *a, *b;
+		~Free() { free(a), free(b); }
+	} guard{up, rpool};
+	if (!up || !rpool) {
+		ctx->last_error = "bmh_phase2_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	R.down.resize(b_down);
+	R.o_mq = o_mq - o_reg, R.o_wk = o_wk - o_reg, R.o_nw = o_nw - o_reg, R.o_pd = o_pd - o_reg;
+	memcpy(up, roff, (nr + 1) * 8);
+	DecideHdr *hdr = (DecideHdr *)(up + o_hdr);
+	memset(hdr, 0, sizeof(*hdr));
+	hdr->opt = *o;
+	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
+	{
+		uint64_t *so = (uint64_t *)(up + o_soff);
+		size_t b = 0;
+		for (int i = 0; i < n; ++i) {
+			so[i] = b;
+			if (reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
+			b += (size_t)reads[i].l_seq;
+		}
+		so[n] = b;
+		memset(rpool + b, 0, 16);
+	}
+	WantedHdr *whdr = (WantedHdr *)(up + o_whdr);
+	const bmh_params_t &p = ctx->params;
+	memset(whdr, 0, sizeof(*whdr));
+	whdr->opt = bmh_rp_opt_t{p.a, p.mat[0], p.o_del, p.e_del, p.o_ins, p.e_ins, p.w};
+	whdr->fix_w = o->w;
+	if (n_term) bmh_pp_fill_term_(o, pes, term_off, (double *)(up + o_term));
+	for (int i = 0; i < n; ++i)
+		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+	std::vector<uint8_t> cigdown, mddown;
+	int64_t n_w = 0, n_rec1 = 0, n_fix = 0;
+	{ // the device section, inside the caller's gate (the redo below enters it again through the host form)
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	if (!ctx->h_wstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_wstat, 2 * sizeof(WantedStatus), hipHostMallocDefault));
+	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
+	Stager st(ctx);
+	st.p2 = true;
+	rc = [&]() -> int {
+		int e;
+		const bool grow = want_log > ctx->logk_n;
+		if (grow) ctx->logk_n = 0; // (ensure may drop the old table)
+		if ((e = ensure(ctx, ctx->d_decide, o_endA)) || (e = ensure(ctx, ctx->d_logk, (size_t)std::max(want_log, 1LL) * 8))) return e;
+		// device pool = [oriented copies | the reads as uploaded], as bmh_region_cigar_batch lays it out
+		const size_t rpool_off = (opool_cap + 16 + 63) & ~(size_t)63;
+		ctx->pool_resident = false;
+		if ((e = ensure(ctx, ctx->d_pool, rpool_off + reads_bytes + 16))) return e;
+		if (wc) {
+			if ((e = ensure(ctx, ctx->d_tasks, 4 * wc * sizeof(bmh_glb_task_t))) || (e = ensure(ctx, ctx->d_res, 3 * wc * sizeof(bmh_glb_result_t)))) return e;
+			if ((e = ensure(ctx, ctx->d_cigar, (3 * wc * BMH_RP_SMALL_CAP + 4) * 4)) || (e = ensure(ctx, ctx->d_wanted, o_endB))) return e;
+		}
+		if ((e = st.stage(b_up + reads_bytes + (grow ? (size_t)want_log * 8 + 64 : 0) + 256, b_down + (o_endB - o_wres) + 256))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_decide.p, *dw = (uint8_t *)ctx->d_wanted.p, *d_pool = (uint8_t *)ctx->d_pool.p;
+		if (grow && (e = st.h2d(ctx->d_logk.p, ctx->h_logk, (size_t)want_log * 8))) return e;
+		if ((e = st.h2d(d, up, b_up)) || (e = st.h2d(d_pool + rpool_off, rpool, reads_bytes + 16))) return e;
+		BMH_HIP(ctx, hipMemsetAsync(d + o_nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
+		DecideArgs D{};
+		D.roff = (const unsigned long long *)d, D.hdr = (const DecideHdr *)(d + o_hdr);
+		D.tab.logk = (const double *)ctx->d_logk.p, D.tab.term = (const double *)(d + o_term);
+		memcpy(D.tab.term_off, term_off, sizeof(term_off));
+		D.tab.n_log = want_log, D.tab.n_term = n_term;
+		D.reg = (bmh_alnreg_t *)(d + o_reg), D.total = total;
+		D.reg_mapq = (int32_t *)(d + o_mq), D.want_k = (int32_t *)(d + o_wk), D.n_want = (int32_t *)(d + o_nw), D.pd = (bmh_pairdec_t *)(d + o_pd);
+		D.z = (int *)(d + o_z), D.v = (bmh_pair64_t *)(d + o_v);
+		D.l_pac = l_pac, D.id0 = id0, D.n = n, D.pe = pe, D.err = ctx->d_err;
+		if ((e = launch_decide(ctx, D))) return e;
+		if (wc == 0) return st.d2h(R.down.data(), d + o_reg, b_down); // no region at all: pass A's verdicts alone
+		// pass B reads n_want, want_k and the sorted regions where decide_kernel left them: no wait, no copy in between
+		BMH_HIP(ctx, hipMemsetAsync(dw + o_stat, 0, 2 * sizeof(WantedStatus), ctx->stream));
+		WantedArgs A{};
+		A.roff = D.roff, A.seq_off = (const unsigned long long *)(d + o_soff), A.hdr = (const WantedHdr *)(d + o_whdr);
+		A.n_want = D.n_want, A.want_k = D.want_k, A.reg = D.reg;
+		A.total = total, A.reads_bytes = reads_bytes, A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.n_seqs = ctx->refidx_n, A.n = n, A.l_pac = l_pac;
+		A.first = (unsigned long long *)(dw + o_first), A.rec = (WantRec *)(dw + o_rec);
+		for (int c = 0; c < 4; ++c) A.key[c] = (uint32_t *)(dw + o_key[c]), A.sum[c] = (unsigned long long *)(dw + o_sum[c]);
+		A.req[0] = (bmh_region_req_t *)(dw + o_req0), A.req[1] = (bmh_region_req_t *)(dw + o_req1);
+		A.task[0] = (bmh_glb_task_t *)ctx->d_tasks.p, A.task[1] = A.task[0] + wc;
+		A.fix_res = (const bmh_region_res_t *)(dw + o_res0), A.fix_cig = (const uint32_t *)(dw + o_cig0);
+		A.main_res = (const bmh_region_res_t *)(dw + o_res1), A.wres = (bmh_wanted_res_t *)(dw + o_wres);
+		A.status = (WantedStatus *)(dw + o_stat), A.w_cap = wc, A.opool_cap = opool_cap, A.err = ctx->d_err;
+		if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + o_stat, 0, (int64_t)wc, &st))) return e;
+		if ((e = wanted_run_round(ctx, A, hs[0], 0, d_pool, rpool_off, (bmh_region_res_t *)(dw + o_res0), (uint32_t *)(dw + o_cig0), (char *)(dw + o_md0), kWantFixMdSlot)))
+			return e;
+		if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + o_stat, 0, (int64_t)wc, &st))) return e;
+		if ((e = wanted_run_round(ctx, A, hs[1], 1, d_pool, rpool_off, (bmh_region_res_t *)(dw + o_res1), (uint32_t *)(dw + o_cig1), (char *)(dw + o_md1), kWantMdSlot)))
+			return e;
+		if ((e = launch_wanted_results(ctx, A))) return e;
+		// every download behind the last kernel
+		n_w = hs[1].n_w, n_rec1 = hs[1].n_rec, n_fix = hs[0].n_rec;
+		R.wr.resize((size_t)n_w), cigdown.resize((size_t)n_rec1 * BMH_RP_SMALL_CAP * 4), mddown.resize((size_t)n_rec1 * kWantMdSlot);
+		if ((e = st.d2h(R.down.data(), d + o_reg, b_down))) return e;
+		if (n_w && (e = st.d2h(R.wr.data(), dw + o_wres, (size_t)n_w * sizeof(bmh_wanted_res_t)))) return e;
+		if (n_rec1 && ((e = st.d2h(cigdown.data(), dw + o_cig1, cigdown.size())) || (e = st.d2h(mddown.data(), dw + o_md1, mddown.size())))) return e;
+		return BMH_OK;
+	}();
+	rc = st.end(rc);
+	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
+	if (rc) return rc;
+	ctx->logk_n = want_log;
+	if (ctx->timing) {
+		BMH_HIP(ctx, hipEventElapsedTime(&ctx->decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
+		if (wc && ctx->ev_wanted[3]) {
+			float a = 0.f, b = 0.f;
+			BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
+			BMH_HIP(ctx, hipEventElapsedTime(&b, ctx->ev_wanted[2], ctx->ev_wanted[3]));
+			ctx->wanted_ms = a + b;
+		}
+	}
+	}
+	// ---- the want list as pass A left it, checked against the vectors and the session's count
+	const uint8_t *down = R.down.data();
+	const bmh_alnreg_t *sreg = (const bmh_alnreg_t *)down;
+	const int32_t *nw = (const int32_t *)(down + R.o_nw), *wk = (const int32_t *)(down + R.o_wk);
+	int64_t sum = 0;
+	bool fits = true;
+	for (int i = 0; i < n; ++i) fits = fits && nw[i] >= 0 && (size_t)nw[i] <= regs[i].n, sum += nw[i];
+	if (!fits || sum != n_w) { // cannot happen
+		ctx->last_error = "bmh_phase2_device: the device's counts are inconsistent";
+		return BMH_E_ARG;
+	}
+	// ---- the records: the device's, and the few regions whose alignments outgrew their slots again through the host form, their region
+	// records from the downloaded, sorted block with the coordinates as cut (the caller's vectors are still unsorted)
+	struct Redo {
+		int64_t j;
+		int read, k;
+	};
+	std::vector<Redo> redo;
+	{
+		int64_t j = 0;
+		for (int i = 0; i < n; ++i)
+			for (int q = 0; q < nw[i]; ++q, ++j) {
+				const bmh_wanted_res_t &x = R.wr[(size_t)j];
+				if (x.flags & BMH_WANTED_HOST) {
+					const int k = wk[roff[i] + q];
+					if (k < 0 || (size_t)k >= regs[i].n) return BMH_E_ARG; // cannot happen
+					redo.push_back(Redo{j, i, k});
+				} else if ((int64_t)x.cigar_off >= n_rec1 || x.n_cigar < 0 || x.n_cigar > BMH_RP_SMALL_CAP || x.md_len > (uint32_t)kWantMdSlot) {
+					ctx->last_error = "bmh_phase2_device: the device's records are inconsistent";
+					return BMH_E_ARG;
+				}
+			}
+	}
+	std::vector<bmh_wanted_res_t> hw(redo.size());
+	uint32_t *hcig = nullptr;
+	char *hmd = nullptr;
+	struct Free2 {
+		uint32_t *&a;
+		char *&b;
+		~Free2() { free(a), free(b); }
+	} guard2{hcig, hmd};
+	if (!redo.empty()) { // one region per read of a small slice of its own: the fix again for a region whose fix outgrew its slot
+		const size_t m = redo.size();
+		std::vector<bmh_alnreg_t> ra(m);
+		std::vector<bmh_alnreg_v> rv(m);
+		std::vector<bmh_read_t> rd(m);
+		std::vector<int64_t> ro(m + 1);
+		std::vector<int32_t> one(m, 1), zero(m, 0);
+		for (size_t t = 0; t < m; ++t) {
+			const bmh_wanted_res_t &x = R.wr[(size_t)redo[t].j];
+			ra[t] = sreg[roff[redo[t].read] + redo[t].k];
+			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe;
+			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[redo[t].read], ro[t] = (int64_t)t;
+		}
+		ro[m] = (int64_t)m;
+		if ((rc = bmh_wanted_host_(ctx, bns, pac, o->w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr)))
+			return rc;
+	}
+	size_t cu = 0, mu = 0, t = 0;
+	for (int64_t j = 0; j < n_w; ++j) {
+		const bmh_wanted_res_t &x = t < redo.size() && redo[t].j == j ? hw[t++] : R.wr[(size_t)j];
+		cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+	}
+	R.cig = (uint32_t *)malloc(4 * (cu + 4)), R.md = (char *)malloc(mu + 4);
+	if (!R.cig || !R.md) {
+		ctx->last_error = "bmh_phase2_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	cu = mu = 0, t = 0;
+	for (int64_t j = 0; j < n_w; ++j) { // packed in want order
+		bmh_wanted_res_t x = R.wr[(size_t)j];
+		const uint32_t *sc;
+		const char *sm;
+		if (t < redo.size() && redo[t].j == j) {
+			const uint32_t fl = x.flags;
+			x = hw[t], sc = hcig + x.cigar_off, sm = hmd + x.md_off;
+			x.flags |= fl | BMH_WANTED_HOST;
+			++t;
+		} else sc = (const uint32_t *)cigdown.data() + (size_t)x.cigar_off * BMH_RP_SMALL_CAP, sm = (const char *)mddown.data() + (size_t)x.md_off * kWantMdSlot;
+		memcpy(R.cig + cu, sc, 4 * (size_t)x.n_cigar), memcpy(R.md + mu, sm, x.md_len), R.md[mu + x.md_len] = 0;
+		x.cigar_off = (uint32_t)cu, x.md_off = (uint32_t)mu;
+		cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+		R.wr[(size_t)j] = x;
+	}
+	R.n_w = n_w;
+	ctx->decide_units = pe ? n >> 1 : n;
+	ctx->wanted_n = n_w, ctx->wanted_fixed = n_fix, ctx->wanted_redone = (long long)redo.size();
+	ctx->p2.units = ctx->decide_units, ctx->p2.wanted = n_w, ctx->p2.fixed = n_fix, ctx->p2.redone = (int64_t)redo.size();
+	ctx->p2.sessions = 1, ctx->p2.decide_ms = ctx->decide_ms, ctx->p2.wanted_ms = ctx->wanted_ms;
+	return BMH_OK;
+}
+
+int bmh_phase2_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                      const bmh_read_t *reads, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want,
+                      int32_t *want_k, bmh_wanted_res_t *results, int64_t results_cap, int64_t *n_wanted, uint32_t *cigar_pool, size_t cigar_words,
+                      char *md_pool, size_t md_bytes)
+{
+	if (!ctx || !n_wanted) return BMH_E_ARG;
+	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	if (rc || (rc = phase2_check_reads(bns, pac, n, reads))) return rc;
+	if (n == 0) {
+		ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+		*n_wanted = 0;
+		return BMH_OK;
+	}
+	if (results_cap < 0 || (roff[n] > 0 && (!results || !cigar_pool || !md_pool))) return BMH_E_ARG;
+	Phase2Run R;
+	bool tables;
+	if ((rc = phase2_device_run(ctx, o, bns, pac, pes, id0, n, reads, regs, roff, R, &tables))) return rc;
+	if (R.n_w > results_cap) return BMH_E_CIGAR_CAP;
+	if (R.n_w && (rc = bmh_wanted_deliver_(R.n_w, R.wr.data(), R.cig, R.md, results, cigar_pool, cigar_words, md_pool, md_bytes))) return rc;
+	phase2_commit(R, (o->flag & BMH_MEM_F_PE) != 0, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	*n_wanted = R.n_w;
+	return BMH_OK;
+}
+
+int bmh_ctx_set_phase2_device(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->phase2_device = on != 0;
+	return BMH_OK;
+}
+
+int bmh_last_phase2_stats(const bmh_ctx_t *ctx, bmh_phase2_stats_t *st)
+{
+	if (!ctx || !st) return BMH_E_ARG;
+	*st = ctx->p2;
+	return BMH_OK;
+}
+
+// bmh_sam_batch's pass A and pass B as one session (host/sam_post.c; not part of the interface).  *done = 1: the outputs are the fused
+// call's, *wr / *cig / *md malloc'd.  *done = 0 with BMH_OK: the switch is off, or the call refused the slice's tables before its
+// upload (the statistics then say one fall-back, two sessions), and the caller goes through the two routed passes.
+__attribute__((visibility("hidden"))) int bmh_phase2_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac,
+                                                             const bmh_pestat_t *pes, int64_t id0, int n, const bmh_read_t *reads, bmh_alnreg_v *regs,
+                                                             const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k,
+                                                             int64_t *n_w, bmh_wanted_res_t **wr, uint32_t **cig, char **md, int *done)
+{
+	*done = 0;
+	if (!ctx || !ctx->phase2_device) return BMH_OK;
+	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	if (rc || (rc = phase2_check_reads(bns, pac, n, reads))) return rc;
+	Phase2Run R;
+	bool tables;
+	rc = phase2_device_run(ctx, o, bns, pac, pes, id0, n, reads, regs, roff, R, &tables);
+	if (rc == BMH_E_RANGE && tables) {
+		ctx->p2.sessions = 2;
+		return BMH_OK;
+	}
+	if (rc) return rc;
+	if (R.n_w) {
+		if (!(*wr = (bmh_wanted_res_t *)malloc(sizeof(bmh_wanted_res_t) * (size_t)R.n_w))) return BMH_E_NOMEM;
+		memcpy(*wr, R.wr.data(), sizeof(bmh_wanted_res_t) * (size_t)R.n_w);
+	}
+	phase2_commit(R, (o->flag & BMH_MEM_F_PE) != 0, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	*cig = R.cig, *md = R.md, R.cig = nullptr, R.md = nullptr;
+	*n_w = R.n_w, *done = 1;
+	return BMH_OK;
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

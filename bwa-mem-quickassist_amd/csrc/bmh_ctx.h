@@ -144,6 +144,9 @@ struct bmh_ctx {
 	hipEvent_t ev_wanted[4] = {};             // around the two groups of planning kernels (timing mode)
 	long long wanted_n = -1, wanted_fixed = -1, wanted_redone = -1; // of the last bmh_wanted_cigar_device call (bmh_last_wanted_stats)
 	float wanted_ms = -1.f;
+	// pass A and pass B as one device session (api.hip): bmh_phase2_device, and bmh_sam_batch with the switch on
+	bool phase2_device = false;               // bmh_ctx_set_phase2_device
+	bmh_phase2_stats_t p2 = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f}; // of the last fused call (bmh_last_phase2_stats)
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 

@@ -51,6 +51,8 @@ struct WantedArgs {
 	bmh_glb_task_t *task[2];                  // w_cap; 3 * w_cap
 	const bmh_region_res_t *fix_res;          // round 0's results, w_cap ...
 	const uint32_t *fix_cig;                  // ... and CIGAR slots of BMH_RP_SMALL_CAP words
+	const bmh_region_res_t *main_res;         // the main round's results, w_cap (the fused session only) ...
+	bmh_wanted_res_t *wres;                   // ... and the records wanted_result_kernel makes of them, w_cap
 	WantedStatus *status;                     // 2
 	unsigned long long w_cap, opool_cap;
 	int *err;
@@ -60,5 +62,7 @@ struct WantedArgs {
 int launch_wanted_begin(bmh_ctx *ctx, const WantedArgs &A);
 // the cut of the regions round 0 aligned, then every region's plan.  Behind it rec[] and status[1] are complete.
 int launch_wanted_main(bmh_ctx *ctx, const WantedArgs &A);
+// behind the main round's region kernels (bmh_phase2_device): wres[j] from rec[j] and its region result, so that rec[] stays on the device
+int launch_wanted_results(bmh_ctx *ctx, const WantedArgs &A);
 
 } // namespace bmh

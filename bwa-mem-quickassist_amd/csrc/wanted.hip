@@ -13,6 +13,8 @@
 //   wanted_emit_kernel   one lane per wanted region: its record and tasks at those sums; GlbShape of the tasks by atomicMax
 //   wanted_cut_kernel    one lane per wanted region: walks round 0's CIGAR to the cut points and rewrites the coordinates
 //                        (bwa.c:199-221), then plans the main round: bands and its keys
+//   wanted_result_kernel (bmh_phase2_device only) one lane per wanted region, behind the main round's region kernels: its
+//                        bmh_wanted_res_t from its WantRec and region result, cigar_off / md_off = its slot for the host's packing
 // Offsets come from sums over the want order in one block each, never from atomicAdd: they do not depend on block scheduling.  Every
 // dependency between blocks is a kernel boundary.  Nothing on the host has seen these records, so the kernels check what
 // bmh_region_cigar_batch checks on the host; a refused region writes and addresses nothing, and the first error goes to the
@@ -226,6 +228,27 @@ __global__ __launch_bounds__(256) void wanted_cut_kernel(WantedArgs A)
 	A.key[0][j] = 1, A.key[1][j] = (uint32_t)(ql + tl), A.key[2][j] = (uint32_t)pl.n_tasks, A.key[3][j] = (uint32_t)pl.n_tasks * pl.cap;
 }
 
+__global__ __launch_bounds__(256) void wanted_result_kernel(WantedArgs A)
+{
+	const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= (unsigned long long)A.status[1].n_w) return;
+	const WantRec x = A.rec[j];
+	bmh_wanted_res_t o;
+	o.rb = x.rb, o.re = x.re, o.qb = x.qb, o.qe = x.qe; // as cut; a region whose fix the host redoes still has its own
+	o.score = 0, o.n_cigar = 0, o.NM = 0, o.tries = 0, o.cigar_off = 0, o.md_off = 0, o.md_len = 0, o.flags = x.flags;
+	o.band[0] = x.band[0], o.band[1] = x.band[1], o.band[2] = x.band[2], o.rsv_ = 0;
+	if (x.state == kWantOk && x.v >= 0 && (unsigned long long)x.v < (unsigned long long)A.status[1].n_rec) {
+		const bmh_region_res_t r = A.main_res[x.v];
+		o.score = r.score, o.n_cigar = r.n_cigar, o.NM = r.NM, o.tries = r.tries, o.md_len = (uint32_t)r.md_len;
+		o.cigar_off = o.md_off = (uint32_t)x.v;
+		if (r.flags) o.flags |= BMH_WANTED_HOST;
+	} else {
+		o.flags |= BMH_WANTED_HOST;
+		if (x.state != kWantHost) wanted_fail(A, BMH_E_ARG); // (cannot happen: a refused region has ended the session before)
+	}
+	A.wres[j] = o;
+}
+
 static int wanted_events(bmh_ctx *ctx, int k)
 {
 	if (!ctx->timing) return BMH_OK;
@@ -259,6 +282,14 @@ int launch_wanted_main(bmh_ctx *ctx, const WantedArgs &A)
 	hipLaunchKernelGGL(wanted_emit_kernel, dim3(blocks), dim3(256), 0, ctx->stream, A, 1);
 	BMH_HIP(ctx, hipGetLastError());
 	return wanted_events(ctx, 3);
+}
+
+int launch_wanted_results(bmh_ctx *ctx, const WantedArgs &A)
+{
+	if (A.n <= 0 || A.w_cap == 0) return BMH_OK;
+	hipLaunchKernelGGL(wanted_result_kernel, dim3((unsigned)((A.w_cap + 255) / 256)), dim3(256), 0, ctx->stream, A);
+	BMH_HIP(ctx, hipGetLastError());
+	return BMH_OK;
 }
 
 } // namespace bmh

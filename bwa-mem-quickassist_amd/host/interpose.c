@@ -28,6 +28,9 @@
  *   BMH_WANTED_DEVICE=1  its pass B's planning -- the bwa_fix_xref2 test and cut, bands, region records and tasks of the regions that
  *                        get printed -- as kernels (bmh_ctx_set_wanted_device).  Needs BMH_PAC_RESIDENT not 0; independent of the
  *                        other switches.
+ *   BMH_PHASE2_DEVICE=1  pass A and pass B as ONE device session (bmh_ctx_set_phase2_device): the regions go up once and the want
+ *                        list never leaves the device between the two.  Needs BMH_PAC_RESIDENT not 0.  A slice the fused call
+ *                        refuses as out of range goes the way the two switches above say.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -432,6 +435,28 @@ static int qa_wanted_device(void)
 }
 static long long g_wanted_cnt[3]; /* regions planned on the device, fixed, redone on the host */
 
+/* BMH_PHASE2_DEVICE=1: phase 2's pass A and pass B as one device session (bmh_ctx_set_phase2_device on every pooled context phase 2
+ * uses, with the sequence table made resident where the reference is).  It needs the resident reference as BMH_WANTED_DEVICE does:
+ * checked when the library is loaded. */
+__attribute__((constructor)) static void qa_check_phase2_device_env(void)
+{
+	const char *e = getenv("BMH_PHASE2_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_PHASE2_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+static int qa_phase2_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_PHASE2_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_phase2_cnt[5]; /* units, regions, fixed, redone on the host, slices that fell back to the two passes */
+
 /* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
 static int qa_regs_device(void)
 {
@@ -680,11 +705,14 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 	int rc;
 	if (J->resident && (rc = bmh_ctx_set_pac(ctx, J->pac, J->bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
 	if ((rc = bmh_ctx_set_decide_device(ctx, qa_decide_device()))) bmh_tls_die(bmh_last_error(ctx), rc); /* per pooled context */
-	if (qa_wanted_device()) { /* the sequence table where the reference is made resident; both stay */
-		if (!J->resident) bmh_tls_die("BMH_WANTED_DEVICE=1 needs the reference resident on the device", BMH_E_ARG);
+	if (qa_wanted_device() || qa_phase2_device()) { /* the sequence table where the reference is made resident; both stay */
+		if (!J->resident)
+			bmh_tls_die(qa_wanted_device() ? "BMH_WANTED_DEVICE=1 needs the reference resident on the device"
+			                               : "BMH_PHASE2_DEVICE=1 needs the reference resident on the device", BMH_E_ARG);
 		if ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns))) bmh_tls_die(bmh_last_error(ctx), rc);
 	}
 	if ((rc = bmh_ctx_set_wanted_device(ctx, qa_wanted_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
+	if ((rc = bmh_ctx_set_phase2_device(ctx, qa_phase2_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	return ctx;
 }
 
@@ -750,6 +778,13 @@ static void qa_sam_slice(void *data, int k, int tid)
 		bmh_last_wanted_stats(ctx, &ww, &wf, &wr, 0);
 		__sync_fetch_and_add(&g_wanted_cnt[0], (long long)(ww > 0 ? ww : 0)), __sync_fetch_and_add(&g_wanted_cnt[1], (long long)(wf > 0 ? wf : 0));
 		__sync_fetch_and_add(&g_wanted_cnt[2], (long long)(wr > 0 ? wr : 0));
+	}
+	if (qa_phase2_device()) {
+		bmh_phase2_stats_t ps;
+		bmh_last_phase2_stats(ctx, &ps);
+		__sync_fetch_and_add(&g_phase2_cnt[0], (long long)(ps.units > 0 ? ps.units : 0)), __sync_fetch_and_add(&g_phase2_cnt[1], (long long)(ps.wanted > 0 ? ps.wanted : 0));
+		__sync_fetch_and_add(&g_phase2_cnt[2], (long long)(ps.fixed > 0 ? ps.fixed : 0)), __sync_fetch_and_add(&g_phase2_cnt[3], (long long)(ps.redone > 0 ? ps.redone : 0));
+		__sync_fetch_and_add(&g_phase2_cnt[4], (long long)(ps.fallbacks > 0 ? ps.fallbacks : 0));
 	}
 	bmh_pool_put(ctx);
 	t2 = stage_now();
@@ -877,6 +912,9 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		if (qa_wanted_device())
 			fprintf(stderr, "[bwamem_hip] phase 2 alignments planned on the device: %lld regions, %lld fixed, %lld redone on the host\n",
 			        g_wanted_cnt[0], g_wanted_cnt[1], g_wanted_cnt[2]);
+		if (qa_phase2_device())
+			fprintf(stderr, "[bwamem_hip] phase 2 on the device in one session: %lld units, %lld regions, %lld fixed, %lld redone on the host, %lld host fall-backs\n",
+			        g_phase2_cnt[0], g_phase2_cnt[1], g_phase2_cnt[2], g_phase2_cnt[3], g_phase2_cnt[4]);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());
 			fprintf(stderr, "[bwamem_hip] wide Smith-Waterman so far: %lld ksw_align2 tasks on the long-query kernel\n", bmh_pool_swl_tasks());

@@ -669,6 +669,13 @@ int bmh_decide_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, co
 int bmh_wanted_routed_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
                        const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t n_w, bmh_wanted_res_t *wr, uint32_t **cig, char **md);
 
+/* pass A and pass B as one device session behind the context's switch (csrc/api.hip): with bmh_ctx_set_phase2_device on, *done = 1 and
+ * bmh_phase2_device's outputs, *wr / *cig / *md malloc'd; *done = 0 with the switch off, and for a slice whose tables the call refuses
+ * before its upload (BMH_E_RANGE), which then goes through the two hooks above */
+int bmh_phase2_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                       const bmh_read_t *reads, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want,
+                       int32_t *want_k, int64_t *n_w, bmh_wanted_res_t **wr, uint32_t **cig, char **md, int *done);
+
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id)
 {
@@ -688,7 +695,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	aln_t *alns = 0;
 	str_t str = {0, 0, 0};
 	size_t j, arena_words = 0;
-	int i, rc = BMH_OK;
+	int i, rc = BMH_OK, fused = 0;
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0;
 	double tt[4] = {0, 0, 0, 0};
 
@@ -712,18 +719,23 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	if (!reg_mapq || !want_k) { rc = BMH_E_NOMEM; goto done; }
 
 	if (trace) tt[0] = now_s();
+	/* ---- pass A and pass B as one device session (bmh_phase2_device behind the context's switch): its want list and records go to
+	 * pass C as they are */
+	if ((rc = bmh_phase2_routed_(ctx, o, bns, pac, pes, id0, n, reads, regs, roff, pd, reg_mapq, n_want, want_k, &n_w, &wr, &cig, &md, &fused))) goto done;
 	/* ---- pass A: decisions (bmh_decide_batch, or bmh_decide_device behind the context's switch) */
-	if ((rc = bmh_decide_routed_(ctx, o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k))) goto done;
-	for (i = 0; i < n; ++i) n_w += n_want[i];
+	if (!fused) {
+		if ((rc = bmh_decide_routed_(ctx, o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k))) goto done;
+		for (i = 0; i < n; ++i) n_w += n_want[i];
+	}
 
 	if (trace) tt[1] = now_s();
 	/* ---- pass B: bwa_fix_xref2 (bwa.c:179-222), then the alignments: bmh_wanted_cigar_batch's work, or with
 	 * bmh_ctx_set_wanted_device on bmh_wanted_cigar_device's (the same records either way) */
 	if (n_w) {
-		wr = (bmh_wanted_res_t *)malloc(sizeof(*wr) * (size_t)n_w);
+		if (!fused) wr = (bmh_wanted_res_t *)malloc(sizeof(*wr) * (size_t)n_w);
 		wk = (int32_t *)malloc(sizeof(*wk) * (size_t)n_w);
 		if (!wr || !wk) { rc = BMH_E_NOMEM; goto done; }
-		if ((rc = bmh_wanted_routed_(ctx, bns, pac, o->w, n, reads, regs, roff, n_want, want_k, n_w, wr, &cig, &md))) goto done;
+		if (!fused && (rc = bmh_wanted_routed_(ctx, bns, pac, o->w, n, reads, regs, roff, n_want, want_k, n_w, wr, &cig, &md))) goto done;
 		for (j = 0; j < (size_t)n_w; ++j) arena_words += (size_t)wr[j].n_cigar + 2;
 	}
 	for (i = 0, j = 0; i < n; ++i) { /* first entry of the want list per read */

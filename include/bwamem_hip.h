@@ -596,7 +596,8 @@ int bmh_pair(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], c
  * fastmap.c:201 does).  id0 = n_processed + index of read 0 (the reference's per-read id, bwamem.c:1287,1291).
  * rg_id: the reference's bwa_rg_id ("" = none).  regs[i].a is left sorted/marked as the reference leaves it.
  * The decisions (everything before the global alignments) are bmh_decide_batch's, or with bmh_ctx_set_decide_device on
- * bmh_decide_device's: the same text either way (below). */
+ * bmh_decide_device's: the same text either way (below).  With bmh_ctx_set_phase2_device on, decisions and alignments are one device
+ * session, bmh_phase2_device's: the same text again. */
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id);
 
@@ -687,8 +688,47 @@ int bmh_ctx_set_wanted_device(bmh_ctx_t *ctx, int on);
 /* Of the last bmh_wanted_cigar_device call on this context, direct or from bmh_sam_batch with the switch on: wanted regions, regions
  * bwa_fix_xref2 moved, regions redone on the host, and the planning kernels' milliseconds with bmh_set_kernel_timing on (else -1).
  * -1, -1, -1, -1 before the first such call.  Any pointer may be NULL.  (With bmh_ctx_set_decide_device also on, pass A and pass B
- * are still two device sessions: the want list is downloaded and uploaded again between them.) */
+ * are still two device sessions: the want list is downloaded and uploaded again between them.  The one session without that hop is
+ * bmh_phase2_device below, behind a switch of its own.) */
 int bmh_last_wanted_stats(const bmh_ctx_t *ctx, int64_t *wanted, int64_t *fixed, int64_t *redone, float *kernel_ms);
+
+/* ---- Pass A and pass B as one device session: bmh_decide_device's kernel and bmh_wanted_cigar_device's kernels on one upload, the
+ * want list and the sorted regions read where decide_kernel left them.  The regions go up once, the want list never goes up, and the
+ * host waits at most three times (two status records, the end).  Arguments as in the two calls, w = o->w.  Every output is byte for
+ * byte what bmh_decide_batch followed by bmh_wanted_cigar_batch(..., w = o->w, ...) leaves in the same arguments; entries of want_k
+ * past a read's n_want stay the caller's.  *n_wanted = the wanted regions, the records written.
+ *   capacities   the caller does not know the want list: results_cap = roff[n] always suffices, and for the pools the sums of
+ *                qe-qb + re-rb + 2 words and of 3*(qe-qb + re-rb) + 16 bytes over ALL regions of the slice; BMH_E_CIGAR_CAP when
+ *                one of the three is too small
+ *   BMH_E_ARG    before any upload: what bmh_decide_batch refuses, what bmh_wanted_cigar_batch refuses of reads, vectors and
+ *                offsets, a NULL n_wanted, no parameters, no resident 2-bit reference or sequence table; from the kernels: a wanted
+ *                region as bmh_wanted_cigar_device refuses it
+ *   BMH_E_RANGE  before any upload: exactly what bmh_decide_device refuses (a table past 1 << 20 entries); from the kernels: a wanted
+ *                window past 65535
+ *   BMH_OK       for n == 0 with *n_wanted = 0, nothing runs
+ * All or nothing: the caller's vectors and every output are written only after everything has succeeded, the host's redo of the
+ * BMH_WANTED_HOST regions included; on any error they are untouched (the vectors not even sorted). */
+int bmh_phase2_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
+                      int64_t id0, int n, const bmh_read_t *reads, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd,
+                      int32_t *reg_mapq, int32_t *n_want, int32_t *want_k, bmh_wanted_res_t *results, int64_t results_cap,
+                      int64_t *n_wanted, uint32_t *cigar_pool, size_t cigar_words, char *md_pool, size_t md_bytes);
+/* Per context, off by default.  While on, bmh_sam_batch takes pass A and pass B from bmh_phase2_device (BMH_E_ARG without the two
+ * resident tables); a slice that call refuses with BMH_E_RANGE before its upload goes the way the other two switches say.  The text
+ * is the same either way. */
+int bmh_ctx_set_phase2_device(bmh_ctx_t *ctx, int on);
+/* Of the last bmh_phase2_device call on this context, direct or from bmh_sam_batch with the switch on; all -1 before the first.
+ *   units, wanted, fixed, redone   reads or pairs decided, wanted regions, regions bwa_fix_xref2 moved, regions redone on the host
+ *   fallbacks, sessions            0 and 1 for a fused run; 1 and 2 where bmh_sam_batch fell back after BMH_E_RANGE; 0 and 0 where
+ *                                  nothing ran (n == 0)
+ *   h2d_bytes, d2h_bytes, waits    of the fused session itself (the host's redo of a few regions is not counted)
+ *   decide_ms, wanted_ms           the kernels' milliseconds with bmh_set_kernel_timing on, else -1 */
+typedef struct bmh_phase2_stats {
+	int64_t units, wanted, fixed, redone, fallbacks;
+	int64_t h2d_bytes, d2h_bytes;
+	int32_t waits, sessions;
+	float decide_ms, wanted_ms;
+} bmh_phase2_stats_t;
+int bmh_last_phase2_stats(const bmh_ctx_t *ctx, bmh_phase2_stats_t *st);
 
 /* ------------------------------------------------------------------------------------------------------------
  * FM-index queries of the seeding stage (first slice): super-maximal exact matches and suffix-
