@@ -77,7 +77,10 @@ WANTED_RES = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"
                        ("rsv", "<i4")])  # bmh_wanted_res_t, 72 bytes
 PHASE2_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i8"), ("redone", "<i8"), ("fallbacks", "<i8"), ("h2d_bytes", "<i8"),
                          ("d2h_bytes", "<i8"), ("waits", "<i4"), ("sessions", "<i4"), ("decide_ms", "<f4"), ("wanted_ms", "<f4")])  # bmh_phase2_stats_t, 72 bytes
+SAMTEXT_STATS = np.dtype([("reads", "<i8"), ("lines", "<i8"), ("text_bytes", "<i8"), ("h2d_bytes", "<i8"), ("d2h_bytes", "<i8"), ("waits", "<i4"),
+                          ("rsv", "<i4"), ("size_ms", "<f4"), ("emit_ms", "<f4")])  # bmh_samtext_stats_t, 56 bytes
 WANTED_MOVED, WANTED_HOST = 4, 8
+MEM_F_NO_MULTI = 0x10
 ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
                    ("truesc", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"),
                    ("w", "<i4"), ("seedcov", "<i4"), ("secondary", "<i4"), ("hash", "<u8")])
@@ -105,6 +108,10 @@ class _Read(C.Structure):
     _fields_ = [("l_seq", C.c_int32), ("seq", C.c_void_p)]
 
 
+class _Seq(C.Structure):  # bmh_seq_t
+    _fields_ = [("l_seq", C.c_int32), ("name", C.c_char_p), ("comment", C.c_char_p), ("seq", C.c_void_p), ("qual", C.c_char_p), ("sam", C.c_void_p)]
+
+
 class _RefAnn(C.Structure):  # bmh_refann_t
     _fields_ = [("offset", C.c_int64), ("len", C.c_int32), ("n_ambs", C.c_int32), ("gi", C.c_uint32), ("name", C.c_char_p), ("anno", C.c_char_p)]
 
@@ -113,11 +120,11 @@ class _RefIdx(C.Structure):  # bmh_refidx_t
     _fields_ = [("l_pac", C.c_int64), ("n_seqs", C.c_int32), ("seed", C.c_uint32), ("anns", C.POINTER(_RefAnn))]
 
 
-def make_refidx(contigs, l_pac=None):
-    """bmh_refidx_t over contigs = [(offset, len), ...] (names seq0, seq1, ...); l_pac defaults to the end of the last one."""
+def make_refidx(contigs, l_pac=None, names=None):
+    """bmh_refidx_t over contigs = [(offset, len), ...] (names seq0, seq1, ... unless given); l_pac defaults to the end of the last one."""
     anns = (_RefAnn * max(len(contigs), 1))()
     for i, (off, ln) in enumerate(contigs):
-        anns[i] = _RefAnn(int(off), int(ln), 0, 0, b"seq%d" % i, b"")
+        anns[i] = _RefAnn(int(off), int(ln), 0, 0, names[i] if names is not None else b"seq%d" % i, b"")
     idx = _RefIdx(int(l_pac if l_pac is not None else contigs[-1][0] + contigs[-1][1]), len(contigs), 11, anns)
     idx._keep = anns
     return idx
@@ -238,6 +245,11 @@ def lib():
                                         C.c_void_p, C.c_size_t])
         L.bmh_ctx_set_phase2_device.argtypes = [C.c_void_p, C.c_int]
         L.bmh_last_phase2_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_sam_text_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_char_p, C.c_void_p, C.c_void_p]
+        L.bmh_sam_text_device.argtypes = [C.c_void_p] + L.bmh_sam_text_batch.argtypes
+        L.bmh_ctx_set_refnames.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_ctx_set_samtext_device.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_last_samtext_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -947,6 +959,24 @@ class Context:
         self._check(lib().bmh_last_phase2_stats(self._h, _ptr(st)))
         return {k: st[0][k].item() for k in PHASE2_STATS.names}
 
+    def set_refnames(self, refidx):
+        """bmh_ctx_set_refnames: the name of every reference sequence resident on the device; None drops it."""
+        self._check(lib().bmh_ctx_set_refnames(self._h, C.byref(refidx) if refidx is not None else None))
+
+    def set_samtext_device(self, on=True):
+        """bmh_ctx_set_samtext_device: while on, bmh_sam_batch takes its pass C from bmh_sam_text_device."""
+        self._check(lib().bmh_ctx_set_samtext_device(self._h, 1 if on else 0))
+
+    def last_samtext_stats(self):
+        """bmh_last_samtext_stats as a dict of SAMTEXT_STATS' fields: the last bmh_sam_text_device call on this context."""
+        st = np.zeros(1, dtype=SAMTEXT_STATS)
+        self._check(lib().bmh_last_samtext_stats(self._h, _ptr(st)))
+        return {k: st[0][k].item() for k in SAMTEXT_STATS.names if k != "rsv"}
+
+    def sam_text_batch(self, *args, device=True, **kw):
+        """sam_text_batch() on this context: bmh_sam_text_device (device=False: the host call, which needs no context)."""
+        return sam_text_batch(*args, ctx=self if device else None, **kw)
+
     def reg2cigar_batch(self, l_pac, pac, reads, reqs):
         """Batched mem_reg2aln band/retry loop over bwa_gen_cigar2 (reference bwamem.c:1187-1201, bwa.c:89-172).
         reads: list of uint8 code arrays; reqs: CIGAR_REQ array.  Returns (results, cigar_pool, md_bytes)."""
@@ -1007,6 +1037,44 @@ def decide_batch(opt, l_pac, pes, id0, vectors, roff=None, inplace=False):
     Returns a dict: regs (per read the vector as pass A leaves it), pd (PAIRDEC per pair), reg_mapq, n_want, want_k (flat, at the
     regions' offsets; entries past n_want stay -1) and want (per read the printed regions' indices)."""
     return _decide(None, opt, l_pac, pes, id0, vectors, roff, inplace)
+
+
+def sam_text_batch(opt, refidx, pes, seqs, vectors, dec, res, cig, md, rg_id=b"", ctx=None, out=None):
+    """bmh_sam_text_batch (with ctx: bmh_sam_text_device on it): pass C of phase 2, the SAM text of a slice.  seqs: per read (name,
+    comment or None, uint8 base codes, qualities or None); vectors: per read its ALNREG array as pass A left it; dec: pass A's outputs
+    by name (pd, reg_mapq, n_want, want_k: decide_batch()'s dict); res, cig, md: pass B's records and pools.  Returns (text, text_off):
+    the pool's bytes and n + 1 offsets.  out: {"text": a C.c_void_p, "text_off": an int64 array} to write into (a test's sentinels)."""
+    n = len(seqs)
+    o = np.array(opt, dtype=SAM_OPT).reshape(1)
+    pe = bool(int(o["flag"][0]) & MEM_F_PE)
+    keep = []
+    c_seqs = (_Seq * max(n, 1))()
+    c_regs = (_AlnregV * max(n, 1))()
+    for r, ((name, comment, seq, qual), v) in enumerate(zip(seqs, vectors)):
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        v = np.ascontiguousarray(v, dtype=ALNREG).reshape(-1)
+        keep += [seq, v]
+        c_seqs[r] = _Seq(len(seq), name, comment, seq.ctypes.data if len(seq) else None, qual, None)
+        c_regs[r].n = c_regs[r].m = len(v)
+        c_regs[r].a = v.ctypes.data if len(v) else None
+    roff = np.concatenate([[0], np.cumsum([len(v) for v in vectors])]).astype(np.int64)
+    arr = {k: (np.ascontiguousarray(dec[k]) if dec.get(k) is not None else None) for k in ("pd", "reg_mapq", "n_want", "want_k")}
+    res = np.ascontiguousarray(res, dtype=WANTED_RES) if res is not None else None
+    cig = np.ascontiguousarray(cig, dtype=np.uint32) if cig is not None else None
+    md = np.ascontiguousarray(md, dtype=np.uint8) if md is not None else None
+    out = out or {}
+    text = out.get("text", C.c_void_p(None))
+    text_off = out.get("text_off", np.zeros(n + 1, dtype=np.int64))
+    pes_p = _ptr(np.ascontiguousarray(pes, dtype=PESTAT)) if pes is not None else None
+    args = (_ptr(o), C.byref(refidx) if refidx is not None else None, pes_p, n, C.cast(c_seqs, C.c_void_p), C.cast(c_regs, C.c_void_p), _ptr(roff),
+            _ptr(arr["pd"]) if pe else None, _ptr(arr["reg_mapq"]), _ptr(arr["n_want"]), _ptr(arr["want_k"]), _ptr(res), _ptr(cig), _ptr(md), rg_id,
+            C.cast(C.byref(text), C.c_void_p), _ptr(text_off))
+    rc = lib().bmh_sam_text_batch(*args) if ctx is None else lib().bmh_sam_text_device(ctx._h, *args)
+    if rc:
+        raise BmhError(rc, lib().bmh_strerror(rc).decode() if ctx is None else lib().bmh_last_error(ctx._h).decode())
+    data = C.string_at(text.value, int(text_off[n]))
+    _libc.free(text)
+    return data, text_off
 
 
 def extend_batch_sharded(ctxs, pool, tasks):

@@ -13,6 +13,7 @@
 #include "bmh_ctx.h"
 #include "decide.h"
 #include "wanted.h"
+#include "samtext.h"
 
 namespace bmh {
 
@@ -92,6 +93,7 @@ struct Stager {
 	bool wide; // an extension batch: end() adds what the int32 kernel received to ctx->wide_total
 	bool up = false, down = false;
 	bool p2 = false; // the fused phase 2 session: bytes and waits go to ctx->p2 (bmh_last_phase2_stats)
+	bool sx = false; // bmh_sam_text_device's session: they go to ctx->stx (bmh_last_samtext_stats)
 	size_t up_used = 0, down_used = 0;
 	struct Pending {
 		void *dst;
@@ -115,6 +117,7 @@ struct Stager {
 			up_used += (bytes + 63) & ~(size_t)63, src = h;
 		}
 		if (p2) ctx->p2.h2d_bytes += (int64_t)bytes;
+		if (sx) ctx->stx.h2d_bytes += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
 		return BMH_OK;
 	}
@@ -127,6 +130,7 @@ struct Stager {
 			down_used += (bytes + 63) & ~(size_t)63;
 		}
 		if (p2) ctx->p2.d2h_bytes += (int64_t)bytes;
+		if (sx) ctx->stx.d2h_bytes += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(to, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
 		return BMH_OK;
 	}
@@ -136,6 +140,7 @@ struct Stager {
 	int end(int rc)
 	{
 		if (p2) ++ctx->p2.waits;
+		if (sx) ++ctx->stx.waits;
 		if (rc) { // (the flag's text must not replace why the call failed)
 			std::string why = std::move(ctx->last_error);
 			(void)fetch_err(ctx);
@@ -310,6 +315,10 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	free(ctx->h_logk);
 	free_buf(ctx->d_refidx), free_buf(ctx->d_wanted);
 	if (ctx->h_wstat) (void)hipHostFree(ctx->h_wstat);
+	free_buf(ctx->d_refnames), free_buf(ctx->d_samtext), free_buf(ctx->d_sam_out);
+	if (ctx->h_ststat) (void)hipHostFree(ctx->h_ststat);
+	for (auto &e : ctx->ev_samtext)
+		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_wanted)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_decide)
@@ -1461,6 +1470,7 @@ __attribute__((visibility("hidden"))) void bmh_decide_stats_reset_(bmh_ctx_t *ct
 	if (ctx && ctx->decide_device) ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
 	if (ctx && ctx->wanted_device) ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
 	if (ctx && ctx->phase2_device) ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+	if (ctx && ctx->samtext_device) ctx->stx = bmh_samtext_stats_t{0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
 }
 
 // bmh_sam_batch's pass A (host/sam_post.c; not part of the interface)
@@ -2178,6 +2188,234 @@ __attribute__((visibility("hidden"))) int bmh_phase2_routed_(bmh_ctx_t *ctx, con
 	*cig = R.cig, *md = R.md, R.cig = nullptr, R.md = nullptr;
 	*n_w = R.n_w, *done = 1;
 	return BMH_OK;
+}
+
+// ------------------------------------------------------------------ pass C of phase 2 on the device (samtext.hip)
+
+// the argument check of the two forms (host/sam_post.c; not part of the interface)
+int bmh_samtext_check_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,
+                       const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq, const int32_t *n_want, const int32_t *want_k,
+                       const bmh_wanted_res_t *wr, const uint32_t *cig, const char *md, char **text, int64_t *text_off, int64_t *first, int64_t *lines,
+                       size_t *cig_words, size_t *md_bytes);
+
+// the names of bns as the device holds them: n_seqs + 1 offsets, then the bytes
+static std::vector<char> refnames_block(const bmh_refidx_t *bns)
+{
+	const size_t ns = (size_t)bns->n_seqs;
+	size_t bytes = 0;
+	for (size_t i = 0; i < ns; ++i) bytes += strlen(bns->anns[i].name);
+	std::vector<char> t((ns + 1) * 8 + bytes);
+	uint64_t at = 0;
+	for (size_t i = 0; i < ns; ++i) {
+		const size_t l = strlen(bns->anns[i].name);
+		memcpy(t.data() + i * 8, &at, 8);
+		memcpy(t.data() + (ns + 1) * 8 + at, bns->anns[i].name, l);
+		at += l;
+	}
+	memcpy(t.data() + ns * 8, &at, 8);
+	return t;
+}
+
+int bmh_ctx_set_refnames(bmh_ctx_t *ctx, const bmh_refidx_t *bns)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (!bns) {
+		ctx->refnames_n = 0, ctx->h_refnames.clear();
+		return BMH_OK;
+	}
+	if (bns->n_seqs <= 0 || !bns->anns) return BMH_E_ARG;
+	for (int i = 0; i < bns->n_seqs; ++i)
+		if (!bns->anns[i].name) return BMH_E_ARG;
+	std::vector<char> t = refnames_block(bns);
+	if (ctx->refnames_n == bns->n_seqs && ctx->h_refnames == t) return BMH_OK; // already resident: the same names
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream)); // (nothing in flight reads the table while it is replaced)
+	ctx->refnames_n = 0, ctx->h_refnames.clear();
+	int rc;
+	if ((rc = ensure(ctx, ctx->d_refnames, t.size()))) return rc;
+	BMH_HIP(ctx, hipMemcpy(ctx->d_refnames.p, t.data(), t.size(), hipMemcpyHostToDevice));
+	ctx->refnames_n = bns->n_seqs, ctx->h_refnames = std::move(t);
+	return BMH_OK;
+}
+
+int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
+                        const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq, const int32_t *n_want,
+                        const int32_t *want_k, const bmh_wanted_res_t *results, const uint32_t *cigar_pool, const char *md_pool, const char *rg_id,
+                        char **text, int64_t *text_off)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->stx = bmh_samtext_stats_t{0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+	std::vector<int64_t> first((size_t)(n > 0 ? n : 0) + 1);
+	int64_t lines = 0;
+	size_t cig_words = 0, md_bytes = 0;
+	int rc = bmh_samtext_check_(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, results, cigar_pool, md_pool, text, text_off, first.data(),
+	                            &lines, &cig_words, &md_bytes);
+	if (rc) return rc;
+	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
+		ctx->last_error = "bmh_sam_text_device needs the resident sequence table (bmh_ctx_set_refidx)";
+		return BMH_E_ARG;
+	}
+	if (ctx->refnames_n == 0 || ctx->refnames_n != bns->n_seqs || ctx->h_refnames != refnames_block(bns)) {
+		ctx->last_error = "bmh_sam_text_device needs the resident sequence names (bmh_ctx_set_refnames)";
+		return BMH_E_ARG;
+	}
+	if (n == 0) {
+		char *p = (char *)malloc(1);
+		if (!p) return BMH_E_NOMEM;
+		*text = p, text_off[0] = 0;
+		return BMH_OK;
+	}
+	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
+	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = (size_t)first[n], l_rg = rg_id ? strlen(rg_id) : 0;
+	if (l_rg > 0x7fffffffu) return BMH_E_ARG;
+	// the device block: everything that goes up, in one piece; then what the kernels make
+	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+	size_t at = 0;
+	auto take = [&](size_t bytes) {
+		const size_t o_ = at;
+		at += al(bytes);
+		return o_;
+	};
+	const size_t o_roff = take((nr + 1) * 8), o_first = take((nr + 1) * 8), o_poff = take((nr + 1) * 8), o_hdr = take(sizeof(SamtextHdr)), o_rg = take(l_rg);
+	const size_t o_nw = take(nr * 4), o_wk = take(total * 4), o_mq = take(total * 4), o_pd = take(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0);
+	const size_t o_reg = take(total * sizeof(bmh_alnreg_t)), o_wr = take(wc * sizeof(bmh_wanted_res_t)), o_cig = take(cig_words * 4), o_md = take(md_bytes);
+	const size_t o_pool = at;
+	std::vector<uint64_t> poff(nr + 1);
+	std::vector<int32_t> l_name(nr), l_com(nr);
+	size_t pool_bytes = 0;
+	for (int i = 0; i < n; ++i) {
+		const size_t ln = strlen(seqs[i].name), lc = seqs[i].comment ? strlen(seqs[i].comment) : 0;
+		if (ln > 0x7fffffffu || lc > 0x7fffffffu) return BMH_E_ARG;
+		l_name[(size_t)i] = (int32_t)ln, l_com[(size_t)i] = seqs[i].comment ? (int32_t)lc : -1;
+		poff[(size_t)i] = pool_bytes;
+		pool_bytes += samtext_read_bytes(ln, (size_t)seqs[i].l_seq, seqs[i].qual != nullptr, l_com[(size_t)i]);
+	}
+	poff[nr] = pool_bytes;
+	at += al(pool_bytes);
+	const size_t b_up = at;
+	const size_t o_alns = take(wc * sizeof(bmh_st_aln_t)), o_plan = take(nr * sizeof(bmh_st_plan_t)), o_size = take(nr * 8), o_toff = take((nr + 1) * 8);
+	const size_t o_stat = take(sizeof(SamtextStatus)), o_end = at;
+	uint8_t *up = (uint8_t *)calloc(b_up, 1);
+	int64_t *toff = (int64_t *)malloc((nr + 1) * 8);
+	char *out = nullptr;
+	struct Free {
+		void *a, *b;
+		char **c;
+		~Free() { free(a), free(b), free(*c); }
+	} guard{up, toff, &out};
+	if (!up || !toff) {
+		ctx->last_error = "bmh_sam_text_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	memcpy(up + o_roff, roff, (nr + 1) * 8), memcpy(up + o_first, first.data(), (nr + 1) * 8), memcpy(up + o_poff, poff.data(), (nr + 1) * 8);
+	SamtextHdr *hdr = (SamtextHdr *)(up + o_hdr);
+	hdr->opt_flag = o->flag, hdr->pe = pe, hdr->l_rg = (int32_t)l_rg;
+	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
+	if (l_rg) memcpy(up + o_rg, rg_id, l_rg);
+	memcpy(up + o_nw, n_want, nr * 4), memcpy(up + o_mq, reg_mapq, total * 4);
+	if (pe) memcpy(up + o_pd, pd, (nr >> 1) * sizeof(bmh_pairdec_t));
+	if (wc) memcpy(up + o_wr, results, wc * sizeof(bmh_wanted_res_t));
+	if (cig_words) memcpy(up + o_cig, cigar_pool, cig_words * 4);
+	if (md_bytes) memcpy(up + o_md, md_pool, md_bytes);
+	for (int i = 0; i < n; ++i) {
+		const bmh_seq_t &s = seqs[i];
+		if (n_want[i]) memcpy(up + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
+		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+		uint8_t *b = up + o_pool + poff[(size_t)i];
+		const SamtextRead h{l_name[(size_t)i], s.l_seq, s.qual != nullptr, l_com[(size_t)i]};
+		memcpy(b, &h, sizeof(h)), b += sizeof(h);
+		memcpy(b, s.name, (size_t)h.l_name), b += h.l_name;
+		if (s.l_seq) memcpy(b, s.seq, (size_t)s.l_seq), b += s.l_seq;
+		if (s.qual && s.l_seq) memcpy(b, s.qual, (size_t)s.l_seq), b += s.l_seq;
+		if (h.l_comment > 0) memcpy(b, s.comment, (size_t)h.l_comment);
+	}
+	long long total_text = 0;
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	if (!ctx->h_ststat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_ststat, sizeof(SamtextStatus), hipHostMallocDefault));
+	const SamtextStatus *hs = (const SamtextStatus *)ctx->h_ststat;
+	Stager st(ctx);
+	st.sx = true;
+	rc = [&]() -> int {
+		int e;
+		if ((e = ensure(ctx, ctx->d_samtext, o_end)) || (e = st.stage(b_up + 256, 0))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_samtext.p;
+		BMH_HIP(ctx, hipMemsetAsync(d + o_stat, 0, sizeof(SamtextStatus), ctx->stream));
+		if ((e = st.h2d(d, up, b_up))) return e;
+		SamtextArgs A{};
+		A.roff = (const int64_t *)(d + o_roff), A.first = (const int64_t *)(d + o_first), A.poff = (const unsigned long long *)(d + o_poff);
+		A.hdr = (const SamtextHdr *)(d + o_hdr), A.rg = (const char *)(d + o_rg);
+		A.n_want = (const int32_t *)(d + o_nw), A.want_k = (const int32_t *)(d + o_wk), A.reg_mapq = (const int32_t *)(d + o_mq);
+		A.pd = (const bmh_pairdec_t *)(d + o_pd), A.reg = (const bmh_alnreg_t *)(d + o_reg), A.wr = (const bmh_wanted_res_t *)(d + o_wr);
+		A.cig = (const uint32_t *)(d + o_cig), A.md = (const char *)(d + o_md), A.rpool = d + o_pool;
+		A.total = total, A.n_w = wc, A.cig_words = cig_words, A.md_bytes = md_bytes, A.rpool_bytes = pool_bytes;
+		A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.name_off = (const uint64_t *)ctx->d_refnames.p;
+		A.names = (const char *)ctx->d_refnames.p + ((size_t)ctx->refnames_n + 1) * 8;
+		A.n_seqs = ctx->refidx_n, A.n = n, A.pe = pe, A.l_pac = bns->l_pac;
+		A.alns = (bmh_st_aln_t *)(d + o_alns), A.plan = (bmh_st_plan_t *)(d + o_plan), A.size = (unsigned long long *)(d + o_size);
+		A.toff = (unsigned long long *)(d + o_toff), A.status = (SamtextStatus *)(d + o_stat), A.text = nullptr, A.text_cap = 0, A.err = ctx->d_err;
+		if ((e = launch_samtext_size(ctx, A))) return e;
+		// the one look between the launches: the text's size and whether a unit was refused
+		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_ststat, d + o_stat, sizeof(SamtextStatus), hipMemcpyDeviceToHost, ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+		++ctx->stx.waits, ctx->stx.d2h_bytes += (int64_t)sizeof(SamtextStatus);
+		if (hs->err) {
+			ctx->last_error = "bmh_sam_text_device: a record lies outside its read, its vector, the pools or the reference";
+			return hs->err;
+		}
+		total_text = hs->total;
+		if (total_text < 0 || total_text > ((long long)1 << 40)) { // cannot happen
+			ctx->last_error = "bmh_sam_text_device: the device's sizes are inconsistent";
+			return BMH_E_ARG;
+		}
+		if (!(out = (char *)malloc((size_t)total_text + 1))) return BMH_E_NOMEM;
+		if ((e = ensure(ctx, ctx->d_sam_out, (size_t)total_text + 64)) || (e = st.stage(b_up + 256, (nr + 1) * 8 + (size_t)total_text + 256))) return e;
+		A.text = (char *)ctx->d_sam_out.p, A.text_cap = (unsigned long long)total_text;
+		if ((e = launch_samtext_emit(ctx, A))) return e;
+		if ((e = st.d2h(toff, d + o_toff, (nr + 1) * 8))) return e;
+		return total_text ? st.d2h(out, ctx->d_sam_out.p, (size_t)total_text) : BMH_OK;
+	}();
+	if ((rc = st.end(rc))) return rc;
+	if (toff[0] != 0 || toff[n] != total_text) { // cannot happen
+		ctx->last_error = "bmh_sam_text_device: the device's offsets are inconsistent";
+		return BMH_E_ARG;
+	}
+	// all or nothing: the caller's outputs only now
+	memcpy(text_off, toff, (nr + 1) * 8);
+	*text = out, out = nullptr;
+	ctx->stx.reads = n, ctx->stx.lines = lines, ctx->stx.text_bytes = total_text;
+	if (ctx->timing) {
+		BMH_HIP(ctx, hipEventElapsedTime(&ctx->stx.size_ms, ctx->ev_samtext[0], ctx->ev_samtext[1]));
+		BMH_HIP(ctx, hipEventElapsedTime(&ctx->stx.emit_ms, ctx->ev_samtext[2], ctx->ev_samtext[3]));
+	}
+	return BMH_OK;
+}
+
+int bmh_ctx_set_samtext_device(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->samtext_device = on != 0;
+	return BMH_OK;
+}
+
+int bmh_last_samtext_stats(const bmh_ctx_t *ctx, bmh_samtext_stats_t *st)
+{
+	if (!ctx || !st) return BMH_E_ARG;
+	*st = ctx->stx;
+	return BMH_OK;
+}
+
+// bmh_sam_batch's pass C (host/sam_post.c; not part of the interface)
+__attribute__((visibility("hidden"))) int bmh_samtext_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n,
+                                                              const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd,
+                                                              const int32_t *reg_mapq, const int32_t *n_want, const int32_t *want_k,
+                                                              const bmh_wanted_res_t *wr, const uint32_t *cig, const char *md, const char *rg_id,
+                                                              char **text, int64_t *text_off)
+{
+	if (ctx && ctx->samtext_device)
+		return bmh_sam_text_device(ctx, o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, text, text_off);
+	return bmh_sam_text_batch(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, text, text_off);
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

@@ -147,6 +147,16 @@ struct bmh_ctx {
 	// pass A and pass B as one device session (api.hip): bmh_phase2_device, and bmh_sam_batch with the switch on
 	bool phase2_device = false;               // bmh_ctx_set_phase2_device
 	bmh_phase2_stats_t p2 = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f}; // of the last fused call (bmh_last_phase2_stats)
+	// pass C of phase 2 on the device (samtext.hip): bmh_sam_text_device, and bmh_sam_batch with the switch on
+	bool samtext_device = false;              // bmh_ctx_set_samtext_device
+	DevBuf d_refnames;                        // n + 1 offsets, then the names' bytes, resident (bmh_ctx_set_refnames)
+	int refnames_n = 0;                       // its names, 0 = none
+	std::vector<char> h_refnames;             // the host's copy of it (offsets and bytes): the same names are not uploaded again
+	DevBuf d_samtext;                         // a call's block: the upload, then records, plans, sizes, offsets, status
+	DevBuf d_sam_out;                         // the text
+	void *h_ststat = nullptr;                 // pinned: the status as the host reads it between scan and emit
+	hipEvent_t ev_samtext[4] = {};            // around the size kernel and the emit kernel (timing mode)
+	bmh_samtext_stats_t stx = {-1, -1, -1, -1, -1, -1, 0, -1.f, -1.f}; // of the last bmh_sam_text_device call (bmh_last_samtext_stats)
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 

@@ -1,0 +1,170 @@
+// samtext.hip -- pass C of phase 2 on the device, behind bmh_sam_text_device (api.hip): from the want list, the regions and pass B's
+// records to SAM text.  The rules -- mem_reg2aln's second half, the mate records and flags of mem_sam_pe / mem_reg2sam_se, mem_aln2sam's
+// columns (reference bwa-0.7.8/bwamem.c:904-1083, :1203-1235) -- are the text of host/samtext_core.h, which gcc compiles for
+// bmh_sam_text_batch: the two give the same bytes.
+//
+//   samtext_size_kernel  one lane per unit (a read, or a pair): checks the unit's offsets, builds its records into alns[], applies the
+//                        per-unit rule (plan[] per read) and runs the composer over the counting sink: size[i] = bytes of read i's lines
+//   samtext_scan_kernel  one block: toff[] = exclusive 64-bit sums of size[], the total into the status word
+//   samtext_emit_kernel  one lane per read: the same composer over the same records, writing into text[toff[i] .. toff[i+1])
+// The writing sink carries the size of the read's slice (samtext_core.h): a byte past it is not stored.  A slice that does not lie in
+// the text buffer is not written at all.  Either raises the error words, and the host delivers nothing.  The emitter's stores are a
+// byte stream per lane, 64 slices per wave: uncoalesced by nature.
+// Nothing on the device trusts an offset it was handed: a unit whose offsets, counts, indices or pool record lie outside the uploaded
+// arrays writes and addresses nothing, and the first error goes to the context's error word and the status by atomicCAS from 0 -- the
+// host launches nothing behind a status with an error.
+#include "samtext.h"
+#include "wanted.h"
+
+namespace bmh {
+
+__device__ __forceinline__ void samtext_fail(const SamtextArgs &A, int code)
+{
+	atomicCAS(A.err, 0, code);
+	atomicCAS(&A.status->err, 0, code);
+}
+
+// read i as the composer sees it, from its record in the pool; false where the record does not lie in the pool
+__device__ __forceinline__ bool samtext_read_view(const SamtextArgs &A, int i, bmh_st_read_t *v)
+{
+	const unsigned long long p0 = A.poff[i], p1 = A.poff[i + 1];
+	if (p0 > p1 || p1 > A.rpool_bytes || p1 - p0 < sizeof(SamtextRead) || (p0 & 7)) return false;
+	const SamtextRead h = *(const SamtextRead *)(A.rpool + p0);
+	if (h.l_name < 0 || h.l_seq < 0 || h.l_comment < -1) return false;
+	if (samtext_read_bytes((size_t)h.l_name, (size_t)h.l_seq, h.has_qual != 0, h.l_comment) > p1 - p0) return false;
+	const char *b = (const char *)(A.rpool + p0 + sizeof(SamtextRead));
+	v->name = b, v->l_name = h.l_name, b += h.l_name;
+	v->seq = (const uint8_t *)b, v->l_seq = h.l_seq, b += h.l_seq;
+	v->qual = h.has_qual ? b : nullptr, b += h.has_qual ? h.l_seq : 0;
+	v->comment = h.l_comment >= 0 ? b : nullptr, v->l_comment = h.l_comment >= 0 ? h.l_comment : 0, v->rsv_ = 0;
+	return true;
+}
+
+__device__ __forceinline__ void samtext_env(const SamtextArgs &A, bmh_st_env_t *E)
+{
+	E->names.pool = A.names, E->names.off = A.name_off, E->names.n_seqs = A.n_seqs, E->names.rsv_ = 0;
+	E->cig = A.cig, E->md = A.md, E->rg_id = A.rg, E->l_rg = A.hdr->l_rg, E->rsv_ = 0;
+}
+
+// read i's offsets and counts against the arrays, then its records; false where something lies outside
+__device__ __forceinline__ bool samtext_records(const SamtextArgs &A, const bmh_rp_refv_t &rv, int i, int l_seq)
+{
+	const int64_t r0 = A.roff[i], r1 = A.roff[i + 1], f0 = A.first[i], f1 = A.first[i + 1];
+	if (r0 < 0 || r0 > r1 || (unsigned long long)r1 > A.total || f0 < 0 || f0 > f1 || (unsigned long long)f1 > A.n_w) return false;
+	if (f1 - f0 != (int64_t)A.n_want[i] || f1 - f0 > r1 - r0) return false;
+	for (int64_t q = f0; q < f1; ++q) {
+		const int k = A.want_k[r0 + (q - f0)];
+		if (k < 0 || (int64_t)k >= r1 - r0) return false;
+		const bmh_wanted_res_t x = A.wr[q];
+		if (x.n_cigar < 0 || (unsigned long long)x.cigar_off + (unsigned long long)x.n_cigar > A.cig_words) return false;
+		if ((unsigned long long)x.md_off + (unsigned long long)x.md_len > A.md_bytes) return false;
+		const bmh_alnreg_t ar = A.reg[r0 + k];
+		bmh_st_aln_t a;
+		if (bmh_st_record(&rv, &x, &ar, A.reg_mapq[r0 + k], l_seq, A.cig, &a)) return false;
+		A.alns[q] = a;
+	}
+	return true;
+}
+
+__global__ __launch_bounds__(256) void samtext_size_kernel(SamtextArgs A)
+{
+	const int pe = A.pe != 0, nr = pe ? 2 : 1;
+	const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (u * nr + nr > (long long)A.n) return;
+	const int i0 = (int)(u * nr);
+	bmh_rp_refv_t rv;
+	rv.off0 = &A.ref[0].offset, rv.len0 = &A.ref[0].len, rv.stride = sizeof(bmh_refspan_t), rv.n_seqs = A.n_seqs, rv.l_pac = A.l_pac;
+	bmh_st_read_t rd[2];
+	bool ok = true;
+	for (int r = 0; r < nr; ++r) {
+		A.size[i0 + r] = 0;
+		ok = ok && samtext_read_view(A, i0 + r, &rd[r]) && samtext_records(A, rv, i0 + r, rd[r].l_seq);
+	}
+	if (!ok) {
+		samtext_fail(A, BMH_E_ARG);
+		return;
+	}
+	const int32_t *const wk[2] = {A.want_k + A.roff[i0], pe ? A.want_k + A.roff[i0 + 1] : nullptr};
+	const bmh_alnreg_t *const ra[2] = {A.reg + A.roff[i0], pe ? A.reg + A.roff[i0 + 1] : nullptr};
+	bmh_st_unit(A.hdr->opt_flag, A.l_pac, A.hdr->pes, pe, pe ? &A.pd[u] : nullptr, A.first + i0, wk, ra, A.alns, A.plan + i0);
+	bmh_st_env_t E;
+	samtext_env(A, &E);
+	for (int r = 0; r < nr; ++r) {
+		const int i = i0 + r;
+		bmh_st_sink_t t = {nullptr, 0, 0, 0, 0};
+		bmh_st_read_text(&E, &t, &rd[r], &A.plan[i], (int)(A.first[i + 1] - A.first[i]), A.alns + A.first[i]);
+		if (t.err || t.l < 0) {
+			samtext_fail(A, BMH_E_ARG);
+			return;
+		}
+		A.size[i] = (unsigned long long)t.l;
+	}
+}
+
+__global__ __launch_bounds__(kScanThreads) void samtext_scan_kernel(SamtextArgs A)
+{
+	__shared__ unsigned long long s[2 * (kScanThreads / 64) + 1];
+	const int t = threadIdx.x;
+	unsigned long long carry = 0;
+	for (int base = 0; base < A.n; base += kScanThreads) { // tiles of one read per lane: neighbouring lanes read neighbouring words
+		const int i = base + t;
+		unsigned long long v[1] = {i < A.n ? A.size[i] : 0}, total[1];
+		block_excl_scan<unsigned long long, 1>(s, v, total);
+		if (i < A.n) A.toff[i] = carry + v[0];
+		carry += total[0];
+	}
+	if (t == 0) {
+		A.toff[A.n] = carry;
+		A.status->total = (long long)carry;
+	}
+}
+
+__global__ __launch_bounds__(256) void samtext_emit_kernel(SamtextArgs A)
+{
+	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= (long long)A.n) return;
+	const unsigned long long o0 = A.toff[i], o1 = A.toff[i + 1];
+	bmh_st_read_t rd;
+	if (o0 > o1 || o1 > A.text_cap || o1 - o0 != A.size[i] || !samtext_read_view(A, (int)i, &rd)) { // a slice outside the buffer: nothing is written
+		samtext_fail(A, BMH_E_ARG);
+		return;
+	}
+	bmh_st_env_t E;
+	samtext_env(A, &E);
+	bmh_st_sink_t t = {A.text + o0, 0, (int64_t)(o1 - o0), 0, 0};
+	bmh_st_read_text(&E, &t, &rd, &A.plan[i], (int)(A.first[i + 1] - A.first[i]), A.alns + A.first[i]);
+	if (t.err || t.l != t.cap) samtext_fail(A, BMH_E_ARG); // (cannot happen: the records and the composer the size came from)
+}
+
+static int samtext_events(bmh_ctx *ctx, int k)
+{
+	if (!ctx->timing) return BMH_OK;
+	if (!ctx->ev_samtext[k]) BMH_HIP(ctx, hipEventCreate(&ctx->ev_samtext[k]));
+	BMH_HIP(ctx, hipEventRecord(ctx->ev_samtext[k], ctx->stream));
+	return BMH_OK;
+}
+
+int launch_samtext_size(bmh_ctx *ctx, const SamtextArgs &A)
+{
+	int rc;
+	if (A.n <= 0) return BMH_OK;
+	const long long units = A.pe ? A.n >> 1 : A.n;
+	if ((rc = samtext_events(ctx, 0))) return rc;
+	hipLaunchKernelGGL(samtext_size_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, A);
+	if ((rc = samtext_events(ctx, 1))) return rc;
+	hipLaunchKernelGGL(samtext_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, A);
+	BMH_HIP(ctx, hipGetLastError());
+	return BMH_OK;
+}
+
+int launch_samtext_emit(bmh_ctx *ctx, const SamtextArgs &A)
+{
+	int rc;
+	if (A.n <= 0) return BMH_OK;
+	if ((rc = samtext_events(ctx, 2))) return rc;
+	hipLaunchKernelGGL(samtext_emit_kernel, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, ctx->stream, A);
+	BMH_HIP(ctx, hipGetLastError());
+	return samtext_events(ctx, 3);
+}
+
+} // namespace bmh

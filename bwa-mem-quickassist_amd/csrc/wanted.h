@@ -58,6 +58,46 @@ struct WantedArgs {
 	int *err;
 };
 
+// ---- the one-block scan of the planning kernels, also samtext.hip's (the sizes of a slice's reads)
+constexpr int kScanThreads = 1024;
+
+// Exclusive sums over the block of K values per thread, in thread order; total[] = the block's sums.  Wave scans by shuffle, the 16
+// wave totals through LDS (s: 2 * K * 16 + K entries), two barriers and one behind for the next tile.
+template <class T, int K> __device__ __forceinline__ void block_excl_scan(T *s, T v[K], T total[K])
+{
+	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	constexpr int W = kScanThreads / 64;
+	T inc[K];
+	for (int c = 0; c < K; ++c) {
+		T x = v[c];
+		for (int d = 1; d < 64; d <<= 1) {
+			const T y = __shfl_up(x, d);
+			if (lane >= d) x += y;
+		}
+		inc[c] = x;
+		if (lane == 63) s[c * W + wave] = x;
+	}
+	__syncthreads();
+	if (wave == 0) {
+		for (int c = 0; c < K; ++c) {
+			const T w = lane < W ? s[c * W + lane] : 0;
+			T x = w;
+			for (int d = 1; d < W; d <<= 1) {
+				const T y = __shfl_up(x, d);
+				if (lane >= d) x += y;
+			}
+			if (lane < W) s[K * W + c * W + lane] = x - w;
+			if (lane == W - 1) s[2 * K * W + c] = x;
+		}
+	}
+	__syncthreads();
+	for (int c = 0; c < K; ++c) {
+		v[c] = inc[c] - v[c] + s[K * W + c * W + wave];
+		total[c] = s[2 * K * W + c];
+	}
+	__syncthreads();
+}
+
 // first[] and the xref test; then round 0's plan.  Behind it status[0] is complete.
 int launch_wanted_begin(bmh_ctx *ctx, const WantedArgs &A);
 // the cut of the regions round 0 aligned, then every region's plan.  Behind it rec[] and status[1] are complete.

@@ -23,50 +23,11 @@
 
 namespace bmh {
 
-constexpr int kScanThreads = 1024;
-
 __device__ __forceinline__ void wanted_fail(const WantedArgs &A, int code)
 {
 	atomicCAS(A.err, 0, code);
 	atomicCAS(&A.status[0].err, 0, code);
 	atomicCAS(&A.status[1].err, 0, code);
-}
-
-// Exclusive sums over the block of K values per thread, in thread order; total[] = the block's sums.  Wave scans by shuffle, the 16
-// wave totals through LDS (s: 2 * K * 16 + K entries), two barriers and one behind for the next tile.
-template <class T, int K> __device__ __forceinline__ void block_excl_scan(T *s, T v[K], T total[K])
-{
-	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	constexpr int W = kScanThreads / 64;
-	T inc[K];
-	for (int c = 0; c < K; ++c) {
-		T x = v[c];
-		for (int d = 1; d < 64; d <<= 1) {
-			const T y = __shfl_up(x, d);
-			if (lane >= d) x += y;
-		}
-		inc[c] = x;
-		if (lane == 63) s[c * W + wave] = x;
-	}
-	__syncthreads();
-	if (wave == 0) {
-		for (int c = 0; c < K; ++c) {
-			const T w = lane < W ? s[c * W + lane] : 0;
-			T x = w;
-			for (int d = 1; d < W; d <<= 1) {
-				const T y = __shfl_up(x, d);
-				if (lane >= d) x += y;
-			}
-			if (lane < W) s[K * W + c * W + lane] = x - w;
-			if (lane == W - 1) s[2 * K * W + c] = x;
-		}
-	}
-	__syncthreads();
-	for (int c = 0; c < K; ++c) {
-		v[c] = inc[c] - v[c] + s[K * W + c * W + wave];
-		total[c] = s[2 * K * W + c];
-	}
-	__syncthreads();
 }
 
 // what read i contributes: its n_want, or 0 and an error where its offsets or its count are outside the arrays

@@ -31,6 +31,9 @@
  *   BMH_PHASE2_DEVICE=1  pass A and pass B as ONE device session (bmh_ctx_set_phase2_device): the regions go up once and the want
  *                        list never leaves the device between the two.  Needs BMH_PAC_RESIDENT not 0.  A slice the fused call
  *                        refuses as out of range goes the way the two switches above say.
+ *   BMH_SAMTEXT_DEVICE=1 its pass C -- coordinates, clipping, flags and the SAM text -- as kernels (bmh_ctx_set_samtext_device), with the
+ *                        sequence table and the sequence names resident.  Needs no resident reference (BMH_PAC_RESIDENT=0 is fine);
+ *                        independent of the other switches.  The text is the same bytes either way.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -457,6 +460,19 @@ static int qa_phase2_device(void)
 }
 static long long g_phase2_cnt[5]; /* units, regions, fixed, redone on the host, slices that fell back to the two passes */
 
+/* BMH_SAMTEXT_DEVICE=1: phase 2's pass C on the device (bmh_ctx_set_samtext_device on every pooled context phase 2 uses, with the
+ * sequence table and the names made resident).  It reads no base of the reference, so it does not need BMH_PAC_RESIDENT. */
+static int qa_samtext_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_SAMTEXT_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_samtext_cnt[3]; /* reads, lines, bytes of text */
+
 /* BMH_REGS_DEVICE=1: seeding, chaining and the chains-to-regions driver in one device call (bmh_seed_chain_regs_batch) */
 static int qa_regs_device(void)
 {
@@ -713,6 +729,9 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 	}
 	if ((rc = bmh_ctx_set_wanted_device(ctx, qa_wanted_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	if ((rc = bmh_ctx_set_phase2_device(ctx, qa_phase2_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
+	if (qa_samtext_device() && ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns)) || (rc = bmh_ctx_set_refnames(ctx, (const bmh_refidx_t *)J->bns))))
+		bmh_tls_die(bmh_last_error(ctx), rc);
+	if ((rc = bmh_ctx_set_samtext_device(ctx, qa_samtext_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	return ctx;
 }
 
@@ -785,6 +804,12 @@ static void qa_sam_slice(void *data, int k, int tid)
 		__sync_fetch_and_add(&g_phase2_cnt[0], (long long)(ps.units > 0 ? ps.units : 0)), __sync_fetch_and_add(&g_phase2_cnt[1], (long long)(ps.wanted > 0 ? ps.wanted : 0));
 		__sync_fetch_and_add(&g_phase2_cnt[2], (long long)(ps.fixed > 0 ? ps.fixed : 0)), __sync_fetch_and_add(&g_phase2_cnt[3], (long long)(ps.redone > 0 ? ps.redone : 0));
 		__sync_fetch_and_add(&g_phase2_cnt[4], (long long)(ps.fallbacks > 0 ? ps.fallbacks : 0));
+	}
+	if (qa_samtext_device()) {
+		bmh_samtext_stats_t ts;
+		bmh_last_samtext_stats(ctx, &ts);
+		__sync_fetch_and_add(&g_samtext_cnt[0], (long long)(ts.reads > 0 ? ts.reads : 0)), __sync_fetch_and_add(&g_samtext_cnt[1], (long long)(ts.lines > 0 ? ts.lines : 0));
+		__sync_fetch_and_add(&g_samtext_cnt[2], (long long)(ts.text_bytes > 0 ? ts.text_bytes : 0));
 	}
 	bmh_pool_put(ctx);
 	t2 = stage_now();
@@ -915,6 +940,8 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		if (qa_phase2_device())
 			fprintf(stderr, "[bwamem_hip] phase 2 on the device in one session: %lld units, %lld regions, %lld fixed, %lld redone on the host, %lld host fall-backs\n",
 			        g_phase2_cnt[0], g_phase2_cnt[1], g_phase2_cnt[2], g_phase2_cnt[3], g_phase2_cnt[4]);
+		if (qa_samtext_device())
+			fprintf(stderr, "[bwamem_hip] SAM text on the device: %lld reads, %lld lines, %lld bytes\n", g_samtext_cnt[0], g_samtext_cnt[1], g_samtext_cnt[2]);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */
 			fprintf(stderr, "[bwamem_hip] wide extension so far: %lld extension tasks on the int32 kernel\n", bmh_pool_wide_tasks());
 			fprintf(stderr, "[bwamem_hip] wide Smith-Waterman so far: %lld ksw_align2 tasks on the long-query kernel\n", bmh_pool_swl_tasks());

@@ -17,7 +17,8 @@
  *      (bwa_fix_xref2 needs one bwa_gen_cigar2 each), then all of them through bmh_reg2cigar_batch (band inference and
  *      the <= 3 widening tries of mem_reg2aln)
  *   C  per read / pair: coordinates, clipping, flags, text
- * No per-region mallocs: alignments live in per-slice arrays, text grows in one buffer per read.
+ *      (bmh_sam_text_batch over samtext_core.h: sized first, then written into one pool per slice)
+ * No per-region mallocs: alignments live in per-slice arrays.
  */
 #include <math.h>
 #include <stdio.h>
@@ -30,6 +31,7 @@
 #include "dedup_core.h"
 #include "postproc_core.h"
 #include "regplan_core.h"
+#include "samtext_core.h"
 #include "sort_exact.h"
 
 static double now_s(void) /* the clock of the BMH_DRIVER_TRACE lines: wall time, or with BMH_TRACE_CPU this thread's CPU time */
@@ -254,200 +256,6 @@ __attribute__((visibility("hidden"))) void bmh_pp_fill_term_(const bmh_sam_opt_t
 
 /* ================================================================================================ alignments and text */
 
-typedef struct { /* mem_aln_t (bwamem.h:72-82) with the CIGAR in a slice arena and the MD string kept apart */
-	int64_t pos;
-	int rid, flag, is_rev, mapq, NM, n_cigar, score, sub;
-	uint32_t cig_off; /* first word in the slice's CIGAR arena */
-	const char *md;
-} aln_t;
-
-typedef struct { /* text under construction: kstring_t without the per-call growth checks */
-	char *s;
-	size_t l, m;
-} str_t;
-
-static inline void st_room(str_t *t, size_t extra)
-{
-	if (t->l + extra + 1 > t->m) {
-		t->m = (t->l + extra + 1) * 2;
-		t->s = (char *)realloc(t->s, t->m);
-	}
-}
-static inline void st_c(str_t *t, char c) { st_room(t, 1), t->s[t->l++] = c; }
-static inline void st_n(str_t *t, const char *p, size_t n) { st_room(t, n), memcpy(t->s + t->l, p, n), t->l += n; }
-static inline void st_s(str_t *t, const char *p) { st_n(t, p, strlen(p)); }
-static void st_l(str_t *t, long c) /* kputw / kputl, kstring.h:62-111 */
-{
-	char buf[32];
-	int l = 0;
-	unsigned long x = c < 0 ? 0ul - (unsigned long)c : (unsigned long)c;
-	if (c == 0) { st_c(t, '0'); return; }
-	for (; x > 0; x /= 10) buf[l++] = (char)('0' + x % 10);
-	if (c < 0) buf[l++] = '-';
-	st_room(t, (size_t)l);
-	while (l > 0) t->s[t->l++] = buf[--l];
-}
-
-static inline int rlen_of(int n_cigar, const uint32_t *cigar) /* get_rlen, bwamem.c:893-902 */
-{
-	int k, l;
-	for (k = l = 0; k < n_cigar; ++k) {
-		const int op = (int)(cigar[k] & 0xf);
-		if (op == 0 || op == 2) l += (int)(cigar[k] >> 4);
-	}
-	return l;
-}
-
-/* ---- One SAM line (what mem_aln2sam prints, bwamem.c:904-1017), built the way this library is: the record and its mate are first
- * RESOLVED into a small value (flag bits, where an unmapped end is placed, clip lengths), then a fixed table of column emitters
- * writes the eleven mandatory columns and the tags from that value.  `cig` is the slice's CIGAR arena. */
-typedef struct {
-	int mapped;           /* has a reference sequence to print (its own, or the mate's for an unmapped end) */
-	int rid, rev, n_op;   /* n_op = 0 when the end only borrows its mate's position */
-	int64_t pos;
-	const uint32_t *op;
-} place_t;
-
-typedef struct {
-	const bmh_refidx_t *bns;
-	const bmh_seq_t *read;
-	const aln_t *all;     /* the read's records (for SA:Z) */
-	int n_all, self;      /* ... and which one this line is */
-	const aln_t *rec;
-	const uint32_t *cig;
-	const char *rg_id;
-	int flag, has_mate;
-	place_t me, mate;
-} samline_t;
-
-static place_t place_of(const aln_t *a, const uint32_t *cig)
-{
-	place_t p;
-	p.mapped = a->rid >= 0, p.rid = a->rid, p.rev = a->is_rev, p.n_op = a->n_cigar, p.pos = a->pos, p.op = cig + a->cig_off;
-	return p;
-}
-/* an unmapped end sits where its mapped mate is, without a CIGAR (bwamem.c:917-918) */
-static void borrow_place(place_t *dst, const place_t *src) { dst->mapped = 1, dst->rid = src->rid, dst->pos = src->pos, dst->rev = src->rev, dst->n_op = 0; }
-
-static int clip_len(const place_t *p, int at) /* length of a clip operation at CIGAR index `at`, else 0 */
-{
-	const int op = (int)(p->op[at] & 0xf);
-	return op == 3 || op == 4 ? (int)(p->op[at] >> 4) : 0;
-}
-static int64_t far_end(const place_t *p) { return p->pos + (p->rev ? rlen_of(p->n_op, p->op) - 1 : 0); } /* 5' end on the reference */
-
-/* bases or qualities of [from,to) in the orientation of the alignment; `code` maps a base code to its letter (NULL: copy bytes) */
-static void put_oriented(str_t *t, const char *src, int from, int to, int rev, const char *code)
-{
-	int i, n = to > from ? to - from : 0;
-	char *d;
-	st_room(t, (size_t)n + 2);
-	d = t->s + t->l;
-	if (!rev) for (i = 0; i < n; ++i) d[i] = code ? code[(int)src[from + i]] : src[from + i];
-	else for (i = 0; i < n; ++i) d[i] = code ? code[(int)src[to - 1 - i]] : src[to - 1 - i];
-	t->l += (size_t)n;
-}
-enum { CLIP_SOFT, CLIP_HARD, CLIP_ASIS }; /* clips of the first line are S, of a supplementary line H; SA:Z prints what is stored */
-static void put_ops(str_t *t, const uint32_t *op, int n, int clips)
-{
-	int i;
-	for (i = 0; i < n; ++i) {
-		int c = (int)(op[i] & 0xf);
-		if (clips != CLIP_ASIS && (c == 3 || c == 4)) c = clips == CLIP_HARD ? 4 : 3;
-		st_l(t, (long)(op[i] >> 4)), st_c(t, "MIDSH"[c]);
-	}
-}
-
-static void col_qname_flag(const samline_t *L, str_t *t)
-{
-	st_s(t, L->read->name), st_c(t, '\t');
-	st_l(t, (L->flag & 0xffff) | (L->flag & 0x10000 ? 0x100 : 0)); /* -M: a supplementary hit is shown as secondary (bwamem.c:928) */
-}
-static void col_rname_pos_mapq_cigar(const samline_t *L, str_t *t)
-{
-	if (!L->me.mapped) { st_n(t, "*\t0\t0\t*", 7); return; }
-	st_s(t, L->bns->anns[L->me.rid].name), st_c(t, '\t');
-	st_l(t, (long)(L->me.pos + 1)), st_c(t, '\t');
-	st_l(t, L->rec->mapq), st_c(t, '\t');
-	if (L->me.n_op) put_ops(t, L->me.op, L->me.n_op, L->self ? CLIP_HARD : CLIP_SOFT);
-	else st_c(t, '*');
-}
-static void col_mate(const samline_t *L, str_t *t)
-{
-	if (!L->has_mate || !L->mate.mapped) { st_n(t, "*\t0\t0", 5); return; }
-	if (L->me.rid == L->mate.rid) st_c(t, '=');
-	else st_s(t, L->bns->anns[L->mate.rid].name);
-	st_c(t, '\t'), st_l(t, (long)(L->mate.pos + 1)), st_c(t, '\t');
-	if (L->me.rid == L->mate.rid && L->me.n_op && L->mate.n_op) { /* TLEN between the two 5' ends (bwamem.c:957-961) */
-		const int64_t d = far_end(&L->me) - far_end(&L->mate);
-		st_l(t, (long)-(d + (d > 0) - (d < 0)));
-	} else st_c(t, '0');
-}
-static void col_seq_qual(const samline_t *L, str_t *t)
-{
-	int from = 0, to = L->read->l_seq;
-	if (L->flag & 0x100) { st_n(t, "*\t*", 3); return; } /* none on secondary lines */
-	if (L->self && L->me.n_op) { /* a supplementary line prints only what it aligns: its clips are hard (bwamem.c:971-976) */
-		const int c5 = clip_len(&L->me, 0), c3 = clip_len(&L->me, L->me.n_op - 1);
-		if (L->me.rev) from += c3, to -= c5;
-		else from += c5, to -= c3;
-	}
-	put_oriented(t, L->read->seq, from, to, L->me.rev, L->me.rev ? "TGCAN" : "ACGTN");
-	st_c(t, '\t');
-	if (L->read->qual) put_oriented(t, L->read->qual, from, to, L->me.rev, 0);
-	else st_c(t, '*');
-}
-static void col_tags(const samline_t *L, str_t *t)
-{
-	const aln_t *r = L->rec;
-	int i, others = 0;
-	if (L->me.n_op) st_n(t, "\tNM:i:", 6), st_l(t, r->NM), st_n(t, "\tMD:Z:", 6), st_s(t, r->md);
-	if (r->score >= 0) st_n(t, "\tAS:i:", 6), st_l(t, r->score);
-	if (r->sub >= 0) st_n(t, "\tXS:i:", 6), st_l(t, r->sub);
-	if (L->rg_id && L->rg_id[0]) st_n(t, "\tRG:Z:", 6), st_s(t, L->rg_id);
-	if (!(L->flag & 0x100)) { /* SA:Z lists the read's other non-secondary lines (bwamem.c:995-1013) */
-		for (i = 0; i < L->n_all; ++i) others += i != L->self && !(L->all[i].flag & 0x100);
-		if (others) st_n(t, "\tSA:Z:", 6);
-		for (i = 0; others && i < L->n_all; ++i) {
-			const aln_t *o = &L->all[i];
-			if (i == L->self || (o->flag & 0x100) || o->rid < 0) continue;
-			st_s(t, L->bns->anns[o->rid].name), st_c(t, ','), st_l(t, (long)(o->pos + 1)), st_c(t, ',');
-			st_c(t, o->is_rev ? '-' : '+'), st_c(t, ',');
-			put_ops(t, L->cig + o->cig_off, o->n_cigar, CLIP_ASIS);
-			st_c(t, ','), st_l(t, o->mapq), st_c(t, ','), st_l(t, o->NM), st_c(t, ';');
-		}
-	}
-	if (L->read->comment) st_c(t, '\t'), st_s(t, L->read->comment);
-}
-
-typedef void (*sam_col_fn)(const samline_t *, str_t *);
-static const sam_col_fn k_sam_cols[] = {col_qname_flag, col_rname_pos_mapq_cigar, col_mate, col_seq_qual};
-
-static void aln2sam(const bmh_refidx_t *bns, str_t *str, const bmh_seq_t *s, int n, const aln_t *list, int which, const aln_t *mate,
-                    const uint32_t *cig, const char *rg_id)
-{
-	samline_t L;
-	size_t c;
-	L.bns = bns, L.read = s, L.all = list, L.n_all = n, L.self = which, L.rec = &list[which], L.cig = cig, L.rg_id = rg_id;
-	L.has_mate = mate != 0;
-	L.me = place_of(L.rec, cig);
-	L.flag = L.rec->flag | (mate ? 0x1 : 0) | (L.me.mapped ? 0 : 0x4);
-	if (mate) {
-		L.mate = place_of(mate, cig);
-		if (!L.mate.mapped) L.flag |= 0x8;
-		if (!L.me.mapped && L.mate.mapped) borrow_place(&L.me, &L.mate);
-		else if (!L.mate.mapped && L.me.mapped) borrow_place(&L.mate, &L.me);
-		if (L.mate.rev) L.flag |= 0x20;
-	}
-	if (L.me.rev) L.flag |= 0x10;
-	for (c = 0; c < sizeof(k_sam_cols) / sizeof(k_sam_cols[0]); ++c) k_sam_cols[c](&L, str), st_c(str, '\t');
-	--str->l; /* the tags bring their own separators */
-	col_tags(&L, str);
-	st_c(str, '\n');
-}
-
-/* ---- bntseq.h:83-86, bntseq.c:316-330 */
-static inline int64_t depos(int64_t l_pac, int64_t pos, int *is_rev) { return (*is_rev = pos >= l_pac) ? (l_pac << 1) - 1 - pos : pos; }
 static bmh_rp_refv_t refv_of(const bmh_refidx_t *bns) /* the reference sequences as regplan_core.h walks them */
 {
 	bmh_rp_refv_t v;
@@ -457,12 +265,6 @@ static bmh_rp_refv_t refv_of(const bmh_refidx_t *bns) /* the reference sequences
 }
 
 const bmh_params_t *bmh_ctx_params_(const bmh_ctx_t *ctx);
-
-static void unmapped(aln_t *a) /* mem_reg2aln(..., 0), bwamem.c:1171-1175 */
-{
-	memset(a, 0, sizeof(*a));
-	a->rid = -1, a->pos = -1, a->flag |= 0x4;
-}
 
 /* ================================================================================================ pass B: the alignments
  * bwa_fix_xref2 (bwa.c:179-222) for the few regions that hang over the end of a reference sequence (one bwa_gen_cigar2 each), then
@@ -659,6 +461,130 @@ __attribute__((visibility("hidden"))) int bmh_wanted_check_args_(bmh_ctx_t *ctx,
 	return wanted_check_args(ctx, bns, pac, n, reads, regs, roff, n_want, want_k, n_w);
 }
 
+/* ================================================================================================ pass C: coordinates and text
+ * mem_reg2aln's second half (bwamem.c:1203-1235) and mem_reg2sam_se / mem_aln2sam (bwamem.c:904-1083) for a slice, over samtext_core.h,
+ * the text the kernels of bmh_sam_text_device (csrc/samtext.hip) run: here only the checks, the arrays and the two passes. */
+
+/* what both forms refuse before anything runs (host only).  first: n + 1 entries, first[i] = wanted regions before read i; *lines = SAM
+ * lines of the slice; *cig_words / *md_bytes = how far the records reach into the two pools */
+__attribute__((visibility("hidden"))) int bmh_samtext_check_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
+                                                             const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq,
+                                                             const int32_t *n_want, const int32_t *want_k, const bmh_wanted_res_t *wr, const uint32_t *cig,
+                                                             const char *md, char **text, int64_t *text_off, int64_t *first, int64_t *lines, size_t *cig_words,
+                                                             size_t *md_bytes)
+{
+	const int pe = o && (o->flag & BMH_MEM_F_PE) != 0;
+	int64_t at = 0, w = 0, j, nl = 0;
+	size_t cw = 0, mb = 0;
+	int i, q;
+	*lines = 0, *cig_words = 0, *md_bytes = 0;
+	if (!o || !bns || !text || !text_off || n < 0 || (pe && ((n & 1) || !pes))) return BMH_E_ARG;
+	if (n == 0) return BMH_OK;
+	if (!first || !seqs || !regs || !roff || !reg_mapq || !n_want || !want_k || (pe && !pd)) return BMH_E_ARG;
+	if (bns->l_pac <= 0 || bns->n_seqs <= 0 || !bns->anns) return BMH_E_ARG;
+	for (i = 0; i < bns->n_seqs; ++i)
+		if (!bns->anns[i].name) return BMH_E_ARG;
+	for (i = 0; i < n; ++i) {
+		if ((regs[i].n && !regs[i].a) || regs[i].n > 0x7fffffffu || roff[i] != at) return BMH_E_ARG;
+		if (n_want[i] < 0 || (size_t)n_want[i] > regs[i].n) return BMH_E_ARG;
+		if (!seqs[i].name || seqs[i].l_seq < 0 || (seqs[i].l_seq > 0 && !seqs[i].seq)) return BMH_E_ARG;
+		for (q = 0; q < n_want[i]; ++q)
+			if (want_k[at + q] < 0 || (size_t)want_k[at + q] >= regs[i].n) return BMH_E_ARG;
+		first[i] = w;
+		at += (int64_t)regs[i].n, w += n_want[i];
+		nl += pe && pd[i >> 1].paired ? 1 : n_want[i] ? n_want[i] : 1;
+	}
+	first[n] = w;
+	if (roff[n] != at || (w > 0 && (!wr || !cig || !md))) return BMH_E_ARG;
+	for (j = 0; j < w; ++j) {
+		if (wr[j].n_cigar < 0) return BMH_E_ARG;
+		if ((size_t)wr[j].cigar_off + (size_t)wr[j].n_cigar > cw) cw = (size_t)wr[j].cigar_off + (size_t)wr[j].n_cigar;
+		if ((size_t)wr[j].md_off + (size_t)wr[j].md_len > mb) mb = (size_t)wr[j].md_off + (size_t)wr[j].md_len;
+	}
+	for (i = 0; pe && i < n; i += 2)
+		if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) {
+			fprintf(stderr, "[bwamem_hip] paired reads have different names: \"%s\", \"%s\"\n", seqs[i].name, seqs[i + 1].name);
+			return BMH_E_ARG;
+		}
+	*lines = nl, *cig_words = cw, *md_bytes = mb;
+	return BMH_OK;
+}
+
+int bmh_sam_text_batch(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,
+                       const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq, const int32_t *n_want, const int32_t *want_k,
+                       const bmh_wanted_res_t *results, const uint32_t *cigar_pool, const char *md_pool, const char *rg_id, char **text, int64_t *text_off)
+{
+	const int pe = o && (o->flag & BMH_MEM_F_PE) != 0, nr = pe ? 2 : 1;
+	bmh_rp_refv_t rv;
+	bmh_st_env_t E;
+	bmh_st_read_t *rd = 0;
+	bmh_st_aln_t *alns = 0;
+	bmh_st_plan_t *plan = 0;
+	int64_t *first = 0, *off = 0, lines, j;
+	uint64_t *noff = 0;
+	char *npool = 0, *buf = 0;
+	size_t cw, mb, nb = 0;
+	int i, r, rc;
+
+	if (n > 0 && !(first = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1)))) return BMH_E_NOMEM;
+	if ((rc = bmh_samtext_check_(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, results, cigar_pool, md_pool, text, text_off, first, &lines,
+	                             &cw, &mb)))
+		goto done;
+	if (n == 0) {
+		if (!(buf = (char *)malloc(1))) return BMH_E_NOMEM;
+		*text = buf, text_off[0] = 0;
+		return BMH_OK;
+	}
+	rv = refv_of(bns);
+	for (i = 0; i < bns->n_seqs; ++i) nb += strlen(bns->anns[i].name);
+	noff = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)bns->n_seqs + 1)), npool = (char *)malloc(nb + 1);
+	rd = (bmh_st_read_t *)malloc(sizeof(*rd) * (size_t)n);
+	alns = (bmh_st_aln_t *)malloc(sizeof(*alns) * ((size_t)first[n] + 1));
+	plan = (bmh_st_plan_t *)malloc(sizeof(*plan) * (size_t)n);
+	off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+	if (!noff || !npool || !rd || !alns || !plan || !off) { rc = BMH_E_NOMEM; goto done; }
+	for (i = 0, nb = 0; i < bns->n_seqs; ++i) {
+		const size_t l = strlen(bns->anns[i].name);
+		noff[i] = nb, memcpy(npool + nb, bns->anns[i].name, l), nb += l;
+	}
+	noff[bns->n_seqs] = nb;
+	E.names.pool = npool, E.names.off = noff, E.names.n_seqs = bns->n_seqs, E.names.rsv_ = 0;
+	E.cig = cigar_pool, E.md = md_pool, E.rg_id = rg_id, E.l_rg = rg_id ? (int32_t)strlen(rg_id) : 0, E.rsv_ = 0;
+	for (i = 0; i < n; ++i) { /* the records, in want order */
+		const bmh_seq_t *s = &seqs[i];
+		bmh_st_read_t *v = &rd[i];
+		v->name = s->name, v->l_name = (int32_t)strlen(s->name), v->comment = s->comment, v->l_comment = s->comment ? (int32_t)strlen(s->comment) : 0;
+		v->qual = s->qual, v->seq = (const uint8_t *)s->seq, v->l_seq = s->l_seq, v->rsv_ = 0;
+		for (j = first[i]; j < first[i + 1]; ++j) {
+			const int k = want_k[roff[i] + (j - first[i])];
+			if ((rc = bmh_st_record(&rv, &results[j], &regs[i].a[k], reg_mapq[roff[i] + k], s->l_seq, cigar_pool, &alns[j]))) goto done;
+		}
+	}
+	for (i = 0; i < n; i += nr) { /* the per-unit rule */
+		const int32_t *const wk[2] = {want_k + roff[i], pe ? want_k + roff[i + 1] : 0};
+		const bmh_alnreg_t *const ra[2] = {regs[i].a, pe ? regs[i + 1].a : 0};
+		bmh_st_unit(o->flag, bns->l_pac, pes, pe, pe ? &pd[i >> 1] : 0, first + i, wk, ra, alns, plan + i);
+	}
+	for (i = 0, off[0] = 0; i < n; ++i) { /* the size of every read's lines, then the same composer into slices of exactly that size */
+		bmh_st_sink_t t = {0, 0, 0, 0, 0};
+		bmh_st_read_text(&E, &t, &rd[i], &plan[i], (int)(first[i + 1] - first[i]), alns + first[i]);
+		if (t.err) { rc = BMH_E_ARG; goto done; }
+		off[i + 1] = off[i] + t.l;
+	}
+	if (!(buf = (char *)malloc((size_t)off[n] + 1))) { rc = BMH_E_NOMEM; goto done; }
+	for (i = 0, r = 0; i < n; ++i) {
+		bmh_st_sink_t t = {buf + off[i], 0, off[i + 1] - off[i], 0, 0};
+		r += bmh_st_read_text(&E, &t, &rd[i], &plan[i], (int)(first[i + 1] - first[i]), alns + first[i]);
+		if (t.err || t.l != t.cap) { rc = BMH_E_ARG; goto done; } /* (cannot happen: the same records, the same composer) */
+	}
+	if (r != lines) { rc = BMH_E_ARG; goto done; } /* (cannot happen) */
+	memcpy(text_off, off, sizeof(int64_t) * ((size_t)n + 1));
+	*text = buf, buf = 0;
+done:
+	free(first), free(off), free(noff), free(npool), free(rd), free(alns), free(plan), free(buf);
+	return rc;
+}
+
 /* pass A behind the context's switch (csrc/api.hip): bmh_decide_device while bmh_ctx_set_decide_device is on, falling back to
  * bmh_decide_batch where that answers BMH_E_RANGE; bmh_decide_batch otherwise */
 void bmh_decide_stats_reset_(bmh_ctx_t *ctx);
@@ -675,26 +601,26 @@ int bmh_wanted_routed_(bmh_ctx_t *ctx, const bmh_refidx_t *bns, const uint8_t *p
 int bmh_phase2_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
                        const bmh_read_t *reads, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want,
                        int32_t *want_k, int64_t *n_w, bmh_wanted_res_t **wr, uint32_t **cig, char **md, int *done);
+/* pass C behind the context's switch (csrc/api.hip): bmh_sam_text_device while bmh_ctx_set_samtext_device is on, else
+ * bmh_sam_text_batch above; *text is malloc'd */
+int bmh_samtext_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
+                        const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq, const int32_t *n_want,
+                        const int32_t *want_k, const bmh_wanted_res_t *wr, const uint32_t *cig, const char *md, const char *rg_id, char **text,
+                        int64_t *text_off);
 
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id)
 {
 	const int pe = (o->flag & BMH_MEM_F_PE) != 0;
 	const int64_t l_pac = bns ? bns->l_pac : 0;
-	bmh_rp_refv_t rv;
 	bmh_wanted_res_t *wr = 0; /* the wanted regions, in want order: final coordinates and alignments */
-	int32_t *wk = 0;          /* ... and the region index of each in its read's vector */
 	int64_t n_w = 0;
 	bmh_pairdec_t *pd = 0;
-	int64_t *roff = 0;
+	int64_t *roff = 0, *text_off = 0;
 	int32_t *reg_mapq = 0, *n_want = 0, *want_k = 0;
 	bmh_read_t *reads = 0;
-	uint32_t *cig = 0, *arena = 0;
-	char *md = 0;
-	size_t *first = 0; /* first entry of W per read (+1 sentinel) */
-	aln_t *alns = 0;
-	str_t str = {0, 0, 0};
-	size_t j, arena_words = 0;
+	uint32_t *cig = 0;
+	char *md = 0, *text = 0;
 	int i, rc = BMH_OK, fused = 0;
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0;
 	double tt[4] = {0, 0, 0, 0};
@@ -702,13 +628,11 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	bmh_decide_stats_reset_(ctx);
 	if (!ctx || !o || !bns || !pac || n < 0 || (n > 0 && (!seqs || !regs)) || (pe && ((n & 1) || !pes))) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
-	rv = refv_of(bns);
-	first = (size_t *)calloc((size_t)n + 1, sizeof(size_t));
 	reads = (bmh_read_t *)malloc(sizeof(bmh_read_t) * (size_t)n);
 	roff = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
 	n_want = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
 	if (pe) pd = (bmh_pairdec_t *)calloc((size_t)(n >> 1), sizeof(bmh_pairdec_t));
-	if (!first || !reads || !roff || !n_want || (pe && !pd)) { rc = BMH_E_NOMEM; goto done; }
+	if (!reads || !roff || !n_want || (pe && !pd)) { rc = BMH_E_NOMEM; goto done; }
 	for (i = 0; i < n; ++i) reads[i].l_seq = seqs[i].l_seq, reads[i].seq = (const uint8_t *)seqs[i].seq;
 	for (i = 0, roff[0] = 0; i < n; ++i) {
 		if (regs[i].n && !regs[i].a) { rc = BMH_E_ARG; goto done; }
@@ -731,139 +655,33 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	if (trace) tt[1] = now_s();
 	/* ---- pass B: bwa_fix_xref2 (bwa.c:179-222), then the alignments: bmh_wanted_cigar_batch's work, or with
 	 * bmh_ctx_set_wanted_device on bmh_wanted_cigar_device's (the same records either way) */
-	if (n_w) {
-		if (!fused) wr = (bmh_wanted_res_t *)malloc(sizeof(*wr) * (size_t)n_w);
-		wk = (int32_t *)malloc(sizeof(*wk) * (size_t)n_w);
-		if (!wr || !wk) { rc = BMH_E_NOMEM; goto done; }
-		if (!fused && (rc = bmh_wanted_routed_(ctx, bns, pac, o->w, n, reads, regs, roff, n_want, want_k, n_w, wr, &cig, &md))) goto done;
-		for (j = 0; j < (size_t)n_w; ++j) arena_words += (size_t)wr[j].n_cigar + 2;
+	if (n_w && !fused) {
+		wr = (bmh_wanted_res_t *)malloc(sizeof(*wr) * (size_t)n_w);
+		if (!wr) { rc = BMH_E_NOMEM; goto done; }
+		if ((rc = bmh_wanted_routed_(ctx, bns, pac, o->w, n, reads, regs, roff, n_want, want_k, n_w, wr, &cig, &md))) goto done;
 	}
-	for (i = 0, j = 0; i < n; ++i) { /* first entry of the want list per read */
-		int q;
-		first[i] = j;
-		for (q = 0; q < n_want[i]; ++q) wk[j++] = want_k[roff[i] + q];
-	}
-	first[n] = j;
 
 	if (trace) tt[2] = now_s();
-	/* ---- pass C: mem_reg2aln's second half (bwamem.c:1203-1235) for every wanted region, then the text */
-	alns = (aln_t *)malloc(sizeof(aln_t) * ((size_t)n_w + 2));
-	arena = (uint32_t *)malloc(4 * (arena_words + 4));
-	if (!alns || !arena) { rc = BMH_E_NOMEM; goto done; }
-	arena_words = 0;
-	for (i = 0, j = 0; i < n; ++i)
-	for (; j < first[i + 1]; ++j) {
-		const bmh_wanted_res_t *x = &wr[j];
-		const bmh_alnreg_t *ar = &regs[i].a[wk[j]];
-		const int l_query = seqs[i].l_seq;
-		aln_t *a = &alns[j];
-		const uint32_t *src = cig + x->cigar_off;
-		uint32_t *dst = arena + arena_words;
-		int nc = x->n_cigar, is_rev, k, clip5, clip3;
-		int64_t pos;
-		memset(a, 0, sizeof(*a));
-		a->mapq = ar->secondary < 0 ? reg_mapq[roff[i] + wk[j]] : 0;
-		if (ar->secondary >= 0) a->flag |= 0x100;
-		a->NM = x->NM, a->md = md + x->md_off;
-		pos = depos(l_pac, x->rb < l_pac ? x->rb : x->re - 1, &is_rev);
-		a->is_rev = is_rev;
-		if (nc > 0) { /* squeeze out a leading or trailing deletion */
-			if ((src[0] & 0xf) == 2) pos += src[0] >> 4, ++src, --nc;
-			else if ((src[nc - 1] & 0xf) == 2) --nc;
+	/* ---- pass C: mem_reg2aln's second half (bwamem.c:1203-1235) for every wanted region, then the text: bmh_sam_text_batch, or with
+	 * bmh_ctx_set_samtext_device on bmh_sam_text_device (the same bytes either way); then one string per read */
+	text_off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+	if (!text_off) { rc = BMH_E_NOMEM; goto done; }
+	if ((rc = bmh_samtext_routed_(ctx, o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, &text, text_off))) goto done;
+	for (i = 0; i < n; ++i) {
+		const size_t len = (size_t)(text_off[i + 1] - text_off[i]);
+		char *s = (char *)malloc(len + 1);
+		if (!s) { /* all or nothing */
+			while (--i >= 0) free(seqs[i].sam), seqs[i].sam = 0;
+			rc = BMH_E_NOMEM;
+			goto done;
 		}
-		clip5 = is_rev ? l_query - x->qe : x->qb, clip3 = is_rev ? x->qb : l_query - x->qe;
-		a->cig_off = (uint32_t)arena_words;
-		k = 0;
-		if (x->qb != 0 || x->qe != l_query) { /* soft clipping */
-			if (clip5) dst[k++] = (uint32_t)clip5 << 4 | 3;
-			memcpy(dst + k, src, 4 * (size_t)nc), k += nc;
-			if (clip3) dst[k++] = (uint32_t)clip3 << 4 | 3;
-		} else memcpy(dst, src, 4 * (size_t)nc), k = nc;
-		a->n_cigar = k, arena_words += (size_t)k;
-		a->rid = bmh_rp_pos2rid(&rv, pos);
-		a->pos = pos - bns->anns[a->rid].offset;
-		a->score = ar->score, a->sub = ar->sub > ar->csub ? ar->sub : ar->csub;
-	}
-	for (i = 0; i < n; i += pe ? 2 : 1) {
-		const int nr = pe ? 2 : 1;
-		aln_t h[2], un;
-		int r, extra = 0;
-		if (i + 8 < n) { /* a read's name, bases and qualities are three allocations of the host program's: scattered */
-			const bmh_seq_t *nx = &seqs[i + 8];
-			__builtin_prefetch(nx->name), __builtin_prefetch(nx->seq), __builtin_prefetch(nx->seq + 64), __builtin_prefetch(nx->seq + 128);
-			if (nx->qual) __builtin_prefetch(nx->qual), __builtin_prefetch(nx->qual + 64), __builtin_prefetch(nx->qual + 128);
-			if (pe) {
-				++nx;
-				__builtin_prefetch(nx->name), __builtin_prefetch(nx->seq), __builtin_prefetch(nx->seq + 64), __builtin_prefetch(nx->seq + 128);
-				if (nx->qual) __builtin_prefetch(nx->qual), __builtin_prefetch(nx->qual + 64), __builtin_prefetch(nx->qual + 128);
-			}
-		}
-		unmapped(&un);
-		if (pe) {
-			const bmh_pairdec_t *d = &pd[i >> 1];
-			extra = d->extra_flag;
-			if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) {
-				fprintf(stderr, "[bwamem_hip] paired reads have different names: \"%s\", \"%s\"\n", seqs[i].name, seqs[i + 1].name);
-				rc = BMH_E_ARG;
-				goto done;
-			}
-			for (r = 0; r < 2; ++r) { /* the mate records: the pair's two alignments, or each end's best hit (bwamem_pair.c:311-312,320-324) */
-				const size_t f0 = first[i + r], f1 = first[i + r + 1];
-				if (d->paired) {
-					if (f1 > f0) h[r] = alns[f0], h[r].mapq = d->q_se[r];
-					else unmapped(&h[r]);
-					h[r].flag |= (r ? 0x80 : 0x40) | extra;
-				} else if (f1 > f0 && wk[f0] == 0) h[r] = alns[f0]; /* regs[].a[0] with score >= T */
-				else unmapped(&h[r]);
-			}
-			if (d->paired) {
-				for (r = 0; r < 2; ++r) {
-					str.l = 0;
-					aln2sam(bns, &str, &seqs[i + r], 1, &h[r], 0, &h[!r], arena, rg_id);
-					st_room(&str, 1), str.s[str.l] = 0;
-					seqs[i + r].sam = (char *)malloc(str.l + 1);
-					memcpy(seqs[i + r].sam, str.s, str.l + 1);
-				}
-				continue;
-			}
-			if (!(o->flag & BMH_MEM_F_NOPAIRING) && h[0].rid == h[1].rid && h[0].rid >= 0) { /* the two top hits make a proper pair? */
-				int64_t dist;
-				const int dd = bmh_pp_infer_dir(l_pac, regs[i].a[0].rb, regs[i + 1].a[0].rb, &dist);
-				if (!pes[dd].failed && dist >= pes[dd].low && dist <= pes[dd].high) extra |= 2;
-			}
-		}
-		for (r = 0; r < nr; ++r) { /* mem_reg2sam_se, bwamem.c:1049-1083 */
-			const int rd = i + r;
-			const size_t f0 = first[rd], f1 = first[rd + 1];
-			const int extra_flag = pe ? ((r ? 0x81 : 0x41) | extra) : 0;
-			const aln_t *mate = pe ? &h[!r] : 0;
-			size_t q;
-			str.l = 0;
-			for (q = f0; q < f1; ++q) { /* alns[f0..f1) is the reference's `aa` */
-				const int k = wk[q];
-				const bmh_alnreg_t *p = &regs[rd].a[k];
-				aln_t *a = &alns[q];
-				a->flag |= extra_flag;
-				if (p->secondary >= 0) a->sub = -1;
-				if (k && p->secondary < 0) a->flag |= (o->flag & BMH_MEM_F_NO_MULTI) ? 0x10000 : 0x800; /* supplementary */
-				if (k && a->mapq > alns[f0].mapq) a->mapq = alns[f0].mapq;
-			}
-			if (f1 == f0) {
-				aln_t t = un;
-				t.flag |= extra_flag;
-				aln2sam(bns, &str, &seqs[rd], 1, &t, 0, mate, arena, rg_id);
-			} else
-				for (q = f0; q < f1; ++q) aln2sam(bns, &str, &seqs[rd], (int)(f1 - f0), &alns[f0], (int)(q - f0), mate, arena, rg_id);
-			st_room(&str, 1), str.s[str.l] = 0;
-			seqs[rd].sam = (char *)malloc(str.l + 1);
-			memcpy(seqs[rd].sam, str.s, str.l + 1);
-		}
+		memcpy(s, text + text_off[i], len), s[len] = 0;
+		seqs[i].sam = s;
 	}
 	if (trace)
 		fprintf(stderr, "[bwamem_hip] bmh_sam_batch %d reads, %zu alignments: marking + pairing %.1f ms, global alignments (bmh_reg2cigar_batch) %.1f ms, coordinates + text %.1f ms\n",
 		        n, (size_t)n_w, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3);
 done:
-	free(wr), free(wk), free(pd), free(reads), free(cig), free(md), free(first), free(alns), free(arena), free(roff), free(reg_mapq),
-	    free(n_want), free(want_k), free(str.s);
+	free(wr), free(pd), free(reads), free(cig), free(md), free(roff), free(reg_mapq), free(n_want), free(want_k), free(text), free(text_off);
 	return rc;
 }

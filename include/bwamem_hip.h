@@ -597,7 +597,8 @@ int bmh_pair(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], c
  * rg_id: the reference's bwa_rg_id ("" = none).  regs[i].a is left sorted/marked as the reference leaves it.
  * The decisions (everything before the global alignments) are bmh_decide_batch's, or with bmh_ctx_set_decide_device on
  * bmh_decide_device's: the same text either way (below).  With bmh_ctx_set_phase2_device on, decisions and alignments are one device
- * session, bmh_phase2_device's: the same text again. */
+ * session, bmh_phase2_device's: the same text again.  The text itself (pass C) is bmh_sam_text_batch's, or with
+ * bmh_ctx_set_samtext_device on bmh_sam_text_device's: the same bytes (below).  All or nothing: on an error no seqs[i].sam is set. */
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id);
 
@@ -729,6 +730,60 @@ typedef struct bmh_phase2_stats {
 	float decide_ms, wanted_ms;
 } bmh_phase2_stats_t;
 int bmh_last_phase2_stats(const bmh_ctx_t *ctx, bmh_phase2_stats_t *st);
+
+/* ---- Pass C of bmh_sam_batch on its own: coordinates, clipping, flags and SAM text (mem_reg2aln's second half, bwamem.c:1203-1235;
+ * mem_reg2sam_se and mem_aln2sam, bwamem.c:904-1083; the mate records of mem_sam_pe, bwamem_pair.c:311-324) of exactly the regions pass
+ * A listed, from the alignments pass B made, for reads [0,n) of a chunk slice.  One text, host/samtext_core.h, compiled by gcc for the
+ * host call and by hipcc for the device call: both give the same bytes.  Needs no context.
+ *   o, bns, pes, n, seqs, regs, roff   as bmh_sam_batch and bmh_decide_batch have them, the vectors as pass A left them; of seqs the
+ *             name, comment, seq (base codes), qual and l_seq are read, sam is not touched
+ *   pd, reg_mapq, n_want, want_k       pass A's outputs (pd NULL for single-end reads)
+ *   results, cigar_pool, md_pool       pass B's outputs: the records in want order and the pools their cigar_off / md_off address
+ *   rg_id     the reference's bwa_rg_id ("" or NULL = none)
+ *   text      *text = one malloc'd pool, which the caller frees
+ *   text_off  n + 1 entries: read i's SAM lines are (*text)[text_off[i] .. text_off[i+1]), each line ending in '\n'; no NUL in the pool
+ * BMH_E_ARG: what bmh_sam_batch refuses of these (a NULL o, bns, or with n > 0 seqs or regs; n < 0; odd n or no pes with PE; a vector with
+ * n > 0 and no array), a NULL text, text_off or with n > 0 pass A output, roff that does not match the vectors, n_want or want_k
+ * outside a vector, a read without a name or with l_seq > 0 and no seq, records or pools missing where a region is wanted, a record
+ * outside its read or the reference, mates whose names differ (with bmh_sam_batch's message).  n == 0: BMH_OK, an empty pool,
+ * text_off[0] = 0.  All or nothing: on any error *text and text_off are untouched. */
+int bmh_sam_text_batch(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
+                       const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq,
+                       const int32_t *n_want, const int32_t *want_k, const bmh_wanted_res_t *results, const uint32_t *cigar_pool,
+                       const char *md_pool, const char *rg_id, char **text, int64_t *text_off);
+/* The same as kernels (csrc/samtext.hip), the same bytes out.  One upload: offsets (roff, the want list's first[], the read pool's
+ * offsets: 3 x 8 (n + 1) bytes), a 128-byte header, rg_id, n_want, want_k and reg_mapq (4 bytes per read / region), pd, the regions, the
+ * records, the CIGAR words and MD bytes the records reach, and a per-read byte pool packed by the host: per read 16 bytes of lengths,
+ * then name, base codes, qualities and comment, rounded up to 8 bytes.  samtext_size_kernel (one lane per read or pair: the records,
+ * the per-unit rule, the composer counting), an exclusive 64-bit scan, samtext_emit_kernel (one lane per read: the composer writing into
+ * the read's slice).  The host reads one 16-byte status between scan and emit (total and error flag) and sizes the text buffer from
+ * it: two waits per call.  One download: text_off and the text.
+ * Needs the sequence table (bmh_ctx_set_refidx) and the sequence names (bmh_ctx_set_refnames) resident, neither parameters nor the
+ * 2-bit reference.  BMH_E_ARG: a NULL ctx, a missing table or one of another reference, and what bmh_sam_text_batch refuses.  A write
+ * past a read's slice or a slice outside the buffer is not made: it raises the context's error flag and the call fails, nothing
+ * written. */
+int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
+                        const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq,
+                        const int32_t *n_want, const int32_t *want_k, const bmh_wanted_res_t *results, const uint32_t *cigar_pool,
+                        const char *md_pool, const char *rg_id, char **text, int64_t *text_off);
+/* Copies the name of every reference sequence of bns to the device (one byte pool plus offsets), where it stays like the sequence
+ * table; NULL drops it. */
+int bmh_ctx_set_refnames(bmh_ctx_t *ctx, const bmh_refidx_t *bns);
+/* Per context, off by default, independent of every other switch.  While on, bmh_sam_batch takes its pass C from bmh_sam_text_device
+ * (BMH_E_ARG without the two resident tables).  The text is the same either way. */
+int bmh_ctx_set_samtext_device(bmh_ctx_t *ctx, int on);
+/* Of the last bmh_sam_text_device call on this context, direct or from bmh_sam_batch with the switch on; all -1 before the first.  With
+ * the switch on bmh_sam_batch sets them to 0 (the milliseconds to -1) at its entry.
+ *   reads, lines, text_bytes       of the slice
+ *   h2d_bytes, d2h_bytes, waits    of the session: the upload above; the status, text_off and the text; 2
+ *   size_ms, emit_ms               the two kernels' milliseconds with bmh_set_kernel_timing on, else -1 */
+typedef struct bmh_samtext_stats {
+	int64_t reads, lines, text_bytes;
+	int64_t h2d_bytes, d2h_bytes;
+	int32_t waits, rsv_;
+	float size_ms, emit_ms;
+} bmh_samtext_stats_t; /* 56 bytes */
+int bmh_last_samtext_stats(const bmh_ctx_t *ctx, bmh_samtext_stats_t *st);
 
 /* ------------------------------------------------------------------------------------------------------------
  * FM-index queries of the seeding stage (first slice): super-maximal exact matches and suffix-
