@@ -194,6 +194,8 @@ def lib():
         L.bmh_last_extend_bin_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_last_global_bin_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_last_global_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.bmh_ctx_set_extend_rows.argtypes = [C.c_void_p, C.c_int64]
+        L.bmh_last_extend_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_last_seedext_round_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_extend_bin_ms_sum.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
         L.bmh_upload_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -400,6 +402,18 @@ class Context:
         bands = np.zeros(int(n), dtype=np.uint8)
         self._check(lib().bmh_last_global_bands(self._h, _ptr(bands), int(n)))
         return bands
+
+    def set_extend_rows(self, cap):
+        """Diagnostic: plain extension launches record the rows each lane-kernel task ran, for task indices below cap; 0 turns it
+        off (bmh_ctx_set_extend_rows)."""
+        self._check(lib().bmh_ctx_set_extend_rows(self._h, int(cap)))
+
+    def last_extend_rows(self, n):
+        """The rows tasks 0..n-1 of the most recent plain extension launch ran, by task index (uint16; 0xffff: no lane kernel took
+        the task).  Raises when nothing was recorded or n is past the launch's cap (bmh_last_extend_rows)."""
+        rows = np.zeros(int(n), dtype=np.uint16)
+        self._check(lib().bmh_last_extend_rows(self._h, _ptr(rows), int(n)))
+        return rows
 
     # ---- L2, host buffers
     def upload_pool(self, pool):

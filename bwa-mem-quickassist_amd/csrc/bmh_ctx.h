@@ -80,6 +80,10 @@ struct bmh_ctx {
 	int ncu = 256; // compute units of the device (persistent grids are sized from it)
 	bool ext_persist = false; // extension lane kernels as one strided launch with a capped grid (env BMH_EXT_PERSIST=1)
 	int ext_grid_mult = 2; // extension lane kernels: grid cap = resident waves x this (env BMH_EXT_GRID_MULT)
+	int ext_stop = 1;      // extension lane kernels end a flank once no later row can change its result (host/extstop_core.h; env BMH_EXT_STOP=0 turns it off)
+	int64_t ext_rows_cap = 0; // diagnostic (bmh_ctx_set_extend_rows): plain extension launches record the rows each lane-kernel task ran, for task indices below this
+	DevBuf d_ext_rows;        // ... uint16 by task index, 0xffff where no lane kernel took the task
+	int64_t ext_rows_n = 0;   // entries the last extension launch recorded into (its ext_rows_cap), 0 if it recorded none (bmh_last_extend_rows)
 	// Bin sizes of the extension dispatcher are only known on the device.  After every launch they are copied to pinned
 	// memory WITHOUT waiting; the next launch of the same kind (plain API call, or stage k of the fused per-seed
 	// pipeline) reads whatever has arrived and sizes its grids / picks the kernel of bin 3 from it.  A stale or missing
@@ -300,6 +304,8 @@ __device__ __forceinline__ bool ext_goes_wide(int qlen, int h0, int max_mat)
 // sort key inside a bin: query-length bucket (major; lanes of a wave then share the unused leading columns,
 // which the lane kernels skip), h0 bucket, and expected row count (minor; lanes of a wave then finish together).
 // rows run at most to tlen, and the band leaves the query after ~qlen+w <= 2*qlen rows (ksw.c:418).
+// (With the lane kernels' early stop, DESIGN.md 4.3, a good flank ends near row qlen instead.  Two minor keys that follow that -- h0 to
+// the base, and tlen - qlen -- were measured level or slower than this one, profiles/ext_stop.md, so it stays.)
 __device__ __forceinline__ int ext_sort_key(int bin, int qlen, int tlen, int h0)
 {
 	if (bin > 4) return 0;

@@ -213,6 +213,7 @@ struct ExtPlan {
 static int extend_plan(bmh_ctx *ctx, int64_t n, int kind, bool device_count, ExtPlan *pl)
 {
 	const bool gaps_wide = ext_gaps_too_large(ctx->params);
+	ctx->ext_rows_n = 0;
 	if (gaps_wide && !ctx->wide_ext) {
 		ctx->last_error = "the extension kernels need o_del+e_del, o_ins+e_ins <= 65535 and e_del, e_ins <= 16383";
 		return BMH_E_RANGE;
@@ -311,6 +312,12 @@ static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_ta
 	int64_t est[kExtBins];
 	for (int b = 0; b < kExtBins; ++b) est[b] = hint.valid ? std::min<int64_t>(n, (int64_t)hint.cnt[b] + (hint.cnt[b] >> 4) + 64) : n;
 	if ((rc = hint_post(ctx, kind, counts))) return rc;
+	if (ctx->ext_rows_cap > 0 && kind == 0) { // the diagnostic of bmh_last_extend_rows: the lane kernels write it, everything else leaves 0xffff
+		const size_t bytes = (size_t)ctx->ext_rows_cap * sizeof(uint16_t);
+		if ((rc = ensure(ctx, ctx->d_ext_rows, bytes))) return rc;
+		BMH_HIP(ctx, hipMemsetAsync(ctx->d_ext_rows.p, 0xff, bytes, ctx->stream));
+		ctx->ext_rows_n = ctx->ext_rows_cap;
+	}
 	const bool tm = ctx->timing;
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
 	// Bins 0-2 (lane-per-task kernels, almost all tasks) run on the caller's stream; the few long flanks of bins 3-5

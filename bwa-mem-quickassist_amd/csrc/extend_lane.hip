@@ -19,13 +19,15 @@
 //   * the interval update (ksw.c:463-466) needs no second pass: while walking the columns a lane tracks the
 //     last zero seen, the last zero left of the running maximum and the first zero right of it;
 //   * all tasks of a wave start together at row 0, so the row index and the loop are wave-uniform; a lane that
-//     finishes (m==0, z-drop, last row) writes its result and idles until the wave is done.  The dispatcher
-//     hands this kernel tasks SORTED by expected row count, so lanes of a wave finish together.
+//     finishes (m==0, z-drop, last row, or no later row can change its result: host/extstop_core.h) writes its
+//     result and idles until the wave is done.  The dispatcher hands this kernel tasks SORTED by expected row
+//     count, so lanes of a wave finish together.
 #include <algorithm>
 #include <type_traits>
 
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "../host/extstop_core.h"
 
 namespace bmh {
 
@@ -44,6 +46,8 @@ __device__ __forceinline__ int bfi2(int mask, int a, int b) { return __builtin_a
 // SYM: o_del+e_del == o_ins+e_ins (bwa's default) -> H-oe is computed once per cell for both gap states
 // LOOP: the block walks the bin with a grid stride from chunk `chunk0` on (persistent grid; costs the register allocator
 // some per-row scratch traffic at C = 128); !LOOP: one chunk per block, chunk = chunk0 + blockIdx.x.
+// stop_a: the allowance per column of the early-stop rule (host/extstop_core.h): max(mat) with the rule on, BMH_EXTSTOP_OFF without.
+// rows_out (nullable, a diagnostic): per task index below rows_cap the rows it ran, written where the lane writes its result.
 template <int C, bool SYM, bool LOOP>
 __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(const uint8_t *__restrict__ pool,
                                                          const bmh_ext_task_t *__restrict__ tasks,
@@ -51,7 +55,8 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
                                                          const uint32_t *__restrict__ count, long long n,
                                                          bmh_ext_result_t *__restrict__ out, DevParams P,
                                                          int *__restrict__ err_flag, long long chunk0,
-                                                         const uint32_t *__restrict__ skip)
+                                                         const uint32_t *__restrict__ skip, int stop_a,
+                                                         uint16_t *__restrict__ rows_out, uint32_t rows_cap)
 {
 	constexpr int NW = C / 32, NQ = C / 4, NB = C / 8;
 	constexpr int INF = 0x7fff;
@@ -109,6 +114,7 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 	if (valid && bad) {
 		int *p = (int *)(out + idx);
 		p[0] = INT32_MIN, p[1] = p[2] = p[3] = p[4] = p[5] = 0;
+		if (rows_out && idx < rows_cap) rows_out[idx] = 0;
 		atomicExch(err_flag, BMH_E_RANGE);
 	}
 	const int off = C - min(max(qlen, 1), C);
@@ -152,6 +158,7 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 	if (valid && !bad && tlen == 0) { // no rows at all
 		int *p = (int *)(out + idx);
 		p[0] = h0, p[1] = 0, p[2] = 0, p[3] = 0, p[4] = -1, p[5] = 0;
+		if (rows_out && idx < rows_cap) rows_out[idx] = 0;
 	}
 	uint8_t *strm = (uint8_t *)stage;
 
@@ -178,6 +185,8 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 			am[v] = hi > lo ? (int)((0xffffffffu >> (32 - (hi - lo))) << lo) : 0;
 		}
 		int f = 0, hprev = left, kmax = -1, hlast = -1;
+		// the early-stop bound U_i (extstop_core.h), begun with the row's own first-column value; a finished lane's is junk
+		int ub = bmh_extstop_first(left, stop_a, C - lb);
 		int nz[NW]; // bit p set <=> h(i,p) != 0 (junk for columns outside the interval; masked with am[] below)
 #pragma unroll
 		for (int v = 0; v < NW; ++v) nz[v] = 0;
@@ -227,6 +236,8 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 			};
 			if (edge) cells(std::true_type{});
 			else if constexpr (kLaneInterior) cells(std::false_type{});
+			// the row maximum up to here (negative: no live column of this lane yet) and the columns right of the block's first one
+			ub = bmh_extstop_block(ub, kmax >> 16, stop_a, C - 1 - 8 * b);
 		}
 		// ---- row end, per lane
 		gk = max(gk, hlast << 16 | i); // column qlen-1 live in this row: ksw.c:447-450 (ties -> later row)
@@ -261,12 +272,18 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 		}
 		begp = lzm + 2;
 		endp = min(fz == INF ? le + 1 : fz + 1, C);
-		const bool done = alive && (stop0 || zd || i + 1 >= tlen);
+		const bool stopr = bmh_extstop_test(ub, best, gk >> 16); // no later row can change a result (gk < 0: gscore == -1, never)
+		const bool done = alive && (stop0 || zd || i + 1 >= tlen || stopr);
 		if (done) { // results, ksw.c:470-475
 			alive = false;
 			int *p = (int *)(out + idx);
 			p[0] = best, p[1] = bjp - off + 1, p[2] = bi + 1;
 			p[3] = gk < 0 ? 0 : (gk & 0xffff) + 1, p[4] = gk < 0 ? -1 : gk >> 16, p[5] = maxoff;
+			if (rows_out) { // (the slot's address is taken from p behind a barrier: computed ahead of the row loop it would occupy two registers throughout)
+				asm volatile("" : "+v"(p));
+				const size_t k = (size_t)((bmh_ext_result_t *)p - out);
+				if (k < rows_cap) rows_out[k] = (uint16_t)(i + 1);
+			}
 		}
 	}
 	} // chunk loop
@@ -278,6 +295,8 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                        bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip)
 {
+	const int stop_a = bmh_extstop_factor(ctx->ext_stop, ctx->params.mat, ctx->dev.o_del, ctx->dev.e_del, ctx->dev.o_ins, ctx->dev.e_ins);
+	uint16_t *d_rows = ctx->ext_rows_n > 0 ? (uint16_t *)ctx->d_ext_rows.p : nullptr; // (set per launch by the dispatcher)
 	if (n <= 0) return BMH_OK;
 	const bool sym = ctx->dev.o_del + ctx->dev.e_del == ctx->dev.o_ins + ctx->dev.e_ins;
 	const long long chunks = (n + 63) / 64;
@@ -286,7 +305,7 @@ int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext
 	const long long n_head = ctx->ext_persist && d_skip ? (1LL << 40) : (long long)n;
 #define BMH_LAUNCH_LANE2(CC, SY, LP, GRID, C0)                                                                          \
 	hipLaunchKernelGGL((extend_lane_kernel<CC, SY, LP>), dim3((unsigned)(GRID)), dim3(64), 0, ctx->stream, d_pool, d_tasks,  \
-	                   d_order, d_count, n_head, d_res, ctx->dev, ctx->d_err, (long long)(C0), d_skip)
+	                   d_order, d_count, n_head, d_res, ctx->dev, ctx->d_err, (long long)(C0), d_skip, stop_a, d_rows, (uint32_t)ctx->ext_rows_n)
 #define BMH_LAUNCH_LANE(CC, LP, GRID, C0)                                                                               \
 	do {                                                                                                                \
 		if (sym) BMH_LAUNCH_LANE2(CC, true, LP, GRID, C0);                                                              \

@@ -286,6 +286,17 @@ int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3]);
  * launched yet, or the workspace was grown since by bmh_ctx_reserve_device).  A call that makes several global launches leaves
  * the last one's bands.  Waits for the stream and copies n bytes; the launches themselves do nothing for it. */
 int bmh_last_global_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n);
+/* Diagnostic: the DP rows each task of a plain extension launch ran.  The lane-per-task kernels end a flank once no later row can
+ * change any of its six results (BMH_EXT_STOP=0 in the environment of bmh_ctx_create turns that off), so this is at
+ * most what ksw_extend2 runs.  With cap > 0, bmh_extend_batch and bmh_extend_batch_device keep cap x uint16 on the device, indexed as
+ * the result array is -- by task index -- which the lane kernels fill, for indices below cap, where they write a result.  cap = 0
+ * (the default): they get a null pointer and do nothing for it. */
+int bmh_ctx_set_extend_rows(bmh_ctx_t *ctx, int64_t cap);
+/* rows[k] belongs to task k of the most recent plain extension launch: the rows it ran, 0 for a task that ran none or was refused,
+ * 0xffff where no lane kernel took it (queries past 128 columns, small batches, the other BMH_EXT_MODEs, an index d_order does not
+ * list).  n <= the cap that launch ran with; BMH_E_ARG when it is not or when nothing was recorded.  Waits for the stream and copies
+ * 2 n bytes. */
+int bmh_last_extend_rows(bmh_ctx_t *ctx, uint16_t *rows, int64_t n);
 /* What the global-alignment launches of this context so far sent to bin 4, the band-ring kernel (tasks with more than 10 176
  * query columns that no lane kernel takes): *tasks = their number, *ms = the ring kernel's time summed over the launches made
  * with timing on (-1 when timing is off).  The counterpart of bmh_extend_wide_stats.  Waits for the stream. */
