@@ -196,6 +196,7 @@ def lib():
         L.bmh_last_global_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_ctx_set_extend_rows.argtypes = [C.c_void_p, C.c_int64]
         L.bmh_last_extend_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.bmh_last_extend_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_last_seedext_round_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_extend_bin_ms_sum.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]
         L.bmh_upload_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -414,6 +415,14 @@ class Context:
         rows = np.zeros(int(n), dtype=np.uint16)
         self._check(lib().bmh_last_extend_rows(self._h, _ptr(rows), int(n)))
         return rows
+
+    def last_extend_bands(self, n):
+        """Diagnostic: the band each of the n entries of the most recent extension launch with a band pass was run on, by input
+        position (uint8; 255 = the task's own, 255 or wider).  Raises when that launch had no band pass or another entry count
+        (bmh_last_extend_bands)."""
+        bands = np.zeros(int(n), dtype=np.uint8)
+        self._check(lib().bmh_last_extend_bands(self._h, _ptr(bands), int(n)))
+        return bands
 
     # ---- L2, host buffers
     def upload_pool(self, pool):

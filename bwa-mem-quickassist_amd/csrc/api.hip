@@ -284,6 +284,8 @@ int bmh_ctx_create(bmh_ctx_t **out, int device)
 	if (const char *m = getenv("BMH_EXT_SPLIT96")) ctx->ext_split96 = atoi(m) != 0; // (A/B knob)
 	if (const char *m = getenv("BMH_EXT_GRID_MULT")) ctx->ext_grid_mult = atoi(m) > 0 ? atoi(m) : ctx->ext_grid_mult;
 	if (const char *m = getenv("BMH_EXT_STOP")) ctx->ext_stop = atoi(m) != 0; // (A/B knob)
+	if (const char *m = getenv("BMH_EXT_NARROW")) ctx->ext_narrow = atoi(m) != 0; // (A/B knob)
+	if (const char *m = getenv("BMH_EXT_BANDKEY")) ctx->ext_bandkey = atoi(m) != 0; // (A/B knob)
 	if (const char *m = getenv("BMH_EXT_SMALL")) ctx->small_batch = atoi(m) >= 0 ? atoi(m) : ctx->small_batch;
 	if (getenv("BMH_EXT_MODE")) ctx->ext_mode_forced = true;
 	if (const char *m = getenv("BMH_EXT_MODE")) ctx->force_kernel = !strcmp(m, "lds") ? 1 : !strcmp(m, "reg") ? 2 : !strcmp(m, "grp") ? 3 : !strcmp(m, "lanex4") ? 4 : !strcmp(m, "wide") ? 5 : 0;
@@ -308,7 +310,7 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)stream_wait(ctx, ctx->stream);
 	free_buf(ctx->d_pool), free_buf(ctx->d_tasks), free_buf(ctx->d_res), free_buf(ctx->d_order);
-	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_gband), free_buf(ctx->d_ext_rows), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
+	free_buf(ctx->d_cigar), free_buf(ctx->d_scratch), free_buf(ctx->d_bins), free_buf(ctx->d_gband), free_buf(ctx->d_ext_rows), free_buf(ctx->d_eband), free_buf(ctx->d_zslab), free_buf(ctx->d_sw), free_buf(ctx->d_swrm);
 	free_buf(ctx->d_seedws), free_buf(ctx->d_region), free_buf(ctx->d_chain), free_buf(ctx->d_wide_slab), free_buf(ctx->d_c2r);
 	if (ctx->d_wide_stat) (void)hipFree(ctx->d_wide_stat);
 	if (ctx->d_swl_stat) (void)hipFree(ctx->d_swl_stat);
@@ -627,6 +629,15 @@ int bmh_last_extend_rows(bmh_ctx_t *ctx, uint16_t *rows, int64_t n)
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
 	BMH_HIP(ctx, hipMemcpy(rows, ctx->d_ext_rows.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+	return BMH_OK;
+}
+
+int bmh_last_extend_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n)
+{
+	if (!ctx || !bands || n <= 0 || n != ctx->eband_n || !ctx->d_eband.p) return BMH_E_ARG;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	BMH_HIP(ctx, hipMemcpy(bands, ctx->d_eband.p, (size_t)n, hipMemcpyDeviceToHost));
 	return BMH_OK;
 }
 

@@ -84,6 +84,11 @@ struct bmh_ctx {
 	int64_t ext_rows_cap = 0; // diagnostic (bmh_ctx_set_extend_rows): plain extension launches record the rows each lane-kernel task ran, for task indices below this
 	DevBuf d_ext_rows;        // ... uint16 by task index, 0xffff where no lane kernel took the task
 	int64_t ext_rows_n = 0;   // entries the last extension launch recorded into (its ext_rows_cap), 0 if it recorded none (bmh_last_extend_rows)
+	int ext_narrow = 1;    // extension lane kernels run each flank on the band its result needs (host/extband_core.h; env BMH_EXT_NARROW=0 turns it
+	                       // off, and so does an armed rows diagnostic: ext_rows_cap > 0).  Off, the band pass still runs and lists every task's own w
+	int ext_bandkey = 1;   // the sort key's 3-bit middle field: 1 the band's class, 0 the h0 bucket (env BMH_EXT_BANDKEY, A/B knob)
+	DevBuf d_eband;        // the bands of a dispatcher launch with a band pass: n bytes by input position, then kSortBins x n bytes parallel to the sort's lists
+	int64_t eband_n = 0;   // entries of the last such launch, else 0 (bmh_last_extend_bands)
 	// Bin sizes of the extension dispatcher are only known on the device.  After every launch they are copied to pinned
 	// memory WITHOUT waiting; the next launch of the same kind (plain API call, or stage k of the fused per-seed
 	// pipeline) reads whatever has arrived and sizes its grids / picks the kernel of bin 3 from it.  A stale or missing
@@ -306,14 +311,16 @@ __device__ __forceinline__ bool ext_goes_wide(int qlen, int h0, int max_mat)
 // rows run at most to tlen, and the band leaves the query after ~qlen+w <= 2*qlen rows (ksw.c:418).
 // (With the lane kernels' early stop, DESIGN.md 4.3, a good flank ends near row qlen instead.  Two minor keys that follow that -- h0 to
 // the base, and tlen - qlen -- were measured level or slower than this one, profiles/ext_stop.md, so it stays.)
-__device__ __forceinline__ int ext_sort_key(int bin, int qlen, int tlen, int h0)
+// cls >= 0: the class of the band the lane kernel will run the task on (bmh_extband_class) stands in the h0 bucket's
+// place -- with a band pass the band decides the interval's width, and narrowed and un-narrowed tasks must not share waves.
+__device__ __forceinline__ int ext_sort_key(int bin, int qlen, int tlen, int h0, int cls = -1)
 {
 	if (bin > 4) return 0;
 	const int qlo = bin == 0 ? 1 : (16 << bin) + 1, qsh = bin < 2 ? 1 : bin; // 16 query-length buckets per bin
 	const int rows = min(tlen, 2 * qlen + 8) >> (bin > 2 ? bin - 2 : 0);
 	// h0 decides how wide the live interval is (cells stay non-zero within ~h0-o-e of the diagonal), so lanes
 	// with a similar h0 need the same 8-column blocks
-	return ((max(qlen - qlo, 0) >> qsh) * 8 + min(max(h0, 0) >> 4, 7)) * 16 + min(rows >> 4, 15);
+	return ((max(qlen - qlo, 0) >> qsh) * 8 + (cls >= 0 ? cls : min(max(h0, 0) >> 4, 7))) * 16 + min(rows >> 4, 15);
 }
 
 struct ExtBinRule { // what a launch fixes for all of its tasks
@@ -326,16 +333,20 @@ struct ExtBinRule { // what a launch fixes for all of its tasks
 
 // bin and sort key of ONE task as binkey holds them (bin * kSortKeys + key).  Past qmax: the failure record of the kernels, here,
 // since the bins that qmax calls empty are not launched
-__device__ __forceinline__ int ext_binkey_of(const ExtBinRule &r, int qlen, int tlen, int h0, size_t idx)
+__device__ __forceinline__ int ext_task_bin(const ExtBinRule &r, int qlen, int tlen, int h0)
 {
-	const bool over = qlen > r.qmax;
-	const int bin = over ? kCapBin : r.wide && (r.wide == 2 || ext_goes_wide(qlen, h0, r.max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, r.mode);
-	if (over) {
+	return qlen > r.qmax ? kCapBin : r.wide && (r.wide == 2 || ext_goes_wide(qlen, h0, r.max_mat)) ? kWideBin : ext_bin_of(qlen, tlen, r.mode);
+}
+
+__device__ __forceinline__ int ext_binkey_of(const ExtBinRule &r, int qlen, int tlen, int h0, size_t idx, int cls = -1)
+{
+	const int bin = ext_task_bin(r, qlen, tlen, h0);
+	if (bin == kCapBin) {
 		int *p = (int *)(r.out + idx);
 		p[0] = INT32_MIN, p[1] = p[2] = p[3] = p[4] = p[5] = 0;
 		atomicExch(r.err_flag, BMH_E_RANGE);
 	}
-	return bin * kSortKeysHost + ext_sort_key(bin, qlen, tlen, h0);
+	return bin * kSortKeysHost + ext_sort_key(bin, qlen, tlen, h0, cls);
 }
 
 // The dispatcher in two halves, for a caller whose own kernel makes the tasks and bins them in the same pass (the fused
@@ -346,6 +357,8 @@ struct ExtBinned {
 	uint32_t *hist;   // kSortBins * kSortKeys counters, zeroed
 	uint16_t *binkey; // n entries
 	unsigned blocks;
+	uint8_t *band; // non-null: the launch has a band pass (extend_dispatch.hip), which bins the tasks itself.  The caller's kernel then
+	               // only marks: binkey[i] = 0 for an entry with a task, kNoTask without, and it leaves hist alone
 	bool tiny; // the bin-size hint calls the batch (almost) empty: rule.mode sends every task to bin 5, and one launch of the
 	           // any-length kernel walks that list (as launch_extend does for a device-counted list)
 };
@@ -380,7 +393,8 @@ constexpr long long sw_long_state_bytes(int cols) { return 5LL * cols; }
 int launch_sw_long(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_sw_task_t *d_tasks, int64_t n, bmh_sw_result_t *d_res,
                    const uint32_t *d_order, const uint32_t *d_count, int qmax, int qmin, int tcap, int wave_cols);
 int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
-                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip = nullptr);
+                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip = nullptr,
+                       const uint8_t *d_bands = nullptr); // d_bands (nullable): one byte beside every entry of d_order, see the kernel
 int launch_extend_reg(bmh_ctx *ctx, int ns, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, int max_count = 0, long long grid_cap = 0);
 // The global wave kernel (global_kernel.hip) in LDS: H and E int32 [qcap+2] each, the profile 8 bytes [qcap], smat; up to

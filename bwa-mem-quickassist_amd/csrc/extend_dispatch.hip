@@ -22,6 +22,7 @@
 
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "../host/extband_core.h"
 
 namespace bmh {
 
@@ -54,6 +55,127 @@ __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const bmh_ext_t
 	}
 	__syncthreads();
 	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kSortThreads)
+		if (lh[t]) atomicAdd(&hist[t], lh[t]);
+}
+
+// the eight base codes at positions [s, s + 8) of a byte sequence (base 0 at pool[off]; with rev it runs downwards), position s in the low byte
+__device__ __forceinline__ uint64_t seq_word(const uint8_t *pool, uint64_t off, int s, bool rev)
+{
+	uint64_t v;
+	__builtin_memcpy(&v, rev ? pool + off - (uint64_t)s - 7 : pool + off + (uint64_t)s, 8);
+	return rev ? __builtin_bswap64(v) : v;
+}
+
+// positions [from, from + 16) of a sequence of len >= 8 bases as two words, position from + j in byte j.  No byte outside the sequence is
+// read: a window that would pass its end is moved back to end there and shifted (what lies past the end reads as 0)
+__device__ __forceinline__ void seq_share(const uint8_t *pool, uint64_t off, int from, int len, bool rev, uint64_t w[2])
+{
+#pragma unroll
+	for (int k = 0; k < 2; ++k) {
+		const int at = from + 8 * k, s = min(at, len - 8), d = at - s;
+		const uint64_t v = seq_word(pool, off, s, rev);
+		w[k] = d < 8 ? v >> (8 * d) : 0;
+	}
+}
+
+// pass 1 with the band pass (host/extband_core.h) in it, for launches whose bins 0-2 run on the lane kernels: per task
+// the band its result needs, as one byte by input position (bmh_extband_byte), and bin and sort key from it -- the band's class is
+// part of the key, so both must be known in the same pass.  EIGHT lanes share a task, each an eighth of the plain diagonal's pairs,
+// joined in order: their loads fall into the task's few cache lines in the same instruction (one lane per task re-fetched lines 16x in
+// the global path's band pass, profiles/global_band.md).  1024 threads: with the histogram's 64 KiB two blocks fill a CU's wave slots.
+// marked: binkey[] holds the caller's marks (ExtBinned::band); an entry without a task gets the byte 255 and is not counted.
+// narrow == 0 (the switch off, or the rows diagnostic armed): no walk, every task's own w.
+constexpr int kBandThreads = 1024, kBandLanes = 8, kBandShare = 128 / kBandLanes; // (a lane kernel's query has at most 128 columns)
+__global__ __launch_bounds__(kBandThreads) void ext_band_hist_kernel(const uint8_t *__restrict__ pool, const bmh_ext_task_t *__restrict__ tasks,
+                                                                     const uint32_t *__restrict__ order, long long n,
+                                                                     uint32_t *__restrict__ hist, uint16_t *__restrict__ binkey,
+                                                                     ExtBinRule rule, const uint32_t *__restrict__ dn,
+                                                                     uint8_t *__restrict__ band, DevParams P, int marked, int narrow, int bandkey)
+{
+	__shared__ uint32_t lh[kSortBins * kSortKeys];
+	__shared__ int8_t smat[32];
+	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kBandThreads) lh[t] = 0;
+	if (threadIdx.x < 25) smat[threadIdx.x] = (int8_t)mat_at(P, threadIdx.x);
+	__syncthreads();
+	const int amax = bmh_extband_amax(smat);
+	const bool applies = narrow && bmh_extband_applies(amax, P.o_del, P.e_del, P.o_ins, P.e_ins);
+	if (dn) n = min(n, (long long)*dn);
+	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
+	const int g = threadIdx.x & (kBandLanes - 1);
+	constexpr int kPer = kBandThreads / kBandLanes;
+	// The entry's mark and record are fetched one turn ahead, so that their round trip runs beside the walk of the entry before.  (The
+	// record of a marked entry without a task is read as well: it lies inside the caller's array, and nothing of it is used.)
+	struct Entry {
+		uint4 a, b;
+		uint32_t idx;
+		bool has;
+	};
+	auto fetch = [&](long long k) {
+		Entry e;
+		e.has = !(marked && binkey[k] == kNoTask);
+		e.idx = order ? order[k] : (uint32_t)k;
+		const uint4 *tp = (const uint4 *)(tasks + e.idx);
+		e.a = tp[0], e.b = tp[1];
+		return e;
+	};
+	long long k = lo + threadIdx.x / kBandLanes; // (uniform in a group of eight)
+	Entry nx = {};
+	if (k < hi) nx = fetch(k);
+	for (; k < hi; k += kPer) {
+		const Entry cur = nx;
+		if (k + kPer < hi) nx = fetch(k + kPer);
+		if (!cur.has) {
+			if (g == 0) band[k] = 255;
+			continue;
+		}
+		const uint32_t idx = cur.idx;
+		const uint4 ta = cur.a, tb = cur.b;
+		const uint64_t q_off = (uint64_t)ta.y << 32 | ta.x, t_off = (uint64_t)ta.w << 32 | ta.z;
+		const int qlen = (int)(tb.x & 0xffff), tlen = (int)(tb.x >> 16), h0 = (int)tb.y;
+		const int w = (int)(int16_t)(tb.z & 0xffff);
+		const int bin = ext_task_bin(rule, qlen, tlen, h0);
+		int we = w;
+		if (applies && bin <= 2 && qlen >= 1 && qlen <= kBandShare * kBandLanes && tlen >= qlen && w >= 1) { // (bins 0-2: qlen <= 128 and within the launch's qmax)
+			const bool qrev = tb.w & BMH_F_QREV, trev = tb.w & BMH_F_TREV, tpac = tb.w & BMH_F_TPAC;
+			const int per = (qlen + kBandLanes - 1) / kBandLanes;
+			const int from = min(g * per, qlen), to = min(from + per, qlen);
+			// A lane's share is at most kBandShare = 16 pairs: two eight-base loads per sequence, so the eight lanes fetch the task's one or
+			// two cache lines per sequence once (byte loads touched them once per pair: 1.82 ms per launch against 1.46, profiles/ext_band.md).
+			// Flanks of fewer than eight bases have one pair per lane, and a packed target (BMH_F_TPAC) is decoded base by base -- byte
+			// loads, all unconditional (a pair past the share reads the query's last pair again and is not counted) and issued together.
+			const int p0 = min(from, qlen - 1);
+			uint64_t qw[2] = {0, 0}, tw[2] = {0, 0};
+			if (qlen >= 8) seq_share(pool, q_off, from, qlen, qrev, qw);
+			else qw[0] = pool[qrev ? q_off - (uint64_t)p0 : q_off + (uint64_t)p0];
+			if (tpac) {
+#pragma unroll
+				for (int j = 0; j < kBandShare; ++j) tw[j >> 3] |= (uint64_t)tgt_base(pool, P, t_off, min(from + j, qlen - 1), trev, true) << (8 * (j & 7));
+			} else if (qlen >= 8) seq_share(pool, t_off, from, tlen, trev, tw);
+			else tw[0] = pool[trev ? t_off - (uint64_t)p0 : t_off + (uint64_t)p0];
+			bmh_xb_part_t mine = {0, 0};
+#pragma unroll
+			for (int j = 0; j < kBandShare; ++j) {
+				const int qb = (int)(qw[j >> 3] >> (8 * (j & 7)) & 255), tg = (int)(tw[j >> 3] >> (8 * (j & 7)) & 255);
+				if (from + j < to) bmh_extband_pair(&mine, smat[min(tg, 4) * 5 + min(qb, 4)]);
+			}
+			bmh_xb_part_t acc = {0, 0};
+#pragma unroll
+			for (int j = 0; j < kBandLanes; ++j) { // every lane joins the eight parts in order
+				const bmh_xb_part_t nx = {__shfl(mine.sum, j, kBandLanes), __shfl(mine.mn, j, kBandLanes)};
+				bmh_extband_join(&acc, &nx);
+			}
+			we = bmh_extband_from_walk(amax, P.o_del, P.e_del, P.o_ins, P.e_ins, P.zdrop, qlen, tlen, h0, w, acc.sum, acc.mn);
+		}
+		if (g == 0) {
+			const int byte = bmh_extband_byte(we);
+			band[k] = (uint8_t)byte;
+			const int bk = ext_binkey_of(rule, qlen, tlen, h0, idx, bandkey && bin <= 2 ? bmh_extband_class(byte) : -1);
+			binkey[k] = (uint16_t)bk;
+			atomicAdd(&lh[bk], 1u);
+		}
+	}
+	__syncthreads();
+	for (int t = threadIdx.x; t < kSortBins * kSortKeys; t += kBandThreads)
 		if (lh[t]) atomicAdd(&hist[t], lh[t]);
 }
 
@@ -207,6 +329,7 @@ struct ExtPlan {
 	int mode; // see ext_bin_of
 	bool tiny; // the hint calls a device-counted batch (almost) empty: no bins, one launch of the any-length kernel
 	int64_t n_eff; // tasks expected: n, or what the hint says of a device-counted list
+	bool band; // the launch has a band pass: its bins 0-2 run on the lane kernels, and it is a flat batch or a big round of the fused call
 };
 
 // device_count: how many of the n entries are tasks is known on the device only, so the hinted size stands in for it
@@ -233,7 +356,30 @@ static int extend_plan(bmh_ctx *ctx, int64_t n, int kind, bool device_count, Ext
 	// 0.84 -> 0.51 ms; level at 65 k).  With a device-side count the decision uses the hinted size.
 	const int64_t n_eff = pl->n_eff = device_count ? std::min<int64_t>(n, est_total + (est_total >> 2) + 64) : n;
 	pl->mode = ctx->ext_mode_forced ? (ctx->force_kernel == 5 ? 0 : ctx->force_kernel) : n_eff <= ctx->small_batch ? 2 : 0;
+	// (the retry rounds of the fused call, kinds 2 and 4, run un-narrowed: a handful of tasks, and the retry rule has asked for 2w)
+	pl->band = (pl->mode == 0 || pl->mode == 4) && !pl->tiny && pl->wide != 2 && (kind == 0 || kind == 1 || kind == 3);
+	ctx->eband_n = 0;
 	return BMH_OK;
+}
+
+// the band pass's workspace: n bytes by input position, then (from a multiple of 16 on) kSortBins x n bytes beside the sort's lists
+static int band_workspace(bmh_ctx *ctx, int64_t n, uint8_t **band)
+{
+	int rc = ensure(ctx, ctx->d_eband, (1 + (size_t)kSortBins) * (size_t)n + 16);
+	if (rc) return rc;
+	*band = (uint8_t *)ctx->d_eband.p;
+	return BMH_OK;
+}
+static uint8_t *band_lists(uint8_t *band, int64_t n) { return band ? band + (((size_t)n + 15) & ~(size_t)15) : nullptr; }
+
+static void launch_band_hist(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, const uint32_t *d_order, int64_t n,
+                             uint32_t *hist, uint16_t *binkey, const ExtBinRule &rule, const uint32_t *d_n, uint8_t *band, unsigned blocks,
+                             bool marked)
+{
+	const int narrow = ctx->ext_narrow && ctx->ext_rows_cap <= 0; // (the rows diagnostic reports the rows of the reference's band)
+	hipLaunchKernelGGL(ext_band_hist_kernel, dim3(blocks), dim3(kBandThreads), 0, ctx->stream, d_pool, d_tasks, d_order, (long long)n, hist,
+	                   binkey, rule, d_n, band, ctx->dev, marked ? 1 : 0, narrow, ctx->ext_bandkey);
+	ctx->eband_n = n;
 }
 
 static unsigned sort_blocks_for(int64_t n)
@@ -243,7 +389,7 @@ static unsigned sort_blocks_for(int64_t n)
 }
 
 static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
-                           int qmax, int kind, const ExtPlan &pl);
+                           int qmax, int kind, const ExtPlan &pl, const uint8_t *blists);
 
 int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
                   bmh_ext_result_t *d_res, const uint32_t *d_order, int qmax, const uint32_t *d_n, int kind)
@@ -261,10 +407,15 @@ int launch_extend(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_t
 	uint16_t *binkey = (uint16_t *)(hist + (size_t)kSortBins * kSortKeys);
 	const unsigned cg = sort_blocks_for(pl.n_eff);
 	const ExtBinRule rule = {pl.mode, pl.wide, ctx->dev.max_mat, qmax, d_res, ctx->d_err};
-	hipLaunchKernelGGL(sort_hist_kernel, dim3(cg), dim3(kSortThreads), 0, ctx->stream, d_tasks, d_order, (long long)n, hist, binkey,
-	                   rule, d_n);
-	if ((rc = sort_tasks_finish(ctx, n, d_order, cg, d_n))) return rc;
-	return extend_run_bins(ctx, d_pool, d_tasks, n, d_res, qmax, kind, pl);
+	uint8_t *band = nullptr;
+	if (pl.band) {
+		if ((rc = band_workspace(ctx, n, &band))) return rc;
+		launch_band_hist(ctx, d_pool, d_tasks, d_order, n, hist, binkey, rule, d_n, band, cg, false);
+	} else
+		hipLaunchKernelGGL(sort_hist_kernel, dim3(cg), dim3(kSortThreads), 0, ctx->stream, d_tasks, d_order, (long long)n, hist, binkey,
+		                   rule, d_n);
+	if ((rc = sort_tasks_finish(ctx, n, d_order, cg, d_n, nullptr, band, band_lists(band, n)))) return rc;
+	return extend_run_bins(ctx, d_pool, d_tasks, n, d_res, qmax, kind, pl, band_lists(band, n));
 }
 
 int extend_binned_begin(bmh_ctx *ctx, int64_t n, bmh_ext_result_t *d_res, int qmax, int kind, ExtBinned *p)
@@ -280,13 +431,16 @@ int extend_binned_begin(bmh_ctx *ctx, int64_t n, bmh_ext_result_t *d_res, int qm
 	p->hist = counts + 16;
 	p->binkey = (uint16_t *)(p->hist + (size_t)kSortBins * kSortKeys);
 	p->blocks = sort_blocks_for(n);
+	p->band = nullptr;
+	if (pl.band && (rc = band_workspace(ctx, n, &p->band))) return rc;
 	return BMH_OK;
 }
 
 int extend_binned_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
                          int qmax, int kind, const ExtBinned &p, uint32_t *d_total)
 {
-	int rc = sort_tasks_finish(ctx, n, nullptr, p.blocks, nullptr, d_total); // (the position in binkey[] is the task index)
+	if (p.band) launch_band_hist(ctx, d_pool, d_tasks, nullptr, n, p.hist, p.binkey, p.rule, nullptr, p.band, p.blocks, true);
+	int rc = sort_tasks_finish(ctx, n, nullptr, p.blocks, nullptr, d_total, p.band, band_lists(p.band, n)); // (the position in binkey[] is the task index)
 	if (rc) return rc;
 	if (p.tiny) {
 		uint32_t *counts = (uint32_t *)ctx->d_bins.p;
@@ -294,13 +448,14 @@ int extend_binned_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task
 		if ((rc = launch_extend_lds(ctx, d_pool, d_tasks, n, d_res, lists + (size_t)5 * (size_t)n, counts + 5, qmax, 2 * kTinyList))) return rc;
 		return hint_post(ctx, kind, counts); // (all of it in bin 5: the total is what the next decision needs)
 	}
-	const ExtPlan pl = {p.rule.wide, p.rule.mode, false, n};
-	return extend_run_bins(ctx, d_pool, d_tasks, n, d_res, qmax, kind, pl);
+	const ExtPlan pl = {p.rule.wide, p.rule.mode, false, n, p.band != nullptr};
+	return extend_run_bins(ctx, d_pool, d_tasks, n, d_res, qmax, kind, pl, band_lists(p.band, n));
 }
 
 // the second half: the bins stand in ctx->d_bins (sizes, cursors, lists), enqueued on ctx->stream
+// blists (nullable): the band pass's bytes beside the lists, for the lane kernels of bins 0-2; the other families keep the task's band
 static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n, bmh_ext_result_t *d_res,
-                           int qmax, int kind, const ExtPlan &pl)
+                           int qmax, int kind, const ExtPlan &pl, const uint8_t *blists)
 {
 	int rc;
 	const int wide = pl.wide, mode = pl.mode;
@@ -353,6 +508,7 @@ static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_ta
 			if (rc) { ctx->stream = main_s; return set_hip_error(ctx, (hipError_t)rc, "hipEventRecord"); }
 		}
 		const uint32_t *lst = lists + (size_t)b * N, *cnt = counts + b;
+		const uint8_t *bnd = blists ? blists + (size_t)b * N : nullptr;
 		const int qlo = b == 0 ? 0 : 16 << b; // bins 0..4 hold qlen <= 32,64,128,256,512
 		// grid of the bin's kernel: sized for the expected count (every kernel strides over its bin, so any grid is
 		// correct); a bin the hint calls empty still gets a few hundred waves in case the batch differs from the last one
@@ -366,9 +522,9 @@ static int extend_run_bins(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_ext_ta
 				// the list, and where it ends stands in the sort's cursor array -- the key range of buckets 0-7 closes at key 1023.  They go
 				// to a 96-column instantiation, whose 120 state registers leave room for 3 waves per SIMD (the 128-column one: 2).
 				const uint32_t *n96 = hist + (size_t)2 * kSortKeys + 1023;
-				rc = launch_extend_lane(ctx, 96, d_pool, d_tasks, hint.valid ? est[b] : n, d_res, lst, n96, true); // (no pick-up launch: see `rem` in the kernel)
-				if (!rc) rc = launch_extend_lane(ctx, 128, d_pool, d_tasks, hint.valid ? est[b] : n, d_res, lst, cnt, !hint.valid, n96);
-			} else if (mode == 0 || mode == 4) rc = launch_extend_lane(ctx, 32 << b, d_pool, d_tasks, hint.valid ? est[b] : n, d_res, lst, cnt, !hint.valid);
+				rc = launch_extend_lane(ctx, 96, d_pool, d_tasks, hint.valid ? est[b] : n, d_res, lst, n96, true, nullptr, bnd); // (no pick-up launch: see `rem` in the kernel)
+				if (!rc) rc = launch_extend_lane(ctx, 128, d_pool, d_tasks, hint.valid ? est[b] : n, d_res, lst, cnt, !hint.valid, n96, bnd);
+			} else if (mode == 0 || mode == 4) rc = launch_extend_lane(ctx, 32 << b, d_pool, d_tasks, hint.valid ? est[b] : n, d_res, lst, cnt, !hint.valid, nullptr, bnd);
 			else if (mode == 3) rc = launch_extend_grp(ctx, 2 << b, d_pool, d_tasks, n, d_res, lst, cnt);
 			else rc = launch_extend_reg(ctx, b == 2 ? 2 : 1, d_pool, d_tasks, n, d_res, lst, cnt, 0, est[b]);
 		} else if (b == 3) {

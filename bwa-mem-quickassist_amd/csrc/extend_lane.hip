@@ -48,6 +48,7 @@ __device__ __forceinline__ int bfi2(int mask, int a, int b) { return __builtin_a
 // some per-row scratch traffic at C = 128); !LOOP: one chunk per block, chunk = chunk0 + blockIdx.x.
 // stop_a: the allowance per column of the early-stop rule (host/extstop_core.h): max(mat) with the rule on, BMH_EXTSTOP_OFF without.
 // rows_out (nullable, a diagnostic): per task index below rows_cap the rows it ran, written where the lane writes its result.
+// bands (nullable): beside order[], the band the task's result needs (the dispatcher's band pass, host/extband_core.h); 255: its own.
 template <int C, bool SYM, bool LOOP>
 __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(const uint8_t *__restrict__ pool,
                                                          const bmh_ext_task_t *__restrict__ tasks,
@@ -56,7 +57,8 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
                                                          bmh_ext_result_t *__restrict__ out, DevParams P,
                                                          int *__restrict__ err_flag, long long chunk0,
                                                          const uint32_t *__restrict__ skip, int stop_a,
-                                                         uint16_t *__restrict__ rows_out, uint32_t rows_cap)
+                                                         uint16_t *__restrict__ rows_out, uint32_t rows_cap,
+                                                         const uint8_t *__restrict__ bands)
 {
 	constexpr int NW = C / 32, NQ = C / 4, NB = C / 8;
 	constexpr int INF = 0x7fff;
@@ -152,6 +154,10 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 	}
 	w = min(w, max(1, band_cap(qlen, P.max_mat, end_bonus, P.o_ins, e_ins))); // ksw.c:398-406
 	w = min(w, max(1, band_cap(qlen, P.max_mat, end_bonus, P.o_del, e_del)));
+	if (bands) {
+		const int wb = bands[lp];
+		w = wb != 255 ? min(w, wb) : w;
+	}
 
 	int begp = off, endp = C, best = h0, bi = -1, bjp = off - 1, maxoff = 0, raw = h0 - P.o_del, gk = -1;
 	bool alive = valid && !bad && tlen > 0;
@@ -293,7 +299,8 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 // bin size (exact or an upper bound without a hint).  persist: one strided launch with a capped grid.  Otherwise one
 // chunk per block over the estimate, plus a small strided launch that picks up whatever lies beyond it.
 int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext_task_t *d_tasks, int64_t n,
-                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip)
+                       bmh_ext_result_t *d_res, const uint32_t *d_order, const uint32_t *d_count, bool exact, const uint32_t *d_skip,
+                       const uint8_t *d_bands)
 {
 	const int stop_a = bmh_extstop_factor(ctx->ext_stop, ctx->params.mat, ctx->dev.o_del, ctx->dev.e_del, ctx->dev.o_ins, ctx->dev.e_ins);
 	uint16_t *d_rows = ctx->ext_rows_n > 0 ? (uint16_t *)ctx->d_ext_rows.p : nullptr; // (set per launch by the dispatcher)
@@ -305,7 +312,7 @@ int launch_extend_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_ext
 	const long long n_head = ctx->ext_persist && d_skip ? (1LL << 40) : (long long)n;
 #define BMH_LAUNCH_LANE2(CC, SY, LP, GRID, C0)                                                                          \
 	hipLaunchKernelGGL((extend_lane_kernel<CC, SY, LP>), dim3((unsigned)(GRID)), dim3(64), 0, ctx->stream, d_pool, d_tasks,  \
-	                   d_order, d_count, n_head, d_res, ctx->dev, ctx->d_err, (long long)(C0), d_skip, stop_a, d_rows, (uint32_t)ctx->ext_rows_n)
+	                   d_order, d_count, n_head, d_res, ctx->dev, ctx->d_err, (long long)(C0), d_skip, stop_a, d_rows, (uint32_t)ctx->ext_rows_n, d_bands)
 #define BMH_LAUNCH_LANE(CC, LP, GRID, C0)                                                                               \
 	do {                                                                                                                \
 		if (sym) BMH_LAUNCH_LANE2(CC, true, LP, GRID, C0);                                                              \

@@ -66,19 +66,23 @@ __device__ __forceinline__ void store_task(bmh_ext_task_t *t, uint64_t q_off, ui
 // T[i] and its bin and sort key -- from the lengths and h0 it holds in registers, by the dispatcher's rule -- in binkey[i]; a seed
 // without one stores kNoTask, which the sort's last pass skips.  1024 threads: the histogram's 64 KiB allow two blocks per CU, and a
 // pass that streams ~100 bytes per seed wants all 32 wave slots of the CU.
+// Where the launch has a band pass (ExtBinned::band: the lane kernels will run the round) bin and key depend on the band the task's
+// result needs, which that pass computes from the sequences: the kernels here then only mark the entries that hold a task.
 constexpr int kMakeThreads = 1024;
 
 struct MakeBin { // the LDS histogram around the per-seed body
 	uint32_t *lh;
-	__device__ __forceinline__ void begin()
+	__device__ __forceinline__ void begin(const ExtBinned &b)
 	{
+		if (b.band) return; // the band pass counts (extend_dispatch.hip)
 		for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += kMakeThreads) lh[t] = 0;
 		__syncthreads();
 	}
 	__device__ __forceinline__ void put(const ExtBinned &b, long long i, bool has, int qlen, int tlen, int h0)
 	{
 		uint16_t bk = kNoTask;
-		if (has) {
+		if (b.band) bk = has ? 0 : kNoTask; // a mark: the band pass bins the task, once it knows its band
+		else if (has) {
 			bk = (uint16_t)ext_binkey_of(b.rule, qlen, tlen, h0, (size_t)i);
 			atomicAdd(&lh[bk], 1u);
 		}
@@ -86,6 +90,7 @@ struct MakeBin { // the LDS histogram around the per-seed body
 	}
 	__device__ __forceinline__ void end(const ExtBinned &b)
 	{
+		if (b.band) return;
 		__syncthreads();
 		for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += kMakeThreads)
 			if (lh[t]) atomicAdd(&b.hist[t], lh[t]);
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(kMakeThreads) void seed_left_make_bin(const bmh_see
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
 	MakeBin mb = {lh};
-	mb.begin();
+	mb.begin(bin);
 	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
 	for (long long i = lo + threadIdx.x; i < hi; i += kMakeThreads) {
 		const bmh_seed_task_t s = S[i];
@@ -162,7 +167,7 @@ __global__ __launch_bounds__(kMakeThreads) void seed_right_make_bin(const bmh_se
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
 	MakeBin mb = {lh};
-	mb.begin();
+	mb.begin(bin);
 	const long long chunk = (n + gridDim.x - 1) / gridDim.x, lo = chunk * blockIdx.x, hi = min(lo + chunk, n);
 	for (long long i = lo + threadIdx.x; i < hi; i += kMakeThreads) {
 		const bmh_seed_task_t s = S[i];

@@ -297,6 +297,17 @@ int bmh_ctx_set_extend_rows(bmh_ctx_t *ctx, int64_t cap);
  * list).  n <= the cap that launch ran with; BMH_E_ARG when it is not or when nothing was recorded.  Waits for the stream and copies
  * 2 n bytes. */
 int bmh_last_extend_rows(bmh_ctx_t *ctx, uint16_t *rows, int64_t n);
+/* Diagnostic: the band each task of the most recent extension launch with a band pass was run on.  Where the lane-per-task kernels
+ * take queries of up to 128 columns -- a flat batch above the small-batch threshold, the two big rounds of the fused per-seed call --
+ * a pass in front of the sort computes per task the band its six results need (host/extband_core.h) and those kernels
+ * run min(w, that band); the task record keeps its w, and every other kernel family, the retry rounds and tiny lists run the task's
+ * own band.  bands[k] belongs to input position k (entry k of d_order, or task k): the band, 255 for "255 or wider" (the task's own
+ * is kept), the task's own w for a task the rule leaves alone or no lane kernel takes, 255 for an entry of a fused round that holds
+ * no task.  BMH_EXT_NARROW=0 in the environment of bmh_ctx_create turns the narrowing off, and so does an armed rows diagnostic
+ * (bmh_ctx_set_extend_rows with cap > 0 -- it reports the rows of the reference's band): the pass then lists every task's own w.
+ * n must be that launch's entry count; BMH_E_ARG when it is not or when the launch had no band pass.  Waits for the stream and
+ * copies n bytes; the launches themselves do nothing for it. */
+int bmh_last_extend_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n);
 /* What the global-alignment launches of this context so far sent to bin 4, the band-ring kernel (tasks with more than 10 176
  * query columns that no lane kernel takes): *tasks = their number, *ms = the ring kernel's time summed over the launches made
  * with timing on (-1 when timing is off).  The counterpart of bmh_extend_wide_stats.  Waits for the stream. */
