@@ -1385,6 +1385,146 @@ static int decide_host_log(bmh_ctx *ctx, long long kmax, long long *want_log_)
 	return BMH_OK;
 }
 
+// offsets into a device block: one section after the other, each 64-byte aligned
+struct Block {
+	size_t at = 0;
+	size_t take(size_t bytes)
+	{
+		const size_t o = at;
+		at += (bytes + 63) & ~(size_t)63;
+		return o;
+	}
+};
+
+struct HostBuf { // malloc'd, freed on the way out
+	uint8_t *p;
+	explicit HostBuf(size_t bytes) : p((uint8_t *)malloc(bytes)) {}
+	~HostBuf() { free(p); }
+};
+
+// the statistics of the phase 2 calls as a call that has done nothing leaves them
+static void reset_decide_stats(bmh_ctx *ctx) { ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f; }
+static void reset_wanted_stats(bmh_ctx *ctx) { ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f; }
+static void reset_phase2_stats(bmh_ctx *ctx)
+{
+	ctx->p2 = bmh_phase2_stats_t{};
+	ctx->p2.decide_ms = ctx->p2.wanted_ms = -1.f;
+}
+static void reset_samtext_stats(bmh_ctx *ctx)
+{
+	ctx->stx = bmh_samtext_stats_t{};
+	ctx->stx.size_ms = ctx->stx.emit_ms = -1.f;
+}
+
+// the tables a device call was prepared with: bns's sequence table and, where the call reads the reference, pac
+static int need_resident(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns, const uint8_t *pac)
+{
+	if (pac && (!ctx->dev.pac || ctx->h_pac != pac || ctx->dev.l_pac != bns->l_pac)) {
+		ctx->last_error = std::string(who) + " needs the resident reference (bmh_ctx_set_pac)";
+		return BMH_E_ARG;
+	}
+	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
+		ctx->last_error = std::string(who) + " needs the resident sequence table (bmh_ctx_set_refidx)";
+		return BMH_E_ARG;
+	}
+	return BMH_OK;
+}
+
+// what decide_table_sizes and decide_host_log found for one slice
+struct DecideTables {
+	long long kmax = 1, n_term = 0, want_log = 0;
+	int64_t term_off[4] = {0, 0, 0, 0};
+};
+
+// Pass A's device block, the offsets at 0: [offsets | opt + pes | read offsets | WantedHdr | pair table | regions] up, [regions | reg_mapq |
+// want_k | n_want | pd] down (the regions come last in the upload so that the download is one copy), then decide_kernel's two scratch
+// arrays.  The read offsets and the WantedHdr are pass B's, there for the fused session and empty without it.
+struct DecideBlock {
+	size_t hdr, soff, whdr, term, reg, mq, wk, nw, pd, z, v, end;
+	size_t up() const { return mq; }
+	size_t down() const { return z - reg; }
+};
+
+static DecideBlock decide_block(size_t n, size_t total, size_t n_term, bool pe, bool with_pass_b)
+{
+	Block b;
+	DecideBlock L;
+	b.take((n + 1) * 8);
+	L.hdr = b.take(sizeof(DecideHdr));
+	L.soff = b.take(with_pass_b ? (n + 1) * 8 : 0), L.whdr = b.take(with_pass_b ? sizeof(WantedHdr) : 0);
+	L.term = b.take(n_term * 8), L.reg = b.take(total * sizeof(bmh_alnreg_t));
+	L.mq = b.take(total * 4), L.wk = b.take(total * 4), L.nw = b.take(n * 4), L.pd = b.take(pe ? (n >> 1) * sizeof(bmh_pairdec_t) : 0);
+	L.z = b.take(total * 4), L.v = b.take(pe ? total * sizeof(bmh_pair64_t) : 0), L.end = b.at;
+	return L;
+}
+
+// pass A's sections of the upload: offsets, DecideHdr, pair table, regions
+static void decide_fill(uint8_t *up, const DecideBlock &L, const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const DecideTables &T, int n,
+                        const bmh_alnreg_v *regs, const int64_t *roff)
+{
+	memcpy(up, roff, ((size_t)n + 1) * 8);
+	DecideHdr *hdr = (DecideHdr *)(up + L.hdr);
+	memset(hdr, 0, sizeof(*hdr));
+	hdr->opt = *o;
+	if (o->flag & BMH_MEM_F_PE) memcpy(hdr->pes, pes, sizeof(hdr->pes));
+	if (T.n_term) bmh_pp_fill_term_(o, pes, T.term_off, (double *)(up + L.term));
+	for (int i = 0; i < n; ++i)
+		if (regs[i].n) memcpy(up + L.reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+}
+
+// Stages a session that moves up_bytes and down_bytes beside the log table, and brings the device's copy of the table to want_log
+// entries.  ctx->logk_n says so only once the session has succeeded: the caller sets it.
+static int decide_stage_log(bmh_ctx *ctx, Stager &st, long long want_log, size_t up_bytes, size_t down_bytes)
+{
+	const bool grow = want_log > ctx->logk_n;
+	const size_t bytes = (size_t)want_log * 8;
+	int e;
+	if (grow) ctx->logk_n = 0; // (ensure may drop the old table)
+	if ((e = ensure(ctx, ctx->d_logk, (size_t)std::max(want_log, 1LL) * 8)) || (e = st.stage(up_bytes + (grow ? bytes + 64 : 0), down_bytes))) return e;
+	return grow ? st.h2d(ctx->d_logk.p, ctx->h_logk, bytes) : BMH_OK;
+}
+
+static DecideArgs decide_args(bmh_ctx *ctx, uint8_t *d, const DecideBlock &L, const DecideTables &T, size_t total, int64_t l_pac, int64_t id0, int n,
+                              bool pe)
+{
+	DecideArgs A{};
+	A.roff = (const unsigned long long *)d, A.hdr = (const DecideHdr *)(d + L.hdr);
+	A.tab.logk = (const double *)ctx->d_logk.p, A.tab.term = (const double *)(d + L.term);
+	memcpy(A.tab.term_off, T.term_off, sizeof(T.term_off));
+	A.tab.n_log = T.want_log, A.tab.n_term = T.n_term;
+	A.reg = (bmh_alnreg_t *)(d + L.reg), A.total = total;
+	A.reg_mapq = (int32_t *)(d + L.mq), A.want_k = (int32_t *)(d + L.wk), A.n_want = (int32_t *)(d + L.nw), A.pd = (bmh_pairdec_t *)(d + L.pd);
+	A.z = (int *)(d + L.z), A.v = (bmh_pair64_t *)(d + L.v);
+	A.l_pac = l_pac, A.id0 = id0, A.n = n, A.pe = pe, A.err = ctx->d_err;
+	return A;
+}
+
+// the wanted regions of the block as downloaded (down = its regions), or -1 where a read wants more than its vector holds (cannot happen)
+static int64_t decide_want_count(const uint8_t *down, const DecideBlock &L, int n, const bmh_alnreg_v *regs)
+{
+	const int32_t *nw = (const int32_t *)(down + (L.nw - L.reg));
+	int64_t sum = 0;
+	for (int i = 0; i < n; ++i) {
+		if (nw[i] < 0 || (size_t)nw[i] > regs[i].n) return -1;
+		sum += nw[i];
+	}
+	return sum;
+}
+
+// all or nothing: the caller's vectors and outputs from the checked block, once nothing can fail any more
+static void decide_commit(const uint8_t *down, const DecideBlock &L, bool pe, int n, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd,
+                          int32_t *reg_mapq, int32_t *n_want, int32_t *want_k)
+{
+	const size_t nr = (size_t)n, total = (size_t)roff[n];
+	const int32_t *nw = (const int32_t *)(down + (L.nw - L.reg)), *wk = (const int32_t *)(down + (L.wk - L.reg));
+	for (int i = 0; i < n; ++i)
+		if (regs[i].n) memcpy(regs[i].a, down + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].n * sizeof(bmh_alnreg_t));
+	memcpy(reg_mapq, down + (L.mq - L.reg), total * 4), memcpy(n_want, nw, nr * 4);
+	for (int i = 0; i < n; ++i) // (entries of want_k past a read's n_want stay the caller's)
+		if (nw[i]) memcpy(want_k + roff[i], wk + roff[i], (size_t)nw[i] * 4);
+	if (pe) memcpy(pd, down + (L.pd - L.reg), (nr >> 1) * sizeof(bmh_pairdec_t));
+}
+
 int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t *pes, int64_t id0, int n, bmh_alnreg_v *regs,
                       const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq, int32_t *n_want, int32_t *want_k)
 {
@@ -1392,86 +1532,45 @@ int bmh_decide_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, con
 	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
 	if (rc) return rc;
 	if (n == 0) {
-		ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+		reset_decide_stats(ctx);
 		return BMH_OK;
 	}
 	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
 	const size_t total = (size_t)roff[n];
 	// what the tables must reach (bwamem_hip.h), before anything is uploaded
-	auto refuse = [&](const char *why) {
-		ctx->last_error = why;
-		ctx->decide_units = 0, ctx->decide_fallbacks = 1, ctx->decide_ms = -1.f;
-		return BMH_E_RANGE;
-	};
-	long long kmax = 1, n_term = 0, want_log = 0;
-	int64_t term_off[4] = {0, 0, 0, 0};
+	DecideTables T;
 	const char *why = nullptr;
-	if (decide_table_sizes(o, pes, n, regs, &kmax, &n_term, term_off, &why)) return refuse(why);
-	if ((rc = decide_host_log(ctx, kmax, &want_log))) return rc;
-	// the device block: [offsets | opt + pes | pair table | regions] up, [regions | reg_mapq | want_k | n_want | pd] down (the regions
-	// come last in the upload so that the download is one copy), then the two scratch arrays
-	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-	const size_t nr = (size_t)n, o_hdr = al((nr + 1) * 8), o_term = o_hdr + al(sizeof(DecideHdr)), o_reg = o_term + al((size_t)n_term * 8);
-	const size_t o_mq = o_reg + al(total * sizeof(bmh_alnreg_t)), o_wk = o_mq + al(total * 4), o_nw = o_wk + al(total * 4), o_pd = o_nw + al(nr * 4);
-	const size_t o_z = o_pd + al(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0), o_v = o_z + al(total * 4), o_end = o_v + al(pe ? total * sizeof(bmh_pair64_t) : 0);
-	const size_t b_up = o_mq, b_down = o_z - o_reg;
-	uint8_t *up = (uint8_t *)malloc(b_up), *down = (uint8_t *)malloc(b_down);
-	struct Free {
-		uint8_t *a, *b;
-		~Free() { free(a), free(b); }
-	} guard{up, down};
-	if (!up || !down) {
+	if (decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why)) {
+		ctx->last_error = why;
+		reset_decide_stats(ctx), ctx->decide_fallbacks = 1;
+		return BMH_E_RANGE;
+	}
+	if ((rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
+	const DecideBlock L = decide_block((size_t)n, total, (size_t)T.n_term, pe, false);
+	HostBuf up(L.up()), down(L.down());
+	if (!up.p || !down.p) {
 		ctx->last_error = "bmh_decide_device: out of host memory";
 		return BMH_E_NOMEM;
 	}
-	memcpy(up, roff, (nr + 1) * 8);
-	DecideHdr *hdr = (DecideHdr *)(up + o_hdr);
-	memset(hdr, 0, sizeof(*hdr));
-	hdr->opt = *o;
-	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
-	if (n_term) bmh_pp_fill_term_(o, pes, term_off, (double *)(up + o_term));
-	for (int i = 0; i < n; ++i)
-		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+	decide_fill(up.p, L, o, pes, T, n, regs, roff);
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	Stager st(ctx);
 	rc = [&]() -> int {
 		int e;
-		const bool grow = want_log > ctx->logk_n;
-		if (grow) ctx->logk_n = 0; // (ensure may drop the old table)
-		if ((e = ensure(ctx, ctx->d_decide, o_end)) || (e = ensure(ctx, ctx->d_logk, (size_t)std::max(want_log, 1LL) * 8))) return e;
-		if ((e = st.stage(b_up + (grow ? (size_t)want_log * 8 + 64 : 0), b_down + 64))) return e;
+		if ((e = ensure(ctx, ctx->d_decide, L.end)) || (e = decide_stage_log(ctx, st, T.want_log, L.up(), L.down() + 64))) return e;
 		uint8_t *d = (uint8_t *)ctx->d_decide.p;
-		if (grow && (e = st.h2d(ctx->d_logk.p, ctx->h_logk, (size_t)want_log * 8))) return e;
-		if ((e = st.h2d(d, up, b_up))) return e;
-		DecideArgs A{};
-		A.roff = (const unsigned long long *)d, A.hdr = (const DecideHdr *)(d + o_hdr);
-		A.tab.logk = (const double *)ctx->d_logk.p, A.tab.term = (const double *)(d + o_term);
-		memcpy(A.tab.term_off, term_off, sizeof(term_off));
-		A.tab.n_log = want_log, A.tab.n_term = n_term;
-		A.reg = (bmh_alnreg_t *)(d + o_reg), A.total = total;
-		A.reg_mapq = (int32_t *)(d + o_mq), A.want_k = (int32_t *)(d + o_wk), A.n_want = (int32_t *)(d + o_nw), A.pd = (bmh_pairdec_t *)(d + o_pd);
-		A.z = (int *)(d + o_z), A.v = (bmh_pair64_t *)(d + o_v);
-		A.l_pac = l_pac, A.id0 = id0, A.n = n, A.pe = pe, A.err = ctx->d_err;
-		if ((e = launch_decide(ctx, A))) return e;
-		return st.d2h(down, d + o_reg, b_down);
+		if ((e = st.h2d(d, up.p, L.up())) || (e = launch_decide(ctx, decide_args(ctx, d, L, T, total, l_pac, id0, n, pe)))) return e;
+		return st.d2h(down.p, d + L.reg, L.down());
 	}();
 	if ((rc = st.end(rc))) return rc;
-	ctx->logk_n = want_log;
-	const int32_t *nw = (const int32_t *)(down + (o_nw - o_reg)), *wk = (const int32_t *)(down + (o_wk - o_reg));
-	for (int i = 0; i < n; ++i)
-		if (nw[i] < 0 || (size_t)nw[i] > regs[i].n) { // cannot happen
-			ctx->last_error = "bmh_decide_device: the device's counts are inconsistent";
-			return BMH_E_ARG;
-		}
-	// all or nothing: the caller's vectors and outputs only now
-	for (int i = 0; i < n; ++i)
-		if (regs[i].n) memcpy(regs[i].a, down + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].n * sizeof(bmh_alnreg_t));
-	memcpy(reg_mapq, down + (o_mq - o_reg), total * 4), memcpy(n_want, nw, nr * 4);
-	for (int i = 0; i < n; ++i) // (entries of want_k past a read's n_want stay the caller's)
-		if (nw[i]) memcpy(want_k + roff[i], wk + roff[i], (size_t)nw[i] * 4);
-	if (pe) memcpy(pd, down + (o_pd - o_reg), (nr >> 1) * sizeof(bmh_pairdec_t));
-	ctx->decide_units = pe ? n >> 1 : n, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+	ctx->logk_n = T.want_log;
+	if (decide_want_count(down.p, L, n, regs) < 0) {
+		ctx->last_error = "bmh_decide_device: the device's counts are inconsistent";
+		return BMH_E_ARG;
+	}
+	decide_commit(down.p, L, pe, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	reset_decide_stats(ctx), ctx->decide_units = pe ? n >> 1 : n;
 	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
 	return BMH_OK;
 }
@@ -1495,10 +1594,10 @@ int bmh_last_decide_stats(const bmh_ctx_t *ctx, int64_t *units, int64_t *fallbac
 // bmh_sam_batch at its entry, before any check of its own: with the switch on the statistics are this call's from here on
 __attribute__((visibility("hidden"))) void bmh_decide_stats_reset_(bmh_ctx_t *ctx)
 {
-	if (ctx && ctx->decide_device) ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
-	if (ctx && ctx->wanted_device) ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
-	if (ctx && ctx->phase2_device) ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
-	if (ctx && ctx->samtext_device) ctx->stx = bmh_samtext_stats_t{0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+	if (ctx && ctx->decide_device) reset_decide_stats(ctx);
+	if (ctx && ctx->wanted_device) reset_wanted_stats(ctx);
+	if (ctx && ctx->phase2_device) reset_phase2_stats(ctx);
+	if (ctx && ctx->samtext_device) reset_samtext_stats(ctx);
 }
 
 // bmh_sam_batch's pass A (host/sam_post.c; not part of the interface)
@@ -1508,7 +1607,7 @@ __attribute__((visibility("hidden"))) int bmh_decide_routed_(bmh_ctx_t *ctx, con
 {
 	if (ctx && ctx->decide_device) {
 		// (statistics of THIS call: a slice that never reaches the device call must not leave an earlier slice's on the context)
-		ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
+		reset_decide_stats(ctx);
 		const int rc = bmh_decide_device(ctx, o, l_pac, pes, id0, n, regs, roff, pd, reg_mapq, n_want, want_k);
 		if (rc != BMH_E_RANGE) return rc;
 	}
@@ -1570,13 +1669,13 @@ static int wanted_run_round(bmh_ctx *ctx, const WantedArgs &A, const WantedStatu
 }
 
 // the status records: the only thing the host reads between launches.  The wanted regions are n_lo..n_hi: the count where the host
-// knows it, 0..the capacity where pass A left the want list on the device.  st: the fused session's Stager, which counts the read.
-static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, Stager *st)
+// knows it, 0..the capacity where pass A left the want list on the device.  The fused session's Stager counts the read.
+static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, const Stager &st)
 {
 	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
 	BMH_HIP(ctx, hipMemcpyAsync(ctx->h_wstat, d_stat, 2 * sizeof(WantedStatus), hipMemcpyDeviceToHost, ctx->stream));
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-	if (st && st->p2) ++ctx->p2.waits, ctx->p2.d2h_bytes += (int64_t)(2 * sizeof(WantedStatus));
+	if (st.p2) ++ctx->p2.waits, ctx->p2.d2h_bytes += (int64_t)(2 * sizeof(WantedStatus));
 	if (hs[0].err || hs[1].err) {
 		ctx->last_error = "bmh_wanted_cigar_device: a wanted region is outside its read, its vector or the reference, or nothing is left of it";
 		return hs[0].err ? hs[0].err : hs[1].err;
@@ -1588,211 +1687,269 @@ static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo,
 	return BMH_OK;
 }
 
-// the device form up to its own records and pools (*cig_ / *md_: malloc'd, the caller frees them), for the public call and bmh_sam_batch
+// ---- Pass B's device session, once.  Two callers feed it: bmh_wanted_cigar_device uploads the want list and the regions in a block of
+// its own and knows the number of wanted regions; the fused session points at pass A's block, where decide_kernel left them, and
+// knows only a capacity.  The reads, the WantedHdr, the work arrays, the launches, the downloads and the host's tail are the same.
+
+// the oriented bytes a region the kernels accept can have: what a session's oriented pool is sized from before the first launch
+static size_t oriented_cap(const bmh_alnreg_t *a)
+{
+	return (size_t)std::clamp<int64_t>((int64_t)a->qe - a->qb, 0, 65535) + (size_t)std::clamp<int64_t>(a->re - a->rb, 0, 65535);
+}
+
+// the sections of an upload that are pass B's in both forms: the reads as one pool with 16 zero bytes behind it, so[] = its n + 1 offsets
+// (q_src = seq_off[read] + qb), and the parameters
+static void wanted_fill(const bmh_ctx *ctx, int w, int n, const bmh_read_t *reads, uint64_t *so, WantedHdr *hdr, uint8_t *rpool)
+{
+	size_t b = 0;
+	for (int i = 0; i < n; ++i) {
+		so[i] = b;
+		if (reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
+		b += (size_t)reads[i].l_seq;
+	}
+	so[n] = b;
+	memset(rpool + b, 0, 16);
+	const bmh_params_t &p = ctx->params;
+	memset(hdr, 0, sizeof(*hdr));
+	hdr->opt = bmh_rp_opt_t{p.a, p.mat[0], p.o_del, p.e_del, p.o_ins, p.e_ins, p.w};
+	hdr->fix_w = w;
+}
+
+// the work arrays, then what comes down, from where b stands in d_wanted; wc = the capacity in wanted regions
+struct WantedBlock {
+	size_t first, rec, key[4], sum[4], req[2], stat, res0, cig0, md0, res1, wres, cig1, md1, end;
+};
+
+static WantedBlock wanted_block(Block &b, size_t n, size_t wc)
+{
+	WantedBlock L;
+	L.first = b.take((n + 1) * 8), L.rec = b.take(wc * sizeof(WantRec));
+	for (int c = 0; c < 4; ++c) L.key[c] = b.take(wc * 4);
+	for (int c = 0; c < 4; ++c) L.sum[c] = b.take(wc * 8);
+	L.req[0] = b.take(wc * sizeof(bmh_region_req_t)), L.req[1] = b.take(wc * sizeof(bmh_region_req_t)), L.stat = b.take(2 * sizeof(WantedStatus));
+	L.res0 = b.take(wc * sizeof(bmh_region_res_t)), L.cig0 = b.take(wc * BMH_RP_SMALL_CAP * 4), L.md0 = b.take(wc * kWantFixMdSlot);
+	L.res1 = b.take(wc * sizeof(bmh_region_res_t)), L.wres = b.take(wc * sizeof(bmh_wanted_res_t));
+	L.cig1 = b.take(wc * BMH_RP_SMALL_CAP * 4), L.md1 = b.take(wc * kWantMdSlot), L.end = b.at;
+	return L;
+}
+
+// Every buffer the kernels write, sized before the first launch.  Device pool = [oriented copies | the reads as uploaded], as
+// bmh_region_cigar_batch lays it out: *rpool_off = where the reads go.
+static int wanted_reserve(bmh_ctx *ctx, size_t wc, size_t opool_cap, size_t reads_bytes, size_t wanted_bytes, size_t *rpool_off)
+{
+	int e;
+	*rpool_off = (opool_cap + 16 + 63) & ~(size_t)63;
+	ctx->pool_resident = false;
+	if (!ctx->h_wstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_wstat, 2 * sizeof(WantedStatus), hipHostMallocDefault));
+	if ((e = ensure(ctx, ctx->d_pool, *rpool_off + reads_bytes + 16)) || wc == 0) return e;
+	if ((e = ensure(ctx, ctx->d_tasks, 4 * wc * sizeof(bmh_glb_task_t))) || (e = ensure(ctx, ctx->d_res, 3 * wc * sizeof(bmh_glb_result_t)))) return e;
+	if ((e = ensure(ctx, ctx->d_cigar, (3 * wc * BMH_RP_SMALL_CAP + 4) * 4))) return e;
+	return ensure(ctx, ctx->d_wanted, wanted_bytes);
+}
+
+// what a session brings down: the records in want order, and the CIGAR and MD slots of the main round's n_rec records
+struct WantedDown {
+	bmh_wanted_res_t *wres = nullptr;      // n_w; cigar_off = md_off = the record's slot; BMH_WANTED_HOST: no slot, the host redoes it
+	uint8_t *cig = nullptr, *md = nullptr; // n_rec slots each, behind the records in the same malloc'd block
+	int64_t n_w = 0, n_rec = 0, n_fix = 0; // wanted regions; records of the main round and of round 0
+	~WantedDown() { free(wres); }
+};
+
+// The launches and the downloads.  A: the inputs as the caller set them -- roff, seq_off, hdr, n_want, want_k and reg where they lie on
+// the device, total, reads_bytes, n, l_pac, w_cap, opool_cap; the rest is set here.  dw, L: the session's arrays; n_lo..n_hi: see
+// wanted_read_status.  D's arrays (malloc'd here) are written behind st.end().
+static int wanted_session(bmh_ctx *ctx, const char *who, Stager &st, WantedArgs A, uint8_t *dw, const WantedBlock &L, size_t rpool_off, int64_t n_lo,
+                          int64_t n_hi, WantedDown &D)
+{
+	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
+	uint8_t *d_pool = (uint8_t *)ctx->d_pool.p;
+	int e;
+	BMH_HIP(ctx, hipMemsetAsync(dw + L.stat, 0, 2 * sizeof(WantedStatus), ctx->stream));
+	A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.n_seqs = ctx->refidx_n;
+	A.first = (unsigned long long *)(dw + L.first), A.rec = (WantRec *)(dw + L.rec);
+	for (int c = 0; c < 4; ++c) A.key[c] = (uint32_t *)(dw + L.key[c]), A.sum[c] = (unsigned long long *)(dw + L.sum[c]);
+	A.req[0] = (bmh_region_req_t *)(dw + L.req[0]), A.req[1] = (bmh_region_req_t *)(dw + L.req[1]);
+	A.task[0] = (bmh_glb_task_t *)ctx->d_tasks.p, A.task[1] = A.task[0] + A.w_cap;
+	A.fix_res = (const bmh_region_res_t *)(dw + L.res0), A.fix_cig = (const uint32_t *)(dw + L.cig0);
+	A.main_res = (const bmh_region_res_t *)(dw + L.res1), A.wres = (bmh_wanted_res_t *)(dw + L.wres);
+	A.status = (WantedStatus *)(dw + L.stat), A.err = ctx->d_err;
+	if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st))) return e;
+	if ((e = wanted_run_round(ctx, A, hs[0], 0, d_pool, rpool_off, (bmh_region_res_t *)(dw + L.res0), (uint32_t *)(dw + L.cig0), (char *)(dw + L.md0), kWantFixMdSlot)))
+		return e;
+	if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st))) return e;
+	if ((e = wanted_run_round(ctx, A, hs[1], 1, d_pool, rpool_off, (bmh_region_res_t *)(dw + L.res1), (uint32_t *)(dw + L.cig1), (char *)(dw + L.md1), kWantMdSlot)))
+		return e;
+	if ((e = launch_wanted_results(ctx, A))) return e;
+	// every download behind the last kernel: the slots of the records the status names, not of the capacity.  One block for the three:
+	// as allocations of their own glibc returned these few MB after every call, and each call paid the page faults again
+	D.n_w = hs[1].n_w, D.n_rec = hs[1].n_rec, D.n_fix = hs[0].n_rec;
+	const size_t bw = (size_t)D.n_w * sizeof(bmh_wanted_res_t), bc = (size_t)D.n_rec * BMH_RP_SMALL_CAP * 4, bm = (size_t)D.n_rec * kWantMdSlot;
+	if (!(D.wres = (bmh_wanted_res_t *)malloc(bw + bc + bm + 4))) {
+		ctx->last_error = std::string(who) + ": out of host memory";
+		return BMH_E_NOMEM;
+	}
+	D.cig = (uint8_t *)D.wres + bw, D.md = D.cig + bc;
+	if (bw && (e = st.d2h(D.wres, dw + L.wres, bw))) return e;
+	return bc && ((e = st.d2h(D.cig, dw + L.cig1, bc)) || (e = st.d2h(D.md, dw + L.md1, bm))) ? e : BMH_OK;
+}
+
+// the planning kernels' time of the session just ended (timing mode)
+static int wanted_kernel_ms(bmh_ctx *ctx)
+{
+	float a = 0.f, b = 0.f;
+	if (!ctx->timing || !ctx->ev_wanted[3]) return BMH_OK;
+	BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
+	BMH_HIP(ctx, hipEventElapsedTime(&b, ctx->ev_wanted[2], ctx->ev_wanted[3]));
+	ctx->wanted_ms = a + b;
+	return BMH_OK;
+}
+
+// The host's tail.  What came down is checked; the regions flagged BMH_WANTED_HOST, whose alignments outgrew their slots, go through
+// the host form again, one region per read of a small slice of its own (the fix again for a region whose fix outgrew its slot), (read, k)
+// from the want list, the region's record from `arena` -- every read's regions flat at roff: the stand-alone form's upload, the fused
+// session's sorted download -- with the coordinates as cut; then CIGAR and MD are packed in want order.  wr: D.n_w records, D.wres
+// itself if the caller likes; *cig_ / *md_: malloc'd, the caller frees them.  The want list is the caller's or checked by the caller.  who: the public entry point.
+static int wanted_tail(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads,
+                       const int64_t *roff, const int32_t *n_want, const int32_t *want_k, const bmh_alnreg_t *arena, const WantedDown &D,
+                       bmh_wanted_res_t *wr, uint32_t **cig_, char **md_, int64_t *redone)
+{
+	struct Redo {
+		int64_t j;
+		int read, k;
+	};
+	std::vector<Redo> redo;
+	const int64_t n_w = D.n_w;
+	size_t cu = 0, mu = 0;
+	int64_t j = 0;
+	for (int i = 0; i < n; ++i)
+		for (int q = 0; q < n_want[i]; ++q, ++j) {
+			const bmh_wanted_res_t &x = D.wres[j];
+			const int k = want_k[roff[i] + q];
+			const bool host = (x.flags & BMH_WANTED_HOST) != 0;
+			if (host ? k < 0 || k >= roff[i + 1] - roff[i]
+			         : (int64_t)x.cigar_off >= D.n_rec || x.n_cigar < 0 || x.n_cigar > BMH_RP_SMALL_CAP || x.md_len > (uint32_t)kWantMdSlot) { // cannot happen
+				ctx->last_error = std::string(who) + ": the device's records are inconsistent";
+				return BMH_E_ARG;
+			}
+			if (host) redo.push_back(Redo{j, i, k});
+			else cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+		}
+	const size_t m = redo.size();
+	std::vector<bmh_wanted_res_t> hw(m);
+	uint32_t *hcig = nullptr;
+	char *hmd = nullptr;
+	struct Free {
+		uint32_t *&a;
+		char *&b;
+		~Free() { free(a), free(b); }
+	} guard{hcig, hmd};
+	if (m) {
+		std::vector<bmh_alnreg_t> ra(m);
+		std::vector<bmh_alnreg_v> rv(m);
+		std::vector<bmh_read_t> rd(m);
+		std::vector<int64_t> ro(m + 1);
+		std::vector<int32_t> one(m, 1), zero(m, 0);
+		for (size_t t = 0; t < m; ++t) {
+			const bmh_wanted_res_t &x = D.wres[redo[t].j];
+			ra[t] = arena[roff[redo[t].read] + redo[t].k];
+			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe; // (as cut; a region whose fix is redone still has its own)
+			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[redo[t].read], ro[t] = (int64_t)t;
+		}
+		ro[m] = (int64_t)m;
+		const int rc = bmh_wanted_host_(ctx, bns, pac, w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr);
+		if (rc) return rc;
+	}
+	for (const bmh_wanted_res_t &x : hw) cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+	uint32_t *cig = (uint32_t *)malloc(4 * (cu + 4));
+	char *md = (char *)malloc(mu + 4);
+	if (!cig || !md) {
+		free(cig), free(md);
+		ctx->last_error = std::string(who) + ": out of host memory";
+		return BMH_E_NOMEM;
+	}
+	cu = mu = 0;
+	size_t t = 0;
+	for (j = 0; j < n_w; ++j) { // packed in want order
+		bmh_wanted_res_t x = D.wres[j];
+		const uint32_t *sc;
+		const char *sm;
+		if (t < m && redo[t].j == j) {
+			const uint32_t fl = x.flags;
+			x = hw[t], sc = hcig + x.cigar_off, sm = hmd + x.md_off;
+			x.flags |= fl | BMH_WANTED_HOST;
+			++t;
+		} else sc = (const uint32_t *)D.cig + (size_t)x.cigar_off * BMH_RP_SMALL_CAP, sm = (const char *)D.md + (size_t)x.md_off * kWantMdSlot;
+		memcpy(cig + cu, sc, 4 * (size_t)x.n_cigar), memcpy(md + mu, sm, x.md_len), md[mu + x.md_len] = 0;
+		x.cigar_off = (uint32_t)cu, x.md_off = (uint32_t)mu;
+		cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+		wr[j] = x;
+	}
+	*cig_ = cig, *md_ = md, *redone = (int64_t)m;
+	return BMH_OK;
+}
+
+// the stand-alone form up to its own records and pools (*cig_ / *md_: malloc'd, the caller frees them), for the public call and bmh_sam_batch
 static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
                              const int64_t *roff, const int32_t *n_want, const int32_t *want_k, int64_t n_w, bmh_wanted_res_t *wr, uint32_t **cig_, char **md_)
 {
 	*cig_ = nullptr, *md_ = nullptr;
-	ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
+	reset_wanted_stats(ctx);
 	if (!ctx->have_params) return BMH_E_ARG;
-	if (!ctx->dev.pac || ctx->h_pac != pac || ctx->dev.l_pac != bns->l_pac) {
-		ctx->last_error = "bmh_wanted_cigar_device needs the resident reference (bmh_ctx_set_pac)";
-		return BMH_E_ARG;
-	}
-	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
-		ctx->last_error = "bmh_wanted_cigar_device needs the resident sequence table (bmh_ctx_set_refidx)";
-		return BMH_E_ARG;
-	}
-	if (n_w == 0) return BMH_OK;
+	int rc = need_resident(ctx, "bmh_wanted_cigar_device", bns, pac);
+	if (rc || n_w == 0) return rc;
 	if (n_w > (1 << 28) || n > (1 << 28)) return BMH_E_ARG;
-	const int64_t l_pac = bns->l_pac;
 	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = (size_t)n_w;
-	// every buffer the kernels write, sized before the first launch: the oriented pool from the lengths a region the kernels accept can have
 	size_t reads_bytes = 0, opool_cap = 0;
 	for (int i = 0; i < n; ++i) {
 		reads_bytes += (size_t)reads[i].l_seq;
 		for (int q = 0; q < n_want[i]; ++q) {
 			const int k = want_k[roff[i] + q];
-			if (k < 0 || (size_t)k >= regs[i].n) continue; // (the kernel refuses it)
-			const bmh_alnreg_t *a = &regs[i].a[k];
-			opool_cap += (size_t)std::clamp<int64_t>((int64_t)a->qe - a->qb, 0, 65535) + (size_t)std::clamp<int64_t>(a->re - a->rb, 0, 65535);
+			if (k >= 0 && (size_t)k < regs[i].n) opool_cap += oriented_cap(&regs[i].a[k]); // (another the kernel refuses)
 		}
 	}
-	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-	// the device block: [offsets | read offsets | parameters | n_want | want_k | regions] up, then work arrays, then what comes down
-	const size_t o_soff = al((nr + 1) * 8), o_hdr = o_soff + al((nr + 1) * 8), o_nw = o_hdr + al(sizeof(WantedHdr)), o_wk = o_nw + al(nr * 4);
-	const size_t o_reg = o_wk + al(total * 4), b_up = o_reg + al(total * sizeof(bmh_alnreg_t));
-	size_t at = b_up;
-	auto take = [&](size_t bytes) {
-		const size_t o = at;
-		at += al(bytes);
-		return o;
-	};
-	const size_t o_first = take((nr + 1) * 8), o_rec = take(wc * sizeof(WantRec));
-	size_t o_key[4], o_sum[4];
-	for (int c = 0; c < 4; ++c) o_key[c] = take(wc * 4);
-	for (int c = 0; c < 4; ++c) o_sum[c] = take(wc * 8);
-	const size_t o_req0 = take(wc * sizeof(bmh_region_req_t)), o_req1 = take(wc * sizeof(bmh_region_req_t)), o_stat = take(2 * sizeof(WantedStatus));
-	const size_t o_res0 = take(wc * sizeof(bmh_region_res_t)), o_cig0 = take(wc * BMH_RP_SMALL_CAP * 4), o_md0 = take(wc * kWantFixMdSlot);
-	const size_t o_res1 = take(wc * sizeof(bmh_region_res_t)), o_cig1 = take(wc * BMH_RP_SMALL_CAP * 4), o_md1 = take(wc * kWantMdSlot), o_end = at;
-	uint8_t *up = (uint8_t *)malloc(b_up), *rpool = (uint8_t *)malloc(reads_bytes + 16);
-	WantRec *rec = (WantRec *)malloc(wc * sizeof(WantRec));
-	uint8_t *down = (uint8_t *)malloc(o_end - o_res1);
-	struct Free {
-		void *a, *b, *c, *d;
-		~Free() { free(a), free(b), free(c), free(d); }
-	} guard{up, rpool, rec, down};
-	if (!up || !rpool || !rec || !down) {
+	// the device block: [offsets | read offsets | parameters | n_want | want_k | regions] up, then the session's arrays
+	Block b;
+	b.take((nr + 1) * 8);
+	const size_t o_soff = b.take((nr + 1) * 8), o_hdr = b.take(sizeof(WantedHdr)), o_nw = b.take(nr * 4), o_wk = b.take(total * 4);
+	const size_t o_reg = b.take(total * sizeof(bmh_alnreg_t)), b_up = b.at;
+	const WantedBlock L = wanted_block(b, nr, wc);
+	HostBuf up(b_up), rpool(reads_bytes + 16);
+	if (!up.p || !rpool.p) {
 		ctx->last_error = "bmh_wanted_cigar_device: out of host memory";
 		return BMH_E_NOMEM;
 	}
-	memcpy(up, roff, (nr + 1) * 8);
-	{
-		uint64_t *so = (uint64_t *)(up + o_soff);
-		size_t b = 0;
-		for (int i = 0; i < n; ++i) {
-			so[i] = b;
-			if (reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
-			b += (size_t)reads[i].l_seq;
-		}
-		so[n] = b;
-		memset(rpool + b, 0, 16);
-	}
-	WantedHdr *hdr = (WantedHdr *)(up + o_hdr);
-	const bmh_params_t &p = ctx->params;
-	hdr->opt = bmh_rp_opt_t{p.a, p.mat[0], p.o_del, p.e_del, p.o_ins, p.e_ins, p.w};
-	hdr->fix_w = w;
-	memcpy(up + o_nw, n_want, nr * 4);
+	memcpy(up.p, roff, (nr + 1) * 8);
+	wanted_fill(ctx, w, n, reads, (uint64_t *)(up.p + o_soff), (WantedHdr *)(up.p + o_hdr), rpool.p);
+	memcpy(up.p + o_nw, n_want, nr * 4);
 	for (int i = 0; i < n; ++i) {
-		if (n_want[i]) memcpy(up + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
-		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+		if (n_want[i]) memcpy(up.p + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
+		if (regs[i].n) memcpy(up.p + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
 	}
-	int64_t n_rec1 = 0, n_fix = 0;
-	int rc = BMH_OK;
-	{ // the device section, inside the caller's gate (the redo below enters it again through the host form)
+	WantedDown D;
+	{ // the device section, inside the caller's gate (the redo enters it again through the host form)
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	if (!ctx->h_wstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_wstat, 2 * sizeof(WantedStatus), hipHostMallocDefault));
-	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
 	Stager st(ctx);
 	rc = [&]() -> int {
 		int e;
-		// device pool = [oriented copies | the reads as uploaded], as bmh_region_cigar_batch lays it out
-		const size_t rpool_off = (opool_cap + 16 + 63) & ~(size_t)63;
-		ctx->pool_resident = false;
-		if ((e = ensure(ctx, ctx->d_pool, rpool_off + reads_bytes + 16))) return e;
-		if ((e = ensure(ctx, ctx->d_tasks, 4 * wc * sizeof(bmh_glb_task_t))) || (e = ensure(ctx, ctx->d_res, 3 * wc * sizeof(bmh_glb_result_t)))) return e;
-		if ((e = ensure(ctx, ctx->d_cigar, (3 * wc * BMH_RP_SMALL_CAP + 4) * 4)) || (e = ensure(ctx, ctx->d_wanted, o_end))) return e;
-		if ((e = st.stage(b_up + reads_bytes + 256, wc * sizeof(WantRec) + (o_end - o_res1) + 256))) return e;
-		uint8_t *d = (uint8_t *)ctx->d_wanted.p, *d_pool = (uint8_t *)ctx->d_pool.p;
-		BMH_HIP(ctx, hipMemsetAsync(d + o_stat, 0, 2 * sizeof(WantedStatus), ctx->stream));
-		if ((e = st.h2d(d, up, b_up)) || (e = st.h2d(d_pool + rpool_off, rpool, reads_bytes + 16))) return e;
+		size_t rpool_off;
+		if ((e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, L.end, &rpool_off)) || (e = st.stage(b_up + reads_bytes + 256, L.end - L.wres + 256))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_wanted.p;
+		if ((e = st.h2d(d, up.p, b_up)) || (e = st.h2d((uint8_t *)ctx->d_pool.p + rpool_off, rpool.p, reads_bytes + 16))) return e;
 		WantedArgs A{};
 		A.roff = (const unsigned long long *)d, A.seq_off = (const unsigned long long *)(d + o_soff), A.hdr = (const WantedHdr *)(d + o_hdr);
 		A.n_want = (const int32_t *)(d + o_nw), A.want_k = (const int32_t *)(d + o_wk), A.reg = (const bmh_alnreg_t *)(d + o_reg);
-		A.total = total, A.reads_bytes = reads_bytes, A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.n_seqs = ctx->refidx_n, A.n = n, A.l_pac = l_pac;
-		A.first = (unsigned long long *)(d + o_first), A.rec = (WantRec *)(d + o_rec);
-		for (int c = 0; c < 4; ++c) A.key[c] = (uint32_t *)(d + o_key[c]), A.sum[c] = (unsigned long long *)(d + o_sum[c]);
-		A.req[0] = (bmh_region_req_t *)(d + o_req0), A.req[1] = (bmh_region_req_t *)(d + o_req1);
-		A.task[0] = (bmh_glb_task_t *)ctx->d_tasks.p, A.task[1] = A.task[0] + wc;
-		A.fix_res = (const bmh_region_res_t *)(d + o_res0), A.fix_cig = (const uint32_t *)(d + o_cig0);
-		A.status = (WantedStatus *)(d + o_stat), A.w_cap = wc, A.opool_cap = opool_cap, A.err = ctx->d_err;
-		auto run_round = [&](int r, size_t o_res, size_t o_cig, size_t o_md, int md_cap) {
-			return wanted_run_round(ctx, A, hs[r], r, d_pool, rpool_off, (bmh_region_res_t *)(d + o_res), (uint32_t *)(d + o_cig), (char *)(d + o_md), md_cap);
-		};
-		auto read_status = [&]() { return wanted_read_status(ctx, d + o_stat, n_w, n_w, nullptr); };
-		if ((e = launch_wanted_begin(ctx, A)) || (e = read_status())) return e;
-		if ((e = run_round(0, o_res0, o_cig0, o_md0, kWantFixMdSlot))) return e;
-		if ((e = launch_wanted_main(ctx, A)) || (e = read_status())) return e;
-		if ((e = run_round(1, o_res1, o_cig1, o_md1, kWantMdSlot))) return e;
-		n_rec1 = hs[1].n_rec;
-		if ((e = st.d2h(rec, d + o_rec, wc * sizeof(WantRec)))) return e;
-		return n_rec1 ? st.d2h(down, d + o_res1, o_end - o_res1) : BMH_OK;
+		A.total = total, A.reads_bytes = reads_bytes, A.n = n, A.l_pac = bns->l_pac, A.w_cap = wc, A.opool_cap = opool_cap;
+		return wanted_session(ctx, "bmh_wanted_cigar_device", st, A, d, L, rpool_off, n_w, n_w, D);
 	}();
 	rc = st.end(rc);
 	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
+	if (rc || (rc = wanted_kernel_ms(ctx))) return rc;
+	}
+	int64_t redone = 0;
+	rc = wanted_tail(ctx, "bmh_wanted_cigar_device", bns, pac, w, n, reads, roff, n_want, want_k, (const bmh_alnreg_t *)(up.p + o_reg), D, wr, cig_, md_, &redone);
 	if (rc) return rc;
-	n_fix = hs[0].n_rec;
-	if (ctx->timing && ctx->ev_wanted[3]) {
-		float a = 0.f, b = 0.f;
-		BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
-		BMH_HIP(ctx, hipEventElapsedTime(&b, ctx->ev_wanted[2], ctx->ev_wanted[3]));
-		ctx->wanted_ms = a + b;
-	}
-	}
-	// ---- the records: the device's, and the few regions whose alignments outgrew their slots again through the host form
-	const bmh_region_res_t *rr = (const bmh_region_res_t *)down;
-	const uint32_t *cout = (const uint32_t *)(down + (o_cig1 - o_res1));
-	const char *mout = (const char *)(down + (o_md1 - o_res1));
-	std::vector<int64_t> redo;
-	size_t cu = 0, mu = 0;
-	for (int64_t j = 0; j < n_w; ++j) {
-		const WantRec &x = rec[j];
-		const bool ok = x.state == kWantOk && x.v >= 0 && x.v < n_rec1 && x.read >= 0 && x.read < n && x.k >= 0 && (size_t)x.k < regs[x.read].n;
-		if (!ok && x.state != kWantHost) {
-			ctx->last_error = "bmh_wanted_cigar_device: the device's records are inconsistent";
-			return BMH_E_ARG;
-		}
-		if (x.state == kWantHost || rr[x.v].flags) redo.push_back(j);
-		else cu += (size_t)rr[x.v].n_cigar, mu += (size_t)rr[x.v].md_len + 1;
-	}
-	std::vector<bmh_wanted_res_t> hw(redo.size());
-	uint32_t *hcig = nullptr;
-	char *hmd = nullptr;
-	struct Free2 {
-		uint32_t *&a;
-		char *&b;
-		~Free2() { free(a), free(b); }
-	} guard2{hcig, hmd};
-	if (!redo.empty()) { // one region per read of a small slice of its own: the fix again for a region whose fix outgrew its slot
-		const size_t m = redo.size();
-		std::vector<bmh_alnreg_t> ra(m);
-		std::vector<bmh_alnreg_v> rv(m);
-		std::vector<bmh_read_t> rd(m);
-		std::vector<int64_t> ro(m + 1);
-		std::vector<int32_t> nw(m, 1), wk(m, 0);
-		for (size_t t = 0; t < m; ++t) {
-			const WantRec &x = rec[redo[t]];
-			ra[t] = regs[x.read].a[x.k];
-			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe; // (as cut; a region whose fix is redone still has its own)
-			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[x.read], ro[t] = (int64_t)t;
-		}
-		ro[m] = (int64_t)m;
-		if ((rc = bmh_wanted_host_(ctx, bns, pac, w, (int)m, rd.data(), rv.data(), ro.data(), nw.data(), wk.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr)))
-			return rc;
-		for (size_t t = 0; t < m; ++t) cu += (size_t)hw[t].n_cigar, mu += (size_t)hw[t].md_len + 1;
-	}
-	uint32_t *cig = (uint32_t *)malloc(4 * (cu + 4));
-	char *md = (char *)malloc(mu + 4);
-	if (!cig || !md) {
-		free(cig), free(md);
-		ctx->last_error = "bmh_wanted_cigar_device: out of host memory";
-		return BMH_E_NOMEM;
-	}
-	cu = mu = 0;
-	size_t t = 0;
-	for (int64_t j = 0; j < n_w; ++j) {
-		const WantRec &x = rec[j];
-		bmh_wanted_res_t o{};
-		const uint32_t *sc;
-		const char *sm;
-		if (t < redo.size() && redo[t] == j) {
-			o = hw[t], sc = hcig + o.cigar_off, sm = hmd + o.md_off;
-			o.flags |= x.flags | BMH_WANTED_HOST;
-			++t;
-		} else {
-			const bmh_region_res_t &r = rr[x.v];
-			o.rb = x.rb, o.re = x.re, o.qb = x.qb, o.qe = x.qe, o.score = r.score, o.n_cigar = r.n_cigar, o.NM = r.NM, o.tries = r.tries;
-			o.md_len = (uint32_t)r.md_len, o.flags = x.flags, o.band[0] = x.band[0], o.band[1] = x.band[1], o.band[2] = x.band[2];
-			sc = cout + (size_t)x.v * BMH_RP_SMALL_CAP, sm = mout + (size_t)x.v * kWantMdSlot;
-		}
-		memcpy(cig + cu, sc, 4 * (size_t)o.n_cigar), memcpy(md + mu, sm, o.md_len), md[mu + o.md_len] = 0;
-		o.cigar_off = (uint32_t)cu, o.md_off = (uint32_t)mu;
-		cu += (size_t)o.n_cigar, mu += (size_t)o.md_len + 1;
-		wr[j] = o;
-	}
-	ctx->wanted_n = n_w, ctx->wanted_fixed = n_fix, ctx->wanted_redone = (long long)redo.size();
-	*cig_ = cig, *md_ = md;
+	ctx->wanted_n = n_w, ctx->wanted_fixed = D.n_fix, ctx->wanted_redone = redone;
 	return BMH_OK;
 }
 
@@ -1855,30 +2012,16 @@ static int phase2_check_reads(const bmh_refidx_t *bns, const uint8_t *pac, int n
 	return BMH_OK;
 }
 
-// what a fused session holds on the host until everything has succeeded: nothing of the caller's is written before phase2_commit
+// what a fused session holds on the host until everything has succeeded: nothing of the caller's is written before decide_commit
 struct Phase2Run {
+	DecideBlock L;
 	std::vector<uint8_t> down;        // pass A's block as downloaded: [regions | reg_mapq | want_k | n_want | pd], the regions sorted
-	size_t o_mq = 0, o_wk = 0, o_nw = 0, o_pd = 0;
 	int64_t n_w = 0;
-	std::vector<bmh_wanted_res_t> wr; // want order; cigar_off / md_off address cig / md
+	bmh_wanted_res_t *wr = nullptr;   // want order; cigar_off / md_off address cig / md
 	uint32_t *cig = nullptr;
 	char *md = nullptr;
-	~Phase2Run() { free(cig), free(md); }
+	~Phase2Run() { free(wr), free(cig), free(md); }
 };
-
-static void phase2_commit(const Phase2Run &R, bool pe, int n, bmh_alnreg_v *regs, const int64_t *roff, bmh_pairdec_t *pd, int32_t *reg_mapq,
-                          int32_t *n_want, int32_t *want_k)
-{
-	const uint8_t *down = R.down.data();
-	const size_t nr = (size_t)n, total = (size_t)roff[n];
-	const int32_t *nw = (const int32_t *)(down + R.o_nw), *wk = (const int32_t *)(down + R.o_wk);
-	for (int i = 0; i < n; ++i)
-		if (regs[i].n) memcpy(regs[i].a, down + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].n * sizeof(bmh_alnreg_t));
-	memcpy(reg_mapq, down + R.o_mq, total * 4), memcpy(n_want, nw, nr * 4);
-	for (int i = 0; i < n; ++i) // (entries of want_k past a read's n_want stay the caller's)
-		if (nw[i]) memcpy(want_k + roff[i], wk + roff[i], (size_t)nw[i] * 4);
-	if (pe) memcpy(pd, down + R.o_pd, (nr >> 1) * sizeof(bmh_pairdec_t));
-}
 
 // The session up to its own records and pools, for the public call and bmh_sam_batch.  n > 0 and the arguments checked.  *tables: the
 // BMH_E_RANGE is bmh_decide_device's refusal before any upload, not a kernel's.
@@ -1886,266 +2029,91 @@ static int phase2_device_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_ref
                              const bmh_read_t *reads, const bmh_alnreg_v *regs, const int64_t *roff, Phase2Run &R, bool *tables)
 {
 	*tables = false;
-	ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
-	ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f;
-	ctx->wanted_n = 0, ctx->wanted_fixed = 0, ctx->wanted_redone = 0, ctx->wanted_ms = -1.f;
+	reset_phase2_stats(ctx), reset_decide_stats(ctx), reset_wanted_stats(ctx);
 	if (!ctx->have_params) return BMH_E_ARG;
-	if (!ctx->dev.pac || ctx->h_pac != pac || ctx->dev.l_pac != bns->l_pac) {
-		ctx->last_error = "bmh_phase2_device needs the resident reference (bmh_ctx_set_pac)";
-		return BMH_E_ARG;
-	}
-	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
-		ctx->last_error = "bmh_phase2_device needs the resident sequence table (bmh_ctx_set_refidx)";
-		return BMH_E_ARG;
-	}
+	int rc = need_resident(ctx, "bmh_phase2_device", bns, pac);
+	if (rc) return rc;
 	if (n > (1 << 28) || roff[n] > (1 << 28)) return BMH_E_ARG;
 	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
-	const int64_t l_pac = bns->l_pac;
 	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = total; // wc: the capacity of everything per wanted region, which bounds their number
-	long long kmax = 1, n_term = 0, want_log = 0;
-	int64_t term_off[4] = {0, 0, 0, 0};
+	DecideTables T;
 	const char *why = nullptr;
-	int rc;
-	if (decide_table_sizes(o, pes, n, regs, &kmax, &n_term, term_off, &why)) {
+	if (decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why)) {
 		ctx->last_error = why;
 		ctx->decide_fallbacks = 1, ctx->p2.fallbacks = 1, *tables = true;
 		return BMH_E_RANGE;
 	}
-	if ((rc = decide_host_log(ctx, kmax, &want_log))) return rc;
+	if ((rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
 	// the oriented pool from the clamped lengths of every region: a sum the sort does not change, and a cut only shortens a region
 	size_t reads_bytes = 0, opool_cap = 0;
 	for (int i = 0; i < n; ++i) {
 		reads_bytes += (size_t)reads[i].l_seq;
-		for (size_t k = 0; k < regs[i].n; ++k) {
-			const bmh_alnreg_t *a = &regs[i].a[k];
-			opool_cap += (size_t)std::clamp<int64_t>((int64_t)a->qe - a->qb, 0, 65535) + (size_t)std::clamp<int64_t>(a->re - a->rb, 0, 65535);
-		}
+		for (size_t k = 0; k < regs[i].n; ++k) opool_cap += oriented_cap(&regs[i].a[k]);
 	}
-	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-	// pass A's block with pass B's inputs in it: [offsets | opt + pes | read offsets | WantedHdr | pair table | regions] up,
-	// [regions | reg_mapq | want_k | n_want | pd] down, then decide_kernel's two scratch arrays
-	const size_t o_hdr = al((nr + 1) * 8), o_soff = o_hdr + al(sizeof(DecideHdr)), o_whdr = o_soff + al((nr + 1) * 8), o_term = o_whdr + al(sizeof(WantedHdr));
-	const size_t o_reg = o_term + al((size_t)n_term * 8), o_mq = o_reg + al(total * sizeof(bmh_alnreg_t)), o_wk = o_mq + al(total * 4), o_nw = o_wk + al(total * 4);
-	const size_t o_pd = o_nw + al(nr * 4), o_z = o_pd + al(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0), o_v = o_z + al(total * 4);
-	const size_t o_endA = o_v + al(pe ? total * sizeof(bmh_pair64_t) : 0), b_up = o_mq, b_down = o_z - o_reg;
-	// pass B's block: work arrays, then what comes down
-	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t o_ = at;
-		at += al(bytes);
-		return o_;
-	};
-	const size_t o_first = take((nr + 1) * 8), o_rec = take(wc * sizeof(WantRec));
-	size_t o_key[4], o_sum[4];
-	for (int c = 0; c < 4; ++c) o_key[c] = take(wc * 4);
-	for (int c = 0; c < 4; ++c) o_sum[c] = take(wc * 8);
-	const size_t o_req0 = take(wc * sizeof(bmh_region_req_t)), o_req1 = take(wc * sizeof(bmh_region_req_t)), o_stat = take(2 * sizeof(WantedStatus));
-	const size_t o_res0 = take(wc * sizeof(bmh_region_res_t)), o_cig0 = take(wc * BMH_RP_SMALL_CAP * 4), o_md0 = take(wc * kWantFixMdSlot);
-	const size_t o_res1 = take(wc * sizeof(bmh_region_res_t)), o_wres = take(wc * sizeof(bmh_wanted_res_t)), o_cig1 = take(wc * BMH_RP_SMALL_CAP * 4);
-	const size_t o_md1 = take(wc * kWantMdSlot), o_endB = at;
-	uint8_t *up = (uint8_t *)malloc(b_up), *rpool = (uint8_t *)malloc(reads_bytes + 16);
-	struct Free {
-		void *a, *b;
-		~Free() { free(a), free(b); }
-	} guard{up, rpool};
-	if (!up || !rpool) {
+	// pass A's block with pass B's inputs in it, and the session's arrays in a block of their own
+	const DecideBlock LA = R.L = decide_block(nr, total, (size_t)T.n_term, pe, true);
+	Block b;
+	const WantedBlock LB = wanted_block(b, nr, wc);
+	HostBuf up(LA.up()), rpool(reads_bytes + 16);
+	if (!up.p || !rpool.p) {
 		ctx->last_error = "bmh_phase2_device: out of host memory";
 		return BMH_E_NOMEM;
 	}
-	R.down.resize(b_down);
-	R.o_mq = o_mq - o_reg, R.o_wk = o_wk - o_reg, R.o_nw = o_nw - o_reg, R.o_pd = o_pd - o_reg;
-	memcpy(up, roff, (nr + 1) * 8);
-	DecideHdr *hdr = (DecideHdr *)(up + o_hdr);
-	memset(hdr, 0, sizeof(*hdr));
-	hdr->opt = *o;
-	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
-	{
-		uint64_t *so = (uint64_t *)(up + o_soff);
-		size_t b = 0;
-		for (int i = 0; i < n; ++i) {
-			so[i] = b;
-			if (reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
-			b += (size_t)reads[i].l_seq;
-		}
-		so[n] = b;
-		memset(rpool + b, 0, 16);
-	}
-	WantedHdr *whdr = (WantedHdr *)(up + o_whdr);
-	const bmh_params_t &p = ctx->params;
-	memset(whdr, 0, sizeof(*whdr));
-	whdr->opt = bmh_rp_opt_t{p.a, p.mat[0], p.o_del, p.e_del, p.o_ins, p.e_ins, p.w};
-	whdr->fix_w = o->w;
-	if (n_term) bmh_pp_fill_term_(o, pes, term_off, (double *)(up + o_term));
-	for (int i = 0; i < n; ++i)
-		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
-	std::vector<uint8_t> cigdown, mddown;
-	int64_t n_w = 0, n_rec1 = 0, n_fix = 0;
-	{ // the device section, inside the caller's gate (the redo below enters it again through the host form)
+	R.down.resize(LA.down());
+	decide_fill(up.p, LA, o, pes, T, n, regs, roff);
+	wanted_fill(ctx, o->w, n, reads, (uint64_t *)(up.p + LA.soff), (WantedHdr *)(up.p + LA.whdr), rpool.p);
+	WantedDown D;
+	{ // the device section, inside the caller's gate (the redo enters it again through the host form)
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
-	if (!ctx->h_wstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_wstat, 2 * sizeof(WantedStatus), hipHostMallocDefault));
-	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
 	Stager st(ctx);
 	st.p2 = true;
 	rc = [&]() -> int {
 		int e;
-		const bool grow = want_log > ctx->logk_n;
-		if (grow) ctx->logk_n = 0; // (ensure may drop the old table)
-		if ((e = ensure(ctx, ctx->d_decide, o_endA)) || (e = ensure(ctx, ctx->d_logk, (size_t)std::max(want_log, 1LL) * 8))) return e;
-		// device pool = [oriented copies | the reads as uploaded], as bmh_region_cigar_batch lays it out
-		const size_t rpool_off = (opool_cap + 16 + 63) & ~(size_t)63;
-		ctx->pool_resident = false;
-		if ((e = ensure(ctx, ctx->d_pool, rpool_off + reads_bytes + 16))) return e;
-		if (wc) {
-			if ((e = ensure(ctx, ctx->d_tasks, 4 * wc * sizeof(bmh_glb_task_t))) || (e = ensure(ctx, ctx->d_res, 3 * wc * sizeof(bmh_glb_result_t)))) return e;
-			if ((e = ensure(ctx, ctx->d_cigar, (3 * wc * BMH_RP_SMALL_CAP + 4) * 4)) || (e = ensure(ctx, ctx->d_wanted, o_endB))) return e;
+		size_t rpool_off;
+		if ((e = ensure(ctx, ctx->d_decide, LA.end)) || (e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, LB.end, &rpool_off))) return e;
+		if ((e = decide_stage_log(ctx, st, T.want_log, LA.up() + reads_bytes + 256, LA.down() + (LB.end - LB.wres) + 256))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_decide.p;
+		if ((e = st.h2d(d, up.p, LA.up())) || (e = st.h2d((uint8_t *)ctx->d_pool.p + rpool_off, rpool.p, reads_bytes + 16))) return e;
+		BMH_HIP(ctx, hipMemsetAsync(d + LA.nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
+		const DecideArgs DA = decide_args(ctx, d, LA, T, total, bns->l_pac, id0, n, pe);
+		if ((e = launch_decide(ctx, DA))) return e;
+		if (wc) { // pass B reads n_want, want_k and the sorted regions where decide_kernel left them: no wait, no copy in between
+			WantedArgs A{};
+			A.roff = DA.roff, A.seq_off = (const unsigned long long *)(d + LA.soff), A.hdr = (const WantedHdr *)(d + LA.whdr);
+			A.n_want = DA.n_want, A.want_k = DA.want_k, A.reg = DA.reg;
+			A.total = total, A.reads_bytes = reads_bytes, A.n = n, A.l_pac = bns->l_pac, A.w_cap = wc, A.opool_cap = opool_cap;
+			if ((e = wanted_session(ctx, "bmh_phase2_device", st, A, (uint8_t *)ctx->d_wanted.p, LB, rpool_off, 0, (int64_t)wc, D))) return e;
 		}
-		if ((e = st.stage(b_up + reads_bytes + (grow ? (size_t)want_log * 8 + 64 : 0) + 256, b_down + (o_endB - o_wres) + 256))) return e;
-		uint8_t *d = (uint8_t *)ctx->d_decide.p, *dw = (uint8_t *)ctx->d_wanted.p, *d_pool = (uint8_t *)ctx->d_pool.p;
-		if (grow && (e = st.h2d(ctx->d_logk.p, ctx->h_logk, (size_t)want_log * 8))) return e;
-		if ((e = st.h2d(d, up, b_up)) || (e = st.h2d(d_pool + rpool_off, rpool, reads_bytes + 16))) return e;
-		BMH_HIP(ctx, hipMemsetAsync(d + o_nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
-		DecideArgs D{};
-		D.roff = (const unsigned long long *)d, D.hdr = (const DecideHdr *)(d + o_hdr);
-		D.tab.logk = (const double *)ctx->d_logk.p, D.tab.term = (const double *)(d + o_term);
-		memcpy(D.tab.term_off, term_off, sizeof(term_off));
-		D.tab.n_log = want_log, D.tab.n_term = n_term;
-		D.reg = (bmh_alnreg_t *)(d + o_reg), D.total = total;
-		D.reg_mapq = (int32_t *)(d + o_mq), D.want_k = (int32_t *)(d + o_wk), D.n_want = (int32_t *)(d + o_nw), D.pd = (bmh_pairdec_t *)(d + o_pd);
-		D.z = (int *)(d + o_z), D.v = (bmh_pair64_t *)(d + o_v);
-		D.l_pac = l_pac, D.id0 = id0, D.n = n, D.pe = pe, D.err = ctx->d_err;
-		if ((e = launch_decide(ctx, D))) return e;
-		if (wc == 0) return st.d2h(R.down.data(), d + o_reg, b_down); // no region at all: pass A's verdicts alone
-		// pass B reads n_want, want_k and the sorted regions where decide_kernel left them: no wait, no copy in between
-		BMH_HIP(ctx, hipMemsetAsync(dw + o_stat, 0, 2 * sizeof(WantedStatus), ctx->stream));
-		WantedArgs A{};
-		A.roff = D.roff, A.seq_off = (const unsigned long long *)(d + o_soff), A.hdr = (const WantedHdr *)(d + o_whdr);
-		A.n_want = D.n_want, A.want_k = D.want_k, A.reg = D.reg;
-		A.total = total, A.reads_bytes = reads_bytes, A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.n_seqs = ctx->refidx_n, A.n = n, A.l_pac = l_pac;
-		A.first = (unsigned long long *)(dw + o_first), A.rec = (WantRec *)(dw + o_rec);
-		for (int c = 0; c < 4; ++c) A.key[c] = (uint32_t *)(dw + o_key[c]), A.sum[c] = (unsigned long long *)(dw + o_sum[c]);
-		A.req[0] = (bmh_region_req_t *)(dw + o_req0), A.req[1] = (bmh_region_req_t *)(dw + o_req1);
-		A.task[0] = (bmh_glb_task_t *)ctx->d_tasks.p, A.task[1] = A.task[0] + wc;
-		A.fix_res = (const bmh_region_res_t *)(dw + o_res0), A.fix_cig = (const uint32_t *)(dw + o_cig0);
-		A.main_res = (const bmh_region_res_t *)(dw + o_res1), A.wres = (bmh_wanted_res_t *)(dw + o_wres);
-		A.status = (WantedStatus *)(dw + o_stat), A.w_cap = wc, A.opool_cap = opool_cap, A.err = ctx->d_err;
-		if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + o_stat, 0, (int64_t)wc, &st))) return e;
-		if ((e = wanted_run_round(ctx, A, hs[0], 0, d_pool, rpool_off, (bmh_region_res_t *)(dw + o_res0), (uint32_t *)(dw + o_cig0), (char *)(dw + o_md0), kWantFixMdSlot)))
-			return e;
-		if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + o_stat, 0, (int64_t)wc, &st))) return e;
-		if ((e = wanted_run_round(ctx, A, hs[1], 1, d_pool, rpool_off, (bmh_region_res_t *)(dw + o_res1), (uint32_t *)(dw + o_cig1), (char *)(dw + o_md1), kWantMdSlot)))
-			return e;
-		if ((e = launch_wanted_results(ctx, A))) return e;
-		// every download behind the last kernel
-		n_w = hs[1].n_w, n_rec1 = hs[1].n_rec, n_fix = hs[0].n_rec;
-		R.wr.resize((size_t)n_w), cigdown.resize((size_t)n_rec1 * BMH_RP_SMALL_CAP * 4), mddown.resize((size_t)n_rec1 * kWantMdSlot);
-		if ((e = st.d2h(R.down.data(), d + o_reg, b_down))) return e;
-		if (n_w && (e = st.d2h(R.wr.data(), dw + o_wres, (size_t)n_w * sizeof(bmh_wanted_res_t)))) return e;
-		if (n_rec1 && ((e = st.d2h(cigdown.data(), dw + o_cig1, cigdown.size())) || (e = st.d2h(mddown.data(), dw + o_md1, mddown.size())))) return e;
-		return BMH_OK;
+		return st.d2h(R.down.data(), d + LA.reg, LA.down());
 	}();
 	rc = st.end(rc);
 	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
 	if (rc) return rc;
-	ctx->logk_n = want_log;
+	ctx->logk_n = T.want_log;
 	if (ctx->timing) {
 		BMH_HIP(ctx, hipEventElapsedTime(&ctx->decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
-		if (wc && ctx->ev_wanted[3]) {
-			float a = 0.f, b = 0.f;
-			BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
-			BMH_HIP(ctx, hipEventElapsedTime(&b, ctx->ev_wanted[2], ctx->ev_wanted[3]));
-			ctx->wanted_ms = a + b;
-		}
+		if (wc && (rc = wanted_kernel_ms(ctx))) return rc;
 	}
 	}
-	// ---- the want list as pass A left it, checked against the vectors and the session's count
+	// the want list as pass A left it, checked against the vectors and the session's count; then pass B's tail over the downloaded,
+	// sorted block (the caller's vectors are still unsorted)
 	const uint8_t *down = R.down.data();
-	const bmh_alnreg_t *sreg = (const bmh_alnreg_t *)down;
-	const int32_t *nw = (const int32_t *)(down + R.o_nw), *wk = (const int32_t *)(down + R.o_wk);
-	int64_t sum = 0;
-	bool fits = true;
-	for (int i = 0; i < n; ++i) fits = fits && nw[i] >= 0 && (size_t)nw[i] <= regs[i].n, sum += nw[i];
-	if (!fits || sum != n_w) { // cannot happen
+	const int64_t n_w = D.n_w;
+	if (decide_want_count(down, LA, n, regs) != n_w) { // cannot happen
 		ctx->last_error = "bmh_phase2_device: the device's counts are inconsistent";
 		return BMH_E_ARG;
 	}
-	// ---- the records: the device's, and the few regions whose alignments outgrew their slots again through the host form, their region
-	// records from the downloaded, sorted block with the coordinates as cut (the caller's vectors are still unsorted)
-	struct Redo {
-		int64_t j;
-		int read, k;
-	};
-	std::vector<Redo> redo;
-	{
-		int64_t j = 0;
-		for (int i = 0; i < n; ++i)
-			for (int q = 0; q < nw[i]; ++q, ++j) {
-				const bmh_wanted_res_t &x = R.wr[(size_t)j];
-				if (x.flags & BMH_WANTED_HOST) {
-					const int k = wk[roff[i] + q];
-					if (k < 0 || (size_t)k >= regs[i].n) return BMH_E_ARG; // cannot happen
-					redo.push_back(Redo{j, i, k});
-				} else if ((int64_t)x.cigar_off >= n_rec1 || x.n_cigar < 0 || x.n_cigar > BMH_RP_SMALL_CAP || x.md_len > (uint32_t)kWantMdSlot) {
-					ctx->last_error = "bmh_phase2_device: the device's records are inconsistent";
-					return BMH_E_ARG;
-				}
-			}
-	}
-	std::vector<bmh_wanted_res_t> hw(redo.size());
-	uint32_t *hcig = nullptr;
-	char *hmd = nullptr;
-	struct Free2 {
-		uint32_t *&a;
-		char *&b;
-		~Free2() { free(a), free(b); }
-	} guard2{hcig, hmd};
-	if (!redo.empty()) { // one region per read of a small slice of its own: the fix again for a region whose fix outgrew its slot
-		const size_t m = redo.size();
-		std::vector<bmh_alnreg_t> ra(m);
-		std::vector<bmh_alnreg_v> rv(m);
-		std::vector<bmh_read_t> rd(m);
-		std::vector<int64_t> ro(m + 1);
-		std::vector<int32_t> one(m, 1), zero(m, 0);
-		for (size_t t = 0; t < m; ++t) {
-			const bmh_wanted_res_t &x = R.wr[(size_t)redo[t].j];
-			ra[t] = sreg[roff[redo[t].read] + redo[t].k];
-			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe;
-			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[redo[t].read], ro[t] = (int64_t)t;
-		}
-		ro[m] = (int64_t)m;
-		if ((rc = bmh_wanted_host_(ctx, bns, pac, o->w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr)))
-			return rc;
-	}
-	size_t cu = 0, mu = 0, t = 0;
-	for (int64_t j = 0; j < n_w; ++j) {
-		const bmh_wanted_res_t &x = t < redo.size() && redo[t].j == j ? hw[t++] : R.wr[(size_t)j];
-		cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
-	}
-	R.cig = (uint32_t *)malloc(4 * (cu + 4)), R.md = (char *)malloc(mu + 4);
-	if (!R.cig || !R.md) {
-		ctx->last_error = "bmh_phase2_device: out of host memory";
-		return BMH_E_NOMEM;
-	}
-	cu = mu = 0, t = 0;
-	for (int64_t j = 0; j < n_w; ++j) { // packed in want order
-		bmh_wanted_res_t x = R.wr[(size_t)j];
-		const uint32_t *sc;
-		const char *sm;
-		if (t < redo.size() && redo[t].j == j) {
-			const uint32_t fl = x.flags;
-			x = hw[t], sc = hcig + x.cigar_off, sm = hmd + x.md_off;
-			x.flags |= fl | BMH_WANTED_HOST;
-			++t;
-		} else sc = (const uint32_t *)cigdown.data() + (size_t)x.cigar_off * BMH_RP_SMALL_CAP, sm = (const char *)mddown.data() + (size_t)x.md_off * kWantMdSlot;
-		memcpy(R.cig + cu, sc, 4 * (size_t)x.n_cigar), memcpy(R.md + mu, sm, x.md_len), R.md[mu + x.md_len] = 0;
-		x.cigar_off = (uint32_t)cu, x.md_off = (uint32_t)mu;
-		cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
-		R.wr[(size_t)j] = x;
-	}
-	R.n_w = n_w;
+	int64_t redone = 0;
+	rc = wanted_tail(ctx, "bmh_phase2_device", bns, pac, o->w, n, reads, roff, (const int32_t *)(down + (LA.nw - LA.reg)), (const int32_t *)(down + (LA.wk - LA.reg)),
+	                 (const bmh_alnreg_t *)down, D, D.wres, &R.cig, &R.md, &redone);
+	if (rc) return rc;
+	// the records were packed where they lay, at the start of the session's block: the slots behind them are given back, the rest handed on
+	if (void *p = realloc(D.wres, (size_t)n_w * sizeof(bmh_wanted_res_t) + 4)) D.wres = (bmh_wanted_res_t *)p;
+	R.wr = D.wres, D.wres = nullptr, R.n_w = n_w;
 	ctx->decide_units = pe ? n >> 1 : n;
-	ctx->wanted_n = n_w, ctx->wanted_fixed = n_fix, ctx->wanted_redone = (long long)redo.size();
-	ctx->p2.units = ctx->decide_units, ctx->p2.wanted = n_w, ctx->p2.fixed = n_fix, ctx->p2.redone = (int64_t)redo.size();
+	ctx->wanted_n = n_w, ctx->wanted_fixed = D.n_fix, ctx->wanted_redone = redone;
+	ctx->p2.units = ctx->decide_units, ctx->p2.wanted = n_w, ctx->p2.fixed = D.n_fix, ctx->p2.redone = redone;
 	ctx->p2.sessions = 1, ctx->p2.decide_ms = ctx->decide_ms, ctx->p2.wanted_ms = ctx->wanted_ms;
 	return BMH_OK;
 }
@@ -2159,7 +2127,7 @@ int bmh_phase2_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t
 	int rc = bmh_pp_check_args(o, pes, n, regs, roff, pd, reg_mapq, n_want, want_k);
 	if (rc || (rc = phase2_check_reads(bns, pac, n, reads))) return rc;
 	if (n == 0) {
-		ctx->p2 = bmh_phase2_stats_t{0, 0, 0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+		reset_phase2_stats(ctx);
 		*n_wanted = 0;
 		return BMH_OK;
 	}
@@ -2168,8 +2136,8 @@ int bmh_phase2_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t
 	bool tables;
 	if ((rc = phase2_device_run(ctx, o, bns, pac, pes, id0, n, reads, regs, roff, R, &tables))) return rc;
 	if (R.n_w > results_cap) return BMH_E_CIGAR_CAP;
-	if (R.n_w && (rc = bmh_wanted_deliver_(R.n_w, R.wr.data(), R.cig, R.md, results, cigar_pool, cigar_words, md_pool, md_bytes))) return rc;
-	phase2_commit(R, (o->flag & BMH_MEM_F_PE) != 0, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	if (R.n_w && (rc = bmh_wanted_deliver_(R.n_w, R.wr, R.cig, R.md, results, cigar_pool, cigar_words, md_pool, md_bytes))) return rc;
+	decide_commit(R.down.data(), R.L, (o->flag & BMH_MEM_F_PE) != 0, n, regs, roff, pd, reg_mapq, n_want, want_k);
 	*n_wanted = R.n_w;
 	return BMH_OK;
 }
@@ -2208,12 +2176,8 @@ __attribute__((visibility("hidden"))) int bmh_phase2_routed_(bmh_ctx_t *ctx, con
 		return BMH_OK;
 	}
 	if (rc) return rc;
-	if (R.n_w) {
-		if (!(*wr = (bmh_wanted_res_t *)malloc(sizeof(bmh_wanted_res_t) * (size_t)R.n_w))) return BMH_E_NOMEM;
-		memcpy(*wr, R.wr.data(), sizeof(bmh_wanted_res_t) * (size_t)R.n_w);
-	}
-	phase2_commit(R, (o->flag & BMH_MEM_F_PE) != 0, n, regs, roff, pd, reg_mapq, n_want, want_k);
-	*cig = R.cig, *md = R.md, R.cig = nullptr, R.md = nullptr;
+	decide_commit(R.down.data(), R.L, (o->flag & BMH_MEM_F_PE) != 0, n, regs, roff, pd, reg_mapq, n_want, want_k);
+	*wr = R.wr, *cig = R.cig, *md = R.md, R.wr = nullptr, R.cig = nullptr, R.md = nullptr;
 	*n_w = R.n_w, *done = 1;
 	return BMH_OK;
 }
@@ -2273,17 +2237,13 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
                         char **text, int64_t *text_off)
 {
 	if (!ctx) return BMH_E_ARG;
-	ctx->stx = bmh_samtext_stats_t{0, 0, 0, 0, 0, 0, 0, -1.f, -1.f};
+	reset_samtext_stats(ctx);
 	std::vector<int64_t> first((size_t)(n > 0 ? n : 0) + 1);
 	int64_t lines = 0;
 	size_t cig_words = 0, md_bytes = 0;
 	int rc = bmh_samtext_check_(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, results, cigar_pool, md_pool, text, text_off, first.data(),
 	                            &lines, &cig_words, &md_bytes);
-	if (rc) return rc;
-	if (ctx->refidx_n == 0 || ctx->refidx_n != bns->n_seqs || ctx->refidx_l_pac != bns->l_pac) {
-		ctx->last_error = "bmh_sam_text_device needs the resident sequence table (bmh_ctx_set_refidx)";
-		return BMH_E_ARG;
-	}
+	if (rc || (rc = need_resident(ctx, "bmh_sam_text_device", bns, nullptr))) return rc;
 	if (ctx->refnames_n == 0 || ctx->refnames_n != bns->n_seqs || ctx->h_refnames != refnames_block(bns)) {
 		ctx->last_error = "bmh_sam_text_device needs the resident sequence names (bmh_ctx_set_refnames)";
 		return BMH_E_ARG;
@@ -2298,17 +2258,11 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
 	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = (size_t)first[n], l_rg = rg_id ? strlen(rg_id) : 0;
 	if (l_rg > 0x7fffffffu) return BMH_E_ARG;
 	// the device block: everything that goes up, in one piece; then what the kernels make
-	auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t o_ = at;
-		at += al(bytes);
-		return o_;
-	};
-	const size_t o_roff = take((nr + 1) * 8), o_first = take((nr + 1) * 8), o_poff = take((nr + 1) * 8), o_hdr = take(sizeof(SamtextHdr)), o_rg = take(l_rg);
-	const size_t o_nw = take(nr * 4), o_wk = take(total * 4), o_mq = take(total * 4), o_pd = take(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0);
-	const size_t o_reg = take(total * sizeof(bmh_alnreg_t)), o_wr = take(wc * sizeof(bmh_wanted_res_t)), o_cig = take(cig_words * 4), o_md = take(md_bytes);
-	const size_t o_pool = at;
+	Block blk;
+	const size_t o_roff = blk.take((nr + 1) * 8), o_first = blk.take((nr + 1) * 8), o_poff = blk.take((nr + 1) * 8), o_hdr = blk.take(sizeof(SamtextHdr)), o_rg = blk.take(l_rg);
+	const size_t o_nw = blk.take(nr * 4), o_wk = blk.take(total * 4), o_mq = blk.take(total * 4), o_pd = blk.take(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0);
+	const size_t o_reg = blk.take(total * sizeof(bmh_alnreg_t)), o_wr = blk.take(wc * sizeof(bmh_wanted_res_t)), o_cig = blk.take(cig_words * 4), o_md = blk.take(md_bytes);
+	const size_t o_pool = blk.at;
 	std::vector<uint64_t> poff(nr + 1);
 	std::vector<int32_t> l_name(nr), l_com(nr);
 	size_t pool_bytes = 0;
@@ -2320,10 +2274,10 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
 		pool_bytes += samtext_read_bytes(ln, (size_t)seqs[i].l_seq, seqs[i].qual != nullptr, l_com[(size_t)i]);
 	}
 	poff[nr] = pool_bytes;
-	at += al(pool_bytes);
-	const size_t b_up = at;
-	const size_t o_alns = take(wc * sizeof(bmh_st_aln_t)), o_plan = take(nr * sizeof(bmh_st_plan_t)), o_size = take(nr * 8), o_toff = take((nr + 1) * 8);
-	const size_t o_stat = take(sizeof(SamtextStatus)), o_end = at;
+	blk.take(pool_bytes);
+	const size_t b_up = blk.at;
+	const size_t o_alns = blk.take(wc * sizeof(bmh_st_aln_t)), o_plan = blk.take(nr * sizeof(bmh_st_plan_t)), o_size = blk.take(nr * 8), o_toff = blk.take((nr + 1) * 8);
+	const size_t o_stat = blk.take(sizeof(SamtextStatus)), o_end = blk.at;
 	uint8_t *up = (uint8_t *)calloc(b_up, 1);
 	int64_t *toff = (int64_t *)malloc((nr + 1) * 8);
 	char *out = nullptr;

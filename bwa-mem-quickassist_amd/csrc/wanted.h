@@ -10,7 +10,7 @@ struct WantedHdr { // the upload's parameter block
 	int32_t fix_w; // opt->w: the band of bwa_fix_xref2's single alignment (bwa.c:198)
 };
 
-// one wanted region, number j in want order, as the planning leaves it (downloaded as it is)
+// one wanted region, number j in want order, as the planning leaves it (it stays on the device: wanted_result_kernel reads it)
 enum { kWantOk = 0, kWantBad = 1, kWantHost = 2 }; // refused (the call ends in an error); its fix outgrew the slot: the host redoes it
 struct WantRec { // 80 bytes
 	int64_t rb, re; // after bwa_fix_xref2
@@ -51,7 +51,7 @@ struct WantedArgs {
 	bmh_glb_task_t *task[2];                  // w_cap; 3 * w_cap
 	const bmh_region_res_t *fix_res;          // round 0's results, w_cap ...
 	const uint32_t *fix_cig;                  // ... and CIGAR slots of BMH_RP_SMALL_CAP words
-	const bmh_region_res_t *main_res;         // the main round's results, w_cap (the fused session only) ...
+	const bmh_region_res_t *main_res;         // the main round's results, w_cap ...
 	bmh_wanted_res_t *wres;                   // ... and the records wanted_result_kernel makes of them, w_cap
 	WantedStatus *status;                     // 2
 	unsigned long long w_cap, opool_cap;
@@ -102,7 +102,8 @@ template <class T, int K> __device__ __forceinline__ void block_excl_scan(T *s, 
 int launch_wanted_begin(bmh_ctx *ctx, const WantedArgs &A);
 // the cut of the regions round 0 aligned, then every region's plan.  Behind it rec[] and status[1] are complete.
 int launch_wanted_main(bmh_ctx *ctx, const WantedArgs &A);
-// behind the main round's region kernels (bmh_phase2_device): wres[j] from rec[j] and its region result, so that rec[] stays on the device
+// behind the main round's region kernels, in both forms of the session: wres[j] from rec[j] and its region result, so that rec[] stays
+// on the device and the host downloads n_w records
 int launch_wanted_results(bmh_ctx *ctx, const WantedArgs &A);
 
 } // namespace bmh

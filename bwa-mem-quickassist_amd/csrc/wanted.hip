@@ -13,8 +13,8 @@
 //   wanted_emit_kernel   one lane per wanted region: its record and tasks at those sums; GlbShape of the tasks by atomicMax
 //   wanted_cut_kernel    one lane per wanted region: walks round 0's CIGAR to the cut points and rewrites the coordinates
 //                        (bwa.c:199-221), then plans the main round: bands and its keys
-//   wanted_result_kernel (bmh_phase2_device only) one lane per wanted region, behind the main round's region kernels: its
-//                        bmh_wanted_res_t from its WantRec and region result, cigar_off / md_off = its slot for the host's packing
+//   wanted_result_kernel one lane per wanted region, behind the main round's region kernels: its bmh_wanted_res_t from its WantRec
+//                        and region result, cigar_off / md_off = its slot for the host's packing
 // Offsets come from sums over the want order in one block each, never from atomicAdd: they do not depend on block scheduling.  Every
 // dependency between blocks is a kernel boundary.  Nothing on the host has seen these records, so the kernels check what
 // bmh_region_cigar_batch checks on the host; a refused region writes and addresses nothing, and the first error goes to the

@@ -230,6 +230,26 @@ def test_alignments_that_outgrow_the_slots_are_redone_from_the_sorted_block(pkg)
         c.close()
 
 
+@pytest.mark.parametrize("n_w", [2, 1])
+def test_no_record_in_the_main_round(pkg, n_w):
+    """wantgen.long_fixes' regions alone, each the one region of its read: every wanted region is the host's after round 0, so the main
+    round has no record, no slot comes down and every record is redone from the sorted block"""
+    whole, c = _long_reference(pkg, 70, 20000)
+    try:
+        b = 10000
+        reads, vectors = [], []
+        for rd, reg in wg.long_fixes(whole, b, score=300)[:n_w]:
+            reg["seedcov"] = 60
+            reads.append(rd), vectors.append(np.array([reg], dtype=kswlib.ALNREG))
+        (a, res, _, _), st = _both(pkg, c, pg.opt(), None, 50, reads, vectors, f"{n_w} long fixes alone")
+        assert [list(k) for k in a["want"]] == [[0]] * n_w
+        assert list(res["flags"]) == [MOVED | HOST] * n_w and int(res["re"][0]) == b
+        assert n_w < 2 or int(res["rb"][1]) == 40000 - b
+        assert (st["wanted"], st["fixed"], st["redone"]) == (n_w, n_w, n_w) and c.last_wanted_stats()[:3] == (n_w, n_w, n_w)
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------- refusals: all or nothing
 
 def _sentinels(pkg, o, vectors):

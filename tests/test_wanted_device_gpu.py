@@ -375,6 +375,55 @@ def test_a_fix_whose_alignment_outgrows_its_slot_is_redone_with_its_fix(pkg):
         c.close()
 
 
+@pytest.mark.parametrize("n_w", [2, 1])
+def test_no_record_in_the_main_round(pkg, n_w):
+    """the long fixes of the test above without the plain read: every wanted region is the host's after round 0, so the main round has
+    no record, no slot comes down and every record is redone"""
+    whole, c = _long_reference(pkg, 70, 20000)
+    try:
+        b = 10000
+        pairs = wg.long_fixes(whole, b)[:n_w]
+        reads, vectors = [rd for rd, _ in pairs], [np.array([reg], dtype=kswlib.ALNREG) for _, reg in pairs]
+        host = _both(c, 100, reads, vectors, [[0]] * n_w, f"{n_w} long fixes alone", idx=c.idx, pac=c.pac)
+        assert list(host[0]["flags"]) == [12] * n_w and int(host[0]["re"][0]) == b
+        assert n_w < 2 or int(host[0]["rb"][1]) == 40000 - b
+        assert c.last_wanted_stats()[:3] == (n_w, n_w, n_w)
+    finally:
+        c.close()
+
+
+def test_a_want_list_that_skips_regions_out_of_vector_order(pkg):
+    """want_k = [2, 0] of the second read's three regions, behind a read that wants none of its two; region 2 has an MD past its slot:
+    the redo takes (read, k) from the want list and the region from the flat arena at roff[read] + k"""
+    whole, c = _long_reference(pkg, 80, 20000)
+    try:
+        rng = np.random.default_rng(81)
+        segs, regs = [], []
+        for pos, ln in ((600, 150), (4100, 140), (7300, 150), (12500, 130), (15200, 250)):
+            sg = kswgen.mutate(rng, whole[pos:pos + ln], sub=0.02)
+            if ln == 250:  # a substitution every 3 bases: an MD past 128 bytes
+                sg = whole[pos:pos + ln].copy()
+                sg[::3] = (sg[::3] + 1) & 3
+            segs.append(sg), regs.append((pos, ln))
+
+        def vector(ks):
+            q, out = 0, []
+            for k in ks:
+                pos, ln = regs[k]
+                out.append(wg.region(q, q + len(segs[k]), pos, pos + ln, len(segs[k]) - 40, 100))
+                q += len(segs[k])
+            return np.concatenate([segs[k] for k in ks]), np.array(out, dtype=kswlib.ALNREG)
+
+        (r0, v0), (r1, v1) = vector([0, 1]), vector([2, 3, 4])
+        host = _both(c, 100, [r0, r1], [v0, v1], [[], [2, 0]], "want_k = [2, 0]", idx=c.idx, pac=c.pac)
+        res = host[0]
+        assert list(res["flags"]) == [8, 0] and int(res["md_len"][0]) > 128
+        assert (int(res["qb"][0]), int(res["rb"][0])) == (int(v1[2]["qb"]), 15200) and (int(res["qb"][1]), int(res["rb"][1])) == (0, 7300)
+        assert c.last_wanted_stats()[:3] == (2, 0, 1)
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------- the switch behind bmh_sam_batch
 
 class _Seq(C.Structure):  # bmh_seq_t

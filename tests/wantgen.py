@@ -34,6 +34,24 @@ def region(qb, qe, rb, re, truesc, w, score=0):
     return a
 
 
+def long_fixes(whole, b, score=0):
+    """Two regions over the boundary b between two sequences of `whole` whose one-try alignment outgrows its 24-word slot, so that the
+    host redoes them, fix included: 14 separated indels on the way to b, then 60 bases past it, forwards and reverse-complemented
+    -> [(read, region)]"""
+    parts, at = [], b - 300
+    for j in range(14):
+        parts.append(whole[at:at + 20])
+        at += 20
+        if j % 2:
+            parts.append(np.array([(int(whole[at]) + 2) & 3, (int(whole[at]) + 1) & 3], dtype=np.uint8))
+        else:
+            at += 2
+    parts.append(whole[at:b + 60])
+    rd, l2 = np.concatenate(parts), 2 * len(whole)
+    return [(rd, region(0, len(rd), b - 300, b + 60, len(rd) - 50, 100, score)),
+            (revcomp(rd), region(0, len(rd), l2 - b - 60, l2 - b + 300, len(rd) - 50, 100, score))]
+
+
 def on_strand(rb, re, rev):
     return (2 * L_PAC - re, 2 * L_PAC - rb) if rev else (rb, re)
 
