@@ -79,6 +79,10 @@ PHASE2_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i8"), 
                          ("d2h_bytes", "<i8"), ("waits", "<i4"), ("sessions", "<i4"), ("decide_ms", "<f4"), ("wanted_ms", "<f4")])  # bmh_phase2_stats_t, 72 bytes
 SAMTEXT_STATS = np.dtype([("reads", "<i8"), ("lines", "<i8"), ("text_bytes", "<i8"), ("h2d_bytes", "<i8"), ("d2h_bytes", "<i8"), ("waits", "<i4"),
                           ("rsv", "<i4"), ("size_ms", "<f4"), ("emit_ms", "<f4")])  # bmh_samtext_stats_t, 56 bytes
+PHASE2_TEXT_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i8"), ("redone", "<i8"), ("reads", "<i8"), ("lines", "<i8"),
+                              ("text_bytes", "<i8"), ("h2d_bytes", "<i8"), ("d2h_bytes", "<i8"), ("fallbacks", "<i8"), ("waits", "<i4"),
+                              ("sessions", "<i4"), ("decide_ms", "<f4"), ("wanted_ms", "<f4"), ("gather_ms", "<f4"), ("size_ms", "<f4"),
+                              ("emit_ms", "<f4"), ("rsv", "<i4")])  # bmh_phase2_text_stats_t, 112 bytes
 WANTED_MOVED, WANTED_HOST = 4, 8
 MEM_F_NO_MULTI = 0x10
 ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
@@ -253,6 +257,9 @@ def lib():
         L.bmh_ctx_set_refnames.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_ctx_set_samtext_device.argtypes = [C.c_void_p, C.c_int]
         L.bmh_last_samtext_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_phase2_text_device.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.bmh_ctx_set_phase2_text_device.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_last_phase2_text_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -995,6 +1002,45 @@ class Context:
         st = np.zeros(1, dtype=SAMTEXT_STATS)
         self._check(lib().bmh_last_samtext_stats(self._h, _ptr(st)))
         return {k: st[0][k].item() for k in SAMTEXT_STATS.names if k != "rsv"}
+
+    def phase2_text_device(self, opt, refidx, pac, pes, id0, seqs, vectors, rg_id=b"", out=None):
+        """bmh_phase2_text_device: passes A, B and C of phase 2 as one device session, only the text comes down.  opt: SAM_OPT; seqs: per
+        read (name, comment or None, uint8 base codes, qualities or None); vectors: per read an ALNREG array, read where it lies and
+        left as it is (an array of another dtype or layout is copied first).  Returns (text, text_off): the pool's bytes and n + 1
+        offsets.  out: {"text": a C.c_void_p, "text_off": an int64 array} to write into (a test's sentinels)."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8) if pac is not None else None
+        n = len(seqs)
+        o = np.array(opt, dtype=SAM_OPT).reshape(1)
+        keep = []
+        c_seqs = (_Seq * max(n, 1))()
+        c_regs = (_AlnregV * max(n, 1))()
+        for r, ((name, comment, seq, qual), v) in enumerate(zip(seqs, vectors)):
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            v = np.ascontiguousarray(v, dtype=ALNREG).reshape(-1)
+            keep += [seq, v]
+            c_seqs[r] = _Seq(len(seq), name, comment, seq.ctypes.data if len(seq) else None, qual, None)
+            c_regs[r].n = c_regs[r].m = len(v)
+            c_regs[r].a = v.ctypes.data if len(v) else None
+        out = out or {}
+        text = out.get("text", C.c_void_p(None))
+        text_off = out.get("text_off", np.zeros(n + 1, dtype=np.int64))
+        pes_p = _ptr(np.ascontiguousarray(pes, dtype=PESTAT)) if pes is not None else None
+        self._check(lib().bmh_phase2_text_device(self._h, _ptr(o), C.byref(refidx) if refidx is not None else None, _ptr(pac), pes_p, C.c_int64(int(id0)), n,
+                                                 C.cast(c_seqs, C.c_void_p), C.cast(c_regs, C.c_void_p), rg_id, C.cast(C.byref(text), C.c_void_p),
+                                                 _ptr(text_off)))
+        data = C.string_at(text.value, int(text_off[n]))
+        _libc.free(text)
+        return data, text_off
+
+    def set_phase2_text_device(self, on=True):
+        """bmh_ctx_set_phase2_text_device: while on, bmh_sam_batch takes all three passes from bmh_phase2_text_device."""
+        self._check(lib().bmh_ctx_set_phase2_text_device(self._h, 1 if on else 0))
+
+    def last_phase2_text_stats(self):
+        """bmh_last_phase2_text_stats as a dict of PHASE2_TEXT_STATS' fields: the last such call on this context."""
+        st = np.zeros(1, dtype=PHASE2_TEXT_STATS)
+        self._check(lib().bmh_last_phase2_text_stats(self._h, _ptr(st)))
+        return {k: st[0][k].item() for k in PHASE2_TEXT_STATS.names if k != "rsv"}
 
     def sam_text_batch(self, *args, device=True, **kw):
         """sam_text_batch() on this context: bmh_sam_text_device (device=False: the host call, which needs no context)."""

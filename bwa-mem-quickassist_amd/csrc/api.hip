@@ -8,6 +8,7 @@
 #include <mutex>
 #include <new>
 #include <numeric>
+#include <optional>
 #include <vector>
 
 #include "bmh_ctx.h"
@@ -94,6 +95,7 @@ struct Stager {
 	bool up = false, down = false;
 	bool p2 = false; // the fused phase 2 session: bytes and waits go to ctx->p2 (bmh_last_phase2_stats)
 	bool sx = false; // bmh_sam_text_device's session: they go to ctx->stx (bmh_last_samtext_stats)
+	bool pt = false; // bmh_phase2_text_device's session: they go to ctx->pt (bmh_last_phase2_text_stats)
 	size_t up_used = 0, down_used = 0;
 	struct Pending {
 		void *dst;
@@ -118,6 +120,7 @@ struct Stager {
 		}
 		if (p2) ctx->p2.h2d_bytes += (int64_t)bytes;
 		if (sx) ctx->stx.h2d_bytes += (int64_t)bytes;
+		if (pt) ctx->pt.h2d_bytes += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
 		return BMH_OK;
 	}
@@ -131,6 +134,7 @@ struct Stager {
 		}
 		if (p2) ctx->p2.d2h_bytes += (int64_t)bytes;
 		if (sx) ctx->stx.d2h_bytes += (int64_t)bytes;
+		if (pt) ctx->pt.d2h_bytes += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(to, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
 		return BMH_OK;
 	}
@@ -141,6 +145,7 @@ struct Stager {
 	{
 		if (p2) ++ctx->p2.waits;
 		if (sx) ++ctx->stx.waits;
+		if (pt) ++ctx->pt.waits;
 		if (rc) { // (the flag's text must not replace why the call failed)
 			std::string why = std::move(ctx->last_error);
 			(void)fetch_err(ctx);
@@ -320,6 +325,9 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	if (ctx->h_wstat) (void)hipHostFree(ctx->h_wstat);
 	free_buf(ctx->d_refnames), free_buf(ctx->d_samtext), free_buf(ctx->d_sam_out);
 	if (ctx->h_ststat) (void)hipHostFree(ctx->h_ststat);
+	if (ctx->h_ptstat) (void)hipHostFree(ctx->h_ptstat);
+	for (auto &e : ctx->ev_gather)
+		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_samtext)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_wanted)
@@ -1410,6 +1418,11 @@ static void reset_phase2_stats(bmh_ctx *ctx)
 	ctx->p2 = bmh_phase2_stats_t{};
 	ctx->p2.decide_ms = ctx->p2.wanted_ms = -1.f;
 }
+static void reset_phase2_text_stats(bmh_ctx *ctx)
+{
+	ctx->pt = bmh_phase2_text_stats_t{};
+	ctx->pt.decide_ms = ctx->pt.wanted_ms = ctx->pt.gather_ms = ctx->pt.size_ms = ctx->pt.emit_ms = -1.f;
+}
 static void reset_samtext_stats(bmh_ctx *ctx)
 {
 	ctx->stx = bmh_samtext_stats_t{};
@@ -1598,6 +1611,7 @@ __attribute__((visibility("hidden"))) void bmh_decide_stats_reset_(bmh_ctx_t *ct
 	if (ctx && ctx->wanted_device) reset_wanted_stats(ctx);
 	if (ctx && ctx->phase2_device) reset_phase2_stats(ctx);
 	if (ctx && ctx->samtext_device) reset_samtext_stats(ctx);
+	if (ctx && ctx->phase2_text_device) reset_phase2_text_stats(ctx);
 }
 
 // bmh_sam_batch's pass A (host/sam_post.c; not part of the interface)
@@ -1669,18 +1683,23 @@ static int wanted_run_round(bmh_ctx *ctx, const WantedArgs &A, const WantedStatu
 }
 
 // the status records: the only thing the host reads between launches.  The wanted regions are n_lo..n_hi: the count where the host
-// knows it, 0..the capacity where pass A left the want list on the device.  The fused session's Stager counts the read.
-static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, const Stager &st)
+// knows it, 0..the capacity where pass A left the want list on the device.  The fused sessions' Stager counts the read.  The session
+// through to the text (st.pt) reads the record of the round just planned alone -- a refused region raises both records' error words,
+// both carry n_w, and record 0 is still the host's from the first look -- so that its downloads stay the text's and three small records.
+static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, const Stager &st, int round)
 {
 	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
-	BMH_HIP(ctx, hipMemcpyAsync(ctx->h_wstat, d_stat, 2 * sizeof(WantedStatus), hipMemcpyDeviceToHost, ctx->stream));
+	const size_t at = st.pt ? (size_t)round * sizeof(WantedStatus) : 0, bytes = (st.pt ? 1 : 2) * sizeof(WantedStatus);
+	BMH_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->h_wstat + at, d_stat + at, bytes, hipMemcpyDeviceToHost, ctx->stream));
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-	if (st.p2) ++ctx->p2.waits, ctx->p2.d2h_bytes += (int64_t)(2 * sizeof(WantedStatus));
-	if (hs[0].err || hs[1].err) {
+	if (st.p2) ++ctx->p2.waits, ctx->p2.d2h_bytes += (int64_t)bytes;
+	if (st.pt) ++ctx->pt.waits, ctx->pt.d2h_bytes += (int64_t)bytes;
+	const bool both = !st.pt || round == 1; // record 1 has been read
+	if (hs[0].err || (both && hs[1].err)) {
 		ctx->last_error = "bmh_wanted_cigar_device: a wanted region is outside its read, its vector or the reference, or nothing is left of it";
 		return hs[0].err ? hs[0].err : hs[1].err;
 	}
-	if (hs[0].n_w < n_lo || hs[0].n_w > n_hi || hs[1].n_rec > hs[0].n_w || hs[0].n_rec > hs[0].n_w) { // cannot happen
+	if (hs[0].n_w < n_lo || hs[0].n_w > n_hi || hs[0].n_rec > hs[0].n_w || (both && hs[1].n_rec > hs[0].n_w)) { // cannot happen
 		ctx->last_error = "bmh_wanted_cigar_device: the device's counts are inconsistent";
 		return BMH_E_ARG;
 	}
@@ -1698,17 +1717,17 @@ static size_t oriented_cap(const bmh_alnreg_t *a)
 }
 
 // the sections of an upload that are pass B's in both forms: the reads as one pool with 16 zero bytes behind it, so[] = its n + 1 offsets
-// (q_src = seq_off[read] + qb), and the parameters
+// (q_src = seq_off[read] + qb), and the parameters.  rpool NULL: the offsets and the parameters alone (the pool is made on the device)
 static void wanted_fill(const bmh_ctx *ctx, int w, int n, const bmh_read_t *reads, uint64_t *so, WantedHdr *hdr, uint8_t *rpool)
 {
 	size_t b = 0;
 	for (int i = 0; i < n; ++i) {
 		so[i] = b;
-		if (reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
+		if (rpool && reads[i].l_seq) memcpy(rpool + b, reads[i].seq, (size_t)reads[i].l_seq);
 		b += (size_t)reads[i].l_seq;
 	}
 	so[n] = b;
-	memset(rpool + b, 0, 16);
+	if (rpool) memset(rpool + b, 0, 16);
 	const bmh_params_t &p = ctx->params;
 	memset(hdr, 0, sizeof(*hdr));
 	hdr->opt = bmh_rp_opt_t{p.a, p.mat[0], p.o_del, p.e_del, p.o_ins, p.e_ins, p.w};
@@ -1752,6 +1771,7 @@ struct WantedDown {
 	bmh_wanted_res_t *wres = nullptr;      // n_w; cigar_off = md_off = the record's slot; BMH_WANTED_HOST: no slot, the host redoes it
 	uint8_t *cig = nullptr, *md = nullptr; // n_rec slots each, behind the records in the same malloc'd block
 	int64_t n_w = 0, n_rec = 0, n_fix = 0; // wanted regions; records of the main round and of round 0
+	bool stay = false;                     // the session through to the text: the counts alone, nothing comes down
 	~WantedDown() { free(wres); }
 };
 
@@ -1773,16 +1793,17 @@ static int wanted_session(bmh_ctx *ctx, const char *who, Stager &st, WantedArgs 
 	A.fix_res = (const bmh_region_res_t *)(dw + L.res0), A.fix_cig = (const uint32_t *)(dw + L.cig0);
 	A.main_res = (const bmh_region_res_t *)(dw + L.res1), A.wres = (bmh_wanted_res_t *)(dw + L.wres);
 	A.status = (WantedStatus *)(dw + L.stat), A.err = ctx->d_err;
-	if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st))) return e;
+	if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st, 0))) return e;
 	if ((e = wanted_run_round(ctx, A, hs[0], 0, d_pool, rpool_off, (bmh_region_res_t *)(dw + L.res0), (uint32_t *)(dw + L.cig0), (char *)(dw + L.md0), kWantFixMdSlot)))
 		return e;
-	if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st))) return e;
+	if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st, 1))) return e;
 	if ((e = wanted_run_round(ctx, A, hs[1], 1, d_pool, rpool_off, (bmh_region_res_t *)(dw + L.res1), (uint32_t *)(dw + L.cig1), (char *)(dw + L.md1), kWantMdSlot)))
 		return e;
 	if ((e = launch_wanted_results(ctx, A))) return e;
 	// every download behind the last kernel: the slots of the records the status names, not of the capacity.  One block for the three:
 	// as allocations of their own glibc returned these few MB after every call, and each call paid the page faults again
 	D.n_w = hs[1].n_w, D.n_rec = hs[1].n_rec, D.n_fix = hs[0].n_rec;
+	if (D.stay) return BMH_OK;
 	const size_t bw = (size_t)D.n_w * sizeof(bmh_wanted_res_t), bc = (size_t)D.n_rec * BMH_RP_SMALL_CAP * 4, bm = (size_t)D.n_rec * kWantMdSlot;
 	if (!(D.wres = (bmh_wanted_res_t *)malloc(bw + bc + bm + 4))) {
 		ctx->last_error = std::string(who) + ": out of host memory";
@@ -2231,6 +2252,50 @@ int bmh_ctx_set_refnames(bmh_ctx_t *ctx, const bmh_refidx_t *bns)
 	return BMH_OK;
 }
 
+// the per-read pool of pass C's two device forms (SamtextRead, samtext.h): planned, then packed into zeroed memory
+struct SamtextPool {
+	std::vector<uint64_t> poff; // n + 1: read i's record; poff[n] = the pool's bytes
+	std::vector<int32_t> l_name, l_com;
+	int plan(int n, const bmh_seq_t *seqs)
+	{
+		const size_t nr = (size_t)n;
+		poff.resize(nr + 1), l_name.resize(nr), l_com.resize(nr);
+		size_t bytes = 0;
+		for (size_t i = 0; i < nr; ++i) {
+			const size_t ln = strlen(seqs[i].name), lc = seqs[i].comment ? strlen(seqs[i].comment) : 0;
+			if (ln > 0x7fffffffu || lc > 0x7fffffffu) return BMH_E_ARG;
+			l_name[i] = (int32_t)ln, l_com[i] = seqs[i].comment ? (int32_t)lc : -1;
+			poff[i] = bytes;
+			bytes += samtext_read_bytes(ln, (size_t)seqs[i].l_seq, seqs[i].qual != nullptr, l_com[i]);
+		}
+		poff[nr] = bytes;
+		return BMH_OK;
+	}
+	void fill(int n, const bmh_seq_t *seqs, uint8_t *pool) const
+	{
+		for (size_t i = 0; i < (size_t)n; ++i) {
+			const bmh_seq_t &s = seqs[i];
+			uint8_t *b = pool + poff[i];
+			const SamtextRead h{l_name[i], s.l_seq, s.qual != nullptr, l_com[i]};
+			memcpy(b, &h, sizeof(h)), b += sizeof(h);
+			memcpy(b, s.name, (size_t)h.l_name), b += h.l_name;
+			if (s.l_seq) memcpy(b, s.seq, (size_t)s.l_seq), b += s.l_seq;
+			if (s.qual && s.l_seq) memcpy(b, s.qual, (size_t)s.l_seq), b += s.l_seq;
+			if (h.l_comment > 0) memcpy(b, s.comment, (size_t)h.l_comment);
+		}
+	}
+};
+
+// the sequence names of bns as the context holds them
+static int need_refnames(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns)
+{
+	if (ctx->refnames_n == 0 || ctx->refnames_n != bns->n_seqs || ctx->h_refnames != refnames_block(bns)) {
+		ctx->last_error = std::string(who) + " needs the resident sequence names (bmh_ctx_set_refnames)";
+		return BMH_E_ARG;
+	}
+	return BMH_OK;
+}
+
 int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
                         const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq, const int32_t *n_want,
                         const int32_t *want_k, const bmh_wanted_res_t *results, const uint32_t *cigar_pool, const char *md_pool, const char *rg_id,
@@ -2243,11 +2308,7 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
 	size_t cig_words = 0, md_bytes = 0;
 	int rc = bmh_samtext_check_(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, results, cigar_pool, md_pool, text, text_off, first.data(),
 	                            &lines, &cig_words, &md_bytes);
-	if (rc || (rc = need_resident(ctx, "bmh_sam_text_device", bns, nullptr))) return rc;
-	if (ctx->refnames_n == 0 || ctx->refnames_n != bns->n_seqs || ctx->h_refnames != refnames_block(bns)) {
-		ctx->last_error = "bmh_sam_text_device needs the resident sequence names (bmh_ctx_set_refnames)";
-		return BMH_E_ARG;
-	}
+	if (rc || (rc = need_resident(ctx, "bmh_sam_text_device", bns, nullptr)) || (rc = need_refnames(ctx, "bmh_sam_text_device", bns))) return rc;
 	if (n == 0) {
 		char *p = (char *)malloc(1);
 		if (!p) return BMH_E_NOMEM;
@@ -2263,17 +2324,10 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
 	const size_t o_nw = blk.take(nr * 4), o_wk = blk.take(total * 4), o_mq = blk.take(total * 4), o_pd = blk.take(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0);
 	const size_t o_reg = blk.take(total * sizeof(bmh_alnreg_t)), o_wr = blk.take(wc * sizeof(bmh_wanted_res_t)), o_cig = blk.take(cig_words * 4), o_md = blk.take(md_bytes);
 	const size_t o_pool = blk.at;
-	std::vector<uint64_t> poff(nr + 1);
-	std::vector<int32_t> l_name(nr), l_com(nr);
-	size_t pool_bytes = 0;
-	for (int i = 0; i < n; ++i) {
-		const size_t ln = strlen(seqs[i].name), lc = seqs[i].comment ? strlen(seqs[i].comment) : 0;
-		if (ln > 0x7fffffffu || lc > 0x7fffffffu) return BMH_E_ARG;
-		l_name[(size_t)i] = (int32_t)ln, l_com[(size_t)i] = seqs[i].comment ? (int32_t)lc : -1;
-		poff[(size_t)i] = pool_bytes;
-		pool_bytes += samtext_read_bytes(ln, (size_t)seqs[i].l_seq, seqs[i].qual != nullptr, l_com[(size_t)i]);
-	}
-	poff[nr] = pool_bytes;
+	SamtextPool P;
+	if ((rc = P.plan(n, seqs))) return rc;
+	const std::vector<uint64_t> &poff = P.poff;
+	const size_t pool_bytes = (size_t)poff[nr];
 	blk.take(pool_bytes);
 	const size_t b_up = blk.at;
 	const size_t o_alns = blk.take(wc * sizeof(bmh_st_aln_t)), o_plan = blk.take(nr * sizeof(bmh_st_plan_t)), o_size = blk.take(nr * 8), o_toff = blk.take((nr + 1) * 8);
@@ -2301,17 +2355,10 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
 	if (cig_words) memcpy(up + o_cig, cigar_pool, cig_words * 4);
 	if (md_bytes) memcpy(up + o_md, md_pool, md_bytes);
 	for (int i = 0; i < n; ++i) {
-		const bmh_seq_t &s = seqs[i];
 		if (n_want[i]) memcpy(up + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
 		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
-		uint8_t *b = up + o_pool + poff[(size_t)i];
-		const SamtextRead h{l_name[(size_t)i], s.l_seq, s.qual != nullptr, l_com[(size_t)i]};
-		memcpy(b, &h, sizeof(h)), b += sizeof(h);
-		memcpy(b, s.name, (size_t)h.l_name), b += h.l_name;
-		if (s.l_seq) memcpy(b, s.seq, (size_t)s.l_seq), b += s.l_seq;
-		if (s.qual && s.l_seq) memcpy(b, s.qual, (size_t)s.l_seq), b += s.l_seq;
-		if (h.l_comment > 0) memcpy(b, s.comment, (size_t)h.l_comment);
 	}
+	P.fill(n, seqs, up + o_pool);
 	long long total_text = 0;
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
@@ -2398,6 +2445,371 @@ __attribute__((visibility("hidden"))) int bmh_samtext_routed_(bmh_ctx_t *ctx, co
 	if (ctx && ctx->samtext_device)
 		return bmh_sam_text_device(ctx, o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, text, text_off);
 	return bmh_sam_text_batch(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, text, text_off);
+}
+
+// ------------------------------------------------------------------ passes A, B and C of phase 2 as one device session
+
+// what bmh_samtext_check_ refuses of the arguments, the reads and the names (host/sam_post.c; not part of the interface)
+int bmh_samtext_check_seqs_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,
+                            char **text, int64_t *text_off);
+
+// ensure() for a block whose first `keep` bytes a session still needs: the new allocation has them before the old one goes.  Every
+// pointer into the block is the caller's to make again.
+static int ensure_keep(bmh_ctx *ctx, DevBuf &b, size_t bytes, size_t keep)
+{
+	if (bytes <= b.cap) return BMH_OK;
+	DevBuf nb;
+	int rc = ensure(ctx, nb, std::max(bytes, 2 * b.cap));
+	if (rc) return rc;
+	hipError_t e = keep ? hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+	if (e == hipSuccess) e = stream_wait(ctx, ctx->stream);
+	if (e != hipSuccess) {
+		(void)hipFree(nb.p);
+		return set_hip_error(ctx, e, "hipMemcpyAsync(workspace)");
+	}
+	free_buf(b);
+	b = nb;
+	return BMH_OK;
+}
+
+// The session.  The arguments are checked here; *early: the BMH_E_RANGE is a refusal before any upload (the decide tables, or slot
+// addresses past 32 bits), which bmh_sam_batch answers with its other routes.  Nothing of the caller's is written before the end.
+static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                           const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const char *rg_id, char **text, int64_t *text_off, bool *early)
+{
+	static const char *const who = "bmh_phase2_text_device";
+	*early = false;
+	reset_phase2_text_stats(ctx);
+	int rc = bmh_samtext_check_seqs_(o, bns, pes, n, seqs, regs, text, text_off);
+	if (rc) return rc;
+	const size_t nr = (size_t)n;
+	std::vector<int64_t> roff(nr + 1, 0);
+	std::vector<bmh_read_t> reads(nr);
+	for (size_t i = 0; i < nr; ++i) { // (what bmh_pp_check_args refuses of the vectors; the offsets are made here)
+		if ((regs[i].n && !regs[i].a) || regs[i].n > 0x7fffffffu) return BMH_E_ARG;
+		roff[i + 1] = roff[i] + (int64_t)regs[i].n;
+		reads[i].l_seq = seqs[i].l_seq, reads[i].seq = (const uint8_t *)seqs[i].seq;
+	}
+	if ((rc = phase2_check_reads(bns, pac, n, reads.data()))) return rc;
+	if (n == 0) {
+		char *p = (char *)malloc(1);
+		if (!p) return BMH_E_NOMEM;
+		*text = p, text_off[0] = 0;
+		return BMH_OK;
+	}
+	if (!ctx->have_params) return BMH_E_ARG;
+	if ((rc = need_resident(ctx, who, bns, pac)) || (rc = need_refnames(ctx, who, bns))) return rc;
+	const size_t l_rg = rg_id ? strlen(rg_id) : 0;
+	if (n > (1 << 28) || roff[nr] > (1 << 28) || l_rg > 0x7fffffffu) return BMH_E_ARG;
+	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
+	const size_t total = (size_t)roff[nr], wc = total; // wc: the capacity of everything per wanted region, which bounds their number
+	// before anything is uploaded: the slots' addresses as the records hold them, and the decide tables
+	if (wc * BMH_RP_SMALL_CAP > 0xffffffffull || wc * kWantMdSlot > 0xffffffffull) {
+		ctx->last_error = std::string(who) + ": the slice's CIGAR or MD slots do not fit 32-bit addresses";
+		ctx->pt.fallbacks = 1, *early = true;
+		return BMH_E_RANGE;
+	}
+	DecideTables T;
+	const char *why = nullptr;
+	if (decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why)) {
+		ctx->last_error = why;
+		ctx->pt.fallbacks = 1, *early = true;
+		return BMH_E_RANGE;
+	}
+	if ((rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
+	size_t reads_bytes = 0, opool_cap = 0;
+	for (size_t i = 0; i < nr; ++i) {
+		reads_bytes += (size_t)reads[i].l_seq;
+		for (size_t k = 0; k < regs[i].n; ++k) opool_cap += oriented_cap(&regs[i].a[k]);
+	}
+	SamtextPool P;
+	if ((rc = P.plan(n, seqs))) return rc;
+	const size_t pool_bytes = (size_t)P.poff[nr];
+	// Three blocks.  Pass A's, with pass B's inputs in it, as bmh_phase2_device uploads it; pass B's arrays, the overflow area of the
+	// redone regions behind them; pass C's: [SamtextHdr | rg_id | poff | the per-read pool] up, then the records, plans, sizes, offsets,
+	// the status with its SamtextFused, and the list of the host's regions
+	const DecideBlock LA = decide_block(nr, total, (size_t)T.n_term, pe, true);
+	Block b;
+	const WantedBlock LB = wanted_block(b, nr, wc);
+	Block tb;
+	const size_t o_hdr = tb.take(sizeof(SamtextHdr)), o_rg = tb.take(l_rg), o_poff = tb.take((nr + 1) * 8), o_pool = tb.take(pool_bytes), t_up = tb.at;
+	const size_t o_alns = tb.take(wc * sizeof(bmh_st_aln_t)), o_plan = tb.take(nr * sizeof(bmh_st_plan_t)), o_size = tb.take(nr * 8), o_toff = tb.take((nr + 1) * 8);
+	const size_t o_stat = tb.take(sizeof(SamtextStatus) + sizeof(SamtextFused)), o_list = tb.take(wc * sizeof(Phase2TextHost)), t_end = tb.at;
+	HostBuf up(LA.up());
+	uint8_t *tup = (uint8_t *)calloc(t_up, 1);
+	int64_t *toff = (int64_t *)malloc((nr + 1) * 8);
+	char *out = nullptr;
+	struct Free {
+		void *a, *b;
+		char **c;
+		~Free() { free(a), free(b), free(*c); }
+	} guard{tup, toff, &out};
+	if (!up.p || !tup || !toff) {
+		ctx->last_error = std::string(who) + ": out of host memory";
+		return BMH_E_NOMEM;
+	}
+	decide_fill(up.p, LA, o, pes, T, n, regs, roff.data());
+	wanted_fill(ctx, o->w, n, reads.data(), (uint64_t *)(up.p + LA.soff), (WantedHdr *)(up.p + LA.whdr), nullptr); // (the bases go up in the per-read pool)
+	SamtextHdr *hdr = (SamtextHdr *)(tup + o_hdr);
+	hdr->opt_flag = o->flag, hdr->pe = pe, hdr->l_rg = (int32_t)l_rg;
+	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
+	if (l_rg) memcpy(tup + o_rg, rg_id, l_rg);
+	memcpy(tup + o_poff, P.poff.data(), (nr + 1) * 8);
+	P.fill(n, seqs, tup + o_pool);
+
+	WantedDown D;
+	D.stay = true;
+	std::vector<Phase2TextHost> list; // the regions the host redoes, by j
+	size_t cig_words = wc * BMH_RP_SMALL_CAP, md_bytes = wc * kWantMdSlot; // how far the records reach from the main round's slots
+	long long total_text = 0, lines = 0;
+	uint8_t *d = nullptr, *dw = nullptr, *dt = nullptr;
+	std::optional<GateGuard> gate; // (left around the host's redo, which enters it again through the host form)
+	gate.emplace();
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	if (!ctx->h_ptstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_ptstat, sizeof(SamtextStatus) + sizeof(SamtextFused), hipHostMallocDefault));
+	const SamtextStatus *hs = (const SamtextStatus *)ctx->h_ptstat;
+	const SamtextFused *hf = (const SamtextFused *)(hs + 1);
+	Stager st(ctx);
+	st.pt = true;
+	// pass C's arguments over the three blocks: the want list, mapQ, verdicts and sorted regions where decide_kernel left them, first[]
+	// and the records where pass B's kernels left them, CIGAR and MD in the main round's slots (and the overflow area behind the block)
+	auto text_args = [&]() {
+		SamtextArgs A{};
+		A.roff = (const int64_t *)d, A.first = (const int64_t *)(dw + LB.first), A.poff = (const unsigned long long *)(dt + o_poff);
+		A.hdr = (const SamtextHdr *)(dt + o_hdr), A.rg = (const char *)(dt + o_rg);
+		A.n_want = (const int32_t *)(d + LA.nw), A.want_k = (const int32_t *)(d + LA.wk), A.reg_mapq = (const int32_t *)(d + LA.mq);
+		A.pd = (const bmh_pairdec_t *)(d + LA.pd), A.reg = (const bmh_alnreg_t *)(d + LA.reg), A.wr = (const bmh_wanted_res_t *)(dw + LB.wres);
+		A.cig = (const uint32_t *)(dw + LB.cig1), A.md = (const char *)(dw + LB.md1), A.rpool = dt + o_pool;
+		A.total = total, A.n_w = (unsigned long long)D.n_w, A.cig_words = cig_words, A.md_bytes = md_bytes, A.rpool_bytes = pool_bytes;
+		A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.name_off = (const uint64_t *)ctx->d_refnames.p;
+		A.names = (const char *)ctx->d_refnames.p + ((size_t)ctx->refnames_n + 1) * 8;
+		A.n_seqs = ctx->refidx_n, A.n = n, A.pe = pe, A.l_pac = bns->l_pac;
+		A.alns = (bmh_st_aln_t *)(dt + o_alns), A.plan = (bmh_st_plan_t *)(dt + o_plan), A.size = (unsigned long long *)(dt + o_size);
+		A.toff = (unsigned long long *)(dt + o_toff), A.status = (SamtextStatus *)(dt + o_stat), A.text = nullptr, A.text_cap = 0, A.err = ctx->d_err;
+		A.fused = (SamtextFused *)(dt + o_stat + sizeof(SamtextStatus));
+		return A;
+	};
+	// size and scan, then the one look behind them: text total, error word, host-region count, lines
+	auto size_and_look = [&]() -> int {
+		int e;
+		if ((e = launch_samtext_size(ctx, text_args()))) return e;
+		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_ptstat, dt + o_stat, sizeof(SamtextStatus) + sizeof(SamtextFused), hipMemcpyDeviceToHost, ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+		++ctx->pt.waits, ctx->pt.d2h_bytes += (int64_t)(sizeof(SamtextStatus) + sizeof(SamtextFused));
+		if (hs->err) {
+			ctx->last_error = std::string(who) + ": a record lies outside its read, its vector, the pools or the reference";
+			return hs->err;
+		}
+		return BMH_OK;
+	};
+
+	// ---- one upload, passes A and B, the bind kernel, size and scan: three waits
+	rc = [&]() -> int {
+		int e;
+		size_t rpool_off;
+		if ((e = ensure(ctx, ctx->d_decide, LA.end)) || (e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, LB.end, &rpool_off))) return e;
+		if ((e = ensure(ctx, ctx->d_wanted, LB.end)) || (e = ensure(ctx, ctx->d_samtext, t_end))) return e; // (d_wanted: first[] also where no read has a region)
+		if ((e = decide_stage_log(ctx, st, T.want_log, LA.up() + t_up + 512, 0))) return e;
+		d = (uint8_t *)ctx->d_decide.p, dw = (uint8_t *)ctx->d_wanted.p, dt = (uint8_t *)ctx->d_samtext.p;
+		BMH_HIP(ctx, hipMemsetAsync(dt + o_stat, 0, sizeof(SamtextStatus) + sizeof(SamtextFused), ctx->stream));
+		if ((e = st.h2d(d, up.p, LA.up())) || (e = st.h2d(dt, tup, t_up))) return e;
+		BMH_HIP(ctx, hipMemsetAsync(d + LA.nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
+		const DecideArgs DA = decide_args(ctx, d, LA, T, total, bns->l_pac, id0, n, pe);
+		if ((e = launch_decide(ctx, DA))) return e;
+		if (wc) {
+			// pass B's reads pool, made where it is read: the bases of the per-read pool at seq_off[], 16 zero bytes behind them
+			uint8_t *rpool = (uint8_t *)ctx->d_pool.p + rpool_off;
+			BMH_HIP(ctx, hipMemsetAsync(rpool + reads_bytes, 0, 16, ctx->stream));
+			if ((e = launch_reads_gather(ctx, text_args(), (const unsigned long long *)(d + LA.soff), rpool, reads_bytes))) return e;
+			WantedArgs A{};
+			A.roff = DA.roff, A.seq_off = (const unsigned long long *)(d + LA.soff), A.hdr = (const WantedHdr *)(d + LA.whdr);
+			A.n_want = DA.n_want, A.want_k = DA.want_k, A.reg = DA.reg;
+			A.total = total, A.reads_bytes = reads_bytes, A.n = n, A.l_pac = bns->l_pac, A.w_cap = wc, A.opool_cap = opool_cap;
+			if ((e = wanted_session(ctx, who, st, A, dw, LB, rpool_off, 0, (int64_t)wc, D))) return e;
+			Phase2TextBindArgs B{};
+			B.status = (const WantedStatus *)(dw + LB.stat), B.wres = (bmh_wanted_res_t *)(dw + LB.wres), B.rec = (const WantRec *)(dw + LB.rec);
+			B.roff = DA.roff, B.reg = DA.reg, B.total = total, B.n = n, B.cig_cap = BMH_RP_SMALL_CAP, B.md_cap = kWantMdSlot, B.w_cap = wc;
+			B.list = (Phase2TextHost *)(dt + o_list), B.fused = (SamtextFused *)(dt + o_stat + sizeof(SamtextStatus));
+			B.status_out = (SamtextStatus *)(dt + o_stat), B.err = ctx->d_err;
+			if ((e = launch_phase2_text_bind(ctx, B, D.n_w))) return e;
+		} else
+			BMH_HIP(ctx, hipMemsetAsync(dw + LB.first, 0, (nr + 1) * 8, ctx->stream));
+		if ((e = size_and_look())) return e;
+		if (hf->n_host == 0) return BMH_OK;
+		if (hf->n_host < 0 || (int64_t)hf->n_host > D.n_w) { // cannot happen
+			ctx->last_error = std::string(who) + ": the device's counts are inconsistent";
+			return BMH_E_ARG;
+		}
+		// only the list comes down
+		list.resize((size_t)hf->n_host);
+		BMH_HIP(ctx, hipMemcpyAsync(list.data(), dt + o_list, list.size() * sizeof(Phase2TextHost), hipMemcpyDeviceToHost, ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+		++ctx->pt.waits, ctx->pt.d2h_bytes += (int64_t)(list.size() * sizeof(Phase2TextHost));
+		return BMH_OK;
+	}();
+
+	// ---- the regions whose alignments outgrew their slots: redone as wanted_tail redoes them, one region per read of a small slice of
+	// its own, from the sorted region with the coordinates as cut; their records, CIGAR words and MD bytes go into the overflow area
+	// behind pass B's block, the records are patched where they lie, and size and scan run again: two more waits
+	const size_t m = list.size();
+	if (!rc && m) {
+		std::sort(list.begin(), list.end(), [](const Phase2TextHost &x, const Phase2TextHost &y) { return x.j < y.j; });
+		std::vector<bmh_wanted_res_t> hw(m);
+		uint32_t *hcig = nullptr;
+		char *hmd = nullptr;
+		struct Free2 {
+			uint32_t *&a;
+			char *&b;
+			~Free2() { free(a), free(b); }
+		} guard2{hcig, hmd};
+		std::vector<bmh_alnreg_t> ra(m);
+		std::vector<bmh_alnreg_v> rv(m);
+		std::vector<bmh_read_t> rd(m);
+		std::vector<int64_t> ro(m + 1);
+		std::vector<int32_t> one(m, 1), zero(m, 0);
+		for (size_t t = 0; t < m && !rc; ++t) {
+			const Phase2TextHost &x = list[t];
+			if (x.j < 0 || x.j >= D.n_w || x.read < 0 || x.read >= n || (t && x.j == list[t - 1].j)) { // cannot happen
+				ctx->last_error = std::string(who) + ": the device's list is inconsistent";
+				rc = BMH_E_ARG;
+				break;
+			}
+			ra[t] = x.reg;
+			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe; // (as cut; a region whose fix is redone still has its own)
+			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[(size_t)x.read], ro[t] = (int64_t)t;
+		}
+		ro[m] = (int64_t)m;
+		if (!rc) {
+			gate.reset();
+			rc = bmh_wanted_host_(ctx, bns, pac, o->w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr);
+			gate.emplace();
+		}
+		if (!rc) rc = [&]() -> int {
+			int e;
+			BMH_HIP(ctx, hipSetDevice(ctx->device));
+			size_t cw = 0, mb = 0;
+			for (const bmh_wanted_res_t &x : hw) cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
+			Block ob;
+			ob.at = LB.end;
+			const size_t o_rec = ob.take(m * sizeof(bmh_wanted_res_t)), o_at = ob.take(m * 8), o_cig = ob.take(cw * 4), o_md = ob.take(mb), o_end = ob.at;
+			const size_t cig0 = (o_cig - LB.cig1) / 4, md0 = o_md - LB.md1; // from the main round's slots, as every record's offsets
+			if (cig0 + cw > 0xffffffffull || md0 + mb > 0xffffffffull) {
+				ctx->last_error = std::string(who) + ": the redone regions' CIGAR or MD do not fit 32-bit addresses";
+				return BMH_E_RANGE;
+			}
+			std::vector<uint8_t> ov(o_end - LB.end, 0);
+			bmh_wanted_res_t *orec = (bmh_wanted_res_t *)(ov.data() + (o_rec - LB.end));
+			int64_t *oat = (int64_t *)(ov.data() + (o_at - LB.end));
+			uint32_t *ocig = (uint32_t *)(ov.data() + (o_cig - LB.end));
+			char *omd = (char *)(ov.data() + (o_md - LB.end));
+			cw = mb = 0;
+			for (size_t t = 0; t < m; ++t) {
+				bmh_wanted_res_t x = hw[t];
+				memcpy(ocig + cw, hcig + x.cigar_off, 4 * (size_t)x.n_cigar), memcpy(omd + mb, hmd + x.md_off, x.md_len);
+				x.cigar_off = (uint32_t)(cig0 + cw), x.md_off = (uint32_t)(md0 + mb), x.flags |= list[t].flags | BMH_WANTED_HOST;
+				cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
+				orec[t] = x, oat[t] = list[t].j;
+			}
+			if ((e = ensure_keep(ctx, ctx->d_wanted, o_end, LB.end))) return e;
+			dw = (uint8_t *)ctx->d_wanted.p;
+			cig_words = cig0 + cw, md_bytes = md0 + mb;
+			st.up_used = 0; // (everything staged so far has arrived; the redo had the staging buffers for itself)
+			if ((e = st.stage(ov.size() + 256, 0))) return e;
+			BMH_HIP(ctx, hipMemsetAsync(dt + o_stat, 0, sizeof(SamtextStatus) + sizeof(SamtextFused), ctx->stream));
+			if ((e = st.h2d(dw + LB.end, ov.data(), ov.size()))) return e;
+			if ((e = launch_phase2_text_patch(ctx, (bmh_wanted_res_t *)(dw + LB.wres), (const bmh_wanted_res_t *)(dw + o_rec), (const int64_t *)(dw + o_at),
+			                                  (int64_t)m, D.n_w, (SamtextStatus *)(dt + o_stat), ctx->d_err)))
+				return e;
+			if ((e = size_and_look())) return e;
+			if (hf->n_host != 0) { // cannot happen
+				ctx->last_error = std::string(who) + ": the device's counts are inconsistent";
+				return BMH_E_ARG;
+			}
+			return BMH_OK;
+		}();
+	}
+
+	// ---- the text: the buffer sized from the status, the emit kernel, text_off and the text down
+	if (!rc) rc = [&]() -> int {
+		int e;
+		total_text = hs->total, lines = hf->lines;
+		if (total_text < 0 || total_text > ((long long)1 << 40) || lines < 0) { // cannot happen
+			ctx->last_error = std::string(who) + ": the device's sizes are inconsistent";
+			return BMH_E_ARG;
+		}
+		if (!(out = (char *)malloc((size_t)total_text + 1))) return BMH_E_NOMEM;
+		if ((e = ensure(ctx, ctx->d_sam_out, (size_t)total_text + 64)) || (e = st.stage(0, (nr + 1) * 8 + (size_t)total_text + 256))) return e;
+		SamtextArgs A = text_args();
+		A.text = (char *)ctx->d_sam_out.p, A.text_cap = (unsigned long long)total_text;
+		if ((e = launch_samtext_emit(ctx, A))) return e;
+		if ((e = st.d2h(toff, dt + o_toff, (nr + 1) * 8))) return e;
+		return total_text ? st.d2h(out, ctx->d_sam_out.p, (size_t)total_text) : BMH_OK;
+	}();
+	rc = st.end(rc);
+	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region, and has been redone
+	if (rc) return rc;
+	ctx->logk_n = T.want_log;
+	if (toff[0] != 0 || toff[n] != total_text) { // cannot happen
+		ctx->last_error = std::string(who) + ": the device's offsets are inconsistent";
+		return BMH_E_ARG;
+	}
+	// all or nothing: the caller's outputs only now
+	memcpy(text_off, toff, (nr + 1) * 8);
+	*text = out, out = nullptr;
+	bmh_phase2_text_stats_t &s = ctx->pt;
+	s.units = pe ? n >> 1 : n, s.wanted = D.n_w, s.fixed = D.n_fix, s.redone = (int64_t)m;
+	s.reads = n, s.lines = lines, s.text_bytes = total_text, s.sessions = 1;
+	if (ctx->timing) {
+		float a = 0.f, c = 0.f;
+		BMH_HIP(ctx, hipEventElapsedTime(&s.decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
+		if (wc) {
+			BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
+			BMH_HIP(ctx, hipEventElapsedTime(&c, ctx->ev_wanted[2], ctx->ev_wanted[3]));
+			s.wanted_ms = a + c;
+			BMH_HIP(ctx, hipEventElapsedTime(&s.gather_ms, ctx->ev_gather[0], ctx->ev_gather[1]));
+		}
+		BMH_HIP(ctx, hipEventElapsedTime(&s.size_ms, ctx->ev_samtext[0], ctx->ev_samtext[1]));
+		BMH_HIP(ctx, hipEventElapsedTime(&s.emit_ms, ctx->ev_samtext[2], ctx->ev_samtext[3]));
+	}
+	return BMH_OK;
+}
+
+int bmh_phase2_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                           const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const char *rg_id, char **text, int64_t *text_off)
+{
+	bool early;
+	if (!ctx) return BMH_E_ARG;
+	return phase2_text_run(ctx, o, bns, pac, pes, id0, n, seqs, regs, rg_id, text, text_off, &early);
+}
+
+int bmh_ctx_set_phase2_text_device(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->phase2_text_device = on != 0;
+	return BMH_OK;
+}
+
+int bmh_last_phase2_text_stats(const bmh_ctx_t *ctx, bmh_phase2_text_stats_t *st)
+{
+	if (!ctx || !st) return BMH_E_ARG;
+	*st = ctx->pt;
+	return BMH_OK;
+}
+
+// bmh_sam_batch's three passes as one session (host/sam_post.c; not part of the interface).  *done = 1: *text (malloc'd) and text_off
+// are the fused call's.  *done = 0 with BMH_OK: the switch is off, or the call refused the slice before its upload (the statistics then
+// say one fall-back), and the caller goes through its other routes.
+__attribute__((visibility("hidden"))) int bmh_phase2_text_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac,
+                                                                  const bmh_pestat_t *pes, int64_t id0, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,
+                                                                  const char *rg_id, char **text, int64_t *text_off, int *done)
+{
+	*done = 0;
+	if (!ctx || !ctx->phase2_text_device) return BMH_OK;
+	bool early;
+	const int rc = phase2_text_run(ctx, o, bns, pac, pes, id0, n, seqs, regs, rg_id, text, text_off, &early);
+	if (rc == BMH_E_RANGE && early) return BMH_OK;
+	*done = rc == BMH_OK;
+	return rc;
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

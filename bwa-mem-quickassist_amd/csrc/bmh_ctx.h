@@ -166,6 +166,12 @@ struct bmh_ctx {
 	void *h_ststat = nullptr;                 // pinned: the status as the host reads it between scan and emit
 	hipEvent_t ev_samtext[4] = {};            // around the size kernel and the emit kernel (timing mode)
 	bmh_samtext_stats_t stx = {-1, -1, -1, -1, -1, -1, 0, -1.f, -1.f}; // of the last bmh_sam_text_device call (bmh_last_samtext_stats)
+	// passes A, B and C as one device session (api.hip): bmh_phase2_text_device, and bmh_sam_batch with the switch on.  Its blocks are
+	// d_decide (pass A's), d_wanted (pass B's, the overflow area behind it) and d_samtext (pass C's inputs and work arrays)
+	bool phase2_text_device = false;          // bmh_ctx_set_phase2_text_device
+	void *h_ptstat = nullptr;                 // pinned: SamtextStatus and SamtextFused as the host reads them behind the scan
+	hipEvent_t ev_gather[2] = {};             // around reads_gather_kernel (timing mode)
+	bmh_phase2_text_stats_t pt = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f, -1.f, -1.f, -1.f, -1}; // of the last such call (bmh_last_phase2_text_stats)
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 

@@ -7,12 +7,21 @@
 //                        per-unit rule (plan[] per read) and runs the composer over the counting sink: size[i] = bytes of read i's lines
 //   samtext_scan_kernel  one block: toff[] = exclusive 64-bit sums of size[], the total into the status word
 //   samtext_emit_kernel  one lane per read: the same composer over the same records, writing into text[toff[i] .. toff[i+1])
+// and, for the session that runs passes A, B and C without a host hop (bmh_phase2_text_device):
+//   reads_gather_kernel       one wave per read: pass B's contiguous reads pool from the per-read pool that went up for pass C
+//   phase2_text_bind_kernel   one lane per wanted region: the record's slot number becomes the slot's address in pass B's CIGAR and MD
+//                             slots, so that pass C reads them where the region kernels wrote them; the regions flagged
+//                             BMH_WANTED_HOST are listed for the host and counted.  While that count is not zero the size and scan
+//                             kernels leave at once: the host redoes the listed regions, phase2_text_patch_kernel puts their records
+//                             in place, and size and scan run again
 // The writing sink carries the size of the read's slice (samtext_core.h): a byte past it is not stored.  A slice that does not lie in
 // the text buffer is not written at all.  Either raises the error words, and the host delivers nothing.  The emitter's stores are a
 // byte stream per lane, 64 slices per wave: uncoalesced by nature.
 // Nothing on the device trusts an offset it was handed: a unit whose offsets, counts, indices or pool record lie outside the uploaded
 // arrays writes and addresses nothing, and the first error goes to the context's error word and the status by atomicCAS from 0 -- the
 // host launches nothing behind a status with an error.
+#include <algorithm>
+
 #include "samtext.h"
 #include "wanted.h"
 
@@ -71,6 +80,7 @@ __global__ __launch_bounds__(256) void samtext_size_kernel(SamtextArgs A)
 	const int pe = A.pe != 0, nr = pe ? 2 : 1;
 	const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (u * nr + nr > (long long)A.n) return;
+	if (A.fused && A.fused->n_host) return; // the fused session: records are still the host's to make, the launch is repeated behind them
 	const int i0 = (int)(u * nr);
 	bmh_rp_refv_t rv;
 	rv.off0 = &A.ref[0].offset, rv.len0 = &A.ref[0].len, rv.stride = sizeof(bmh_refspan_t), rv.n_seqs = A.n_seqs, rv.l_pac = A.l_pac;
@@ -89,16 +99,18 @@ __global__ __launch_bounds__(256) void samtext_size_kernel(SamtextArgs A)
 	bmh_st_unit(A.hdr->opt_flag, A.l_pac, A.hdr->pes, pe, pe ? &A.pd[u] : nullptr, A.first + i0, wk, ra, A.alns, A.plan + i0);
 	bmh_st_env_t E;
 	samtext_env(A, &E);
+	int lines = 0;
 	for (int r = 0; r < nr; ++r) {
 		const int i = i0 + r;
 		bmh_st_sink_t t = {nullptr, 0, 0, 0, 0};
-		bmh_st_read_text(&E, &t, &rd[r], &A.plan[i], (int)(A.first[i + 1] - A.first[i]), A.alns + A.first[i]);
+		lines += bmh_st_read_text(&E, &t, &rd[r], &A.plan[i], (int)(A.first[i + 1] - A.first[i]), A.alns + A.first[i]);
 		if (t.err || t.l < 0) {
 			samtext_fail(A, BMH_E_ARG);
 			return;
 		}
 		A.size[i] = (unsigned long long)t.l;
 	}
+	if (A.fused) atomicAdd((unsigned long long *)&A.fused->lines, (unsigned long long)lines);
 }
 
 __global__ __launch_bounds__(kScanThreads) void samtext_scan_kernel(SamtextArgs A)
@@ -106,6 +118,7 @@ __global__ __launch_bounds__(kScanThreads) void samtext_scan_kernel(SamtextArgs 
 	__shared__ unsigned long long s[2 * (kScanThreads / 64) + 1];
 	const int t = threadIdx.x;
 	unsigned long long carry = 0;
+	if (A.fused && A.fused->n_host) return; // (the whole block: see the size kernel)
 	for (int base = 0; base < A.n; base += kScanThreads) { // tiles of one read per lane: neighbouring lanes read neighbouring words
 		const int i = base + t;
 		unsigned long long v[1] = {i < A.n ? A.size[i] : 0}, total[1];
@@ -134,6 +147,110 @@ __global__ __launch_bounds__(256) void samtext_emit_kernel(SamtextArgs A)
 	bmh_st_sink_t t = {A.text + o0, 0, (int64_t)(o1 - o0), 0, 0};
 	bmh_st_read_text(&E, &t, &rd, &A.plan[i], (int)(A.first[i + 1] - A.first[i]), A.alns + A.first[i]);
 	if (t.err || t.l != t.cap) samtext_fail(A, BMH_E_ARG); // (cannot happen: the records and the composer the size came from)
+}
+
+// ---- the fused session's joints (bmh_phase2_text_device)
+
+// One wave per read, the lanes on neighbouring bytes: reads and writes coalesce whatever the read's alignment in either pool.
+__global__ __launch_bounds__(256) void reads_gather_kernel(SamtextArgs A, const unsigned long long *seq_off, uint8_t *dst, unsigned long long reads_bytes)
+{
+	const int lane = threadIdx.x & 63;
+	const long long waves = ((long long)gridDim.x * blockDim.x) >> 6;
+	for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < (long long)A.n; i += waves) {
+		const unsigned long long s0 = seq_off[i], s1 = seq_off[i + 1];
+		bmh_st_read_t rd;
+		if (!samtext_read_view(A, (int)i, &rd) || s0 > s1 || s1 > reads_bytes || s1 - s0 != (unsigned long long)rd.l_seq) { // nothing is copied
+			if (lane == 0) samtext_fail(A, BMH_E_ARG);
+			continue;
+		}
+		for (int b = lane; b < rd.l_seq; b += 64) dst[s0 + (unsigned long long)b] = rd.seq[b];
+	}
+}
+
+__device__ __forceinline__ void bind_fail(const Phase2TextBindArgs &A)
+{
+	atomicCAS(A.err, 0, BMH_E_ARG);
+	atomicCAS(&A.status_out->err, 0, BMH_E_ARG);
+}
+
+__global__ __launch_bounds__(256) void phase2_text_bind_kernel(Phase2TextBindArgs A)
+{
+	const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= (unsigned long long)A.status[1].n_w) return;
+	bmh_wanted_res_t x = A.wres[j];
+	if (!(x.flags & BMH_WANTED_HOST)) { // its slot's address: v * cap fits 32 bits for every v < w_cap (the host refuses the slice otherwise)
+		const unsigned long long v = x.cigar_off;
+		if (v >= A.w_cap) {
+			bind_fail(A); // (cannot happen: wanted_result_kernel took v from the main round's records)
+			return;
+		}
+		x.cigar_off = (uint32_t)(v * (unsigned long long)A.cig_cap), x.md_off = (uint32_t)(v * (unsigned long long)A.md_cap);
+		A.wres[j] = x;
+		return;
+	}
+	const WantRec r = A.rec[j];
+	if (r.read < 0 || r.read >= A.n || r.k < 0) {
+		bind_fail(A);
+		return;
+	}
+	const unsigned long long r0 = A.roff[r.read], r1 = A.roff[r.read + 1];
+	if (r0 > r1 || r1 > A.total || (unsigned long long)r.k >= r1 - r0) {
+		bind_fail(A);
+		return;
+	}
+	const unsigned long long at = (unsigned long long)atomicAdd(&A.fused->n_host, 1);
+	if (at >= A.w_cap) return; // (cannot happen: one entry per wanted region at most)
+	Phase2TextHost h;
+	h.j = (int64_t)j, h.read = r.read, h.k = r.k, h.reg = A.reg[r0 + (unsigned long long)r.k];
+	h.rb = x.rb, h.re = x.re, h.qb = x.qb, h.qe = x.qe, h.flags = x.flags, h.rsv = 0;
+	A.list[at] = h;
+}
+
+__global__ __launch_bounds__(256) void phase2_text_patch_kernel(bmh_wanted_res_t *wres, const bmh_wanted_res_t *recs, const int64_t *at, long long m,
+                                                                 long long n_w, SamtextStatus *status, int *err)
+{
+	const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= m) return;
+	const int64_t j = at[t];
+	if (j < 0 || j >= n_w) {
+		atomicCAS(err, 0, BMH_E_ARG);
+		atomicCAS(&status->err, 0, BMH_E_ARG);
+		return;
+	}
+	wres[j] = recs[t];
+}
+
+int launch_reads_gather(bmh_ctx *ctx, const SamtextArgs &A, const unsigned long long *seq_off, uint8_t *dst, unsigned long long reads_bytes)
+{
+	if (A.n <= 0) return BMH_OK;
+	if (ctx->timing) {
+		if (!ctx->ev_gather[0]) BMH_HIP(ctx, hipEventCreate(&ctx->ev_gather[0]));
+		if (!ctx->ev_gather[1]) BMH_HIP(ctx, hipEventCreate(&ctx->ev_gather[1]));
+		BMH_HIP(ctx, hipEventRecord(ctx->ev_gather[0], ctx->stream));
+	}
+	const long long blocks = std::min<long long>(((long long)A.n + 3) / 4, 8192); // four reads per block; past that the waves stride
+	hipLaunchKernelGGL(reads_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, A, seq_off, dst, reads_bytes);
+	BMH_HIP(ctx, hipGetLastError());
+	if (ctx->timing) BMH_HIP(ctx, hipEventRecord(ctx->ev_gather[1], ctx->stream));
+	return BMH_OK;
+}
+
+int launch_phase2_text_bind(bmh_ctx *ctx, const Phase2TextBindArgs &A, int64_t n_w)
+{
+	if (n_w <= 0) return BMH_OK;
+	hipLaunchKernelGGL(phase2_text_bind_kernel, dim3((unsigned)((n_w + 255) / 256)), dim3(256), 0, ctx->stream, A);
+	BMH_HIP(ctx, hipGetLastError());
+	return BMH_OK;
+}
+
+int launch_phase2_text_patch(bmh_ctx *ctx, bmh_wanted_res_t *wres, const bmh_wanted_res_t *recs, const int64_t *at, int64_t m, int64_t n_w,
+                             SamtextStatus *status, int *err)
+{
+	if (m <= 0) return BMH_OK;
+	hipLaunchKernelGGL(phase2_text_patch_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, wres, recs, at, (long long)m, (long long)n_w,
+	                   status, err);
+	BMH_HIP(ctx, hipGetLastError());
+	return BMH_OK;
 }
 
 static int samtext_events(bmh_ctx *ctx, int k)

@@ -34,6 +34,10 @@
  *   BMH_SAMTEXT_DEVICE=1 its pass C -- coordinates, clipping, flags and the SAM text -- as kernels (bmh_ctx_set_samtext_device), with the
  *                        sequence table and the sequence names resident.  Needs no resident reference (BMH_PAC_RESIDENT=0 is fine);
  *                        independent of the other switches.  The text is the same bytes either way.
+ *   BMH_PHASE2_TEXT_DEVICE=1  passes A, B and C as ONE device session (bmh_ctx_set_phase2_text_device): the regions and the reads go up
+ *                        once and only SAM text comes down; the few alignments that outgrow the device's slots are redone on the host
+ *                        and patched in.  Needs BMH_PAC_RESIDENT not 0; makes the sequence table and the names resident.  A slice the
+ *                        fused call refuses as out of range goes the way the switches above say.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -460,6 +464,28 @@ static int qa_phase2_device(void)
 }
 static long long g_phase2_cnt[5]; /* units, regions, fixed, redone on the host, slices that fell back to the two passes */
 
+/* BMH_PHASE2_TEXT_DEVICE=1: phase 2's three passes as one device session (bmh_ctx_set_phase2_text_device on every pooled context phase 2
+ * uses, with the sequence table and the names made resident where the reference is).  It needs the resident reference as
+ * BMH_PHASE2_DEVICE does: checked when the library is loaded. */
+__attribute__((constructor)) static void qa_check_phase2_text_device_env(void)
+{
+	const char *e = getenv("BMH_PHASE2_TEXT_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_PHASE2_TEXT_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+static int qa_phase2_text_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_PHASE2_TEXT_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_phase2_text_cnt[6]; /* units, regions, redone on the host, lines, bytes of text, slices that fell back to the other routes */
+
 /* BMH_SAMTEXT_DEVICE=1: phase 2's pass C on the device (bmh_ctx_set_samtext_device on every pooled context phase 2 uses, with the
  * sequence table and the names made resident).  It reads no base of the reference, so it does not need BMH_PAC_RESIDENT. */
 static int qa_samtext_device(void)
@@ -732,6 +758,12 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 	if (qa_samtext_device() && ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns)) || (rc = bmh_ctx_set_refnames(ctx, (const bmh_refidx_t *)J->bns))))
 		bmh_tls_die(bmh_last_error(ctx), rc);
 	if ((rc = bmh_ctx_set_samtext_device(ctx, qa_samtext_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
+	if (qa_phase2_text_device()) { /* the sequence table and the names where the reference is made resident */
+		if (!J->resident) bmh_tls_die("BMH_PHASE2_TEXT_DEVICE=1 needs the reference resident on the device", BMH_E_ARG);
+		if ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns)) || (rc = bmh_ctx_set_refnames(ctx, (const bmh_refidx_t *)J->bns)))
+			bmh_tls_die(bmh_last_error(ctx), rc);
+	}
+	if ((rc = bmh_ctx_set_phase2_text_device(ctx, qa_phase2_text_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	return ctx;
 }
 
@@ -810,6 +842,15 @@ static void qa_sam_slice(void *data, int k, int tid)
 		bmh_last_samtext_stats(ctx, &ts);
 		__sync_fetch_and_add(&g_samtext_cnt[0], (long long)(ts.reads > 0 ? ts.reads : 0)), __sync_fetch_and_add(&g_samtext_cnt[1], (long long)(ts.lines > 0 ? ts.lines : 0));
 		__sync_fetch_and_add(&g_samtext_cnt[2], (long long)(ts.text_bytes > 0 ? ts.text_bytes : 0));
+	}
+	if (qa_phase2_text_device()) {
+		bmh_phase2_text_stats_t ps;
+		int c;
+		bmh_last_phase2_text_stats(ctx, &ps);
+		{
+			const int64_t got[6] = {ps.units, ps.wanted, ps.redone, ps.lines, ps.text_bytes, ps.fallbacks};
+			for (c = 0; c < 6; ++c) __sync_fetch_and_add(&g_phase2_text_cnt[c], (long long)(got[c] > 0 ? got[c] : 0));
+		}
 	}
 	bmh_pool_put(ctx);
 	t2 = stage_now();
@@ -940,6 +981,9 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		if (qa_phase2_device())
 			fprintf(stderr, "[bwamem_hip] phase 2 on the device in one session: %lld units, %lld regions, %lld fixed, %lld redone on the host, %lld host fall-backs\n",
 			        g_phase2_cnt[0], g_phase2_cnt[1], g_phase2_cnt[2], g_phase2_cnt[3], g_phase2_cnt[4]);
+		if (qa_phase2_text_device())
+			fprintf(stderr, "[bwamem_hip] phase 2 and SAM text on the device in one session: %lld units, %lld regions, %lld redone on the host, %lld lines, %lld bytes, %lld host fall-backs\n",
+			        g_phase2_text_cnt[0], g_phase2_text_cnt[1], g_phase2_text_cnt[2], g_phase2_text_cnt[3], g_phase2_text_cnt[4], g_phase2_text_cnt[5]);
 		if (qa_samtext_device())
 			fprintf(stderr, "[bwamem_hip] SAM text on the device: %lld reads, %lld lines, %lld bytes\n", g_samtext_cnt[0], g_samtext_cnt[1], g_samtext_cnt[2]);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */

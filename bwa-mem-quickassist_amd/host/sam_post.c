@@ -465,6 +465,17 @@ __attribute__((visibility("hidden"))) int bmh_wanted_check_args_(bmh_ctx_t *ctx,
  * mem_reg2aln's second half (bwamem.c:1203-1235) and mem_reg2sam_se / mem_aln2sam (bwamem.c:904-1083) for a slice, over samtext_core.h,
  * the text the kernels of bmh_sam_text_device (csrc/samtext.hip) run: here only the checks, the arrays and the two passes. */
 
+static int mates_named_alike(int n, const bmh_seq_t *seqs) /* reads 2p, 2p + 1 of an even n, every name there */
+{
+	int i;
+	for (i = 0; i < n; i += 2)
+		if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) {
+			fprintf(stderr, "[bwamem_hip] paired reads have different names: \"%s\", \"%s\"\n", seqs[i].name, seqs[i + 1].name);
+			return BMH_E_ARG;
+		}
+	return BMH_OK;
+}
+
 /* what both forms refuse before anything runs (host only).  first: n + 1 entries, first[i] = wanted regions before read i; *lines = SAM
  * lines of the slice; *cig_words / *md_bytes = how far the records reach into the two pools */
 __attribute__((visibility("hidden"))) int bmh_samtext_check_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
@@ -501,13 +512,26 @@ __attribute__((visibility("hidden"))) int bmh_samtext_check_(const bmh_sam_opt_t
 		if ((size_t)wr[j].cigar_off + (size_t)wr[j].n_cigar > cw) cw = (size_t)wr[j].cigar_off + (size_t)wr[j].n_cigar;
 		if ((size_t)wr[j].md_off + (size_t)wr[j].md_len > mb) mb = (size_t)wr[j].md_off + (size_t)wr[j].md_len;
 	}
-	for (i = 0; pe && i < n; i += 2)
-		if (strcmp(seqs[i].name, seqs[i + 1].name) != 0) {
-			fprintf(stderr, "[bwamem_hip] paired reads have different names: \"%s\", \"%s\"\n", seqs[i].name, seqs[i + 1].name);
-			return BMH_E_ARG;
-		}
+	if (pe && (i = mates_named_alike(n, seqs))) return i;
 	*lines = nl, *cig_words = cw, *md_bytes = mb;
 	return BMH_OK;
+}
+
+/* what bmh_samtext_check_ refuses of a slice whose pass A and pass B outputs stay on the device (bmh_phase2_text_device, csrc/api.hip):
+ * the arguments, the reads and the names.  The vectors and offsets are bmh_pp_check_args's there. */
+__attribute__((visibility("hidden"))) int bmh_samtext_check_seqs_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n,
+                                                                  const bmh_seq_t *seqs, const bmh_alnreg_v *regs, char **text, int64_t *text_off)
+{
+	const int pe = o && (o->flag & BMH_MEM_F_PE) != 0;
+	int i;
+	if (!o || !bns || !text || !text_off || n < 0 || (pe && ((n & 1) || !pes))) return BMH_E_ARG;
+	if (n == 0) return BMH_OK;
+	if (!seqs || !regs || bns->l_pac <= 0 || bns->n_seqs <= 0 || !bns->anns) return BMH_E_ARG;
+	for (i = 0; i < bns->n_seqs; ++i)
+		if (!bns->anns[i].name) return BMH_E_ARG;
+	for (i = 0; i < n; ++i)
+		if (!seqs[i].name || seqs[i].l_seq < 0 || (seqs[i].l_seq > 0 && !seqs[i].seq)) return BMH_E_ARG;
+	return pe ? mates_named_alike(n, seqs) : BMH_OK;
 }
 
 int bmh_sam_text_batch(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,
@@ -608,6 +632,12 @@ int bmh_samtext_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
                         const int32_t *want_k, const bmh_wanted_res_t *wr, const uint32_t *cig, const char *md, const char *rg_id, char **text,
                         int64_t *text_off);
 
+/* all three passes as one device session behind the context's switch (csrc/api.hip): with bmh_ctx_set_phase2_text_device on, *done = 1
+ * and bmh_phase2_text_device's text, *text malloc'd, the vectors untouched; *done = 0 with the switch off, and for a slice the call
+ * refuses before its upload (BMH_E_RANGE), which then goes through the hooks above whatever the other switches say */
+int bmh_phase2_text_routed_(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
+                            const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const char *rg_id, char **text, int64_t *text_off, int *done);
+
 int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                   int64_t id0, int n, bmh_seq_t *seqs, bmh_alnreg_v *regs, const char *rg_id)
 {
@@ -621,7 +651,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	bmh_read_t *reads = 0;
 	uint32_t *cig = 0;
 	char *md = 0, *text = 0;
-	int i, rc = BMH_OK, fused = 0;
+	int i, rc = BMH_OK, fused = 0, texted = 0;
 	const int trace = getenv("BMH_DRIVER_TRACE") != 0;
 	double tt[4] = {0, 0, 0, 0};
 
@@ -638,11 +668,20 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 		if (regs[i].n && !regs[i].a) { rc = BMH_E_ARG; goto done; }
 		roff[i + 1] = roff[i] + (int64_t)regs[i].n;
 	}
+	text_off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+	if (!text_off) { rc = BMH_E_NOMEM; goto done; }
+
+	if (trace) tt[0] = now_s();
+	/* ---- all three passes as one device session (bmh_phase2_text_device behind the context's switch): only the text comes back, and the
+	 * vectors stay as they came */
+	if ((rc = bmh_phase2_text_routed_(ctx, o, bns, pac, pes, id0, n, seqs, regs, rg_id, &text, text_off, &texted))) goto done;
+	if (texted) {
+		if (trace) tt[1] = tt[2] = now_s();
+		goto strings;
+	}
 	reg_mapq = (int32_t *)malloc(sizeof(int32_t) * ((size_t)roff[n] + 1));
 	want_k = (int32_t *)malloc(sizeof(int32_t) * ((size_t)roff[n] + 1));
 	if (!reg_mapq || !want_k) { rc = BMH_E_NOMEM; goto done; }
-
-	if (trace) tt[0] = now_s();
 	/* ---- pass A and pass B as one device session (bmh_phase2_device behind the context's switch): its want list and records go to
 	 * pass C as they are */
 	if ((rc = bmh_phase2_routed_(ctx, o, bns, pac, pes, id0, n, reads, regs, roff, pd, reg_mapq, n_want, want_k, &n_w, &wr, &cig, &md, &fused))) goto done;
@@ -664,9 +703,8 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	if (trace) tt[2] = now_s();
 	/* ---- pass C: mem_reg2aln's second half (bwamem.c:1203-1235) for every wanted region, then the text: bmh_sam_text_batch, or with
 	 * bmh_ctx_set_samtext_device on bmh_sam_text_device (the same bytes either way); then one string per read */
-	text_off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
-	if (!text_off) { rc = BMH_E_NOMEM; goto done; }
 	if ((rc = bmh_samtext_routed_(ctx, o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, &text, text_off))) goto done;
+strings:
 	for (i = 0; i < n; ++i) {
 		const size_t len = (size_t)(text_off[i + 1] - text_off[i]);
 		char *s = (char *)malloc(len + 1);
@@ -681,6 +719,16 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	if (trace)
 		fprintf(stderr, "[bwamem_hip] bmh_sam_batch %d reads, %zu alignments: marking + pairing %.1f ms, global alignments (bmh_reg2cigar_batch) %.1f ms, coordinates + text %.1f ms\n",
 		        n, (size_t)n_w, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3);
+	if (trace) { /* what this slice's device sessions of phase 2 moved (each switch's statistics are this call's while it is on, -1 otherwise) */
+		bmh_phase2_stats_t p2;
+		bmh_samtext_stats_t sx;
+		bmh_phase2_text_stats_t pt;
+		long long up = 0, down = 0, waits = 0;
+		if (bmh_last_phase2_stats(ctx, &p2) == BMH_OK && p2.h2d_bytes > 0) up += p2.h2d_bytes, down += p2.d2h_bytes, waits += p2.waits;
+		if (bmh_last_samtext_stats(ctx, &sx) == BMH_OK && sx.h2d_bytes > 0) up += sx.h2d_bytes, down += sx.d2h_bytes, waits += sx.waits;
+		if (bmh_last_phase2_text_stats(ctx, &pt) == BMH_OK && pt.h2d_bytes > 0) up += pt.h2d_bytes, down += pt.d2h_bytes, waits += pt.waits;
+		if (waits) fprintf(stderr, "[bwamem_hip] bmh_sam_batch %d reads: phase 2 device sessions moved %lld bytes up, %lld bytes down, %lld waits\n", n, up, down, waits);
+	}
 done:
 	free(wr), free(pd), free(reads), free(cig), free(md), free(roff), free(reg_mapq), free(n_want), free(want_k), free(text), free(text_off);
 	return rc;

@@ -616,7 +616,8 @@ int bmh_pair(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], c
  * and 2p+1 are mates, pes = the four insert-size models, mate rescue already done or off), runs the global alignments
  * of exactly the regions that get printed as GPU batches, and writes seqs[i].sam (malloc'd, the caller frees it as
  * fastmap.c:201 does).  id0 = n_processed + index of read 0 (the reference's per-read id, bwamem.c:1287,1291).
- * rg_id: the reference's bwa_rg_id ("" = none).  regs[i].a is left sorted/marked as the reference leaves it.
+ * rg_id: the reference's bwa_rg_id ("" = none).  regs[i].a is left sorted/marked as the reference leaves it -- except with
+ * bmh_ctx_set_phase2_text_device on (below), where all three passes are one device session and the vectors stay exactly as they came.
  * The decisions (everything before the global alignments) are bmh_decide_batch's, or with bmh_ctx_set_decide_device on
  * bmh_decide_device's: the same text either way (below).  With bmh_ctx_set_phase2_device on, decisions and alignments are one device
  * session, bmh_phase2_device's: the same text again.  The text itself (pass C) is bmh_sam_text_batch's, or with
@@ -806,6 +807,57 @@ typedef struct bmh_samtext_stats {
 	float size_ms, emit_ms;
 } bmh_samtext_stats_t; /* 56 bytes */
 int bmh_last_samtext_stats(const bmh_ctx_t *ctx, bmh_samtext_stats_t *st);
+
+/* ---- Passes A, B and C as one device session: the slice's regions and reads go up once, and only SAM text comes down.
+ * *text / text_off[0..n] are byte for byte what bmh_decide_batch, then bmh_wanted_cigar_batch(..., w = o->w, ...), then
+ * bmh_sam_text_batch give for the same arguments: the concatenation of the seqs[i].sam strings bmh_sam_batch writes.  regs is read
+ * only: the caller's vectors are left exactly as they came, not sorted and not marked, because nothing of pass A comes down.
+ *   one upload   bmh_phase2_device's block as it is (offsets, opt + pes, read offsets, parameters, pair table, regions), and pass C's
+ *                inputs the device does not yet have: the 144-byte header, rg_id, the per-read pool's offsets and the per-read pool of
+ *                bmh_sam_text_device (name, base codes, qualities, comment).  The bases go up once, inside that pool;
+ *                reads_gather_kernel builds pass B's contiguous reads pool from it on the device.
+ *   the passes   A and B exactly as in bmh_phase2_device, through wanted_result_kernel (the host reads one 64-byte status record
+ *                twice).  phase2_text_bind_kernel then turns every record's slot number into the slot's address in the main round's
+ *                CIGAR and MD slots, where pass C reads them -- nothing is packed -- and lists the regions flagged BMH_WANTED_HOST.
+ *                samtext_size_kernel and the scan follow with no wait between; the host reads one 32-byte status (text total, error
+ *                word, host-region count, lines), launches samtext_emit_kernel and downloads text_off and the text: four waits.
+ *   the redo     where the host-region count is not zero only the list comes down (112 bytes per region); the host redoes those
+ *                regions as bmh_wanted_cigar_device does, uploads their records, CIGAR words and MD bytes into an overflow area behind
+ *                the slots, patches the records on the device and runs size and scan again: six waits, the rest of the slice unaffected.
+ * Needs the context's parameters, the resident 2-bit reference, the sequence table (bmh_ctx_set_refidx) and the sequence names
+ * (bmh_ctx_set_refnames): BMH_E_ARG without any of them.
+ *   BMH_E_ARG    before any upload: a NULL ctx, text or text_off, and what bmh_phase2_device and bmh_sam_text_batch refuse of o, bns,
+ *                pac, pes, n, seqs and regs (a read without a name, mates whose names differ, ...); from the kernels: what
+ *                bmh_phase2_device's and bmh_sam_text_device's raise
+ *   BMH_E_RANGE  before any upload: what bmh_decide_device refuses (a table past 1 << 20 entries), and a slice whose slot addresses
+ *                (regions x 24 words, regions x 128 bytes) do not fit in 32 bits; from the kernels: a wanted window past 65535;
+ *                behind the redo: an overflow area whose addresses do not fit in 32 bits
+ *   BMH_OK       for n == 0 with an empty pool and text_off[0] = 0, nothing runs
+ * All or nothing: on any error *text and text_off are untouched. */
+int bmh_phase2_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
+                           int64_t id0, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const char *rg_id, char **text,
+                           int64_t *text_off);
+/* Per context, off by default.  While on, bmh_sam_batch takes all three passes from bmh_phase2_text_device (BMH_E_ARG without the
+ * resident tables) and leaves regs[i].a exactly as it came.  A slice that call refuses with BMH_E_RANGE before its upload goes the way
+ * the other switches say, and is counted as a fall-back.  The text is the same either way. */
+int bmh_ctx_set_phase2_text_device(bmh_ctx_t *ctx, int on);
+/* Of the last bmh_phase2_text_device call on this context, direct or from bmh_sam_batch with the switch on; all -1 before the first.
+ * With the switch on bmh_sam_batch sets the counts to 0 (the milliseconds to -1) at its entry.
+ *   units, wanted, fixed, redone   reads or pairs decided, wanted regions, regions bwa_fix_xref2 moved, regions redone on the host
+ *   reads, lines, text_bytes       of the slice
+ *   h2d_bytes, d2h_bytes, waits    of the fused session only (not of the host's redo): waits is 4, or 6 with redone regions (2 for a
+ *                                  slice without a single region, where pass B has nothing to run)
+ *   fallbacks, sessions            0 and 1 for a fused run; 1 and 0 where the call refused the slice before its upload (BMH_E_RANGE)
+ *   decide_ms, wanted_ms, gather_ms, size_ms, emit_ms   the kernels' milliseconds with bmh_set_kernel_timing on, else -1 */
+typedef struct bmh_phase2_text_stats {
+	int64_t units, wanted, fixed, redone;
+	int64_t reads, lines, text_bytes;
+	int64_t h2d_bytes, d2h_bytes, fallbacks;
+	int32_t waits, sessions;
+	float decide_ms, wanted_ms, gather_ms, size_ms, emit_ms;
+	int32_t rsv_;
+} bmh_phase2_text_stats_t; /* 112 bytes */
+int bmh_last_phase2_text_stats(const bmh_ctx_t *ctx, bmh_phase2_text_stats_t *st);
 
 /* ------------------------------------------------------------------------------------------------------------
  * FM-index queries of the seeding stage (first slice): super-maximal exact matches and suffix-
