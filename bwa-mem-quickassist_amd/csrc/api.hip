@@ -2454,9 +2454,10 @@ int bmh_samtext_check_seqs_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, con
                             char **text, int64_t *text_off);
 
 // ensure() for a block whose first `keep` bytes a session still needs: the new allocation has them before the old one goes.  Every
-// pointer into the block is the caller's to make again.
-static int ensure_keep(bmh_ctx *ctx, DevBuf &b, size_t bytes, size_t keep)
+// pointer into the block is the caller's to make again.  *waited: whether the block moved, which costs the caller one wait.
+static int ensure_keep(bmh_ctx *ctx, DevBuf &b, size_t bytes, size_t keep, bool *waited)
 {
+	*waited = false;
 	if (bytes <= b.cap) return BMH_OK;
 	DevBuf nb;
 	int rc = ensure(ctx, nb, std::max(bytes, 2 * b.cap));
@@ -2469,6 +2470,7 @@ static int ensure_keep(bmh_ctx *ctx, DevBuf &b, size_t bytes, size_t keep)
 	}
 	free_buf(b);
 	b = nb;
+	*waited = true;
 	return BMH_OK;
 }
 
@@ -2710,7 +2712,9 @@ static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refid
 				cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
 				orec[t] = x, oat[t] = list[t].j;
 			}
-			if ((e = ensure_keep(ctx, ctx->d_wanted, o_end, LB.end))) return e;
+			bool moved;
+			if ((e = ensure_keep(ctx, ctx->d_wanted, o_end, LB.end, &moved))) return e;
+			if (moved) ++ctx->pt.waits; // (the seventh wait: the block's copy had to arrive before the old one went)
 			dw = (uint8_t *)ctx->d_wanted.p;
 			cig_words = cig0 + cw, md_bytes = md0 + mb;
 			st.up_used = 0; // (everything staged so far has arrived; the redo had the staging buffers for itself)

@@ -823,7 +823,8 @@ int bmh_last_samtext_stats(const bmh_ctx_t *ctx, bmh_samtext_stats_t *st);
  *                word, host-region count, lines), launches samtext_emit_kernel and downloads text_off and the text: four waits.
  *   the redo     where the host-region count is not zero only the list comes down (112 bytes per region); the host redoes those
  *                regions as bmh_wanted_cigar_device does, uploads their records, CIGAR words and MD bytes into an overflow area behind
- *                the slots, patches the records on the device and runs size and scan again: six waits, the rest of the slice unaffected.
+ *                the slots, patches the records on the device and runs size and scan again: six waits, the rest of the slice unaffected
+ *                (seven where the overflow area outgrew the block, which then moves with its contents kept).
  * Needs the context's parameters, the resident 2-bit reference, the sequence table (bmh_ctx_set_refidx) and the sequence names
  * (bmh_ctx_set_refnames): BMH_E_ARG without any of them.
  *   BMH_E_ARG    before any upload: a NULL ctx, text or text_off, and what bmh_phase2_device and bmh_sam_text_batch refuse of o, bns,
@@ -845,8 +846,9 @@ int bmh_ctx_set_phase2_text_device(bmh_ctx_t *ctx, int on);
  * With the switch on bmh_sam_batch sets the counts to 0 (the milliseconds to -1) at its entry.
  *   units, wanted, fixed, redone   reads or pairs decided, wanted regions, regions bwa_fix_xref2 moved, regions redone on the host
  *   reads, lines, text_bytes       of the slice
- *   h2d_bytes, d2h_bytes, waits    of the fused session only (not of the host's redo): waits is 4, or 6 with redone regions (2 for a
- *                                  slice without a single region, where pass B has nothing to run)
+ *   h2d_bytes, d2h_bytes, waits    of the fused session only (not of the host's redo): waits is 4, or 6 with redone regions, 7 where
+ *                                  the overflow area outgrew the block (2 for a slice without a single region, where pass B has
+ *                                  nothing to run)
  *   fallbacks, sessions            0 and 1 for a fused run; 1 and 0 where the call refused the slice before its upload (BMH_E_RANGE)
  *   decide_ms, wanted_ms, gather_ms, size_ms, emit_ms   the kernels' milliseconds with bmh_set_kernel_timing on, else -1 */
 typedef struct bmh_phase2_text_stats {

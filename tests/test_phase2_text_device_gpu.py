@@ -2,8 +2,9 @@
 against the host composition bmh_decide_batch, then bmh_wanted_cigar_batch, then bmh_sam_text_batch on copies of the vectors: the text
 and text_off byte for byte.  Slices of tests/phase2gen.py at the kernels' block sizes, dressed with names, comments and qualities;
 reads of unequal length next to each other (reads_gather_kernel's tails); regions bwa_fix_xref2 moves; alignments that outgrow their
-slots and are redone on the host without sending the slice there; every refusal with the outputs untouched; the session's transfers
-and waits in numbers; and the switch behind bmh_sam_batch."""
+slots and are redone on the host without sending the slice there -- also where their overflow area outgrows the block and the live
+session moves it, around the 256-lane blocks of the bind and patch kernels, in pairs, and through the switch (tests/redogen.py);
+every refusal with the outputs untouched; the session's transfers and waits in numbers; and the switch behind bmh_sam_batch."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +14,7 @@ import decidegen as dg
 import kswgen
 import kswlib
 import phase2gen as pg
+import redogen
 import samtextgen as sg
 import wantgen as wg
 from __graft_entry__ import load_package
@@ -74,7 +76,7 @@ def _same_text(dt, doff, ht, hoff, what):
         raise AssertionError((what, i, dt[int(hoff[i]):int(hoff[i + 1])][:400], ht[int(hoff[i]):int(hoff[i + 1])][:400]))
 
 
-def _both(pkg, c, o, pes, id0, seqs, vectors, what, rg=RG, host=None):
+def _both(pkg, c, o, pes, id0, seqs, vectors, what, rg=RG, host=None, expect_waits=None):
     vecs = [np.ascontiguousarray(v, dtype=kswlib.ALNREG).reshape(-1).copy() for v in vectors]
     before = [v.tobytes() for v in vecs]
     ht, hoff, a, res = host or _host(pkg, c, o, pes, id0, seqs, vecs, rg)
@@ -86,7 +88,8 @@ def _both(pkg, c, o, pes, id0, seqs, vectors, what, rg=RG, host=None):
     n = len(seqs)
     got = (st["units"], st["wanted"], st["reads"], st["lines"], st["text_bytes"], st["fallbacks"], st["sessions"])
     assert got == (n // 2 if _is_pe(o) else n, len(res), n, ht.count(b"\n"), len(ht), 0, 1), (what, st)
-    assert st["waits"] == (6 if st["redone"] else 4 if any(len(v) for v in vecs) else 2), (what, st)  # (no region at all: pass B has nothing to wait for)
+    # (no region at all: pass B has nothing to wait for; expect_waits: 7 where the overflow area is to outgrow the block)
+    assert st["waits"] == (expect_waits if expect_waits is not None else 6 if st["redone"] else 4 if any(len(v) for v in vecs) else 2), (what, st)
     return (ht, hoff, a, res), st
 
 
@@ -187,10 +190,10 @@ def _long_reference(pkg, seed, l_pac):
     return whole, _context(pkg, [(0, l_pac // 2), (l_pac // 2, l_pac - l_pac // 2)], wg.pack(whole), l_pac)
 
 
-def _outgrowing(whole, rng):
+def _outgrowing(whole, rng, l_pac=20000):
     """the slice of test_alignments_that_outgrow_the_slots_are_redone_from_the_sorted_block (tests/test_phase2_device_gpu.py): 24 reads, of
     which four have an MD past the 128 bytes of its slot and four a CIGAR past 24 words, each of the eight the second region of its input
-    vector and the first after the sort"""
+    vector and the first after the sort; l_pac: of the reference `whole` is (at least 18 000 bases in its first sequence)"""
     reads, vectors, special = [], [], []
     for k in range(24):
         pos = 500 + 700 * k
@@ -213,7 +216,7 @@ def _outgrowing(whole, rng):
             rd = kswgen.mutate(rng, whole[pos:pos + 150], sub=0.02)
             tl = 150
         rev = bool(k & 1)
-        rb, re = (pos, pos + tl) if not rev else (40000 - pos - tl, 40000 - pos)
+        rb, re = (pos, pos + tl) if not rev else (2 * l_pac - pos - tl, 2 * l_pac - pos)
         rd = wg.revcomp(rd) if rev else rd
         reg = wg.region(0, len(rd), rb, re, len(rd) - 40, 100, len(rd) - 40)
         reg["seedcov"] = 60
@@ -260,6 +263,93 @@ def test_no_record_in_the_main_round(pkg, n_w):
         assert (st["wanted"], st["fixed"], st["redone"], st["waits"], st["fallbacks"]) == (n_w, n_w, n_w, 6, 0), st
     finally:
         c.close()
+
+
+# ---------------------------------------------------------------- the redo path where it grows and branches (tests/redogen.py)
+
+def _past_the_slots(res):
+    return (res["md_len"] > redogen.MD_SLOT) | (res["n_cigar"] > redogen.CIGAR_SLOT)
+
+
+def test_the_overflow_area_outgrows_the_block(pkg):
+    """The redone regions' records, CIGAR words and MD bytes go behind pass B's block in d_wanted.  A fresh context's block has under a
+    MiB to spare; redogen.FIRST's 32 long reads need 1.6 MB there, so the live session moves the block under its own pointers
+    (ensure_keep): seven waits.  The same slice again fits: six.  Then, on the block that has just been replaced, an ordinary slice with
+    its regions and the 24-read slice with eight redone regions; then redogen.SECOND, whose 7.5 MB pass twice the capacity the first
+    growth left, so that ensure_keep's max(bytes, 2 * capacity) has taken either side; and that slice again.  Every call byte for byte
+    the host composition's text, with no fall-back.  That each slice does reach its branch is asserted on the yardstick's own records
+    before the device call is trusted with it (and, from the substitutions alone, in tests/test_redogen_cpu.py).
+    Measured on an MI355X: 1 662 733 bytes of overflow against 1 048 576, then 7 551 075 against 6 291 456; 1.3 s for the whole test."""
+    whole, contigs = redogen.growth_reference()
+    l_pac = len(whole)
+    c = _context(pkg, contigs, wg.pack(whole), l_pac)
+    try:
+        o, caps = pg.opt(), []
+        for spec, name in ((redogen.FIRST, "first"), (redogen.SECOND, "second")):
+            reads, vectors, info = redogen.growth(whole, spec)
+            seqs = _dress(reads, False)
+            host = _host(pkg, c, o, None, 50, seqs, vectors)
+            over, m = redogen.overflow_bytes(host[3]["md_len"], host[3]["n_cigar"])
+            lb = redogen.lb_max(len(reads), sum(map(len, vectors)))
+            if not caps:  # a fresh block: whatever its layout, it holds no more than this
+                bound = redogen.first_cap(lb)
+                caps.append(redogen.grown_cap(bound, lb + over + 4 * 64)[0])  # (... and no more than this once it has grown)
+            else:
+                bound = 2 * caps[0]
+            print(f"{name} growth: {over} bytes of overflow in {m} regions against {bound}, predicted {redogen.predicted_overflow(info)}")
+            assert m == info["n_long"] and over > bound, (name, over, bound, m)
+            for what, waits in (("grows the block", 7), ("fits", 6)):
+                _, st = _both(pkg, c, o, None, 50, seqs, vectors, f"{name} growth slice, {what}", host=host, expect_waits=waits)
+                assert (st["redone"], st["fixed"], st["wanted"]) == (m, 0, len(reads)), (name, what, st)
+            if name == "first":
+                o2, pes2, id2, r2, v2 = pg.make("se", units=50, seed=41)
+                _, st = _both(pkg, c, o2, pes2, id2, _dress(r2, False), v2, "an ordinary slice on the block that moved")
+                assert st["wanted"] >= 30 and (st["redone"], st["waits"]) == (0, 4), st
+                r3, v3, special = _outgrowing(whole, np.random.default_rng(61), l_pac)
+                _, st = _both(pkg, c, o, None, 50, _dress(r3, False), v3, "eight redone regions on the block that moved")
+                assert len(special) == 8 and (st["redone"], st["waits"], st["wanted"], st["fixed"]) == (8, 6, 32, 0), st
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("m", [255, 256, 257, 513])
+def test_redone_counts_around_a_block(pkg, ctx, ref, m):
+    """phase2_text_bind_kernel appends the host's regions to its list through an atomic counter and phase2_text_patch_kernel writes their
+    records back, both in blocks of 256 lanes: one short of a block, a block, one more, two blocks and one.  The redone regions lie at
+    irregular places in want order, on both strands, some by their MD and some by their CIGAR, some behind the sort."""
+    reads, vectors = redogen.counted_slice(ref[0], m, seed=90)
+    o, seqs = pg.opt(), _dress(reads, False)
+    host = _host(pkg, ctx, o, None, 120, seqs, vectors)
+    # Whether the overflow area fits behind the block depends on what the shared context has served before (513 regions outgrow a block
+    # of one MiB): the first call may grow it, the second finds it large enough whatever came before
+    dt, doff = ctx.phase2_text_device(o, ctx.idx, ctx.pac, None, 120, seqs, vectors, RG)
+    _same_text(dt, doff, host[0], host[1], f"{m} redone regions, the block as it was")
+    st = ctx.last_phase2_text_stats()
+    assert st["redone"] == m and st["waits"] in (6, 7), st
+    (_, _, a, res), st = _both(pkg, ctx, o, None, 120, seqs, vectors, f"{m} redone regions", host=host)
+    past = _past_the_slots(res)
+    j = np.flatnonzero(past)
+    gaps = np.diff(j)
+    assert int((gaps == 1).sum()) >= 20 and int((gaps > 1).sum()) >= 20 and len(set(gaps.tolist())) >= 4  # runs and single ones
+    assert int((res["n_cigar"] > redogen.CIGAR_SLOT).sum()) >= m // 8 and int((res["md_len"] > redogen.MD_SLOT).sum()) >= m // 2
+    assert 0 < int((res["rb"][past] >= wg.L_PAC).sum()) < m
+    assert len(j) == m and (st["redone"], st["fixed"], st["waits"]) == (m, 0, 6) and st["wanted"] > m + 100, (m, len(j), st)
+    # the list, 112 bytes per region, and one more status: nothing else of passes A and B came down
+    assert st["d2h_bytes"] <= st["text_bytes"] + 8 * (len(reads) + 1) + 256 + 112 * m + 32, st
+
+
+def test_paired_end_with_redone_mates(pkg, ctx, ref):
+    """samtext_size_kernel composes both reads of a pair in one lane, each from its own records: pairs of which the first mate's record
+    is a patched one and the second's is not, the reverse, both, and a redone mate beside one without any region; 72 pairs, past one
+    block of decide_kernel"""
+    reads, vectors, kinds = redogen.paired_slice(ref[0], 72, seed=95)
+    assert set(kinds) == set(redogen.PAIR_KINDS) and len(reads) == 144
+    o, pes = pg.opt(100, pg.PE), pg.pes_fr()
+    (_, _, a, res), st = _both(pkg, ctx, o, pes, 7000, _dress(reads, True), vectors, "pairs with redone mates")
+    expect = sum(k.count("redone") + k.count("cigar") for k in kinds)
+    past = int(_past_the_slots(res).sum())
+    assert past == expect and (st["redone"], st["waits"], st["fixed"]) == (past, 6, 0) and st["wanted"] > past, (past, expect, st)
+    assert int((a["pd"]["paired"] != 0).sum()) >= 20  # (proper pairs among them, so the mates' records meet in one line's fields)
 
 
 # ---------------------------------------------------------------- one session, in numbers
@@ -500,5 +590,36 @@ def test_switch_behind_sam_batch(pkg, ref, mode):
         before = c.last_phase2_text_stats()
         t5, r5 = _sam_batch(pkg, c, o, pes, id0, vectors, reads, b"grp")
         assert t0 == t5 and r0 == r5 and c.last_phase2_text_stats() == before
+    finally:
+        c.close()
+
+
+def test_switch_behind_sam_batch_with_redone_regions(pkg):
+    """bmh_phase2_text_routed_ with regions to redo: the session leaves its gate around the host's redo and takes it again, inside
+    bmh_sam_batch, and the caller's vectors still come back as they came"""
+    whole, c = _long_reference(pkg, 60, 20000)
+    try:
+        reads, vectors, special = _outgrowing(whole, np.random.default_rng(61))
+        plain = [k for k in range(len(reads)) if k not in special]
+        pr, pv = [reads[k] for k in plain], [vectors[k] for k in plain]
+        came = [np.array(v, dtype=kswlib.ALNREG, copy=True).tobytes() for v in vectors]
+        o = pg.opt()
+        t0, r0 = _sam_batch(pkg, c, o, None, 50, vectors, reads, b"grp")
+        p0, q0 = _sam_batch(pkg, c, o, None, 90, pv, pr, b"grp")
+        assert r0 != came and c.last_phase2_text_stats()["sessions"] == -1  # the default route sorts and marks; nothing fused yet
+        c.set_phase2_text_device(True)
+        t1, r1 = _sam_batch(pkg, c, o, None, 50, vectors, reads, b"grp")
+        assert t0 == t1 and r1 == came  # the same text; the vectors as they came
+        st = c.last_phase2_text_stats()
+        assert len(special) == 8 and (st["redone"], st["waits"], st["fallbacks"], st["sessions"], st["wanted"], st["fixed"]) == (8, 6, 0, 1, 32, 0), st
+        assert (st["reads"], st["lines"], st["text_bytes"]) == (len(reads), sum(t.count(b"\n") for t in t0), sum(map(len, t0))), st
+        # the next slice on the same context is an ordinary one again
+        p1, q1 = _sam_batch(pkg, c, o, None, 90, pv, pr, b"grp")
+        assert p0 == p1 and q1 == [np.array(v, dtype=kswlib.ALNREG, copy=True).tobytes() for v in pv]
+        st = c.last_phase2_text_stats()
+        assert (st["redone"], st["waits"], st["fallbacks"], st["sessions"], st["wanted"]) == (0, 4, 0, 1, len(pr)), st
+        c.set_phase2_text_device(False)
+        t2, r2 = _sam_batch(pkg, c, o, None, 50, vectors, reads, b"grp")
+        assert t0 == t2 and r0 == r2
     finally:
         c.close()
