@@ -240,6 +240,13 @@ def lib():
         L.bmh_sort_dedup_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float]
         L.bmh_ctx_set_regs_dedup.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.bmh_last_dedup_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.bmh_pestat_candidates.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.bmh_pestat_from_candidates.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+        L.bmh_pestat_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.bmh_ctx_set_regs_drop_exact.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_ctx_set_pestat_collect.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.bmh_last_pestat_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
+        L.bmh_last_drop_exact_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.bmh_decide_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6
         L.bmh_decide_device.argtypes = [C.c_void_p] + L.bmh_decide_batch.argtypes
         L.bmh_ctx_set_decide_device.argtypes = [C.c_void_p, C.c_int]
@@ -875,6 +882,34 @@ class Context:
         self._check(lib().bmh_last_dedup_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
         return a.value, b.value, ms.value
 
+    def pestat_device(self, opt, l_pac, vectors):
+        """bmh_pestat_device: mem_pestat's pair walk for a caller's vectors in one device call.  Arguments and result as
+        pestat_candidates()."""
+        return _pestat_words(self, opt, l_pac, vectors)
+
+    def set_regs_drop_exact(self, on=True):
+        """bmh_ctx_set_regs_drop_exact: while on (with set_regs_dedup on), chains2regs_device and seed_chain_regs_batch apply
+        mem_test_and_remove_exact on the device, behind the de-duplication."""
+        self._check(lib().bmh_ctx_set_regs_drop_exact(self._h, 1 if on else 0))
+
+    def set_pestat_collect(self, on=True, opt=None):
+        """bmh_ctx_set_pestat_collect: while on (with set_regs_dedup on), the two calls also compute mem_pestat's word per pair of
+        reads (2p, 2p+1) under opt (SAM_OPT, copied); last_pestat_candidates() hands them out."""
+        o = np.array(opt, dtype=SAM_OPT).reshape(1) if opt is not None else None
+        self._check(lib().bmh_ctx_set_pestat_collect(self._h, 1 if on else 0, _ptr(o) if o is not None else None))
+
+    def last_pestat_candidates(self, n_pairs):
+        """(words, kernel ms or -1) of the last successful collecting call, which had n_pairs pairs."""
+        w, ms = np.zeros(max(int(n_pairs), 0), dtype=np.uint32), C.c_float(0)
+        self._check(lib().bmh_last_pestat_candidates(self._h, _ptr(w) if len(w) else None, int(n_pairs), C.byref(ms)))
+        return w, ms.value
+
+    def last_drop_exact_stats(self):
+        """Regions drop-exact removed in the last successful call that ran with it on; -1 before the first."""
+        a = C.c_int64(0)
+        self._check(lib().bmh_last_drop_exact_stats(self._h, C.byref(a)))
+        return a.value
+
     def decide_device(self, opt, l_pac, pes, id0, vectors, roff=None, inplace=False):
         """bmh_decide_device: pass A of phase 2 as a kernel.  Arguments and result as decide_batch()."""
         return _decide(self, opt, l_pac, pes, id0, vectors, roff, inplace)
@@ -1106,6 +1141,43 @@ def decide_batch(opt, l_pac, pes, id0, vectors, roff=None, inplace=False):
     Returns a dict: regs (per read the vector as pass A leaves it), pd (PAIRDEC per pair), reg_mapq, n_want, want_k (flat, at the
     regions' offsets; entries past n_want stay -1) and want (per read the printed regions' indices)."""
     return _decide(None, opt, l_pac, pes, id0, vectors, roff, inplace)
+
+
+def _pestat_words(ctx, opt, l_pac, vectors):
+    n = len(vectors)
+    o = np.array(opt, dtype=SAM_OPT).reshape(1)
+    bufs = [np.ascontiguousarray(v, dtype=ALNREG).reshape(-1) for v in vectors]
+    c_regs = (_AlnregV * max(n, 1))()
+    for r, a in enumerate(bufs):
+        c_regs[r].n = c_regs[r].m = len(a)
+        c_regs[r].a = a.ctypes.data if len(a) else None
+    cand = np.zeros(n // 2, dtype=np.uint32)
+    cp = _ptr(cand) if len(cand) else None
+    if ctx is None:
+        rc = lib().bmh_pestat_candidates(_ptr(o), int(l_pac), n, C.cast(c_regs, C.c_void_p), cp)
+        if rc:
+            raise BmhError(rc, lib().bmh_strerror(rc).decode())
+    else:
+        ctx._check(lib().bmh_pestat_device(ctx._h, _ptr(o), int(l_pac), n, C.cast(c_regs, C.c_void_p), cp))
+    return cand
+
+
+def pestat_candidates(opt, l_pac, vectors):
+    """bmh_pestat_candidates: mem_pestat's pair walk on the host.  opt: SAM_OPT; vectors: per read an ALNREG array, reads 2p and
+    2p+1 being mates (an odd count ignores the last).  Returns len(vectors) // 2 words: 0 = no candidate, else
+    orientation << 30 | insert size."""
+    return _pestat_words(None, opt, l_pac, vectors)
+
+
+def pestat_from_candidates(opt, cand, verbose=-1):
+    """bmh_pestat_from_candidates: mem_pestat's statistics from such words.  Returns PESTAT[4]."""
+    o = np.array(opt, dtype=SAM_OPT).reshape(1)
+    cand = np.ascontiguousarray(cand, dtype=np.uint32).reshape(-1)
+    pes = np.zeros(4, dtype=PESTAT)
+    rc = lib().bmh_pestat_from_candidates(_ptr(o), len(cand), _ptr(cand) if len(cand) else None, _ptr(pes), int(verbose))
+    if rc:
+        raise BmhError(rc, lib().bmh_strerror(rc).decode())
+    return pes
 
 
 def sam_text_batch(opt, refidx, pes, seqs, vectors, dec, res, cig, md, rg_id=b"", ctx=None, out=None):

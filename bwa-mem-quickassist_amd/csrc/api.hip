@@ -15,6 +15,7 @@
 #include "decide.h"
 #include "wanted.h"
 #include "samtext.h"
+#include "../host/pestat_core.h"
 
 namespace bmh {
 
@@ -337,6 +338,9 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 	for (auto &e : ctx->ev_chain)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_dedup)
+		if (e) (void)hipEventDestroy(e);
+	free_buf(ctx->d_pestat);
+	for (auto &e : ctx->ev_pestat)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
 		if (h.ev) (void)hipEventDestroy(h.ev);
@@ -1325,6 +1329,101 @@ int bmh_last_dedup_stats(const bmh_ctx_t *ctx, int64_t *regions_in, int64_t *reg
 	if (regions_in) *regions_in = ctx->dedup_in;
 	if (regions_out) *regions_out = ctx->dedup_out;
 	if (kernel_ms) *kernel_ms = ctx->dedup_ms;
+	return BMH_OK;
+}
+
+// ------------------------------------------------------------------ mem_pestat's pair walk (pestat.hip)
+
+int bmh_pestat_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, uint32_t *cand)
+{
+	if (!ctx || !o || l_pac < 0 || n < 0 || (n > 0 && !regs) || (n > 1 && !cand)) return BMH_E_ARG;
+	const int np = n >> 1, n_reads = np << 1; // an odd n ignores the last read, as the reference's n>>1 does
+	size_t total = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		if (regs[r].n && !regs[r].a) return BMH_E_ARG;
+		if (regs[r].n > 0x7fffffffu - total) {
+			ctx->last_error = "bmh_pestat_device: more than 2^31-1 regions in the batch";
+			return BMH_E_ARG;
+		}
+		total += regs[r].n;
+	}
+	if (o->max_ins > BMH_PS_MAX_INS) {
+		ctx->last_error = "bmh_pestat_device: max_ins must be below 2^30, the word carries the orientation above it";
+		return BMH_E_RANGE;
+	}
+	if (np) memset(cand, 0, (size_t)np * sizeof(uint32_t));
+	if (total == 0) return BMH_OK; // nothing to launch: no pair of empty vectors is a candidate
+	// device block: [the words | off[n_reads + 1] | cnt[n_reads] | the regions]; everything behind the words goes up in one copy
+	const size_t nr = (size_t)n_reads, o_off = ((size_t)np * 4 + 63) & ~(size_t)63, o_cnt = o_off + (nr + 1) * 8, o_reg = (o_cnt + nr * 8 + 63) & ~(size_t)63;
+	const size_t b_up = o_reg - o_off + total * sizeof(bmh_alnreg_t);
+	std::vector<uint8_t> up;
+	try {
+		up.resize(b_up);
+	} catch (const std::bad_alloc &) {
+		ctx->last_error = "bmh_pestat_device: out of host memory";
+		return BMH_E_NOMEM;
+	}
+	unsigned long long *off = (unsigned long long *)up.data(), *cnt = (unsigned long long *)(up.data() + (o_cnt - o_off));
+	size_t at = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		off[r] = at, cnt[r] = regs[r].n;
+		if (regs[r].n) memcpy(up.data() + (o_reg - o_off) + at * sizeof(bmh_alnreg_t), regs[r].a, regs[r].n * sizeof(bmh_alnreg_t));
+		at += regs[r].n;
+	}
+	off[n_reads] = at;
+	memset(up.data() + (o_cnt - o_off) + nr * 8, 0, o_reg - (o_cnt + nr * 8));
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	Stager st(ctx);
+	const int rc = [&]() -> int {
+		int e;
+		if ((e = ensure(ctx, ctx->d_pestat, o_off + b_up)) || (e = st.stage(b_up, (size_t)np * 4 + 64))) return e;
+		uint8_t *d = (uint8_t *)ctx->d_pestat.p;
+		if ((e = st.h2d(d + o_off, up.data(), b_up))) return e;
+		if ((e = launch_pestat_collect(ctx, (bmh_alnreg_t *)(d + o_reg), (const unsigned long long *)(d + o_off), (unsigned long long *)(d + o_cnt), nullptr, n_reads,
+		                               (unsigned long long)total, *o, l_pac, 0, false, (uint32_t *)d, nullptr, ctx->d_err)))
+			return e;
+		return st.d2h(cand, d, (size_t)np * 4);
+	}();
+	return st.end(rc);
+}
+
+int bmh_ctx_set_regs_drop_exact(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->regs_drop_exact = on != 0;
+	return BMH_OK;
+}
+
+int bmh_ctx_set_pestat_collect(bmh_ctx_t *ctx, int on, const bmh_sam_opt_t *o)
+{
+	if (!ctx || (on && !o)) return BMH_E_ARG;
+	ctx->pestat_collect = on != 0;
+	if (on) ctx->pestat_opt = *o;
+	return BMH_OK;
+}
+
+int bmh_last_pestat_candidates(bmh_ctx_t *ctx, uint32_t *cand, int64_t n_pairs, float *kernel_ms)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (ctx->regs_drop_exact && !ctx->pestat_collect) {
+		ctx->last_error = "bmh_last_pestat_candidates: the collect switch is off (bmh_ctx_set_pestat_collect)";
+		return BMH_E_ARG;
+	}
+	if (ctx->pestat_pairs < 0 || n_pairs != (int64_t)ctx->pestat_pairs || (n_pairs > 0 && !cand)) {
+		ctx->last_error = ctx->pestat_pairs < 0 ? "bmh_last_pestat_candidates: no collecting call has been made on this context"
+		                                        : "bmh_last_pestat_candidates: n_pairs is not the last collecting call's pair count";
+		return BMH_E_ARG;
+	}
+	if (n_pairs) memcpy(cand, ctx->pestat_cand.data(), (size_t)n_pairs * sizeof(uint32_t));
+	if (kernel_ms) *kernel_ms = ctx->pestat_ms;
+	return BMH_OK;
+}
+
+int bmh_last_drop_exact_stats(const bmh_ctx_t *ctx, int64_t *removed)
+{
+	if (!ctx) return BMH_E_ARG;
+	if (removed) *removed = ctx->drop_exact_removed;
 	return BMH_OK;
 }
 

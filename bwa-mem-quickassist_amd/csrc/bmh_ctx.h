@@ -132,6 +132,16 @@ struct bmh_ctx {
 	hipEvent_t ev_dedup[2] = {};              // around the kernel (timing mode)
 	long long dedup_in = -1, dedup_out = -1;  // regions in / kept of the last call that ran it (bmh_last_dedup_stats), -1 = none yet
 	float dedup_ms = -1.f;                    // ... and the kernel's duration with kernel timing on, else -1
+	// mem_pestat's pair walk on the device (pestat_collect_kernel, pestat.hip): bmh_pestat_device, and with a switch on
+	// (bmh_ctx_set_pestat_collect, bmh_ctx_set_regs_drop_exact) the chains-to-regions calls behind their de-duplication
+	bool pestat_collect = false, regs_drop_exact = false;
+	bmh_sam_opt_t pestat_opt{};               // the options the collect switch was set with
+	DevBuf d_pestat;                          // bmh_pestat_device: offsets, counts, words, regions
+	hipEvent_t ev_pestat[2] = {};             // around the kernel (timing mode)
+	std::vector<uint32_t> pestat_cand;        // the words of the last successful collecting call (bmh_last_pestat_candidates)
+	long long pestat_pairs = -1;              // ... and its pair count, -1 = none yet
+	float pestat_ms = -1.f;                   // ... and the kernel's duration with kernel timing on, else -1
+	long long drop_exact_removed = -1;        // regions drop-exact removed in the last successful call that ran it (bmh_last_drop_exact_stats)
 	// pass A of phase 2 on the device (decide_kernel, decide.hip): bmh_decide_device, and bmh_sam_batch with the switch on
 	bool decide_device = false;               // bmh_ctx_set_decide_device
 	DevBuf d_decide;                          // a call's block: offsets, parameters, pair table, regions, outputs, scratch
@@ -441,6 +451,15 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
 // In timing mode ctx->ev_dedup are recorded around the kernel.
 int launch_region_dedup(bmh_ctx *ctx, bmh_alnreg_t *d_reg, const unsigned long long *d_off, unsigned long long *d_cnt, int n_reads,
                         unsigned long long total, float mask_level_redun, unsigned long long *d_removed, int *d_err);
+
+// mem_pestat's pair walk (host/pestat_core.h), one lane per pair p over the slices of reads 2p and 2p + 1 of reg (slices as above: the
+// counts decide, not the slice lengths); d_cand[p], n_reads / 2 words, receives the word (null: none wanted).  With drop_exact the lane
+// first applies mem_test_and_remove_exact (d_len[r] * match) to its slices -- the lone last read of an odd batch included --, rewrites
+// cnt[r] and adds what it removed to *removed; d_len and d_removed may be null without it.  A slice outside the array: BMH_E_ARG into
+// *err, nothing written.  In timing mode ctx->ev_pestat are recorded around the kernel.
+int launch_pestat_collect(bmh_ctx *ctx, bmh_alnreg_t *d_reg, const unsigned long long *d_off, unsigned long long *d_cnt, const int *d_len,
+                          int n_reads, unsigned long long total, const bmh_sam_opt_t &o, int64_t l_pac, int match, bool drop_exact, uint32_t *d_cand,
+                          unsigned long long *d_removed, int *d_err);
 
 int launch_region_orient(bmh_ctx *ctx, uint8_t *d_pool, size_t rpool_off, const bmh_region_req_t *d_reqs, int64_t n);
 int launch_region_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_region_req_t *d_reqs, int64_t n, const bmh_glb_task_t *d_tasks,

@@ -31,12 +31,13 @@
 #include "bmh_device.h"
 #include "../host/chain2aln_core.h"
 #include "../host/dedup_core.h"
+#include "../host/pestat_core.h"
 
 namespace bmh {
 
 enum { C2R_NEXT_CHAIN = 0, C2R_NEXT_SEED = 1, C2R_DONE = 2 };
 // status words (uint32 index).  0..3 are what the host reads in the loop
-enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_DEDUP_REMOVED = 12, C2R_STATUS_BYTES = 64 };
+enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_DEDUP_REMOVED = 12, C2R_DROP_REMOVED = 14, C2R_STATUS_BYTES = 64 };
 
 struct C2rChain { // one chain's record, 64 bytes
 	int64_t rmax0, rmax1;
@@ -75,6 +76,7 @@ struct C2rWs {
 	bmh_sw_result_t *swr;    // tc
 	bmh_alnreg_t *reg;       // ts: the region arena, read r's slice at soff[r]
 	unsigned long long *nreg, *roff; // n_reads + 1: regions per read, their exclusive sums
+	uint32_t *cand;          // n_reads / 2 + 1: mem_pestat's word per pair (pestat_collect_kernel), right behind roff: one copy brings both
 	bmh_alnreg_t *out;       // ts: the compact regions
 };
 
@@ -351,7 +353,7 @@ namespace {
 size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct C2rLayout {
-	size_t status, chn, state, srt, slot, tasks, res, swt, swr, reg, nreg, roff, out, total;
+	size_t status, chn, state, srt, slot, tasks, res, swt, swr, reg, nreg, roff, cand, out, total;
 	C2rLayout(size_t n, size_t tc, size_t ts)
 	{
 		size_t o = 0;
@@ -363,7 +365,8 @@ struct C2rLayout {
 		status = take(C2R_STATUS_BYTES), chn = take((tc + 1) * sizeof(C2rChain)), state = take(n * sizeof(C2rState)), srt = take(ts * 8);
 		slot = take(ts * 4), tasks = take(ts * sizeof(bmh_seed_task_t)), res = take(ts * sizeof(bmh_seed_result_t));
 		swt = take(tc * sizeof(bmh_sw_task_t)), swr = take(tc * sizeof(bmh_sw_result_t)), reg = take(ts * sizeof(bmh_alnreg_t));
-		nreg = take((n + 1) * 8), roff = take((n + 1) * 8), out = take(ts * sizeof(bmh_alnreg_t)), total = o;
+		nreg = take((n + 1) * 8), roff = take((n + 1) * 8 + (n / 2 + 1) * 4), cand = roff + (n + 1) * 8; // (the words share roff's block)
+		out = take(ts * sizeof(bmh_alnreg_t)), total = o;
 	}
 };
 
@@ -396,7 +399,8 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	uint8_t *d = (uint8_t *)ctx->d_c2r.p;
 	const C2rWs ws{(uint32_t *)(d + L.status), (C2rChain *)(d + L.chn), (C2rState *)(d + L.state), (uint64_t *)(d + L.srt), (uint32_t *)(d + L.slot),
 	               (bmh_seed_task_t *)(d + L.tasks), (bmh_seed_result_t *)(d + L.res), (bmh_sw_task_t *)(d + L.swt), (bmh_sw_result_t *)(d + L.swr),
-	               (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (bmh_alnreg_t *)(d + L.out)};
+	               (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (uint32_t *)(d + L.cand),
+	               (bmh_alnreg_t *)(d + L.out)};
 	const bmh_params_t &p = ctx->params;
 	const C2rSwRule sw{msl, ctx->dev.max_mat, ctx->wide_sw ? 1 : 0, sw_byte_gaps_wrap(p) ? 1 : 0};
 	const unsigned rb = (unsigned)((n + 63) / 64);
@@ -450,6 +454,12 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	if (dedup && (rc = launch_region_dedup(ctx, ws.reg, in.soff, ws.nreg, n, in.ts, ctx->regs_dedup_mask,
 	                                       (unsigned long long *)&ws.status[C2R_DEDUP_REMOVED], (int *)&ws.status[C2R_ERR])))
 		return rc;
+	// with either of its switches on: mem_test_and_remove_exact on the survivors, then mem_pestat's word per pair from what is left
+	const bool collect = ctx->pestat_collect, drop = ctx->regs_drop_exact;
+	if ((collect || drop) && (rc = launch_pestat_collect(ctx, ws.reg, in.soff, ws.nreg, in.len, n, in.ts, ctx->pestat_opt, l_pac, p.a, drop,
+	                                                     collect ? ws.cand : nullptr, (unsigned long long *)&ws.status[C2R_DROP_REMOVED],
+	                                                     (int *)&ws.status[C2R_ERR])))
+		return rc;
 	// gather: count -> scan -> place, then the counts and the compact records
 	hipLaunchKernelGGL(c2r_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long *)ws.nreg, n, ws.roff);
 	hipLaunchKernelGGL(c2r_place_kernel, dim3(rb), dim3(64), 0, s, in, ws);
@@ -457,8 +467,8 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, stream_wait(ctx, s));
-	unsigned long long tr, u64s[4], removed;
-	memcpy(&tr, h + 16, 8), memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&removed, h + C2R_DEDUP_REMOVED, 8);
+	unsigned long long tr, u64s[4], removed, dropped;
+	memcpy(&tr, h + 16, 8), memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&removed, h + C2R_DEDUP_REMOVED, 8), memcpy(&dropped, h + C2R_DROP_REMOVED, 8);
 	if (chains_in) *chains_in = (long long)u64s[3];
 	if ((int)h[C2R_ERR] || tr > in.ts) {
 		ctx->last_error = "chains to regions: the region counts are inconsistent";
@@ -467,36 +477,77 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	st->ext_tasks = (int64_t)u64s[0], st->seeds_extended = (int64_t)u64s[1], st->seeds_skipped = (int64_t)u64s[2];
 	st->seeds_speculated = (int64_t)n_tasks - st->seeds_extended; // extended on the device but never used
 	if (dedup) { // (the driver's statistics are about extensions and stay what they are without the switch)
-		ctx->dedup_in = (long long)(tr + removed), ctx->dedup_out = (long long)tr, ctx->dedup_ms = -1.f;
+		ctx->dedup_in = (long long)(tr + dropped + removed), ctx->dedup_out = (long long)(tr + dropped), ctx->dedup_ms = -1.f;
 		if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->dedup_ms, ctx->ev_dedup[0], ctx->ev_dedup[1]));
 	}
-	const size_t b_off = al256(((size_t)n + 1) * 8), b_reg = (size_t)tr * sizeof(bmh_alnreg_t);
+	float pestat_ms = -1.f;
+	if ((collect || drop) && ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&pestat_ms, ctx->ev_pestat[0], ctx->ev_pestat[1]));
+	const size_t b_roff = ((size_t)n + 1) * 8 + (collect ? ((size_t)n / 2) * 4 : 0); // the words lie right behind roff[]
+	const size_t b_off = al256(b_roff + 4), b_reg = (size_t)tr * sizeof(bmh_alnreg_t);
 	if ((rc = ensure_host(ctx, ctx->h_down, b_off + b_reg + 64))) return rc;
 	uint8_t *hb = (uint8_t *)ctx->h_down.p;
-	BMH_HIP(ctx, hipMemcpyAsync(hb, ws.roff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, hipMemcpyAsync(hb, ws.roff, b_roff, hipMemcpyDeviceToHost, s));
 	if (b_reg) BMH_HIP(ctx, hipMemcpyAsync(hb + b_off, ws.out, b_reg, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, stream_wait(ctx, s));
 	const unsigned long long *roff = (const unsigned long long *)hb;
 	const bmh_alnreg_t *ra = (const bmh_alnreg_t *)(hb + b_off);
+	// gives back the arrays of reads [0, upto) -- those this call made, not what a caller left in the .a of a read without regions
+	auto undo = [&](int upto) {
+		for (int q = 0; q < upto; ++q)
+			if (roff[q + 1] > roff[q]) free(regs[q].a), regs[q].a = nullptr, regs[q].n = regs[q].m = 0;
+	};
 	for (int r = 0; r < n; ++r) {
 		const size_t k = (size_t)(roff[r + 1] - roff[r]);
 		if (!k) continue;
 		bmh_alnreg_t *a = (bmh_alnreg_t *)malloc(k * sizeof(bmh_alnreg_t));
 		if (!a) {
-			for (int q = 0; q < r; ++q) free(regs[q].a), regs[q].a = nullptr, regs[q].n = regs[q].m = 0;
+			undo(r);
 			ctx->last_error = "chains to regions: out of host memory for the regions";
 			return BMH_E_NOMEM;
 		}
 		memcpy(a, ra + roff[r], k * sizeof(bmh_alnreg_t));
 		regs[r].a = a, regs[r].n = regs[r].m = k;
 	}
+	if (collect) { // of a successful call only (bmh_last_pestat_candidates)
+		const uint32_t *w = (const uint32_t *)(hb + ((size_t)n + 1) * 8);
+		try {
+			ctx->pestat_cand.assign(w, w + n / 2);
+		} catch (const std::bad_alloc &) {
+			undo(n);
+			ctx->last_error = "chains to regions: out of host memory for the insert-size words";
+			return BMH_E_NOMEM;
+		}
+		ctx->pestat_pairs = n / 2, ctx->pestat_ms = pestat_ms;
+	}
+	if (drop) ctx->drop_exact_removed = (long long)dropped;
 	return BMH_OK;
+}
+
+// a successful call without reads ran no kernel: what the switches report of "the last successful call" is that of an empty batch
+void c2r_empty(bmh_ctx *ctx)
+{
+	if (ctx->pestat_collect) ctx->pestat_cand.clear(), ctx->pestat_pairs = 0, ctx->pestat_ms = -1.f;
+	if (ctx->regs_drop_exact) ctx->drop_exact_removed = 0;
 }
 
 int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads, int min_seed_len, const bmh_alnreg_v *regs, const char *who)
 {
 	if (!ctx || n_reads < 0 || l_pac < 0 || min_seed_len < 0 || (n_reads > 0 && (!reads || !regs))) return BMH_E_ARG;
 	if (!ctx->have_params) return BMH_E_ARG;
+	// the two switches behind the de-duplication (pestat.hip): refused here, before anything is enqueued; the switches stay as set
+	if ((ctx->pestat_collect || ctx->regs_drop_exact) && !ctx->regs_dedup) {
+		ctx->last_error = std::string(who) + ": " + (ctx->pestat_collect ? "bmh_ctx_set_pestat_collect" : "bmh_ctx_set_regs_drop_exact") +
+		                  " is on, which needs bmh_ctx_set_regs_dedup on: both run on the regions mem_sort_and_dedup leaves";
+		return BMH_E_ARG;
+	}
+	if (ctx->pestat_collect && (n_reads & 1)) {
+		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on and n_reads is odd: reads 2p and 2p+1 are mates";
+		return BMH_E_ARG;
+	}
+	if (ctx->pestat_collect && ctx->pestat_opt.max_ins > BMH_PS_MAX_INS) {
+		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on with max_ins >= 2^30, which the word cannot hold";
+		return BMH_E_RANGE;
+	}
 	if (!ctx->dev.pac || ctx->dev.l_pac != l_pac) {
 		ctx->last_error = std::string(who) + ": needs the 2-bit reference of this l_pac resident on the device (bmh_ctx_set_pac)";
 		return BMH_E_ARG;
@@ -550,7 +601,10 @@ int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh
 	if (n_reads > 0 && !chains) return BMH_E_ARG;
 	bmh_driver_stats_t st{};
 	ctx->dstats = st;
-	if (n_reads == 0) return BMH_OK;
+	if (n_reads == 0) {
+		c2r_empty(ctx);
+		return BMH_OK;
+	}
 	// the compact form of the chains (empty chains do nothing in the reference's loop and are left out), and the reads
 	size_t tc = 0, ts = 0, bytes = 0;
 	int lmax = 1;
@@ -620,6 +674,7 @@ int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bm
 	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
 	FusedArgs u{co, l_pac, lmax, min_seed_len, regs, &st};
 	rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
+	if (!rc && n_reads == 0) c2r_empty(ctx);
 	ctx->dstats = st;
 	return rc;
 }

@@ -18,6 +18,9 @@
  * After it the host sorts and de-duplicates each read's regions (bmh_sort_and_dedup) -- or, with
  *   BMH_DEDUP_DEVICE=1   (needs BMH_REGS_DEVICE=1) the same call does that on the device before the regions come down
  *                        (bmh_ctx_set_regs_dedup) and phase 1 makes no host bmh_sort_and_dedup call.
+ *   BMH_PESTAT_DEVICE=1  (needs the two above) behind that, the same call answers mem_pestat's question per pair (bmh_ctx_set_pestat_collect)
+ *                        and under -e applies mem_test_and_remove_exact (bmh_ctx_set_regs_drop_exact): a paired-end chunk's serial
+ *                        section is bmh_pestat_from_candidates over four bytes per pair, not bmh_pestat over the region vectors.
  * Mate rescue (bmh_matesw_batch per slice of the chunk) has a switch of its own:
  *   BMH_MATESW_DEVICE=1  mate rescue's driver (planning, folding, mem_sort_and_dedup) as kernels, bmh_matesw_device(): no host
  *                        callback, 16 bytes per round back.  Needs BMH_PAC_RESIDENT not 0; independent of BMH_REGS_DEVICE.
@@ -384,6 +387,17 @@ __attribute__((constructor)) static void qa_check_dedup_device_env(void)
 	}
 }
 
+/* BMH_PESTAT_DEVICE=1 takes mem_pestat's pair walk from the kernel behind the device's de-duplication, so it means nothing without
+ * BMH_REGS_DEVICE=1 and BMH_DEDUP_DEVICE=1.  Checked like the two above. */
+__attribute__((constructor)) static void qa_check_pestat_device_env(void)
+{
+	const char *p = getenv("BMH_PESTAT_DEVICE"), *d = getenv("BMH_DEDUP_DEVICE"), *e = getenv("BMH_REGS_DEVICE");
+	if (p && p[0] && strcmp(p, "0") != 0 && !(d && d[0] && strcmp(d, "0") != 0 && e && e[0] && strcmp(e, "0") != 0)) {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_PESTAT_DEVICE=1 collects insert-size candidates behind the device's de-duplication: it needs BMH_REGS_DEVICE=1 and BMH_DEDUP_DEVICE=1\n");
+		exit(1);
+	}
+}
+
 /* BMH_MATESW_DEVICE=1 rescues mates against the reference resident on the device, so BMH_PAC_RESIDENT=0 contradicts it as well.
  * Checked like the two above; it does not depend on BMH_REGS_DEVICE. */
 __attribute__((constructor)) static void qa_check_matesw_device_env(void)
@@ -523,6 +537,20 @@ static int qa_dedup_device(void)
 }
 static long long g_dedup_cnt[3]; /* regions de-duplicated on the device, regions kept, host bmh_sort_and_dedup calls of phase 1 */
 
+/* BMH_PESTAT_DEVICE=1 (with the two above): mem_pestat's pair walk as a kernel behind the de-duplication (bmh_ctx_set_pestat_collect),
+ * and under -e mem_test_and_remove_exact with it (bmh_ctx_set_regs_drop_exact); the chunk's serial section is then
+ * bmh_pestat_from_candidates over a flat array of words */
+static int qa_pestat_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_PESTAT_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0 && qa_dedup_device();
+	}
+	return on;
+}
+static long long g_pes_removed; /* this chunk: exact matches removed on the device */
+
 /* BMH_CHAIN_DEVICE=1 (implied by BMH_REGS_DEVICE=1): chaining on the device, fused with seeding (bmh_seed_chain_batch); unset or 0:
  * bmh_chain_reads on the host */
 static int qa_chain_device(void)
@@ -537,8 +565,10 @@ static int qa_chain_device(void)
 
 /* (a static body behind both exported names: inside a process that also holds the reference's own definitions -- the tests load
  * libbwa_ref.so next to this library -- a call through the exported name would bind to whichever was loaded first) */
+/* cand (nullable, with pso): the chunk's insert-size words; the batch starts at an even read, holds an even number of reads and
+ * leaves the words of its pairs at cand[start / 2 ...] (BMH_PESTAT_DEVICE=1, mem_process_seqs below) */
 static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, const ref_bntseq_head_t *bns,
-                                 const uint8_t *pac, ref_bseq1_t *seqs, int start, int batch_size)
+                                 const uint8_t *pac, ref_bseq1_t *seqs, int start, int batch_size, uint32_t *cand, const bmh_sam_opt_t *pso)
 {
 	bmh_chain_v *chn = (bmh_chain_v *)malloc(sizeof(bmh_chain_v) * (size_t)batch_size);
 	bmh_alnreg_v *regs = (bmh_alnreg_v *)calloc((size_t)batch_size, sizeof(bmh_alnreg_v));
@@ -547,6 +577,8 @@ static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, cons
 	bmh_ctx_t *ctx;
 	double tq[6];
 	int b, i, rc;
+	const int collect = cand != 0 && qa_regs_device();
+	const int drop_dev = collect && (opt->flag & REF_MEM_F_NO_EXACT) != 0; /* mem_test_and_remove_exact behind the same kernel */
 
 	for (b = 0; b < batch_size; ++b) { /* bwamem.c:1093-1094 */
 		ref_bseq1_t *s = &seqs[start + b];
@@ -569,7 +601,15 @@ static bmh_alnreg_v *align_batch(const ref_mem_opt_t *opt, const void *bwt, cons
 		qa_seed_setup(ctx, opt, (const ref_bwt_t *)bwt, &so);
 		qa_chain_opt(opt, &co);
 		if ((rc = bmh_ctx_set_regs_dedup(ctx, qa_dedup_device(), opt->mask_level_redun))) bmh_tls_die(bmh_last_error(ctx), rc); /* bwamem.c:1114 behind the call */
+		/* (contexts are pooled: both switches are set on every call, on or off) */
+		if ((rc = bmh_ctx_set_pestat_collect(ctx, collect, pso)) || (rc = bmh_ctx_set_regs_drop_exact(ctx, drop_dev))) bmh_tls_die(bmh_last_error(ctx), rc);
 		if ((rc = bmh_seed_chain_regs_batch(ctx, &so, &co, bns->l_pac, batch_size, reads, opt->min_seed_len, regs))) bmh_tls_die(bmh_last_error(ctx), rc);
+		if (collect && (rc = bmh_last_pestat_candidates(ctx, cand + (start >> 1), batch_size >> 1, 0))) bmh_tls_die(bmh_last_error(ctx), rc);
+		if (drop_dev) {
+			int64_t gone = 0;
+			bmh_last_drop_exact_stats(ctx, &gone);
+			__sync_fetch_and_add(&g_pes_removed, (long long)gone);
+		}
 		if (qa_dedup_device()) {
 			int64_t din = 0, dout = 0;
 			bmh_last_dedup_stats(ctx, &din, &dout, 0);
@@ -649,7 +689,7 @@ folded:
 			regs[b].n = (size_t)bmh_sort_and_dedup((int)regs[b].n, regs[b].a, opt->mask_level_redun); /* bwamem.c:1114 */
 			__sync_fetch_and_add(&g_dedup_cnt[2], 1);
 		}
-		if ((opt->flag & REF_MEM_F_NO_EXACT) && regs[b].n && regs[b].a[0].truesc == seqs[start + b].l_seq * opt->a) { /* mem_test_and_remove_exact, bwamem.c:438-443 */
+		if (!drop_dev && (opt->flag & REF_MEM_F_NO_EXACT) && regs[b].n && regs[b].a[0].truesc == seqs[start + b].l_seq * opt->a) { /* mem_test_and_remove_exact, bwamem.c:438-443 */
 			memmove(regs[b].a, regs[b].a + 1, (regs[b].n - 1) * sizeof(bmh_alnreg_t));
 			--regs[b].n;
 		}
@@ -662,7 +702,7 @@ folded:
 bmh_alnreg_v *mem_align1_core_batched(const ref_mem_opt_t *opt, const void *bwt, const ref_bntseq_head_t *bns,
                                       const uint8_t *pac, ref_bseq1_t *seqs, int start, int batch_size)
 {
-	return align_batch(opt, bwt, bns, pac, seqs, start, batch_size);
+	return align_batch(opt, bwt, bns, pac, seqs, start, batch_size, 0, 0);
 }
 
 /* mem_align1_core() with the reference's exact signature (bwamem.c:1122-1149; used by mem_align1 :1151 and example.c:44): one
@@ -675,7 +715,7 @@ bmh_alnreg_v mem_align1_core(const ref_mem_opt_t *opt, const void *bwt, const re
 	bmh_alnreg_v *v, out;
 	memset(&one, 0, sizeof(one));
 	one.l_seq = l_seq, one.seq = seq;
-	v = align_batch(opt, bwt, bns, pac, &one, 0, 1);
+	v = align_batch(opt, bwt, bns, pac, &one, 0, 1, 0, 0);
 	out = v[0];
 	free(v);
 	return out;
@@ -707,12 +747,14 @@ typedef struct {
 	const uint8_t *pac;
 	ref_bseq1_t *seqs;
 	bmh_alnreg_v *regs;
+	uint32_t *cand; /* BMH_PESTAT_DEVICE=1 and the chunk qualifies: its insert-size words, one per pair; else null */
+	const bmh_sam_opt_t *sopt;
 } qa_worker_t;
 
 static void qa_worker1_batched(void *data, int start, int batch_size, int tid) /* == worker1_batched, bwamem.c:1264-1279 */
 {
 	qa_worker_t *w = (qa_worker_t *)data;
-	bmh_alnreg_v *ret = align_batch(w->opt, w->bwt, w->bns, w->pac, w->seqs, start, batch_size);
+	bmh_alnreg_v *ret = align_batch(w->opt, w->bwt, w->bns, w->pac, w->seqs, start, batch_size, w->cand, w->sopt);
 	int i;
 	(void)tid;
 	for (i = start; i < start + batch_size; ++i) w->regs[i] = ret[i - start];
@@ -879,13 +921,28 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	bmh_read_t *reads;
 	qa_slice_job_t J;
 	double ctime, rtime, t_[4], t_pes;
-	int i, nt2;
+	const char *why_host = 0; /* BMH_PESTAT_DEVICE=1: why this chunk keeps the host's bmh_pestat, or null */
+	int i, nt2, n_host_pestat = 0, p1_batch[2] = {0, 0}; /* phase 1's batch size: as evened out, and as run */
 	ctime = cputime(), rtime = realtime();
 	t_[0] = rtime;
 	if (n_processed == 0 && g_t_loaded > 0 && getenv("BMH_VERBOSE"))
 		fprintf(stderr, "[bwamem_hip] the first chunk starts %.3f s after the shim was loaded\n", rtime - g_t_loaded);
 	w.opt = opt, w.bwt = bwt, w.bns = bns, w.pac = pac, w.seqs = seqs;
 	w.regs = (bmh_alnreg_v *)malloc((size_t)n * sizeof(bmh_alnreg_v));
+	memset(&so, 0, sizeof(so)); /* the fields of mem_opt_t phase 2 (and mem_pestat's pair walk in phase 1) reads */
+	so.a = opt->a, so.b = opt->b, so.o_del = opt->o_del, so.e_del = opt->e_del, so.o_ins = opt->o_ins, so.e_ins = opt->e_ins;
+	so.pen_unpaired = opt->pen_unpaired, so.w = opt->w, so.T = opt->T, so.flag = opt->flag, so.min_seed_len = opt->min_seed_len;
+	so.max_ins = opt->max_ins, so.mapQ_coef_fac = opt->mapQ_coef_fac, so.max_matesw = opt->max_matesw, so.mask_level = opt->mask_level;
+	so.mask_level_redun = opt->mask_level_redun, so.mapQ_coef_len = opt->mapQ_coef_len;
+	memcpy(so.mat, opt->mat, 25);
+	w.cand = 0, w.sopt = &so;
+	g_pes_removed = 0;
+	if (qa_pestat_device()) { /* the pair walk in phase 1: a paired-end chunk whose statistics are not given, in batches that split no pair */
+		const int odd_exact = getenv("BMH_BATCH_EXACT") && ((opt->batch_size > 0 ? opt->batch_size : 1) & 1);
+		why_host = !pe ? "single-end reads" : pes0 ? "the insert-size statistics are given" : (n & 1) ? "an odd number of reads" : n < 2 ? "no pair"
+		           : odd_exact ? "BMH_BATCH_EXACT=1 with an odd batch size" : opt->max_ins >= (1 << 30) ? "max_ins >= 2^30" : 0;
+		if (!why_host && !(w.cand = (uint32_t *)calloc((size_t)(n >> 1), sizeof(uint32_t)))) bmh_tls_die("out of memory for the insert-size words", BMH_E_NOMEM);
+	}
 	{ /* bwamem.c:1313, with the batch size evened out: -b 65536 cuts a chunk of 1 066 668 reads into 16 batches and a 17th
 	   * of 18 092 that one thread runs alone after all others are done; the same reads in 16 batches of 66 667 are not a
 	   * read slower per batch.  As many batches as -b asks for, rounded to a multiple of the thread count, at least 4 096
@@ -899,18 +956,18 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 			if ((int64_t)n / nb < 4096) nb = ((int64_t)n + 4095) / 4096;
 			b = (int)(((int64_t)n + nb - 1) / nb);
 		}
+		p1_batch[0] = b;
+		if (w.cand && (b & 1)) ++b; /* no pair straddles two batches; reads are independent, so the regions do not change */
+		p1_batch[1] = b;
 		kt_for_batch(nt, qa_worker1_batched, &w, n, b);
 	}
 	t_[1] = realtime();
-	memset(&so, 0, sizeof(so)); /* the fields of mem_opt_t phase 2 reads */
-	so.a = opt->a, so.b = opt->b, so.o_del = opt->o_del, so.e_del = opt->e_del, so.o_ins = opt->o_ins, so.e_ins = opt->e_ins;
-	so.pen_unpaired = opt->pen_unpaired, so.w = opt->w, so.T = opt->T, so.flag = opt->flag, so.min_seed_len = opt->min_seed_len;
-	so.max_ins = opt->max_ins, so.mapQ_coef_fac = opt->mapQ_coef_fac, so.max_matesw = opt->max_matesw, so.mask_level = opt->mask_level;
-	so.mask_level_redun = opt->mask_level_redun, so.mapQ_coef_len = opt->mapQ_coef_len;
-	memcpy(so.mat, opt->mat, 25);
 	if (pe) {                                                                /* bwamem.c:1314-1317 */
 		if (pes0) memcpy(pes, pes0, 4 * sizeof(bmh_pestat_t));
-		else bmh_pestat(&so, bns->l_pac, n, w.regs, pes, bwa_verbose);
+		else if (w.cand) { /* the words came down with the regions: what is left of mem_pestat is a pass over a flat array */
+			int rc = bmh_pestat_from_candidates(&so, n >> 1, w.cand, pes, bwa_verbose);
+			if (rc) bmh_tls_die("the device's insert-size words are inconsistent", rc);
+		} else bmh_pestat(&so, bns->l_pac, n, w.regs, pes, bwa_verbose), ++n_host_pestat;
 	}
 	t_pes = realtime();
 	/* reads are base codes by now (bwamem.c:1093-1094) */
@@ -971,6 +1028,18 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		if (qa_dedup_device())
 			fprintf(stderr, "[bwamem_hip] region de-duplication so far: %lld regions de-duplicated on the device, %lld kept, %lld host bmh_sort_and_dedup calls in phase 1\n",
 			        g_dedup_cnt[0], g_dedup_cnt[1], g_dedup_cnt[2]);
+		if (qa_pestat_device()) {
+			if (w.cand) {
+				long long nc = 0;
+				for (i = 0; i < n >> 1; ++i) nc += w.cand[i] != 0;
+				fprintf(stderr, "[bwamem_hip] insert-size candidates from the device: %d pairs, %lld candidates, %lld exact matches removed on the device, %d host bmh_pestat calls\n",
+				        n >> 1, nc, g_pes_removed, n_host_pestat);
+				fprintf(stderr, "[bwamem_hip] insert-size candidates from the device: %d phase-1 batches of up to %d reads (evened out to %d%s)\n",
+				        (n + p1_batch[1] - 1) / p1_batch[1], p1_batch[1], p1_batch[0],
+				        p1_batch[1] != p1_batch[0] ? ", rounded up to an even number so that no pair straddles two batches" : "");
+			} else
+				fprintf(stderr, "[bwamem_hip] insert-size candidates from the device: off for this chunk (%s), %d host bmh_pestat calls\n", why_host, n_host_pestat);
+		}
 		if (rescue) fprintf(stderr, "[bwamem_hip] mate rescue driver so far: %.3f thread-s in %s\n", g_msw_us * 1e-6, qa_matesw_device() ? "bmh_matesw_device" : "bmh_matesw_batch");
 		fprintf(stderr, "[bwamem_hip] phase 2 thread-seconds so far: wait %.3f, bmh_sam_batch %.3f\n", g_sam_us[0] * 1e-6, g_sam_us[1] * 1e-6);
 		if (qa_decide_device())
@@ -995,6 +1064,7 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		        t_[1] - t_[0], t_pes - t_[1], t_[2] - t_pes, t_[3] - t_[2]);
 	}
 	free(w.regs);
+	free(w.cand);
 	if (bwa_verbose >= 3)
 		fprintf(stderr, "[M::%s] Processed %d reads in %.3f CPU sec, %.3f real sec\n", __func__, n, cputime() - ctime, realtime() - rtime);
 }

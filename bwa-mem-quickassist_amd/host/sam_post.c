@@ -29,6 +29,7 @@
 
 #include "../../include/bwamem_hip.h"
 #include "dedup_core.h"
+#include "pestat_core.h"
 #include "postproc_core.h"
 #include "regplan_core.h"
 #include "samtext_core.h"
@@ -43,15 +44,11 @@ static double now_s(void) /* the clock of the BMH_DRIVER_TRACE lines: wall time,
 	return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-#define MIN_RATIO 0.8 /* bwamem_pair.c:14-18 */
-#define MIN_DIR_CNT 10
+#define MIN_DIR_CNT 10 /* bwamem_pair.c:15-18; MIN_RATIO (:14) is pestat_core.h's */
 #define MIN_DIR_RATIO 0.05
 #define OUTLIER_BOUND 2.0
 #define MAPPING_BOUND 3.0
 #define MAX_STDDEV 4.0
-
-static inline int imin(int a, int b) { return a < b ? a : b; }
-static inline int imax(int a, int b) { return a > b ? a : b; }
 
 /* ---- orders (utils.c:45); those of mem_sort_and_dedup are in dedup_core.h, those of marking and pairing in postproc_core.h */
 static int lt_u64(const void *x, const void *y) { return *(const uint64_t *)x < *(const uint64_t *)y; }
@@ -100,53 +97,22 @@ void bmh_mark_primary_se(const bmh_sam_opt_t *o, int n, bmh_alnreg_t *a, int64_t
 /* ---- bwamem.c:1023-1047 */
 int bmh_approx_mapq_se(const bmh_sam_opt_t *o, const bmh_alnreg_t *a) { return bmh_pp_mapq(o, a, 0); }
 
-/* ---- bwamem_pair.c:34-44 */
-static int cal_sub(const bmh_sam_opt_t *o, const bmh_alnreg_v *r)
-{
-	size_t j;
-	for (j = 1; j < r->n; ++j) {
-		const int b_max = imax(r->a[j].qb, r->a[0].qb), e_min = imin(r->a[j].qe, r->a[0].qe);
-		if (e_min > b_max) {
-			const int min_l = imin(r->a[j].qe - r->a[j].qb, r->a[0].qe - r->a[0].qb);
-			if (e_min - b_max >= min_l * o->mask_level) break;
-		}
-	}
-	return j < r->n ? r->a[j].score : o->min_seed_len * o->a;
-}
+/* ---- bwamem_pair.c:46-107 in two halves.  The pair walk (:56-72) is pestat_core.h's, shared with the device kernel; the
+ * statistics below it are host only: they are cheap, and their two sums are added in ascending order in double. */
 
-/* ---- bwamem_pair.c:46-107 */
-void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, bmh_pestat_t pes[4], int verbose)
+/* bwamem_pair.c:73-106 over the candidates of each orientation, q[d][0..qn[d]) */
+static void pestat_finish(const bmh_sam_opt_t *o, uint64_t *const qv[4], const size_t qnv[4], bmh_pestat_t pes[4], int verbose)
 {
-	struct { size_t n, m; uint64_t *a; } isize[4];
 	size_t max;
-	int i, d;
+	int d;
 	memset(pes, 0, 4 * sizeof(bmh_pestat_t));
-	memset(isize, 0, sizeof(isize));
-	for (i = 0; i < n >> 1; ++i) {
-		const bmh_alnreg_v *r0 = &regs[i << 1 | 0], *r1 = &regs[i << 1 | 1];
-		int64_t is;
-		int dir;
-		if (i + 8 < n >> 1) /* every read's region vector is an allocation of its own: this serial loop is all cache misses */
-			__builtin_prefetch(regs[(i + 8) << 1].a), __builtin_prefetch(regs[(i + 8) << 1 | 1].a);
-		if (r0->n == 0 || r1->n == 0) continue;
-		if (cal_sub(o, r0) > MIN_RATIO * r0->a[0].score) continue;
-		if (cal_sub(o, r1) > MIN_RATIO * r1->a[0].score) continue;
-		dir = bmh_pp_infer_dir(l_pac, r0->a[0].rb, r1->a[0].rb, &is);
-		if (is && is <= o->max_ins) {
-			if (isize[dir].n == isize[dir].m) {
-				isize[dir].m = isize[dir].m ? isize[dir].m << 1 : 2;
-				isize[dir].a = (uint64_t *)realloc(isize[dir].a, 8 * isize[dir].m);
-			}
-			isize[dir].a[isize[dir].n++] = (uint64_t)is;
-		}
-	}
 	if (verbose >= 3)
-		fprintf(stderr, "[M::mem_pestat] # candidate unique pairs for (FF, FR, RF, RR): (%ld, %ld, %ld, %ld)\n", (long)isize[0].n, (long)isize[1].n,
-		        (long)isize[2].n, (long)isize[3].n);
+		fprintf(stderr, "[M::mem_pestat] # candidate unique pairs for (FF, FR, RF, RR): (%ld, %ld, %ld, %ld)\n", (long)qnv[0], (long)qnv[1], (long)qnv[2],
+		        (long)qnv[3]);
 	for (d = 0; d < 4; ++d) {
 		bmh_pestat_t *r = &pes[d];
-		uint64_t *q = isize[d].a;
-		const size_t qn = isize[d].n;
+		uint64_t *q = qv[d];
+		const size_t qn = qnv[d];
 		size_t k;
 		int p25, p50, p75, x;
 		if (qn < MIN_DIR_CNT) {
@@ -179,14 +145,93 @@ void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v
 		if (r->low < 1) r->low = 1;
 		if (verbose >= 0) fprintf(stderr, "[M::mem_pestat] low and high boundaries for proper pairs: (%d, %d)\n", r->low, r->high);
 	}
-	for (d = 0, max = 0; d < 4; ++d) max = max > isize[d].n ? max : isize[d].n;
-	for (d = 0; d < 4; ++d) {
-		if (pes[d].failed == 0 && isize[d].n < max * MIN_DIR_RATIO) {
+	for (d = 0, max = 0; d < 4; ++d) max = max > qnv[d] ? max : qnv[d];
+	for (d = 0; d < 4; ++d)
+		if (pes[d].failed == 0 && qnv[d] < max * MIN_DIR_RATIO) {
 			pes[d].failed = 1;
 			if (verbose >= 0) fprintf(stderr, "[M::mem_pestat] skip orientation %c%c\n", "FR"[d >> 1 & 1], "FR"[d & 1]);
 		}
-		free(isize[d].a);
+}
+
+/* one array for the four orientations' candidates, cnt[d] of them each; q[d] = where orientation d's start.  0 = out of memory */
+static uint64_t *pestat_split(const size_t cnt[4], uint64_t *q[4])
+{
+	uint64_t *buf = (uint64_t *)malloc(8 * (cnt[0] + cnt[1] + cnt[2] + cnt[3] + 1));
+	if (buf) q[0] = buf, q[1] = q[0] + cnt[0], q[2] = q[1] + cnt[1], q[3] = q[2] + cnt[2];
+	return buf;
+}
+
+/* the pair walk, bwamem_pair.c:56-72, over np pairs: the one loop behind bmh_pestat_candidates (w32: the words) and bmh_pestat (w64:
+ * dir << 62 | is, which holds any max_ins).  Exactly one of w32, w64 is given. */
+static void pestat_walk(const bmh_sam_opt_t *o, int64_t l_pac, size_t np, const bmh_alnreg_v *regs, uint32_t *w32, uint64_t *w64)
+{
+	size_t i;
+	for (i = 0; i < np; ++i) {
+		const bmh_alnreg_v *r0 = &regs[i << 1 | 0], *r1 = &regs[i << 1 | 1];
+		int64_t is = 0;
+		int dir;
+		if (i + 8 < np) /* every read's region vector is an allocation of its own: this serial loop is all cache misses */
+			__builtin_prefetch(regs[(i + 8) << 1].a), __builtin_prefetch(regs[(i + 8) << 1 | 1].a);
+		dir = bmh_ps_pair(o, l_pac, r0->a, r0->n, r1->a, r1->n, &is);
+		if (w32) w32[i] = dir < 0 ? 0 : (uint32_t)dir << 30 | (uint32_t)is; /* == bmh_ps_candidate */
+		else w64[i] = dir < 0 ? 0 : (uint64_t)dir << 62 | (uint64_t)is;
 	}
+}
+
+int bmh_pestat_candidates(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, uint32_t *cand)
+{
+	int i;
+	if (!o || l_pac < 0 || n < 0 || (n > 0 && !regs) || (n > 1 && !cand)) return BMH_E_ARG;
+	if (o->max_ins > BMH_PS_MAX_INS) return BMH_E_RANGE;
+	for (i = 0; i < (n & ~1); ++i)
+		if (regs[i].n && !regs[i].a) return BMH_E_ARG;
+	pestat_walk(o, l_pac, (size_t)(n >> 1), regs, cand, 0);
+	return BMH_OK;
+}
+
+int bmh_pestat_from_candidates(const bmh_sam_opt_t *o, int64_t n_pairs, const uint32_t *cand, bmh_pestat_t pes[4], int verbose)
+{
+	size_t cnt[4] = {0, 0, 0, 0}, at[4] = {0, 0, 0, 0};
+	uint64_t *q[4], *buf;
+	int64_t i;
+	if (!o || n_pairs < 0 || (n_pairs > 0 && !cand) || !pes) return BMH_E_ARG;
+	if (o->max_ins > BMH_PS_MAX_INS) return BMH_E_RANGE;
+	for (i = 0; i < n_pairs; ++i) {
+		if (!cand[i]) continue;
+		if (BMH_PS_IS(cand[i]) == 0 || BMH_PS_IS(cand[i]) > o->max_ins) return BMH_E_ARG; /* no word of bmh_ps_candidate; pes is as it came */
+		++cnt[BMH_PS_DIR(cand[i])];
+	}
+	if (!(buf = pestat_split(cnt, q))) return BMH_E_NOMEM;
+	for (i = 0; i < n_pairs; ++i)
+		if (cand[i]) q[BMH_PS_DIR(cand[i])][at[BMH_PS_DIR(cand[i])]++] = (uint64_t)BMH_PS_IS(cand[i]);
+	pestat_finish(o, q, cnt, pes, verbose);
+	free(buf);
+	return BMH_OK;
+}
+
+/* candidates, then finish.  The candidates are kept as 64-bit values (dir << 62 | is), so any max_ins is served */
+void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, bmh_pestat_t pes[4], int verbose)
+{
+	const size_t np = n > 0 ? (size_t)(n >> 1) : 0;
+	size_t cnt[4] = {0, 0, 0, 0}, at[4] = {0, 0, 0, 0}, i;
+	uint64_t *v = (uint64_t *)malloc(8 * (np + 1)), *q[4], *buf = 0;
+	if (v) pestat_walk(o, l_pac, np, regs, 0, v);
+	for (i = 0; v && i < np; ++i)
+		if (v[i]) ++cnt[v[i] >> 62];
+	/* Out of memory: the reference aborts when its vectors cannot grow; a void routine can only say it, so it prints a message and
+	 * marks all four orientations as failed (pairing then goes without insert-size windows).  No test reaches this branch. */
+	if (!v || !(buf = pestat_split(cnt, q))) {
+		fprintf(stderr, "[bwamem_hip] bmh_pestat: out of memory, every orientation is marked as failed\n");
+		memset(pes, 0, 4 * sizeof(bmh_pestat_t));
+		pes[0].failed = pes[1].failed = pes[2].failed = pes[3].failed = 1;
+		free(v);
+		return;
+	}
+	for (i = 0; i < np; ++i)
+		if (v[i]) q[v[i] >> 62][at[v[i] >> 62]++] = v[i] & ~(3ull << 62);
+	free(v);
+	pestat_finish(o, q, cnt, pes, verbose);
+	free(buf);
 }
 
 /* ---- bwamem_pair.c:177-238: the routine is postproc_core.h's; here its key vector and range stack */

@@ -606,8 +606,20 @@ int bmh_sort_and_dedup(int n, bmh_alnreg_t *a, float mask_level_redun);         
 void bmh_mark_primary_se(const bmh_sam_opt_t *o, int n, bmh_alnreg_t *a, int64_t id);         /* mem_mark_primary_se */
 int bmh_approx_mapq_se(const bmh_sam_opt_t *o, const bmh_alnreg_t *a);                         /* mem_approx_mapq_se  */
 /* (the three above and bmh_pair below as one batch call, on the host or the device: bmh_decide_batch / bmh_decide_device) */
-/* mem_pestat; with verbose >= 3 it prints the reference's "[M::mem_pestat] ..." lines to stderr */
+/* mem_pestat; with verbose >= 3 it prints the reference's "[M::mem_pestat] ..." lines to stderr.  Out of host memory (where the
+ * reference aborts) it prints a "[bwamem_hip]" message and marks all four orientations as failed. */
 void bmh_pestat(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, bmh_pestat_t pes[4], int verbose);
+/* mem_pestat in its two halves; bmh_pestat equals the first followed by the second, field for field and in its stderr text.
+ * bmh_pestat_candidates: the pair walk (bwamem_pair.c:56-72, the text of host/pestat_core.h) over n reads, reads 2p and 2p+1 being
+ * mates (an odd n ignores the last read); cand[p], n/2 words, is 0 where pair p is no candidate and orientation << 30 | insert size
+ * where it is (1 <= insert size <= o->max_ins, so a candidate's word is never 0).  On the device: bmh_pestat_device, and
+ * bmh_ctx_set_pestat_collect behind the chains-to-regions calls.
+ * bmh_pestat_from_candidates: the statistics (:73-106) from such words.  A word whose insert size is 0 or above o->max_ins is
+ * refused with BMH_E_ARG and pes is left untouched.
+ * Both: BMH_E_ARG for a NULL argument or a negative size, BMH_E_RANGE for o->max_ins >= 2^30 (the word cannot hold it; bmh_pestat
+ * serves such a value). */
+int bmh_pestat_candidates(const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, uint32_t *cand);
+int bmh_pestat_from_candidates(const bmh_sam_opt_t *o, int64_t n_pairs, const uint32_t *cand, bmh_pestat_t pes[4], int verbose);
 /* mem_pair (bwamem_pair.c:177-238): the best-scoring properly oriented pair of hits of the two ends; returns its score
  * (0 = none), *sub / *n_sub the runner-up and how many lie within one event of it, z[] the chosen hit of each end */
 int bmh_pair(const bmh_sam_opt_t *o, int64_t l_pac, const bmh_pestat_t pes[4], const bmh_alnreg_v a[2], uint64_t id, int *sub,
@@ -1026,6 +1038,35 @@ int bmh_ctx_set_regs_dedup(bmh_ctx_t *ctx, int on, float mask_level_redun);
  * on): regions in, regions kept, and the kernel's milliseconds with bmh_set_kernel_timing on (else -1).  -1 each before the first such
  * call.  Any of the three pointers may be NULL. */
 int bmh_last_dedup_stats(const bmh_ctx_t *ctx, int64_t *regions_in, int64_t *regions_out, float *kernel_ms);
+
+/* ---- mem_pestat's pair walk on the device (reference bwamem_pair.c:46-72): the text of bmh_pestat_candidates (host/pestat_core.h)
+ * as a kernel, one lane per pair.  The words are bmh_pestat_candidates' words, bit for bit; the statistics stay on the host
+ * (bmh_pestat_from_candidates).
+ *
+ * For a caller's own vectors: offsets, counts and regions up in one copy, the kernel, the words down, one wait.  Needs neither
+ * parameters nor a resident reference.  Arguments as bmh_pestat_candidates' (an odd n ignores the last read); BMH_E_ARG as
+ * bmh_sort_dedup_batch gives it, BMH_E_RANGE for o->max_ins >= 2^30.  n == 0 and batches of empty vectors: BMH_OK with zeroed
+ * words and no launch. */
+int bmh_pestat_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, int64_t l_pac, int n, const bmh_alnreg_v *regs, uint32_t *cand);
+/* Two switches per context, off by default, both behind bmh_ctx_set_regs_dedup (which must be on).  While either is on,
+ * bmh_chains2regs_device and bmh_seed_chain_regs_batch run the kernel on the reads' region slices after the de-duplication and
+ * before the gather:
+ *   drop exact   mem_test_and_remove_exact (bwamem.c:438-443) with MEM_F_NO_EXACT set: a read whose head region has
+ *                truesc == l_seq * params.a loses it; the gather places, downloads and mallocs what is left
+ *   collect      reads 2p and 2p+1 are mates; the word of every pair (bmh_pestat_candidates' under *o, which is copied) comes down
+ *                with the regions' offsets, and bmh_last_pestat_candidates hands the words out.  The call waits as often as without.
+ * Refused before anything is enqueued, the switches staying as set and the context usable: either switch on while regs_dedup is
+ * off (BMH_E_ARG; bmh_last_error names the switch), collect with an odd n_reads (BMH_E_ARG), collect with max_ins >= 2^30
+ * (BMH_E_RANGE).  bmh_driver_stats and bmh_last_dedup_stats report what they report without the switches. */
+int bmh_ctx_set_regs_drop_exact(bmh_ctx_t *ctx, int on);
+int bmh_ctx_set_pestat_collect(bmh_ctx_t *ctx, int on, const bmh_sam_opt_t *o);
+/* The words of the last successful collecting call on this context, copied out of host memory the context owns (no device work),
+ * and the kernel's milliseconds with bmh_set_kernel_timing on (else -1; nullable).  BMH_E_ARG when n_pairs is not that call's pair
+ * count, when no such call has been made, and while drop exact is on and collect is off.  A successful call with n_reads == 0 is a
+ * collecting call of 0 pairs (and one that removed 0 regions): n_pairs == 0 then answers BMH_OK, cand may be NULL. */
+int bmh_last_pestat_candidates(bmh_ctx_t *ctx, uint32_t *cand, int64_t n_pairs, float *kernel_ms);
+/* Regions drop exact removed in the last successful chains-to-regions call that ran with it on; -1 before the first. */
+int bmh_last_drop_exact_stats(const bmh_ctx_t *ctx, int64_t *removed);
 
 #ifdef __cplusplus
 }

@@ -72,8 +72,9 @@ def sim_pairs_fast(rng, ref, n, L, noisy_frac):
 
 
 def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=False, regs_device=False, dedup_device=False, matesw_device=False,
-        decide_device=False, wanted_device=False, phase2_device=False, samtext_device=False, phase2_text_device=False):
+        decide_device=False, wanted_device=False, phase2_device=False, samtext_device=False, phase2_text_device=False, pestat_device=False):
     env = dict(os.environ)
+    env.pop("BMH_PESTAT_DEVICE", None)
     env.pop("BMH_CHAIN_DEVICE", None)
     env.pop("BMH_REGS_DEVICE", None)
     env.pop("BMH_DEDUP_DEVICE", None)
@@ -98,10 +99,12 @@ def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=Fals
             env["BMH_MATESW_DEVICE"] = "1"
         if chain_device:
             env["BMH_CHAIN_DEVICE"] = "1"
-        if regs_device or dedup_device:
+        if regs_device or dedup_device or pestat_device:
             env["BMH_REGS_DEVICE"] = "1"
-        if dedup_device:
+        if dedup_device or pestat_device:
             env["BMH_DEDUP_DEVICE"] = "1"
+        if pestat_device:
+            env["BMH_PESTAT_DEVICE"] = "1"
         env["LD_PRELOAD"] = load_package().DROPIN_PATH
         env["BMH_KSW_DROPIN"] = "1" if ksw_dropin else "0"
         env["BMH_VERBOSE"] = "1"
@@ -151,7 +154,10 @@ def main():
                     help="the DUT's phase 2 coordinates and SAM text are made on the device (BMH_SAMTEXT_DEVICE=1)")
     ap.add_argument("--phase2-text-device", action="store_true",
                     help="the DUT's whole phase 2 runs as one device session, only SAM text comes down (BMH_PHASE2_TEXT_DEVICE=1)")
+    ap.add_argument("--pestat-device", action="store_true",
+                    help="--pe: ... and answers mem_pestat's question per pair there (BMH_PESTAT_DEVICE=1); implies --regs-device --dedup-device")
     a = ap.parse_args()
+    a.dedup_device = a.dedup_device or a.pestat_device
     a.regs_device = a.regs_device or a.dedup_device
     rng = np.random.default_rng(20261007)
     tmp = tempfile.mkdtemp(prefix="bmh_pipe_")
@@ -175,7 +181,7 @@ def main():
         reflib.write_fastq(fq, list(reads))
     res = {"genome_bp": a.genome, "repeats": a.repeats, "reads": a.reads, "paired": bool(a.pe), "index_s": t_index, "chain_device": bool(a.chain_device), "regs_device": bool(a.regs_device),
            "dedup_device": bool(a.dedup_device), "matesw_device": bool(a.matesw_device), "decide_device": bool(a.decide_device), "wanted_device": bool(a.wanted_device),
-           "phase2_device": bool(a.phase2_device), "samtext_device": bool(a.samtext_device), "phase2_text_device": bool(a.phase2_text_device), "runs": []}
+           "phase2_device": bool(a.phase2_device), "samtext_device": bool(a.samtext_device), "phase2_text_device": bool(a.phase2_text_device), "pestat_device": bool(a.pestat_device), "runs": []}
     # one untimed DUT run first: on a fresh box the first process to load the HIP runtime and the library's code objects
     # pays for reading them from disk (seconds), which has nothing to do with the pipeline
     run(fa, fq, 8, a.batch, True, os.path.join(tmp, "warm.sam"), ksw_dropin=False)
@@ -184,13 +190,13 @@ def main():
         refsam = [l for l in open(os.path.join(tmp, "ref.sam")) if not l.startswith("@PG")]
         d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False, chain_device=a.chain_device, regs_device=a.regs_device,
                  dedup_device=a.dedup_device, matesw_device=a.matesw_device, decide_device=a.decide_device, wanted_device=a.wanted_device,
-                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device)
+                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device)
         same1 = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         d2 = None
         if a.full:
             d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True, chain_device=a.chain_device, regs_device=a.regs_device,
                  dedup_device=a.dedup_device, matesw_device=a.matesw_device, decide_device=a.decide_device, wanted_device=a.wanted_device,
-                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device)
+                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device)
             d2["sam_identical"] = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         res["runs"].append({"threads": t, "batch": a.batch, "ref": r, "dut_phase1_gpu": d1, "sam_identical": same1,
                             "dut_phase1_gpu_plus_percall_global": d2})
