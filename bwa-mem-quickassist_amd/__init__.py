@@ -62,6 +62,9 @@ CIGAR_REQ = np.dtype([("read", "<i4"), ("qb", "<i4"), ("qe", "<i4"), ("pad", "<i
 CIGAR_RES = np.dtype([("score", "<i4"), ("n_cigar", "<i4"), ("NM", "<i4"), ("tries", "<i4"), ("cigar_off", "<u4"),
                       ("md_off", "<u4"), ("md_len", "<u4"), ("rsv", "<u4")])
 BMH_REGION_CIGAR_CUT, BMH_REGION_MD_CUT = 1, 2
+BMH_REGION_LONG = 4  # finished by the long round of bmh_region_cigar_batch_long
+BMH_REGION_LONG_GUARD = 16
+REGION_LONG = np.dtype([("region", "<i8"), ("cigar_off", "<u8"), ("md_off", "<u8")])  # 24 bytes
 REGION_REQ = np.dtype([("q_src", "<u8"), ("rb", "<i8"), ("o_off", "<u8"), ("ql", "<i4"), ("tl", "<i4"), ("truesc", "<i4"),
                        ("task", "<i4", (3,))])
 REGION_RES = np.dtype([("score", "<i4"), ("n_cigar", "<i4"), ("tries", "<i4"), ("NM", "<i4"), ("md_len", "<i4"), ("flags", "<u4")])
@@ -271,6 +274,12 @@ def lib():
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_region_cigar_batch.restype = C.c_int
+        L.bmh_region_cigar_batch_long.argtypes = L.bmh_region_cigar_batch.argtypes + [C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.bmh_region_cigar_batch_long.restype = C.c_int
+        L.bmh_last_region_long_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.bmh_ctx_set_region_long.argtypes = [C.c_void_p, C.c_int]
+        L.bmh_last_reg2cigar_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.bmh_reg2cigar_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         _lib = L
@@ -508,6 +517,68 @@ class Context:
                                                  _ptr(tasks), len(tasks), int(task_cigar_words), int(cig_cap), int(md_cap), _ptr(res),
                                                  _ptr(cig), _ptr(md)))
         return res, cig, md
+
+    def region_cigar_batch_long(self, readpool, opool_bytes, reqs, tasks, task_cigar_words, cig_cap=24, md_cap=64, guard=0):
+        """region_cigar_batch() with the regions past their slots finished on the device (bmh_region_cigar_batch_long).  Returns
+        (results, cigar words [n, cig_cap], MD bytes [n, md_cap], longs, long_cigar, long_md): longs is a REGION_LONG array, ascending
+        by region, into the two dense pools -- copies, the call's own allocations are freed here.  guard: bytes behind each of the
+        three outputs the call is given that must come back untouched (checked here; a test's knob)."""
+        readpool = np.ascontiguousarray(readpool, dtype=np.uint8)
+        reqs = np.ascontiguousarray(reqs, dtype=REGION_REQ)
+        tasks = np.ascontiguousarray(tasks, dtype=GLB_TASK)
+        n = len(reqs)
+        res_b = np.full(n * REGION_RES.itemsize + guard + 1, 0x5A, dtype=np.uint8)
+        cig_b = np.full(max(n, 1) * cig_cap * 4 + guard, 0x5A, dtype=np.uint8)
+        md_b = np.full(max(n, 1) * md_cap + guard, 0x5A, dtype=np.uint8)
+        longs, n_long, lcig, lmd = C.c_void_p(), C.c_int64(-1), C.c_void_p(), C.c_void_p()
+        self._check(lib().bmh_region_cigar_batch_long(self._h, _ptr(readpool), readpool.nbytes, int(opool_bytes), _ptr(reqs), n, _ptr(tasks),
+                                                      len(tasks), int(task_cigar_words), int(cig_cap), int(md_cap), _ptr(res_b), _ptr(cig_b),
+                                                      _ptr(md_b), C.byref(longs), C.byref(n_long), C.byref(lcig), C.byref(lmd)))
+        libc = C.CDLL(None)
+        libc.free.argtypes = [C.c_void_p]
+        try:
+            res = res_b[:n * REGION_RES.itemsize].view(REGION_RES).copy()
+            assert (res_b[n * REGION_RES.itemsize:] == 0x5A).all() and (cig_b[max(n, 1) * cig_cap * 4:] == 0x5A).all() \
+                and (md_b[max(n, 1) * md_cap:] == 0x5A).all(), "bmh_region_cigar_batch_long wrote behind one of its outputs"
+            cig = cig_b[:max(n, 1) * cig_cap * 4].view(np.uint32).reshape(max(n, 1), cig_cap).copy()
+            md = md_b[:max(n, 1) * md_cap].reshape(max(n, 1), md_cap).copy()
+            nl = n_long.value
+            lg = np.zeros(nl, dtype=REGION_LONG)
+            lc, lm = np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+            if nl > 0:
+                C.memmove(lg.ctypes.data, longs.value, nl * REGION_LONG.itemsize)
+                fl = res[lg["region"]]
+                words = int((lg["cigar_off"] + fl["n_cigar"].astype(np.uint64)).max())
+                mbytes = int((lg["md_off"] + fl["md_len"].astype(np.uint64)).max())
+                lc, lm = np.zeros(words, dtype=np.uint32), np.zeros(mbytes, dtype=np.uint8)
+                C.memmove(lc.ctypes.data, lcig.value, words * 4)
+                C.memmove(lm.ctypes.data, lmd.value, mbytes)
+                # the pools are dense and end with their last entry; behind each come BMH_REGION_LONG_GUARD bytes of 0xA5, set on the
+                # device before the kernels ran and brought back with the pool
+                g = np.zeros(2 * BMH_REGION_LONG_GUARD, dtype=np.uint8)
+                C.memmove(g.ctypes.data, lcig.value + words * 4, BMH_REGION_LONG_GUARD)
+                C.memmove(g.ctypes.data + BMH_REGION_LONG_GUARD, lmd.value + mbytes, BMH_REGION_LONG_GUARD)
+                assert (g == 0xA5).all(), "the long round wrote behind one of its pools"
+        finally:
+            libc.free(longs), libc.free(lcig), libc.free(lmd)
+        return res, cig, md, lg, lc, lm
+
+    def last_region_long_stats(self):
+        """bmh_last_region_long_stats: (regions, cigar_words, md_bytes, kernel_ms) of the last region_cigar_batch_long()."""
+        a, b, c, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_float()
+        self._check(lib().bmh_last_region_long_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(ms)))
+        return a.value, b.value, c.value, ms.value
+
+    def set_region_long(self, on=True):
+        """bmh_ctx_set_region_long: while on, reg2cigar_batch() -- and pass B of phase 2 through it -- finishes the regions past the
+        region record's slots on the device instead of redoing them with host copies."""
+        self._check(lib().bmh_ctx_set_region_long(self._h, 1 if on else 0))
+
+    def last_reg2cigar_stats(self):
+        """bmh_last_reg2cigar_stats: (regions, long_device, redone_host) of the last reg2cigar_batch() on this context."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(lib().bmh_last_reg2cigar_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     # ---- L2, device-resident (raw device pointers, e.g. torch tensors' data_ptr())
     def sw_batch(self, pool, tasks):

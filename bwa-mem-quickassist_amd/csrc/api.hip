@@ -339,6 +339,9 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_dedup)
 		if (e) (void)hipEventDestroy(e);
+	free_buf(ctx->d_rlong), free_buf(ctx->d_lcig), free_buf(ctx->d_lmd);
+	for (auto &e : ctx->ev_rlong)
+		if (e) (void)hipEventDestroy(e);
 	free_buf(ctx->d_pestat);
 	for (auto &e : ctx->ev_pestat)
 		if (e) (void)hipEventDestroy(e);
@@ -942,16 +945,24 @@ int bmh_global_batch(bmh_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes, con
 
 // ------------------------------------------------------------------ the region record (bwa_gen_cigar2 around ksw_global2)
 
-int bmh_region_cigar_batch(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readpool_bytes, size_t opool_bytes, const bmh_region_req_t *reqs,
-                           int64_t n_req, const bmh_glb_task_t *tasks, int64_t n_tasks, size_t task_cigar_words, int cig_cap, int md_cap,
-                           bmh_region_res_t *results, uint32_t *cigar_out, char *md_out)
+// where region_cigar_round left the round's arrays on the device, for the long round behind it
+struct RegionRoundDev {
+	const bmh_region_req_t *reqs;
+	bmh_region_res_t *res;
+	const uint32_t *cig;
+};
+
+// bmh_region_cigar_batch: checks, one enqueue, one wait.  `what` names the caller in the error text.
+static int region_cigar_round(bmh_ctx_t *ctx, const char *what, const uint8_t *readpool, size_t readpool_bytes, size_t opool_bytes,
+                              const bmh_region_req_t *reqs, int64_t n_req, const bmh_glb_task_t *tasks, int64_t n_tasks, size_t task_cigar_words,
+                              int cig_cap, int md_cap, bmh_region_res_t *results, uint32_t *cigar_out, char *md_out, RegionRoundDev *dev)
 {
 	if (!ctx || n_req < 0 || n_tasks < 0 || cig_cap < 1 || md_cap < 1) return BMH_E_ARG;
 	if (n_req > 0 && (!readpool || !reqs || !results || !cigar_out || !md_out)) return BMH_E_ARG;
 	if (n_tasks > 0 && !tasks) return BMH_E_ARG;
 	if (!ctx->have_params) return BMH_E_ARG;
 	if (!ctx->dev.pac) {
-		ctx->last_error = "bmh_region_cigar_batch needs the resident reference (bmh_ctx_set_pac)";
+		ctx->last_error = std::string(what) + " needs the resident reference (bmh_ctx_set_pac)";
 		return BMH_E_ARG;
 	}
 	if (n_req == 0) return BMH_OK;
@@ -1008,11 +1019,218 @@ int bmh_region_cigar_batch(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readp
 		if ((rc = launch_region_finish(ctx, (const uint8_t *)ctx->d_pool.p, d_reqs, n_req, (const bmh_glb_task_t *)ctx->d_tasks.p,
 		                               (const bmh_glb_result_t *)ctx->d_res.p, (const uint32_t *)ctx->d_cigar.p, d_rres, d_cout, cig_cap, d_md, md_cap)))
 			return rc;
+		if (dev) dev->reqs = d_reqs, dev->res = d_rres, dev->cig = d_cout;
 		if ((rc = st.d2h(results, d_rres, (size_t)n_req * sizeof(bmh_region_res_t)))) return rc;
 		if ((rc = st.d2h(cigar_out, d_cout, (size_t)n_req * (size_t)cig_cap * 4))) return rc;
 		return st.d2h(md_out, d_md, (size_t)n_req * (size_t)md_cap);
 	}());
 	return rc == BMH_E_CIGAR_CAP ? BMH_OK : rc; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
+}
+
+int bmh_region_cigar_batch(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readpool_bytes, size_t opool_bytes, const bmh_region_req_t *reqs,
+                           int64_t n_req, const bmh_glb_task_t *tasks, int64_t n_tasks, size_t task_cigar_words, int cig_cap, int md_cap,
+                           bmh_region_res_t *results, uint32_t *cigar_out, char *md_out)
+{
+	return region_cigar_round(ctx, "bmh_region_cigar_batch", readpool, readpool_bytes, opool_bytes, reqs, n_req, tasks, n_tasks, task_cigar_words,
+	                          cig_cap, md_cap, results, cigar_out, md_out, nullptr);
+}
+
+// ---- ... and the regions that round flags, finished behind it (region_long.hip).  The round's device arrays stay where they are:
+// d_pool (the oriented copies), d_tasks, d_res and d_region are read, the long round's own buffers are d_rlong, d_lcig and d_lmd.
+enum { kLongGuard = BMH_REGION_LONG_GUARD }; // bytes behind each dense pool, set before the kernels run and brought back with it: they must come back as set
+
+static int region_long_round(bmh_ctx_t *ctx, const RegionRoundDev &D, const bmh_region_req_t *reqs, int64_t n_req, const bmh_glb_task_t *tasks,
+                             int cig_cap, const bmh_region_res_t *rr, int64_t n_long, int64_t n_cut, uint64_t words, RegionLongEnt *ent,
+                             uint32_t **cig_, char **md_, uint64_t *md_bytes_)
+{
+	GlbShape gs; // the host's maxima over the flagged regions' tries: the rerun's tasks are among them
+	for (int64_t k = 0; k < n_req; ++k) {
+		if (!(rr[k].flags & BMH_REGION_CIGAR_CUT) || reqs[k].task[0] < 0) continue;
+		for (int t = 0; t < (reqs[k].truesc == INT32_MIN ? 1 : 3); ++t) {
+			const bmh_glb_task_t &x = tasks[reqs[k].task[t]];
+			if (x.qlen <= kGlbLdsQcap) {
+				gs.qmax = std::max(gs.qmax, (int)x.qlen), gs.tmax = std::max(gs.tmax, (int)x.tlen);
+				gs.wmax = std::max(gs.wmax, std::min(x.w, (int)x.qlen));
+			} else {
+				gs.lg.qmax = std::max(gs.lg.qmax, (int)x.qlen), gs.lg.tmax = std::max(gs.lg.tmax, (int)x.tlen);
+				gs.lg.wmax = std::max(gs.lg.wmax, std::min(x.w, (int)x.qlen));
+			}
+			gs.wraw = std::max(gs.wraw, x.w);
+		}
+		if (reqs[k].ql > kGlbLdsQcap) ++gs.lg.n;
+	}
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	uint32_t *h_cig = nullptr;
+	char *h_md = nullptr;
+	Stager st(ctx);
+	int rc = [&]() -> int {
+		int rc;
+		const size_t nb = (size_t)((n_req + 255) / 256) + 1; // block sums of the widest scan, and its total
+		const size_t o_ent = (nb * sizeof(RegionLongSum) + 255) & ~(size_t)255;
+		const size_t o_task = o_ent + (((size_t)n_long * sizeof(RegionLongEnt) + 255) & ~(size_t)255);
+		const size_t o_res = o_task + (((size_t)std::max<int64_t>(n_cut, 1) * sizeof(bmh_glb_task_t) + 255) & ~(size_t)255);
+		const size_t total = o_res + (size_t)std::max<int64_t>(n_cut, 1) * sizeof(bmh_glb_result_t);
+		if ((rc = ensure(ctx, ctx->d_rlong, total)) || (rc = ensure(ctx, ctx->d_lcig, (size_t)words * 4 + kLongGuard))) return rc;
+		uint8_t *dl = (uint8_t *)ctx->d_rlong.p;
+		RegionLongSum *d_bsum = (RegionLongSum *)dl;
+		RegionLongEnt *d_ent = (RegionLongEnt *)(dl + o_ent);
+		bmh_glb_task_t *d_lt = (bmh_glb_task_t *)(dl + o_task);
+		bmh_glb_result_t *d_lr = (bmh_glb_result_t *)(dl + o_res);
+		uint32_t *d_lcig = (uint32_t *)ctx->d_lcig.p;
+		const uint8_t *d_pool = (const uint8_t *)ctx->d_pool.p;
+		const bool tm = ctx->timing;
+		if (tm)
+			for (auto &e : ctx->ev_rlong)
+				if (!e) BMH_HIP(ctx, hipEventCreate(&e));
+		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_rlong[0], ctx->stream));
+		BMH_HIP(ctx, hipMemsetAsync(d_lcig + words, 0xA5, kLongGuard, ctx->stream));
+		if ((rc = launch_region_long_list(ctx, D.reqs, D.res, n_req, (const bmh_glb_result_t *)ctx->d_res.p, d_bsum, d_ent, n_long))) return rc;
+		if ((rc = launch_region_long_tasks(ctx, d_ent, n_long, d_bsum, (const bmh_glb_task_t *)ctx->d_tasks.p, d_lt, n_cut, words))) return rc;
+		if (n_cut > 0 && (rc = launch_global(ctx, d_pool, d_lt, n_cut, d_lr, d_lcig, nullptr, gs.qmax, gs.tmax, gs.wmax, gs.wraw, &gs.lg))) return rc;
+		if ((rc = launch_region_long_sizes(ctx, d_pool, D.reqs, d_ent, n_long, d_lr, D.cig, cig_cap, d_lcig, d_bsum))) return rc;
+		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_rlong[1], ctx->stream));
+		// first wait: the MD pool's size
+		const size_t nbe = (size_t)((n_long + 255) / 256);
+		if ((rc = ensure_host(ctx, ctx->h_down, 256))) return rc;
+		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_down.p, d_bsum + nbe, sizeof(RegionLongSum), hipMemcpyDeviceToHost, ctx->stream));
+		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+		const uint64_t md_bytes = ((const RegionLongSum *)ctx->h_down.p)->a;
+		if (md_bytes > (uint64_t)n_long * (3ull * 131070 + 16)) { // (more than any walk can write: the device's error word says why)
+			ctx->last_error = "the long round's MD sizes are not credible";
+			return BMH_E_ARG;
+		}
+		if ((rc = ensure(ctx, ctx->d_lmd, (size_t)md_bytes + kLongGuard))) return rc;
+		char *d_lmd = (char *)ctx->d_lmd.p;
+		h_cig = (uint32_t *)malloc((size_t)words * 4 + kLongGuard);
+		h_md = (char *)malloc((size_t)md_bytes + kLongGuard);
+		if (!h_cig || !h_md) return BMH_E_NOMEM;
+		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_rlong[2], ctx->stream));
+		BMH_HIP(ctx, hipMemsetAsync(d_lmd + md_bytes, 0xA5, kLongGuard, ctx->stream));
+		if ((rc = launch_region_long_md(ctx, d_pool, D.reqs, d_ent, n_long, d_lcig, d_bsum, d_lmd, md_bytes))) return rc;
+		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_rlong[3], ctx->stream));
+		// second wait: the download
+		if ((rc = st.stage(0, (size_t)n_long * sizeof(RegionLongEnt) + (size_t)words * 4 + (size_t)md_bytes + 2 * kLongGuard + 256))) return rc;
+		if ((rc = st.d2h(ent, d_ent, (size_t)n_long * sizeof(RegionLongEnt)))) return rc;
+		if ((rc = st.d2h(h_cig, d_lcig, (size_t)words * 4 + kLongGuard))) return rc;
+		if ((rc = st.d2h(h_md, d_lmd, (size_t)md_bytes + kLongGuard))) return rc;
+		*md_bytes_ = md_bytes;
+		return BMH_OK;
+	}();
+	rc = st.end(rc);
+	if (!rc && ctx->timing) {
+		float m0 = 0.f, m1 = 0.f;
+		hipError_t e = hipEventElapsedTime(&m0, ctx->ev_rlong[0], ctx->ev_rlong[1]);
+		if (e == hipSuccess) e = hipEventElapsedTime(&m1, ctx->ev_rlong[2], ctx->ev_rlong[3]);
+		if (e != hipSuccess) rc = set_hip_error(ctx, e, "hipEventElapsedTime(long round)");
+		ctx->rlong_ms = m0 + m1;
+	}
+	if (rc) {
+		free(h_cig), free(h_md);
+		return rc;
+	}
+	*cig_ = h_cig, *md_ = h_md;
+	return BMH_OK;
+}
+
+int bmh_region_cigar_batch_long(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readpool_bytes, size_t opool_bytes, const bmh_region_req_t *reqs,
+                                int64_t n_req, const bmh_glb_task_t *tasks, int64_t n_tasks, size_t task_cigar_words, int cig_cap, int md_cap,
+                                bmh_region_res_t *results, uint32_t *cigar_out, char *md_out, bmh_region_long_t **longs, int64_t *n_long,
+                                uint32_t **long_cigar, char **long_md)
+{
+	if (!ctx || !longs || !n_long || !long_cigar || !long_md) return BMH_E_ARG;
+	if (n_req < 0 || n_tasks < 0 || cig_cap < 1 || md_cap < 1) return BMH_E_ARG;
+	if (n_req > 0 && (!readpool || !reqs || !results || !cigar_out || !md_out)) return BMH_E_ARG;
+	if (n_tasks > 0 && !tasks) return BMH_E_ARG;
+	// the round's outputs go to the caller only once the whole call has succeeded
+	const size_t rb = (size_t)n_req * sizeof(bmh_region_res_t), cb = (size_t)n_req * (size_t)cig_cap * 4, mb = (size_t)n_req * (size_t)md_cap;
+	bmh_region_res_t *rr = (bmh_region_res_t *)malloc(rb + 1);
+	uint32_t *tc = (uint32_t *)malloc(cb + 4);
+	char *tmd = (char *)malloc(mb + 1);
+	RegionLongEnt *ent = nullptr;
+	bmh_region_long_t *lg = nullptr;
+	uint32_t *h_cig = nullptr;
+	char *h_md = nullptr;
+	int64_t nl = 0, n_cut = 0;
+	uint64_t words = 0, md_bytes = 0;
+	RegionRoundDev D{nullptr, nullptr, nullptr};
+	int rc = rr && tc && tmd ? BMH_OK : BMH_E_NOMEM;
+	if (!rc)
+		rc = region_cigar_round(ctx, "bmh_region_cigar_batch_long", readpool, readpool_bytes, opool_bytes, reqs, n_req, tasks, n_tasks,
+		                        task_cigar_words, cig_cap, md_cap, rr, tc, tmd, &D);
+	for (int64_t k = 0; !rc && k < n_req; ++k)
+		if (rr[k].flags) {
+			++nl, words += (uint64_t)(rr[k].n_cigar > 0 ? rr[k].n_cigar : 0);
+			if (rr[k].flags & BMH_REGION_CIGAR_CUT) ++n_cut;
+		}
+	if (!rc && words > 0xffffffffull) { // the rerun's tasks address the pool through the uint32 cigar_off
+		ctx->last_error = "the flagged regions' CIGARs have " + std::to_string(words) + " words: more than one call's pool can address";
+		rc = BMH_E_RANGE;
+	}
+	if (!rc && nl > 0) {
+		ent = (RegionLongEnt *)malloc((size_t)nl * sizeof(RegionLongEnt));
+		lg = (bmh_region_long_t *)malloc((size_t)nl * sizeof(bmh_region_long_t));
+		if (!ent || !lg) rc = BMH_E_NOMEM;
+		if (!rc) rc = region_long_round(ctx, D, reqs, n_req, tasks, cig_cap, rr, nl, n_cut, words, ent, &h_cig, &h_md, &md_bytes);
+		for (int64_t e = 0; !rc && e < nl; ++e) { // the entries are the flagged regions in ascending order, each inside the two pools
+			const RegionLongEnt &x = ent[e];
+			if (x.bad || x.region < 0 || x.region >= n_req || (e > 0 && x.region <= ent[e - 1].region) || !rr[x.region].flags ||
+			    x.n_cigar != rr[x.region].n_cigar || x.cigar_off + (uint64_t)x.n_cigar > words || x.md_len < 0 ||
+			    x.md_off + (uint64_t)x.md_len > md_bytes) {
+				ctx->last_error = "the long round's entry " + std::to_string(e) + " is inconsistent";
+				rc = BMH_E_ARG;
+			}
+		}
+		for (int g = 0; !rc && g < kLongGuard; ++g)
+			if (((const uint8_t *)h_cig)[words * 4 + g] != 0xA5 || ((const uint8_t *)h_md)[md_bytes + g] != 0xA5) {
+				ctx->last_error = "the long round wrote behind one of its pools";
+				rc = BMH_E_HIP;
+			}
+	}
+	if (rc) {
+		free(rr), free(tc), free(tmd), free(ent), free(lg), free(h_cig), free(h_md);
+		return rc;
+	}
+	for (int64_t e = 0; e < nl; ++e) {
+		const RegionLongEnt &x = ent[e];
+		bmh_region_res_t &r = rr[x.region];
+		r.NM = x.NM, r.md_len = x.md_len, r.flags |= BMH_REGION_LONG;
+		lg[e].region = x.region, lg[e].cigar_off = x.cigar_off, lg[e].md_off = x.md_off;
+	}
+	if (n_req > 0) memcpy(results, rr, rb), memcpy(cigar_out, tc, cb), memcpy(md_out, tmd, mb);
+	*longs = lg, *n_long = nl, *long_cigar = h_cig, *long_md = h_md;
+	ctx->rlong_regions = nl, ctx->rlong_words = (long long)words, ctx->rlong_md = (long long)md_bytes;
+	if (nl == 0 || !ctx->timing) ctx->rlong_ms = nl == 0 && ctx->timing ? 0.f : -1.f;
+	free(rr), free(tc), free(tmd), free(ent);
+	return BMH_OK;
+}
+
+int bmh_last_region_long_stats(const bmh_ctx_t *ctx, int64_t *regions, int64_t *cigar_words, int64_t *md_bytes, float *kernel_ms)
+{
+	if (!ctx || !regions || !cigar_words || !md_bytes || !kernel_ms) return BMH_E_ARG;
+	*regions = ctx->rlong_regions, *cigar_words = ctx->rlong_words, *md_bytes = ctx->rlong_md, *kernel_ms = ctx->rlong_ms;
+	return BMH_OK;
+}
+
+int bmh_ctx_set_region_long(bmh_ctx_t *ctx, int on)
+{
+	if (!ctx) return BMH_E_ARG;
+	ctx->region_long = on != 0;
+	return BMH_OK;
+}
+
+// internal hooks for host/reg2cigar_batch.c: the switch, and the counts of its last call
+int bmh_ctx_region_long_(const bmh_ctx_t *ctx) { return ctx && ctx->region_long; }
+void bmh_ctx_set_reg2cigar_stats_(bmh_ctx_t *ctx, int64_t regions, int64_t long_device, int64_t redone_host)
+{
+	if (ctx) ctx->r2c_regions = regions, ctx->r2c_long_device = long_device, ctx->r2c_redone_host = redone_host;
+}
+
+int bmh_last_reg2cigar_stats(const bmh_ctx_t *ctx, int64_t *regions, int64_t *long_device, int64_t *redone_host)
+{
+	if (!ctx || !regions || !long_device || !redone_host) return BMH_E_ARG;
+	*regions = ctx->r2c_regions, *long_device = ctx->r2c_long_device, *redone_host = ctx->r2c_redone_host;
+	return BMH_OK;
 }
 
 // ------------------------------------------------------------------ local Smith-Waterman (ksw_align2)

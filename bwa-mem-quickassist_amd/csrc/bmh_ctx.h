@@ -102,6 +102,14 @@ struct bmh_ctx {
 	} hint[kHintKinds];
 	DevBuf d_seedws; // workspace of the fused per-seed extension (seedext.hip)
 	DevBuf d_region; // region records, their results, CIGAR and MD slots (bmh_region_cigar_batch)
+	// the long round of bmh_region_cigar_batch_long (region_long.hip)
+	DevBuf d_rlong;                           // block sums, entries, the rerun's tasks and results
+	DevBuf d_lcig, d_lmd;                     // the dense CIGAR and MD pools, 16 guard bytes behind each
+	hipEvent_t ev_rlong[4] = {};              // around the round's two halves (timing mode)
+	long long rlong_regions = -1, rlong_words = -1, rlong_md = -1; // of the last bmh_region_cigar_batch_long (bmh_last_region_long_stats), -1 = none yet
+	float rlong_ms = -1.f;                    // ... and its kernels' duration with kernel timing on, else -1
+	bool region_long = false;                 // bmh_ctx_set_region_long: bmh_reg2cigar_batch finishes flagged regions through that call
+	long long r2c_regions = -1, r2c_long_device = -1, r2c_redone_host = -1; // of the last bmh_reg2cigar_batch (bmh_last_reg2cigar_stats)
 	bmh_seedext_stats_t sstats{};
 	int64_t seed_pending_n = -1; // tasks of the bmh_seedext_submit() in flight, -1 = none
 	DevBuf d_chain;                // device chainer (chain.hip): per-read bounds, arena, compact output
@@ -465,5 +473,32 @@ int launch_region_orient(bmh_ctx *ctx, uint8_t *d_pool, size_t rpool_off, const 
 int launch_region_finish(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_region_req_t *d_reqs, int64_t n, const bmh_glb_task_t *d_tasks,
                          const bmh_glb_result_t *d_gres, const uint32_t *d_tcig, bmh_region_res_t *d_out, uint32_t *d_cig_out, int cig_cap,
                          char *d_md_out, int md_cap);
+
+// ---- the long round behind launch_region_finish (region_long.hip, bmh_region_cigar_batch_long).  One entry per flagged region, in
+// region order; the scans run over pairs of 64-bit sums, one per block of 256 positions and one more for the total
+struct RegionLongSum {
+	unsigned long long a, b;
+};
+struct RegionLongEnt { // 64 bytes
+	int64_t region;
+	uint64_t cigar_off, md_off; // first word / byte in the two dense pools
+	int32_t fin, tix;           // final task of round 1 (-1: the no-gap case); its rerun among the long tasks (-1: none, the CIGAR fitted its slot)
+	int32_t n_cigar, score, NM, md_len;
+	uint32_t flags; // BMH_REGION_*_CUT as round 1 set them
+	int32_t bad;    // left out of the round, BMH_E_ARG is in the error word
+	int64_t rsv_;
+};
+// the flagged records of d_res, compacted into d_ent (n_ent of them, as the host counted); d_gres: round 1's task results
+int launch_region_long_list(bmh_ctx *ctx, const bmh_region_req_t *d_reqs, const bmh_region_res_t *d_res, int64_t n,
+                            const bmh_glb_result_t *d_gres, RegionLongSum *d_bsum, RegionLongEnt *d_ent, int64_t n_ent);
+// cigar_off of every entry in a pool of `words` words, and the n_cut tasks of the CIGAR-cut ones (their final try, n_cigar slots)
+int launch_region_long_tasks(bmh_ctx *ctx, RegionLongEnt *d_ent, int64_t n_ent, RegionLongSum *d_bsum, const bmh_glb_task_t *d_tasks,
+                             bmh_glb_task_t *d_ltasks, int64_t n_cut, uint64_t words);
+// behind the rerun: its results against round 1's, the slot CIGARs of the other entries into the pool, NM and md_len of every entry,
+// and the scan of md_len: d_bsum[blocks of n_ent].a is the MD pool's size
+int launch_region_long_sizes(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_region_req_t *d_reqs, RegionLongEnt *d_ent, int64_t n_ent,
+                             const bmh_glb_result_t *d_lres, const uint32_t *d_cig_out, int cig_cap, uint32_t *d_lcig, RegionLongSum *d_bsum);
+int launch_region_long_md(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_region_req_t *d_reqs, RegionLongEnt *d_ent, int64_t n_ent,
+                          const uint32_t *d_lcig, const RegionLongSum *d_bsum, char *d_lmd, uint64_t md_bytes);
 
 } // namespace bmh

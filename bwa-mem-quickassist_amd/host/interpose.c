@@ -31,6 +31,9 @@
  *   BMH_WANTED_DEVICE=1  its pass B's planning -- the bwa_fix_xref2 test and cut, bands, region records and tasks of the regions that
  *                        get printed -- as kernels (bmh_ctx_set_wanted_device).  Needs BMH_PAC_RESIDENT not 0; independent of the
  *                        other switches.
+ *   BMH_REGION_LONG=1    the alignments of pass B whose CIGAR or MD outgrow the region record's slots -- on long reads, all of them --
+ *                        are finished on the device behind the others (bmh_ctx_set_region_long) instead of being redone with oriented
+ *                        copies made on the host.  Needs BMH_PAC_RESIDENT not 0; holds for every form of pass B above and below.
  *   BMH_PHASE2_DEVICE=1  pass A and pass B as ONE device session (bmh_ctx_set_phase2_device): the regions go up once and the want
  *                        list never leaves the device between the two.  Needs BMH_PAC_RESIDENT not 0.  A slice the fused call
  *                        refuses as out of range goes the way the two switches above say.
@@ -456,6 +459,28 @@ static int qa_wanted_device(void)
 }
 static long long g_wanted_cnt[3]; /* regions planned on the device, fixed, redone on the host */
 
+/* BMH_REGION_LONG=1: the regions whose CIGAR or MD outgrow the region record's slots are finished on the device
+ * (bmh_ctx_set_region_long on every pooled context phase 2 uses) instead of being redone with host copies.  The region record
+ * aligns against the resident reference, so BMH_PAC_RESIDENT=0 contradicts it: checked when the library is loaded, like its siblings. */
+__attribute__((constructor)) static void qa_check_region_long_env(void)
+{
+	const char *e = getenv("BMH_REGION_LONG"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_REGION_LONG=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+static int qa_region_long(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_REGION_LONG");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+void bmh_reg2cigar_totals_(long long *long_device, long long *redone_host); /* host/reg2cigar_batch.c */
+
 /* BMH_PHASE2_DEVICE=1: phase 2's pass A and pass B as one device session (bmh_ctx_set_phase2_device on every pooled context phase 2
  * uses, with the sequence table made resident where the reference is).  It needs the resident reference as BMH_WANTED_DEVICE does:
  * checked when the library is loaded. */
@@ -796,6 +821,7 @@ static bmh_ctx_t *qa_slice_ctx(const qa_slice_job_t *J)
 		if ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns))) bmh_tls_die(bmh_last_error(ctx), rc);
 	}
 	if ((rc = bmh_ctx_set_wanted_device(ctx, qa_wanted_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
+	if ((rc = bmh_ctx_set_region_long(ctx, qa_region_long()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	if ((rc = bmh_ctx_set_phase2_device(ctx, qa_phase2_device()))) bmh_tls_die(bmh_last_error(ctx), rc);
 	if (qa_samtext_device() && ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns)) || (rc = bmh_ctx_set_refnames(ctx, (const bmh_refidx_t *)J->bns))))
 		bmh_tls_die(bmh_last_error(ctx), rc);
@@ -1053,6 +1079,11 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		if (qa_phase2_text_device())
 			fprintf(stderr, "[bwamem_hip] phase 2 and SAM text on the device in one session: %lld units, %lld regions, %lld redone on the host, %lld lines, %lld bytes, %lld host fall-backs\n",
 			        g_phase2_text_cnt[0], g_phase2_text_cnt[1], g_phase2_text_cnt[2], g_phase2_text_cnt[3], g_phase2_text_cnt[4], g_phase2_text_cnt[5]);
+		if (qa_region_long()) {
+			long long ld = 0, rh = 0;
+			bmh_reg2cigar_totals_(&ld, &rh);
+			fprintf(stderr, "[bwamem_hip] long region records so far: %lld regions finished on the device, %lld redone with host copies\n", ld, rh);
+		}
 		if (qa_samtext_device())
 			fprintf(stderr, "[bwamem_hip] SAM text on the device: %lld reads, %lld lines, %lld bytes\n", g_samtext_cnt[0], g_samtext_cnt[1], g_samtext_cnt[2]);
 		if (bmh_pool_wide()) { /* BMH_WIDE_EXT=1 */

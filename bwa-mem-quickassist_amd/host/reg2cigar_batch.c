@@ -18,7 +18,9 @@
  * bmh_region_cigar_batch(): the host lays out pools and computes bands, which needs no sequence byte; window fetch, orientation, the
  * no-gap score, the alignments, the replay of the loop, NM and MD are the device's (csrc/region_cigar.hip).  The few regions whose
  * CIGAR or MD outgrow the fixed slots coming back, and every call on a context without the resident reference, take the older
- * path below it: oriented copies made on the host, bmh_global_batch(), replay, NM and MD on the host.
+ * path below it: oriented copies made on the host, bmh_global_batch(), replay, NM and MD on the host.  With bmh_ctx_set_region_long
+ * on, the call is bmh_region_cigar_batch_long() instead: the regions past their slots are finished on the device behind the others
+ * (csrc/region_long.hip) and packed from its two pools, and the older path is left to contexts without the resident reference.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -335,6 +337,16 @@ done:
 enum { MD_SLOT = 96 }; /* bytes of MD coming back per region: "150", "75A74", ... (a 150 bp mate with 12 % substitutions: ~55); the rare longer one is redone by the host path */
 
 int bmh_ctx_has_pac_(const bmh_ctx_t *ctx, const uint8_t *pac, int64_t l_pac);
+int bmh_ctx_region_long_(const bmh_ctx_t *ctx);
+void bmh_ctx_set_reg2cigar_stats_(bmh_ctx_t *ctx, int64_t regions, int64_t long_device, int64_t redone_host);
+
+/* ... and over the process, for the preload shim's log: regions the long round finished, regions redone with host copies out of a
+ * call that went through the region record */
+static long long g_long_device, g_redone_host;
+void bmh_reg2cigar_totals_(long long *long_device, long long *redone_host)
+{
+	*long_device = __sync_fetch_and_add(&g_long_device, 0), *redone_host = __sync_fetch_and_add(&g_redone_host, 0);
+}
 
 static int reg2cigar_region_records(bmh_ctx_t *ctx, const bmh_params_t *p, int64_t l_pac, const uint8_t *pac, const bmh_read_t *reads,
                                     int64_t n_req, const bmh_cigar_req_t *reqs, bmh_cigar_res_t *res, uint32_t *cigar_pool,
@@ -349,7 +361,11 @@ static int reg2cigar_region_records(bmh_ctx_t *ctx, const bmh_params_t *p, int64
 	uint8_t *rpool = 0;
 	uint32_t *cout = 0;
 	char *mout = 0;
-	int64_t k, v, n_v = 0, n_tasks = 0, task_cap, n_redo = 0;
+	bmh_region_long_t *longs = 0; /* with bmh_ctx_set_region_long on: the regions past their slots and the two pools they lie in */
+	uint32_t *lcig = 0;
+	char *lmd = 0;
+	int64_t k, v, n_v = 0, n_tasks = 0, task_cap, n_redo = 0, n_long = 0, li = 0;
+	const int use_long = bmh_ctx_region_long_(ctx);
 	size_t rbytes = 0, obytes = 0, slot = 0, cig_used = 0, md_used = 0;
 	int rc = BMH_OK;
 	const bmh_rp_opt_t po = rp_opt(p);
@@ -397,12 +413,29 @@ static int reg2cigar_region_records(bmh_ctx_t *ctx, const bmh_params_t *p, int64
 		memcpy(rpool + rq[v].q_src, reads[r->read].seq + r->qb, (size_t)rq[v].ql);
 	}
 	if (trace) tt[1] = now_s();
-	if (n_v > 0 && (rc = bmh_region_cigar_batch(ctx, rpool, rbytes, obytes, rq, n_v, tasks, n_tasks, slot + 4, SMALL_CAP, MD_SLOT, rr, cout, mout)))
+	if (n_v > 0 && use_long) {
+		if ((rc = bmh_region_cigar_batch_long(ctx, rpool, rbytes, obytes, rq, n_v, tasks, n_tasks, slot + 4, SMALL_CAP, MD_SLOT, rr, cout, mout, &longs,
+		                                      &n_long, &lcig, &lmd)))
+			goto done;
+	} else if (n_v > 0 && (rc = bmh_region_cigar_batch(ctx, rpool, rbytes, obytes, rq, n_v, tasks, n_tasks, slot + 4, SMALL_CAP, MD_SLOT, rr, cout, mout)))
 		goto done;
 	if (trace) tt[2] = now_s();
 	for (v = 0; v < n_v; ++v) { /* the packed outputs */
 		const bmh_region_res_t *x = &rr[v];
 		bmh_cigar_res_t *o = &res[of[v]];
+		if (x->flags & BMH_REGION_LONG) { /* finished by the long round: packed from its pools, in the place the region has in the batch */
+			const bmh_region_long_t *g;
+			if (li >= n_long || longs[li].region != v) { rc = BMH_E_ARG; goto done; } /* (ascending by region, one per flagged record: cannot happen) */
+			g = &longs[li++];
+			if (cig_used + (size_t)x->n_cigar > cigar_words || md_used + (size_t)x->md_len + 1 > md_bytes) { rc = BMH_E_CIGAR_CAP; goto done; }
+			memcpy(cigar_pool + cig_used, lcig + g->cigar_off, 4 * (size_t)x->n_cigar);
+			memcpy(md_pool + md_used, lmd + g->md_off, (size_t)x->md_len);
+			md_pool[md_used + (size_t)x->md_len] = 0;
+			o->score = x->score, o->n_cigar = x->n_cigar, o->NM = x->NM, o->tries = x->tries;
+			o->cigar_off = (uint32_t)cig_used, o->md_off = (uint32_t)md_used, o->md_len = (uint32_t)x->md_len;
+			cig_used += (size_t)x->n_cigar, md_used += (size_t)x->md_len + 1;
+			continue;
+		}
 		if (x->flags) { ++n_redo; continue; }
 		if (cig_used + (size_t)x->n_cigar > cigar_words || md_used + (size_t)x->md_len + 1 > md_bytes) { rc = BMH_E_CIGAR_CAP; goto done; }
 		memcpy(cigar_pool + cig_used, cout + (size_t)v * SMALL_CAP, 4 * (size_t)x->n_cigar);
@@ -425,10 +458,13 @@ static int reg2cigar_region_records(bmh_ctx_t *ctx, const bmh_params_t *p, int64
 			goto done;
 		for (j = 0; j < n_redo; ++j) res[redo_of[j]] = redo_res[j];
 	}
+	bmh_ctx_set_reg2cigar_stats_(ctx, n_req, n_long, n_redo);
+	(void)__sync_fetch_and_add(&g_long_device, (long long)n_long), (void)__sync_fetch_and_add(&g_redone_host, (long long)n_redo);
 	if (trace)
-		fprintf(stderr, "[bwamem_hip] bmh_reg2cigar_batch %lld regions, region records: layout + query windows %.1f ms, upload + GPU call %.1f ms, packing %.1f ms (%lld tasks, %lld regions redone with host copies)\n",
-		        (long long)n_req, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3, (long long)n_tasks, (long long)n_redo);
+		fprintf(stderr, "[bwamem_hip] bmh_reg2cigar_batch %lld regions, region records: layout + query windows %.1f ms, upload + GPU call %.1f ms, packing %.1f ms (%lld tasks, %lld regions finished on the device, %lld regions redone with host copies)\n",
+		        (long long)n_req, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3, (long long)n_tasks, (long long)n_long, (long long)n_redo);
 done:
+	free(longs), free(lcig), free(lmd);
 	free(rq), free(rr), free(of), free(tasks), free(rpool), free(cout), free(mout), free(redo_req), free(redo_res), free(redo_of);
 	return rc;
 }
@@ -450,5 +486,9 @@ int bmh_reg2cigar_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, const
 	}
 	if (!host_only && bmh_ctx_has_pac_(ctx, pac, l_pac))
 		return reg2cigar_region_records(ctx, p, l_pac, pac, reads, n_req, reqs, res, cigar_pool, cigar_words, md_pool, md_bytes);
-	return reg2cigar_host_copies(ctx, p, l_pac, pac, reads, n_req, reqs, res, cigar_pool, cigar_words, &cig_used, md_pool, md_bytes, &md_used);
+	{
+		const int rc = reg2cigar_host_copies(ctx, p, l_pac, pac, reads, n_req, reqs, res, cigar_pool, cigar_words, &cig_used, md_pool, md_bytes, &md_used);
+		if (!rc) bmh_ctx_set_reg2cigar_stats_(ctx, n_req, 0, n_req);
+		return rc;
+	}
 }

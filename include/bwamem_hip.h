@@ -444,6 +444,47 @@ int bmh_region_cigar_batch(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readp
                            size_t task_cigar_words, int cig_cap, int md_cap, bmh_region_res_t *results, uint32_t *cigar_out,
                            char *md_out);
 
+/* ---- the same call with no region left to the caller: a region record of any CIGAR and MD length.  The regions bmh_region_cigar_batch
+ * would flag are finished on the device behind it, where the oriented copies already lie: their final try runs once more with exactly
+ * n_cigar slots in one dense CIGAR pool (through the same dispatcher: lane, wave or ring kernel by shape), NM and MD are walked there
+ * (host/regfinish_core.h), and the MD bytes go into one dense MD pool, without NUL, as in the slots.
+ *   - A region that call would not flag comes back exactly as from it, bytes of the three arrays included.
+ *   - A region it would flag: results[k] holds the exact score, n_cigar, tries, NM and md_len; flags has BMH_REGION_LONG beside the cut
+ *     bit or bits; its slots in cigar_out / md_out are unspecified; longs[] -- ascending by region -- names its n_cigar words in
+ *     long_cigar and its md_len bytes in long_md.  A region whose MD alone was cut has its CIGAR in the pool all the same.
+ *   - *longs, *long_cigar and *long_md are malloc'd and the caller's to free(); all three are NULL and *n_long is 0 when nothing was
+ *     flagged, and such a call enqueues and waits exactly as bmh_region_cigar_batch does.  Otherwise the long round adds two waits
+ *     (the MD pool's size, the download).
+ *   - Both pools are dense: the last entry's data ends them.  Behind each the call leaves BMH_REGION_LONG_GUARD bytes of 0xA5 that
+ *     were set on the device before the long round's kernels ran and came back with the pool; the call checks them (BMH_E_HIP).
+ *   - On any error nothing stays allocated and no output is written.  BMH_E_RANGE when the flagged regions' n_cigar sum to more than
+ *     2^32 - 1 words (the tasks' cigar_off is 32 bits wide), before the long round is enqueued, and -- as from the old call -- for a
+ *     task no kernel takes; BMH_E_ARG without a resident reference, and if the rerun of a try disagrees with its first run. */
+#define BMH_REGION_LONG_GUARD 16
+#define BMH_REGION_LONG 4u /* finished by the long round: CIGAR and MD are in the pools bmh_region_cigar_batch_long returned */
+typedef struct bmh_region_long { /* 24 bytes */
+	int64_t region;     /* index into reqs / results */
+	uint64_t cigar_off; /* first word in long_cigar */
+	uint64_t md_off;    /* first byte in long_md    */
+} bmh_region_long_t;
+int bmh_region_cigar_batch_long(bmh_ctx_t *ctx, const uint8_t *readpool, size_t readpool_bytes, size_t opool_bytes,
+                                const bmh_region_req_t *reqs, int64_t n_req, const bmh_glb_task_t *tasks, int64_t n_tasks,
+                                size_t task_cigar_words, int cig_cap, int md_cap, bmh_region_res_t *results, uint32_t *cigar_out,
+                                char *md_out, bmh_region_long_t **longs, int64_t *n_long, uint32_t **long_cigar, char **long_md);
+/* Of the context's last successful bmh_region_cigar_batch_long: regions the long round finished, the words and bytes of its two pools,
+ * and with bmh_set_kernel_timing on the duration of its kernels (0 when nothing was flagged), else -1.  All -1 before the first call. */
+int bmh_last_region_long_stats(const bmh_ctx_t *ctx, int64_t *regions, int64_t *cigar_words, int64_t *md_bytes, float *kernel_ms);
+
+/* Per context, off by default: bmh_reg2cigar_batch -- and through it pass B of phase 2 in all its forms, which redo the regions
+ * past their slots with it -- finishes the regions whose CIGAR or MD outgrow the region record's slots through
+ * bmh_region_cigar_batch_long, instead of redoing them with oriented copies made on the host.  The records and bytes it returns
+ * are the same; where they lie in the two pools may differ.  Without a resident reference, or under BMH_REG2CIGAR_HOST=1, the call
+ * takes the path with host copies as before. */
+int bmh_ctx_set_region_long(bmh_ctx_t *ctx, int on);
+/* Of the context's last bmh_reg2cigar_batch that reached the device: the regions it was given, those the long round finished and
+ * those redone with host copies (every region, on the path without the region record).  All -1 before the first call. */
+int bmh_last_reg2cigar_stats(const bmh_ctx_t *ctx, int64_t *regions, int64_t *long_device, int64_t *redone_host);
+
 /* Counters of the last bmh_chain2aln_batch call (for the bench / logs). */
 typedef struct bmh_driver_stats {
 	int64_t rounds, ext_tasks, seeds_extended, seeds_skipped;

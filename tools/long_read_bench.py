@@ -14,7 +14,9 @@ Cells are band cells, sum of tlen * min(qlen, 2w+1) per task (an upper bound of 
 --sam [LO-HI] adds a `bwa mem` single-end run on reads of LO-HI bases (default 8500-9500, at --sam-scoring, default "-A 4"):
 REF (the compiled reference) against DUT (the preload shim with BMH_WIDE_EXT=1), wall time of each and whether the SAM is
 identical (minus @PG).  Reads past 10 kb go through the band-ring kernel in phase 2, e.g. --sam 20000-40000 --sam-scoring "".
-Usage: python tools/long_read_bench.py [--steps 5] [--warmup 1] [--shapes A10_4kb,glb_w200,...] [--sam [LO-HI]]
+--dut-stderr FILE keeps what the shim writes in that run (with BMH_VERBOSE=1 BMH_DRIVER_TRACE=1 in the environment: its counters and
+the drivers' trace lines); the shim's own switches, e.g. BMH_REGION_LONG=1, are taken from the environment as well.
+Usage: python tools/long_read_bench.py [--steps 5] [--warmup 1] [--shapes A10_4kb,glb_w200,...] [--sam [LO-HI]] [--dut-stderr FILE]
 """
 import argparse
 import json
@@ -106,7 +108,7 @@ def measure(name, steps, warmup):
             "band_cells_per_s": round(cells / dt, 1), "wide_kernel_ms": round(wide_ms, 3), "lds_kernel_ms": round(bins[5], 3)}
 
 
-def sam_run(threads, lens=(8500, 9500), scoring=("-A", "4"), n_reads=200):
+def sam_run(threads, lens=(8500, 9500), scoring=("-A", "4"), n_reads=200, dut_stderr=None):
     rng = np.random.default_rng(43)
     tmp = tempfile.mkdtemp(prefix="bmh_longsam_")
     genome = kswgen.rand_seq(rng, 2_000_000)
@@ -123,8 +125,8 @@ def sam_run(threads, lens=(8500, 9500), scoring=("-A", "4"), n_reads=200):
             env.update(LD_PRELOAD=load_package().DROPIN_PATH, BMH_WIDE_EXT="1")
         path = os.path.join(tmp, f"{who}.sam")
         t0 = time.perf_counter()
-        with open(path, "w") as f:
-            subprocess.run([reflib.REF_BWA, "mem", "-v", "1", "-t", str(threads)] + list(scoring) + [fa, fq], stdout=f, stderr=subprocess.DEVNULL,
+        with open(path, "w") as f, open(dut_stderr if who == "dut" and dut_stderr else os.devnull, "w") as err:
+            subprocess.run([reflib.REF_BWA, "mem", "-v", "1", "-t", str(threads)] + list(scoring) + [fa, fq], stdout=f, stderr=err,
                            env=env, check=True, timeout=1200)
         out[who + "_wall_s"] = round(time.perf_counter() - t0, 3)
         out[who] = [l for l in open(path) if not l.startswith("@PG")]
@@ -141,6 +143,8 @@ def main():
     ap.add_argument("--sam-scoring", default="-A 4")
     ap.add_argument("--sam-reads", type=int, default=200)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--dut-stderr", default=None, metavar="FILE",
+                    help="keep what the shim writes in the --sam run (BMH_VERBOSE, BMH_DRIVER_TRACE; BMH_REGION_LONG=1 in the environment is the shim's)")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:  # one shape in this process (the second process of the in-range comparison)
@@ -155,7 +159,7 @@ def main():
         res["inrange_on_wide_kernel"] = json.loads(r.stdout.strip().splitlines()[-1])
     if a.sam:
         lo, hi = (int(x) for x in a.sam.split("-"))
-        res["bwa_mem_long_se"] = sam_run(a.threads, (lo, hi), tuple(a.sam_scoring.split()), a.sam_reads)
+        res["bwa_mem_long_se"] = sam_run(a.threads, (lo, hi), tuple(a.sam_scoring.split()), a.sam_reads, a.dut_stderr)
     print(json.dumps(res))
 
 
