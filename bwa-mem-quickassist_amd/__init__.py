@@ -201,6 +201,7 @@ def lib():
         L.bmh_last_extend_bin_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_last_global_bin_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.bmh_last_global_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.bmh_last_global_bin_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_ctx_set_extend_rows.argtypes = [C.c_void_p, C.c_int64]
         L.bmh_last_extend_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bmh_last_extend_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -426,6 +427,13 @@ class Context:
         bands = np.zeros(int(n), dtype=np.uint8)
         self._check(lib().bmh_last_global_bands(self._h, _ptr(bands), int(n)))
         return bands
+
+    def last_global_bin_counts(self):
+        """Diagnostic: the tasks of the most recent global launch per dispatcher bin (uint32 x 8; bins 6 and 7 are the exact-band
+        kernel's).  Raises once a later call has sorted tasks of its own (bmh_last_global_bin_counts)."""
+        counts = np.zeros(8, dtype=np.uint32)
+        self._check(lib().bmh_last_global_bin_counts(self._h, _ptr(counts)))
+        return counts
 
     def set_extend_rows(self, cap):
         """Diagnostic: plain extension launches record the rows each lane-kernel task ran, for task indices below cap; 0 turns it

@@ -301,6 +301,7 @@ int bmh_ctx_create(bmh_ctx_t **out, int device)
 	if (const char *m = getenv("BMH_GL_FAST")) ctx->glb_fast = atoi(m) != 0;
 	if (const char *m = getenv("BMH_GLB_C32")) ctx->glb_c32 = atoi(m) != 0; // (A/B knob)
 	if (const char *m = getenv("BMH_GLB_NARROW")) ctx->glb_narrow = atoi(m) != 0; // (A/B knob)
+	if (const char *m = getenv("BMH_GLB_EXACT")) ctx->glb_exact = atoi(m) >= 7 ? 7 : atoi(m) >= 3 ? 3 : 0; // (A/B knob)
 	if (const char *m = getenv("BMH_GRID_MULT")) ctx->grid_mult = atoi(m) > 0 ? atoi(m) : 1;
 	if (const char *m = getenv("BMH_EXT_SCHED")) ctx->ext_sched = atoi(m) >= 0 && atoi(m) <= 4 ? atoi(m) : -1;
 	*out = ctx;
@@ -628,6 +629,15 @@ int bmh_last_global_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n)
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
 	BMH_HIP(ctx, hipMemcpy(bands, ctx->d_gband.p, (size_t)n, hipMemcpyDeviceToHost));
+	return BMH_OK;
+}
+
+int bmh_last_global_bin_counts(bmh_ctx_t *ctx, uint32_t counts[8])
+{
+	if (!ctx || !counts || !ctx->gbins_valid || !ctx->d_bins.p) return BMH_E_ARG;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	BMH_HIP(ctx, hipMemcpy(counts, ctx->d_bins.p, kSortBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return BMH_OK;
 }
 
@@ -1439,6 +1449,7 @@ int bmh_ctx_reserve_device(bmh_ctx_t *ctx, size_t pool_bytes, int64_t max_tasks,
 	const size_t N = (size_t)max_tasks;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	if (ctx->glb_narrow && (1 + (size_t)kSortBins) * N + 16 > ctx->d_gband.cap) ctx->gband_n = 0; // (growing drops the last launch's bands)
+	if ((16 + (size_t)kSortBins * kSortKeysHost + (N + 1) / 2 + 1 + (size_t)kSortBins * N) * 4 > ctx->d_bins.cap) ctx->gbins_valid = false; // (... and its bin sizes)
 	if ((rc = ensure(ctx, ctx->d_pool, pool_bytes + 16)) || (rc = ensure(ctx, ctx->d_tasks, N * 40 + 64)) || (rc = ensure(ctx, ctx->d_res, N * 32 + 64)) ||
 	    (rc = ensure(ctx, ctx->d_cigar, (cigar_words + 4) * 4)) ||
 	    (rc = ensure(ctx, ctx->d_bins, (16 + (size_t)kSortBins * kSortKeysHost + (N + 1) / 2 + 1 + (size_t)kSortBins * N) * 4)) ||
@@ -1458,7 +1469,7 @@ int bmh_ctx_reserve_kernels(bmh_ctx_t *ctx, int seed_reads, int seed_read_len, i
 	}
 	if (global_tasks > 0) { // the lane kernels' direction slab (global_lane.hip): resident waves x rows x 8 blocks x 256 bytes
 		const size_t grid = std::min<size_t>(((size_t)global_tasks + 63) / 64, (size_t)std::max(ctx->ncu, 1) * 4 * 2);
-		if ((rc = ensure(ctx, ctx->d_zslab, grid * (size_t)std::min(global_rows, 512) * 8 * 256))) return rc;
+		if ((rc = ensure(ctx, ctx->d_zslab, grid * (size_t)std::min(global_rows, 512) * 8 * 256))) return rc; // (global_narrow.hip: four times the waves, two blocks each: the same)
 	}
 	return BMH_OK;
 }

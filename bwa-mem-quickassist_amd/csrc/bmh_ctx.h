@@ -37,6 +37,9 @@ struct bmh_ctx {
 	int glb_fast = 1;   // unmasked body for blocks inside every lane's band (env BMH_GL_FAST=0 turns it off)
 	int glb_narrow = 1; // lane kernels run each task on the band its result needs (host/glbband_core.h; env BMH_GLB_NARROW=0 turns it off)
 	int glb_c32 = 1;    // bands up to 15 run on the 32-slot instantiation, four waves per SIMD (env BMH_GLB_C32=0: on the 64-slot one)
+	int glb_exact = 7;  // bands of 0..3 (level 3) and of 4..7 (level 7) run on global_narrow_kernel, each row on exactly its 2w+1 cells
+	                    // (global_narrow.hip; env BMH_GLB_EXACT=0|3|7, 0 = the bins as they were)
+	bool gbins_valid = false; // the sort workspace still holds the bin sizes of the last global launch (bmh_last_global_bin_counts)
 	DevBuf d_gband;     // ... those bands: n bytes by input position, then kSortBins x n bytes parallel to the sort's lists
 	int64_t gband_n = 0; // tasks of the last global launch if its band pass ran, else 0 (bmh_last_global_bands)
 	int sw_wave = 1;  // batches of up to 32 k tasks: one wave per task (sw_wave.hip); env BMH_SW_WAVE=0 turns it off
@@ -303,9 +306,11 @@ int sort_tasks_finish(bmh_ctx *ctx, int64_t n, const uint32_t *d_order, unsigned
 int launch_global_lane(bmh_ctx *ctx, int c, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n,
                        bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, const uint32_t *d_count,
                        int rows_cap, const uint8_t *d_band = nullptr);
+int launch_global_narrow(bmh_ctx *ctx, int wlo, const uint8_t *d_pool, const bmh_glb_task_t *d_tasks, int64_t n, bmh_glb_result_t *d_res,
+                         uint32_t *d_cigar, const uint32_t *d_order, const uint32_t *d_count, int rows_cap, const uint8_t *d_band = nullptr);
 constexpr int kExtBins = 6;        // length bins of the extension dispatcher (the 16-bit kernels)
 constexpr int kWideBin = 6;        // ... and the int32 kernel's bin, used only with bmh_ctx_set_wide_extension on
-constexpr int kSortBins = 8;       // bins the shared counting sort can tell apart (extension 6, global 6, Smith-Waterman 8)
+constexpr int kSortBins = 8;       // bins the shared counting sort can tell apart (extension 6, global 8, Smith-Waterman 8)
 constexpr int kGrpTcapHost = 1024; // == kGrpTcap in extend_grp.hip
 
 // ---- the extension dispatcher's binning rule, for every kernel that fills binkey[] and the histogram: sort_hist_kernel over

@@ -245,6 +245,7 @@ static_assert(kSortKeys == kSortKeysHost, "keep bmh_ctx.h in sync");
 int sort_tasks_begin(bmh_ctx *ctx, int64_t n, uint32_t **counts, uint32_t **lists)
 {
 	const size_t N = (size_t)n, hist_words = (size_t)kSortBins * kSortKeys;
+	ctx->gbins_valid = false; // the counters of the last global launch go with the workspace (launch_global sets it again for its own)
 	int rc = ensure(ctx, ctx->d_bins, (16 + hist_words + (N + 1) / 2 + 1 + (size_t)kSortBins * N) * 4);
 	if (rc) return rc;
 	*counts = (uint32_t *)ctx->d_bins.p;

@@ -18,6 +18,7 @@
 #include "bmh_ctx.h"
 #include "bmh_device.h"
 #include "../host/glbband_core.h"
+#include "../host/glbbin_core.h"
 
 namespace bmh {
 
@@ -253,6 +254,8 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 
 // ---- dispatcher -----------------------------------------------------------------------------------
 // (w below: the band the lane kernels run the task on -- the band pass's w_eff, or the task's own with BMH_GLB_NARROW=0)
+// bin 6: w <= 3   -> global_narrow_kernel     (eight waves per SIMD, each row on exactly its 2w+1 cells; BMH_GLB_EXACT >= 3)
+// bin 7: w 4..7   -> global_narrow_kernel     (BMH_GLB_EXACT=7; the rule: host/glbbin_core.h)
 // bin 5: w <= 15  -> global_lane_kernel<32>   (four waves per SIMD; with BMH_GLB_C32=0 these stay in bin 0)
 // bin 0: w <= 31  -> global_lane_kernel<64>   (64 tasks per wave, band-relative registers)
 // bin 1: w <= 63  -> global_lane_kernel<128>
@@ -321,7 +324,7 @@ __global__ __launch_bounds__(256) void glb_sort_hist_kernel(const bmh_glb_task_t
                                                             const uint32_t *__restrict__ order, long long n,
                                                             uint32_t *__restrict__ hist, uint16_t *__restrict__ binkey,
                                                             DevParams P, int lane_ok, int rows_cap, int lds_qcap,
-                                                            const uint8_t *__restrict__ band, int c32)
+                                                            const uint8_t *__restrict__ band, int c32, int exact)
 {
 	__shared__ uint32_t lh[kSortBins * kSortKeysHost];
 	for (int t = threadIdx.x; t < kSortBins * kSortKeysHost; t += 256) lh[t] = 0;
@@ -335,13 +338,14 @@ __global__ __launch_bounds__(256) void glb_sort_hist_kernel(const bmh_glb_task_t
 			// the band pass has been here (band != null): the lane kernels run the task on band[k], so that picks the bin and the key.
 			// It only ever narrows, so the host's gates (which lane kernels are launched at all) still hold
 			if (band) w = band[k];
-			bin = c32 && w <= 15 ? 5 : w <= 31 ? 0 : w <= 47 ? 3 : (w <= 63 ? 1 : 2);
+			bin = bmh_glb_lane_bin(w, c32, exact);
 		}
 		if (bin == 2 && qlen > lds_qcap) bin = 4;
 		// inside a lane bin: rows first (lanes of a wave run until their longest target ends), then band width (a wave
 		// computes and stores the 8-slot blocks that ANY of its lanes needs, and its lanes' tracebacks share cache lines
 		// when they sit in the same block)
-		const int bk = bin * kSortKeysHost + (bin != 2 && bin != 4 ? (min(tlen >> 3, 127) << 4 | (min(w, 63) >> (bin == 5 ? 0 : bin == 0 ? 1 : 2) & 15)) : 0);
+		// bins 6 and 7 the other way round, band first: a wave of global_narrow_kernel runs one row pass per band among its lanes
+		const int bk = bin * kSortKeysHost + bmh_glb_sort_key(bin, tlen, w);
 		binkey[k] = (uint16_t)bk;
 		atomicAdd(&lh[bk], 1u);
 	}
@@ -354,7 +358,7 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
                   bmh_glb_result_t *d_res, uint32_t *d_cigar, const uint32_t *d_order, int qmax, int tmax,
                   int wmax, int wgate, const GlbLongShape *lg)
 {
-	ctx->gband_n = 0;
+	ctx->gband_n = 0, ctx->gbins_valid = false;
 	if (n <= 0) return BMH_OK;
 	int rc;
 	const size_t N = (size_t)n;
@@ -410,12 +414,17 @@ int launch_global(bmh_ctx *ctx, const uint8_t *d_pool, const bmh_glb_task_t *d_t
 		ctx->gband_n = n;
 	}
 	hipLaunchKernelGGL(glb_sort_hist_kernel, dim3((unsigned)cg), dim3(256), 0, ctx->stream, d_tasks, d_order, (long long)n, hist,
-	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap, longb ? kGlbLdsQcap : 65535, band, ctx->glb_c32);
+	                   binkey, ctx->dev, lane_ok ? 1 : 0, rows_cap, longb ? kGlbLdsQcap : 65535, band, ctx->glb_c32, ctx->glb_exact);
 	if ((rc = sort_tasks_finish(ctx, n, d_order, (unsigned)cg, nullptr, nullptr, band, blists))) return rc;
+	ctx->gbins_valid = true;
 	const bool tm = ctx->timing;
 	if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
 	if (lane_ok) {
 		if (tm) BMH_HIP(ctx, hipEventRecord(ctx->ev_gbin[0], ctx->stream));
+		for (int b = 7; b >= 6; --b) // the exact-band bins, the wider one first
+			if (ctx->glb_exact >= (b == 7 ? kGlbExactAll : kGlbExactLow) &&
+			    (rc = launch_global_narrow(ctx, b == 7 ? 4 : 0, d_pool, d_tasks, n, d_res, d_cigar, lists + b * N, counts + b, rows_cap, blists ? blists + b * N : nullptr)))
+				return rc;
 		if (ctx->glb_c32 && (rc = launch_global_lane(ctx, 32, d_pool, d_tasks, n, d_res, d_cigar, lists + 5 * N, counts + 5, rows_cap,
 		                                             blists ? blists + 5 * N : nullptr)))
 			return rc;

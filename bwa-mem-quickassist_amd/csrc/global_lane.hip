@@ -267,7 +267,9 @@ __global__ __launch_bounds__(64, (C <= 32 ? BMH_GL_WAVES32 : C <= 64 ? BMH_GL_WA
 						for (int k = 0; k < len; ++k) T[k] = (ss >> bit & 1) ? T[2 * k + 1] : T[2 * k];
 					pick = (ss >> 5) == c0 / 32 ? T[0] : pick;
 				}
-				if (live && i == tlen - 1 && ss >= 0 && ss < C) score = (int)(int16_t)(pick & 0xffff);
+				// (a slot past 2w is no cell: with w < qlen - tlen the last row ends short of column qlen and eh[qlen].h keeps its -inf, while
+				// such a slot of a computed block holds the first-column fill during the first w rows)
+				if (live && i == tlen - 1 && ss >= 0 && ss <= 2 * w) score = (int)(int16_t)(pick & 0xffff);
 			}
 			// slide the query window by one base (row i+1 looks at q[i+1-w+s])
 #pragma unroll

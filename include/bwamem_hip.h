@@ -286,6 +286,12 @@ int bmh_last_global_bin_ms(bmh_ctx_t *ctx, float ms[3]);
  * launched yet, or the workspace was grown since by bmh_ctx_reserve_device).  A call that makes several global launches leaves
  * the last one's bands.  Waits for the stream and copies n bytes; the launches themselves do nothing for it. */
 int bmh_last_global_bands(bmh_ctx_t *ctx, uint8_t *bands, int64_t n);
+/* Diagnostic: how many tasks of the context's most recent global-alignment launch its sort put into each of the dispatcher's eight
+ * bins -- 0, 3, 1, 5: the lane kernels of 64, 96, 128 and 32 slots; 2 and 4: one wave per task; 6 and 7: the exact-band kernel for
+ * bands of 0..3 and 4..7 (BMH_GLB_EXACT).  Read from the sort's workspace where the launch left them: the launch does nothing for
+ * it, the call waits for the stream and copies 32 bytes.  BMH_E_ARG when no global launch has run, or when any later call has used
+ * or grown the sort's workspace (every batch call of the extension, global and Smith-Waterman paths sorts its tasks there). */
+int bmh_last_global_bin_counts(bmh_ctx_t *ctx, uint32_t counts[8]);
 /* Diagnostic: the DP rows each task of a plain extension launch ran.  The lane-per-task kernels end a flank once no later row can
  * change any of its six results (BMH_EXT_STOP=0 in the environment of bmh_ctx_create turns that off), so this is at
  * most what ksw_extend2 runs.  With cap > 0, bmh_extend_batch and bmh_extend_batch_device keep cap x uint16 on the device, indexed as
