@@ -22,6 +22,10 @@ struct DevParams {
 constexpr int kScoreLimit = 32000; // h0 + qlen*max_mat must stay below this (16-bit lanes)
 constexpr int kWideScoreLimit = 1 << 24; // ... and below this in the int32 kernel (extend_wide.hip: 64*e of its scan stays in int32)
 constexpr int kNegInf16 = -16384;  // scan identity for 16-bit-ranged values held in int32
+// The global lane kernels (global_lane.hip, global_narrow.hip) take a task only while glb_lane_domain's bound on |score| of any cell,
+// o_del + o_ins + max(e_del,e_ins)*(qlen+tlen) + max|mat|*max(qlen,tlen), stays below this: every real score lies in (-12000, 12000),
+// their "-inf" is -16384, and what comes out at or below -12000 is therefore "no cell written", never a score.
+constexpr int kGlbLaneWorst = 12000;
 
 // ---- DPP controls (GFX9 encoding) ----
 constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118;

@@ -268,13 +268,15 @@ __global__ __launch_bounds__(64) void global_kernel(const uint8_t *__restrict__ 
 //        (lds_qcap < 65535) -> global_kernel<false, true> (the band ring)
 // Bins and the order inside them (by row count) come from the same device-side counting sort as the extension path.
 // A task may run on a lane kernel when its rows fit the direction slab and no cell can leave the 16-bit range; which one, its band
-// decides.  (The lane kernels take the sign of 16-bit differences such as m - e - o_del: with |m|, |e| < 12000 and the -16384
-// sentinel that stays inside +-32767 as long as the gap-open penalties are not absurd.)
+// decides.  (The lane kernels take the sign of 16-bit differences such as m - e - o_del: with |m| < 12000, e and f no lower than
+// one gap extension below the -16384 sentinel, and o_del + o_ins < 4000 these stay inside +-32767 -- the extension cancels in
+// (m - o - e_x) - (e - e_x), and a large e_x forces short sequences, hence a small m.  tests/test_score_domain_gpu.py runs real
+// scores of -11129 .. +11684, opens of 3999 in sum and extensions up to 2596 through every lane kernel.)
 __device__ __forceinline__ bool glb_lane_domain(const DevParams &P, int qlen, int tlen, int w, int lane_ok, int rows_cap)
 {
 	const int emax = max(P.e_del, P.e_ins), smax = max(P.bias, P.max_mat);
 	const int worst = P.o_del + P.o_ins + emax * (qlen + tlen) + smax * max(qlen, tlen); // |score| bound of any cell
-	return lane_ok && tlen <= rows_cap && worst < 12000 && P.o_del + P.o_ins < 4000 && w >= 0;
+	return lane_ok && tlen <= rows_cap && worst < kGlbLaneWorst && P.o_del + P.o_ins < 4000 && w >= 0;
 }
 
 // The band pass, in front of the sort: band[k] = the band the result of the task at input position k needs (host/glbband_core.h,

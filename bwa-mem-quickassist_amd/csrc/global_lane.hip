@@ -14,7 +14,8 @@
 // left of the band is the virtual column -1 that the next row's column 0 reads diagonally -- or with -inf.
 // "-inf" is -16384: every comparison of the reference that involves MINUS_INF (ksw.c:487) has a finite value on the
 // other side (a cell inside the band always has an in-band diagonal predecessor), so any sentinel below all finite
-// scores reproduces it; the dispatcher sends tasks whose scores could reach -12000 to the int32 wave kernel.
+// scores reproduces it; the dispatcher sends tasks whose scores could reach +-12000 (kGlbLaneWorst) to the int32 wave kernel,
+// and every score inside (-12000, 12000) comes out as the reference's.
 // Direction state: the reference keeps one byte per cell (ksw.c:547-561: 2 bits "where H came from", 2 bits "E continues",
 // 2 bits "F continues", of which 4 bits carry information).  Here a cell costs 4 bits -- the sign bits of the four
 // differences the reference compares (see the fill) -- eight cells (one 8-slot block) per dword, and ONLY the blocks a wave computes are written, to a
@@ -278,7 +279,9 @@ __global__ __launch_bounds__(64, (C <= 32 ? BMH_GL_WAVES32 : C <= 64 ? BMH_GL_WA
 		}
 
 		if (tlen == 0) score = qlen == 0 ? 0 : (qlen <= w ? -(P.o_ins + e_ins * qlen) : kNeg16); // eh[qlen].h of ksw.c:519-522
-		if (score <= kNeg16 / 2) score = -0x40000000; // the reference's MINUS_INF (out-of-domain input only)
+		// No cell written (the band does not reach the last cell, or tlen == 0 with qlen > w): score is still kNeg16, and the reference
+		// returns its MINUS_INF.  A real score of a task the dispatcher admits is above -kGlbLaneWorst (glb_lane_domain), so the test is exact.
+		if (score <= -kGlbLaneWorst) score = -0x40000000;
 
 		// ---- traceback, ksw.c:566-581, one path per lane
 		const uint2 tc = *(const uint2 *)((const uint8_t *)(tasks + idx) + 24); // {cigar_off, cigar_cap}, re-read (see fill_stream)

@@ -246,7 +246,9 @@ __global__ __launch_bounds__(64, (WLO == 0 ? BMH_GN_WAVES_LO : BMH_GN_WAVES_HI))
 			todo &= ~__builtin_amdgcn_ballot_w64(mine);
 		}
 		if (tlen == 0) score = qlen == 0 ? 0 : (qlen <= w ? -(P.o_ins + P.e_ins * qlen) : kNeg16); // eh[qlen].h of ksw.c:519-522
-		if (score <= kNeg16 / 2) score = -0x40000000; // the reference's MINUS_INF (the band does not reach the last cell)
+		// No cell written (the band does not reach the last cell, or tlen == 0 with qlen > w): score is still kNeg16, the reference's
+		// MINUS_INF.  A real score of an admitted task is above -kGlbLaneWorst (glb_lane_domain), so the test is exact.
+		if (score <= -kGlbLaneWorst) score = -0x40000000;
 
 		// ---- traceback, ksw.c:566-581, one path per lane: global_lane_kernel's, every lane on its own band
 		const uint2 tc = *(const uint2 *)((const uint8_t *)(tasks + idx) + 24); // {cigar_off, cigar_cap}

@@ -113,10 +113,13 @@ def assert_seed(got, want, tasks, what=""):
 def assert_glb(res, cig, want, wcig, tasks, what=""):
     bad = np.nonzero(res != want)[0]
     assert len(bad) == 0, f"{what}{len(bad)} of {len(res)} global results differ; first {bad[0]}: task={tasks[bad[0]]} gpu={res[bad[0]]} want={want[bad[0]]}"
-    for k, t in enumerate(tasks):
-        o, n = int(t["cigar_off"]), int(res[k]["n_cigar"])
-        if int(t["cigar_cap"]) and 0 < n <= int(t["cigar_cap"]):
-            assert np.array_equal(cig[o:o + n], wcig[o:o + n]), f"{what}task {k}: CIGAR words differ"
+    # every task's words [cigar_off, cigar_off + n_cigar) where it wanted a CIGAR and it fitted, gathered in one go
+    n, cap = res["n_cigar"].astype(np.int64), tasks["cigar_cap"].astype(np.int64)
+    n = np.where((cap > 0) & (n > 0) & (n <= cap), n, 0)
+    first = np.cumsum(n) - n
+    idx = np.repeat(tasks["cigar_off"].astype(np.int64) - first, n) + np.arange(int(n.sum()))
+    diff = np.nonzero(cig[idx] != wcig[idx])[0]
+    assert len(diff) == 0, f"{what}task {np.searchsorted(first, diff[0], side='right') - 1}: CIGAR words differ"
 
 
 def assert_sw(got, want, tasks, what=""):

@@ -1,9 +1,11 @@
 """Tasks at the edges of the DP kernels' integer domains and routing switches, shared by test_score_domain_cpu.py (oracle vs
 the compiled reference) and test_score_domain_gpu.py (kernels vs the oracle).  The routing functions restate, in Python, the
-conditions the dispatchers use (ext_bin, glb_lane_bin, glb_wave_lds, sw_bin, sw_kernel_of), so that a test can assert that its tasks land on both sides of
-the switch it targets."""
+conditions the dispatchers use (ext_bin, glb_wave_lds, sw_bin, sw_kernel_of; the global dispatcher's lane bins are restated once,
+in glbbin_ref.py), so that a test can assert that its tasks land on both sides of the switch it targets."""
 import numpy as np
 
+import glbband_ref
+import glbbin_ref
 import kswgen
 import kswlib
 
@@ -35,14 +37,11 @@ def ext_bin(qlen, mode=0):
     return 0 if qlen <= 32 else 1 if qlen <= 64 else 2 if qlen <= 128 else 3 if qlen <= 256 else 4 if (qlen <= 512 and mode == 4) else 5
 
 
-def glb_lane_bin(p, qlen, tlen, w, rows_cap):
-    """glb_sort_hist_kernel, global_kernel.hip:227-235: 0/3/1 = lane kernels of 64/96/128 columns, 2 = int32 wave kernel."""
-    emax = max(int(p["e_del"]), int(p["e_ins"]))
-    smax = max(max(0, -int(np.min(p["mat"]))), max_mat(p))
-    worst = int(p["o_del"]) + int(p["o_ins"]) + emax * (qlen + tlen) + smax * max(qlen, tlen)
-    if tlen <= rows_cap and worst < 12000 and int(p["o_del"]) + int(p["o_ins"]) < 4000 and w >= 0:
-        return 0 if w <= 31 else 3 if w <= 47 else 1 if w <= 63 else 2
-    return 2
+def glb_lane_bin(p, qlen, tlen, w, rows_cap, c32=0, exact=0):
+    """The kernel class of a task on band w, from glbband_ref.lane_domain and glbbin_ref.lane_bin: 0/3/1 = the lane kernels' domain at
+    bands up to 31/47/63, 2 = the int32 wave kernel.  c32 and exact switch on the dispatcher's narrower bins 5, 6 and 7, which split
+    class 0 further (glbbin_ref.expected_bins gives a whole batch's bins, with the band pass as well)."""
+    return glbbin_ref.lane_bin(w, c32, exact) if glbband_ref.lane_domain(p, qlen, tlen, w, rows_cap) else 2
 
 
 def glb_wave_lds(tasks):
@@ -227,6 +226,207 @@ def gen_glb_deep(rng, lens=(300, 1200), per=4):
                 t = kswgen.rand_seq(rng, L + int(rng.integers(-30, 30)))
             kswgen._add_glb(pb, q, t, abs(len(q) - len(t)) + int(rng.integers(5, 80)))
     return kswgen.finish_glb(pb)
+
+
+# ---- global: real scores across the lane kernels' 16-bit domain ---------------------------------------------------------
+# Every family below yields (label, params, (pool, tasks, cigar words)) batches, one per scoring, whose tasks ALL satisfy
+# glbband_ref.lane_domain (asserted in _lane_batch): none can drift to the int32 wave kernel.  No task has tlen > qlen + w, where
+# the reference's traceback is undefined.
+
+MINUS_INF = -0x40000000  # ksw.c:487
+GLB_LANE_BINS = (6, 7, 5, 0, 3, 1)
+
+
+def _lane_batch(p, pb):
+    pool, tasks, words = kswgen.finish_glb(pb)
+    assert len(tasks)
+    rows_cap = min(int(tasks["tlen"].max()), glbband_ref.ROWS_CAP)
+    for t in tasks:
+        assert glbband_ref.lane_domain(p, int(t["qlen"]), int(t["tlen"]), int(t["w"]), rows_cap), f"outside the lane domain: {t}"
+        assert int(t["tlen"]) <= int(t["qlen"]) + int(t["w"]), f"tlen > qlen + w: {t}"
+    return pool, tasks, words
+
+
+def _in_domain(p, ql, tl):
+    return tl <= glbband_ref.ROWS_CAP and glb_worst(p, ql, tl) < 12000 and int(p["o_del"]) + int(p["o_ins"]) < 4000
+
+
+def _disjoint(rng, ql, tl):
+    """A query over codes {0,1} and a target over {2,3}: every cell is a mismatch."""
+    return rng.integers(0, 2, ql).astype(np.uint8), rng.integers(2, 4, tl).astype(np.uint8)
+
+
+DEEP_GAPS = ((60, 4, 60, 4), (1000, 4, 1000, 4), (1800, 1, 1800, 1), (3000, 1, 600, 1), (600, 1, 3000, 1))
+DEEP_BANDS = (0, 1, 2, 3, 4, 5, 7, 8, 12, 15)
+
+
+def gen_glb_deep_negative_equal(rng):
+    """b = 64, 100, 127 on all-mismatch pairs of 64..90 bases (the longest the domain admits under each scoring, and a few below) at
+    own bands 0..15, tlen = qlen, qlen +- 1, qlen +- 3 (qlen - tlen > w: the reference's MINUS_INF)."""
+    out = []
+    for b in (64, 100, 127):
+        for od, ed, oi, ei in DEEP_GAPS:
+            p = kswlib.make_params(a=1, b=b, o_del=od, e_del=ed, o_ins=oi, e_ins=ei)
+            top = max(L for L in range(64, 91) if _in_domain(p, L, L))  # (64 is inside under every one of these scorings)
+            pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+            for k, w in enumerate(DEEP_BANDS):
+                for d in (0, 1, -1, 3, -3):  # tlen - qlen
+                    ql = max(64, top - (k + abs(d)) % 3 - max(d, 0))
+                    tl = ql + d
+                    if tl > ql + w or not _in_domain(p, ql, tl):
+                        continue
+                    q, t = _disjoint(rng, ql, tl)
+                    kswgen._add_glb(pb, q, t, w, want_cigar=(k + d) % 5 != 0)
+            out.append((f"b={b} gaps={(od, ed, oi, ei)}", p, _lane_batch(p, pb)))
+    return out
+
+
+def gen_glb_threshold():
+    """A^L against C^L, L = 127, 128, 129 under a=1 b=64: scores -8128, -8192, -8256, either side of half the -16384 sentinel.  At
+    w = 0 under the default gaps; at w = 5 and 12 under gap opens large enough that the all-mismatch diagonal stays the optimum.
+    o_del = o_ins = 1900 puts all three lengths outside the domain (worst = 12182, 12248, 12314); 1740 is the largest open that
+    keeps L = 129 inside (worst = 11994), so the three run under that."""
+    out = []
+    for label, o, bands in (("o=6", 6, (0,)), ("o=1740", 1740, (0, 5, 12))):
+        p = kswlib.make_params(a=1, b=64, o_del=o, e_del=1, o_ins=o, e_ins=1)
+        assert not any(_in_domain(kswlib.make_params(a=1, b=64, o_del=1900, e_del=1, o_ins=1900, e_ins=1), L, L) for L in (127, 128, 129))
+        pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+        for w in bands:
+            for L in (127, 128, 129):
+                kswgen._add_glb(pb, np.zeros(L, np.uint8), np.ones(L, np.uint8), w)
+        out.append((f"threshold {label}", p, _lane_batch(p, pb)))
+    return out
+
+
+# (b, o_del, o_ins, e).  The last three go deeper in the wide bins: a smaller mismatch cost admits longer pairs (251 and 366 rows), and
+# with b*d < min(o_del, o_ins) + 2d a second gap inside the band never pays, so the score stays -(b*min(qlen,tlen) + o + e*d).
+UNEQUAL_SCORINGS = ((60, 999, 3000, 1), (60, 3000, 999, 1), (80, 500, 2500, 1), (90, 1999, 2000, 1),
+                    (30, 999, 3000, 1), (30, 3000, 999, 1), (20, 999, 3000, 1))
+UNEQUAL_DELTAS = (16, 20, 24, 31, 32, 40, 47, 48, 56, 63)
+
+
+def gen_glb_deep_negative_unequal(rng):
+    """Disjoint alphabets with |qlen - tlen| = d and w = d + 0, 1, 2 (<= 63), both signs, at the longest lengths the domain admits."""
+    out = []
+    for b, od, oi, e in UNEQUAL_SCORINGS:
+        p = kswlib.make_params(a=1, b=b, o_del=od, e_del=e, o_ins=oi, e_ins=e)
+        pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+        for d in UNEQUAL_DELTAS:
+            top = max(L for L in range(d + 1, 513) if _in_domain(p, L, L - d))
+            for slack in (0, 1, 2):
+                if d + slack > 63:
+                    continue
+                for ql, tl in ((top, top - d), (top - d, top)):  # an insertion of d bases, a deletion of d bases
+                    q, t = _disjoint(rng, ql, tl)
+                    kswgen._add_glb(pb, q, t, d + slack, want_cigar=slack != 1 or ql > tl)
+        out.append((f"unequal b={b} gaps={(od, e, oi, e)}", p, _lane_batch(p, pb)))
+    return out
+
+
+EMPTY_BANDS = (0, 2, 3, 7, 12, 20, 40, 47, 60, 63)
+
+
+def gen_glb_empty_target(rng):
+    """tlen = 0: the score is eh[qlen].h of ksw.c:519-522, -(o_ins + e_ins*qlen) for qlen <= w and MINUS_INF past the band.  Per band
+    one scoring with o_ins = 3000 and the smallest e_ins that takes qlen = w to -8192 or below (qlen = w + 1 is then still inside the
+    domain); and every shape once under the default gaps."""
+    out = []
+    shapes = [(w, ql) for w in EMPTY_BANDS for ql in sorted({w, w + 1, 1, 3})]
+    for w in EMPTY_BANDS:
+        e = -(-(8192 - 3000) // w) if w else 1
+        p = kswlib.make_params(o_del=6, e_del=1, o_ins=3000, e_ins=e)
+        pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+        for ww, ql in shapes:
+            if ww == w:
+                kswgen._add_glb(pb, kswgen.rand_seq(rng, ql), np.zeros(0, np.uint8), w, want_cigar=ql != 3)
+        out.append((f"empty target w={w} e_ins={e}", p, _lane_batch(p, pb)))
+    p = kswlib.make_params()
+    pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+    for w, ql in shapes:
+        kswgen._add_glb(pb, kswgen.rand_seq(rng, ql), np.zeros(0, np.uint8), w)
+    out.append(("empty target, default gaps", p, _lane_batch(p, pb)))
+    return out
+
+
+POSITIVE_BANDS = (0, 3, 7, 15, 31, 47, 63)
+
+
+def gen_glb_deep_positive(rng):
+    """Identical sequences: a=127 b=127 on 80, 90 and 92 bases (10160 .. 11684), a=21 b=21 on 500 bases (10500)."""
+    out = []
+    p = kswlib.make_params(a=127, b=127)
+    pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+    for L in (80, 90, 92):
+        for w in POSITIVE_BANDS:
+            q = kswgen.rand_seq(rng, L)
+            kswgen._add_glb(pb, q, q.copy(), w)
+    out.append(("a=127", p, _lane_batch(p, pb)))
+    p = kswlib.make_params(a=21, b=21)
+    pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+    for w in (0, 7):
+        q = kswgen.rand_seq(rng, 500)
+        kswgen._add_glb(pb, q, q.copy(), w)
+    out.append(("a=21, 500 bases", p, _lane_batch(p, pb)))
+    return out
+
+
+EXTREME_GAPS = ((6, 1150, 6, 1150), (6, 1150, 6, 3), (3, 2, 6, 1150), (2000, 1, 1999, 1))
+
+
+def gen_glb_extreme_gaps():
+    """Every pair of up to five bases of two letters at every band up to 7 (26 576 tasks) under gap extensions of 1150 and gap opens of
+    1999 + 2000, all inside the domain; and the 11 216 of them that a=100 b=127 with gaps (1999, 900, 2000, 900) leaves inside."""
+    pool, tasks, _ = glbband_ref.exhaustive_set(2, 5, 7)
+    out = []
+    for od, ed, oi, ei in EXTREME_GAPS:
+        p = kswlib.make_params(o_del=od, e_del=ed, o_ins=oi, e_ins=ei)
+        out.append((f"exhaustive gaps={(od, ed, oi, ei)}", p, _lane_subset(p, pool, tasks)))
+        assert len(out[-1][2][1]) == 26576
+    p = kswlib.make_params(a=100, b=127, o_del=1999, e_del=900, o_ins=2000, e_ins=900)
+    out.append(("exhaustive a=100 b=127 gaps=(1999, 900, 2000, 900)", p, _lane_subset(p, pool, tasks)))
+    assert len(out[-1][2][1]) == 11216
+    return out
+
+
+def _lane_subset(p, pool, tasks):
+    """The tasks inside the lane domain (judged with the slab of the whole set: no target here is longer), CIGAR offsets re-packed."""
+    keep = np.array([_in_domain(p, int(t["qlen"]), int(t["tlen"])) for t in tasks])
+    sub = tasks[keep].copy()
+    sub["cigar_off"] = np.cumsum(sub["cigar_cap"]) - sub["cigar_cap"]
+    return pool, sub, int(sub["cigar_cap"].sum())
+
+
+def n_matrix(rng, a, lo):
+    """big_matrix with nine distinct entries in row 4 and column 4 (the N base), none equal to a regular entry of its row or column:
+    a selector that reads another base for N, or N for "no base", changes the score."""
+    while True:
+        m = big_matrix(rng, a, lo).astype(np.int64).reshape(5, 5)
+        edge = np.concatenate([m[4, :], m[:4, 4]])
+        if len(set(edge.tolist())) == 9 and all(m[4, j] not in m[:4, j] and m[i, 4] not in m[i, :4] for i in range(4) for j in range(4)):
+            return m.reshape(25).astype(np.int8)
+
+
+N_BANDS = (0, 1, 2, 3, 4, 5, 6, 7, 12)
+
+
+def gen_glb_n_bases(rng, per=6):
+    """Queries of 20..90 bases with 15 % N against mutated copies at own bands 0..7 and 12, under general matrices with entries down
+    to -120 (a = 100; with gap costs (40, 3, 30, 4) a pair of 90 bases has worst = 11590) and to -60 (a = 50, default gaps)."""
+    out = []
+    for a, lo, gaps in ((100, -120, dict(o_del=40, e_del=3, o_ins=30, e_ins=4)), (50, -60, dict())):
+        p = kswlib.make_params(a=a, mat=n_matrix(rng, a, lo), **gaps)
+        pb = kswgen.PoolBuilder(kswlib.GLB_TASK)
+        for w in N_BANDS:
+            for k in range(per):
+                ql = (20, 90)[k] if k < 2 else int(rng.integers(20, 91))
+                q = kswgen.rand_seq(rng, ql, p_n=0.15)
+                t = kswgen.mutate(rng, q, 0.1, 0.03 if w else 0.0, 0.03 if w else 0.0, 3)
+                t[rng.random(len(t)) < 0.05] = 4
+                tl = int(np.clip(len(t), max(1, ql - w), min(ql + w, 90)))
+                t = np.concatenate([t, kswgen.rand_seq(rng, max(0, tl - len(t)), p_n=0.15)])[:tl]
+                kswgen._add_glb(pb, q, t.astype(np.uint8), w, want_cigar=k != 3)
+        out.append((f"N bases a={a}", p, _lane_batch(p, pb)))
+    return out
 
 
 # ---- local Smith-Waterman (ksw_align2) --------------------------------------------------------------------------------

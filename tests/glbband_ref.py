@@ -52,15 +52,26 @@ def lane_domain(p, ql, tl, w, rows_cap):
     return tl <= rows_cap and worst < 12000 and od + oi < 4000 and w >= 0
 
 
+def lane_domain_all(p, tasks, rows_cap):
+    """lane_domain of every task of a batch at once."""
+    mat = np.asarray(p["mat"], dtype=np.int64)
+    od, ed, oi, ei = (int(p[k]) for k in ("o_del", "e_del", "o_ins", "e_ins"))
+    smax = max(int(-mat.min()), int(max(mat.max(), 0)))
+    ql, tl = tasks["qlen"].astype(np.int64), tasks["tlen"].astype(np.int64)
+    worst = od + oi + max(ed, ei) * (ql + tl) + smax * np.maximum(ql, tl)
+    return (tl <= rows_cap) & (worst < 12000) & (od + oi < 4000) & (tasks["w"].astype(np.int64) >= 0)
+
+
 def expected_bands(p, pool, tasks, rows_cap=None):
     """The byte of every task, in the order given: the rule's band where the rule and the lane kernels' domain apply, else the task's
     own w; 255 for everything past a byte.  rows_cap: of a host-fed batch (the default) the longest target, up to ROWS_CAP."""
     if rows_cap is None:
         rows_cap = min(int(tasks["tlen"].max()), ROWS_CAP) if len(tasks) else ROWS_CAP
     out = np.zeros(len(tasks), dtype=np.uint8)
+    dom = lane_domain_all(p, tasks, rows_cap)
     for k, x in enumerate(tasks):
         ql, tl, w = int(x["qlen"]), int(x["tlen"]), int(x["w"])
-        if lane_domain(p, ql, tl, w, rows_cap):
+        if dom[k]:
             qo, to = int(x["q_off"]), int(x["t_off"])
             w = w_eff(p, pool[qo:qo + ql], pool[to:to + tl], w)
         out[k] = 255 if w < 0 or w > 255 else w

@@ -28,16 +28,19 @@ def sort_key(b, tlen, w):
     return min(rows, 127) << 4 | (min(w, 63) >> (0 if b == 5 else 1 if b == 0 else 2) & 15)
 
 
-def expected_bins(p, pool, tasks, narrow=True, c32=1, exact=EXACT_ALL, rows_cap=None):
-    """(bin, band the lane kernels run on) of every task of a batch whose queries all fit the wave kernel's LDS row (no bin 4)."""
+def expected_bins(p, pool, tasks, narrow=True, c32=1, exact=EXACT_ALL, rows_cap=None, bands=None):
+    """(bin, band the lane kernels run on) of every task of a batch whose queries all fit the wave kernel's LDS row (no bin 4).
+    bands: glbband_ref.expected_bands of the batch, where the caller has them already."""
     if rows_cap is None:
         rows_cap = min(int(tasks["tlen"].max()), glbband_ref.ROWS_CAP) if len(tasks) else glbband_ref.ROWS_CAP
-    bands = glbband_ref.expected_bands(p, pool, tasks, rows_cap) if narrow else None
+    if narrow and bands is None:
+        bands = glbband_ref.expected_bands(p, pool, tasks, rows_cap)
     bins, ws = np.zeros(len(tasks), dtype=np.int64), np.zeros(len(tasks), dtype=np.int64)
+    dom = glbband_ref.lane_domain_all(p, tasks, rows_cap)
     for k, x in enumerate(tasks):
-        ql, tl, w = int(x["qlen"]), int(x["tlen"]), int(x["w"])
+        w = int(x["w"])
         b = 2
-        if glbband_ref.lane_domain(p, ql, tl, w, rows_cap):
+        if dom[k]:
             if narrow:
                 w = int(bands[k])
             b = lane_bin(w, c32, exact)

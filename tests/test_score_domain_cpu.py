@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import domaingen as dg
+import glbbin_ref as br
 import kswgen
 import kswlib
 
@@ -67,6 +68,88 @@ def test_global_routing_edges():
     _check_glb(p, pool, tasks)
     pool, tasks, _ = dg.gen_glb_shape_edges(rng)
     _check_glb(kswlib.make_params(), pool, tasks)
+
+
+# ---- global: real scores across the lane kernels' 16-bit domain (domaingen's families) --------------------------------------------
+# Besides pinning the oracle to the reference, each case asserts what test_score_domain_gpu.py relies on: which of the dispatcher's
+# lane bins (glbbin_ref.expected_bins on the tasks' own bands) the family's deep scores reach, from the REFERENCE's scores.
+
+def _family(batches):
+    """Reference == oracle on every batch; returns the reference scores and the bins of all tasks (own bands, every bin switched on)."""
+    scores, bins = [], []
+    for label, p, (pool, tasks, _) in batches:
+        scores.append(_check_glb(p, pool, tasks)["score"])
+        bins.append(br.expected_bins(p, pool, tasks, narrow=False)[0])
+        assert np.isin(bins[-1], dg.GLB_LANE_BINS).all(), label
+    return np.concatenate(scores).astype(np.int64), np.concatenate(bins)
+
+
+def _deep(scores, bins, b, at=-8192):
+    """Real scores (not MINUS_INF) of bin b at or below `at`."""
+    return int(((bins == b) & (scores <= at) & (scores > dg.MINUS_INF)).sum())
+
+
+def test_global_deep_negative_equal_lengths():
+    """All-mismatch pairs at own bands 0..15: down to -11129, and at least three real scores <= -8192 in each of bins 6, 7 and 5."""
+    scores, bins = _family(dg.gen_glb_deep_negative_equal(np.random.default_rng(9100)))
+    for b in (6, 7, 5):
+        assert _deep(scores, bins, b) >= 3, b
+    assert scores[scores > dg.MINUS_INF].min() <= -11000 and (scores == dg.MINUS_INF).sum() >= 15  # (qlen - tlen = 3 at bands 0..2)
+
+
+def test_global_threshold_of_half_the_sentinel():
+    """-8128, -8192 and -8256 at band 0 (bin 6), and under gap opens of 1740 at bands 0, 5 (bin 7) and 12 (bin 5)."""
+    scores, bins = _family(dg.gen_glb_threshold())
+    assert scores.tolist() == [-8128, -8192, -8256] * 4 and bins.tolist() == [6] * 6 + [7] * 3 + [5] * 3
+
+
+def test_global_deep_negative_unequal_lengths():
+    """|qlen - tlen| of 16..63 at bands up to 63: bin 0 (<64>) down to -10036, bin 3 (<96>) to -9711, bin 1 (<128>) to -9407."""
+    scores, bins = _family(dg.gen_glb_deep_negative_unequal(np.random.default_rng(9101)))
+    low = {b: int(scores[bins == b].min()) for b in (0, 3, 1)}
+    assert set(bins) == {0, 3, 1} and (scores > dg.MINUS_INF).all()
+    assert low == {0: -10036, 3: -9711, 1: -9407}
+    for b in (0, 3, 1):
+        assert _deep(scores, bins, b) >= 3, b
+
+
+def test_global_empty_targets():
+    """tlen = 0: a real score <= -8192 in every lane bin, a genuine MINUS_INF (qlen = w + 1) in every lane bin, and 0 for qlen = 0."""
+    batches = dg.gen_glb_empty_target(np.random.default_rng(9102))
+    scores, bins = _family(batches)
+    qlen = np.concatenate([b[2][1]["qlen"] for b in batches])
+    w = np.concatenate([b[2][1]["w"] for b in batches])
+    for b in dg.GLB_LANE_BINS:
+        assert _deep(scores, bins, b) >= 1 and ((bins == b) & (scores == dg.MINUS_INF)).sum() >= 1, b
+    assert ((scores == dg.MINUS_INF) == (qlen > w)).all() and (scores[qlen == 0] == 0).all() and (qlen == 0).sum() == 2
+
+
+def test_global_deep_positive():
+    """Identical sequences under a=127 and a=21: 10160 .. 11684, and 10000 or more in every lane bin."""
+    scores, bins = _family(dg.gen_glb_deep_positive(np.random.default_rng(9103)))
+    assert scores.min() == 10160 and scores.max() == 11684
+    for b in dg.GLB_LANE_BINS:
+        assert ((bins == b) & (scores >= 10000)).sum() >= 1, b
+
+
+def test_global_extreme_gaps_on_the_exhaustive_set():
+    """Gap extensions of 1150 and gap opens of 1999 + 2000 on every pair of up to five bases at every band up to 7."""
+    batches = dg.gen_glb_extreme_gaps()
+    assert [len(b[2][1]) for b in batches] == [26576] * 4 + [11216]
+    scores, bins = _family(batches)
+    assert set(bins) == {6, 7} and scores.min() == -5727 and (scores > dg.MINUS_INF).all()
+
+
+def test_global_n_bases_on_a_general_matrix():
+    """15 % N in the queries, 5 % more in the targets, distinct entries in the matrix's N row and N column."""
+    batches = dg.gen_glb_n_bases(np.random.default_rng(9104))
+    for _, p, (pool, tasks, _) in batches:
+        m = np.asarray(p["mat"]).reshape(5, 5)
+        assert len(set(m[4, :].tolist() + m[:4, 4].tolist())) == 9
+        seqs = [kswlib.task_seqs(pool, t) for t in tasks]
+        assert sum(int((q == 4).sum()) for q, _ in seqs) > 100 and sum(int((t == 4).sum()) for _, t in seqs) > 100
+    scores, bins = _family(batches)
+    assert set(bins) == {6, 7, 5}
 
 
 def _check_sw(p, pool, tasks):

@@ -2,13 +2,17 @@
 the reference there): scores at the top of the 16-bit range, gap costs past 2^15 and 2^16, scaled and general matrices, and
 tasks on both sides of every routing switch.  Each test asserts, with domaingen's copy of the dispatcher's condition, that its
 tasks really sit on both sides of the switch it targets, and each refusal at the limit is followed by an exact batch on the
-same context."""
+same context.  The global tests also hold the device's own per-bin task counts (bmh_last_global_bin_counts) to the dispatcher as
+glbbin_ref.py restates it: equal results alone do not show which kernel ran."""
 import importlib
 
 import numpy as np
 import pytest
 
+import devcalls as dc
 import domaingen as dg
+import glbband_ref as gr
+import glbbin_ref as br
 import kswgen
 import kswlib
 from __graft_entry__ import load_package
@@ -21,7 +25,9 @@ EXT_ENV = {"auto": {}, "reg": {"BMH_EXT_MODE": "reg", "BMH_EXT_SMALL": "0"}, "gr
            "lane": {"BMH_EXT_MODE": "lane", "BMH_EXT_SMALL": "0"},
            "persist": {"BMH_EXT_MODE": "lane", "BMH_EXT_SMALL": "0", "BMH_EXT_PERSIST": "1"}}
 SEED_ENV = {"auto": {}, "lane": {"BMH_EXT_SMALL": "0"}, "persist": {"BMH_EXT_SMALL": "0", "BMH_EXT_PERSIST": "1"}}
-GLB_ENV = {"lane": {}, "wave": {"BMH_GLB_MODE": "wave"}, "masked": {"BMH_EXT_SMALL": "0", "BMH_GL_FAST": "0"}}
+GLB_ENV = {"lane": {}, "own": {"BMH_GLB_NARROW": "0"}, "wave": {"BMH_GLB_MODE": "wave"}, "masked": {"BMH_EXT_SMALL": "0", "BMH_GL_FAST": "0"}}
+# what glbbin_ref.expected_bins must be told about each of these contexts; None: no lane kernel runs, everything is in bin 2
+GLB_RULE = {"lane": dict(narrow=True), "own": dict(narrow=False), "wave": None, "masked": dict(narrow=True)}
 SW_ENV = {"wave": {"BMH_SW_MODE": "default"}, "lane": {"BMH_SW_MODE": "default", "BMH_SW_WAVE": "0"},
           "generic": {"BMH_SW_MODE": "generic"}}
 SEED_FIELDS = ("qb", "qe", "rb", "re", "score", "truesc", "w", "n_ext")
@@ -147,10 +153,27 @@ def test_seedext_at_the_top_of_the_score_range(mode):
 
 # ---- global ---------------------------------------------------------------------------------------------------------------
 
+def _glb_bins(mode, p, pool, tasks):
+    """(bin, band run on) of every task under the context of GLB_ENV[mode]."""
+    if GLB_RULE[mode] is None:
+        return np.full(len(tasks), 2), tasks["w"].astype(np.int64)
+    return br.expected_bins(p, pool, tasks, **GLB_RULE[mode])
+
+
+def _cmp_glb_bins(ctx, mode, p, pool, tasks, words, what):
+    """_cmp_glb, and the device's per-bin counts of that launch against the rule's."""
+    res = _cmp_glb(ctx, p, pool, tasks, words, what)
+    counts, expect = ctx.last_global_bin_counts(), np.bincount(_glb_bins(mode, p, pool, tasks)[0], minlength=8)
+    assert (counts == expect).all(), f"{what}: bin counts {counts.tolist()}, the rule gives {expect.tolist()}"
+    return res
+
+
 @pytest.mark.parametrize("mode", list(GLB_ENV))
 def test_global_on_both_sides_of_every_switch(mode):
-    """global_kernel.hip:231-235: worst 11999 / 12000, o_del+o_ins 3999 / 4000, tlen 512 / 513, w 31/32, 47/48, 63/64 -- and
-    scores far into the int32 range in the wave kernel's LDS and HBM-scratch variants."""
+    """global_kernel.hip:273-278 and host/glbbin_core.h: worst 11999 / 12000, o_del+o_ins 3999 / 4000, tlen 512 / 513, w 31/32, 47/48,
+    63/64 -- and scores far into the int32 range in the wave kernel's LDS and HBM-scratch variants.  Every batch's per-bin task
+    counts on the device are the rule's; on the tasks' own bands ("own") that puts w = 31 on <64>, 32 and 47 on <96>, 48 and 63 on
+    <128> and 64 on the wave kernel, and with the band pass ("lane", "masked") wherever the narrowed band says."""
     ctx = _ctx_with(GLB_ENV[mode])
     rng = np.random.default_rng(7300)
     p = kswlib.make_params(a=5, b=20, o_del=30, e_del=1, o_ins=40, e_ins=1)
@@ -160,7 +183,9 @@ def test_global_on_both_sides_of_every_switch(mode):
     rows_cap = min(int(tasks["tlen"].max()), 512)
     bins = [dg.glb_lane_bin(p, int(t["qlen"]), int(t["tlen"]), int(t["w"]), rows_cap) for t in tasks]
     assert bins[worst.index(12000)] == 2 and bins[worst.index(11999)] != 2
-    _cmp_glb(ctx, p, pool, tasks, words, f"{mode} worst")
+    run = _glb_bins(mode, p, pool, tasks)[0]
+    assert ((run == 2) == (np.array(worst) >= 12000)).all() or mode == "wave"  # `worst` alone decides lane or wave here, narrowed or not
+    _cmp_glb_bins(ctx, mode, p, pool, tasks, words, f"{mode} worst")
 
     p = kswlib.make_params()
     pool, tasks, words = dg.gen_glb_shape_edges(rng)
@@ -169,14 +194,26 @@ def test_global_on_both_sides_of_every_switch(mode):
     assert rows_cap == 512 and {b for (tl, _), b in bins.items() if tl == 513} == {2} and any(b != 2 for (tl, _), b in bins.items() if tl == 512)
     assert {b for (_, w), b in bins.items() if w in (31, 32, 47, 48, 63, 64) and b != 2} >= {0, 3, 1}
     assert any(b == 2 for (tl, w), b in bins.items() if w == 64 and tl <= 512)
-    _cmp_glb(ctx, p, pool, tasks, words, f"{mode} shapes")
+    run, ws = _glb_bins(mode, p, pool, tasks)
+    short = tasks["tlen"] <= 512
+    assert (run[~short] == 2).all()
+    if mode == "own":  # each side of each band switch on the kernel the dispatcher names for it, four tasks a side
+        for w, b in ((31, 0), (32, 3), (47, 3), (48, 1), (63, 1), (64, 2)):
+            on = run[short & (tasks["w"] == w)]
+            assert len(on) >= 4 and (on == b).all(), (w, on)
+    elif mode != "wave":  # the band pass narrows these lightly mutated pairs, so the device must bin them by the narrowed band
+        assert (ws[short] <= tasks["w"][short]).all() and (ws[short] < tasks["w"][short]).any()
+        assert (run[short] == [br.lane_bin(int(w)) for w in ws[short]]).all()
+    _cmp_glb_bins(ctx, mode, p, pool, tasks, words, f"{mode} shapes")
 
     for oo, lane_side in ((3999, True), (4000, False)):  # a parameter-level switch: two batches on the same context
         p = kswlib.make_params(o_del=oo - 1999, e_del=1, o_ins=1999, e_ins=1)
         pool, tasks, words = dg.gen_glb_shape_edges(rng, per=2)
         t0 = tasks[0]
         assert (dg.glb_lane_bin(p, int(t0["qlen"]), 20, 20, 512) != 2) == lane_side
-        _cmp_glb(ctx, p, pool, tasks, words, f"{mode} o_del+o_ins={oo}")
+        run = _glb_bins(mode, p, pool, tasks)[0]
+        assert (run != 2).any() == (lane_side and mode != "wave")
+        _cmp_glb_bins(ctx, mode, p, pool, tasks, words, f"{mode} o_del+o_ins={oo}")
 
     # deep scores in the wave kernel: the LDS / HBM-scratch variant is chosen once per batch (global_kernel.hip:288), so each
     # length gets a batch of its own
@@ -188,10 +225,96 @@ def test_global_on_both_sides_of_every_switch(mode):
             pool, tasks, words = dg.gen_glb_deep(rng, lens=(L,), per=3)
             assert dg.glb_wave_lds(tasks) == lds
             assert all(dg.glb_lane_bin(p, int(t["qlen"]), int(t["tlen"]), int(t["w"]), min(int(tasks["tlen"].max()), 512)) == 2 for t in tasks)
-            res = _cmp_glb(ctx, p, pool, tasks, words, f"{mode} deep {L}")
+            res = _cmp_glb_bins(ctx, mode, p, pool, tasks, words, f"{mode} deep {L}")
             low[lds] = min(low[lds], int(res["score"].min()))
     assert low[True] < -100_000 and low[False] < -1_000_000
     ctx.close()
+
+
+# ---- global: real scores across the lane kernels' 16-bit domain ---------------------------------------------------------
+
+# The contexts every family runs on, and what glbbin_ref.expected_bins must be told about each
+LANE_CTX = {
+    "own-exact": ({"BMH_GLB_EXACT": "7", "BMH_GLB_NARROW": "0"}, dict(narrow=False, exact=7)),
+    "narrowed": ({"BMH_GLB_EXACT": "7"}, dict(narrow=True, exact=7)),
+    "own-c32": ({"BMH_GLB_EXACT": "0", "BMH_GLB_NARROW": "0"}, dict(narrow=False, exact=0)),
+    "own-c64": ({"BMH_GLB_EXACT": "0", "BMH_GLB_NARROW": "0", "BMH_GLB_C32": "0"}, dict(narrow=False, exact=0, c32=0)),
+    "own-masked": ({"BMH_GLB_NARROW": "0", "BMH_GL_FAST": "0"}, dict(narrow=False, exact=7)),  # (BMH_GLB_EXACT at its default)
+}
+LANE_FAMILIES = {
+    "deep-negative-equal": lambda: dg.gen_glb_deep_negative_equal(np.random.default_rng(7310)),
+    "threshold": dg.gen_glb_threshold,
+    "deep-negative-unequal": lambda: dg.gen_glb_deep_negative_unequal(np.random.default_rng(7311)),
+    "empty-target": lambda: dg.gen_glb_empty_target(np.random.default_rng(7312)),
+    "deep-positive": lambda: dg.gen_glb_deep_positive(np.random.default_rng(7313)),
+    "extreme-gaps": dg.gen_glb_extreme_gaps,
+    "n-bases": lambda: dg.gen_glb_n_bases(np.random.default_rng(7314)),
+}
+
+
+@pytest.fixture(scope="module")
+def lane_family():
+    """name -> [(label, params, (pool, tasks, words), (oracle results, oracle CIGAR pool))], generated and run through the oracle once;
+    (name, "bands") -> {label: glbband_ref.expected_bands of that batch}, worked out once as well."""
+    cache = {}
+
+    def get(name, what="batches"):
+        if name not in cache:
+            cache[name] = [(label, p, batch, kswlib.orc_global_batch_mt(p, *batch, nthreads=8)[:2]) for label, p, batch in LANE_FAMILIES[name]()]
+        if what == "bands" and (name, what) not in cache:
+            cache[name, what] = {label: gr.expected_bands(p, pool, tasks) for label, p, (pool, tasks, _), _ in cache[name]}
+        return cache[name, what] if what == "bands" else cache[name]
+    return get
+
+
+@pytest.mark.parametrize("mode", list(LANE_CTX))
+@pytest.mark.parametrize("family", list(LANE_FAMILIES))
+def test_global_lane_kernels_across_their_domain(lane_family, family, mode):
+    """Real scores from -11129 to +11684 (test_score_domain_cpu.py pins the depth each family reaches in each bin to the reference),
+    gap opens up to 3999 in sum, gap extensions up to 2596, matrix entries of +-127 and N bases, on global_narrow_kernel and on
+    global_lane_kernel<32|64|96|128>: every result field and CIGAR word is the oracle's, the device's per-bin task counts are the
+    dispatcher's as glbbin_ref.py restates it, and with the band pass on its per-task bands are glbband_ref.py's."""
+    env, rule = LANE_CTX[mode]
+    ctx = _ctx_with(env)
+    try:
+        for label, p, (pool, tasks, words), (want, wcig) in lane_family(family):
+            what = f"{family} / {label} / {mode}: "
+            ctx.set_params(p)
+            res, cig = ctx.global_batch(pool, tasks, words)
+            bands = lane_family(family, "bands")[label] if rule["narrow"] else None
+            counts, expect = ctx.last_global_bin_counts(), br.expected_counts(p, pool, tasks, bands=bands, **rule)
+            print(f"{what}bins {counts.tolist()} scores {int(want['score'].min())} .. {int(want['score'].max())}")
+            bad = np.nonzero(res != want)[0]
+            if len(bad):  # which scores go wrong, before the assertion names the first task
+                print(f"{what}{len(bad)} differ; oracle scores of those {sorted(set(want['score'][bad].tolist()))[:4]} .. {int(want['score'][bad].max())}, "
+                      f"device scores {sorted(set(res['score'][bad].tolist()))[:4]}")
+            dc.assert_glb(res, cig, want, wcig, tasks, what)
+            assert (counts == expect).all() and expect[2] == 0 and expect[4] == 0, f"{what}bin counts {counts.tolist()}, the rule gives {expect.tolist()}"
+            if rule["narrow"]:
+                assert np.array_equal(ctx.last_global_bands(len(tasks)), bands), what
+    finally:
+        ctx.close()
+
+
+def test_global_deep_scores_through_the_device_entry(lane_family):
+    """bmh_global_batch_device on the deep-negative family: tasks, pool and results stay on the device, the slab is sized from the
+    context's capacity hint (as test_global_exact_gpu.py's sparse-order case works it out)."""
+    ctx = _ctx_with({"BMH_GLB_EXACT": "7"})
+    try:
+        for label, p, (pool, tasks, words), (want, wcig) in lane_family("deep-negative-equal"):
+            ctx.set_params(p)
+            ctx.set_qcap(int(tasks["qlen"].max()))
+            g = dc.Glb(pool, tasks, words)
+            g.run(ctx)
+            ctx.sync()
+            counts = ctx.last_global_bin_counts()
+            res, cig = g.result()
+            dc.assert_glb(res, cig, want, wcig, tasks, f"device entry / {label}: ")
+            rows_cap = min(int(tasks["qlen"].max()) + 2 * int(p["w"]) + 64, gr.ROWS_CAP)
+            expect = br.expected_counts(p, pool, tasks, rows_cap=rows_cap)
+            assert (counts == expect).all() and expect[2] == 0, (label, counts.tolist(), expect.tolist())
+    finally:
+        ctx.close()
 
 
 # ---- local Smith-Waterman -----------------------------------------------------------------------------------------------
