@@ -519,7 +519,9 @@ def test_refusals_without_the_resident_tables(pkg, ref):
 
 # ---------------------------------------------------------------- the switch behind bmh_sam_batch
 
-def _sam_batch(pkg, c, o, pes, id0, vecs, reads, rg_id=b""):
+def _sam_batch(pkg, c, o, pes, id0, vecs, reads, rg_id=b"", dress=None):
+    """bmh_sam_batch over a slice: (per read its SAM text, the vectors as the call left them).  dress: per read (name, comment or
+    None, qualities or None); without it the names, comments and qualities these tests make up."""
     lib = pkg.lib()
     lib.bmh_sam_batch.restype = C.c_int
     pe = _is_pe(o)
@@ -528,7 +530,8 @@ def _sam_batch(pkg, c, o, pes, id0, vecs, reads, rg_id=b""):
     for i, r in enumerate(reads):
         r = np.ascontiguousarray(r, dtype=np.uint8)
         keep.append(r)
-        seqs[i] = pkg._Seq(len(r), b"r%d" % (i // 2 if pe else i), b"co" if i % 3 == 0 else None, r.ctypes.data, bytes([35 + i % 40]) * len(r) if i % 4 else None, None)
+        name, comment, qual = dress[i] if dress is not None else (b"r%d" % (i // 2 if pe else i), b"co" if i % 3 == 0 else None, bytes([35 + i % 40]) * len(r) if i % 4 else None)
+        seqs[i] = pkg._Seq(len(r), name, comment, r.ctypes.data, qual, None)
     bufs = [np.array(v, dtype=kswlib.ALNREG, copy=True) for v in vecs]
     c_regs = (kswlib.CAlnregV * max(len(bufs), 1))()
     for i, a in enumerate(bufs):
