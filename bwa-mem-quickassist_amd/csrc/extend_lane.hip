@@ -28,6 +28,7 @@
 #include "bmh_ctx.h"
 #include "bmh_device.h"
 #include "../host/extstop_core.h"
+#include "seq_stream.h"
 
 namespace bmh {
 
@@ -69,6 +70,10 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 	// loaded inside the row loop (under an exec mask, so that the compiler cannot count it) every row paid an `s_waitcnt vmcnt(0)` right
 	// behind the load -- a full memory round trip per DP row.
 	constexpr int kStreamRows = 64;
+	// Both go through seq_stream.h: two dwords in flight per wait, from addresses clamped into the sequence and with no test of their
+	// own (each byte load behind its own `i + r < tlen` test had a wait of its own: 64 round trips per refill, C for the selectors).  At
+	// four dwords per wait the 32- and 64-column kernels put 12 and 24 bytes per lane more into scratch.
+	constexpr int kStreamBatch = 2, kSelBatch = 2;
 	__shared__ uint32_t stage[(C > kStreamRows ? C : kStreamRows) * 16]; // C/4 dwords x 64 lanes, or kStreamRows x 64 bytes
 #ifdef BMH_LANE_LDS_SEL
 	__shared__ uint8_t qsel[C * 64]; // query code of column p of lane l at [p*64+l]: one conflict-free ds_read_u8 per cell
@@ -132,17 +137,13 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 	}
 #else
 	int QS[NQ];
-#pragma unroll 2
-	for (int v = 0; v < NQ; ++v) {
-		int s = 0;
+#pragma unroll 1
+	for (int v0 = 0; v0 < NQ; v0 += kSelBatch) { // positions [-off, C - off) of the query, kSelBatch dwords per wait (seq_stream.h)
+		uint32_t qs[kSelBatch];
+		seq_issue<kSelBatch>(qs, pool, seq_lo(q_off, qlen, qrev), qlen, 4 * v0 - off, qrev, valid && !bad);
+		seq_finish<kSelBatch>(qs, qlen, 4 * v0 - off, qrev, valid && !bad);
 #pragma unroll
-		for (int b = 0; b < 4; ++b) {
-			const int j = 4 * v + b - off;
-			int qb = 4;
-			if (valid && !bad && j >= 0) qb = seq_base(pool, q_off, j, qrev);
-			s |= qb << (8 * b);
-		}
-		stage[v * 64 + lane] = (uint32_t)s;
+		for (int v = 0; v < kSelBatch; ++v) stage[(v0 + v) * 64 + lane] = qs[v];
 	}
 #pragma unroll
 	for (int v = 0; v < NQ; ++v) QS[v] = (int)stage[v * 64 + lane];
@@ -170,11 +171,30 @@ __global__ __launch_bounds__(64, BMH_LANE_WAVES(C)) void extend_lane_kernel(cons
 
 	for (int i = 0; __builtin_amdgcn_ballot_w64(alive) != 0; ++i) { // i is wave-uniform: all tasks started together
 		if ((i & (kStreamRows - 1)) == 0) { // wave-uniform: target rows [i, i + kStreamRows) of every lane still running
+			// a target in the byte pool, forward or reversed: kStreamBatch dwords per wait (seq_stream.h); one in the 2-bit reference is
+			// decoded base by base
+			if (__builtin_amdgcn_ballot_w64(alive && tpac) != 0) {
 #pragma unroll 4
-			for (int r = 0; r < kStreamRows; ++r) {
-				int tb = 0;
-				if (alive && i + r < tlen) tb = tgt_base(pool, P, t_off, i + r, trev, tpac);
-				strm[r * 64 + lane] = (uint8_t)tb;
+				for (int r = 0; r < kStreamRows; ++r) {
+					int tb = 0;
+					if (alive && tpac && i + r < tlen) tb = tgt_base(pool, P, t_off, i + r, trev, true);
+					strm[r * 64 + lane] = (uint8_t)tb;
+				}
+			}
+			const bool byt = alive && !tpac;
+			if (__builtin_amdgcn_ballot_w64(byt) != 0) {
+				int tl = tlen; // (opaque: what the batches derive from it is made here, not held across the row loop; see glb_fill_stream)
+				asm volatile("" : "+v"(tl));
+#pragma unroll 1
+				for (int rb = 0; rb < kStreamRows; rb += 4 * kStreamBatch) {
+					uint32_t t[kStreamBatch];
+					seq_issue<kStreamBatch>(t, pool, seq_lo(t_off, tl, trev), tl, i + rb, trev, byt);
+					seq_finish<kStreamBatch>(t, tl, i + rb, trev, byt);
+					if (byt) {
+#pragma unroll
+						for (int k = 0; k < 4 * kStreamBatch; ++k) strm[(rb + k) * 64 + lane] = (uint8_t)(t[k >> 2] >> (8 * (k & 3)));
+					}
+				}
 			}
 		}
 		const int tcur = strm[(i & (kStreamRows - 1)) * 64 + lane];

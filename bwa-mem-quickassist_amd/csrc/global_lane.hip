@@ -30,12 +30,15 @@
 
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "seq_stream.h"
 
 namespace bmh {
 
 constexpr int kNeg16 = -16384;
 constexpr int kTbRows = 16;     // rows of a path's block fetched together by the traceback (LDS strip of kTbRows x 64 dwords = 4 KB)
 constexpr int kStreamRows = 64; // rows of the {target base, incoming query base} stream staged in LDS at a time
+constexpr int kStreamBatch = 2; // dwords of each sequence a refill has in flight per wait: at 4, every instantiation needs 12+ registers more
+constexpr int kWindowBatch = 8; // dwords of the initial query window in flight per wait
 
 __device__ __forceinline__ int sel3(int mask, int a, int b) { return __builtin_amdgcn_bitop3_b32(mask, a, b, 0xca); }
 
@@ -108,24 +111,23 @@ __global__ __launch_bounds__(64, (C <= 32 ? BMH_GL_WAVES32 : C <= 64 ? BMH_GL_WA
 		// enters the window's top slot, q[i+C-w]; loaded from global memory inside the row loop they cost an `s_waitcnt vmcnt(0)` per row
 		// (loads under an exec mask cannot be counted, and the counter they share with the direction-word stores runs in order: 40 % of
 		// the waves' lifetime was spent waiting).  Both are staged in LDS, one byte per row (two nibbles) at [row][lane], kStreamRows rows
-		// at a time: the row loop waits for memory once per kStreamRows rows.  The window staging area is reused for the stream.
+		// at a time, by glb_fill_stream (seq_stream.h): every load of a batch from an address clamped into its sequence and issued with
+		// no test of its own, so a refill waits once per batch -- kStreamRows / (4 kStreamBatch) = 8 times, and once for the task record --
+		// and not once per load, as it did while each dword sat behind its own `r + 4 <= tlen` test.  The window staging area is reused
+		// for the stream.
 		uint8_t *strm = dyn_lds;
 		uint32_t *qstage = (uint32_t *)dyn_lds;
-#pragma unroll 2
-		for (int v = 0; v < NQ; ++v) {
-			int sv = 0;
+#pragma unroll 1
+		for (int v0 = 0; v0 < NQ; v0 += kWindowBatch) { // positions [-w, C - w) of the query, kWindowBatch dwords per wait (seq_stream.h)
+			uint32_t qw[kWindowBatch];
+			seq_issue<kWindowBatch>(qw, pool, q_off, qlen, 4 * v0 - w, false, live);
+			seq_finish<kWindowBatch>(qw, qlen, 4 * v0 - w, false, live);
 #pragma unroll
-			for (int b = 0; b < 4; ++b) {
-				const int j = 4 * v + b - w;
-				int qb = 4;
-				if (live && j >= 0 && j < qlen) qb = pool[q_off + (uint64_t)j];
-				sv |= qb << (8 * b);
-			}
-			qstage[v * 64 + lane] = (uint32_t)sv;
+			for (int v = 0; v < kWindowBatch; ++v) qstage[(v0 + v) * 64 + lane] = qw[v];
 		}
 #pragma unroll
 		for (int v = 0; v < NQ; ++v) QW[v] = (int)qstage[v * 64 + lane];
-		// the stream holds kStreamRows rows at a time and is refilled by the row loop every kStreamRows rows (one wait per chunk)
+		// the stream holds kStreamRows rows at a time and is refilled by the row loop every kStreamRows rows
 		const int qsh = C - w; // row i takes q[i + qsh] into the top slot of the window of row i+1
 		auto fill_stream = [&](int r0) {
 			// the sequence offsets are read again from the task record here (once per kStreamRows rows) instead of living in four
@@ -133,26 +135,9 @@ __global__ __launch_bounds__(64, (C <= 32 ? BMH_GL_WAVES32 : C <= 64 ? BMH_GL_WA
 			// also waits for every direction-word store in flight
 			const uint4 tq = *(const uint4 *)(tasks + idx);
 			const uint64_t q_off = (uint64_t)tq.y << 32 | tq.x, t_off = (uint64_t)tq.w << 32 | tq.z;
-#pragma unroll 2
-			for (int r4 = 0; r4 < kStreamRows; r4 += 4) { // four rows per trip: one (unaligned) dword of each sequence where it fits
-				const int r = r0 + r4;
-				uint32_t t4 = 0, q4 = 0x04040404u;
-				if (live && r + 4 <= tlen) __builtin_memcpy(&t4, pool + t_off + (uint64_t)r, 4);
-				else if (live) {
-#pragma unroll
-					for (int k = 0; k < 4; ++k)
-						if (r + k < tlen) t4 |= (uint32_t)pool[t_off + (uint64_t)(r + k)] << (8 * k);
-				}
-				if (live && r + qsh + 4 <= qlen) __builtin_memcpy(&q4, pool + q_off + (uint64_t)(r + qsh), 4);
-				else if (live) {
-#pragma unroll
-					for (int k = 0; k < 4; ++k)
-						if (r + qsh + k < qlen) q4 = (q4 & ~(0xffu << (8 * k))) | (uint32_t)pool[q_off + (uint64_t)(r + qsh + k)] << (8 * k);
-				}
-				const uint32_t m4 = (t4 & 0x0f0f0f0fu) | (q4 & 0x0f0f0f0fu) << 4;
-#pragma unroll
-				for (int k = 0; k < 4; ++k) strm[(r4 + k) * 64 + lane] = (uint8_t)(m4 >> (8 * k));
-			}
+			int lane_now;
+			asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_now));
+			glb_fill_stream<kStreamRows, kStreamBatch>(strm, lane_now, pool, t_off, tlen, q_off, qlen, r0, qsh, live);
 		};
 		int i = 0, score = kNeg16;
 		for (; __builtin_amdgcn_ballot_w64(live && i < tlen) != 0; ++i) { // ksw.c:524-564; i is wave-uniform

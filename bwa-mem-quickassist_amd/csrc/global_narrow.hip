@@ -15,12 +15,17 @@
 //     other than its own: a wider one is not exact once it exceeds the task's w.
 //   * W = 0 walks its one cell per row like the others (its direction bits are all "diagonal"); the traceback then reads them as for
 //     any band.  (Not special-cased: see profiles/global_exact.md.)
+//   * The sequences reach the row loop as in global_lane_kernel, through the same routine (glb_fill_stream, seq_stream.h): 64 rows
+//     of {target base, incoming query base} staged in LDS per refill, in batches of unconditional loads with one wait each -- a row
+//     here is 64..370 instructions, so the 17 and more waits per refill it had, one per four rows and one per byte near a lane's end, were a large part of a wave's lifetime.  The
+//     query window of row 0 is one such batch.
 // The traceback is a copy of global_lane_kernel's, so that kernel's register figures stay what they were.
 #include <algorithm>
 #include <type_traits>
 
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "seq_stream.h"
 
 namespace bmh {
 
@@ -29,6 +34,7 @@ namespace {
 constexpr int kNeg16 = -16384;
 constexpr int kTbRows = 16;     // rows of a path's block fetched together by the traceback (LDS strip of kTbRows x 64 dwords = 4 KB)
 constexpr int kStreamRows = 64; // rows of the {target base, incoming query base} stream staged in LDS at a time
+constexpr int kStreamBatch = 2; // dwords of each sequence a refill has in flight per wait: at 4, bands 0..3 spill 40 bytes more per lane
 constexpr int kNarrowBlocks = 2; // direction dwords per row the slab has room for (W <= 7: 15 cells)
 
 __device__ __forceinline__ int sel3n(int mask, int a, int b) { return __builtin_amdgcn_bitop3_b32(mask, a, b, 0xca); }
@@ -65,43 +71,20 @@ __device__ __forceinline__ int narrow_rows(const bool mine, const bool want, con
 		R[s] = (int)((uint32_t)kNeg16 << 16 | ((uint32_t)hd & 0xffffu)); // {H(-1,j-1) as eh[j].h, E = -inf}
 	}
 	// the query window of row 0, four v_perm selectors per register: slot s looks at q[s-W]; 4 marks "no base"
+	{ // one batch (seq_stream.h): positions [-W, 4 NQ - W)
+		uint32_t qw[NQ];
+		int ql = qlen; // (opaque, so that what the batch derives from it is not kept for the row loop: see glb_fill_stream)
+		asm volatile("" : "+v"(ql));
+		seq_issue<NQ>(qw, pool, q_off0, ql, -W, false, mine);
+		seq_finish<NQ>(qw, ql, -W, false, mine);
 #pragma unroll
-	for (int v = 0; v < NQ; ++v) {
-		int sv = 0;
-#pragma unroll
-		for (int b = 0; b < 4; ++b) {
-			const int j = 4 * v + b - W;
-			int qb = 4;
-			if (mine && j >= 0 && j < qlen) qb = pool[q_off0 + (uint64_t)j];
-			sv |= qb << (8 * b);
-		}
-		QW[v] = sv;
+		for (int v = 0; v < NQ; ++v) QW[v] = (int)qw[v];
 	}
 	constexpr int qsh = 4 * NQ - W; // row i takes q[i + qsh] into the top byte of the window for row i+1
 	auto fill_stream = [&](int r0) { // rows [r0, r0 + kStreamRows) of the {t, q} stream, one byte per row at [row][lane] (global_lane.hip)
 		const uint4 tq = *(const uint4 *)(tasks + idx);
 		const uint64_t q_off = (uint64_t)tq.y << 32 | tq.x, t_off = (uint64_t)tq.w << 32 | tq.z;
-		const int lane = lane_now();
-#pragma unroll 2
-		for (int r4 = 0; r4 < kStreamRows; r4 += 4) {
-			const int r = r0 + r4;
-			uint32_t t4 = 0, q4 = 0x04040404u;
-			if (mine && r + 4 <= tlen) __builtin_memcpy(&t4, pool + t_off + (uint64_t)r, 4);
-			else if (mine) {
-#pragma unroll
-				for (int k = 0; k < 4; ++k)
-					if (r + k < tlen) t4 |= (uint32_t)pool[t_off + (uint64_t)(r + k)] << (8 * k);
-			}
-			if (mine && r + qsh + 4 <= qlen) __builtin_memcpy(&q4, pool + q_off + (uint64_t)(r + qsh), 4);
-			else if (mine) {
-#pragma unroll
-				for (int k = 0; k < 4; ++k)
-					if (r + qsh + k < qlen) q4 = (q4 & ~(0xffu << (8 * k))) | (uint32_t)pool[q_off + (uint64_t)(r + qsh + k)] << (8 * k);
-			}
-			const uint32_t m4 = (t4 & 0x0f0f0f0fu) | (q4 & 0x0f0f0f0fu) << 4;
-#pragma unroll
-			for (int k = 0; k < 4; ++k) strm[(r4 + k) * 64 + lane] = (uint8_t)(m4 >> (8 * k));
-		}
+		glb_fill_stream<kStreamRows, kStreamBatch>(strm, lane_now(), pool, t_off, tlen, q_off, qlen, r0, qsh, mine);
 	};
 
 	int score = kNeg16;
