@@ -86,8 +86,12 @@ PHASE2_TEXT_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i
                               ("text_bytes", "<i8"), ("h2d_bytes", "<i8"), ("d2h_bytes", "<i8"), ("fallbacks", "<i8"), ("waits", "<i4"),
                               ("sessions", "<i4"), ("decide_ms", "<f4"), ("wanted_ms", "<f4"), ("gather_ms", "<f4"), ("size_ms", "<f4"),
                               ("emit_ms", "<f4"), ("rsv", "<i4")])  # bmh_phase2_text_stats_t, 112 bytes
+READS_SAM_STATS = np.dtype([("reads", "<i8"), ("regions_in", "<i8"), ("regions", "<i8"), ("kmax", "<i8"), ("opool_cap", "<i8"),
+                            ("handoff_d2h_bytes", "<i8"), ("waits_tail", "<i4"), ("plan_ms", "<f4"), ("neg_index", "<i4"),
+                            ("rsv", "<i4")])  # bmh_reads_sam_stats_t, 64 bytes
 WANTED_MOVED, WANTED_HOST = 4, 8
 MEM_F_NO_MULTI = 0x10
+MEM_F_NO_EXACT = 0x40
 ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
                    ("truesc", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"),
                    ("w", "<i4"), ("seedcov", "<i4"), ("secondary", "<i4"), ("hash", "<u8")])
@@ -271,6 +275,9 @@ def lib():
         L.bmh_phase2_text_device.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
         L.bmh_ctx_set_phase2_text_device.argtypes = [C.c_void_p, C.c_int]
         L.bmh_last_phase2_text_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_reads_sam_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.bmh_last_reads_sam_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1155,6 +1162,39 @@ class Context:
         st = np.zeros(1, dtype=PHASE2_TEXT_STATS)
         self._check(lib().bmh_last_phase2_text_stats(self._h, _ptr(st)))
         return {k: st[0][k].item() for k in PHASE2_TEXT_STATS.names if k != "rsv"}
+
+    def reads_sam_device(self, smem_opt, chain_opt, min_seed_len, opt, refidx, pac, id0, seqs, rg_id=b"", out=None):
+        """bmh_reads_sam_device: single-end reads to SAM text as one device session; the regions never leave the device.  smem_opt,
+        chain_opt, min_seed_len as seed_chain_regs_batch's, opt (SAM_OPT), refidx, pac, id0, seqs, rg_id and out as
+        phase2_text_device's.  Returns (text, text_off)."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8) if pac is not None else None
+        n = len(seqs)
+        o_in, so = np.asarray(smem_opt), np.zeros((), dtype=SMEM_OPT)
+        for k in o_in.dtype.names:
+            so[k] = o_in[k]
+        co = np.ascontiguousarray(np.asarray(chain_opt, dtype=CHAIN_OPT).reshape(()))
+        o = np.array(opt, dtype=SAM_OPT).reshape(1)
+        keep = []
+        c_seqs = (_Seq * max(n, 1))()
+        for r, (name, comment, seq, qual) in enumerate(seqs):
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            keep.append(seq)
+            c_seqs[r] = _Seq(len(seq), name, comment, seq.ctypes.data if len(seq) else None, qual, None)
+        out = out or {}
+        text = out.get("text", C.c_void_p(None))
+        text_off = out.get("text_off", np.zeros(n + 1, dtype=np.int64))
+        self._check(lib().bmh_reads_sam_device(self._h, _ptr(so), _ptr(co), int(min_seed_len), _ptr(o), C.byref(refidx) if refidx is not None else None,
+                                               _ptr(pac), C.c_int64(int(id0)), n, C.cast(c_seqs, C.c_void_p), rg_id, C.cast(C.byref(text), C.c_void_p),
+                                               _ptr(text_off)))
+        data = C.string_at(text.value, int(text_off[n]))
+        _libc.free(text)
+        return data, text_off
+
+    def last_reads_sam_stats(self):
+        """bmh_last_reads_sam_stats as a dict of READS_SAM_STATS' fields: the last reads_sam_device call on this context."""
+        st = np.zeros(1, dtype=READS_SAM_STATS)
+        self._check(lib().bmh_last_reads_sam_stats(self._h, _ptr(st)))
+        return {k: st[0][k].item() for k in READS_SAM_STATS.names if k != "rsv"}
 
     def sam_text_batch(self, *args, device=True, **kw):
         """sam_text_batch() on this context: bmh_sam_text_device (device=False: the host call, which needs no context)."""

@@ -15,6 +15,7 @@
 #include "decide.h"
 #include "wanted.h"
 #include "samtext.h"
+#include "../host/handoff_core.h"
 #include "../host/pestat_core.h"
 
 namespace bmh {
@@ -345,6 +346,8 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 		if (e) (void)hipEventDestroy(e);
 	free_buf(ctx->d_pestat);
 	for (auto &e : ctx->ev_pestat)
+		if (e) (void)hipEventDestroy(e);
+	for (auto &e : ctx->ev_plan)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
 		if (h.ev) (void)hipEventDestroy(h.ev);
@@ -1663,42 +1666,42 @@ void bmh_pp_fill_log_(double *logk, int64_t k0, int64_t k1);
 void bmh_pp_fill_term_(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const int64_t term_off[4], double *term);
 
 // What the tables of a pass A on the device must reach (bwamem_hip.h), before anything is uploaded: BMH_E_RANGE and *why where one
-// would pass 2^20 entries or an index is negative
-static int decide_table_sizes(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, int n, const bmh_alnreg_v *regs, long long *kmax_, long long *n_term_,
-                              int64_t term_off[4], const char **why)
+// would pass 2^20 entries or an index is negative.  plan: the regions' part of it (host/handoff_core.h), from a walk over the caller's
+// vectors (decide_table_sizes below) or from regs_plan_kernel where the regions are on the device; pair_kmax: what the pairs add, 0 = none
+static int decide_tables_from_plan(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const bmh_ho_plan_t &plan, long long pair_kmax, long long *kmax_,
+                                   long long *n_term_, int64_t term_off[4], const char **why)
 {
-	constexpr long long kTabMax = 1LL << 20;
-	const bool pe = (o->flag & BMH_MEM_F_PE) != 0, pairing = pe && !(o->flag & BMH_MEM_F_NOPAIRING);
-	long long kmax = 1, n_term = 0;
+	const bool pairing = (o->flag & BMH_MEM_F_PE) && !(o->flag & BMH_MEM_F_NOPAIRING);
+	const long long kmax = std::max<long long>(plan.kmax, pair_kmax);
+	long long n_term = 0;
 	auto refuse = [&](const char *w) {
 		*why = w;
 		return BMH_E_RANGE;
 	};
-	for (int i = 0; i < n; ++i) {
-		const long long nv = (long long)regs[i].n;
-		for (long long j = 0; j < nv; ++j) {
-			const bmh_alnreg_t *a = &regs[i].a[j];
-			long long idx = 0;
-			if (o->mapQ_coef_len > 0) {
-				const int l = bmh_pp_len(a);
-				if (!(l < o->mapQ_coef_len)) idx = l;
-			} else idx = a->seedcov;
-			if (idx < 0) return refuse("bmh_decide_device: a region asks for the logarithm of a negative number");
-			kmax = std::max(kmax, std::max(idx, (long long)std::max(a->sub_n, 0) + nv + 1));
-		}
-		if (pe && (i & 1)) {
-			const long long m = (long long)regs[i - 1].n + nv;
-			kmax = std::max(kmax, m > 1024 ? kTabMax : m * m + 1); // (past 1024 the square is out of the table anyway, and of long long at 2^32)
-		}
-	}
-	if (kmax + 1 > kTabMax) return refuse("bmh_decide_device: the log table would pass 2^20 entries");
+	if (plan.neg) return refuse("bmh_decide_device: a region asks for the logarithm of a negative number");
+	if (kmax + 1 > BMH_HO_TAB_MAX) return refuse("bmh_decide_device: the log table would pass 2^20 entries");
 	if (pairing)
 		for (int d = 0; d < 4; ++d) {
 			term_off[d] = n_term, n_term += bmh_pp_term_len(&pes[d]);
-			if (n_term > kTabMax) return refuse("bmh_decide_device: the pair table would pass 2^20 entries");
+			if (n_term > BMH_HO_TAB_MAX) return refuse("bmh_decide_device: the pair table would pass 2^20 entries");
 		}
 	*kmax_ = kmax, *n_term_ = n_term;
 	return BMH_OK;
+}
+
+// ... for the caller's vectors; *opool_cap (may be null): the sum of oriented_cap over all of them
+static int decide_table_sizes(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, int n, const bmh_alnreg_v *regs, long long *kmax_, long long *n_term_,
+                              int64_t term_off[4], const char **why, size_t *opool_cap = nullptr)
+{
+	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
+	bmh_ho_plan_t plan = BMH_HO_PLAN_INIT;
+	long long pair_kmax = 0;
+	for (int i = 0; i < n; ++i) {
+		bmh_ho_read(o, regs[i].a, (int64_t)regs[i].n, &plan);
+		if (pe && (i & 1)) pair_kmax = std::max<long long>(pair_kmax, bmh_ho_pair_kmax((int64_t)regs[i - 1].n, (int64_t)regs[i].n));
+	}
+	if (opool_cap) *opool_cap = (size_t)plan.opool_cap;
+	return decide_tables_from_plan(o, pes, plan, pair_kmax, kmax_, n_term_, term_off, why);
 }
 
 // the host's copy of the log table up to kmax, grown in powers of two; *want_log = the entries the device's copy must have
@@ -1799,17 +1802,18 @@ static DecideBlock decide_block(size_t n, size_t total, size_t n_term, bool pe, 
 	return L;
 }
 
-// pass A's sections of the upload: offsets, DecideHdr, pair table, regions
+// pass A's sections of the upload: offsets, DecideHdr, pair table, regions (roff NULL: neither the offsets nor the regions, which
+// are on the device already)
 static void decide_fill(uint8_t *up, const DecideBlock &L, const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const DecideTables &T, int n,
                         const bmh_alnreg_v *regs, const int64_t *roff)
 {
-	memcpy(up, roff, ((size_t)n + 1) * 8);
+	if (roff) memcpy(up, roff, ((size_t)n + 1) * 8);
 	DecideHdr *hdr = (DecideHdr *)(up + L.hdr);
 	memset(hdr, 0, sizeof(*hdr));
 	hdr->opt = *o;
 	if (o->flag & BMH_MEM_F_PE) memcpy(hdr->pes, pes, sizeof(hdr->pes));
 	if (T.n_term) bmh_pp_fill_term_(o, pes, T.term_off, (double *)(up + L.term));
-	for (int i = 0; i < n; ++i)
+	for (int i = 0; roff && i < n; ++i)
 		if (regs[i].n) memcpy(up + L.reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
 }
 
@@ -2039,10 +2043,7 @@ static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo,
 // knows only a capacity.  The reads, the WantedHdr, the work arrays, the launches, the downloads and the host's tail are the same.
 
 // the oriented bytes a region the kernels accept can have: what a session's oriented pool is sized from before the first launch
-static size_t oriented_cap(const bmh_alnreg_t *a)
-{
-	return (size_t)std::clamp<int64_t>((int64_t)a->qe - a->qb, 0, 65535) + (size_t)std::clamp<int64_t>(a->re - a->rb, 0, 65535);
-}
+static size_t oriented_cap(const bmh_alnreg_t *a) { return (size_t)bmh_ho_oriented_cap(a); }
 
 // the sections of an upload that are pass B's in both forms: the reads as one pool with 16 zero bytes behind it, so[] = its n + 1 offsets
 // (q_src = seq_off[read] + qb), and the parameters.  rpool NULL: the offsets and the parameters alone (the pool is made on the device)
@@ -2780,6 +2781,9 @@ __attribute__((visibility("hidden"))) int bmh_samtext_routed_(bmh_ctx_t *ctx, co
 // what bmh_samtext_check_ refuses of the arguments, the reads and the names (host/sam_post.c; not part of the interface)
 int bmh_samtext_check_seqs_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,
                             char **text, int64_t *text_off);
+// ... without the vectors: a slice whose regions are on the device already
+int bmh_samtext_check_reads_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, char **text,
+                             int64_t *text_off);
 
 // ensure() for a block whose first `keep` bytes a session still needs: the new allocation has them before the old one goes.  Every
 // pointer into the block is the caller's to make again.  *waited: whether the block moved, which costs the caller one wait.
@@ -2802,37 +2806,54 @@ static int ensure_keep(bmh_ctx *ctx, DevBuf &b, size_t bytes, size_t keep, bool 
 	return BMH_OK;
 }
 
-// The session.  The arguments are checked here; *early: the BMH_E_RANGE is a refusal before any upload (the decide tables, or slot
-// addresses past 32 bits), which bmh_sam_batch answers with its other routes.  Nothing of the caller's is written before the end.
-static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
-                           const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const char *rg_id, char **text, int64_t *text_off, bool *early)
+// What the session refuses of its arguments and the context before anything is uploaded, n == 0 included; res: the regions are on the
+// device (regs is not looked at).  reads: n entries, made here from seqs.
+static int phase2_text_check(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
+                             int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs, bool res, const char *rg_id, char **text, int64_t *text_off,
+                             std::vector<bmh_read_t> &reads)
 {
-	static const char *const who = "bmh_phase2_text_device";
-	*early = false;
-	reset_phase2_text_stats(ctx);
-	int rc = bmh_samtext_check_seqs_(o, bns, pes, n, seqs, regs, text, text_off);
+	int rc = res ? bmh_samtext_check_reads_(o, bns, pes, n, seqs, text, text_off) : bmh_samtext_check_seqs_(o, bns, pes, n, seqs, regs, text, text_off);
 	if (rc) return rc;
 	const size_t nr = (size_t)n;
-	std::vector<int64_t> roff(nr + 1, 0);
-	std::vector<bmh_read_t> reads(nr);
-	for (size_t i = 0; i < nr; ++i) { // (what bmh_pp_check_args refuses of the vectors; the offsets are made here)
-		if ((regs[i].n && !regs[i].a) || regs[i].n > 0x7fffffffu) return BMH_E_ARG;
-		roff[i + 1] = roff[i] + (int64_t)regs[i].n;
+	reads.resize(nr);
+	for (size_t i = 0; i < nr; ++i) { // (what bmh_pp_check_args refuses of the vectors)
+		if (!res && ((regs[i].n && !regs[i].a) || regs[i].n > 0x7fffffffu)) return BMH_E_ARG;
 		reads[i].l_seq = seqs[i].l_seq, reads[i].seq = (const uint8_t *)seqs[i].seq;
 	}
-	if ((rc = phase2_check_reads(bns, pac, n, reads.data()))) return rc;
+	if ((rc = phase2_check_reads(bns, pac, n, reads.data())) || n == 0) return rc;
+	if (!ctx->have_params) return BMH_E_ARG;
+	if ((rc = need_resident(ctx, who, bns, pac)) || (rc = need_refnames(ctx, who, bns))) return rc;
+	return n > (1 << 28) || (rg_id ? strlen(rg_id) : 0) > 0x7fffffffu ? BMH_E_ARG : BMH_OK;
+}
+
+// The session.  The arguments are checked here; *early: the BMH_E_RANGE is a refusal before any upload (the decide tables, or slot
+// addresses past 32 bits), which bmh_sam_batch answers with its other routes.  Nothing of the caller's is written before the end.
+// The regions come from the caller's vectors, or -- res, regs being NULL -- from where phase 1 left them on the device with what
+// regs_plan_kernel found: their offsets and records are then copied on the stream into pass A's block instead of uploaded, and
+// everything from launch_decide on is the same.
+static int phase2_text_run(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
+                           int64_t id0, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const ResidentRegs *res, const char *rg_id, char **text,
+                           int64_t *text_off, bool *early)
+{
+	*early = false;
+	reset_phase2_text_stats(ctx);
+	std::vector<bmh_read_t> reads;
+	int rc = phase2_text_check(ctx, who, o, bns, pac, pes, n, seqs, regs, res != nullptr, rg_id, text, text_off, reads);
+	if (rc) return rc;
+	const size_t nr = (size_t)n;
+	std::vector<int64_t> roff(res ? 0 : nr + 1, 0);
+	for (size_t i = 0; !res && i < nr; ++i) roff[i + 1] = roff[i] + (int64_t)regs[i].n; // (the offsets are made here)
 	if (n == 0) {
 		char *p = (char *)malloc(1);
 		if (!p) return BMH_E_NOMEM;
 		*text = p, text_off[0] = 0;
 		return BMH_OK;
 	}
-	if (!ctx->have_params) return BMH_E_ARG;
-	if ((rc = need_resident(ctx, who, bns, pac)) || (rc = need_refnames(ctx, who, bns))) return rc;
 	const size_t l_rg = rg_id ? strlen(rg_id) : 0;
-	if (n > (1 << 28) || roff[nr] > (1 << 28) || l_rg > 0x7fffffffu) return BMH_E_ARG;
+	const long long n_regs = res ? res->total : (long long)roff[nr];
+	if (n_regs < 0 || n_regs > (1 << 28)) return BMH_E_ARG;
 	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
-	const size_t total = (size_t)roff[nr], wc = total; // wc: the capacity of everything per wanted region, which bounds their number
+	const size_t total = (size_t)n_regs, wc = total; // wc: the capacity of everything per wanted region, which bounds their number
 	// before anything is uploaded: the slots' addresses as the records hold them, and the decide tables
 	if (wc * BMH_RP_SMALL_CAP > 0xffffffffull || wc * kWantMdSlot > 0xffffffffull) {
 		ctx->last_error = std::string(who) + ": the slice's CIGAR or MD slots do not fit 32-bit addresses";
@@ -2841,17 +2862,20 @@ static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refid
 	}
 	DecideTables T;
 	const char *why = nullptr;
-	if (decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why)) {
+	size_t reads_bytes = 0, opool_cap = 0;
+	if (res) {
+		const bmh_ho_plan_t plan{res->kmax, res->opool_cap, res->total, res->neg ? 1 : 0, 0};
+		rc = decide_tables_from_plan(o, pes, plan, 0, &T.kmax, &T.n_term, T.term_off, &why);
+		opool_cap = (size_t)res->opool_cap;
+	} else
+		rc = decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why, &opool_cap);
+	if (rc) {
 		ctx->last_error = why;
 		ctx->pt.fallbacks = 1, *early = true;
 		return BMH_E_RANGE;
 	}
 	if ((rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
-	size_t reads_bytes = 0, opool_cap = 0;
-	for (size_t i = 0; i < nr; ++i) {
-		reads_bytes += (size_t)reads[i].l_seq;
-		for (size_t k = 0; k < regs[i].n; ++k) opool_cap += oriented_cap(&regs[i].a[k]);
-	}
+	for (size_t i = 0; i < nr; ++i) reads_bytes += (size_t)reads[i].l_seq;
 	SamtextPool P;
 	if ((rc = P.plan(n, seqs))) return rc;
 	const size_t pool_bytes = (size_t)P.poff[nr];
@@ -2865,7 +2889,9 @@ static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refid
 	const size_t o_hdr = tb.take(sizeof(SamtextHdr)), o_rg = tb.take(l_rg), o_poff = tb.take((nr + 1) * 8), o_pool = tb.take(pool_bytes), t_up = tb.at;
 	const size_t o_alns = tb.take(wc * sizeof(bmh_st_aln_t)), o_plan = tb.take(nr * sizeof(bmh_st_plan_t)), o_size = tb.take(nr * 8), o_toff = tb.take((nr + 1) * 8);
 	const size_t o_stat = tb.take(sizeof(SamtextStatus) + sizeof(SamtextFused)), o_list = tb.take(wc * sizeof(Phase2TextHost)), t_end = tb.at;
-	HostBuf up(LA.up());
+	// (resident regions: the offsets at the block's head and the regions at the upload's tail are not the host's to send)
+	const size_t up_lo = res ? LA.hdr : 0, up_hi = res ? LA.reg : LA.up();
+	HostBuf up(up_hi);
 	uint8_t *tup = (uint8_t *)calloc(t_up, 1);
 	int64_t *toff = (int64_t *)malloc((nr + 1) * 8);
 	char *out = nullptr;
@@ -2878,7 +2904,7 @@ static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refid
 		ctx->last_error = std::string(who) + ": out of host memory";
 		return BMH_E_NOMEM;
 	}
-	decide_fill(up.p, LA, o, pes, T, n, regs, roff.data());
+	decide_fill(up.p, LA, o, pes, T, n, regs, res ? nullptr : roff.data());
 	wanted_fill(ctx, o->w, n, reads.data(), (uint64_t *)(up.p + LA.soff), (WantedHdr *)(up.p + LA.whdr), nullptr); // (the bases go up in the per-read pool)
 	SamtextHdr *hdr = (SamtextHdr *)(tup + o_hdr);
 	hdr->opt_flag = o->flag, hdr->pe = pe, hdr->l_rg = (int32_t)l_rg;
@@ -2939,10 +2965,14 @@ static int phase2_text_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refid
 		size_t rpool_off;
 		if ((e = ensure(ctx, ctx->d_decide, LA.end)) || (e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, LB.end, &rpool_off))) return e;
 		if ((e = ensure(ctx, ctx->d_wanted, LB.end)) || (e = ensure(ctx, ctx->d_samtext, t_end))) return e; // (d_wanted: first[] also where no read has a region)
-		if ((e = decide_stage_log(ctx, st, T.want_log, LA.up() + t_up + 512, 0))) return e;
+		if ((e = decide_stage_log(ctx, st, T.want_log, up_hi - up_lo + t_up + 512, 0))) return e;
 		d = (uint8_t *)ctx->d_decide.p, dw = (uint8_t *)ctx->d_wanted.p, dt = (uint8_t *)ctx->d_samtext.p;
 		BMH_HIP(ctx, hipMemsetAsync(dt + o_stat, 0, sizeof(SamtextStatus) + sizeof(SamtextFused), ctx->stream));
-		if ((e = st.h2d(d, up.p, LA.up())) || (e = st.h2d(dt, tup, t_up))) return e;
+		if (res) { // phase 1's offsets and compact records, from its workspace: nothing of it is read after these two copies
+			BMH_HIP(ctx, hipMemcpyAsync(d, res->roff, (nr + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+			if (total) BMH_HIP(ctx, hipMemcpyAsync(d + LA.reg, res->reg, total * sizeof(bmh_alnreg_t), hipMemcpyDeviceToDevice, ctx->stream));
+		}
+		if ((e = st.h2d(d + up_lo, up.p + up_lo, up_hi - up_lo)) || (e = st.h2d(dt, tup, t_up))) return e;
 		BMH_HIP(ctx, hipMemsetAsync(d + LA.nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
 		const DecideArgs DA = decide_args(ctx, d, LA, T, total, bns->l_pac, id0, n, pe);
 		if ((e = launch_decide(ctx, DA))) return e;
@@ -3111,7 +3141,7 @@ int bmh_phase2_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_ref
 {
 	bool early;
 	if (!ctx) return BMH_E_ARG;
-	return phase2_text_run(ctx, o, bns, pac, pes, id0, n, seqs, regs, rg_id, text, text_off, &early);
+	return phase2_text_run(ctx, "bmh_phase2_text_device", o, bns, pac, pes, id0, n, seqs, regs, nullptr, rg_id, text, text_off, &early);
 }
 
 int bmh_ctx_set_phase2_text_device(bmh_ctx_t *ctx, int on)
@@ -3138,10 +3168,52 @@ __attribute__((visibility("hidden"))) int bmh_phase2_text_routed_(bmh_ctx_t *ctx
 	*done = 0;
 	if (!ctx || !ctx->phase2_text_device) return BMH_OK;
 	bool early;
-	const int rc = phase2_text_run(ctx, o, bns, pac, pes, id0, n, seqs, regs, rg_id, text, text_off, &early);
+	const int rc = phase2_text_run(ctx, "bmh_phase2_text_device", o, bns, pac, pes, id0, n, seqs, regs, nullptr, rg_id, text, text_off, &early);
 	if (rc == BMH_E_RANGE && early) return BMH_OK;
 	*done = rc == BMH_OK;
 	return rc;
+}
+
+// ------------------------------------------------------------------ single-end reads to SAM text, the regions resident between the phases
+
+static_assert(sizeof(bmh_reads_sam_stats_t) == 64, "bmh_reads_sam_stats_t is part of the interface");
+
+int bmh_reads_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_sam_opt_t *o,
+                         const bmh_refidx_t *bns, const uint8_t *pac, int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id, char **text,
+                         int64_t *text_off)
+{
+	static const char *const who = "bmh_reads_sam_device";
+	if (!ctx || !so || !co || !o || !bns || !text || !text_off || n < 0 || (n > 0 && !seqs)) return BMH_E_ARG;
+	if (o->flag & BMH_MEM_F_PE) {
+		ctx->last_error = std::string(who) + ": single-end only (mate rescue lies between the two phases of a paired-end batch)";
+		return BMH_E_ARG;
+	}
+	// what either phase refuses, phase 1's first, before anything is uploaded
+	std::vector<bmh_read_t> reads((size_t)n), again;
+	for (int i = 0; i < n; ++i) reads[(size_t)i].l_seq = seqs[i].l_seq, reads[(size_t)i].seq = (const uint8_t *)seqs[i].seq;
+	int rc;
+	if ((rc = reads_regs_check(ctx, so, co, bns->l_pac, n, reads.data(), min_seed_len, who))) return rc;
+	if ((rc = phase2_text_check(ctx, who, o, bns, pac, nullptr, n, seqs, nullptr, true, rg_id, text, text_off, again))) return rc;
+	bool early;
+	if (n == 0) { // nothing runs
+		if ((rc = phase2_text_run(ctx, who, o, bns, pac, nullptr, id0, 0, seqs, nullptr, nullptr, rg_id, text, text_off, &early))) return rc;
+		ctx->dstats = bmh_driver_stats_t{};
+		if (o->flag & BMH_MEM_F_NO_EXACT) ctx->drop_exact_removed = 0;
+		ctx->rs = bmh_reads_sam_stats_t{0, 0, 0, 1, 0, 0, 0, -1.f, 0, 0};
+		return BMH_OK;
+	}
+	ResidentRegs R;
+	if ((rc = reads_regs_resident(ctx, so, co, bns->l_pac, n, reads.data(), min_seed_len, o, &R))) return rc;
+	rc = phase2_text_run(ctx, who, o, bns, pac, nullptr, id0, n, seqs, nullptr, &R, rg_id, text, text_off, &early);
+	ctx->rs.waits_tail = 1 + ctx->pt.waits;
+	return rc;
+}
+
+int bmh_last_reads_sam_stats(const bmh_ctx_t *ctx, bmh_reads_sam_stats_t *st)
+{
+	if (!ctx || !st) return BMH_E_ARG;
+	*st = ctx->rs;
+	return BMH_OK;
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

@@ -193,6 +193,9 @@ struct bmh_ctx {
 	void *h_ptstat = nullptr;                 // pinned: SamtextStatus and SamtextFused as the host reads them behind the scan
 	hipEvent_t ev_gather[2] = {};             // around reads_gather_kernel (timing mode)
 	bmh_phase2_text_stats_t pt = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f, -1.f, -1.f, -1.f, -1}; // of the last such call (bmh_last_phase2_text_stats)
+	// reads to SAM text with the regions resident between the phases (bmh_reads_sam_device: chain2reg.hip's hand-off, api.hip's session)
+	hipEvent_t ev_plan[2] = {};               // around regs_plan_kernel (timing mode)
+	bmh_reads_sam_stats_t rs = {-1, -1, -1, -1, -1, -1, -1, -1.f, -1, -1}; // of the last such call (bmh_last_reads_sam_stats)
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 };
 
@@ -249,6 +252,21 @@ typedef int (*SeedTablesFn)(bmh_ctx *ctx, const DevSeedTables &t, void *user);
 // bmh_seed_batch up to its device tables, then fn on them (on the context's stream, inside the same gate); returns fn's result.
 // Capacities grow inside; env BMH_CHAIN_INIT_CAP (test knob) starts them at that many entries.
 int seed_tables_device(bmh_ctx *ctx, const bmh_smem_opt_t *o, int max_occ, int n_reads, const bmh_read_t *reads, SeedTablesFn fn, void *user);
+// A batch's regions where c2r_place_kernel left them, in ctx->d_c2r: read r's at reg[roff[r] .. roff[r + 1]), and what regs_plan_kernel
+// found in them (host/handoff_core.h's bmh_ho_plan_t fields).  Valid until the next call that uses d_c2r; nothing phase 2 allocates does.
+struct ResidentRegs {
+	const unsigned long long *roff = nullptr; // n_reads + 1
+	const bmh_alnreg_t *reg = nullptr;
+	long long total = 0, kmax = 1, opool_cap = 0;
+	bool neg = false;
+};
+// bmh_seed_chain_regs_batch's checks and its run for bmh_reads_sam_device (chain2reg.hip): the context's three switches are neither read
+// nor written, the de-duplication runs at o->mask_level_redun, drop-exact with MEM_F_NO_EXACT in o->flag, and the driver ends behind
+// c2r_place_kernel and regs_plan_kernel: *out, and ctx->rs up to the hand-off.  reads_regs_check refuses before anything is uploaded.
+int reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                     int min_seed_len, const char *who);
+int reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                        int min_seed_len, const bmh_sam_opt_t *o, ResidentRegs *out);
 // every host wait for a stream goes through here (bmh_set_wait_mode)
 extern int g_wait_blocking;
 inline hipError_t stream_wait(bmh_ctx *ctx, hipStream_t s)

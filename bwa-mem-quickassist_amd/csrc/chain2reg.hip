@@ -23,6 +23,9 @@
 //                       (api.hip) runs on a caller's vectors.
 //   gather              count -> scan -> place of the regions (each read wrote into its slice of the region arena, the soff prefix
 //                       sums: a read yields at most as many regions as it has kept seeds), then the counts and the compact records down.
+//   regs_plan_kernel    resident mode (bmh_reads_sam_device) instead of the download: the compact records and their offsets stay where
+//                       c2r_place_kernel left them, and one lane per read folds its vector into what phase 2 must know before its first
+//                       launch (host/handoff_core.h).  One 128-byte record -- the status words and the plan -- comes down: one wait.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +34,7 @@
 #include "bmh_device.h"
 #include "../host/chain2aln_core.h"
 #include "../host/dedup_core.h"
+#include "../host/handoff_core.h"
 #include "../host/pestat_core.h"
 
 namespace bmh {
@@ -38,6 +42,13 @@ namespace bmh {
 enum { C2R_NEXT_CHAIN = 0, C2R_NEXT_SEED = 1, C2R_DONE = 2 };
 // status words (uint32 index).  0..3 are what the host reads in the loop
 enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_DEDUP_REMOVED = 12, C2R_DROP_REMOVED = 14, C2R_STATUS_BYTES = 64 };
+
+struct C2rPlan { // regs_plan_kernel's record, right behind the status words: one copy brings both
+	bmh_ho_plan_t plan;
+	uint32_t ticket; // waves that have written their part
+	uint32_t rsv[7];
+};
+static_assert(sizeof(C2rPlan) == 64 && sizeof(bmh_ho_plan_t) == 32, "plan record");
 
 struct C2rChain { // one chain's record, 64 bytes
 	int64_t rmax0, rmax1;
@@ -78,6 +89,7 @@ struct C2rWs {
 	unsigned long long *nreg, *roff; // n_reads + 1: regions per read, their exclusive sums
 	uint32_t *cand;          // n_reads / 2 + 1: mem_pestat's word per pair (pestat_collect_kernel), right behind roff: one copy brings both
 	bmh_alnreg_t *out;       // ts: the compact regions
+	bmh_ho_plan_t *part;     // n_reads / 64 + 1: regs_plan_kernel's per-wave parts
 };
 
 struct C2rSwRule { // what validate_sw (api.hip) checks per task of a host-fed batch
@@ -312,6 +324,56 @@ __global__ __launch_bounds__(64) void c2r_place_kernel(C2rIn in, C2rWs ws)
 	for (unsigned long long k = 0; k < n * 4; ++k) dst[k] = src[k];
 }
 
+// What phase 2 learns from a walk over the host's vectors, from the compact records instead (host/handoff_core.h): one lane per read
+// folds its vector, the wave folds its lanes with shuffles and writes its part, and one atomic per wave -- the ticket -- tells the last
+// wave to arrive that every part is there; it folds them into the record behind the status words.  Blocks are one wave.
+__global__ __launch_bounds__(64) void regs_plan_kernel(bmh_sam_opt_t o, int n_reads, unsigned long long ts, C2rWs ws)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x;
+	C2rPlan *rec = (C2rPlan *)((uint8_t *)ws.status + C2R_STATUS_BYTES);
+	bmh_ho_plan_t p = BMH_HO_PLAN_INIT;
+	if (r < n_reads) {
+		const unsigned long long n = ws.nreg[r], at = ws.roff[r];
+		if (at > ts || n > ts - at) c2r_fail(ws.status, BMH_E_ARG); // (c2r_place_kernel has said so already; nothing is read)
+		else bmh_ho_read(&o, ws.out + at, (int64_t)n, &p);
+	}
+	auto fold = [&](bmh_ho_plan_t &x) {
+		for (int d = 32; d >= 1; d >>= 1) {
+			bmh_ho_plan_t q;
+			q.kmax = __shfl_xor((long long)x.kmax, d), q.opool_cap = __shfl_xor((long long)x.opool_cap, d);
+			q.total = __shfl_xor((long long)x.total, d), q.neg = __shfl_xor(x.neg, d), q.rsv = 0;
+			bmh_ho_merge(&x, &q);
+		}
+	};
+	fold(p);
+	uint32_t ticket = 0;
+	// The parts cross compute units and dies inside one launch: written through with agent-scope stores and released before the
+	// ticket, read with agent-scope loads behind the ticket's acquire -- never from a cache line this unit may hold.
+	if (lane == 0) {
+		long long *w = (long long *)&ws.part[blockIdx.x];
+		__hip_atomic_store(w, (long long)p.kmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(w + 1, (long long)p.opool_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(w + 2, (long long)p.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(w + 3, (long long)(uint32_t)p.neg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__threadfence();
+		ticket = atomicAdd(&rec->ticket, 1u);
+	}
+	ticket = (uint32_t)__shfl((int)ticket, 0);
+	if (ticket != gridDim.x - 1) return;
+	__threadfence();
+	bmh_ho_plan_t t = BMH_HO_PLAN_INIT;
+	for (unsigned b = (unsigned)lane; b < gridDim.x; b += 64) {
+		const long long *w = (const long long *)&ws.part[b];
+		bmh_ho_plan_t q;
+		q.kmax = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), q.opool_cap = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		q.total = __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		q.neg = (int32_t)(__hip_atomic_load(w + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffffffll), q.rsv = 0;
+		bmh_ho_merge(&t, &q);
+	}
+	fold(t);
+	if (lane == 0) rec->plan = t;
+}
+
 // mem_sort_and_dedup (host/dedup_core.h, the text bmh_sort_and_dedup runs) on read r's slice of a region array, one lane per read.
 // The range stack of the two introsorts is the lane's own: bmh_sort_stack_len(n) <= 33 entries for n < 2^31.
 constexpr int kDedupStk = 34;
@@ -353,7 +415,7 @@ namespace {
 size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct C2rLayout {
-	size_t status, chn, state, srt, slot, tasks, res, swt, swr, reg, nreg, roff, cand, out, total;
+	size_t status, chn, state, srt, slot, tasks, res, swt, swr, reg, nreg, roff, cand, out, part, total;
 	C2rLayout(size_t n, size_t tc, size_t ts)
 	{
 		size_t o = 0;
@@ -362,11 +424,11 @@ struct C2rLayout {
 			o += al256(bytes);
 			return at;
 		};
-		status = take(C2R_STATUS_BYTES), chn = take((tc + 1) * sizeof(C2rChain)), state = take(n * sizeof(C2rState)), srt = take(ts * 8);
+		status = take(C2R_STATUS_BYTES + sizeof(C2rPlan)), chn = take((tc + 1) * sizeof(C2rChain)), state = take(n * sizeof(C2rState)), srt = take(ts * 8);
 		slot = take(ts * 4), tasks = take(ts * sizeof(bmh_seed_task_t)), res = take(ts * sizeof(bmh_seed_result_t));
 		swt = take(tc * sizeof(bmh_sw_task_t)), swr = take(tc * sizeof(bmh_sw_result_t)), reg = take(ts * sizeof(bmh_alnreg_t));
 		nreg = take((n + 1) * 8), roff = take((n + 1) * 8 + (n / 2 + 1) * 4), cand = roff + (n + 1) * 8; // (the words share roff's block)
-		out = take(ts * sizeof(bmh_alnreg_t)), total = o;
+		out = take(ts * sizeof(bmh_alnreg_t)), part = take((n / 64 + 1) * sizeof(bmh_ho_plan_t)), total = o;
 	}
 };
 
@@ -388,8 +450,25 @@ int c2r_abandon(bmh_ctx *ctx, int rc)
 
 // The driver proper, on the context's stream.  The workspace lies at the start of ctx->d_c2r (a caller that keeps its own input there
 // puts it behind C2rLayout::total and has made the buffer large enough).  regs[r] receive malloc'd arrays with n == m.
+// post: what runs behind the replay loop, the context's switches for every call but bmh_reads_sam_device.  post.resident: the driver
+// ends behind c2r_place_kernel and regs_plan_kernel (under *post.plan_opt), regs is not looked at, and *post.resident says where the
+// records lie and what the plan kernel found.
+struct C2rPost {
+	bool dedup;
+	float mask;
+	bool drop, collect;
+	ResidentRegs *resident = nullptr;
+	const bmh_sam_opt_t *plan_opt = nullptr;
+};
+
+// (a NULL context is c2r_check's to refuse)
+C2rPost c2r_post_of(const bmh_ctx *ctx)
+{
+	return ctx ? C2rPost{ctx->regs_dedup, ctx->regs_dedup_mask, ctx->regs_drop_exact, ctx->pestat_collect} : C2rPost{false, 0.f, false, false};
+}
+
 int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in, int lmax, int msl, bmh_alnreg_v *regs, bmh_driver_stats_t *st,
-            long long *chains_in = nullptr)
+            const C2rPost &post, long long *chains_in = nullptr)
 {
 	const int n = in.n_reads;
 	const C2rLayout L((size_t)n, (size_t)in.tc, (size_t)in.ts);
@@ -400,13 +479,13 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	const C2rWs ws{(uint32_t *)(d + L.status), (C2rChain *)(d + L.chn), (C2rState *)(d + L.state), (uint64_t *)(d + L.srt), (uint32_t *)(d + L.slot),
 	               (bmh_seed_task_t *)(d + L.tasks), (bmh_seed_result_t *)(d + L.res), (bmh_sw_task_t *)(d + L.swt), (bmh_sw_result_t *)(d + L.swr),
 	               (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (uint32_t *)(d + L.cand),
-	               (bmh_alnreg_t *)(d + L.out)};
+	               (bmh_alnreg_t *)(d + L.out), (bmh_ho_plan_t *)(d + L.part)};
 	const bmh_params_t &p = ctx->params;
 	const C2rSwRule sw{msl, ctx->dev.max_mat, ctx->wide_sw ? 1 : 0, sw_byte_gaps_wrap(p) ? 1 : 0};
 	const unsigned rb = (unsigned)((n + 63) / 64);
 	uint32_t *h = (uint32_t *)ctx->h_down.p;
 	hipStream_t s = ctx->stream;
-	BMH_HIP(ctx, hipMemsetAsync(ws.status, 0, C2R_STATUS_BYTES, s)); // the error flag starts clean on every call
+	BMH_HIP(ctx, hipMemsetAsync(ws.status, 0, C2R_STATUS_BYTES + sizeof(C2rPlan), s)); // the error flag starts clean on every call
 	hipLaunchKernelGGL(c2r_window_kernel, dim3(rb), dim3(64), 0, s, p, l_pac, in, ws, sw);
 	BMH_HIP(ctx, hipGetLastError());
 	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, 16, hipMemcpyDeviceToHost, s));
@@ -450,12 +529,12 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 		}
 	}
 	// with the switch on: mem_sort_and_dedup on every read's arena slice, so that the gather places and downloads the survivors only
-	const bool dedup = ctx->regs_dedup;
-	if (dedup && (rc = launch_region_dedup(ctx, ws.reg, in.soff, ws.nreg, n, in.ts, ctx->regs_dedup_mask,
+	const bool dedup = post.dedup;
+	if (dedup && (rc = launch_region_dedup(ctx, ws.reg, in.soff, ws.nreg, n, in.ts, post.mask,
 	                                       (unsigned long long *)&ws.status[C2R_DEDUP_REMOVED], (int *)&ws.status[C2R_ERR])))
 		return rc;
 	// with either of its switches on: mem_test_and_remove_exact on the survivors, then mem_pestat's word per pair from what is left
-	const bool collect = ctx->pestat_collect, drop = ctx->regs_drop_exact;
+	const bool collect = post.collect, drop = post.drop;
 	if ((collect || drop) && (rc = launch_pestat_collect(ctx, ws.reg, in.soff, ws.nreg, in.len, n, in.ts, ctx->pestat_opt, l_pac, p.a, drop,
 	                                                     collect ? ws.cand : nullptr, (unsigned long long *)&ws.status[C2R_DROP_REMOVED],
 	                                                     (int *)&ws.status[C2R_ERR])))
@@ -464,11 +543,29 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	hipLaunchKernelGGL(c2r_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long *)ws.nreg, n, ws.roff);
 	hipLaunchKernelGGL(c2r_place_kernel, dim3(rb), dim3(64), 0, s, in, ws);
 	BMH_HIP(ctx, hipGetLastError());
-	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
-	BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
-	BMH_HIP(ctx, stream_wait(ctx, s));
 	unsigned long long tr, u64s[4], removed, dropped;
-	memcpy(&tr, h + 16, 8), memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&removed, h + C2R_DEDUP_REMOVED, 8), memcpy(&dropped, h + C2R_DROP_REMOVED, 8);
+	C2rPlan plan{};
+	if (post.resident) { // the status words and the plan in one record: the one wait of the hand-off
+		if (ctx->timing) {
+			for (hipEvent_t &e : ctx->ev_plan)
+				if (!e) BMH_HIP(ctx, hipEventCreate(&e));
+			BMH_HIP(ctx, hipEventRecord(ctx->ev_plan[0], s));
+		}
+		hipLaunchKernelGGL(regs_plan_kernel, dim3(rb), dim3(64), 0, s, *post.plan_opt, n, in.ts, ws);
+		BMH_HIP(ctx, hipGetLastError());
+		if (ctx->timing) BMH_HIP(ctx, hipEventRecord(ctx->ev_plan[1], s));
+		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES + sizeof(C2rPlan), hipMemcpyDeviceToHost, s));
+		BMH_HIP(ctx, stream_wait(ctx, s));
+		memcpy(&plan, h + C2R_STATUS_BYTES / 4, sizeof(plan));
+		tr = (unsigned long long)plan.plan.total;
+		if (plan.ticket != rb || plan.plan.total < 0 || plan.plan.opool_cap < 0) tr = in.ts + 1; // cannot happen: refused below
+	} else {
+		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
+		BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
+		BMH_HIP(ctx, stream_wait(ctx, s));
+		memcpy(&tr, h + 16, 8);
+	}
+	memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&removed, h + C2R_DEDUP_REMOVED, 8), memcpy(&dropped, h + C2R_DROP_REMOVED, 8);
 	if (chains_in) *chains_in = (long long)u64s[3];
 	if ((int)h[C2R_ERR] || tr > in.ts) {
 		ctx->last_error = "chains to regions: the region counts are inconsistent";
@@ -482,6 +579,17 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	}
 	float pestat_ms = -1.f;
 	if ((collect || drop) && ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&pestat_ms, ctx->ev_pestat[0], ctx->ev_pestat[1]));
+	if (post.resident) { // nothing of the regions comes down and no vector is made
+		ResidentRegs &R = *post.resident;
+		R.roff = ws.roff, R.reg = ws.out;
+		R.total = (long long)tr, R.kmax = (long long)plan.plan.kmax, R.opool_cap = (long long)plan.plan.opool_cap, R.neg = plan.plan.neg != 0;
+		bmh_reads_sam_stats_t &rs = ctx->rs;
+		rs = bmh_reads_sam_stats_t{n, (int64_t)(tr + dropped + removed), (int64_t)tr, R.kmax, R.opool_cap, (int64_t)(C2R_STATUS_BYTES + sizeof(C2rPlan)),
+		                           1, -1.f, R.neg ? 1 : 0, 0};
+		if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&rs.plan_ms, ctx->ev_plan[0], ctx->ev_plan[1]));
+		if (drop) ctx->drop_exact_removed = (long long)dropped;
+		return BMH_OK;
+	}
 	const size_t b_roff = ((size_t)n + 1) * 8 + (collect ? ((size_t)n / 2) * 4 : 0); // the words lie right behind roff[]
 	const size_t b_off = al256(b_roff + 4), b_reg = (size_t)tr * sizeof(bmh_alnreg_t);
 	if ((rc = ensure_host(ctx, ctx->h_down, b_off + b_reg + 64))) return rc;
@@ -530,21 +638,23 @@ void c2r_empty(bmh_ctx *ctx)
 	if (ctx->regs_drop_exact) ctx->drop_exact_removed = 0;
 }
 
-int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads, int min_seed_len, const bmh_alnreg_v *regs, const char *who)
+// regs NULL: a call that makes no vectors (resident mode), post being its own and not the context's switches
+int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads, int min_seed_len, const bmh_alnreg_v *regs, const char *who,
+              const C2rPost &post, bool with_regs = true)
 {
-	if (!ctx || n_reads < 0 || l_pac < 0 || min_seed_len < 0 || (n_reads > 0 && (!reads || !regs))) return BMH_E_ARG;
+	if (!ctx || n_reads < 0 || l_pac < 0 || min_seed_len < 0 || (n_reads > 0 && (!reads || (with_regs && !regs)))) return BMH_E_ARG;
 	if (!ctx->have_params) return BMH_E_ARG;
 	// the two switches behind the de-duplication (pestat.hip): refused here, before anything is enqueued; the switches stay as set
-	if ((ctx->pestat_collect || ctx->regs_drop_exact) && !ctx->regs_dedup) {
-		ctx->last_error = std::string(who) + ": " + (ctx->pestat_collect ? "bmh_ctx_set_pestat_collect" : "bmh_ctx_set_regs_drop_exact") +
+	if ((post.collect || post.drop) && !post.dedup) {
+		ctx->last_error = std::string(who) + ": " + (post.collect ? "bmh_ctx_set_pestat_collect" : "bmh_ctx_set_regs_drop_exact") +
 		                  " is on, which needs bmh_ctx_set_regs_dedup on: both run on the regions mem_sort_and_dedup leaves";
 		return BMH_E_ARG;
 	}
-	if (ctx->pestat_collect && (n_reads & 1)) {
+	if (post.collect && (n_reads & 1)) {
 		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on and n_reads is odd: reads 2p and 2p+1 are mates";
 		return BMH_E_ARG;
 	}
-	if (ctx->pestat_collect && ctx->pestat_opt.max_ins > BMH_PS_MAX_INS) {
+	if (post.collect && ctx->pestat_opt.max_ins > BMH_PS_MAX_INS) {
 		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on with max_ins >= 2^30, which the word cannot hold";
 		return BMH_E_RANGE;
 	}
@@ -557,11 +667,23 @@ int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads,
 			ctx->last_error = std::string(who) + ": read " + std::to_string(r) + " is longer than 65535 bases";
 			return BMH_E_RANGE;
 		}
-	for (int r = 0; r < n_reads; ++r)
+	for (int r = 0; with_regs && r < n_reads; ++r)
 		if (regs[r].n) {
 			ctx->last_error = std::string(who) + ": regs[" + std::to_string(r) + "] is not empty";
 			return BMH_E_ARG;
 		}
+	return BMH_OK;
+}
+
+// what the fused call refuses of its two option records
+int fused_check_opts(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, const char *who)
+{
+	if (co->min_seed_len < 0 || co->max_occ < 0) return BMH_E_ARG;
+	if (so->min_seed_len != co->min_seed_len || so->split_len != co->split_len || so->split_width != co->split_width || so->min_emit_len < 0 ||
+	    so->min_emit_len > co->min_seed_len) {
+		ctx->last_error = std::string(who) + ": min_seed_len / split_len / split_width must agree and min_emit_len <= min_seed_len";
+		return BMH_E_ARG;
+	}
 	return BMH_OK;
 }
 
@@ -571,6 +693,7 @@ struct FusedArgs {
 	int lmax, msl;
 	bmh_alnreg_v *regs;
 	bmh_driver_stats_t *st;
+	C2rPost post;
 };
 
 // seeding's tables -> compact chains -> regions, all where they lie on the device; the reads are the pool seeding uploaded
@@ -584,7 +707,7 @@ int fused_cb(bmh_ctx *ctx, const DevSeedTables &t, void *user)
 	// (the chains before the filter, for bmh_chain_stats, are summed on the device and come back in the status words)
 	const C2rIn in{n, t.read_off, t.len, dc.coff, dc.soff, dc.cn, dc.seeds, dc.tc, dc.ts, dc.n_keys};
 	long long before = 0;
-	if ((rc = c2r_run(ctx, u->l_pac, t.pool, in, u->lmax, u->msl, u->regs, u->st, &before))) return rc;
+	if ((rc = c2r_run(ctx, u->l_pac, t.pool, in, u->lmax, u->msl, u->regs, u->st, u->post, &before))) return rc;
 	ctx->cstats = bmh_chain_stats_t{n, before, (int64_t)dc.tc, (int64_t)dc.ts, (int64_t)dc.n_equal, dc.kernel_ms}; // of a successful call only
 	return BMH_OK;
 }
@@ -597,7 +720,7 @@ int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh
                            bmh_alnreg_v *regs)
 {
 	int rc;
-	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, regs, "bmh_chains2regs_device"))) return rc;
+	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, regs, "bmh_chains2regs_device", c2r_post_of(ctx)))) return rc;
 	if (n_reads > 0 && !chains) return BMH_E_ARG;
 	bmh_driver_stats_t st{};
 	ctx->dstats = st;
@@ -651,7 +774,7 @@ int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh
 	st.pool_bytes = (int64_t)bytes + 16; // the reads and the 16 bytes of padding behind them, as the host driver counts its pool
 	const C2rIn in{n_reads, (const uint64_t *)(d + i_off), (const int *)(d + i_len), (const unsigned long long *)(d + i_coff),
 	               (const unsigned long long *)(d + i_soff), (const uint32_t *)(d + i_cn), (const bmh_seed_t *)(d + i_seed), tc, ts, nullptr};
-	rc = c2r_run(ctx, l_pac, d + i_pool, in, lmax, min_seed_len, regs, &st);
+	rc = c2r_run(ctx, l_pac, d + i_pool, in, lmax, min_seed_len, regs, &st, c2r_post_of(ctx));
 	ctx->dstats = st;
 	return rc;
 }
@@ -661,18 +784,13 @@ int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bm
 {
 	int rc;
 	if (!so || !co) return BMH_E_ARG;
-	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, regs, "bmh_seed_chain_regs_batch"))) return rc;
-	if (co->min_seed_len < 0 || co->max_occ < 0) return BMH_E_ARG;
-	if (so->min_seed_len != co->min_seed_len || so->split_len != co->split_len || so->split_width != co->split_width || so->min_emit_len < 0 ||
-	    so->min_emit_len > co->min_seed_len) {
-		ctx->last_error = "bmh_seed_chain_regs_batch: min_seed_len / split_len / split_width must agree and min_emit_len <= min_seed_len";
-		return BMH_E_ARG;
-	}
+	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, regs, "bmh_seed_chain_regs_batch", c2r_post_of(ctx)))) return rc;
+	if ((rc = fused_check_opts(ctx, so, co, "bmh_seed_chain_regs_batch"))) return rc;
 	bmh_driver_stats_t st{}; // (pool_bytes stays 0: the reads are where seeding uploaded them)
 	ctx->dstats = st;
 	int lmax = 1;
 	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
-	FusedArgs u{co, l_pac, lmax, min_seed_len, regs, &st};
+	FusedArgs u{co, l_pac, lmax, min_seed_len, regs, &st, c2r_post_of(ctx)};
 	rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
 	if (!rc && n_reads == 0) c2r_empty(ctx);
 	ctx->dstats = st;
@@ -680,3 +798,39 @@ int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bm
 }
 
 } // extern "C"
+
+// ---- bmh_reads_sam_device's phase 1 (api.hip): bmh_seed_chain_regs_batch with its own post-processing and the regions left resident
+
+static C2rPost reads_sam_post(const bmh_sam_opt_t *o, ResidentRegs *out)
+{
+	return C2rPost{true, o->mask_level_redun, (o->flag & BMH_MEM_F_NO_EXACT) != 0, false, out, o};
+}
+
+int bmh::reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                          int min_seed_len, const char *who)
+{
+	int rc;
+	if (!so || !co) return BMH_E_ARG;
+	const C2rPost post{true, 0.f, false, false}; // (the context's switches are not this call's)
+	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, nullptr, who, post, false)) || (rc = fused_check_opts(ctx, so, co, who))) return rc;
+	if (!ctx->bwt_bind) { // what seeding refuses before its upload
+		ctx->last_error = "no FM-index on the device (bmh_ctx_set_bwt)";
+		return BMH_E_ARG;
+	}
+	for (int r = 0; r < n_reads; ++r)
+		if (reads[r].l_seq < 0 || (reads[r].l_seq > 0 && !reads[r].seq)) return BMH_E_ARG;
+	return BMH_OK;
+}
+
+int bmh::reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                             int min_seed_len, const bmh_sam_opt_t *o, ResidentRegs *out)
+{
+	bmh_driver_stats_t st{};
+	ctx->dstats = st;
+	int lmax = 1;
+	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
+	FusedArgs u{co, l_pac, lmax, min_seed_len, nullptr, &st, reads_sam_post(o, out)};
+	const int rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
+	ctx->dstats = st;
+	return rc;
+}

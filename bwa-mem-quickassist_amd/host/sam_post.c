@@ -562,21 +562,30 @@ __attribute__((visibility("hidden"))) int bmh_samtext_check_(const bmh_sam_opt_t
 	return BMH_OK;
 }
 
-/* what bmh_samtext_check_ refuses of a slice whose pass A and pass B outputs stay on the device (bmh_phase2_text_device, csrc/api.hip):
- * the arguments, the reads and the names.  The vectors and offsets are bmh_pp_check_args's there. */
-__attribute__((visibility("hidden"))) int bmh_samtext_check_seqs_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n,
-                                                                  const bmh_seq_t *seqs, const bmh_alnreg_v *regs, char **text, int64_t *text_off)
+/* what bmh_samtext_check_ refuses of the arguments, the reads and the names alone: a slice whose regions are on the device already
+ * (bmh_reads_sam_device, csrc/api.hip) */
+__attribute__((visibility("hidden"))) int bmh_samtext_check_reads_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n,
+                                                                   const bmh_seq_t *seqs, char **text, int64_t *text_off)
 {
 	const int pe = o && (o->flag & BMH_MEM_F_PE) != 0;
 	int i;
 	if (!o || !bns || !text || !text_off || n < 0 || (pe && ((n & 1) || !pes))) return BMH_E_ARG;
 	if (n == 0) return BMH_OK;
-	if (!seqs || !regs || bns->l_pac <= 0 || bns->n_seqs <= 0 || !bns->anns) return BMH_E_ARG;
+	if (!seqs || bns->l_pac <= 0 || bns->n_seqs <= 0 || !bns->anns) return BMH_E_ARG;
 	for (i = 0; i < bns->n_seqs; ++i)
 		if (!bns->anns[i].name) return BMH_E_ARG;
 	for (i = 0; i < n; ++i)
 		if (!seqs[i].name || seqs[i].l_seq < 0 || (seqs[i].l_seq > 0 && !seqs[i].seq)) return BMH_E_ARG;
 	return pe ? mates_named_alike(n, seqs) : BMH_OK;
+}
+
+/* what bmh_samtext_check_ refuses of a slice whose pass A and pass B outputs stay on the device (bmh_phase2_text_device, csrc/api.hip):
+ * the arguments, the reads and the names.  The vectors and offsets are bmh_pp_check_args's there. */
+__attribute__((visibility("hidden"))) int bmh_samtext_check_seqs_(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n,
+                                                                  const bmh_seq_t *seqs, const bmh_alnreg_v *regs, char **text, int64_t *text_off)
+{
+	if (n > 0 && !regs) return BMH_E_ARG;
+	return bmh_samtext_check_reads_(o, bns, pes, n, seqs, text, text_off);
 }
 
 int bmh_sam_text_batch(const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs,

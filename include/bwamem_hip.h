@@ -631,6 +631,7 @@ typedef struct bmh_sam_opt { /* the mem_opt_t fields phase 2 reads (bwamem.h:21-
 #define BMH_MEM_F_ALL 0x8
 #define BMH_MEM_F_NO_MULTI 0x10
 #define BMH_MEM_F_NO_RESCUE 0x20
+#define BMH_MEM_F_NO_EXACT 0x40
 
 typedef struct bmh_refann { /* == bntann1_t, bntseq.h:39-45: one reference sequence */
 	int64_t offset;
@@ -1114,6 +1115,55 @@ int bmh_ctx_set_pestat_collect(bmh_ctx_t *ctx, int on, const bmh_sam_opt_t *o);
 int bmh_last_pestat_candidates(bmh_ctx_t *ctx, uint32_t *cand, int64_t n_pairs, float *kernel_ms);
 /* Regions drop exact removed in the last successful chains-to-regions call that ran with it on; -1 before the first. */
 int bmh_last_drop_exact_stats(const bmh_ctx_t *ctx, int64_t *removed);
+
+/* ---- Single-end reads to SAM text as one device session: seeding, chaining, chains to regions, the de-duplication, marking, mapQ,
+ * the alignments and the text, with the region vectors on the device from the kernel that makes them to the kernel that sorts them.
+ * *text / text_off[0..n] are byte for byte what this composition gives on a context whose de-duplication switch is on at
+ * o->mask_level_redun:
+ *   bmh_seed_chain_regs_batch(so, co, bns->l_pac, n, reads, min_seed_len, regs), reads[i] = seqs[i]'s bases, with
+ *       bmh_ctx_set_regs_drop_exact on exactly when o->flag has MEM_F_NO_EXACT (0x40) and bmh_ctx_set_pestat_collect off, then
+ *   bmh_phase2_text_device(o, bns, pac, NULL, id0, n, seqs, regs, rg_id, text, text_off).
+ *   the hand-off  the chains-to-regions driver ends behind c2r_place_kernel: the compact records and their offsets stay in its
+ *                 workspace, nothing of them comes down and no vector is made.  regs_plan_kernel, one lane per read, finds what phase 2
+ *                 otherwise learns by walking the vectors (host/handoff_core.h): the largest index of the log table, the negative-index
+ *                 flag, the capacity of the oriented pool, the region total.  They come down in one 128-byte record with the driver's
+ *                 status words: one wait where bmh_seed_chain_regs_batch has two, and as many bytes for one read as for a million.
+ *   phase 2       bmh_phase2_text_device's session from those numbers.  Its upload leaves out the offsets and the regions; both are copied
+ *                 on the stream, device to device, into pass A's block.  From decide_kernel on it is the same code, the redo included
+ *                 (the list that comes down for it carries each redone region's record).  The bases still go up a second time, inside
+ *                 pass C's per-read pool.
+ * The call neither reads nor changes the context's bmh_ctx_set_regs_dedup, bmh_ctx_set_regs_drop_exact and bmh_ctx_set_pestat_collect
+ * switches; it honours bmh_ctx_set_wide_extension, bmh_ctx_set_wide_sw and bmh_ctx_set_region_long as the two calls do.
+ * Needs what the two calls need: the parameters, the FM-index, the resident 2-bit reference with this pac, the sequence table and the
+ * sequence names: BMH_E_ARG without any of them.
+ *   BMH_E_ARG    before anything runs: o->flag has BMH_MEM_F_PE (mate rescue lies between the phases there); a NULL ctx, so, co, o,
+ *                bns, text or text_off; what either call refuses of n, seqs, so, co or o
+ *   BMH_E_RANGE  before anything runs: a read longer than 65535 bases.  After phase 1 and before phase 2's upload: what
+ *                bmh_phase2_text_device refuses there (a decide table past 1 << 20 entries, a negative table index, slot addresses
+ *                past 32 bits); from the kernels: as in the two calls
+ *   BMH_OK       for n == 0 with a 1-byte *text and text_off[0] = 0, nothing runs
+ * All or nothing: on any error *text and text_off are untouched, and the context stays usable.
+ * Afterwards bmh_driver_stats, bmh_chain_stats, bmh_last_dedup_stats and bmh_last_drop_exact_stats are valid as after
+ * bmh_seed_chain_regs_batch, and bmh_last_phase2_text_stats as after bmh_phase2_text_device. */
+int bmh_reads_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_sam_opt_t *o,
+                         const bmh_refidx_t *bns, const uint8_t *pac, int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id,
+                         char **text, int64_t *text_off);
+/* Of the last bmh_reads_sam_device call on this context that got as far as the hand-off; all -1 before the first.
+ *   reads                 of the batch
+ *   regions_in, regions   before and after the de-duplication plus drop-exact
+ *   kmax, opool_cap       what regs_plan_kernel found: the largest index of the log table (at least 1), the oriented pool's capacity
+ *   handoff_d2h_bytes     bytes that came down between the last replay round and phase 2's upload: 128, whatever n
+ *   waits_tail            host waits behind the last replay round of chains-to-regions: 1 and phase 2's (bmh_last_phase2_text_stats)
+ *   plan_ms               regs_plan_kernel's milliseconds with bmh_set_kernel_timing on, else -1
+ *   neg_index             1 where a region asked for a negative table index (the call then returned BMH_E_RANGE), else 0 */
+typedef struct bmh_reads_sam_stats {
+	int64_t reads, regions_in, regions;
+	int64_t kmax, opool_cap, handoff_d2h_bytes;
+	int32_t waits_tail;
+	float plan_ms;
+	int32_t neg_index, rsv_;
+} bmh_reads_sam_stats_t; /* 64 bytes */
+int bmh_last_reads_sam_stats(const bmh_ctx_t *ctx, bmh_reads_sam_stats_t *st);
 
 #ifdef __cplusplus
 }
