@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -91,13 +92,17 @@ static int fetch_err(bmh_ctx *ctx)
 // (slow, process-wide serialised) path for pageable memory; larger transfers go the direct way, and so do all the
 // transfers of a Stager that stage() was not called for.
 constexpr size_t kStageMax = (size_t)64 << 20;
+// where a phase 2 session counts its bytes and the host's waits: h2d_bytes, d2h_bytes and waits of the statistics record it reports to
+// (ctx->p2, ctx->stx or ctx->pt).  Null: nothing is counted (the batch calls, the stand-alone passes A and B)
+struct StagerCount {
+	int64_t *h2d = nullptr, *d2h = nullptr;
+	int32_t *waits = nullptr;
+};
 struct Stager {
 	bmh_ctx *ctx;
 	bool wide; // an extension batch: end() adds what the int32 kernel received to ctx->wide_total
 	bool up = false, down = false;
-	bool p2 = false; // the fused phase 2 session: bytes and waits go to ctx->p2 (bmh_last_phase2_stats)
-	bool sx = false; // bmh_sam_text_device's session: they go to ctx->stx (bmh_last_samtext_stats)
-	bool pt = false; // bmh_phase2_text_device's session: they go to ctx->pt (bmh_last_phase2_text_stats)
+	StagerCount cnt;
 	size_t up_used = 0, down_used = 0;
 	struct Pending {
 		void *dst;
@@ -120,9 +125,7 @@ struct Stager {
 			memcpy(h, src, bytes);
 			up_used += (bytes + 63) & ~(size_t)63, src = h;
 		}
-		if (p2) ctx->p2.h2d_bytes += (int64_t)bytes;
-		if (sx) ctx->stx.h2d_bytes += (int64_t)bytes;
-		if (pt) ctx->pt.h2d_bytes += (int64_t)bytes;
+		if (cnt.h2d) *cnt.h2d += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
 		return BMH_OK;
 	}
@@ -134,20 +137,18 @@ struct Stager {
 			pend[n_pend++] = Pending{dst, down_used, bytes};
 			down_used += (bytes + 63) & ~(size_t)63;
 		}
-		if (p2) ctx->p2.d2h_bytes += (int64_t)bytes;
-		if (sx) ctx->stx.d2h_bytes += (int64_t)bytes;
-		if (pt) ctx->pt.d2h_bytes += (int64_t)bytes;
+		if (cnt.d2h) *cnt.d2h += (int64_t)bytes;
 		BMH_HIP(ctx, hipMemcpyAsync(to, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
 		return BMH_OK;
 	}
+	// a wait the session made itself, behind a download of `bytes` that did not go through d2h()
+	void waited(size_t bytes) { if (cnt.waits) ++*cnt.waits, *cnt.d2h += (int64_t)bytes; }
 	// The one way out of a call that has enqueued work on ctx's stream, rc being how far it got: wait for the stream and read
 	// and clear the device error flag whatever happened, then -- only if everything was enqueued -- copy what was staged to
 	// the caller and count the int32 kernel's tasks.  Returns rc, else the device's verdict.
 	int end(int rc)
 	{
-		if (p2) ++ctx->p2.waits;
-		if (sx) ++ctx->stx.waits;
-		if (pt) ++ctx->pt.waits;
+		waited(0);
 		if (rc) { // (the flag's text must not replace why the call failed)
 			std::string why = std::move(ctx->last_error);
 			(void)fetch_err(ctx);
@@ -1735,11 +1736,38 @@ struct Block {
 	}
 };
 
-struct HostBuf { // malloc'd, freed on the way out
-	uint8_t *p;
-	explicit HostBuf(size_t bytes) : p((uint8_t *)malloc(bytes)) {}
+struct HostBuf { // malloc'd (zero: calloc'd), freed on the way out
+	uint8_t *p = nullptr;
+	HostBuf() = default;
+	explicit HostBuf(size_t bytes, bool zero = false) { alloc(bytes, zero); }
 	~HostBuf() { free(p); }
+	HostBuf(const HostBuf &) = delete;
+	uint8_t *alloc(size_t bytes, bool zero = false) { return p = (uint8_t *)(zero ? calloc(bytes, 1) : malloc(bytes)); }
 };
+
+// the bases of a slice's reads
+static size_t reads_total(int n, const bmh_read_t *reads)
+{
+	return std::accumulate(reads, reads + n, (size_t)0, [](size_t b, const bmh_read_t &r) { return b + (size_t)r.l_seq; });
+}
+
+// the flat copy of a slice in an upload block: every read's regions to entry roff[i] of reg and, n_want not NULL, its wanted indices to wk's
+static void slice_copy_flat(int n, const bmh_alnreg_v *regs, const int64_t *roff, uint8_t *reg, const int32_t *n_want = nullptr, const int32_t *want_k = nullptr, uint8_t *wk = nullptr)
+{
+	for (int i = 0; i < n; ++i) {
+		if (n_want && n_want[i]) memcpy(wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
+		if (regs[i].n) memcpy(reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+	}
+}
+
+// what the text calls answer for n == 0: an empty text, text_off[0] = 0
+static int empty_text(char **text, int64_t *text_off)
+{
+	char *p = (char *)malloc(1);
+	if (!p) return BMH_E_NOMEM;
+	*text = p, text_off[0] = 0;
+	return BMH_OK;
+}
 
 // the statistics of the phase 2 calls as a call that has done nothing leaves them
 static void reset_decide_stats(bmh_ctx *ctx) { ctx->decide_units = 0, ctx->decide_fallbacks = 0, ctx->decide_ms = -1.f; }
@@ -1813,8 +1841,7 @@ static void decide_fill(uint8_t *up, const DecideBlock &L, const bmh_sam_opt_t *
 	hdr->opt = *o;
 	if (o->flag & BMH_MEM_F_PE) memcpy(hdr->pes, pes, sizeof(hdr->pes));
 	if (T.n_term) bmh_pp_fill_term_(o, pes, T.term_off, (double *)(up + L.term));
-	for (int i = 0; roff && i < n; ++i)
-		if (regs[i].n) memcpy(up + L.reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
+	if (roff) slice_copy_flat(n, regs, roff, up + L.reg);
 }
 
 // Stages a session that moves up_bytes and down_bytes beside the log table, and brings the device's copy of the table to want_log
@@ -2016,17 +2043,16 @@ static int wanted_run_round(bmh_ctx *ctx, const WantedArgs &A, const WantedStatu
 
 // the status records: the only thing the host reads between launches.  The wanted regions are n_lo..n_hi: the count where the host
 // knows it, 0..the capacity where pass A left the want list on the device.  The fused sessions' Stager counts the read.  The session
-// through to the text (st.pt) reads the record of the round just planned alone -- a refused region raises both records' error words,
+// through to the text (`one`) reads the record of the round just planned alone -- a refused region raises both records' error words,
 // both carry n_w, and record 0 is still the host's from the first look -- so that its downloads stay the text's and three small records.
-static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, const Stager &st, int round)
+static int wanted_read_status(bmh_ctx *ctx, const uint8_t *d_stat, int64_t n_lo, int64_t n_hi, Stager &st, bool one, int round)
 {
 	const WantedStatus *hs = (const WantedStatus *)ctx->h_wstat;
-	const size_t at = st.pt ? (size_t)round * sizeof(WantedStatus) : 0, bytes = (st.pt ? 1 : 2) * sizeof(WantedStatus);
+	const size_t at = one ? (size_t)round * sizeof(WantedStatus) : 0, bytes = (one ? 1 : 2) * sizeof(WantedStatus);
 	BMH_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->h_wstat + at, d_stat + at, bytes, hipMemcpyDeviceToHost, ctx->stream));
 	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-	if (st.p2) ++ctx->p2.waits, ctx->p2.d2h_bytes += (int64_t)bytes;
-	if (st.pt) ++ctx->pt.waits, ctx->pt.d2h_bytes += (int64_t)bytes;
-	const bool both = !st.pt || round == 1; // record 1 has been read
+	st.waited(bytes);
+	const bool both = !one || round == 1; // record 1 has been read
 	if (hs[0].err || (both && hs[1].err)) {
 		ctx->last_error = "bmh_wanted_cigar_device: a wanted region is outside its read, its vector or the reference, or nothing is left of it";
 		return hs[0].err ? hs[0].err : hs[1].err;
@@ -2104,6 +2130,23 @@ struct WantedDown {
 	~WantedDown() { free(wres); }
 };
 
+struct WantedSizes { // what a pass B session is sized from
+	size_t total, reads_bytes, wc, opool_cap; // regions, bases, the capacity in wanted regions, the oriented pool's bytes
+	int n;
+	int64_t l_pac;
+};
+
+// a session's inputs where they lie on the device: the offsets, the want list and the regions, the read offsets and the parameters
+static WantedArgs wanted_inputs(const void *roff, const int32_t *n_want, const int32_t *want_k, const bmh_alnreg_t *reg, const uint8_t *seq_off, const uint8_t *hdr,
+                                const WantedSizes &Z)
+{
+	WantedArgs A{};
+	A.roff = (const unsigned long long *)roff, A.seq_off = (const unsigned long long *)seq_off, A.hdr = (const WantedHdr *)hdr;
+	A.n_want = n_want, A.want_k = want_k, A.reg = reg;
+	A.total = Z.total, A.reads_bytes = Z.reads_bytes, A.n = Z.n, A.l_pac = Z.l_pac, A.w_cap = Z.wc, A.opool_cap = Z.opool_cap;
+	return A;
+}
+
 // The launches and the downloads.  A: the inputs as the caller set them -- roff, seq_off, hdr, n_want, want_k and reg where they lie on
 // the device, total, reads_bytes, n, l_pac, w_cap, opool_cap; the rest is set here.  dw, L: the session's arrays; n_lo..n_hi: see
 // wanted_read_status.  D's arrays (malloc'd here) are written behind st.end().
@@ -2122,10 +2165,10 @@ static int wanted_session(bmh_ctx *ctx, const char *who, Stager &st, WantedArgs 
 	A.fix_res = (const bmh_region_res_t *)(dw + L.res0), A.fix_cig = (const uint32_t *)(dw + L.cig0);
 	A.main_res = (const bmh_region_res_t *)(dw + L.res1), A.wres = (bmh_wanted_res_t *)(dw + L.wres);
 	A.status = (WantedStatus *)(dw + L.stat), A.err = ctx->d_err;
-	if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st, 0))) return e;
+	if ((e = launch_wanted_begin(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st, D.stay, 0))) return e;
 	if ((e = wanted_run_round(ctx, A, hs[0], 0, d_pool, rpool_off, (bmh_region_res_t *)(dw + L.res0), (uint32_t *)(dw + L.cig0), (char *)(dw + L.md0), kWantFixMdSlot)))
 		return e;
-	if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st, 1))) return e;
+	if ((e = launch_wanted_main(ctx, A)) || (e = wanted_read_status(ctx, dw + L.stat, n_lo, n_hi, st, D.stay, 1))) return e;
 	if ((e = wanted_run_round(ctx, A, hs[1], 1, d_pool, rpool_off, (bmh_region_res_t *)(dw + L.res1), (uint32_t *)(dw + L.cig1), (char *)(dw + L.md1), kWantMdSlot)))
 		return e;
 	if ((e = launch_wanted_results(ctx, A))) return e;
@@ -2143,31 +2186,54 @@ static int wanted_session(bmh_ctx *ctx, const char *who, Stager &st, WantedArgs 
 	return bc && ((e = st.d2h(D.cig, dw + L.cig1, bc)) || (e = st.d2h(D.md, dw + L.md1, bm))) ? e : BMH_OK;
 }
 
-// the planning kernels' time of the session just ended (timing mode)
-static int wanted_kernel_ms(bmh_ctx *ctx)
+// the planning kernels' time of the session just ended to *ms (timing mode)
+static int wanted_kernel_ms(bmh_ctx *ctx, float *ms)
 {
 	float a = 0.f, b = 0.f;
 	if (!ctx->timing || !ctx->ev_wanted[3]) return BMH_OK;
 	BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
 	BMH_HIP(ctx, hipEventElapsedTime(&b, ctx->ev_wanted[2], ctx->ev_wanted[3]));
-	ctx->wanted_ms = a + b;
+	*ms = a + b;
 	return BMH_OK;
 }
 
+// a region whose alignment outgrew its slots: its read, and its record with the coordinates as cut (a region whose fix is redone still has its own)
+struct RedoRegion {
+	int read;
+	bmh_alnreg_t reg;
+};
+struct RedoOut { // what the redo makes: one record per region in the order given, cigar_off / md_off addressing cig / md
+	std::vector<bmh_wanted_res_t> hw;
+	uint32_t *cig = nullptr;
+	char *md = nullptr;
+	~RedoOut() { free(cig), free(md); }
+};
+
+// the host's redo: through the host form again (it enters the device gate itself), one region per read of a small slice of its own
+static int wanted_redo_host(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_t *pac, int w, const bmh_read_t *reads, std::vector<RedoRegion> &rr, RedoOut &R)
+{
+	const size_t m = rr.size();
+	R.hw.resize(m);
+	if (!m) return BMH_OK;
+	std::vector<bmh_alnreg_v> rv(m);
+	std::vector<bmh_read_t> rd(m);
+	std::vector<int64_t> ro(m + 1);
+	std::vector<int32_t> one(m, 1), zero(m, 0);
+	for (size_t t = 0; t < m; ++t) rv[t].n = rv[t].m = 1, rv[t].a = &rr[t].reg, rd[t] = reads[rr[t].read], ro[t] = (int64_t)t;
+	ro[m] = (int64_t)m;
+	return bmh_wanted_host_(ctx, bns, pac, w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, R.hw.data(), &R.cig, &R.md, nullptr);
+}
+
 // The host's tail.  What came down is checked; the regions flagged BMH_WANTED_HOST, whose alignments outgrew their slots, go through
-// the host form again, one region per read of a small slice of its own (the fix again for a region whose fix outgrew its slot), (read, k)
-// from the want list, the region's record from `arena` -- every read's regions flat at roff: the stand-alone form's upload, the fused
-// session's sorted download -- with the coordinates as cut; then CIGAR and MD are packed in want order.  wr: D.n_w records, D.wres
+// wanted_redo_host, (read, k) from the want list, the region's record from `arena` -- every read's regions flat at roff: the stand-alone
+// form's upload, the fused session's sorted download -- with the coordinates as cut; then CIGAR and MD are packed in want order.  wr: D.n_w records, D.wres
 // itself if the caller likes; *cig_ / *md_: malloc'd, the caller frees them.  The want list is the caller's or checked by the caller.  who: the public entry point.
 static int wanted_tail(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns, const uint8_t *pac, int w, int n, const bmh_read_t *reads,
                        const int64_t *roff, const int32_t *n_want, const int32_t *want_k, const bmh_alnreg_t *arena, const WantedDown &D,
                        bmh_wanted_res_t *wr, uint32_t **cig_, char **md_, int64_t *redone)
 {
-	struct Redo {
-		int64_t j;
-		int read, k;
-	};
-	std::vector<Redo> redo;
+	std::vector<int64_t> redo; // their places in want order
+	std::vector<RedoRegion> rr;
 	const int64_t n_w = D.n_w;
 	size_t cu = 0, mu = 0;
 	int64_t j = 0;
@@ -2181,35 +2247,17 @@ static int wanted_tail(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns, c
 				ctx->last_error = std::string(who) + ": the device's records are inconsistent";
 				return BMH_E_ARG;
 			}
-			if (host) redo.push_back(Redo{j, i, k});
-			else cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+			if (host) {
+				redo.push_back(j), rr.push_back(RedoRegion{i, arena[roff[i] + k]});
+				bmh_alnreg_t &a = rr.back().reg;
+				a.rb = x.rb, a.re = x.re, a.qb = x.qb, a.qe = x.qe;
+			} else cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
 		}
 	const size_t m = redo.size();
-	std::vector<bmh_wanted_res_t> hw(m);
-	uint32_t *hcig = nullptr;
-	char *hmd = nullptr;
-	struct Free {
-		uint32_t *&a;
-		char *&b;
-		~Free() { free(a), free(b); }
-	} guard{hcig, hmd};
-	if (m) {
-		std::vector<bmh_alnreg_t> ra(m);
-		std::vector<bmh_alnreg_v> rv(m);
-		std::vector<bmh_read_t> rd(m);
-		std::vector<int64_t> ro(m + 1);
-		std::vector<int32_t> one(m, 1), zero(m, 0);
-		for (size_t t = 0; t < m; ++t) {
-			const bmh_wanted_res_t &x = D.wres[redo[t].j];
-			ra[t] = arena[roff[redo[t].read] + redo[t].k];
-			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe; // (as cut; a region whose fix is redone still has its own)
-			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[redo[t].read], ro[t] = (int64_t)t;
-		}
-		ro[m] = (int64_t)m;
-		const int rc = bmh_wanted_host_(ctx, bns, pac, w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr);
-		if (rc) return rc;
-	}
-	for (const bmh_wanted_res_t &x : hw) cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
+	RedoOut H;
+	const int rc = wanted_redo_host(ctx, bns, pac, w, reads, rr, H);
+	if (rc) return rc;
+	for (const bmh_wanted_res_t &x : H.hw) cu += (size_t)x.n_cigar, mu += (size_t)x.md_len + 1;
 	uint32_t *cig = (uint32_t *)malloc(4 * (cu + 4));
 	char *md = (char *)malloc(mu + 4);
 	if (!cig || !md) {
@@ -2223,9 +2271,9 @@ static int wanted_tail(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns, c
 		bmh_wanted_res_t x = D.wres[j];
 		const uint32_t *sc;
 		const char *sm;
-		if (t < m && redo[t].j == j) {
+		if (t < m && redo[t] == j) {
 			const uint32_t fl = x.flags;
-			x = hw[t], sc = hcig + x.cigar_off, sm = hmd + x.md_off;
+			x = H.hw[t], sc = H.cig + x.cigar_off, sm = H.md + x.md_off;
 			x.flags |= fl | BMH_WANTED_HOST;
 			++t;
 		} else sc = (const uint32_t *)D.cig + (size_t)x.cigar_off * BMH_RP_SMALL_CAP, sm = (const char *)D.md + (size_t)x.md_off * kWantMdSlot;
@@ -2249,14 +2297,13 @@ static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_
 	if (rc || n_w == 0) return rc;
 	if (n_w > (1 << 28) || n > (1 << 28)) return BMH_E_ARG;
 	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = (size_t)n_w;
-	size_t reads_bytes = 0, opool_cap = 0;
-	for (int i = 0; i < n; ++i) {
-		reads_bytes += (size_t)reads[i].l_seq;
+	const size_t reads_bytes = reads_total(n, reads);
+	size_t opool_cap = 0;
+	for (int i = 0; i < n; ++i)
 		for (int q = 0; q < n_want[i]; ++q) {
 			const int k = want_k[roff[i] + q];
 			if (k >= 0 && (size_t)k < regs[i].n) opool_cap += oriented_cap(&regs[i].a[k]); // (another the kernel refuses)
 		}
-	}
 	// the device block: [offsets | read offsets | parameters | n_want | want_k | regions] up, then the session's arrays
 	Block b;
 	b.take((nr + 1) * 8);
@@ -2271,10 +2318,8 @@ static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_
 	memcpy(up.p, roff, (nr + 1) * 8);
 	wanted_fill(ctx, w, n, reads, (uint64_t *)(up.p + o_soff), (WantedHdr *)(up.p + o_hdr), rpool.p);
 	memcpy(up.p + o_nw, n_want, nr * 4);
-	for (int i = 0; i < n; ++i) {
-		if (n_want[i]) memcpy(up.p + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
-		if (regs[i].n) memcpy(up.p + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
-	}
+	slice_copy_flat(n, regs, roff, up.p + o_reg, n_want, want_k, up.p + o_wk);
+	const WantedSizes Z{total, reads_bytes, wc, opool_cap, n, bns->l_pac};
 	WantedDown D;
 	{ // the device section, inside the caller's gate (the redo enters it again through the host form)
 	GateGuard gate;
@@ -2286,15 +2331,12 @@ static int wanted_device_run(bmh_ctx *ctx, const bmh_refidx_t *bns, const uint8_
 		if ((e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, L.end, &rpool_off)) || (e = st.stage(b_up + reads_bytes + 256, L.end - L.wres + 256))) return e;
 		uint8_t *d = (uint8_t *)ctx->d_wanted.p;
 		if ((e = st.h2d(d, up.p, b_up)) || (e = st.h2d((uint8_t *)ctx->d_pool.p + rpool_off, rpool.p, reads_bytes + 16))) return e;
-		WantedArgs A{};
-		A.roff = (const unsigned long long *)d, A.seq_off = (const unsigned long long *)(d + o_soff), A.hdr = (const WantedHdr *)(d + o_hdr);
-		A.n_want = (const int32_t *)(d + o_nw), A.want_k = (const int32_t *)(d + o_wk), A.reg = (const bmh_alnreg_t *)(d + o_reg);
-		A.total = total, A.reads_bytes = reads_bytes, A.n = n, A.l_pac = bns->l_pac, A.w_cap = wc, A.opool_cap = opool_cap;
+		const WantedArgs A = wanted_inputs(d, (const int32_t *)(d + o_nw), (const int32_t *)(d + o_wk), (const bmh_alnreg_t *)(d + o_reg), d + o_soff, d + o_hdr, Z);
 		return wanted_session(ctx, "bmh_wanted_cigar_device", st, A, d, L, rpool_off, n_w, n_w, D);
 	}();
 	rc = st.end(rc);
 	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
-	if (rc || (rc = wanted_kernel_ms(ctx))) return rc;
+	if (rc || (rc = wanted_kernel_ms(ctx, &ctx->wanted_ms))) return rc;
 	}
 	int64_t redone = 0;
 	rc = wanted_tail(ctx, "bmh_wanted_cigar_device", bns, pac, w, n, reads, roff, n_want, want_k, (const bmh_alnreg_t *)(up.p + o_reg), D, wr, cig_, md_, &redone);
@@ -2373,6 +2415,66 @@ struct Phase2Run {
 	~Phase2Run() { free(wr), free(cig), free(md); }
 };
 
+// What passes A and B of a fused session are sized from, pass A's tables, and the two blocks: pass A's with pass B's inputs in it, and
+// pass B's arrays in a block of their own.  Z.wc = Z.total: the capacity of everything per wanted region, which bounds their number.
+struct Phase2Plan {
+	DecideTables T;
+	DecideBlock LA;
+	WantedBlock LB;
+	WantedSizes Z;
+	bool pe;
+	int64_t id0;
+};
+
+// ... from the caller's vectors or, res, from what regs_plan_kernel found.  The oriented pool is sized from the clamped lengths of every
+// region: a sum the sort does not change, and a cut only shortens a region.  *why not NULL: the tables' refusal, before any upload.
+static int phase2_plan(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_pestat_t *pes, int64_t l_pac, int64_t id0, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
+                       const ResidentRegs *res, size_t total, Phase2Plan &P, const char **why)
+{
+	DecideTables &T = P.T;
+	size_t opool_cap = 0;
+	int rc;
+	*why = nullptr;
+	if (res) {
+		const bmh_ho_plan_t plan{res->kmax, res->opool_cap, res->total, res->neg ? 1 : 0, 0};
+		rc = decide_tables_from_plan(o, pes, plan, 0, &T.kmax, &T.n_term, T.term_off, why);
+		opool_cap = (size_t)res->opool_cap;
+	} else
+		rc = decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, why, &opool_cap);
+	if (rc || (rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
+	P.pe = (o->flag & BMH_MEM_F_PE) != 0, P.id0 = id0;
+	P.Z = WantedSizes{total, reads_total(n, reads), total, opool_cap, n, l_pac};
+	P.LA = decide_block((size_t)n, total, (size_t)T.n_term, P.pe, true);
+	Block b;
+	P.LB = wanted_block(b, (size_t)n, P.Z.wc);
+	return BMH_OK;
+}
+
+// Passes A and B of a fused session on the stream, up to and including wanted_session: the workspaces, the log table, upload(d, rpool)
+// -- what the session sends or copies into pass A's block at d and pass B's reads pool at rpool, staged as up_bytes and down_bytes --
+// then decide_kernel and, where there are regions, pass B on what it left in place: no wait, no copy in between.  gather: the reads
+// pool is not uploaded but made on the device from the per-read pool that these arguments of pass C name.
+static int phase2_enqueue_ab(bmh_ctx *ctx, const char *who, Stager &st, const Phase2Plan &P, size_t up_bytes, size_t down_bytes,
+                             const std::function<int(uint8_t *, uint8_t *)> &upload, const SamtextArgs *gather, WantedDown &D)
+{
+	const WantedSizes &Z = P.Z;
+	int e;
+	size_t rpool_off;
+	if ((e = ensure(ctx, ctx->d_decide, P.LA.end)) || (e = wanted_reserve(ctx, Z.wc, Z.opool_cap, Z.reads_bytes, P.LB.end, &rpool_off))) return e;
+	if ((e = decide_stage_log(ctx, st, P.T.want_log, up_bytes, down_bytes))) return e;
+	uint8_t *d = (uint8_t *)ctx->d_decide.p, *rpool = (uint8_t *)ctx->d_pool.p + rpool_off;
+	if ((e = upload(d, rpool))) return e;
+	BMH_HIP(ctx, hipMemsetAsync(d + P.LA.nw, 0, (size_t)Z.n * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
+	const DecideArgs DA = decide_args(ctx, d, P.LA, P.T, Z.total, Z.l_pac, P.id0, Z.n, P.pe);
+	if ((e = launch_decide(ctx, DA)) || !Z.wc) return e;
+	if (gather) { // the bases of the per-read pool at seq_off[], 16 zero bytes behind them
+		BMH_HIP(ctx, hipMemsetAsync(rpool + Z.reads_bytes, 0, 16, ctx->stream));
+		if ((e = launch_reads_gather(ctx, *gather, (const unsigned long long *)(d + P.LA.soff), rpool, Z.reads_bytes))) return e;
+	}
+	const WantedArgs A = wanted_inputs(DA.roff, DA.n_want, DA.want_k, DA.reg, d + P.LA.soff, d + P.LA.whdr, Z);
+	return wanted_session(ctx, who, st, A, (uint8_t *)ctx->d_wanted.p, P.LB, rpool_off, 0, (int64_t)Z.wc, D);
+}
+
 // The session up to its own records and pools, for the public call and bmh_sam_batch.  n > 0 and the arguments checked.  *tables: the
 // BMH_E_RANGE is bmh_decide_device's refusal before any upload, not a kernel's.
 static int phase2_device_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,
@@ -2384,66 +2486,45 @@ static int phase2_device_run(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_ref
 	int rc = need_resident(ctx, "bmh_phase2_device", bns, pac);
 	if (rc) return rc;
 	if (n > (1 << 28) || roff[n] > (1 << 28)) return BMH_E_ARG;
-	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
-	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = total; // wc: the capacity of everything per wanted region, which bounds their number
-	DecideTables T;
-	const char *why = nullptr;
-	if (decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why)) {
-		ctx->last_error = why;
-		ctx->decide_fallbacks = 1, ctx->p2.fallbacks = 1, *tables = true;
-		return BMH_E_RANGE;
+	Phase2Plan P;
+	const char *why;
+	if ((rc = phase2_plan(ctx, o, pes, bns->l_pac, id0, n, reads, regs, nullptr, (size_t)roff[n], P, &why))) {
+		if (why) {
+			ctx->last_error = why;
+			ctx->decide_fallbacks = 1, ctx->p2.fallbacks = 1, *tables = true;
+		}
+		return rc;
 	}
-	if ((rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
-	// the oriented pool from the clamped lengths of every region: a sum the sort does not change, and a cut only shortens a region
-	size_t reads_bytes = 0, opool_cap = 0;
-	for (int i = 0; i < n; ++i) {
-		reads_bytes += (size_t)reads[i].l_seq;
-		for (size_t k = 0; k < regs[i].n; ++k) opool_cap += oriented_cap(&regs[i].a[k]);
-	}
-	// pass A's block with pass B's inputs in it, and the session's arrays in a block of their own
-	const DecideBlock LA = R.L = decide_block(nr, total, (size_t)T.n_term, pe, true);
-	Block b;
-	const WantedBlock LB = wanted_block(b, nr, wc);
+	const DecideBlock &LA = R.L = P.LA;
+	const size_t reads_bytes = P.Z.reads_bytes, wc = P.Z.wc;
+	const bool pe = P.pe;
 	HostBuf up(LA.up()), rpool(reads_bytes + 16);
 	if (!up.p || !rpool.p) {
 		ctx->last_error = "bmh_phase2_device: out of host memory";
 		return BMH_E_NOMEM;
 	}
 	R.down.resize(LA.down());
-	decide_fill(up.p, LA, o, pes, T, n, regs, roff);
+	decide_fill(up.p, LA, o, pes, P.T, n, regs, roff);
 	wanted_fill(ctx, o->w, n, reads, (uint64_t *)(up.p + LA.soff), (WantedHdr *)(up.p + LA.whdr), rpool.p);
 	WantedDown D;
 	{ // the device section, inside the caller's gate (the redo enters it again through the host form)
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	Stager st(ctx);
-	st.p2 = true;
-	rc = [&]() -> int {
-		int e;
-		size_t rpool_off;
-		if ((e = ensure(ctx, ctx->d_decide, LA.end)) || (e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, LB.end, &rpool_off))) return e;
-		if ((e = decide_stage_log(ctx, st, T.want_log, LA.up() + reads_bytes + 256, LA.down() + (LB.end - LB.wres) + 256))) return e;
-		uint8_t *d = (uint8_t *)ctx->d_decide.p;
-		if ((e = st.h2d(d, up.p, LA.up())) || (e = st.h2d((uint8_t *)ctx->d_pool.p + rpool_off, rpool.p, reads_bytes + 16))) return e;
-		BMH_HIP(ctx, hipMemsetAsync(d + LA.nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
-		const DecideArgs DA = decide_args(ctx, d, LA, T, total, bns->l_pac, id0, n, pe);
-		if ((e = launch_decide(ctx, DA))) return e;
-		if (wc) { // pass B reads n_want, want_k and the sorted regions where decide_kernel left them: no wait, no copy in between
-			WantedArgs A{};
-			A.roff = DA.roff, A.seq_off = (const unsigned long long *)(d + LA.soff), A.hdr = (const WantedHdr *)(d + LA.whdr);
-			A.n_want = DA.n_want, A.want_k = DA.want_k, A.reg = DA.reg;
-			A.total = total, A.reads_bytes = reads_bytes, A.n = n, A.l_pac = bns->l_pac, A.w_cap = wc, A.opool_cap = opool_cap;
-			if ((e = wanted_session(ctx, "bmh_phase2_device", st, A, (uint8_t *)ctx->d_wanted.p, LB, rpool_off, 0, (int64_t)wc, D))) return e;
-		}
-		return st.d2h(R.down.data(), d + LA.reg, LA.down());
-	}();
+	st.cnt = {&ctx->p2.h2d_bytes, &ctx->p2.d2h_bytes, &ctx->p2.waits};
+	auto upload = [&](uint8_t *d, uint8_t *d_rpool) {
+		const int e = st.h2d(d, up.p, LA.up());
+		return e ? e : st.h2d(d_rpool, rpool.p, reads_bytes + 16);
+	};
+	rc = phase2_enqueue_ab(ctx, "bmh_phase2_device", st, P, LA.up() + reads_bytes + 256, LA.down() + (P.LB.end - P.LB.wres) + 256, upload, nullptr, D);
+	if (!rc) rc = st.d2h(R.down.data(), (uint8_t *)ctx->d_decide.p + LA.reg, LA.down());
 	rc = st.end(rc);
 	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region (BMH_REGION_CIGAR_CUT)
 	if (rc) return rc;
-	ctx->logk_n = T.want_log;
+	ctx->logk_n = P.T.want_log;
 	if (ctx->timing) {
 		BMH_HIP(ctx, hipEventElapsedTime(&ctx->decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
-		if (wc && (rc = wanted_kernel_ms(ctx))) return rc;
+		if (wc && (rc = wanted_kernel_ms(ctx, &ctx->wanted_ms))) return rc;
 	}
 	}
 	// the want list as pass A left it, checked against the vectors and the session's count; then pass B's tail over the downloaded,
@@ -2625,11 +2706,141 @@ static int need_refnames(bmh_ctx *ctx, const char *who, const bmh_refidx_t *bns)
 	return BMH_OK;
 }
 
+// Pass C's device block, in two forms.  Stand-alone (bmh_sam_text_device): [roff | first | poff | SamtextHdr | rg_id | n_want | want_k |
+// reg_mapq | pd | regions | records | CIGAR | MD | the per-read pool] up, then what the kernels make: the records, plans, sizes,
+// offsets and the status.  Fused (the session through to the text): the want list, mapQ, verdicts, regions, records, CIGAR and MD lie
+// in pass A's and pass B's blocks, so [SamtextHdr | rg_id | poff | the per-read pool] goes up, a SamtextFused sits behind the status
+// and the list of the host's regions behind that.
+struct SamtextBlock {
+	size_t roff, first, poff, hdr, rg, nw, wk, mq, pd, reg, wr, cig, md, pool, up, alns, plan, size, toff, stat, list, end;
+	size_t pool_bytes, stat_bytes; // the per-read pool; what the look brings down: the status, and the SamtextFused where there is one
+	bool fused;
+};
+
+static SamtextBlock samtext_block(bool fused, size_t n, size_t total, size_t wc, size_t l_rg, size_t pool_bytes, bool pe, size_t cig_words, size_t md_bytes)
+{
+	Block b;
+	SamtextBlock L{};
+	if (!fused) L.roff = b.take((n + 1) * 8), L.first = b.take((n + 1) * 8), L.poff = b.take((n + 1) * 8);
+	L.hdr = b.take(sizeof(SamtextHdr)), L.rg = b.take(l_rg);
+	if (fused) L.poff = b.take((n + 1) * 8);
+	else {
+		L.nw = b.take(n * 4), L.wk = b.take(total * 4), L.mq = b.take(total * 4), L.pd = b.take(pe ? (n >> 1) * sizeof(bmh_pairdec_t) : 0);
+		L.reg = b.take(total * sizeof(bmh_alnreg_t)), L.wr = b.take(wc * sizeof(bmh_wanted_res_t)), L.cig = b.take(cig_words * 4), L.md = b.take(md_bytes);
+	}
+	L.pool = b.take(pool_bytes), L.up = b.at, L.pool_bytes = pool_bytes, L.fused = fused;
+	L.alns = b.take(wc * sizeof(bmh_st_aln_t)), L.plan = b.take(n * sizeof(bmh_st_plan_t)), L.size = b.take(n * 8), L.toff = b.take((n + 1) * 8);
+	L.stat_bytes = sizeof(SamtextStatus) + (fused ? sizeof(SamtextFused) : 0);
+	L.stat = b.take(L.stat_bytes), L.list = b.take(fused ? wc * sizeof(Phase2TextHost) : 0), L.end = b.at;
+	return L;
+}
+
+// Pass C's arguments for the size kernels (text and text_cap are the emit's: samtext_emit_down) over its block at dt.  Fused: the want
+// list, mapQ, verdicts and sorted regions where decide_kernel left them in pass A's block at d; first[] and the records where pass B's
+// kernels left them in its block at dw, CIGAR and MD in the main round's slots there (and the overflow area behind the block)
+static SamtextArgs samtext_args(bmh_ctx *ctx, uint8_t *dt, const SamtextBlock &L, size_t total, size_t n_w, size_t cig_words, size_t md_bytes, int n, bool pe,
+                                int64_t l_pac, const uint8_t *d = nullptr, const DecideBlock *LA = nullptr, const uint8_t *dw = nullptr, const WantedBlock *LB = nullptr)
+{
+	const bool f = L.fused;
+	SamtextArgs A{};
+	A.roff = (const int64_t *)(f ? d : dt + L.roff), A.first = (const int64_t *)(f ? dw + LB->first : dt + L.first), A.poff = (const unsigned long long *)(dt + L.poff);
+	A.hdr = (const SamtextHdr *)(dt + L.hdr), A.rg = (const char *)(dt + L.rg);
+	A.n_want = (const int32_t *)(f ? d + LA->nw : dt + L.nw), A.want_k = (const int32_t *)(f ? d + LA->wk : dt + L.wk);
+	A.reg_mapq = (const int32_t *)(f ? d + LA->mq : dt + L.mq), A.pd = (const bmh_pairdec_t *)(f ? d + LA->pd : dt + L.pd);
+	A.reg = (const bmh_alnreg_t *)(f ? d + LA->reg : dt + L.reg), A.wr = (const bmh_wanted_res_t *)(f ? dw + LB->wres : dt + L.wr);
+	A.cig = (const uint32_t *)(f ? dw + LB->cig1 : dt + L.cig), A.md = (const char *)(f ? dw + LB->md1 : dt + L.md), A.rpool = dt + L.pool;
+	A.total = total, A.n_w = n_w, A.cig_words = cig_words, A.md_bytes = md_bytes, A.rpool_bytes = L.pool_bytes;
+	A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.name_off = (const uint64_t *)ctx->d_refnames.p;
+	A.names = (const char *)ctx->d_refnames.p + ((size_t)ctx->refnames_n + 1) * 8;
+	A.n_seqs = ctx->refidx_n, A.n = n, A.pe = pe, A.l_pac = l_pac;
+	A.alns = (bmh_st_aln_t *)(dt + L.alns), A.plan = (bmh_st_plan_t *)(dt + L.plan), A.size = (unsigned long long *)(dt + L.size);
+	A.toff = (unsigned long long *)(dt + L.toff), A.status = (SamtextStatus *)(dt + L.stat), A.text = nullptr, A.text_cap = 0, A.err = ctx->d_err;
+	A.fused = f ? (SamtextFused *)(dt + L.stat + sizeof(SamtextStatus)) : nullptr;
+	return A;
+}
+
+// the sections of pass C's upload that both forms have, into zeroed memory: SamtextHdr, rg_id, poff and the per-read pool
+static void samtext_fill_up(uint8_t *up, const SamtextBlock &L, const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const char *rg_id, size_t l_rg,
+                            const SamtextPool &P, int n, const bmh_seq_t *seqs)
+{
+	SamtextHdr *hdr = (SamtextHdr *)(up + L.hdr);
+	hdr->opt_flag = o->flag, hdr->pe = (o->flag & BMH_MEM_F_PE) != 0, hdr->l_rg = (int32_t)l_rg;
+	if (hdr->pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
+	if (l_rg) memcpy(up + L.rg, rg_id, l_rg);
+	memcpy(up + L.poff, P.poff.data(), ((size_t)n + 1) * 8);
+	P.fill(n, seqs, up + L.pool);
+}
+
+// what pass C holds on the host until everything has succeeded
+struct SamtextOut {
+	int64_t *toff = nullptr; // n + 1, malloc'd by the caller
+	char *out = nullptr;     // the text, malloc'd by samtext_emit_down
+	long long total = 0, lines = 0;
+	~SamtextOut() { free(toff), free(out); }
+};
+
+// pass C, first half: size and scan, then the one look behind them: stat_bytes of the block's status to the session's pinned h_stat
+static int samtext_size_look(bmh_ctx *ctx, const char *who, Stager &st, const SamtextArgs &A, void *h_stat, size_t stat_bytes)
+{
+	int e;
+	if ((e = launch_samtext_size(ctx, A))) return e;
+	BMH_HIP(ctx, hipMemcpyAsync(h_stat, A.status, stat_bytes, hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	st.waited(stat_bytes);
+	if (const int err = ((const SamtextStatus *)h_stat)->err) {
+		ctx->last_error = std::string(who) + ": a record lies outside its read, its vector, the pools or the reference";
+		return err;
+	}
+	return BMH_OK;
+}
+
+// ... second half: the buffer sized from the status at h_stat, the emit kernel, text_off and the text down, stage_up bytes staged up
+// beside them.  O.toff is the caller's already; O.out, O.total and O.lines are set here.
+static int samtext_emit_down(bmh_ctx *ctx, const char *who, Stager &st, SamtextArgs A, const void *h_stat, size_t stage_up, SamtextOut &O)
+{
+	const SamtextStatus *hs = (const SamtextStatus *)h_stat;
+	const size_t nr = (size_t)A.n;
+	int e;
+	O.total = hs->total, O.lines = A.fused ? ((const SamtextFused *)(hs + 1))->lines : 0;
+	if (O.total < 0 || O.total > ((long long)1 << 40) || O.lines < 0) { // cannot happen
+		ctx->last_error = std::string(who) + ": the device's sizes are inconsistent";
+		return BMH_E_ARG;
+	}
+	const size_t bytes = (size_t)O.total;
+	if (!(O.out = (char *)malloc(bytes + 1))) return BMH_E_NOMEM;
+	if ((e = ensure(ctx, ctx->d_sam_out, bytes + 64)) || (e = st.stage(stage_up, (nr + 1) * 8 + bytes + 256))) return e;
+	A.text = (char *)ctx->d_sam_out.p, A.text_cap = (unsigned long long)O.total;
+	if ((e = launch_samtext_emit(ctx, A)) || (e = st.d2h(O.toff, A.toff, (nr + 1) * 8))) return e;
+	return bytes ? st.d2h(O.out, ctx->d_sam_out.p, bytes) : BMH_OK;
+}
+
+// Behind st.end(): the offsets checked, then -- all or nothing, the caller's outputs only now -- the hand-over
+static int samtext_commit(bmh_ctx *ctx, const char *who, int n, SamtextOut &O, char **text, int64_t *text_off)
+{
+	if (O.toff[0] != 0 || O.toff[n] != O.total) { // cannot happen
+		ctx->last_error = std::string(who) + ": the device's offsets are inconsistent";
+		return BMH_E_ARG;
+	}
+	memcpy(text_off, O.toff, ((size_t)n + 1) * 8);
+	*text = O.out, O.out = nullptr;
+	return BMH_OK;
+}
+
+// the size and emit kernels' times of the session just ended (timing mode)
+static int samtext_kernel_ms(bmh_ctx *ctx, float *size_ms, float *emit_ms)
+{
+	if (!ctx->timing) return BMH_OK;
+	BMH_HIP(ctx, hipEventElapsedTime(size_ms, ctx->ev_samtext[0], ctx->ev_samtext[1]));
+	BMH_HIP(ctx, hipEventElapsedTime(emit_ms, ctx->ev_samtext[2], ctx->ev_samtext[3]));
+	return BMH_OK;
+}
+
 int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const bmh_pestat_t *pes, int n, const bmh_seq_t *seqs,
                         const bmh_alnreg_v *regs, const int64_t *roff, const bmh_pairdec_t *pd, const int32_t *reg_mapq, const int32_t *n_want,
                         const int32_t *want_k, const bmh_wanted_res_t *results, const uint32_t *cigar_pool, const char *md_pool, const char *rg_id,
                         char **text, int64_t *text_off)
 {
+	static const char *const who = "bmh_sam_text_device";
 	if (!ctx) return BMH_E_ARG;
 	reset_samtext_stats(ctx);
 	std::vector<int64_t> first((size_t)(n > 0 ? n : 0) + 1);
@@ -2637,117 +2848,48 @@ int bmh_sam_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx
 	size_t cig_words = 0, md_bytes = 0;
 	int rc = bmh_samtext_check_(o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, results, cigar_pool, md_pool, text, text_off, first.data(),
 	                            &lines, &cig_words, &md_bytes);
-	if (rc || (rc = need_resident(ctx, "bmh_sam_text_device", bns, nullptr)) || (rc = need_refnames(ctx, "bmh_sam_text_device", bns))) return rc;
-	if (n == 0) {
-		char *p = (char *)malloc(1);
-		if (!p) return BMH_E_NOMEM;
-		*text = p, text_off[0] = 0;
-		return BMH_OK;
-	}
+	if (rc || (rc = need_resident(ctx, who, bns, nullptr)) || (rc = need_refnames(ctx, who, bns))) return rc;
+	if (n == 0) return empty_text(text, text_off);
 	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
 	const size_t nr = (size_t)n, total = (size_t)roff[n], wc = (size_t)first[n], l_rg = rg_id ? strlen(rg_id) : 0;
 	if (l_rg > 0x7fffffffu) return BMH_E_ARG;
-	// the device block: everything that goes up, in one piece; then what the kernels make
-	Block blk;
-	const size_t o_roff = blk.take((nr + 1) * 8), o_first = blk.take((nr + 1) * 8), o_poff = blk.take((nr + 1) * 8), o_hdr = blk.take(sizeof(SamtextHdr)), o_rg = blk.take(l_rg);
-	const size_t o_nw = blk.take(nr * 4), o_wk = blk.take(total * 4), o_mq = blk.take(total * 4), o_pd = blk.take(pe ? (nr >> 1) * sizeof(bmh_pairdec_t) : 0);
-	const size_t o_reg = blk.take(total * sizeof(bmh_alnreg_t)), o_wr = blk.take(wc * sizeof(bmh_wanted_res_t)), o_cig = blk.take(cig_words * 4), o_md = blk.take(md_bytes);
-	const size_t o_pool = blk.at;
 	SamtextPool P;
 	if ((rc = P.plan(n, seqs))) return rc;
-	const std::vector<uint64_t> &poff = P.poff;
-	const size_t pool_bytes = (size_t)poff[nr];
-	blk.take(pool_bytes);
-	const size_t b_up = blk.at;
-	const size_t o_alns = blk.take(wc * sizeof(bmh_st_aln_t)), o_plan = blk.take(nr * sizeof(bmh_st_plan_t)), o_size = blk.take(nr * 8), o_toff = blk.take((nr + 1) * 8);
-	const size_t o_stat = blk.take(sizeof(SamtextStatus)), o_end = blk.at;
-	uint8_t *up = (uint8_t *)calloc(b_up, 1);
-	int64_t *toff = (int64_t *)malloc((nr + 1) * 8);
-	char *out = nullptr;
-	struct Free {
-		void *a, *b;
-		char **c;
-		~Free() { free(a), free(b), free(*c); }
-	} guard{up, toff, &out};
-	if (!up || !toff) {
-		ctx->last_error = "bmh_sam_text_device: out of host memory";
+	// the device block: everything that goes up, in one piece; then what the kernels make
+	const SamtextBlock L = samtext_block(false, nr, total, wc, l_rg, (size_t)P.poff[nr], pe, cig_words, md_bytes);
+	HostBuf up(L.up, true);
+	SamtextOut O;
+	O.toff = (int64_t *)malloc((nr + 1) * 8);
+	if (!up.p || !O.toff) {
+		ctx->last_error = std::string(who) + ": out of host memory";
 		return BMH_E_NOMEM;
 	}
-	memcpy(up + o_roff, roff, (nr + 1) * 8), memcpy(up + o_first, first.data(), (nr + 1) * 8), memcpy(up + o_poff, poff.data(), (nr + 1) * 8);
-	SamtextHdr *hdr = (SamtextHdr *)(up + o_hdr);
-	hdr->opt_flag = o->flag, hdr->pe = pe, hdr->l_rg = (int32_t)l_rg;
-	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
-	if (l_rg) memcpy(up + o_rg, rg_id, l_rg);
-	memcpy(up + o_nw, n_want, nr * 4), memcpy(up + o_mq, reg_mapq, total * 4);
-	if (pe) memcpy(up + o_pd, pd, (nr >> 1) * sizeof(bmh_pairdec_t));
-	if (wc) memcpy(up + o_wr, results, wc * sizeof(bmh_wanted_res_t));
-	if (cig_words) memcpy(up + o_cig, cigar_pool, cig_words * 4);
-	if (md_bytes) memcpy(up + o_md, md_pool, md_bytes);
-	for (int i = 0; i < n; ++i) {
-		if (n_want[i]) memcpy(up + o_wk + (size_t)roff[i] * 4, want_k + roff[i], (size_t)n_want[i] * 4);
-		if (regs[i].n) memcpy(up + o_reg + (size_t)roff[i] * sizeof(bmh_alnreg_t), regs[i].a, regs[i].n * sizeof(bmh_alnreg_t));
-	}
-	P.fill(n, seqs, up + o_pool);
-	long long total_text = 0;
+	memcpy(up.p + L.roff, roff, (nr + 1) * 8), memcpy(up.p + L.first, first.data(), (nr + 1) * 8);
+	memcpy(up.p + L.nw, n_want, nr * 4), memcpy(up.p + L.mq, reg_mapq, total * 4);
+	if (pe) memcpy(up.p + L.pd, pd, (nr >> 1) * sizeof(bmh_pairdec_t));
+	if (wc) memcpy(up.p + L.wr, results, wc * sizeof(bmh_wanted_res_t));
+	if (cig_words) memcpy(up.p + L.cig, cigar_pool, cig_words * 4);
+	if (md_bytes) memcpy(up.p + L.md, md_pool, md_bytes);
+	slice_copy_flat(n, regs, roff, up.p + L.reg, n_want, want_k, up.p + L.wk);
+	samtext_fill_up(up.p, L, o, pes, rg_id, l_rg, P, n, seqs);
 	GateGuard gate;
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	if (!ctx->h_ststat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_ststat, sizeof(SamtextStatus), hipHostMallocDefault));
-	const SamtextStatus *hs = (const SamtextStatus *)ctx->h_ststat;
 	Stager st(ctx);
-	st.sx = true;
+	st.cnt = {&ctx->stx.h2d_bytes, &ctx->stx.d2h_bytes, &ctx->stx.waits};
 	rc = [&]() -> int {
 		int e;
-		if ((e = ensure(ctx, ctx->d_samtext, o_end)) || (e = st.stage(b_up + 256, 0))) return e;
+		if ((e = ensure(ctx, ctx->d_samtext, L.end)) || (e = st.stage(L.up + 256, 0))) return e;
 		uint8_t *d = (uint8_t *)ctx->d_samtext.p;
-		BMH_HIP(ctx, hipMemsetAsync(d + o_stat, 0, sizeof(SamtextStatus), ctx->stream));
-		if ((e = st.h2d(d, up, b_up))) return e;
-		SamtextArgs A{};
-		A.roff = (const int64_t *)(d + o_roff), A.first = (const int64_t *)(d + o_first), A.poff = (const unsigned long long *)(d + o_poff);
-		A.hdr = (const SamtextHdr *)(d + o_hdr), A.rg = (const char *)(d + o_rg);
-		A.n_want = (const int32_t *)(d + o_nw), A.want_k = (const int32_t *)(d + o_wk), A.reg_mapq = (const int32_t *)(d + o_mq);
-		A.pd = (const bmh_pairdec_t *)(d + o_pd), A.reg = (const bmh_alnreg_t *)(d + o_reg), A.wr = (const bmh_wanted_res_t *)(d + o_wr);
-		A.cig = (const uint32_t *)(d + o_cig), A.md = (const char *)(d + o_md), A.rpool = d + o_pool;
-		A.total = total, A.n_w = wc, A.cig_words = cig_words, A.md_bytes = md_bytes, A.rpool_bytes = pool_bytes;
-		A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.name_off = (const uint64_t *)ctx->d_refnames.p;
-		A.names = (const char *)ctx->d_refnames.p + ((size_t)ctx->refnames_n + 1) * 8;
-		A.n_seqs = ctx->refidx_n, A.n = n, A.pe = pe, A.l_pac = bns->l_pac;
-		A.alns = (bmh_st_aln_t *)(d + o_alns), A.plan = (bmh_st_plan_t *)(d + o_plan), A.size = (unsigned long long *)(d + o_size);
-		A.toff = (unsigned long long *)(d + o_toff), A.status = (SamtextStatus *)(d + o_stat), A.text = nullptr, A.text_cap = 0, A.err = ctx->d_err;
-		if ((e = launch_samtext_size(ctx, A))) return e;
-		// the one look between the launches: the text's size and whether a unit was refused
-		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_ststat, d + o_stat, sizeof(SamtextStatus), hipMemcpyDeviceToHost, ctx->stream));
-		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-		++ctx->stx.waits, ctx->stx.d2h_bytes += (int64_t)sizeof(SamtextStatus);
-		if (hs->err) {
-			ctx->last_error = "bmh_sam_text_device: a record lies outside its read, its vector, the pools or the reference";
-			return hs->err;
-		}
-		total_text = hs->total;
-		if (total_text < 0 || total_text > ((long long)1 << 40)) { // cannot happen
-			ctx->last_error = "bmh_sam_text_device: the device's sizes are inconsistent";
-			return BMH_E_ARG;
-		}
-		if (!(out = (char *)malloc((size_t)total_text + 1))) return BMH_E_NOMEM;
-		if ((e = ensure(ctx, ctx->d_sam_out, (size_t)total_text + 64)) || (e = st.stage(b_up + 256, (nr + 1) * 8 + (size_t)total_text + 256))) return e;
-		A.text = (char *)ctx->d_sam_out.p, A.text_cap = (unsigned long long)total_text;
-		if ((e = launch_samtext_emit(ctx, A))) return e;
-		if ((e = st.d2h(toff, d + o_toff, (nr + 1) * 8))) return e;
-		return total_text ? st.d2h(out, ctx->d_sam_out.p, (size_t)total_text) : BMH_OK;
+		BMH_HIP(ctx, hipMemsetAsync(d + L.stat, 0, L.stat_bytes, ctx->stream));
+		if ((e = st.h2d(d, up.p, L.up))) return e;
+		const SamtextArgs A = samtext_args(ctx, d, L, total, wc, cig_words, md_bytes, n, pe, bns->l_pac);
+		if ((e = samtext_size_look(ctx, who, st, A, ctx->h_ststat, L.stat_bytes))) return e;
+		return samtext_emit_down(ctx, who, st, A, ctx->h_ststat, L.up + 256, O);
 	}();
-	if ((rc = st.end(rc))) return rc;
-	if (toff[0] != 0 || toff[n] != total_text) { // cannot happen
-		ctx->last_error = "bmh_sam_text_device: the device's offsets are inconsistent";
-		return BMH_E_ARG;
-	}
-	// all or nothing: the caller's outputs only now
-	memcpy(text_off, toff, (nr + 1) * 8);
-	*text = out, out = nullptr;
-	ctx->stx.reads = n, ctx->stx.lines = lines, ctx->stx.text_bytes = total_text;
-	if (ctx->timing) {
-		BMH_HIP(ctx, hipEventElapsedTime(&ctx->stx.size_ms, ctx->ev_samtext[0], ctx->ev_samtext[1]));
-		BMH_HIP(ctx, hipEventElapsedTime(&ctx->stx.emit_ms, ctx->ev_samtext[2], ctx->ev_samtext[3]));
-	}
-	return BMH_OK;
+	if ((rc = st.end(rc)) || (rc = samtext_commit(ctx, who, n, O, text, text_off))) return rc;
+	ctx->stx.reads = n, ctx->stx.lines = lines, ctx->stx.text_bytes = O.total;
+	return samtext_kernel_ms(ctx, &ctx->stx.size_ms, &ctx->stx.emit_ms);
 }
 
 int bmh_ctx_set_samtext_device(bmh_ctx_t *ctx, int on)
@@ -2826,6 +2968,205 @@ static int phase2_text_check(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t 
 	return n > (1 << 28) || (rg_id ? strlen(rg_id) : 0) > 0x7fffffffu ? BMH_E_ARG : BMH_OK;
 }
 
+// One session through to the text as the host holds it: the layouts of its three blocks -- pass A's, with pass B's inputs in it, as
+// bmh_phase2_device uploads it; pass B's arrays, the overflow area of the redone regions behind them; pass C's in its fused form --
+// where the blocks lie on the device, how far the records reach, and every host buffer until the end.
+struct Phase2TextRun {
+	bmh_ctx *ctx;
+	const char *who;
+	const ResidentRegs *res; // not NULL: the regions are on the device, see phase2_text_run
+	Stager st;
+	Phase2Plan P;
+	SamtextBlock LT;
+	size_t up_lo = 0, up_hi = 0; // the part of pass A's upload that is the host's to send
+	HostBuf up, tup;             // pass A's and pass C's uploads
+	uint8_t *d = nullptr, *dw = nullptr, *dt = nullptr; // d_decide, d_wanted, d_samtext; dw moves where the overflow area outgrows its block
+	size_t cig_words = 0, md_bytes = 0; // how far the records reach from the main round's slots
+	WantedDown D;
+	std::vector<Phase2TextHost> list; // the regions the host redoes, by j
+	SamtextOut O;
+	// pass C's arguments over the three blocks as they lie and reach now
+	SamtextArgs args() const { return samtext_args(ctx, dt, LT, P.Z.total, (size_t)D.n_w, cig_words, md_bytes, P.Z.n, P.pe, P.Z.l_pac, d, &P.LA, dw, &P.LB); }
+	// size and scan again, then the look: SamtextStatus and the SamtextFused behind it
+	int look() { return samtext_size_look(ctx, who, st, args(), ctx->h_ptstat, LT.stat_bytes); }
+	const SamtextFused *fused() const { return (const SamtextFused *)((const SamtextStatus *)ctx->h_ptstat + 1); }
+};
+
+// what the session refuses of the slice itself (*early: see phase2_text_run), then its plan, its layouts and its two uploads, filled
+static int phase2_text_plan(Phase2TextRun &S, const bmh_sam_opt_t *o, const bmh_pestat_t *pes, int64_t l_pac, int64_t id0, int n, const bmh_seq_t *seqs,
+                            const bmh_read_t *reads, const bmh_alnreg_v *regs, const char *rg_id, bool *early)
+{
+	bmh_ctx *ctx = S.ctx;
+	const ResidentRegs *res = S.res;
+	const DecideBlock &LA = S.P.LA;
+	const size_t nr = (size_t)n, l_rg = rg_id ? strlen(rg_id) : 0;
+	std::vector<int64_t> roff(res ? 0 : nr + 1, 0);
+	for (size_t i = 0; !res && i < nr; ++i) roff[i + 1] = roff[i] + (int64_t)regs[i].n; // (the offsets are made here)
+	const long long n_regs = res ? res->total : (long long)roff[nr];
+	if (n_regs < 0 || n_regs > (1 << 28)) return BMH_E_ARG;
+	const size_t total = (size_t)n_regs;
+	auto refuse = [&](const std::string &why) {
+		ctx->last_error = why;
+		ctx->pt.fallbacks = 1, *early = true;
+		return BMH_E_RANGE;
+	};
+	// the slots' addresses as the records hold them (every region may be wanted), then the decide tables
+	if (total * BMH_RP_SMALL_CAP > 0xffffffffull || total * kWantMdSlot > 0xffffffffull)
+		return refuse(std::string(S.who) + ": the slice's CIGAR or MD slots do not fit 32-bit addresses");
+	const char *why;
+	int rc = phase2_plan(ctx, o, pes, l_pac, id0, n, reads, regs, res, total, S.P, &why);
+	if (rc) return why ? refuse(why) : rc;
+	SamtextPool pool;
+	if ((rc = pool.plan(n, seqs))) return rc;
+	S.LT = samtext_block(true, nr, total, total, l_rg, (size_t)pool.poff[nr], S.P.pe, 0, 0);
+	// (resident regions: the offsets at the block's head and the regions at the upload's tail are not the host's to send)
+	S.up_lo = res ? LA.hdr : 0, S.up_hi = res ? LA.reg : LA.up();
+	S.up.alloc(S.up_hi), S.tup.alloc(S.LT.up, true), S.O.toff = (int64_t *)malloc((nr + 1) * 8);
+	if (!S.up.p || !S.tup.p || !S.O.toff) {
+		ctx->last_error = std::string(S.who) + ": out of host memory";
+		return BMH_E_NOMEM;
+	}
+	decide_fill(S.up.p, LA, o, pes, S.P.T, n, regs, res ? nullptr : roff.data());
+	wanted_fill(ctx, o->w, n, reads, (uint64_t *)(S.up.p + LA.soff), (WantedHdr *)(S.up.p + LA.whdr), nullptr); // (the bases go up in the per-read pool)
+	samtext_fill_up(S.tup.p, S.LT, o, pes, rg_id, l_rg, pool, n, seqs);
+	S.cig_words = total * BMH_RP_SMALL_CAP, S.md_bytes = total * kWantMdSlot;
+	return BMH_OK;
+}
+
+// one upload, passes A and B, the bind kernel, size and scan: three waits; the list of the regions the host redoes, alone, behind a fourth
+static int phase2_text_enqueue(Phase2TextRun &S)
+{
+	bmh_ctx *ctx = S.ctx;
+	const DecideBlock &LA = S.P.LA;
+	const WantedBlock &LB = S.P.LB;
+	const SamtextBlock &LT = S.LT;
+	int e;
+	// (d_wanted: first[] also where no read has a region)
+	if ((e = ensure(ctx, ctx->d_decide, LA.end)) || (e = ensure(ctx, ctx->d_wanted, LB.end)) || (e = ensure(ctx, ctx->d_samtext, LT.end))) return e;
+	S.d = (uint8_t *)ctx->d_decide.p, S.dw = (uint8_t *)ctx->d_wanted.p, S.dt = (uint8_t *)ctx->d_samtext.p;
+	const SamtextArgs gather = S.args();
+	auto upload = [&S](uint8_t *, uint8_t *) -> int {
+		bmh_ctx *ctx = S.ctx;
+		const size_t total = S.P.Z.total;
+		BMH_HIP(ctx, hipMemsetAsync(S.dt + S.LT.stat, 0, S.LT.stat_bytes, ctx->stream));
+		if (S.res) { // phase 1's offsets and compact records, from its workspace: nothing of it is read after these two copies
+			BMH_HIP(ctx, hipMemcpyAsync(S.d, S.res->roff, ((size_t)S.P.Z.n + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+			if (total) BMH_HIP(ctx, hipMemcpyAsync(S.d + S.P.LA.reg, S.res->reg, total * sizeof(bmh_alnreg_t), hipMemcpyDeviceToDevice, ctx->stream));
+		}
+		const int e = S.st.h2d(S.d + S.up_lo, S.up.p + S.up_lo, S.up_hi - S.up_lo);
+		return e ? e : S.st.h2d(S.dt, S.tup.p, S.LT.up);
+	};
+	if ((e = phase2_enqueue_ab(ctx, S.who, S.st, S.P, S.up_hi - S.up_lo + LT.up + 512, 0, upload, &gather, S.D))) return e;
+	if (S.P.Z.wc) { // what joins pass B's arrays to pass C's input: the slots' addresses into the records, the host's regions into the list
+		Phase2TextBindArgs B{};
+		B.status = (const WantedStatus *)(S.dw + LB.stat), B.wres = (bmh_wanted_res_t *)(S.dw + LB.wres), B.rec = (const WantRec *)(S.dw + LB.rec);
+		B.roff = (const unsigned long long *)S.d, B.reg = (const bmh_alnreg_t *)(S.d + LA.reg), B.total = S.P.Z.total, B.n = S.P.Z.n;
+		B.cig_cap = BMH_RP_SMALL_CAP, B.md_cap = kWantMdSlot, B.w_cap = S.P.Z.wc;
+		B.list = (Phase2TextHost *)(S.dt + LT.list), B.fused = (SamtextFused *)(S.dt + LT.stat + sizeof(SamtextStatus));
+		B.status_out = (SamtextStatus *)(S.dt + LT.stat), B.err = ctx->d_err;
+		if ((e = launch_phase2_text_bind(ctx, B, S.D.n_w))) return e;
+	} else
+		BMH_HIP(ctx, hipMemsetAsync(S.dw + LB.first, 0, ((size_t)S.P.Z.n + 1) * 8, ctx->stream));
+	if ((e = S.look())) return e;
+	const int32_t n_host = S.fused()->n_host;
+	if (n_host == 0) return BMH_OK;
+	if (n_host < 0 || (int64_t)n_host > S.D.n_w) { // cannot happen
+		ctx->last_error = std::string(S.who) + ": the device's counts are inconsistent";
+		return BMH_E_ARG;
+	}
+	S.list.resize((size_t)n_host);
+	BMH_HIP(ctx, hipMemcpyAsync(S.list.data(), S.dt + LT.list, S.list.size() * sizeof(Phase2TextHost), hipMemcpyDeviceToHost, ctx->stream));
+	BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
+	S.st.waited(S.list.size() * sizeof(Phase2TextHost));
+	return BMH_OK;
+}
+
+// The overflow area behind pass B's block as it goes up at LB.end: the redone regions' records, their places in want order, their
+// CIGAR words and MD bytes.  rec, at, end: where the sections lie in the block; cig_words, md_bytes: how far the records reach with it
+struct Phase2TextOverflow {
+	std::vector<uint8_t> ov;
+	size_t rec, at, end, cig_words, md_bytes;
+};
+// ... packed from what the host's redo made of list[], the records' offsets counted from the main round's slots, as every record's
+static int phase2_text_overflow(bmh_ctx *ctx, const char *who, const WantedBlock &LB, const std::vector<Phase2TextHost> &list, const RedoOut &H, Phase2TextOverflow &V)
+{
+	const size_t m = list.size();
+	size_t cw = 0, mb = 0;
+	for (const bmh_wanted_res_t &x : H.hw) cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
+	Block ob;
+	ob.at = LB.end;
+	V.rec = ob.take(m * sizeof(bmh_wanted_res_t)), V.at = ob.take(m * 8);
+	const size_t o_cig = ob.take(cw * 4), o_md = ob.take(mb), cig0 = (o_cig - LB.cig1) / 4, md0 = o_md - LB.md1;
+	V.end = ob.at;
+	if (cig0 + cw > 0xffffffffull || md0 + mb > 0xffffffffull) {
+		ctx->last_error = std::string(who) + ": the redone regions' CIGAR or MD do not fit 32-bit addresses";
+		return BMH_E_RANGE;
+	}
+	V.ov.assign(V.end - LB.end, 0);
+	bmh_wanted_res_t *orec = (bmh_wanted_res_t *)(V.ov.data() + (V.rec - LB.end));
+	int64_t *oat = (int64_t *)(V.ov.data() + (V.at - LB.end));
+	uint32_t *ocig = (uint32_t *)(V.ov.data() + (o_cig - LB.end));
+	char *omd = (char *)(V.ov.data() + (o_md - LB.end));
+	cw = mb = 0;
+	for (size_t t = 0; t < m; ++t) {
+		bmh_wanted_res_t x = H.hw[t];
+		memcpy(ocig + cw, H.cig + x.cigar_off, 4 * (size_t)x.n_cigar), memcpy(omd + mb, H.md + x.md_off, x.md_len);
+		x.cigar_off = (uint32_t)(cig0 + cw), x.md_off = (uint32_t)(md0 + mb), x.flags |= list[t].flags | BMH_WANTED_HOST;
+		cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
+		orec[t] = x, oat[t] = list[t].j;
+	}
+	V.cig_words = cig0 + cw, V.md_bytes = md0 + mb;
+	return BMH_OK;
+}
+
+// The regions whose alignments outgrew their slots: redone by wanted_redo_host from the sorted region with the coordinates as cut, the
+// device gate left around it; their records, CIGAR words and MD bytes go into the overflow area behind pass B's block, the records
+// are patched where they lie, and size and scan run again: two more waits, a third where the block had to move
+static int phase2_text_redo(Phase2TextRun &S, const bmh_refidx_t *bns, const uint8_t *pac, int w, const bmh_read_t *reads, std::optional<GateGuard> &gate)
+{
+	bmh_ctx *ctx = S.ctx;
+	const WantedBlock &LB = S.P.LB;
+	const size_t m = S.list.size();
+	int e;
+	std::sort(S.list.begin(), S.list.end(), [](const Phase2TextHost &x, const Phase2TextHost &y) { return x.j < y.j; });
+	std::vector<RedoRegion> rr(m);
+	for (size_t t = 0; t < m; ++t) {
+		const Phase2TextHost &x = S.list[t];
+		if (x.j < 0 || x.j >= S.D.n_w || x.read < 0 || x.read >= S.P.Z.n || (t && x.j == S.list[t - 1].j)) { // cannot happen
+			ctx->last_error = std::string(S.who) + ": the device's list is inconsistent";
+			return BMH_E_ARG;
+		}
+		rr[t] = RedoRegion{x.read, x.reg};
+		rr[t].reg.rb = x.rb, rr[t].reg.re = x.re, rr[t].reg.qb = x.qb, rr[t].reg.qe = x.qe;
+	}
+	RedoOut H;
+	gate.reset();
+	e = wanted_redo_host(ctx, bns, pac, w, reads, rr, H);
+	gate.emplace();
+	if (e) return e;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	Phase2TextOverflow V;
+	if ((e = phase2_text_overflow(ctx, S.who, LB, S.list, H, V))) return e;
+	bool moved;
+	if ((e = ensure_keep(ctx, ctx->d_wanted, V.end, LB.end, &moved))) return e;
+	if (moved) S.st.waited(0); // (the seventh wait: the block's copy had to arrive before the old one went)
+	S.dw = (uint8_t *)ctx->d_wanted.p;
+	S.cig_words = V.cig_words, S.md_bytes = V.md_bytes;
+	S.st.up_used = 0; // (everything staged so far has arrived; the redo had the staging buffers for itself)
+	if ((e = S.st.stage(V.ov.size() + 256, 0))) return e;
+	BMH_HIP(ctx, hipMemsetAsync(S.dt + S.LT.stat, 0, S.LT.stat_bytes, ctx->stream));
+	if ((e = S.st.h2d(S.dw + LB.end, V.ov.data(), V.ov.size()))) return e;
+	if ((e = launch_phase2_text_patch(ctx, (bmh_wanted_res_t *)(S.dw + LB.wres), (const bmh_wanted_res_t *)(S.dw + V.rec), (const int64_t *)(S.dw + V.at),
+	                                  (int64_t)m, S.D.n_w, (SamtextStatus *)(S.dt + S.LT.stat), ctx->d_err)))
+		return e;
+	if ((e = S.look())) return e;
+	if (S.fused()->n_host != 0) { // cannot happen
+		ctx->last_error = std::string(S.who) + ": the device's counts are inconsistent";
+		return BMH_E_ARG;
+	}
+	return BMH_OK;
+}
+
 // The session.  The arguments are checked here; *early: the BMH_E_RANGE is a refusal before any upload (the decide tables, or slot
 // addresses past 32 bits), which bmh_sam_batch answers with its other routes.  Nothing of the caller's is written before the end.
 // The regions come from the caller's vectors, or -- res, regs being NULL -- from where phase 1 left them on the device with what
@@ -2840,300 +3181,33 @@ static int phase2_text_run(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t *o
 	std::vector<bmh_read_t> reads;
 	int rc = phase2_text_check(ctx, who, o, bns, pac, pes, n, seqs, regs, res != nullptr, rg_id, text, text_off, reads);
 	if (rc) return rc;
-	const size_t nr = (size_t)n;
-	std::vector<int64_t> roff(res ? 0 : nr + 1, 0);
-	for (size_t i = 0; !res && i < nr; ++i) roff[i + 1] = roff[i] + (int64_t)regs[i].n; // (the offsets are made here)
-	if (n == 0) {
-		char *p = (char *)malloc(1);
-		if (!p) return BMH_E_NOMEM;
-		*text = p, text_off[0] = 0;
-		return BMH_OK;
-	}
-	const size_t l_rg = rg_id ? strlen(rg_id) : 0;
-	const long long n_regs = res ? res->total : (long long)roff[nr];
-	if (n_regs < 0 || n_regs > (1 << 28)) return BMH_E_ARG;
-	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
-	const size_t total = (size_t)n_regs, wc = total; // wc: the capacity of everything per wanted region, which bounds their number
-	// before anything is uploaded: the slots' addresses as the records hold them, and the decide tables
-	if (wc * BMH_RP_SMALL_CAP > 0xffffffffull || wc * kWantMdSlot > 0xffffffffull) {
-		ctx->last_error = std::string(who) + ": the slice's CIGAR or MD slots do not fit 32-bit addresses";
-		ctx->pt.fallbacks = 1, *early = true;
-		return BMH_E_RANGE;
-	}
-	DecideTables T;
-	const char *why = nullptr;
-	size_t reads_bytes = 0, opool_cap = 0;
-	if (res) {
-		const bmh_ho_plan_t plan{res->kmax, res->opool_cap, res->total, res->neg ? 1 : 0, 0};
-		rc = decide_tables_from_plan(o, pes, plan, 0, &T.kmax, &T.n_term, T.term_off, &why);
-		opool_cap = (size_t)res->opool_cap;
-	} else
-		rc = decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, &why, &opool_cap);
-	if (rc) {
-		ctx->last_error = why;
-		ctx->pt.fallbacks = 1, *early = true;
-		return BMH_E_RANGE;
-	}
-	if ((rc = decide_host_log(ctx, T.kmax, &T.want_log))) return rc;
-	for (size_t i = 0; i < nr; ++i) reads_bytes += (size_t)reads[i].l_seq;
-	SamtextPool P;
-	if ((rc = P.plan(n, seqs))) return rc;
-	const size_t pool_bytes = (size_t)P.poff[nr];
-	// Three blocks.  Pass A's, with pass B's inputs in it, as bmh_phase2_device uploads it; pass B's arrays, the overflow area of the
-	// redone regions behind them; pass C's: [SamtextHdr | rg_id | poff | the per-read pool] up, then the records, plans, sizes, offsets,
-	// the status with its SamtextFused, and the list of the host's regions
-	const DecideBlock LA = decide_block(nr, total, (size_t)T.n_term, pe, true);
-	Block b;
-	const WantedBlock LB = wanted_block(b, nr, wc);
-	Block tb;
-	const size_t o_hdr = tb.take(sizeof(SamtextHdr)), o_rg = tb.take(l_rg), o_poff = tb.take((nr + 1) * 8), o_pool = tb.take(pool_bytes), t_up = tb.at;
-	const size_t o_alns = tb.take(wc * sizeof(bmh_st_aln_t)), o_plan = tb.take(nr * sizeof(bmh_st_plan_t)), o_size = tb.take(nr * 8), o_toff = tb.take((nr + 1) * 8);
-	const size_t o_stat = tb.take(sizeof(SamtextStatus) + sizeof(SamtextFused)), o_list = tb.take(wc * sizeof(Phase2TextHost)), t_end = tb.at;
-	// (resident regions: the offsets at the block's head and the regions at the upload's tail are not the host's to send)
-	const size_t up_lo = res ? LA.hdr : 0, up_hi = res ? LA.reg : LA.up();
-	HostBuf up(up_hi);
-	uint8_t *tup = (uint8_t *)calloc(t_up, 1);
-	int64_t *toff = (int64_t *)malloc((nr + 1) * 8);
-	char *out = nullptr;
-	struct Free {
-		void *a, *b;
-		char **c;
-		~Free() { free(a), free(b), free(*c); }
-	} guard{tup, toff, &out};
-	if (!up.p || !tup || !toff) {
-		ctx->last_error = std::string(who) + ": out of host memory";
-		return BMH_E_NOMEM;
-	}
-	decide_fill(up.p, LA, o, pes, T, n, regs, res ? nullptr : roff.data());
-	wanted_fill(ctx, o->w, n, reads.data(), (uint64_t *)(up.p + LA.soff), (WantedHdr *)(up.p + LA.whdr), nullptr); // (the bases go up in the per-read pool)
-	SamtextHdr *hdr = (SamtextHdr *)(tup + o_hdr);
-	hdr->opt_flag = o->flag, hdr->pe = pe, hdr->l_rg = (int32_t)l_rg;
-	if (pe) memcpy(hdr->pes, pes, sizeof(hdr->pes));
-	if (l_rg) memcpy(tup + o_rg, rg_id, l_rg);
-	memcpy(tup + o_poff, P.poff.data(), (nr + 1) * 8);
-	P.fill(n, seqs, tup + o_pool);
-
-	WantedDown D;
-	D.stay = true;
-	std::vector<Phase2TextHost> list; // the regions the host redoes, by j
-	size_t cig_words = wc * BMH_RP_SMALL_CAP, md_bytes = wc * kWantMdSlot; // how far the records reach from the main round's slots
-	long long total_text = 0, lines = 0;
-	uint8_t *d = nullptr, *dw = nullptr, *dt = nullptr;
+	if (n == 0) return empty_text(text, text_off);
+	Phase2TextRun S{ctx, who, res, Stager(ctx)};
+	S.st.cnt = {&ctx->pt.h2d_bytes, &ctx->pt.d2h_bytes, &ctx->pt.waits}, S.D.stay = true;
+	if ((rc = phase2_text_plan(S, o, pes, bns->l_pac, id0, n, seqs, reads.data(), regs, rg_id, early))) return rc;
 	std::optional<GateGuard> gate; // (left around the host's redo, which enters it again through the host form)
 	gate.emplace();
 	BMH_HIP(ctx, hipSetDevice(ctx->device));
 	if (!ctx->h_ptstat) BMH_HIP(ctx, hipHostMalloc(&ctx->h_ptstat, sizeof(SamtextStatus) + sizeof(SamtextFused), hipHostMallocDefault));
-	const SamtextStatus *hs = (const SamtextStatus *)ctx->h_ptstat;
-	const SamtextFused *hf = (const SamtextFused *)(hs + 1);
-	Stager st(ctx);
-	st.pt = true;
-	// pass C's arguments over the three blocks: the want list, mapQ, verdicts and sorted regions where decide_kernel left them, first[]
-	// and the records where pass B's kernels left them, CIGAR and MD in the main round's slots (and the overflow area behind the block)
-	auto text_args = [&]() {
-		SamtextArgs A{};
-		A.roff = (const int64_t *)d, A.first = (const int64_t *)(dw + LB.first), A.poff = (const unsigned long long *)(dt + o_poff);
-		A.hdr = (const SamtextHdr *)(dt + o_hdr), A.rg = (const char *)(dt + o_rg);
-		A.n_want = (const int32_t *)(d + LA.nw), A.want_k = (const int32_t *)(d + LA.wk), A.reg_mapq = (const int32_t *)(d + LA.mq);
-		A.pd = (const bmh_pairdec_t *)(d + LA.pd), A.reg = (const bmh_alnreg_t *)(d + LA.reg), A.wr = (const bmh_wanted_res_t *)(dw + LB.wres);
-		A.cig = (const uint32_t *)(dw + LB.cig1), A.md = (const char *)(dw + LB.md1), A.rpool = dt + o_pool;
-		A.total = total, A.n_w = (unsigned long long)D.n_w, A.cig_words = cig_words, A.md_bytes = md_bytes, A.rpool_bytes = pool_bytes;
-		A.ref = (const bmh_refspan_t *)ctx->d_refidx.p, A.name_off = (const uint64_t *)ctx->d_refnames.p;
-		A.names = (const char *)ctx->d_refnames.p + ((size_t)ctx->refnames_n + 1) * 8;
-		A.n_seqs = ctx->refidx_n, A.n = n, A.pe = pe, A.l_pac = bns->l_pac;
-		A.alns = (bmh_st_aln_t *)(dt + o_alns), A.plan = (bmh_st_plan_t *)(dt + o_plan), A.size = (unsigned long long *)(dt + o_size);
-		A.toff = (unsigned long long *)(dt + o_toff), A.status = (SamtextStatus *)(dt + o_stat), A.text = nullptr, A.text_cap = 0, A.err = ctx->d_err;
-		A.fused = (SamtextFused *)(dt + o_stat + sizeof(SamtextStatus));
-		return A;
-	};
-	// size and scan, then the one look behind them: text total, error word, host-region count, lines
-	auto size_and_look = [&]() -> int {
-		int e;
-		if ((e = launch_samtext_size(ctx, text_args()))) return e;
-		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_ptstat, dt + o_stat, sizeof(SamtextStatus) + sizeof(SamtextFused), hipMemcpyDeviceToHost, ctx->stream));
-		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-		++ctx->pt.waits, ctx->pt.d2h_bytes += (int64_t)(sizeof(SamtextStatus) + sizeof(SamtextFused));
-		if (hs->err) {
-			ctx->last_error = std::string(who) + ": a record lies outside its read, its vector, the pools or the reference";
-			return hs->err;
-		}
-		return BMH_OK;
-	};
-
-	// ---- one upload, passes A and B, the bind kernel, size and scan: three waits
-	rc = [&]() -> int {
-		int e;
-		size_t rpool_off;
-		if ((e = ensure(ctx, ctx->d_decide, LA.end)) || (e = wanted_reserve(ctx, wc, opool_cap, reads_bytes, LB.end, &rpool_off))) return e;
-		if ((e = ensure(ctx, ctx->d_wanted, LB.end)) || (e = ensure(ctx, ctx->d_samtext, t_end))) return e; // (d_wanted: first[] also where no read has a region)
-		if ((e = decide_stage_log(ctx, st, T.want_log, up_hi - up_lo + t_up + 512, 0))) return e;
-		d = (uint8_t *)ctx->d_decide.p, dw = (uint8_t *)ctx->d_wanted.p, dt = (uint8_t *)ctx->d_samtext.p;
-		BMH_HIP(ctx, hipMemsetAsync(dt + o_stat, 0, sizeof(SamtextStatus) + sizeof(SamtextFused), ctx->stream));
-		if (res) { // phase 1's offsets and compact records, from its workspace: nothing of it is read after these two copies
-			BMH_HIP(ctx, hipMemcpyAsync(d, res->roff, (nr + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-			if (total) BMH_HIP(ctx, hipMemcpyAsync(d + LA.reg, res->reg, total * sizeof(bmh_alnreg_t), hipMemcpyDeviceToDevice, ctx->stream));
-		}
-		if ((e = st.h2d(d + up_lo, up.p + up_lo, up_hi - up_lo)) || (e = st.h2d(dt, tup, t_up))) return e;
-		BMH_HIP(ctx, hipMemsetAsync(d + LA.nw, 0, nr * 4, ctx->stream)); // a unit decide_kernel refuses wants nothing
-		const DecideArgs DA = decide_args(ctx, d, LA, T, total, bns->l_pac, id0, n, pe);
-		if ((e = launch_decide(ctx, DA))) return e;
-		if (wc) {
-			// pass B's reads pool, made where it is read: the bases of the per-read pool at seq_off[], 16 zero bytes behind them
-			uint8_t *rpool = (uint8_t *)ctx->d_pool.p + rpool_off;
-			BMH_HIP(ctx, hipMemsetAsync(rpool + reads_bytes, 0, 16, ctx->stream));
-			if ((e = launch_reads_gather(ctx, text_args(), (const unsigned long long *)(d + LA.soff), rpool, reads_bytes))) return e;
-			WantedArgs A{};
-			A.roff = DA.roff, A.seq_off = (const unsigned long long *)(d + LA.soff), A.hdr = (const WantedHdr *)(d + LA.whdr);
-			A.n_want = DA.n_want, A.want_k = DA.want_k, A.reg = DA.reg;
-			A.total = total, A.reads_bytes = reads_bytes, A.n = n, A.l_pac = bns->l_pac, A.w_cap = wc, A.opool_cap = opool_cap;
-			if ((e = wanted_session(ctx, who, st, A, dw, LB, rpool_off, 0, (int64_t)wc, D))) return e;
-			Phase2TextBindArgs B{};
-			B.status = (const WantedStatus *)(dw + LB.stat), B.wres = (bmh_wanted_res_t *)(dw + LB.wres), B.rec = (const WantRec *)(dw + LB.rec);
-			B.roff = DA.roff, B.reg = DA.reg, B.total = total, B.n = n, B.cig_cap = BMH_RP_SMALL_CAP, B.md_cap = kWantMdSlot, B.w_cap = wc;
-			B.list = (Phase2TextHost *)(dt + o_list), B.fused = (SamtextFused *)(dt + o_stat + sizeof(SamtextStatus));
-			B.status_out = (SamtextStatus *)(dt + o_stat), B.err = ctx->d_err;
-			if ((e = launch_phase2_text_bind(ctx, B, D.n_w))) return e;
-		} else
-			BMH_HIP(ctx, hipMemsetAsync(dw + LB.first, 0, (nr + 1) * 8, ctx->stream));
-		if ((e = size_and_look())) return e;
-		if (hf->n_host == 0) return BMH_OK;
-		if (hf->n_host < 0 || (int64_t)hf->n_host > D.n_w) { // cannot happen
-			ctx->last_error = std::string(who) + ": the device's counts are inconsistent";
-			return BMH_E_ARG;
-		}
-		// only the list comes down
-		list.resize((size_t)hf->n_host);
-		BMH_HIP(ctx, hipMemcpyAsync(list.data(), dt + o_list, list.size() * sizeof(Phase2TextHost), hipMemcpyDeviceToHost, ctx->stream));
-		BMH_HIP(ctx, stream_wait(ctx, ctx->stream));
-		++ctx->pt.waits, ctx->pt.d2h_bytes += (int64_t)(list.size() * sizeof(Phase2TextHost));
-		return BMH_OK;
-	}();
-
-	// ---- the regions whose alignments outgrew their slots: redone as wanted_tail redoes them, one region per read of a small slice of
-	// its own, from the sorted region with the coordinates as cut; their records, CIGAR words and MD bytes go into the overflow area
-	// behind pass B's block, the records are patched where they lie, and size and scan run again: two more waits
-	const size_t m = list.size();
-	if (!rc && m) {
-		std::sort(list.begin(), list.end(), [](const Phase2TextHost &x, const Phase2TextHost &y) { return x.j < y.j; });
-		std::vector<bmh_wanted_res_t> hw(m);
-		uint32_t *hcig = nullptr;
-		char *hmd = nullptr;
-		struct Free2 {
-			uint32_t *&a;
-			char *&b;
-			~Free2() { free(a), free(b); }
-		} guard2{hcig, hmd};
-		std::vector<bmh_alnreg_t> ra(m);
-		std::vector<bmh_alnreg_v> rv(m);
-		std::vector<bmh_read_t> rd(m);
-		std::vector<int64_t> ro(m + 1);
-		std::vector<int32_t> one(m, 1), zero(m, 0);
-		for (size_t t = 0; t < m && !rc; ++t) {
-			const Phase2TextHost &x = list[t];
-			if (x.j < 0 || x.j >= D.n_w || x.read < 0 || x.read >= n || (t && x.j == list[t - 1].j)) { // cannot happen
-				ctx->last_error = std::string(who) + ": the device's list is inconsistent";
-				rc = BMH_E_ARG;
-				break;
-			}
-			ra[t] = x.reg;
-			ra[t].rb = x.rb, ra[t].re = x.re, ra[t].qb = x.qb, ra[t].qe = x.qe; // (as cut; a region whose fix is redone still has its own)
-			rv[t].n = rv[t].m = 1, rv[t].a = &ra[t], rd[t] = reads[(size_t)x.read], ro[t] = (int64_t)t;
-		}
-		ro[m] = (int64_t)m;
-		if (!rc) {
-			gate.reset();
-			rc = bmh_wanted_host_(ctx, bns, pac, o->w, (int)m, rd.data(), rv.data(), ro.data(), one.data(), zero.data(), (int64_t)m, 1, hw.data(), &hcig, &hmd, nullptr);
-			gate.emplace();
-		}
-		if (!rc) rc = [&]() -> int {
-			int e;
-			BMH_HIP(ctx, hipSetDevice(ctx->device));
-			size_t cw = 0, mb = 0;
-			for (const bmh_wanted_res_t &x : hw) cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
-			Block ob;
-			ob.at = LB.end;
-			const size_t o_rec = ob.take(m * sizeof(bmh_wanted_res_t)), o_at = ob.take(m * 8), o_cig = ob.take(cw * 4), o_md = ob.take(mb), o_end = ob.at;
-			const size_t cig0 = (o_cig - LB.cig1) / 4, md0 = o_md - LB.md1; // from the main round's slots, as every record's offsets
-			if (cig0 + cw > 0xffffffffull || md0 + mb > 0xffffffffull) {
-				ctx->last_error = std::string(who) + ": the redone regions' CIGAR or MD do not fit 32-bit addresses";
-				return BMH_E_RANGE;
-			}
-			std::vector<uint8_t> ov(o_end - LB.end, 0);
-			bmh_wanted_res_t *orec = (bmh_wanted_res_t *)(ov.data() + (o_rec - LB.end));
-			int64_t *oat = (int64_t *)(ov.data() + (o_at - LB.end));
-			uint32_t *ocig = (uint32_t *)(ov.data() + (o_cig - LB.end));
-			char *omd = (char *)(ov.data() + (o_md - LB.end));
-			cw = mb = 0;
-			for (size_t t = 0; t < m; ++t) {
-				bmh_wanted_res_t x = hw[t];
-				memcpy(ocig + cw, hcig + x.cigar_off, 4 * (size_t)x.n_cigar), memcpy(omd + mb, hmd + x.md_off, x.md_len);
-				x.cigar_off = (uint32_t)(cig0 + cw), x.md_off = (uint32_t)(md0 + mb), x.flags |= list[t].flags | BMH_WANTED_HOST;
-				cw += (size_t)x.n_cigar, mb += (size_t)x.md_len;
-				orec[t] = x, oat[t] = list[t].j;
-			}
-			bool moved;
-			if ((e = ensure_keep(ctx, ctx->d_wanted, o_end, LB.end, &moved))) return e;
-			if (moved) ++ctx->pt.waits; // (the seventh wait: the block's copy had to arrive before the old one went)
-			dw = (uint8_t *)ctx->d_wanted.p;
-			cig_words = cig0 + cw, md_bytes = md0 + mb;
-			st.up_used = 0; // (everything staged so far has arrived; the redo had the staging buffers for itself)
-			if ((e = st.stage(ov.size() + 256, 0))) return e;
-			BMH_HIP(ctx, hipMemsetAsync(dt + o_stat, 0, sizeof(SamtextStatus) + sizeof(SamtextFused), ctx->stream));
-			if ((e = st.h2d(dw + LB.end, ov.data(), ov.size()))) return e;
-			if ((e = launch_phase2_text_patch(ctx, (bmh_wanted_res_t *)(dw + LB.wres), (const bmh_wanted_res_t *)(dw + o_rec), (const int64_t *)(dw + o_at),
-			                                  (int64_t)m, D.n_w, (SamtextStatus *)(dt + o_stat), ctx->d_err)))
-				return e;
-			if ((e = size_and_look())) return e;
-			if (hf->n_host != 0) { // cannot happen
-				ctx->last_error = std::string(who) + ": the device's counts are inconsistent";
-				return BMH_E_ARG;
-			}
-			return BMH_OK;
-		}();
-	}
-
-	// ---- the text: the buffer sized from the status, the emit kernel, text_off and the text down
-	if (!rc) rc = [&]() -> int {
-		int e;
-		total_text = hs->total, lines = hf->lines;
-		if (total_text < 0 || total_text > ((long long)1 << 40) || lines < 0) { // cannot happen
-			ctx->last_error = std::string(who) + ": the device's sizes are inconsistent";
-			return BMH_E_ARG;
-		}
-		if (!(out = (char *)malloc((size_t)total_text + 1))) return BMH_E_NOMEM;
-		if ((e = ensure(ctx, ctx->d_sam_out, (size_t)total_text + 64)) || (e = st.stage(0, (nr + 1) * 8 + (size_t)total_text + 256))) return e;
-		SamtextArgs A = text_args();
-		A.text = (char *)ctx->d_sam_out.p, A.text_cap = (unsigned long long)total_text;
-		if ((e = launch_samtext_emit(ctx, A))) return e;
-		if ((e = st.d2h(toff, dt + o_toff, (nr + 1) * 8))) return e;
-		return total_text ? st.d2h(out, ctx->d_sam_out.p, (size_t)total_text) : BMH_OK;
-	}();
-	rc = st.end(rc);
+	rc = phase2_text_enqueue(S);
+	if (!rc && !S.list.empty()) rc = phase2_text_redo(S, bns, pac, o->w, reads.data(), gate);
+	if (!rc) rc = samtext_emit_down(ctx, who, S.st, S.args(), ctx->h_ptstat, 0, S.O);
+	rc = S.st.end(rc);
 	if (rc == BMH_E_CIGAR_CAP) rc = BMH_OK; // a task that outgrew its slots is reported per region, and has been redone
 	if (rc) return rc;
-	ctx->logk_n = T.want_log;
-	if (toff[0] != 0 || toff[n] != total_text) { // cannot happen
-		ctx->last_error = std::string(who) + ": the device's offsets are inconsistent";
-		return BMH_E_ARG;
-	}
-	// all or nothing: the caller's outputs only now
-	memcpy(text_off, toff, (nr + 1) * 8);
-	*text = out, out = nullptr;
+	ctx->logk_n = S.P.T.want_log;
+	if ((rc = samtext_commit(ctx, who, n, S.O, text, text_off))) return rc;
 	bmh_phase2_text_stats_t &s = ctx->pt;
-	s.units = pe ? n >> 1 : n, s.wanted = D.n_w, s.fixed = D.n_fix, s.redone = (int64_t)m;
-	s.reads = n, s.lines = lines, s.text_bytes = total_text, s.sessions = 1;
+	s.units = S.P.pe ? n >> 1 : n, s.wanted = S.D.n_w, s.fixed = S.D.n_fix, s.redone = (int64_t)S.list.size();
+	s.reads = n, s.lines = S.O.lines, s.text_bytes = S.O.total, s.sessions = 1;
 	if (ctx->timing) {
-		float a = 0.f, c = 0.f;
 		BMH_HIP(ctx, hipEventElapsedTime(&s.decide_ms, ctx->ev_decide[0], ctx->ev_decide[1]));
-		if (wc) {
-			BMH_HIP(ctx, hipEventElapsedTime(&a, ctx->ev_wanted[0], ctx->ev_wanted[1]));
-			BMH_HIP(ctx, hipEventElapsedTime(&c, ctx->ev_wanted[2], ctx->ev_wanted[3]));
-			s.wanted_ms = a + c;
+		if (S.P.Z.wc) {
+			if ((rc = wanted_kernel_ms(ctx, &s.wanted_ms))) return rc;
 			BMH_HIP(ctx, hipEventElapsedTime(&s.gather_ms, ctx->ev_gather[0], ctx->ev_gather[1]));
 		}
-		BMH_HIP(ctx, hipEventElapsedTime(&s.size_ms, ctx->ev_samtext[0], ctx->ev_samtext[1]));
-		BMH_HIP(ctx, hipEventElapsedTime(&s.emit_ms, ctx->ev_samtext[2], ctx->ev_samtext[3]));
 	}
-	return BMH_OK;
+	return samtext_kernel_ms(ctx, &s.size_ms, &s.emit_ms);
 }
 
 int bmh_phase2_text_device(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes, int64_t id0, int n,

@@ -90,6 +90,22 @@ def test_sizes(ctx, ref, n_wanted, w):
         ctx.set_params(kswlib.make_params())
 
 
+def test_planning_kernels_time_in_timing_mode(ctx, ref):
+    """the stand-alone call's kernel time: -1 with timing off, positive with it on, -1 again once it is off; records and pools as the host's"""
+    reads, vectors, want = wg.slice_of(np.random.default_rng(65), ref[0], 65)
+    _both(ctx, 100, reads, vectors, want, "timing off")
+    assert ctx.last_wanted_stats() == (65, 0, 0, -1)
+    ctx.set_kernel_timing(True)
+    try:
+        _both(ctx, 100, reads, vectors, want, "timing on")
+        wanted, fixed, redone, ms = ctx.last_wanted_stats()
+        assert (wanted, fixed, redone) == (65, 0, 0) and ms > 0, ms
+    finally:
+        ctx.set_kernel_timing(False)
+    _both(ctx, 100, reads, vectors, want, "timing off again")
+    assert ctx.last_wanted_stats() == (65, 0, 0, -1)
+
+
 def test_no_want_at_all(ctx, ref):
     rng = np.random.default_rng(3)
     reads, vectors, _ = wg.random_slice(rng, ref[0], 20)
