@@ -44,6 +44,13 @@
  *                        once and only SAM text comes down; the few alignments that outgrow the device's slots are redone on the host
  *                        and patched in.  Needs BMH_PAC_RESIDENT not 0; makes the sequence table and the names resident.  A slice the
  *                        fused call refuses as out of range goes the way the switches above say.
+ * A single-end chunk has a route of its own that replaces all of the above:
+ *   BMH_READS_SAM_DEVICE=1  both phases as ONE device session per batch (bmh_reads_sam_device): the reads go up, only SAM text comes
+ *                        down, and the regions never exist on the host.  A chunk has no serial section without insert-size statistics,
+ *                        so there is no barrier between the phases either: one job per batch of `-b` reads, from bases to strings.
+ *                        Needs BMH_PAC_RESIDENT not 0; needs none of the other switches and consults none of them, BMH_REGION_LONG
+ *                        excepted.  A call that refuses a batch ends the run: there is no other route for it.  Paired-end chunks go
+ *                        the way they go without the switch.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -63,6 +70,7 @@
 #include <semaphore.h>
 
 #include "../../include/bwamem_hip.h"
+#include "samcut_core.h"
 #include "tls_ctx.h"
 
 /* At most this many host threads are inside a GPU batch call at a time ($BMH_GPU_CONCURRENCY, default 12): the calls of
@@ -185,13 +193,13 @@ __attribute__((constructor)) static void qa_shim_loaded(void)
 				const char *v = buf[i + 2] ? buf + i + 2 : (i + 3 < n ? buf + i + 3 : "");
 				if (atoi(v) > 0) g_prewarm_n = atoi(v);
 			}
-		{ /* phase 2 runs -t * 3/2 threads; $BMH_P1_THREADS / $BMH_P2_THREADS override the phases' thread counts; $BMH_PREWARM=N: N */
-			const char *v[3] = {getenv("BMH_P1_THREADS"), getenv("BMH_P2_THREADS"), e};
+		{ /* phase 2 runs -t * 3/2 threads; $BMH_P1_THREADS / $BMH_P2_THREADS / $BMH_RS_THREADS override the phases' thread counts; $BMH_PREWARM=N: N */
+			const char *v[4] = {getenv("BMH_P1_THREADS"), getenv("BMH_P2_THREADS"), getenv("BMH_RS_THREADS"), e};
 			int k;
 			g_prewarm_n += g_prewarm_n / 2;
-			for (k = 0; k < 2; ++k)
+			for (k = 0; k < 3; ++k)
 				if (v[k] && atoi(v[k]) > g_prewarm_n) g_prewarm_n = atoi(v[k]);
-			if (v[2] && atoi(v[2]) > 0) g_prewarm_n = atoi(v[2]);
+			if (v[3] && atoi(v[3]) > 0) g_prewarm_n = atoi(v[3]);
 			if (g_prewarm_n > 128) g_prewarm_n = 128;
 		}
 	}
@@ -524,6 +532,28 @@ static int qa_phase2_text_device(void)
 	return on;
 }
 static long long g_phase2_text_cnt[6]; /* units, regions, redone on the host, lines, bytes of text, slices that fell back to the other routes */
+
+/* BMH_READS_SAM_DEVICE=1: a single-end chunk's batches go from bases to SAM text in one device session each (bmh_reads_sam_device:
+ * mem_process_seqs below).  Its phase 1 extends from the resident reference and its phase 2 aligns against it, so BMH_PAC_RESIDENT=0
+ * contradicts it: checked when the library is loaded, like its siblings.  It needs and consults no other switch. */
+__attribute__((constructor)) static void qa_check_reads_sam_device_env(void)
+{
+	const char *e = getenv("BMH_READS_SAM_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_READS_SAM_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+static int qa_reads_sam_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_READS_SAM_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_reads_sam_cnt[6]; /* batches, reads, regions behind the de-duplication, redone on the host, lines, bytes of text */
 
 /* BMH_SAMTEXT_DEVICE=1: phase 2's pass C on the device (bmh_ctx_set_samtext_device on every pooled context phase 2 uses, with the
  * sequence table and the names made resident).  It reads no base of the reference, so it does not need BMH_PAC_RESIDENT. */
@@ -935,6 +965,124 @@ static int qa_threads(const char *var, int dflt)
 	return v > 0 ? v : dflt > 0 ? dflt : 1;
 }
 
+/* the fields of mem_opt_t phase 2 (and mem_pestat's pair walk in phase 1) reads */
+static void qa_sam_opt(const ref_mem_opt_t *opt, bmh_sam_opt_t *so)
+{
+	memset(so, 0, sizeof(*so));
+	so->a = opt->a, so->b = opt->b, so->o_del = opt->o_del, so->e_del = opt->e_del, so->o_ins = opt->o_ins, so->e_ins = opt->e_ins;
+	so->pen_unpaired = opt->pen_unpaired, so->w = opt->w, so->T = opt->T, so->flag = opt->flag, so->min_seed_len = opt->min_seed_len;
+	so->max_ins = opt->max_ins, so->mapQ_coef_fac = opt->mapQ_coef_fac, so->max_matesw = opt->max_matesw, so->mask_level = opt->mask_level;
+	so->mask_level_redun = opt->mask_level_redun, so->mapQ_coef_len = opt->mapQ_coef_len;
+	memcpy(so->mat, opt->mat, 25);
+}
+
+/* the hot-path fields of mem_opt_t */
+static void qa_params(const ref_mem_opt_t *opt, bmh_params_t *p)
+{
+	memset(p, 0, sizeof(*p));
+	p->o_del = opt->o_del, p->e_del = opt->e_del, p->o_ins = opt->o_ins, p->e_ins = opt->e_ins, p->zdrop = opt->zdrop;
+	p->a = opt->a, p->w = opt->w, p->pen_clip5 = opt->pen_clip5, p->pen_clip3 = opt->pen_clip3;
+	memcpy(p->mat, opt->mat, 25);
+}
+
+/* bwamem.c:1313's batch size, evened out over a chunk of n reads run by nt threads: -b 65536 cuts a chunk of 1 066 668 reads into 16
+ * batches and a 17th of 18 092 that one thread runs alone after all others are done; the same reads in 16 batches of 66 667 are not a
+ * read slower per batch.  As many batches as -b asks for, rounded to a multiple of the thread count, at least 4 096 reads each.
+ * BMH_BATCH_EXACT=1 keeps -b to the read. */
+static int qa_even_batch(const ref_mem_opt_t *opt, int n, int nt)
+{
+	int b = opt->batch_size > 0 ? opt->batch_size : 1;
+	if (!getenv("BMH_BATCH_EXACT") && n > 0) {
+		int64_t rounds = ((int64_t)n + (int64_t)b * nt / 2) / ((int64_t)b * nt), nb;
+		if (rounds < 1) rounds = 1;
+		nb = rounds * nt;
+		if ((int64_t)n / nb < 4096) nb = ((int64_t)n + 4095) / 4096;
+		b = (int)(((int64_t)n + nb - 1) / nb);
+	}
+	return b;
+}
+
+/* ---- BMH_READS_SAM_DEVICE=1, a single-end chunk: one job per batch, from the batch's bases to its reads' SAM strings.  Nothing of a
+ * chunk is serial without insert-size statistics, so the jobs share nothing and wait for nothing but the device: no region vector, no
+ * second upload of regions, no barrier between "all of phase 1" and "all of phase 2". */
+typedef struct {
+	const ref_mem_opt_t *opt;
+	const void *bwt;
+	const ref_bntseq_head_t *bns;
+	const uint8_t *pac;
+	int64_t n_processed;
+	int n, batch;
+	ref_bseq1_t *seqs;
+	const bmh_params_t *params;
+	const bmh_sam_opt_t *sopt;
+} qa_reads_sam_job_t;
+
+static void qa_reads_sam_batch(void *data, int k, int tid)
+{
+	const qa_reads_sam_job_t *J = (const qa_reads_sam_job_t *)data;
+	const int64_t lo64 = (int64_t)k * J->batch, hi64 = lo64 + J->batch < J->n ? lo64 + J->batch : J->n;
+	const int lo = (int)lo64, hi = (int)hi64;
+	bmh_smem_opt_t so;
+	bmh_chain_opt_t co;
+	bmh_reads_sam_stats_t rs;
+	bmh_phase2_text_stats_t ps;
+	bmh_ctx_t *ctx;
+	int64_t *text_off;
+	char *text = 0;
+	int b, i, rc;
+	(void)tid;
+	if (hi <= lo) return;
+	for (b = lo; b < hi; ++b) { /* bwamem.c:1093-1094 */
+		ref_bseq1_t *s = &J->seqs[b];
+		for (i = 0; i < s->l_seq; ++i) s->seq[i] = s->seq[i] < 4 ? s->seq[i] : (char)nst_nt4_table[(int)s->seq[i]];
+	}
+	if (!(text_off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)(hi - lo) + 1)))) bmh_tls_die("out of memory for the batch's text offsets", BMH_E_NOMEM);
+	ctx = bmh_pool_get(J->params);
+	/* what the call needs resident (BMH_PAC_RESIDENT=0 was refused when the library was loaded); contexts are pooled, so every job says it */
+	if ((rc = bmh_ctx_set_pac(ctx, J->pac, J->bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
+	qa_seed_setup(ctx, J->opt, (const ref_bwt_t *)J->bwt, &so);
+	qa_chain_opt(J->opt, &co);
+	if ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns)) || (rc = bmh_ctx_set_refnames(ctx, (const bmh_refidx_t *)J->bns)) ||
+	    (rc = bmh_ctx_set_region_long(ctx, qa_region_long())))
+		bmh_tls_die(bmh_last_error(ctx), rc);
+	if ((rc = bmh_reads_sam_device(ctx, &so, &co, J->opt->min_seed_len, J->sopt, (const bmh_refidx_t *)J->bns, J->pac, J->n_processed + lo, hi - lo,
+	                               (bmh_seq_t *)(J->seqs + lo), bwa_rg_id, &text, text_off)))
+		bmh_tls_die(bmh_last_error(ctx), rc); /* no other route for the batch */
+	bmh_last_reads_sam_stats(ctx, &rs);
+	bmh_last_phase2_text_stats(ctx, &ps);
+	bmh_pool_put(ctx);
+	if ((rc = bmh_sam_cut(hi - lo, (bmh_seq_t *)(J->seqs + lo), text, text_off))) bmh_tls_die("the batch's SAM text could not be cut into strings", rc);
+	free(text), free(text_off);
+	{
+		const int64_t got[6] = {1, rs.reads, rs.regions, ps.redone, ps.lines, ps.text_bytes};
+		int c;
+		for (c = 0; c < 6; ++c) __sync_fetch_and_add(&g_reads_sam_cnt[c], (long long)(got[c] > 0 ? got[c] : 0));
+	}
+}
+
+static void qa_reads_sam_chunk(const ref_mem_opt_t *opt, const void *bwt, const ref_bntseq_head_t *bns, const uint8_t *pac, int64_t n_processed, int n,
+                               ref_bseq1_t *seqs)
+{
+	/* A thread inside the call sleeps on several waits per batch, so half again as many threads as -t pay here as they do in phase 2
+	 * (measured at -t 16 on 2.4 M reads of 150 bases, from the second chunk on: 2.39 M reads/s with 16 threads, 2.46 M with 24, 2.20 M
+	 * with 32; the process 4.03, 3.28 and 3.81 s: profiles/reads_sam_shim.md).  The pre-warming makes that many contexts. */
+	const int nt = qa_threads("BMH_RS_THREADS", opt->n_threads + opt->n_threads / 2);
+	const double t0 = realtime();
+	qa_reads_sam_job_t J;
+	bmh_params_t p;
+	bmh_sam_opt_t so;
+	qa_sam_opt(opt, &so);
+	qa_params(opt, &p);
+	J.opt = opt, J.bwt = bwt, J.bns = bns, J.pac = pac, J.n_processed = n_processed, J.n = n, J.seqs = seqs, J.params = &p, J.sopt = &so;
+	J.batch = qa_even_batch(opt, n, nt);
+	kt_for(nt, qa_reads_sam_batch, &J, (int)(((int64_t)n + J.batch - 1) / J.batch));
+	if (getenv("BMH_VERBOSE")) {
+		fprintf(stderr, "[bwamem_hip] single-end reads to SAM text in one session so far: %lld batches, %lld reads, %lld regions, %lld redone on the host, %lld lines, %lld bytes\n",
+		        g_reads_sam_cnt[0], g_reads_sam_cnt[1], g_reads_sam_cnt[2], g_reads_sam_cnt[3], g_reads_sam_cnt[4], g_reads_sam_cnt[5]);
+		fprintf(stderr, "[bwamem_hip] chunk of %d reads: reads to SAM text in one session %.3f s\n", n, realtime() - t0);
+	}
+}
+
 void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntseq_head_t *bns, const uint8_t *pac,
                       int64_t n_processed, int n, ref_bseq1_t *seqs, const bmh_pestat_t *pes0)
 {
@@ -953,14 +1101,16 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	t_[0] = rtime;
 	if (n_processed == 0 && g_t_loaded > 0 && getenv("BMH_VERBOSE"))
 		fprintf(stderr, "[bwamem_hip] the first chunk starts %.3f s after the shim was loaded\n", rtime - g_t_loaded);
+	if (qa_reads_sam_device()) { /* a single-end chunk: bases to SAM strings, one device session per batch; nothing below runs */
+		if (!pe) {
+			qa_reads_sam_chunk(opt, bwt, bns, pac, n_processed, n, seqs);
+			goto processed;
+		}
+		if (getenv("BMH_VERBOSE")) fprintf(stderr, "[bwamem_hip] single-end reads to SAM text in one session: off for this chunk (paired-end reads)\n");
+	}
 	w.opt = opt, w.bwt = bwt, w.bns = bns, w.pac = pac, w.seqs = seqs;
 	w.regs = (bmh_alnreg_v *)malloc((size_t)n * sizeof(bmh_alnreg_v));
-	memset(&so, 0, sizeof(so)); /* the fields of mem_opt_t phase 2 (and mem_pestat's pair walk in phase 1) reads */
-	so.a = opt->a, so.b = opt->b, so.o_del = opt->o_del, so.e_del = opt->e_del, so.o_ins = opt->o_ins, so.e_ins = opt->e_ins;
-	so.pen_unpaired = opt->pen_unpaired, so.w = opt->w, so.T = opt->T, so.flag = opt->flag, so.min_seed_len = opt->min_seed_len;
-	so.max_ins = opt->max_ins, so.mapQ_coef_fac = opt->mapQ_coef_fac, so.max_matesw = opt->max_matesw, so.mask_level = opt->mask_level;
-	so.mask_level_redun = opt->mask_level_redun, so.mapQ_coef_len = opt->mapQ_coef_len;
-	memcpy(so.mat, opt->mat, 25);
+	qa_sam_opt(opt, &so);
 	w.cand = 0, w.sopt = &so;
 	g_pes_removed = 0;
 	if (qa_pestat_device()) { /* the pair walk in phase 1: a paired-end chunk whose statistics are not given, in batches that split no pair */
@@ -969,19 +1119,9 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 		           : odd_exact ? "BMH_BATCH_EXACT=1 with an odd batch size" : opt->max_ins >= (1 << 30) ? "max_ins >= 2^30" : 0;
 		if (!why_host && !(w.cand = (uint32_t *)calloc((size_t)(n >> 1), sizeof(uint32_t)))) bmh_tls_die("out of memory for the insert-size words", BMH_E_NOMEM);
 	}
-	{ /* bwamem.c:1313, with the batch size evened out: -b 65536 cuts a chunk of 1 066 668 reads into 16 batches and a 17th
-	   * of 18 092 that one thread runs alone after all others are done; the same reads in 16 batches of 66 667 are not a
-	   * read slower per batch.  As many batches as -b asks for, rounded to a multiple of the thread count, at least 4 096
-	   * reads each.  BMH_BATCH_EXACT=1 keeps -b to the read. */
+	{ /* bwamem.c:1313, with the batch size evened out (qa_even_batch) */
 		const int nt = qa_threads("BMH_P1_THREADS", opt->n_threads);
-		int b = opt->batch_size > 0 ? opt->batch_size : 1;
-		if (!getenv("BMH_BATCH_EXACT") && n > 0) {
-			int64_t rounds = ((int64_t)n + (int64_t)b * nt / 2) / ((int64_t)b * nt), nb;
-			if (rounds < 1) rounds = 1;
-			nb = rounds * nt;
-			if ((int64_t)n / nb < 4096) nb = ((int64_t)n + 4095) / 4096;
-			b = (int)(((int64_t)n + nb - 1) / nb);
-		}
+		int b = qa_even_batch(opt, n, nt);
 		p1_batch[0] = b;
 		if (w.cand && (b & 1)) ++b; /* no pair straddles two batches; reads are independent, so the regions do not change */
 		p1_batch[1] = b;
@@ -999,10 +1139,7 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	/* reads are base codes by now (bwamem.c:1093-1094) */
 	reads = (bmh_read_t *)malloc(sizeof(bmh_read_t) * (size_t)n);
 	for (i = 0; i < n; ++i) reads[i].l_seq = seqs[i].l_seq, reads[i].seq = (const uint8_t *)seqs[i].seq;
-	memset(&p, 0, sizeof(p));
-	p.o_del = opt->o_del, p.e_del = opt->e_del, p.o_ins = opt->o_ins, p.e_ins = opt->e_ins, p.zdrop = opt->zdrop;
-	p.a = opt->a, p.w = opt->w, p.pen_clip5 = opt->pen_clip5, p.pen_clip3 = opt->pen_clip3;
-	memcpy(p.mat, opt->mat, 25);
+	qa_params(opt, &p);
 	{
 		const char *pr = getenv("BMH_PAC_RESIDENT");
 		J.resident = !(pr && pr[0] == '0');
@@ -1096,6 +1233,7 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 	}
 	free(w.regs);
 	free(w.cand);
+processed:
 	if (bwa_verbose >= 3)
 		fprintf(stderr, "[M::%s] Processed %d reads in %.3f CPU sec, %.3f real sec\n", __func__, n, cputime() - ctime, realtime() - rtime);
 }

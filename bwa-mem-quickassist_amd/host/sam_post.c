@@ -32,6 +32,7 @@
 #include "pestat_core.h"
 #include "postproc_core.h"
 #include "regplan_core.h"
+#include "samcut_core.h"
 #include "samtext_core.h"
 #include "sort_exact.h"
 
@@ -759,17 +760,7 @@ int bmh_sam_batch(bmh_ctx_t *ctx, const bmh_sam_opt_t *o, const bmh_refidx_t *bn
 	 * bmh_ctx_set_samtext_device on bmh_sam_text_device (the same bytes either way); then one string per read */
 	if ((rc = bmh_samtext_routed_(ctx, o, bns, pes, n, seqs, regs, roff, pd, reg_mapq, n_want, want_k, wr, cig, md, rg_id, &text, text_off))) goto done;
 strings:
-	for (i = 0; i < n; ++i) {
-		const size_t len = (size_t)(text_off[i + 1] - text_off[i]);
-		char *s = (char *)malloc(len + 1);
-		if (!s) { /* all or nothing */
-			while (--i >= 0) free(seqs[i].sam), seqs[i].sam = 0;
-			rc = BMH_E_NOMEM;
-			goto done;
-		}
-		memcpy(s, text + text_off[i], len), s[len] = 0;
-		seqs[i].sam = s;
-	}
+	if ((rc = bmh_sam_cut(n, seqs, text, text_off))) goto done; /* host/samcut_core.h: all or nothing */
 	if (trace)
 		fprintf(stderr, "[bwamem_hip] bmh_sam_batch %d reads, %zu alignments: marking + pairing %.1f ms, global alignments (bmh_reg2cigar_batch) %.1f ms, coordinates + text %.1f ms\n",
 		        n, (size_t)n_w, (tt[1] - tt[0]) * 1e3, (tt[2] - tt[1]) * 1e3, (now_s() - tt[2]) * 1e3);

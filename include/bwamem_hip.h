@@ -1144,7 +1144,9 @@ int bmh_last_drop_exact_stats(const bmh_ctx_t *ctx, int64_t *removed);
  *   BMH_OK       for n == 0 with a 1-byte *text and text_off[0] = 0, nothing runs
  * All or nothing: on any error *text and text_off are untouched, and the context stays usable.
  * Afterwards bmh_driver_stats, bmh_chain_stats, bmh_last_dedup_stats and bmh_last_drop_exact_stats are valid as after
- * bmh_seed_chain_regs_batch, and bmh_last_phase2_text_stats as after bmh_phase2_text_device. */
+ * bmh_seed_chain_regs_batch, and bmh_last_phase2_text_stats as after bmh_phase2_text_device.
+ * The preload shim makes this call once per batch of a single-end chunk under BMH_READS_SAM_DEVICE=1 (host/interpose.c) and ends the run
+ * on any error: it has no other route for the batch. */
 int bmh_reads_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_sam_opt_t *o,
                          const bmh_refidx_t *bns, const uint8_t *pac, int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id,
                          char **text, int64_t *text_off);

@@ -72,7 +72,8 @@ def sim_pairs_fast(rng, ref, n, L, noisy_frac):
 
 
 def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=False, regs_device=False, dedup_device=False, matesw_device=False,
-        decide_device=False, wanted_device=False, phase2_device=False, samtext_device=False, phase2_text_device=False, pestat_device=False):
+        decide_device=False, wanted_device=False, phase2_device=False, samtext_device=False, phase2_text_device=False, pestat_device=False,
+        reads_sam_device=False, more_env=None):
     env = dict(os.environ)
     env.pop("BMH_PESTAT_DEVICE", None)
     env.pop("BMH_CHAIN_DEVICE", None)
@@ -84,7 +85,10 @@ def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=Fals
     env.pop("BMH_PHASE2_DEVICE", None)
     env.pop("BMH_SAMTEXT_DEVICE", None)
     env.pop("BMH_PHASE2_TEXT_DEVICE", None)
+    env.pop("BMH_READS_SAM_DEVICE", None)
     if preload:
+        if reads_sam_device:
+            env["BMH_READS_SAM_DEVICE"] = "1"
         if phase2_text_device:
             env["BMH_PHASE2_TEXT_DEVICE"] = "1"
         if samtext_device:
@@ -111,20 +115,54 @@ def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=Fals
         env["BMH_SMEM_TRACE"] = "1"
         if os.environ.get("BMH_DRIVER_TRACE"):
             env["BMH_DRIVER_TRACE"] = "1"
+        env.update(more_env or {})
     t0 = time.time()
     with open(out, "w") as f:
         p = subprocess.run([reflib.REF_BWA, "mem", "-t", str(threads), "-b", str(batch), fa] + (fq if isinstance(fq, list) else [fq]), stdout=f,
                            stderr=subprocess.PIPE, env=env, check=True, timeout=3000)
     wall = time.time() - t0
     reads = real = 0
+    chunks = []  # (reads, real seconds) of every chunk, in order
     for m in re.finditer(r"Processed (\d+) reads in ([\d.]+) CPU sec, ([\d.]+) real sec", p.stderr.decode()):
         reads += int(m.group(1))
         real += float(m.group(3))
+        chunks.append((int(m.group(1)), float(m.group(3))))
     shim = [l for l in p.stderr.decode().splitlines() if l.startswith("[bwamem_hip]")]
     drv = [l for l in shim if "bmh_chain2aln_batch" in l]
     cgr = [l for l in shim if "bmh_reg2cigar_batch" in l and "regions:" in l]
     shim = [l for l in shim if l not in drv and l not in cgr]
-    return {"reads": reads, "shim": shim[:6] + drv[2:8] + cgr[:4] + shim[-8:], "process_seqs_real_s": real, "reads_per_s": reads / real if real else None, "wall_s": wall}
+    res = {"reads": reads, "shim": shim[:6] + drv[2:8] + cgr[:4] + shim[-8:], "process_seqs_real_s": real, "reads_per_s": reads / real if real else None, "wall_s": wall,
+           "chunks": chunks}
+    if preload and reads_sam_device:  # which way the chunks went: the session's line, or the shim's word that a paired-end chunk took the other route
+        one = [l for l in shim if "in one session so far" in l]
+        res["reads_sam_device"] = {"chunks_in_one_session": len(one), "chunks_the_other_way": sum("in one session: off for this chunk" in l for l in shim),
+                                   "so_far": one[-1] if one else None}
+    return res
+
+
+def make_input(a, tmp):
+    """The run's genome, its index and its reads under tmp, from a.genome, a.repeats, a.reads, a.pe and a.noisy: (fasta, fastq or the two
+    fastq files, seconds the index took).  The same arguments give the same files."""
+    rng = np.random.default_rng(20261007)
+    ref = kswgen.rand_seq(rng, a.genome)
+    for _ in range(a.repeats):  # multi-copy sequence: seeds with many occurrences, secondary hits, mapQ ties, more rescue
+        src, dst, L = int(rng.integers(0, a.genome - 4000)), int(rng.integers(0, a.genome - 4000)), int(rng.integers(200, 3000))
+        ref[dst:dst + L] = kswgen.mutate(rng, ref[src:src + L + 40], float(rng.choice([0.0, 0.005, 0.02])), 0.001, 0.001, 2)[:L]
+    fa, fq = os.path.join(tmp, "ref.fa"), os.path.join(tmp, "reads.fq")
+    reflib.write_fasta(fa, "synth", ref)
+    t0 = time.time()
+    reflib.build_index(fa)
+    t_index = time.time() - t0
+    if a.pe:
+        m1, m2 = sim_pairs_fast(rng, ref, a.reads // 2, 150, a.noisy)
+        fq2 = os.path.join(tmp, "reads_2.fq")
+        reflib.write_fastq(fq, list(m1), "p")
+        reflib.write_fastq(fq2, list(m2), "p")
+        fq = [fq, fq2]
+    else:
+        reads = sim_reads_fast(rng, ref, a.reads, 150)
+        reflib.write_fastq(fq, list(reads))
+    return fa, fq, t_index
 
 
 def main():
@@ -154,34 +192,20 @@ def main():
                     help="the DUT's phase 2 coordinates and SAM text are made on the device (BMH_SAMTEXT_DEVICE=1)")
     ap.add_argument("--phase2-text-device", action="store_true",
                     help="the DUT's whole phase 2 runs as one device session, only SAM text comes down (BMH_PHASE2_TEXT_DEVICE=1)")
+    ap.add_argument("--reads-sam-device", action="store_true",
+                    help="single-end reads: every batch of the DUT goes from bases to SAM text in one device session (BMH_READS_SAM_DEVICE=1); "
+                         "with --pe the chunks go the way they go without it, and the run says so")
     ap.add_argument("--pestat-device", action="store_true",
                     help="--pe: ... and answers mem_pestat's question per pair there (BMH_PESTAT_DEVICE=1); implies --regs-device --dedup-device")
     a = ap.parse_args()
     a.dedup_device = a.dedup_device or a.pestat_device
     a.regs_device = a.regs_device or a.dedup_device
-    rng = np.random.default_rng(20261007)
     tmp = tempfile.mkdtemp(prefix="bmh_pipe_")
-    ref = kswgen.rand_seq(rng, a.genome)
-    for _ in range(a.repeats):  # multi-copy sequence: seeds with many occurrences, secondary hits, mapQ ties, more rescue
-        src, dst, L = int(rng.integers(0, a.genome - 4000)), int(rng.integers(0, a.genome - 4000)), int(rng.integers(200, 3000))
-        ref[dst:dst + L] = kswgen.mutate(rng, ref[src:src + L + 40], float(rng.choice([0.0, 0.005, 0.02])), 0.001, 0.001, 2)[:L]
-    fa, fq = os.path.join(tmp, "ref.fa"), os.path.join(tmp, "reads.fq")
-    reflib.write_fasta(fa, "synth", ref)
-    t0 = time.time()
-    reflib.build_index(fa)
-    t_index = time.time() - t0
-    if a.pe:
-        m1, m2 = sim_pairs_fast(rng, ref, a.reads // 2, 150, a.noisy)
-        fq2 = os.path.join(tmp, "reads_2.fq")
-        reflib.write_fastq(fq, list(m1), "p")
-        reflib.write_fastq(fq2, list(m2), "p")
-        fq = [fq, fq2]
-    else:
-        reads = sim_reads_fast(rng, ref, a.reads, 150)
-        reflib.write_fastq(fq, list(reads))
+    fa, fq, t_index = make_input(a, tmp)
+
     res = {"genome_bp": a.genome, "repeats": a.repeats, "reads": a.reads, "paired": bool(a.pe), "index_s": t_index, "chain_device": bool(a.chain_device), "regs_device": bool(a.regs_device),
            "dedup_device": bool(a.dedup_device), "matesw_device": bool(a.matesw_device), "decide_device": bool(a.decide_device), "wanted_device": bool(a.wanted_device),
-           "phase2_device": bool(a.phase2_device), "samtext_device": bool(a.samtext_device), "phase2_text_device": bool(a.phase2_text_device), "pestat_device": bool(a.pestat_device), "runs": []}
+           "phase2_device": bool(a.phase2_device), "samtext_device": bool(a.samtext_device), "phase2_text_device": bool(a.phase2_text_device), "pestat_device": bool(a.pestat_device), "reads_sam_device": bool(a.reads_sam_device), "runs": []}
     # one untimed DUT run first: on a fresh box the first process to load the HIP runtime and the library's code objects
     # pays for reading them from disk (seconds), which has nothing to do with the pipeline
     run(fa, fq, 8, a.batch, True, os.path.join(tmp, "warm.sam"), ksw_dropin=False)
@@ -190,13 +214,15 @@ def main():
         refsam = [l for l in open(os.path.join(tmp, "ref.sam")) if not l.startswith("@PG")]
         d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False, chain_device=a.chain_device, regs_device=a.regs_device,
                  dedup_device=a.dedup_device, matesw_device=a.matesw_device, decide_device=a.decide_device, wanted_device=a.wanted_device,
-                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device)
+                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device,
+                 reads_sam_device=a.reads_sam_device)
         same1 = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         d2 = None
         if a.full:
             d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True, chain_device=a.chain_device, regs_device=a.regs_device,
                  dedup_device=a.dedup_device, matesw_device=a.matesw_device, decide_device=a.decide_device, wanted_device=a.wanted_device,
-                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device)
+                 phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device,
+                 reads_sam_device=a.reads_sam_device)
             d2["sam_identical"] = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         res["runs"].append({"threads": t, "batch": a.batch, "ref": r, "dut_phase1_gpu": d1, "sam_identical": same1,
                             "dut_phase1_gpu_plus_percall_global": d2})
