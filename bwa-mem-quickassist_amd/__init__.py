@@ -89,6 +89,9 @@ PHASE2_TEXT_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i
 READS_SAM_STATS = np.dtype([("reads", "<i8"), ("regions_in", "<i8"), ("regions", "<i8"), ("kmax", "<i8"), ("opool_cap", "<i8"),
                             ("handoff_d2h_bytes", "<i8"), ("waits_tail", "<i4"), ("plan_ms", "<f4"), ("neg_index", "<i4"),
                             ("rsv", "<i4")])  # bmh_reads_sam_stats_t, 64 bytes
+MATESW_TABLE_STATS = np.dtype([("regions_in", "<i8"), ("regions_out", "<i8"), ("arena_records", "<i8"), ("hits", "<i8"), ("mid_bytes", "<i8"),
+                               ("pairs", "<i4"), ("active", "<i4"), ("waits", "<i4"), ("filter_ms", "<f4"), ("pack_ms", "<f4"),
+                               ("merge_ms", "<f4")])  # bmh_matesw_table_stats_t, 64 bytes
 WANTED_MOVED, WANTED_HOST = 4, 8
 MEM_F_NO_MULTI = 0x10
 MEM_F_NO_EXACT = 0x40
@@ -231,6 +234,9 @@ def lib():
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmh_matesw_device.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                         C.c_void_p]
+        L.bmh_matesw_table_device.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmh_last_matesw_table_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_sw_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p]
         L.bmh_sw_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.bmh_extend_batch_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -817,6 +823,49 @@ class Context:
             e.regs = out
             raise
         return out, n_sw[:n_pairs].tolist()
+
+    def matesw_table_device(self, l_pac, reads, regs, pes, opt, mask_level_redun, roff=None):
+        """bmh_matesw_table_device: matesw_device over a flat region table.  Arguments and result as matesw_device's: the vectors are
+        flattened here (read k's regions at reg[roff[k]:roff[k + 1]]) and the output table is cut into vectors again.  roff: the
+        offsets to pass instead of the vectors' own (for the argument checks).  A refused call raises BmhError with what it left of
+        the outputs in `outputs`: (roff_out, the region pointer, n_sw), each as it was before the call if nothing was written."""
+        n_pairs = len(reads) // 2
+        pes = np.ascontiguousarray(pes, dtype=PESTAT)
+        opt = np.ascontiguousarray(opt, dtype=MATESW_OPT)
+        keep = []
+        c_reads = (_Read * max(len(reads), 1))()
+        for k, r in enumerate(reads):
+            r = np.ascontiguousarray(r, dtype=np.uint8)
+            keep.append(r)
+            c_reads[k].l_seq, c_reads[k].seq = len(r), r.ctypes.data
+        vecs = [np.ascontiguousarray(r, dtype=ALNREG).reshape(-1) for r in regs]
+        flat = np.concatenate([np.zeros(0, dtype=ALNREG)] + vecs)
+        if roff is None:
+            roff = np.concatenate([[0], np.cumsum([len(v) for v in vecs])])
+        roff = np.ascontiguousarray(roff, dtype=np.uint64)
+        roff_out = np.full(2 * n_pairs + 1, 0xdeadbeefdeadbeef, dtype=np.uint64)
+        n_sw = np.full(max(n_pairs, 1), -77, dtype=np.int32)
+        reg_out = C.c_void_p(None)
+        rc = lib().bmh_matesw_table_device(self._h, C.c_int64(l_pac), n_pairs, C.cast(c_reads, C.c_void_p), _ptr(roff),
+                                           _ptr(flat) if len(flat) else None, _ptr(pes), _ptr(opt), C.c_float(mask_level_redun), _ptr(roff_out),
+                                           C.cast(C.byref(reg_out), C.c_void_p), _ptr(n_sw))
+        try:
+            self._check(rc)
+        except BmhError as e:
+            e.outputs = (roff_out, reg_out.value, n_sw[:n_pairs])
+            raise
+        total = int(roff_out[2 * n_pairs])
+        table = np.zeros(total, dtype=ALNREG)
+        if total:
+            C.memmove(table.ctypes.data, reg_out.value, total * ALNREG.itemsize)
+        _libc.free(reg_out)
+        return [table[int(roff_out[k]):int(roff_out[k + 1])].copy() for k in range(2 * n_pairs)], n_sw[:n_pairs].tolist()
+
+    def last_matesw_table_stats(self):
+        """bmh_last_matesw_table_stats as a dict of MATESW_TABLE_STATS' fields: the last matesw_table_device call on this context."""
+        st = np.zeros(1, dtype=MATESW_TABLE_STATS)
+        self._check(lib().bmh_last_matesw_table_stats(self._h, _ptr(st)))
+        return {k: st[0][k].item() for k in MATESW_TABLE_STATS.names}
 
     def extend_batch_device(self, d_pool, d_tasks, n, d_res, d_order=0):
         self._check(lib().bmh_extend_batch_device(self._h, C.c_void_p(d_pool), C.c_void_p(d_tasks), int(n),

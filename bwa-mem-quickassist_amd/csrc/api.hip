@@ -350,6 +350,9 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_plan)
 		if (e) (void)hipEventDestroy(e);
+	free_buf(ctx->d_mswt), free_buf(ctx->d_mswin);
+	for (auto &e : ctx->ev_mswt)
+		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
 		if (h.ev) (void)hipEventDestroy(h.ev);
 		if (h.h) (void)hipHostFree(h.h);

@@ -197,6 +197,11 @@ struct bmh_ctx {
 	hipEvent_t ev_plan[2] = {};               // around regs_plan_kernel (timing mode)
 	bmh_reads_sam_stats_t rs = {-1, -1, -1, -1, -1, -1, -1, -1.f, -1, -1}; // of the last such call (bmh_last_reads_sam_stats)
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
+	// ... over a region table (matesw_resident): behind those the output table, offsets first, and n_sw per pair
+	DevBuf d_mswt;                            // its filter stage: plan record, per-wave parts, per-pair records, block sums
+	DevBuf d_mswin;                           // bmh_matesw_table_device's upload: read offsets, region offsets, regions, reads
+	hipEvent_t ev_mswt[6] = {};               // around the filter, pack and merge kernels (timing mode)
+	bmh_matesw_table_stats_t mt = {-1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f, -1.f}; // of the last such call (bmh_last_matesw_table_stats)
 };
 
 namespace bmh {
@@ -267,6 +272,14 @@ int reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt
                      int min_seed_len, const char *who);
 int reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
                         int min_seed_len, const bmh_sam_opt_t *o, ResidentRegs *out);
+// Mate rescue over a resident table (matesw.hip): reads 2p and 2p + 1 are mates, read k's bases d_pool[d_soff[k] .. d_soff[k + 1]) with 16
+// bytes of padding behind the last, its regions in.reg[in.roff[k] .. in.roff[k + 1]) (in.total of them; the other fields are not read).
+// Fills out->roff, out->reg and out->total, and *d_n_sw (n_pairs entries): all in ctx->d_msw, valid until the next call that uses that
+// buffer, so `in` must not lie there.  Between its first launch and its return the host reads the 64-byte plan record, 16 bytes per
+// round and the 16-byte total.  ctx->dstats and ctx->mt are the call's.  The caller holds the gate and has checked l_pac against the
+// resident reference.
+int matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t *d_pool, const unsigned long long *d_soff, const ResidentRegs &in,
+                    const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, ResidentRegs *out, int **d_n_sw);
 // every host wait for a stream goes through here (bmh_set_wait_mode)
 extern int g_wait_blocking;
 inline hipError_t stream_wait(bmh_ctx *ctx, hipStream_t s)

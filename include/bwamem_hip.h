@@ -608,6 +608,46 @@ int bmh_matesw_batch(bmh_ctx_t *ctx, int64_t l_pac, const uint8_t *pac, int n_pa
  * ksw_align2 tasks, and as pool_bytes the reads of the pairs that need rescue plus 16 bytes of padding (0 if no round launched). */
 int bmh_matesw_device(bmh_ctx_t *ctx, int64_t l_pac, int n_pairs, const bmh_read_t *reads, bmh_alnreg_v *regs,
                       const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, int *n_sw);
+/* The same rescue over a flat region table that stays on the device (csrc/matesw.hip): read k's regions are reg[roff[k] .. roff[k+1]),
+ * reads 2p and 2p+1 are mates.  What bmh_matesw_device does on the host around its rounds runs as kernels here: the pre-filter and the
+ * refusals (mt_filter_kernel, one lane per pair, over host/matesw_table_core.h), the sizing (scans), the packing of the arena slices,
+ * the candidate hits and the pair records (mt_pack_kernel, mt_slices_kernel; the reads are one pool on the device and are not copied),
+ * and the merge of the rescued vectors with the untouched ones into a second table (mt_count_kernel, mt_place_kernel, mt_copy_kernel).
+ * The rounds between are bmh_matesw_device's own.  The call uploads every read as one pool and the table, runs that, and downloads
+ * the result; between the upload and the download the host reads one 64-byte plan record, 16 status bytes per round as
+ * bmh_matesw_device does, and one 16-byte total.
+ *   result       roff_out[0 .. 2*n_pairs], *reg_out (malloc'd, the caller frees it; one record at least) and n_sw (nullable) are the
+ *                flattening of what bmh_matesw_device leaves in the vectors and in n_sw for the same reads, regions, pes, o and
+ *                mask_level_redun, byte for byte
+ *   BMH_E_ARG    before anything is uploaded: a NULL ctx, roff, pes, o, roff_out or reg_out; NULL reads with n_pairs > 0; n_pairs < 0;
+ *                l_pac <= 0; no parameters set; no 2-bit reference of this l_pac resident on the device (bmh_ctx_set_pac); roff[0] != 0
+ *                or roff not non-decreasing; a vector of more than 2^31 - 1 regions; a NULL reg with roff[2*n_pairs] > 0; a read with
+ *                l_seq < 0, or with l_seq > 0 and a NULL seq (every read goes up, also those of pairs that need no rescue)
+ *   BMH_E_RANGE  from the plan record, before any round runs: bmh_matesw_device's conditions with its texts and the read's index -- a
+ *                pair that needs rescue with a read outside 1..65535 bases, byte mode under gap penalties that wrap, l_seq*max(mat) >=
+ *                32000 without bmh_ctx_set_wide_sw.  The reads of pairs that need no rescue do not count.
+ *   BMH_OK       without a round for n_pairs == 0 and for a batch in which no pair needs rescue: the output is a copy of the input,
+ *                made on the device
+ * All or nothing: on any error roff_out, *reg_out and n_sw are untouched, the Smith-Waterman kernels' error flag is clean and the
+ * context stays usable.  bmh_driver_stats reports bmh_matesw_device's rounds and ext_tasks; pool_bytes is the uploaded pool -- every
+ * read plus 16 bytes of padding -- when a round launched Smith-Waterman, else 0.  Nothing routes to this call by default. */
+int bmh_matesw_table_device(bmh_ctx_t *ctx, int64_t l_pac, int n_pairs, const bmh_read_t *reads,
+                            const uint64_t *roff, const bmh_alnreg_t *reg,
+                            const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun,
+                            uint64_t *roff_out, bmh_alnreg_t **reg_out, int *n_sw);
+/* Of the last bmh_matesw_table_device call on this context that got past its argument checks; all -1 before the first.
+ *   regions_in, regions_out  of the two tables
+ *   arena_records, hits      what the filter sized for the pairs that need rescue: the slices' records, the candidate hits
+ *   mid_bytes                bytes that crossed PCIe between the upload and the final download: 64 + 16 per status read-back + 16
+ *   pairs, active            of the batch; that need rescue
+ *   waits                    host waits between the upload and the final download: 2 + the status read-backs
+ *   filter_ms, pack_ms, merge_ms   the three kernel groups' milliseconds with bmh_set_kernel_timing on, else -1 */
+typedef struct bmh_matesw_table_stats {
+	int64_t regions_in, regions_out, arena_records, hits, mid_bytes;
+	int32_t pairs, active, waits;
+	float filter_ms, pack_ms, merge_ms;
+} bmh_matesw_table_stats_t; /* 64 bytes */
+int bmh_last_matesw_table_stats(const bmh_ctx_t *ctx, bmh_matesw_table_stats_t *st);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Region post-processing and SAM text: everything mem_process_seqs does with a read's region
