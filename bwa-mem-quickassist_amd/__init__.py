@@ -89,6 +89,10 @@ PHASE2_TEXT_STATS = np.dtype([("units", "<i8"), ("wanted", "<i8"), ("fixed", "<i
 READS_SAM_STATS = np.dtype([("reads", "<i8"), ("regions_in", "<i8"), ("regions", "<i8"), ("kmax", "<i8"), ("opool_cap", "<i8"),
                             ("handoff_d2h_bytes", "<i8"), ("waits_tail", "<i4"), ("plan_ms", "<f4"), ("neg_index", "<i4"),
                             ("rsv", "<i4")])  # bmh_reads_sam_stats_t, 64 bytes
+PAIRS_SAM_STATS = np.dtype([("reads", "<i8"), ("pairs", "<i8"), ("regions_in", "<i8"), ("regions", "<i8"), ("regions_out", "<i8"), ("n_sw", "<i8"),
+                            ("kmax", "<i8"), ("pair_kmax", "<i8"), ("opool_cap", "<i8"), ("mid_d2h_bytes", "<i8"), ("mid_h2d_bytes", "<i8"),
+                            ("waits_mid", "<i4"), ("pes_given", "<i4"), ("plan_ms", "<f4"), ("neg_index", "<i4"),
+                            ("rsv", "<i4", (6,))])  # bmh_pairs_sam_stats_t, 128 bytes
 MATESW_TABLE_STATS = np.dtype([("regions_in", "<i8"), ("regions_out", "<i8"), ("arena_records", "<i8"), ("hits", "<i8"), ("mid_bytes", "<i8"),
                                ("pairs", "<i4"), ("active", "<i4"), ("waits", "<i4"), ("filter_ms", "<f4"), ("pack_ms", "<f4"),
                                ("merge_ms", "<f4")])  # bmh_matesw_table_stats_t, 64 bytes
@@ -284,6 +288,9 @@ def lib():
         L.bmh_reads_sam_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
         L.bmh_last_reads_sam_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_pairs_sam_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.bmh_last_pairs_sam_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1244,6 +1251,43 @@ class Context:
         st = np.zeros(1, dtype=READS_SAM_STATS)
         self._check(lib().bmh_last_reads_sam_stats(self._h, _ptr(st)))
         return {k: st[0][k].item() for k in READS_SAM_STATS.names if k != "rsv"}
+
+    def pairs_sam_device(self, smem_opt, chain_opt, min_seed_len, matesw_opt, opt, refidx, pac, pes, id0, seqs, rg_id=b"", out=None):
+        """bmh_pairs_sam_device: paired-end reads to SAM text as one device session; the regions never leave the device.  Reads 2p and
+        2p + 1 are mates.  matesw_opt: MATESW_OPT; pes: the caller's PESTAT[4], or None for the table of exactly these reads; the rest as
+        reads_sam_device's.  Returns (text, text_off, pes): pes is the table that was used.  out may also hold "pes", a PESTAT[4] array
+        to write into."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8) if pac is not None else None
+        n = len(seqs)
+        o_in, so = np.asarray(smem_opt), np.zeros((), dtype=SMEM_OPT)
+        for k in o_in.dtype.names:
+            so[k] = o_in[k]
+        co = np.ascontiguousarray(np.asarray(chain_opt, dtype=CHAIN_OPT).reshape(()))
+        mo = np.ascontiguousarray(matesw_opt, dtype=MATESW_OPT)
+        o = np.array(opt, dtype=SAM_OPT).reshape(1)
+        keep = []
+        c_seqs = (_Seq * max(n, 1))()
+        for r, (name, comment, seq, qual) in enumerate(seqs):
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            keep.append(seq)
+            c_seqs[r] = _Seq(len(seq), name, comment, seq.ctypes.data if len(seq) else None, qual, None)
+        out = out or {}
+        text = out.get("text", C.c_void_p(None))
+        text_off = out.get("text_off", np.zeros(n + 1, dtype=np.int64))
+        pes_out = out.get("pes", np.zeros(4, dtype=PESTAT))
+        pes_p = _ptr(np.ascontiguousarray(pes, dtype=PESTAT)) if pes is not None else None
+        self._check(lib().bmh_pairs_sam_device(self._h, _ptr(so), _ptr(co), int(min_seed_len), _ptr(mo), _ptr(o),
+                                               C.byref(refidx) if refidx is not None else None, _ptr(pac), pes_p, _ptr(pes_out), C.c_int64(int(id0)), n,
+                                               C.cast(c_seqs, C.c_void_p), rg_id, C.cast(C.byref(text), C.c_void_p), _ptr(text_off)))
+        data = C.string_at(text.value, int(text_off[n]))
+        _libc.free(text)
+        return data, text_off, pes_out
+
+    def last_pairs_sam_stats(self):
+        """bmh_last_pairs_sam_stats as a dict of PAIRS_SAM_STATS' fields: the last pairs_sam_device call on this context."""
+        st = np.zeros(1, dtype=PAIRS_SAM_STATS)
+        self._check(lib().bmh_last_pairs_sam_stats(self._h, _ptr(st)))
+        return {k: st[0][k].item() for k in PAIRS_SAM_STATS.names if k != "rsv"}
 
     def sam_text_batch(self, *args, device=True, **kw):
         """sam_text_batch() on this context: bmh_sam_text_device (device=False: the host call, which needs no context)."""

@@ -350,7 +350,7 @@ int bmh_ctx_destroy(bmh_ctx_t *ctx)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : ctx->ev_plan)
 		if (e) (void)hipEventDestroy(e);
-	free_buf(ctx->d_mswt), free_buf(ctx->d_mswin);
+	free_buf(ctx->d_mswt), free_buf(ctx->d_mswin), free_buf(ctx->d_pbase);
 	for (auto &e : ctx->ev_mswt)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &h : ctx->hint) {
@@ -1699,10 +1699,11 @@ static int decide_table_sizes(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, i
 {
 	const bool pe = (o->flag & BMH_MEM_F_PE) != 0;
 	bmh_ho_plan_t plan = BMH_HO_PLAN_INIT;
-	long long pair_kmax = 0;
+	int64_t pair_kmax = BMH_HO_PAIRS_INIT;
 	for (int i = 0; i < n; ++i) {
 		bmh_ho_read(o, regs[i].a, (int64_t)regs[i].n, &plan);
-		if (pe && (i & 1)) pair_kmax = std::max<long long>(pair_kmax, bmh_ho_pair_kmax((int64_t)regs[i - 1].n, (int64_t)regs[i].n));
+		// the paired-end clause as table_plan_kernel folds it: a first mate raises the fold to its pair's bmh_ho_pair_kmax(n0, n1)
+		if (pe && bmh_ho_first_mate(i, n)) bmh_ho_pair((int64_t)regs[i].n, (int64_t)regs[i + 1].n, &pair_kmax);
 	}
 	if (opool_cap) *opool_cap = (size_t)plan.opool_cap;
 	return decide_tables_from_plan(o, pes, plan, pair_kmax, kmax_, n_term_, term_off, why);
@@ -2440,7 +2441,7 @@ static int phase2_plan(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_pestat_t 
 	*why = nullptr;
 	if (res) {
 		const bmh_ho_plan_t plan{res->kmax, res->opool_cap, res->total, res->neg ? 1 : 0, 0};
-		rc = decide_tables_from_plan(o, pes, plan, 0, &T.kmax, &T.n_term, T.term_off, why);
+		rc = decide_tables_from_plan(o, pes, plan, res->pair_kmax, &T.kmax, &T.n_term, T.term_off, why); // (pair_kmax: 0 from a single-end call)
 		opool_cap = (size_t)res->opool_cap;
 	} else
 		rc = decide_table_sizes(o, pes, n, regs, &T.kmax, &T.n_term, T.term_off, why, &opool_cap);
@@ -3262,7 +3263,7 @@ int bmh_reads_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_cha
 	static const char *const who = "bmh_reads_sam_device";
 	if (!ctx || !so || !co || !o || !bns || !text || !text_off || n < 0 || (n > 0 && !seqs)) return BMH_E_ARG;
 	if (o->flag & BMH_MEM_F_PE) {
-		ctx->last_error = std::string(who) + ": single-end only (mate rescue lies between the two phases of a paired-end batch)";
+		ctx->last_error = std::string(who) + ": single-end only (mate rescue lies between the two phases of a paired-end batch: bmh_pairs_sam_device)";
 		return BMH_E_ARG;
 	}
 	// what either phase refuses, phase 1's first, before anything is uploaded
@@ -3290,6 +3291,101 @@ int bmh_last_reads_sam_stats(const bmh_ctx_t *ctx, bmh_reads_sam_stats_t *st)
 {
 	if (!ctx || !st) return BMH_E_ARG;
 	*st = ctx->rs;
+	return BMH_OK;
+}
+
+// ------------------------------------------------------------------ paired-end reads to SAM text: phase 1, the insert-size barrier, mate
+// rescue over the resident table, the plan over its output, phase 2 -- the table in d_c2r, then in d_msw, then in pass A's block
+
+static_assert(sizeof(bmh_pairs_sam_stats_t) == 128, "bmh_pairs_sam_stats_t is part of the interface");
+
+int bmh_pairs_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_matesw_opt_t *mo,
+                         const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes0, bmh_pestat_t pes_out[4],
+                         int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id, char **text, int64_t *text_off)
+{
+	static const char *const who = "bmh_pairs_sam_device";
+	if (!ctx || !so || !co || !mo || !o || !bns || !text || !text_off || n < 0 || (n > 0 && !seqs)) return BMH_E_ARG;
+	if (!(o->flag & BMH_MEM_F_PE)) {
+		ctx->last_error = std::string(who) + ": paired-end only (o->flag lacks BMH_MEM_F_PE; single-end reads: bmh_reads_sam_device)";
+		return BMH_E_ARG;
+	}
+	if (n & 1) {
+		ctx->last_error = std::string(who) + ": n is odd: reads 2p and 2p+1 are mates";
+		return BMH_E_ARG;
+	}
+	// what either phase refuses, phase 1's first, before anything is uploaded (phase 2's check wants a table: any will do for it)
+	bmh_pestat_t pes[4];
+	if (pes0) memcpy(pes, pes0, sizeof(pes));
+	else {
+		memset(pes, 0, sizeof(pes));
+		for (bmh_pestat_t &x : pes) x.failed = 1;
+	}
+	std::vector<bmh_read_t> reads((size_t)n), again;
+	for (int i = 0; i < n; ++i) reads[(size_t)i].l_seq = seqs[i].l_seq, reads[(size_t)i].seq = (const uint8_t *)seqs[i].seq;
+	int rc;
+	if ((rc = reads_regs_check(ctx, so, co, bns->l_pac, n, reads.data(), min_seed_len, who))) return rc;
+	if (!pes0 && o->max_ins > BMH_PS_MAX_INS) {
+		ctx->last_error = std::string(who) + ": max_ins must be below 2^30 without a table of the caller's: the insert-size word carries the orientation above it";
+		return BMH_E_RANGE;
+	}
+	if ((rc = phase2_text_check(ctx, who, o, bns, pac, pes, n, seqs, nullptr, true, rg_id, text, text_off, again))) return rc;
+	bool early;
+	if (n == 0) { // nothing runs
+		if ((rc = phase2_text_run(ctx, who, o, bns, pac, pes, id0, 0, seqs, nullptr, nullptr, rg_id, text, text_off, &early))) return rc;
+		ctx->dstats = bmh_driver_stats_t{};
+		if (o->flag & BMH_MEM_F_NO_EXACT) ctx->drop_exact_removed = 0;
+		ctx->ps = bmh_pairs_sam_stats_t{0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, pes0 ? 1 : 0, -1.f, 0, {0, 0, 0, 0, 0, 0}};
+		if (pes_out) memcpy(pes_out, pes, sizeof(pes));
+		return BMH_OK;
+	}
+	const int64_t l_pac = bns->l_pac;
+	// ---- phase 1: the table in d_c2r, the bases in d_pbase, and without a table of the caller's the words
+	PairsPhase1 P1;
+	if ((rc = pairs_regs_resident(ctx, so, co, l_pac, n, reads.data(), min_seed_len, o, pes0 == nullptr, &P1))) return rc;
+	// ---- the insert-size barrier: the table of exactly this call's reads, a host pass over 4 bytes per pair
+	if (!pes0 && (rc = bmh_pestat_from_candidates(o, n >> 1, P1.cand.data(), pes, -1))) {
+		ctx->last_error = std::string(who) + ": the insert-size words are inconsistent";
+		return rc;
+	}
+	{ // the pair table's refusal needs the table alone: before rescue opens windows of that width
+		const char *why = nullptr;
+		long long kmax, n_term;
+		int64_t term_off[4];
+		const bmh_ho_plan_t none = BMH_HO_PLAN_INIT;
+		if (decide_tables_from_plan(o, pes, none, 0, &kmax, &n_term, term_off, &why)) {
+			reset_phase2_text_stats(ctx);
+			ctx->last_error = why ? why : "bmh_decide_device: the tables are out of range";
+			ctx->pt.fallbacks = 1;
+			return BMH_E_RANGE;
+		}
+	}
+	// ---- mate rescue over the table where it lies; its output table, n_sw and the plan over it in d_msw
+	ResidentRegs R;
+	long long n_sw = 0;
+	{
+		GateGuard gate;
+		BMH_HIP(ctx, hipSetDevice(ctx->device));
+		int *d_n_sw = nullptr;
+		if ((rc = matesw_resident(ctx, l_pac, n >> 1, P1.pool, P1.soff, P1.regs, pes, mo, o->mask_level_redun, &R, &d_n_sw, o, &n_sw))) {
+			const std::string table_name = "bmh_matesw_table_device"; // the refusals speak as bmh_matesw_device's do
+			for (size_t at; (at = ctx->last_error.find(table_name)) != std::string::npos;) ctx->last_error.replace(at, table_name.size(), who);
+			return rc;
+		}
+	}
+	bmh_pairs_sam_stats_t &ps = ctx->ps;
+	ps = bmh_pairs_sam_stats_t{n, n >> 1, P1.regions_in, P1.regs.total, R.total, n_sw, R.kmax, R.pair_kmax, R.opool_cap,
+	                           P1.d2h_bytes + ctx->mt.mid_bytes, 0, 1 + ctx->mt.waits, pes0 ? 1 : 0, -1.f, R.neg ? 1 : 0, {0, 0, 0, 0, 0, 0}};
+	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ps.plan_ms, ctx->ev_plan[0], ctx->ev_plan[1]));
+	// ---- phase 2 from the plan's numbers: nothing it ensures or launches touches d_msw
+	if ((rc = phase2_text_run(ctx, who, o, bns, pac, pes, id0, n, seqs, nullptr, &R, rg_id, text, text_off, &early))) return rc;
+	if (pes_out) memcpy(pes_out, pes, sizeof(pes));
+	return BMH_OK;
+}
+
+int bmh_last_pairs_sam_stats(const bmh_ctx_t *ctx, bmh_pairs_sam_stats_t *st)
+{
+	if (!ctx || !st) return BMH_E_ARG;
+	*st = ctx->ps;
 	return BMH_OK;
 }
 

@@ -202,6 +202,9 @@ struct bmh_ctx {
 	DevBuf d_mswin;                           // bmh_matesw_table_device's upload: read offsets, region offsets, regions, reads
 	hipEvent_t ev_mswt[6] = {};               // around the filter, pack and merge kernels (timing mode)
 	bmh_matesw_table_stats_t mt = {-1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f, -1.f}; // of the last such call (bmh_last_matesw_table_stats)
+	// paired-end reads to SAM text with the region table resident from phase 1 through mate rescue to phase 2 (bmh_pairs_sam_device)
+	DevBuf d_pbase;                           // the bases for the rescue: 64-bit offsets, the reads, 16 zero bytes (copied from seeding's pool)
+	bmh_pairs_sam_stats_t ps = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1, {0, 0, 0, 0, 0, 0}}; // of the last such call (bmh_last_pairs_sam_stats)
 };
 
 namespace bmh {
@@ -259,11 +262,13 @@ typedef int (*SeedTablesFn)(bmh_ctx *ctx, const DevSeedTables &t, void *user);
 int seed_tables_device(bmh_ctx *ctx, const bmh_smem_opt_t *o, int max_occ, int n_reads, const bmh_read_t *reads, SeedTablesFn fn, void *user);
 // A batch's regions where c2r_place_kernel left them, in ctx->d_c2r: read r's at reg[roff[r] .. roff[r + 1]), and what regs_plan_kernel
 // found in them (host/handoff_core.h's bmh_ho_plan_t fields).  Valid until the next call that uses d_c2r; nothing phase 2 allocates does.
+// A table mate rescue left in ctx->d_msw has the same form; pair_kmax: what its mates add (bmh_ho_pairs), 0 for single-end reads.
 struct ResidentRegs {
 	const unsigned long long *roff = nullptr; // n_reads + 1
 	const bmh_alnreg_t *reg = nullptr;
 	long long total = 0, kmax = 1, opool_cap = 0;
 	bool neg = false;
+	long long pair_kmax = 0;
 };
 // bmh_seed_chain_regs_batch's checks and its run for bmh_reads_sam_device (chain2reg.hip): the context's three switches are neither read
 // nor written, the de-duplication runs at o->mask_level_redun, drop-exact with MEM_F_NO_EXACT in o->flag, and the driver ends behind
@@ -272,14 +277,39 @@ int reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt
                      int min_seed_len, const char *who);
 int reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
                         int min_seed_len, const bmh_sam_opt_t *o, ResidentRegs *out);
+// The same run for bmh_pairs_sam_device: no plan over the table (mate rescue changes it first; out->kmax, opool_cap and neg stay as
+// they start), the bases kept for the rescue, and with `collect` mem_pestat's word per pair under *o, brought down in the wait that
+// brings the status words.  ctx->rs and what bmh_last_pestat_candidates answers are not touched.
+struct PairsPhase1 {
+	ResidentRegs regs;                        // in ctx->d_c2r
+	const uint8_t *pool = nullptr;            // in ctx->d_pbase: matesw_resident's form, nothing else writes that buffer
+	const unsigned long long *soff = nullptr; // n_reads + 1
+	std::vector<uint32_t> cand;               // n_reads / 2 words, with collect
+	long long regions_in = 0;                 // before the de-duplication
+	long long d2h_bytes = 0;                  // what the hand-off's one wait brought down
+};
+int pairs_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                        int min_seed_len, const bmh_sam_opt_t *o, bool collect, PairsPhase1 *out);
+// table_plan_kernel (chain2reg.hip) over any table of that form: regs_plan_kernel's fold (host/handoff_core.h) with the paired-end clause
+// and, n_sw not NULL, the sum of n_sw[0 .. n_reads / 2).  rec: kTablePlanRecBytes, part: table_plan_part_bytes(n_reads), both device
+// memory the caller owns; cap: the table's room in records; err: set to BMH_E_ARG where the offsets leave it.  Timed by ctx->ev_plan.
+constexpr size_t kTablePlanRecBytes = 64;
+size_t table_plan_part_bytes(int n_reads);
+int launch_table_plan(bmh_ctx *ctx, const bmh_sam_opt_t &o, int n_reads, const unsigned long long *d_roff, const bmh_alnreg_t *d_reg, unsigned long long cap,
+                      const int *d_n_sw, void *d_part, void *d_rec, int *d_err);
+// ... its record as it came down into *out (roff and reg are left alone) and *n_sw_sum; false: not every wave has reported, or a sum is negative
+bool table_plan_read(const void *h_rec, int n_reads, ResidentRegs *out, long long *n_sw_sum);
 // Mate rescue over a resident table (matesw.hip): reads 2p and 2p + 1 are mates, read k's bases d_pool[d_soff[k] .. d_soff[k + 1]) with 16
 // bytes of padding behind the last, its regions in.reg[in.roff[k] .. in.roff[k + 1]) (in.total of them; the other fields are not read).
 // Fills out->roff, out->reg and out->total, and *d_n_sw (n_pairs entries): all in ctx->d_msw, valid until the next call that uses that
 // buffer, so `in` must not lie there.  Between its first launch and its return the host reads the 64-byte plan record, 16 bytes per
 // round and the 16-byte total.  ctx->dstats and ctx->mt are the call's.  The caller holds the gate and has checked l_pac against the
-// resident reference.
+// resident reference.  plan_opt not NULL (bmh_pairs_sam_device): table_plan_kernel runs over the output table under *plan_opt and its
+// record comes down in the copy that brings the total: out's other fields and *n_sw_sum are filled from it, no wait is added, and
+// ctx->mt.mid_bytes counts its 64 bytes.
 int matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t *d_pool, const unsigned long long *d_soff, const ResidentRegs &in,
-                    const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, ResidentRegs *out, int **d_n_sw);
+                    const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, ResidentRegs *out, int **d_n_sw,
+                    const bmh_sam_opt_t *plan_opt = nullptr, long long *n_sw_sum = nullptr);
 // every host wait for a stream goes through here (bmh_set_wait_mode)
 extern int g_wait_blocking;
 inline hipError_t stream_wait(bmh_ctx *ctx, hipStream_t s)

@@ -43,12 +43,16 @@ enum { C2R_NEXT_CHAIN = 0, C2R_NEXT_SEED = 1, C2R_DONE = 2 };
 // status words (uint32 index).  0..3 are what the host reads in the loop
 enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_DEDUP_REMOVED = 12, C2R_DROP_REMOVED = 14, C2R_STATUS_BYTES = 64 };
 
-struct C2rPlan { // regs_plan_kernel's record, right behind the status words: one copy brings both
+struct C2rPlan { // regs_plan_kernel's record, right behind the status words: one copy brings both.  Also table_plan_kernel's
 	bmh_ho_plan_t plan;
 	uint32_t ticket; // waves that have written their part
-	uint32_t rsv[7];
+	uint32_t rsv0;
+	int64_t pair_kmax; // bmh_ho_pairs over the table's mates, 0 from regs_plan_kernel
+	int64_t n_sw;      // table_plan_kernel's sum of the per-pair counts it was given, else 0
+	uint32_t rsv[2];
 };
-static_assert(sizeof(C2rPlan) == 64 && sizeof(bmh_ho_plan_t) == 32, "plan record");
+static_assert(sizeof(C2rPlan) == 64 && sizeof(bmh_ho_plan_t) == 32 && sizeof(C2rPlan) == kTablePlanRecBytes, "plan record");
+constexpr int kPlanPartWords = 8; // a wave's part: kmax, opool_cap, total, neg | pair_kmax << 32, n_sw, three spare words
 
 struct C2rChain { // one chain's record, 64 bytes
 	int64_t rmax0, rmax1;
@@ -89,7 +93,7 @@ struct C2rWs {
 	unsigned long long *nreg, *roff; // n_reads + 1: regions per read, their exclusive sums
 	uint32_t *cand;          // n_reads / 2 + 1: mem_pestat's word per pair (pestat_collect_kernel), right behind roff: one copy brings both
 	bmh_alnreg_t *out;       // ts: the compact regions
-	bmh_ho_plan_t *part;     // n_reads / 64 + 1: regs_plan_kernel's per-wave parts
+	long long *part;         // (n_reads / 64 + 1) x kPlanPartWords: regs_plan_kernel's per-wave parts
 };
 
 struct C2rSwRule { // what validate_sw (api.hip) checks per task of a host-fed batch
@@ -326,10 +330,69 @@ __global__ __launch_bounds__(64) void c2r_place_kernel(C2rIn in, C2rWs ws)
 
 // What phase 2 learns from a walk over the host's vectors, from the compact records instead (host/handoff_core.h): one lane per read
 // folds its vector, the wave folds its lanes with shuffles and writes its part, and one atomic per wave -- the ticket -- tells the last
-// wave to arrive that every part is there; it folds them into the record behind the status words.  Blocks are one wave.
+// wave to arrive that every part is there; it folds them into the record.  Blocks are one wave.  The fold and the ticket are one text
+// for the two kernels: regs_plan_kernel over phase 1's workspace, table_plan_kernel over any table with the paired-end clause.
+struct HoFold {
+	bmh_ho_plan_t p;
+	int64_t pk;    // bmh_ho_pair's fold
+	long long nsw; // a plain sum beside it
+};
+
+__device__ __forceinline__ void ho_fold_merge(HoFold &x, const HoFold &q)
+{
+	bmh_ho_merge(&x.p, &q.p), bmh_ho_pairs_merge(&x.pk, q.pk), x.nsw += q.nsw;
+}
+
+__device__ __forceinline__ void ho_wave_fold(HoFold &x)
+{
+	for (int d = 32; d >= 1; d >>= 1) {
+		HoFold q;
+		q.p.kmax = __shfl_xor((long long)x.p.kmax, d), q.p.opool_cap = __shfl_xor((long long)x.p.opool_cap, d);
+		q.p.total = __shfl_xor((long long)x.p.total, d), q.p.neg = __shfl_xor(x.p.neg, d), q.p.rsv = 0;
+		q.pk = __shfl_xor((long long)x.pk, d), q.nsw = __shfl_xor(x.nsw, d);
+		ho_fold_merge(x, q);
+	}
+}
+
+// every lane of the block's one wave arrives here with its own fold; part: the launch's parts, rec: its record with the ticket at 0
+__device__ __forceinline__ void ho_plan_finish(HoFold x, long long *part, C2rPlan *rec)
+{
+	const int lane = threadIdx.x;
+	ho_wave_fold(x);
+	uint32_t ticket = 0;
+	// The parts cross compute units and dies inside one launch: written through with agent-scope stores and released before the
+	// ticket, read with agent-scope loads behind the ticket's acquire -- never from a cache line this unit may hold.
+	if (lane == 0) {
+		long long *w = part + kPlanPartWords * (size_t)blockIdx.x;
+		__hip_atomic_store(w, (long long)x.p.kmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(w + 1, (long long)x.p.opool_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(w + 2, (long long)x.p.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(w + 3, (long long)(uint32_t)x.p.neg | (long long)x.pk << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (pk has 21 bits)
+		__hip_atomic_store(w + 4, x.nsw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__threadfence();
+		ticket = atomicAdd(&rec->ticket, 1u);
+	}
+	ticket = (uint32_t)__shfl((int)ticket, 0);
+	if (ticket != gridDim.x - 1) return;
+	__threadfence();
+	HoFold t = {BMH_HO_PLAN_INIT, BMH_HO_PAIRS_INIT, 0};
+	for (unsigned b = (unsigned)lane; b < gridDim.x; b += 64) {
+		const long long *w = part + kPlanPartWords * (size_t)b;
+		HoFold q;
+		q.p.kmax = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), q.p.opool_cap = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		q.p.total = __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const long long w3 = __hip_atomic_load(w + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		q.p.neg = (int32_t)(w3 & 0xffffffffll), q.p.rsv = 0, q.pk = w3 >> 32;
+		q.nsw = __hip_atomic_load(w + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		ho_fold_merge(t, q);
+	}
+	ho_wave_fold(t);
+	if (lane == 0) rec->plan = t.p, rec->pair_kmax = t.pk, rec->n_sw = t.nsw;
+}
+
 __global__ __launch_bounds__(64) void regs_plan_kernel(bmh_sam_opt_t o, int n_reads, unsigned long long ts, C2rWs ws)
 {
-	const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x;
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
 	C2rPlan *rec = (C2rPlan *)((uint8_t *)ws.status + C2R_STATUS_BYTES);
 	bmh_ho_plan_t p = BMH_HO_PLAN_INIT;
 	if (r < n_reads) {
@@ -337,41 +400,59 @@ __global__ __launch_bounds__(64) void regs_plan_kernel(bmh_sam_opt_t o, int n_re
 		if (at > ts || n > ts - at) c2r_fail(ws.status, BMH_E_ARG); // (c2r_place_kernel has said so already; nothing is read)
 		else bmh_ho_read(&o, ws.out + at, (int64_t)n, &p);
 	}
-	auto fold = [&](bmh_ho_plan_t &x) {
-		for (int d = 32; d >= 1; d >>= 1) {
-			bmh_ho_plan_t q;
-			q.kmax = __shfl_xor((long long)x.kmax, d), q.opool_cap = __shfl_xor((long long)x.opool_cap, d);
-			q.total = __shfl_xor((long long)x.total, d), q.neg = __shfl_xor(x.neg, d), q.rsv = 0;
-			bmh_ho_merge(&x, &q);
-		}
-	};
-	fold(p);
-	uint32_t ticket = 0;
-	// The parts cross compute units and dies inside one launch: written through with agent-scope stores and released before the
-	// ticket, read with agent-scope loads behind the ticket's acquire -- never from a cache line this unit may hold.
-	if (lane == 0) {
-		long long *w = (long long *)&ws.part[blockIdx.x];
-		__hip_atomic_store(w, (long long)p.kmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 1, (long long)p.opool_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 2, (long long)p.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 3, (long long)(uint32_t)p.neg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__threadfence();
-		ticket = atomicAdd(&rec->ticket, 1u);
+	ho_plan_finish(HoFold{p, BMH_HO_PAIRS_INIT, 0}, ws.part, rec);
+}
+
+// The same over any table in c2r_place_kernel's form -- read r's regions at reg[roff[r] .. roff[r + 1]), cap records of room -- with the
+// paired-end clause: a first mate (bmh_ho_first_mate) learns its mate's count from the lane beside it and folds the pair, and adds its
+// pair's n_sw where the caller has such counts.  A read whose offsets leave the table sets *err and is not looked at.
+__global__ __launch_bounds__(64) void table_plan_kernel(bmh_sam_opt_t o, int n_reads, const unsigned long long *__restrict__ roff, const bmh_alnreg_t *__restrict__ reg,
+                                                        unsigned long long cap, const int *__restrict__ n_sw, long long *part, C2rPlan *rec, int *err)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
+	HoFold x = {BMH_HO_PLAN_INIT, BMH_HO_PAIRS_INIT, 0};
+	long long n = 0;
+	if (r < n_reads) {
+		const unsigned long long at = roff[r], end = roff[r + 1];
+		if (at > end || end > cap) atomicCAS(err, 0, BMH_E_ARG);
+		else n = (long long)(end - at), bmh_ho_read(&o, reg + at, (int64_t)n, &x.p);
 	}
-	ticket = (uint32_t)__shfl((int)ticket, 0);
-	if (ticket != gridDim.x - 1) return;
-	__threadfence();
-	bmh_ho_plan_t t = BMH_HO_PLAN_INIT;
-	for (unsigned b = (unsigned)lane; b < gridDim.x; b += 64) {
-		const long long *w = (const long long *)&ws.part[b];
-		bmh_ho_plan_t q;
-		q.kmax = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), q.opool_cap = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		q.total = __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		q.neg = (int32_t)(__hip_atomic_load(w + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffffffll), q.rsv = 0;
-		bmh_ho_merge(&t, &q);
+	const long long mate = __shfl_xor(n, 1); // (64 is even: mates share a wave, and every lane of it is here)
+	if (bmh_ho_first_mate(r, n_reads)) {
+		bmh_ho_pair((int64_t)n, (int64_t)mate, &x.pk);
+		if (n_sw) x.nsw = n_sw[r >> 1];
 	}
-	fold(t);
-	if (lane == 0) rec->plan = t;
+	ho_plan_finish(x, part, rec);
+}
+
+size_t table_plan_part_bytes(int n_reads) { return ((size_t)n_reads / 64 + 1) * kPlanPartWords * sizeof(long long); }
+
+int launch_table_plan(bmh_ctx *ctx, const bmh_sam_opt_t &o, int n_reads, const unsigned long long *d_roff, const bmh_alnreg_t *d_reg, unsigned long long cap,
+                      const int *d_n_sw, void *d_part, void *d_rec, int *d_err)
+{
+	hipStream_t s = ctx->stream;
+	BMH_HIP(ctx, hipMemsetAsync(d_rec, 0, sizeof(C2rPlan), s)); // the ticket starts at 0
+	if (ctx->timing) {
+		for (hipEvent_t &e : ctx->ev_plan)
+			if (!e) BMH_HIP(ctx, hipEventCreate(&e));
+		BMH_HIP(ctx, hipEventRecord(ctx->ev_plan[0], s));
+	}
+	hipLaunchKernelGGL(table_plan_kernel, dim3((unsigned)std::max((n_reads + 63) / 64, 1)), dim3(64), 0, s, o, n_reads, d_roff, d_reg, cap, d_n_sw, (long long *)d_part,
+	                   (C2rPlan *)d_rec, d_err);
+	BMH_HIP(ctx, hipGetLastError());
+	if (ctx->timing) BMH_HIP(ctx, hipEventRecord(ctx->ev_plan[1], s));
+	return BMH_OK;
+}
+
+bool table_plan_read(const void *h_rec, int n_reads, ResidentRegs *out, long long *n_sw_sum)
+{
+	C2rPlan plan;
+	memcpy(&plan, h_rec, sizeof(plan));
+	if (plan.ticket != (uint32_t)std::max((n_reads + 63) / 64, 1) || plan.plan.total < 0 || plan.plan.opool_cap < 0 || plan.pair_kmax < 0 || plan.n_sw < 0) return false;
+	out->total = (long long)plan.plan.total, out->kmax = (long long)plan.plan.kmax, out->opool_cap = (long long)plan.plan.opool_cap;
+	out->neg = plan.plan.neg != 0, out->pair_kmax = (long long)plan.pair_kmax;
+	if (n_sw_sum) *n_sw_sum = (long long)plan.n_sw;
+	return true;
 }
 
 // mem_sort_and_dedup (host/dedup_core.h, the text bmh_sort_and_dedup runs) on read r's slice of a region array, one lane per read.
@@ -428,7 +509,7 @@ struct C2rLayout {
 		slot = take(ts * 4), tasks = take(ts * sizeof(bmh_seed_task_t)), res = take(ts * sizeof(bmh_seed_result_t));
 		swt = take(tc * sizeof(bmh_sw_task_t)), swr = take(tc * sizeof(bmh_sw_result_t)), reg = take(ts * sizeof(bmh_alnreg_t));
 		nreg = take((n + 1) * 8), roff = take((n + 1) * 8 + (n / 2 + 1) * 4), cand = roff + (n + 1) * 8; // (the words share roff's block)
-		out = take(ts * sizeof(bmh_alnreg_t)), part = take((n / 64 + 1) * sizeof(bmh_ho_plan_t)), total = o;
+		out = take(ts * sizeof(bmh_alnreg_t)), part = take((n / 64 + 1) * kPlanPartWords * sizeof(long long)), total = o;
 	}
 };
 
@@ -450,15 +531,19 @@ int c2r_abandon(bmh_ctx *ctx, int rc)
 
 // The driver proper, on the context's stream.  The workspace lies at the start of ctx->d_c2r (a caller that keeps its own input there
 // puts it behind C2rLayout::total and has made the buffer large enough).  regs[r] receive malloc'd arrays with n == m.
-// post: what runs behind the replay loop, the context's switches for every call but bmh_reads_sam_device.  post.resident: the driver
+// post: what runs behind the replay loop, the context's switches for every call but the two sessions.  post.resident: the driver
 // ends behind c2r_place_kernel and regs_plan_kernel (under *post.plan_opt), regs is not looked at, and *post.resident says where the
-// records lie and what the plan kernel found.
+// records lie and what the plan kernel found.  post.pairs (bmh_pairs_sam_device; resident is its regs): no plan kernel -- the total
+// comes down beside the status words -- the words are collected under *post.collect_opt, not the context's options, and come down
+// in the same wait into post.pairs->cand; ctx->rs and the context's words are left alone.
 struct C2rPost {
 	bool dedup;
 	float mask;
 	bool drop, collect;
 	ResidentRegs *resident = nullptr;
 	const bmh_sam_opt_t *plan_opt = nullptr;
+	PairsPhase1 *pairs = nullptr;
+	const bmh_sam_opt_t *collect_opt = nullptr;
 };
 
 // (a NULL context is c2r_check's to refuse)
@@ -474,12 +559,19 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	const C2rLayout L((size_t)n, (size_t)in.tc, (size_t)in.ts);
 	int rc;
 	if ((rc = ensure(ctx, ctx->d_c2r, L.total))) return rc;
-	if ((rc = ensure_host(ctx, ctx->h_down, 256))) return rc;
+	const size_t b_words = post.pairs && post.collect ? ((size_t)n / 2) * 4 : 0; // the session's words come down behind the status record
+	if (post.pairs) try {
+			post.pairs->cand.assign((size_t)n / 2, 0u);
+		} catch (const std::bad_alloc &) {
+			ctx->last_error = "chains to regions: out of host memory for the insert-size words";
+			return BMH_E_NOMEM;
+		}
+	if ((rc = ensure_host(ctx, ctx->h_down, 256 + b_words))) return rc;
 	uint8_t *d = (uint8_t *)ctx->d_c2r.p;
 	const C2rWs ws{(uint32_t *)(d + L.status), (C2rChain *)(d + L.chn), (C2rState *)(d + L.state), (uint64_t *)(d + L.srt), (uint32_t *)(d + L.slot),
 	               (bmh_seed_task_t *)(d + L.tasks), (bmh_seed_result_t *)(d + L.res), (bmh_sw_task_t *)(d + L.swt), (bmh_sw_result_t *)(d + L.swr),
 	               (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (uint32_t *)(d + L.cand),
-	               (bmh_alnreg_t *)(d + L.out), (bmh_ho_plan_t *)(d + L.part)};
+	               (bmh_alnreg_t *)(d + L.out), (long long *)(d + L.part)};
 	const bmh_params_t &p = ctx->params;
 	const C2rSwRule sw{msl, ctx->dev.max_mat, ctx->wide_sw ? 1 : 0, sw_byte_gaps_wrap(p) ? 1 : 0};
 	const unsigned rb = (unsigned)((n + 63) / 64);
@@ -535,7 +627,7 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 		return rc;
 	// with either of its switches on: mem_test_and_remove_exact on the survivors, then mem_pestat's word per pair from what is left
 	const bool collect = post.collect, drop = post.drop;
-	if ((collect || drop) && (rc = launch_pestat_collect(ctx, ws.reg, in.soff, ws.nreg, in.len, n, in.ts, ctx->pestat_opt, l_pac, p.a, drop,
+	if ((collect || drop) && (rc = launch_pestat_collect(ctx, ws.reg, in.soff, ws.nreg, in.len, n, in.ts, post.collect_opt ? *post.collect_opt : ctx->pestat_opt, l_pac, p.a, drop,
 	                                                     collect ? ws.cand : nullptr, (unsigned long long *)&ws.status[C2R_DROP_REMOVED],
 	                                                     (int *)&ws.status[C2R_ERR])))
 		return rc;
@@ -545,7 +637,13 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	BMH_HIP(ctx, hipGetLastError());
 	unsigned long long tr, u64s[4], removed, dropped;
 	C2rPlan plan{};
-	if (post.resident) { // the status words and the plan in one record: the one wait of the hand-off
+	if (post.pairs) { // the status words, the total and the words: the one wait of the hand-off; the plan waits for the table after rescue
+		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
+		BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
+		if (b_words) BMH_HIP(ctx, hipMemcpyAsync(h + 64, ws.cand, b_words, hipMemcpyDeviceToHost, s));
+		BMH_HIP(ctx, stream_wait(ctx, s));
+		memcpy(&tr, h + 16, 8);
+	} else if (post.resident) { // the status words and the plan in one record: the one wait of the hand-off
 		if (ctx->timing) {
 			for (hipEvent_t &e : ctx->ev_plan)
 				if (!e) BMH_HIP(ctx, hipEventCreate(&e));
@@ -579,7 +677,16 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	}
 	float pestat_ms = -1.f;
 	if ((collect || drop) && ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&pestat_ms, ctx->ev_pestat[0], ctx->ev_pestat[1]));
-	if (post.resident) { // nothing of the regions comes down and no vector is made
+	if (post.pairs) { // nothing of the regions comes down and no vector is made
+		PairsPhase1 &P = *post.pairs;
+		P.regs = ResidentRegs{};
+		P.regs.roff = ws.roff, P.regs.reg = ws.out, P.regs.total = (long long)tr;
+		P.regions_in = (long long)(tr + dropped + removed), P.d2h_bytes = (long long)(C2R_STATUS_BYTES + 8 + b_words);
+		if (b_words) memcpy(P.cand.data(), h + 64, b_words);
+		if (drop) ctx->drop_exact_removed = (long long)dropped;
+		return BMH_OK;
+	}
+	if (post.resident) {
 		ResidentRegs &R = *post.resident;
 		R.roff = ws.roff, R.reg = ws.out;
 		R.total = (long long)tr, R.kmax = (long long)plan.plan.kmax, R.opool_cap = (long long)plan.plan.opool_cap, R.neg = plan.plan.neg != 0;
@@ -654,7 +761,7 @@ int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads,
 		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on and n_reads is odd: reads 2p and 2p+1 are mates";
 		return BMH_E_ARG;
 	}
-	if (post.collect && ctx->pestat_opt.max_ins > BMH_PS_MAX_INS) {
+	if (post.collect && (post.collect_opt ? post.collect_opt->max_ins : ctx->pestat_opt.max_ins) > BMH_PS_MAX_INS) {
 		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on with max_ins >= 2^30, which the word cannot hold";
 		return BMH_E_RANGE;
 	}
@@ -694,7 +801,35 @@ struct FusedArgs {
 	bmh_alnreg_v *regs;
 	bmh_driver_stats_t *st;
 	C2rPost post;
+	size_t bases = 0; // post.pairs: the bases of all reads
 };
+
+// The bases where nothing between here and mate rescue's last round writes: seeding's pool lies in ctx->d_scratch, which launch_sw may
+// reallocate or overwrite, and the rescue's rounds call launch_sw.  ctx->d_pbase is this copy's alone: [soff[n + 1] | the reads | 16
+// zero bytes], matesw_resident's form.  Seeding laid the reads end to end in read order, so the pool moves as one copy.
+__global__ __launch_bounds__(256) void bases_soff_kernel(const uint64_t *__restrict__ read_off, const int *__restrict__ len, int n, unsigned long long *__restrict__ soff)
+{
+	const int r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= n) return;
+	soff[r] = read_off[r];
+	if (r == n - 1) soff[n] = read_off[r] + (unsigned long long)len[r];
+}
+
+int bases_keep(bmh_ctx *ctx, const DevSeedTables &t, size_t bytes, PairsPhase1 *out)
+{
+	const size_t n = (size_t)t.n_reads, o_pool = al256((n + 1) * 8);
+	int rc;
+	if ((rc = ensure(ctx, ctx->d_pbase, o_pool + bytes + 16))) return rc;
+	uint8_t *d = (uint8_t *)ctx->d_pbase.p;
+	hipStream_t s = ctx->stream;
+	if (n) hipLaunchKernelGGL(bases_soff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.read_off, t.len, (int)n, (unsigned long long *)d);
+	else BMH_HIP(ctx, hipMemsetAsync(d, 0, 8, s));
+	BMH_HIP(ctx, hipGetLastError());
+	if (bytes) BMH_HIP(ctx, hipMemcpyAsync(d + o_pool, t.pool, bytes, hipMemcpyDeviceToDevice, s));
+	BMH_HIP(ctx, hipMemsetAsync(d + o_pool + bytes, 0, 16, s));
+	out->soff = (const unsigned long long *)d, out->pool = d + o_pool;
+	return BMH_OK;
+}
 
 // seeding's tables -> compact chains -> regions, all where they lie on the device; the reads are the pool seeding uploaded
 int fused_cb(bmh_ctx *ctx, const DevSeedTables &t, void *user)
@@ -708,6 +843,7 @@ int fused_cb(bmh_ctx *ctx, const DevSeedTables &t, void *user)
 	const C2rIn in{n, t.read_off, t.len, dc.coff, dc.soff, dc.cn, dc.seeds, dc.tc, dc.ts, dc.n_keys};
 	long long before = 0;
 	if ((rc = c2r_run(ctx, u->l_pac, t.pool, in, u->lmax, u->msl, u->regs, u->st, u->post, &before))) return rc;
+	if (u->post.pairs && (rc = bases_keep(ctx, t, u->bases, u->post.pairs))) return rc;
 	ctx->cstats = bmh_chain_stats_t{n, before, (int64_t)dc.tc, (int64_t)dc.ts, (int64_t)dc.n_equal, dc.kernel_ms}; // of a successful call only
 	return BMH_OK;
 }
@@ -830,6 +966,21 @@ int bmh::reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_c
 	int lmax = 1;
 	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
 	FusedArgs u{co, l_pac, lmax, min_seed_len, nullptr, &st, reads_sam_post(o, out)};
+	const int rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
+	ctx->dstats = st;
+	return rc;
+}
+
+int bmh::pairs_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
+                             int min_seed_len, const bmh_sam_opt_t *o, bool collect, PairsPhase1 *out)
+{
+	bmh_driver_stats_t st{};
+	ctx->dstats = st;
+	int lmax = 1;
+	size_t bytes = 0;
+	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq), bytes += (size_t)reads[r].l_seq;
+	const C2rPost post{true, o->mask_level_redun, (o->flag & BMH_MEM_F_NO_EXACT) != 0, collect, &out->regs, nullptr, out, o};
+	FusedArgs u{co, l_pac, lmax, min_seed_len, nullptr, &st, post, bytes};
 	const int rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
 	ctx->dstats = st;
 	return rc;

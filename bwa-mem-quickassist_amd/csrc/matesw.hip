@@ -738,7 +738,8 @@ struct MtEvents { // the three kernel groups' brackets in timing mode
 } // namespace
 
 int bmh::matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t *d_pool, const unsigned long long *d_soff, const ResidentRegs &in,
-                         const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, ResidentRegs *out, int **d_n_sw)
+                         const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, ResidentRegs *out, int **d_n_sw,
+                         const bmh_sam_opt_t *plan_opt, long long *n_sw_sum)
 {
 	static const char *who = "bmh_matesw_table_device";
 	bmh_driver_stats_t st{};
@@ -801,7 +802,10 @@ int bmh::matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t
 		at += al256(bytes);
 		return x;
 	};
-	const size_t o_act = take(n_act * 4), o_roff = take((2 * np + 1) * 8), o_nsw = take(np * 4), o_tot = take(sizeof(MtTotal)), o_reg = take(out_cap * sizeof(bmh_alnreg_t));
+	// (the plan record of a caller with plan_opt lies right behind the total: one copy brings both)
+	const size_t b_tot = sizeof(MtTotal) + (plan_opt ? kTablePlanRecBytes : 0);
+	const size_t o_act = take(n_act * 4), o_roff = take((2 * np + 1) * 8), o_nsw = take(np * 4), o_tot = take(b_tot), o_reg = take(out_cap * sizeof(bmh_alnreg_t));
+	const size_t o_ppart = take(plan_opt ? table_plan_part_bytes(2 * n_pairs) : 0);
 	if ((rc = ensure(ctx, ctx->d_msw, at))) return rc;
 	uint8_t *d = (uint8_t *)ctx->d_msw.p;
 	if ((const uint8_t *)in.reg >= d && (const uint8_t *)in.reg < d + ctx->d_msw.cap) return BMH_E_ARG; // the input must not lie in the output's buffer
@@ -839,14 +843,17 @@ int bmh::matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t
 		                   (unsigned long long)arena_n, (const unsigned long long *)d_roff_out, d_reg_out, (unsigned long long)out_cap);
 		BMH_HIP(ctx, hipGetLastError());
 		if ((e = ev.end(2))) return e;
-		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_down.p, d_tot, sizeof(MtTotal), hipMemcpyDeviceToHost, s));
+		// what phase 2 must know of the table just made (table_plan_kernel, chain2reg.hip); an offset past the table's room is the total's error
+		if (plan_opt && (e = launch_table_plan(ctx, *plan_opt, 2 * n_pairs, d_roff_out, d_reg_out, (unsigned long long)out_cap, d_nsw_out, d + o_ppart, d_tot + 1, &d_tot->err)))
+			return e;
+		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_down.p, d_tot, b_tot, hipMemcpyDeviceToHost, s));
 		BMH_HIP(ctx, stream_wait(ctx, s));
 		return BMH_OK;
 	}();
 	mt.mid_bytes += 16 * (int64_t)readbacks, mt.waits += readbacks;
 	ctx->dstats = st;
 	if (rc) return msw_abandon(ctx, rc);
-	mt.mid_bytes += (int64_t)sizeof(MtTotal), ++mt.waits;
+	mt.mid_bytes += (int64_t)b_tot, ++mt.waits; // (with the plan record behind the total where the caller asked for one)
 	const MtTotal tot = *(const MtTotal *)ctx->h_down.p;
 	if (tot.err || tot.total > out_cap) { // cannot happen
 		ctx->last_error = "mate rescue on the device: the device's counts are inconsistent";
@@ -856,6 +863,10 @@ int bmh::matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t
 	if ((rc = ev.ms(2, &mt.merge_ms))) return rc;
 	mt.regions_out = (int64_t)tot.total;
 	*out = ResidentRegs{};
+	if (plan_opt && (!table_plan_read((const uint8_t *)ctx->h_down.p + sizeof(MtTotal), 2 * n_pairs, out, n_sw_sum) || out->total != (long long)tot.total)) { // cannot happen
+		ctx->last_error = "mate rescue on the device: the plan over its table is inconsistent";
+		return BMH_E_ARG;
+	}
 	out->roff = d_roff_out, out->reg = d_reg_out, out->total = (long long)tot.total;
 	*d_n_sw = d_nsw_out;
 	return BMH_OK;

@@ -9,6 +9,9 @@
  *   bmh_ho_read          one read's vector folded into a bmh_ho_plan_t
  *   bmh_ho_merge         two plans into one: the maximum, the sums, the flag
  *   bmh_ho_pair_kmax     the paired-end clause: the square of a pair's region count, for decide_table_sizes' callers with mates
+ *   bmh_ho_pair, bmh_ho_pairs, bmh_ho_pairs_merge   the clause folded over a batch of mates: one pair, a slice of a region table, two
+ *                        folds into one.  table_plan_kernel (csrc/chain2reg.hip) folds it over the table mate rescue leaves on the device
+ *                        (bmh_pairs_sam_device); tests/pairs_plan_core_main.c runs it stand-alone
  * A plan starts as BMH_HO_PLAN_INIT.  Integer arithmetic only, nothing is allocated and no libc is called.  Under hipcc the routines
  * are __host__ __device__ and always inlined.
  */
@@ -80,6 +83,33 @@ BMH_HO_HD static inline int64_t bmh_ho_pair_kmax(int64_t n0, int64_t n1)
 {
 	const int64_t m = n0 + n1;
 	return m > 1024 ? BMH_HO_TAB_MAX : m * m + 1;
+}
+
+/* The clause folded over a batch: *pk starts as BMH_HO_PAIRS_INIT (no pair seen: the clause adds nothing), a pair raises it to its
+ * bmh_ho_pair_kmax, and two folds merge to their maximum -- in any order and grouping.  At most BMH_HO_TAB_MAX + 1: 21 bits. */
+#define BMH_HO_PAIRS_INIT 0
+
+BMH_HO_HD static inline void bmh_ho_pair(int64_t n0, int64_t n1, int64_t *pk)
+{
+	const int64_t v = bmh_ho_pair_kmax(n0, n1);
+	if (v > *pk) *pk = v;
+}
+
+BMH_HO_HD static inline void bmh_ho_pairs_merge(int64_t *pk, int64_t q)
+{
+	if (q > *pk) *pk = q;
+}
+
+/* read r of n_reads speaks for its pair: it is even and its mate exists.  An odd trailing read has no pair and adds nothing */
+BMH_HO_HD static inline int bmh_ho_first_mate(int64_t r, int64_t n_reads) { return !(r & 1) && r + 1 < n_reads; }
+
+/* Reads [r0, r1) of a table whose read r holds roff[r + 1] - roff[r] regions, n_reads in all: every first mate among them folds its
+ * pair, whichever slice its mate falls into */
+BMH_HO_HD static inline void bmh_ho_pairs(const uint64_t *roff, int64_t r0, int64_t r1, int64_t n_reads, int64_t *pk)
+{
+	int64_t r;
+	for (r = r0; r < r1; ++r)
+		if (bmh_ho_first_mate(r, n_reads)) bmh_ho_pair((int64_t)(roff[r + 1] - roff[r]), (int64_t)(roff[r + 2] - roff[r + 1]), pk);
 }
 
 #endif

@@ -1207,6 +1207,73 @@ typedef struct bmh_reads_sam_stats {
 } bmh_reads_sam_stats_t; /* 64 bytes */
 int bmh_last_reads_sam_stats(const bmh_ctx_t *ctx, bmh_reads_sam_stats_t *st);
 
+/* ---- Paired-end reads to SAM text as one device session: bmh_reads_sam_device's two phases with the insert-size statistics and mate
+ * rescue between them, and the region table on the device from the kernel that makes it, through the rescue that grows it, to the
+ * kernel that sorts it.  Reads 2p and 2p + 1 are mates.  *text / text_off[0..n] are byte for byte what this composition gives on one
+ * context:
+ *   bmh_seed_chain_regs_batch(so, co, bns->l_pac, n, reads, min_seed_len, regs), reads[i] = seqs[i]'s bases, with
+ *       bmh_ctx_set_regs_dedup on at o->mask_level_redun, bmh_ctx_set_regs_drop_exact on exactly when o->flag has MEM_F_NO_EXACT (0x40)
+ *       and bmh_ctx_set_pestat_collect on under *o exactly when pes0 is NULL, then
+ *   pes = pes0 if it is given (the caller's table: -I, or the table of a chunk the caller already has), else
+ *       bmh_pestat_from_candidates(o, n / 2, that call's words, pes, quiet): the table of exactly this call's reads, then
+ *   bmh_matesw_device(l_pac, n / 2, reads, regs, pes, mo, o->mask_level_redun, n_sw), then
+ *   bmh_phase2_text_device(o, bns, pac, pes, id0, n, seqs, regs, rg_id, text, text_off).
+ * pes_out (nullable) receives the table that was used.
+ *   phase 1       bmh_reads_sam_device's, without the plan over its table.  Its status words and the table's total come down in one
+ *                 wait; with pes0 NULL the insert-size words, 4 bytes per pair, come down in the same wait
+ *   the barrier   the host makes the table from the words (bmh_pestat_from_candidates's arithmetic): inside the call, no wait of its own
+ *   the rescue    bmh_matesw_table_device's kernels over phase 1's table where it lies, against the bases kept in a buffer of their own
+ *                 (copied on the stream, device to device, from the pool seeding uploaded).  The table it leaves stays on the device
+ *   the plan      table_plan_kernel, one lane per read over the table after rescue: what regs_plan_kernel finds, and the paired-end
+ *                 clause (the square of a pair's region count).  Its 64-byte record comes down with rescue's final 16-byte record
+ *   phase 2       bmh_phase2_text_device's session from those numbers, the offsets and regions copied device to device
+ * Nothing of the regions crosses the bus in either direction.  The bases still go up a second time, inside pass C's per-read pool.
+ * The call neither reads nor changes the context's bmh_ctx_set_regs_dedup, bmh_ctx_set_regs_drop_exact and bmh_ctx_set_pestat_collect
+ * switches (nor what bmh_last_pestat_candidates answers); it honours bmh_ctx_set_wide_extension, bmh_ctx_set_wide_sw and
+ * bmh_ctx_set_region_long as the composition does.  Needs what the composition needs: the parameters, the FM-index, the resident 2-bit
+ * reference with this pac, the sequence table and the sequence names: BMH_E_ARG without any of them.
+ *   BMH_E_ARG    before anything runs: a NULL ctx, so, co, mo, o, bns, text or text_off; o->flag without BMH_MEM_F_PE; an odd n; mates
+ *                whose names differ; what either phase refuses of n, seqs, so, co or o
+ *   BMH_E_RANGE  before anything runs: a read longer than 65535 bases; o->max_ins >= 2^30 with pes0 NULL (the word cannot hold it).
+ *                After phase 1 and before phase 2's upload: a pair table past 1 << 20 entries (before rescue runs); rescue's per-read
+ *                refusals, in bmh_matesw_device's words; what bmh_phase2_text_device refuses there (a log table past 1 << 20 entries, a
+ *                negative table index, slot addresses past 32 bits); from the kernels: as in the composition
+ *   BMH_OK       for n == 0 with a 1-byte *text and text_off[0] = 0, nothing runs (pes_out: pes0, or all four orientations failed)
+ * A table in which all four orientations failed is no error: rescue has no active pair then and the session runs through.
+ * All or nothing: on any error *text, text_off and pes_out are untouched, and the context stays usable.
+ * Afterwards bmh_chain_stats, bmh_last_dedup_stats and bmh_last_drop_exact_stats are valid as after bmh_seed_chain_regs_batch,
+ * bmh_last_matesw_table_stats as after bmh_matesw_table_device (its mid_bytes with the plan record's 64 bytes, which ride on its last
+ * copy) and bmh_last_phase2_text_stats as after bmh_phase2_text_device.
+ * bmh_driver_stats holds the rescue's numbers, as after bmh_matesw_table_device (rounds, Smith-Waterman tasks; pool_bytes stays 0: the
+ * bases did not go up for it); phase 1's extension counts are not kept. */
+int bmh_pairs_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_matesw_opt_t *mo,
+                         const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes0,
+                         bmh_pestat_t pes_out[4] /* nullable */, int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id, char **text,
+                         int64_t *text_off);
+/* Of the last bmh_pairs_sam_device call on this context that got as far as the plan over rescue's table; all -1 before the first.
+ *   reads, pairs          of the call
+ *   regions_in, regions   before and after the de-duplication plus drop-exact
+ *   regions_out           after rescue
+ *   n_sw                  mem_matesw's Smith-Waterman count, summed over the pairs
+ *   kmax, pair_kmax, opool_cap   what table_plan_kernel found: the largest index of the log table the regions ask for (at least 1), the
+ *                         largest bmh_ho_pair_kmax of a pair, the oriented pool's capacity
+ *   mid_d2h_bytes         bytes that came down between phase 1's last replay round and phase 2's upload: 72 (phase 1's status words and
+ *                         total) + 64 (rescue's plan) + 16 per rescue round + 80 (rescue's total and the plan record), and 4 per pair with
+ *                         pes0 NULL: nothing that grows with the regions
+ *   mid_h2d_bytes         bytes that went up in the same span: 0
+ *   waits_mid             host waits in the same span: 3 + rescue's rounds, that is 1 + bmh_last_matesw_table_stats' waits
+ *   pes_given             1 if the caller supplied the table
+ *   plan_ms               table_plan_kernel's milliseconds with bmh_set_kernel_timing on, else -1
+ *   neg_index             1 where a region asked for a negative table index (the call then returned BMH_E_RANGE), else 0 */
+typedef struct bmh_pairs_sam_stats {
+	int64_t reads, pairs, regions_in, regions, regions_out, n_sw;
+	int64_t kmax, pair_kmax, opool_cap, mid_d2h_bytes, mid_h2d_bytes;
+	int32_t waits_mid, pes_given;
+	float plan_ms;
+	int32_t neg_index, rsv_[6];
+} bmh_pairs_sam_stats_t; /* 128 bytes */
+int bmh_last_pairs_sam_stats(const bmh_ctx_t *ctx, bmh_pairs_sam_stats_t *st);
+
 #ifdef __cplusplus
 }
 #endif
