@@ -1671,7 +1671,7 @@ void bmh_pp_fill_term_(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const in
 
 // What the tables of a pass A on the device must reach (bwamem_hip.h), before anything is uploaded: BMH_E_RANGE and *why where one
 // would pass 2^20 entries or an index is negative.  plan: the regions' part of it (host/handoff_core.h), from a walk over the caller's
-// vectors (decide_table_sizes below) or from regs_plan_kernel where the regions are on the device; pair_kmax: what the pairs add, 0 = none
+// vectors (decide_table_sizes below) or from table_plan_kernel where the regions are on the device; pair_kmax: what the pairs add, 0 = none
 static int decide_tables_from_plan(const bmh_sam_opt_t *o, const bmh_pestat_t *pes, const bmh_ho_plan_t &plan, long long pair_kmax, long long *kmax_,
                                    long long *n_term_, int64_t term_off[4], const char **why)
 {
@@ -2430,7 +2430,7 @@ struct Phase2Plan {
 	int64_t id0;
 };
 
-// ... from the caller's vectors or, res, from what regs_plan_kernel found.  The oriented pool is sized from the clamped lengths of every
+// ... from the caller's vectors or, res, from what table_plan_kernel found.  The oriented pool is sized from the clamped lengths of every
 // region: a sum the sort does not change, and a cut only shortens a region.  *why not NULL: the tables' refusal, before any upload.
 static int phase2_plan(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_pestat_t *pes, int64_t l_pac, int64_t id0, int n, const bmh_read_t *reads, const bmh_alnreg_v *regs,
                        const ResidentRegs *res, size_t total, Phase2Plan &P, const char **why)
@@ -3174,7 +3174,7 @@ static int phase2_text_redo(Phase2TextRun &S, const bmh_refidx_t *bns, const uin
 // The session.  The arguments are checked here; *early: the BMH_E_RANGE is a refusal before any upload (the decide tables, or slot
 // addresses past 32 bits), which bmh_sam_batch answers with its other routes.  Nothing of the caller's is written before the end.
 // The regions come from the caller's vectors, or -- res, regs being NULL -- from where phase 1 left them on the device with what
-// regs_plan_kernel found: their offsets and records are then copied on the stream into pass A's block instead of uploaded, and
+// table_plan_kernel found: their offsets and records are then copied on the stream into pass A's block instead of uploaded, and
 // everything from launch_decide on is the same.
 static int phase2_text_run(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                            int64_t id0, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const ResidentRegs *res, const char *rg_id, char **text,

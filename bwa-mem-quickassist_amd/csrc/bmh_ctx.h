@@ -194,7 +194,7 @@ struct bmh_ctx {
 	hipEvent_t ev_gather[2] = {};             // around reads_gather_kernel (timing mode)
 	bmh_phase2_text_stats_t pt = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1.f, -1.f, -1.f, -1.f, -1}; // of the last such call (bmh_last_phase2_text_stats)
 	// reads to SAM text with the regions resident between the phases (bmh_reads_sam_device: chain2reg.hip's hand-off, api.hip's session)
-	hipEvent_t ev_plan[2] = {};               // around regs_plan_kernel (timing mode)
+	hipEvent_t ev_plan[2] = {};               // around table_plan_kernel (timing mode)
 	bmh_reads_sam_stats_t rs = {-1, -1, -1, -1, -1, -1, -1, -1.f, -1, -1}; // of the last such call (bmh_last_reads_sam_stats)
 	DevBuf d_msw; // mate rescue on the device (matesw.hip): status words, counts, region arena, pair records, hits, reads, machines, tasks, results
 	// ... over a region table (matesw_resident): behind those the output table, offsets first, and n_sw per pair
@@ -260,7 +260,7 @@ typedef int (*SeedTablesFn)(bmh_ctx *ctx, const DevSeedTables &t, void *user);
 // bmh_seed_batch up to its device tables, then fn on them (on the context's stream, inside the same gate); returns fn's result.
 // Capacities grow inside; env BMH_CHAIN_INIT_CAP (test knob) starts them at that many entries.
 int seed_tables_device(bmh_ctx *ctx, const bmh_smem_opt_t *o, int max_occ, int n_reads, const bmh_read_t *reads, SeedTablesFn fn, void *user);
-// A batch's regions where c2r_place_kernel left them, in ctx->d_c2r: read r's at reg[roff[r] .. roff[r + 1]), and what regs_plan_kernel
+// A batch's regions where c2r_place_kernel left them, in ctx->d_c2r: read r's at reg[roff[r] .. roff[r + 1]), and what table_plan_kernel
 // found in them (host/handoff_core.h's bmh_ho_plan_t fields).  Valid until the next call that uses d_c2r; nothing phase 2 allocates does.
 // A table mate rescue left in ctx->d_msw has the same form; pair_kmax: what its mates add (bmh_ho_pairs), 0 for single-end reads.
 struct ResidentRegs {
@@ -272,7 +272,7 @@ struct ResidentRegs {
 };
 // bmh_seed_chain_regs_batch's checks and its run for bmh_reads_sam_device (chain2reg.hip): the context's three switches are neither read
 // nor written, the de-duplication runs at o->mask_level_redun, drop-exact with MEM_F_NO_EXACT in o->flag, and the driver ends behind
-// c2r_place_kernel and regs_plan_kernel: *out, and ctx->rs up to the hand-off.  reads_regs_check refuses before anything is uploaded.
+// c2r_place_kernel and table_plan_kernel: *out, and ctx->rs up to the hand-off.  reads_regs_check refuses before anything is uploaded.
 int reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
                      int min_seed_len, const char *who);
 int reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
@@ -290,9 +290,10 @@ struct PairsPhase1 {
 };
 int pairs_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
                         int min_seed_len, const bmh_sam_opt_t *o, bool collect, PairsPhase1 *out);
-// table_plan_kernel (chain2reg.hip) over any table of that form: regs_plan_kernel's fold (host/handoff_core.h) with the paired-end clause
-// and, n_sw not NULL, the sum of n_sw[0 .. n_reads / 2).  rec: kTablePlanRecBytes, part: table_plan_part_bytes(n_reads), both device
-// memory the caller owns; cap: the table's room in records; err: set to BMH_E_ARG where the offsets leave it.  Timed by ctx->ev_plan.
+// table_plan_kernel (chain2reg.hip) over any table of that form: host/handoff_core.h's fold per read with the paired-end clause and,
+// n_sw not NULL, the sum of n_sw[0 .. n_reads / 2).  rec: kTablePlanRecBytes, which the caller has zeroed on the stream (the ticket
+// starts at 0), part: table_plan_part_bytes(n_reads), both device memory the caller owns; cap: the table's room in records; err: set to
+// BMH_E_ARG where the offsets leave it.  Timed by ctx->ev_plan.
 constexpr size_t kTablePlanRecBytes = 64;
 size_t table_plan_part_bytes(int n_reads);
 int launch_table_plan(bmh_ctx *ctx, const bmh_sam_opt_t &o, int n_reads, const unsigned long long *d_roff, const bmh_alnreg_t *d_reg, unsigned long long cap,
@@ -310,6 +311,10 @@ bool table_plan_read(const void *h_rec, int n_reads, ResidentRegs *out, long lon
 int matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t *d_pool, const unsigned long long *d_soff, const ResidentRegs &in,
                     const bmh_pestat_t pes[4], const bmh_matesw_opt_t *o, float mask_level_redun, ResidentRegs *out, int **d_n_sw,
                     const bmh_sam_opt_t *plan_opt = nullptr, long long *n_sw_sum = nullptr);
+// After an error inside a driver's enqueued section (chain2reg.hip, matesw.hip): nothing of the call is left running, and the
+// extension and Smith-Waterman kernels' error flag is clean for the next call; rc and the context's error text stay the answer.
+int abandon_call(bmh_ctx *ctx, int rc);
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; } // the drivers' buffers are laid out in 256-byte steps
 // every host wait for a stream goes through here (bmh_set_wait_mode)
 extern int g_wait_blocking;
 inline hipError_t stream_wait(bmh_ctx *ctx, hipStream_t s)

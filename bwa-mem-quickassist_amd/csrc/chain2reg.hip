@@ -23,15 +23,19 @@
 //                       (api.hip) runs on a caller's vectors.
 //   gather              count -> scan -> place of the regions (each read wrote into its slice of the region arena, the soff prefix
 //                       sums: a read yields at most as many regions as it has kept seeds), then the counts and the compact records down.
-//   regs_plan_kernel    resident mode (bmh_reads_sam_device) instead of the download: the compact records and their offsets stay where
+//   table_plan_kernel   resident mode (bmh_reads_sam_device) instead of the download: the compact records and their offsets stay where
 //                       c2r_place_kernel left them, and one lane per read folds its vector into what phase 2 must know before its first
 //                       launch (host/handoff_core.h).  One 128-byte record -- the status words and the plan -- comes down: one wait.
+//                       The same kernel runs over the table mate rescue leaves (matesw.hip).
+// Behind c2r_place_kernel the driver has three tails, each chosen by its caller: vectors for the host, resident regions with the plan,
+// resident regions with the total and the insert-size words.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "wave_ticket.h"
 #include "../host/chain2aln_core.h"
 #include "../host/dedup_core.h"
 #include "../host/handoff_core.h"
@@ -43,12 +47,12 @@ enum { C2R_NEXT_CHAIN = 0, C2R_NEXT_SEED = 1, C2R_DONE = 2 };
 // status words (uint32 index).  0..3 are what the host reads in the loop
 enum { C2R_N_TASKS = 0, C2R_N_STOPPED = 1, C2R_ERR = 2, C2R_N_SHORT = 3, C2R_EXT_TASKS = 4, C2R_EXTENDED = 6, C2R_SKIPPED = 8, C2R_CHAINS_IN = 10, C2R_DEDUP_REMOVED = 12, C2R_DROP_REMOVED = 14, C2R_STATUS_BYTES = 64 };
 
-struct C2rPlan { // regs_plan_kernel's record, right behind the status words: one copy brings both.  Also table_plan_kernel's
+struct C2rPlan { // table_plan_kernel's record; the single-end hand-off keeps it right behind the status words: one copy brings both
 	bmh_ho_plan_t plan;
 	uint32_t ticket; // waves that have written their part
 	uint32_t rsv0;
-	int64_t pair_kmax; // bmh_ho_pairs over the table's mates, 0 from regs_plan_kernel
-	int64_t n_sw;      // table_plan_kernel's sum of the per-pair counts it was given, else 0
+	int64_t pair_kmax; // bmh_ho_pairs over the table's mates
+	int64_t n_sw;      // the sum of the per-pair counts the kernel was given, else 0
 	uint32_t rsv[2];
 };
 static_assert(sizeof(C2rPlan) == 64 && sizeof(bmh_ho_plan_t) == 32 && sizeof(C2rPlan) == kTablePlanRecBytes, "plan record");
@@ -93,7 +97,7 @@ struct C2rWs {
 	unsigned long long *nreg, *roff; // n_reads + 1: regions per read, their exclusive sums
 	uint32_t *cand;          // n_reads / 2 + 1: mem_pestat's word per pair (pestat_collect_kernel), right behind roff: one copy brings both
 	bmh_alnreg_t *out;       // ts: the compact regions
-	long long *part;         // (n_reads / 64 + 1) x kPlanPartWords: regs_plan_kernel's per-wave parts
+	long long *part;         // (n_reads / 64 + 1) x kPlanPartWords: table_plan_kernel's per-wave parts
 };
 
 struct C2rSwRule { // what validate_sw (api.hip) checks per task of a host-fed batch
@@ -330,8 +334,8 @@ __global__ __launch_bounds__(64) void c2r_place_kernel(C2rIn in, C2rWs ws)
 
 // What phase 2 learns from a walk over the host's vectors, from the compact records instead (host/handoff_core.h): one lane per read
 // folds its vector, the wave folds its lanes with shuffles and writes its part, and one atomic per wave -- the ticket -- tells the last
-// wave to arrive that every part is there; it folds them into the record.  Blocks are one wave.  The fold and the ticket are one text
-// for the two kernels: regs_plan_kernel over phase 1's workspace, table_plan_kernel over any table with the paired-end clause.
+// wave to arrive that every part is there; it folds them into the record.  Blocks are one wave.  The part and the ticket are
+// wave_ticket.h's protocol, which mt_filter_kernel (matesw.hip) ends in as well.
 struct HoFold {
 	bmh_ho_plan_t p;
 	int64_t pk;    // bmh_ho_pair's fold
@@ -359,53 +363,26 @@ __device__ __forceinline__ void ho_plan_finish(HoFold x, long long *part, C2rPla
 {
 	const int lane = threadIdx.x;
 	ho_wave_fold(x);
-	uint32_t ticket = 0;
-	// The parts cross compute units and dies inside one launch: written through with agent-scope stores and released before the
-	// ticket, read with agent-scope loads behind the ticket's acquire -- never from a cache line this unit may hold.
-	if (lane == 0) {
-		long long *w = part + kPlanPartWords * (size_t)blockIdx.x;
-		__hip_atomic_store(w, (long long)x.p.kmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 1, (long long)x.p.opool_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 2, (long long)x.p.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 3, (long long)(uint32_t)x.p.neg | (long long)x.pk << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (pk has 21 bits)
-		__hip_atomic_store(w + 4, x.nsw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__threadfence();
-		ticket = atomicAdd(&rec->ticket, 1u);
-	}
-	ticket = (uint32_t)__shfl((int)ticket, 0);
-	if (ticket != gridDim.x - 1) return;
-	__threadfence();
+	const long long w[5] = {(long long)x.p.kmax, (long long)x.p.opool_cap, (long long)x.p.total, (long long)(uint32_t)x.p.neg | (long long)x.pk << 32, x.nsw}; // (pk has 21 bits)
+	if (!wave_ticket_publish<5, kPlanPartWords>(part, w, &rec->ticket)) return;
 	HoFold t = {BMH_HO_PLAN_INIT, BMH_HO_PAIRS_INIT, 0};
 	for (unsigned b = (unsigned)lane; b < gridDim.x; b += 64) {
-		const long long *w = part + kPlanPartWords * (size_t)b;
 		HoFold q;
-		q.p.kmax = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), q.p.opool_cap = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		q.p.total = __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		const long long w3 = __hip_atomic_load(w + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		q.p.kmax = wave_ticket_word<kPlanPartWords>(part, b, 0), q.p.opool_cap = wave_ticket_word<kPlanPartWords>(part, b, 1);
+		q.p.total = wave_ticket_word<kPlanPartWords>(part, b, 2);
+		const long long w3 = wave_ticket_word<kPlanPartWords>(part, b, 3);
 		q.p.neg = (int32_t)(w3 & 0xffffffffll), q.p.rsv = 0, q.pk = w3 >> 32;
-		q.nsw = __hip_atomic_load(w + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		q.nsw = wave_ticket_word<kPlanPartWords>(part, b, 4);
 		ho_fold_merge(t, q);
 	}
 	ho_wave_fold(t);
 	if (lane == 0) rec->plan = t.p, rec->pair_kmax = t.pk, rec->n_sw = t.nsw;
 }
 
-__global__ __launch_bounds__(64) void regs_plan_kernel(bmh_sam_opt_t o, int n_reads, unsigned long long ts, C2rWs ws)
-{
-	const int r = blockIdx.x * blockDim.x + threadIdx.x;
-	C2rPlan *rec = (C2rPlan *)((uint8_t *)ws.status + C2R_STATUS_BYTES);
-	bmh_ho_plan_t p = BMH_HO_PLAN_INIT;
-	if (r < n_reads) {
-		const unsigned long long n = ws.nreg[r], at = ws.roff[r];
-		if (at > ts || n > ts - at) c2r_fail(ws.status, BMH_E_ARG); // (c2r_place_kernel has said so already; nothing is read)
-		else bmh_ho_read(&o, ws.out + at, (int64_t)n, &p);
-	}
-	ho_plan_finish(HoFold{p, BMH_HO_PAIRS_INIT, 0}, ws.part, rec);
-}
-
-// The same over any table in c2r_place_kernel's form -- read r's regions at reg[roff[r] .. roff[r + 1]), cap records of room -- with the
-// paired-end clause: a first mate (bmh_ho_first_mate) learns its mate's count from the lane beside it and folds the pair, and adds its
-// pair's n_sw where the caller has such counts.  A read whose offsets leave the table sets *err and is not looked at.
+// Over any table in c2r_place_kernel's form -- read r's regions at reg[roff[r] .. roff[r + 1]), cap records of room: phase 1's workspace
+// behind c2r_scan, or what mate rescue leaves -- with the paired-end clause: a first mate (bmh_ho_first_mate) learns its mate's count
+// from the lane beside it and folds the pair, and adds its pair's n_sw where the caller has such counts.  A single-end caller ignores
+// the pairs' fold.  A read whose offsets leave the table sets *err and is not looked at.
 __global__ __launch_bounds__(64) void table_plan_kernel(bmh_sam_opt_t o, int n_reads, const unsigned long long *__restrict__ roff, const bmh_alnreg_t *__restrict__ reg,
                                                         unsigned long long cap, const int *__restrict__ n_sw, long long *part, C2rPlan *rec, int *err)
 {
@@ -431,7 +408,6 @@ int launch_table_plan(bmh_ctx *ctx, const bmh_sam_opt_t &o, int n_reads, const u
                       const int *d_n_sw, void *d_part, void *d_rec, int *d_err)
 {
 	hipStream_t s = ctx->stream;
-	BMH_HIP(ctx, hipMemsetAsync(d_rec, 0, sizeof(C2rPlan), s)); // the ticket starts at 0
 	if (ctx->timing) {
 		for (hipEvent_t &e : ctx->ev_plan)
 			if (!e) BMH_HIP(ctx, hipEventCreate(&e));
@@ -493,8 +469,6 @@ using namespace bmh;
 
 namespace {
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct C2rLayout {
 	size_t status, chn, state, srt, slot, tasks, res, swt, swr, reg, nreg, roff, cand, out, part, total;
 	C2rLayout(size_t n, size_t tc, size_t ts)
@@ -513,72 +487,45 @@ struct C2rLayout {
 	}
 };
 
-// reads the extension kernels' error flag after a call that was refused on the host, and clears it; the refusal stays the answer
-int c2r_abandon(bmh_ctx *ctx, int rc)
-{
-	std::string why = std::move(ctx->last_error);
-	int e = 0;
-	if (hipMemcpyAsync(ctx->h_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-	    stream_wait(ctx, ctx->stream) == hipSuccess)
-		e = *ctx->h_err;
-	if (e) {
-		(void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream);
-		(void)stream_wait(ctx, ctx->stream);
-	}
-	ctx->last_error = std::move(why);
-	return rc;
-}
-
-// The driver proper, on the context's stream.  The workspace lies at the start of ctx->d_c2r (a caller that keeps its own input there
-// puts it behind C2rLayout::total and has made the buffer large enough).  regs[r] receive malloc'd arrays with n == m.
-// post: what runs behind the replay loop, the context's switches for every call but the two sessions.  post.resident: the driver
-// ends behind c2r_place_kernel and regs_plan_kernel (under *post.plan_opt), regs is not looked at, and *post.resident says where the
-// records lie and what the plan kernel found.  post.pairs (bmh_pairs_sam_device; resident is its regs): no plan kernel -- the total
-// comes down beside the status words -- the words are collected under *post.collect_opt, not the context's options, and come down
-// in the same wait into post.pairs->cand; ctx->rs and the context's words are left alone.
+// What runs behind the replay loop: the context's switches for the two calls that fill the host's vectors (c2r_post_of), a session's own
+// for the two that leave the regions resident.  collect_opt: the options the words are collected under.
 struct C2rPost {
 	bool dedup;
 	float mask;
 	bool drop, collect;
-	ResidentRegs *resident = nullptr;
-	const bmh_sam_opt_t *plan_opt = nullptr;
-	PairsPhase1 *pairs = nullptr;
-	const bmh_sam_opt_t *collect_opt = nullptr;
+	bmh_sam_opt_t collect_opt;
 };
 
 // (a NULL context is c2r_check's to refuse)
 C2rPost c2r_post_of(const bmh_ctx *ctx)
 {
-	return ctx ? C2rPost{ctx->regs_dedup, ctx->regs_dedup_mask, ctx->regs_drop_exact, ctx->pestat_collect} : C2rPost{false, 0.f, false, false};
+	return ctx ? C2rPost{ctx->regs_dedup, ctx->regs_dedup_mask, ctx->regs_drop_exact, ctx->pestat_collect, ctx->pestat_opt} : C2rPost{false, 0.f, false, false, {}};
 }
 
-int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in, int lmax, int msl, bmh_alnreg_v *regs, bmh_driver_stats_t *st,
-            const C2rPost &post, long long *chains_in = nullptr)
+// The workspace of a call, at the start of ctx->d_c2r (a caller that keeps its own input there puts it behind C2rLayout::total and has
+// made the buffer large enough), and room in ctx->h_down for the status record and down_extra bytes behind it.
+int c2r_workspace(bmh_ctx *ctx, const C2rIn &in, size_t down_extra, C2rWs *ws)
 {
-	const int n = in.n_reads;
-	const C2rLayout L((size_t)n, (size_t)in.tc, (size_t)in.ts);
+	const C2rLayout L((size_t)in.n_reads, (size_t)in.tc, (size_t)in.ts);
 	int rc;
-	if ((rc = ensure(ctx, ctx->d_c2r, L.total))) return rc;
-	const size_t b_words = post.pairs && post.collect ? ((size_t)n / 2) * 4 : 0; // the session's words come down behind the status record
-	if (post.pairs) try {
-			post.pairs->cand.assign((size_t)n / 2, 0u);
-		} catch (const std::bad_alloc &) {
-			ctx->last_error = "chains to regions: out of host memory for the insert-size words";
-			return BMH_E_NOMEM;
-		}
-	if ((rc = ensure_host(ctx, ctx->h_down, 256 + b_words))) return rc;
+	if ((rc = ensure(ctx, ctx->d_c2r, L.total)) || (rc = ensure_host(ctx, ctx->h_down, 256 + down_extra))) return rc;
 	uint8_t *d = (uint8_t *)ctx->d_c2r.p;
-	const C2rWs ws{(uint32_t *)(d + L.status), (C2rChain *)(d + L.chn), (C2rState *)(d + L.state), (uint64_t *)(d + L.srt), (uint32_t *)(d + L.slot),
-	               (bmh_seed_task_t *)(d + L.tasks), (bmh_seed_result_t *)(d + L.res), (bmh_sw_task_t *)(d + L.swt), (bmh_sw_result_t *)(d + L.swr),
-	               (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (uint32_t *)(d + L.cand),
-	               (bmh_alnreg_t *)(d + L.out), (long long *)(d + L.part)};
+	*ws = C2rWs{(uint32_t *)(d + L.status), (C2rChain *)(d + L.chn), (C2rState *)(d + L.state), (uint64_t *)(d + L.srt), (uint32_t *)(d + L.slot),
+	            (bmh_seed_task_t *)(d + L.tasks), (bmh_seed_result_t *)(d + L.res), (bmh_sw_task_t *)(d + L.swt), (bmh_sw_result_t *)(d + L.swr),
+	            (bmh_alnreg_t *)(d + L.reg), (unsigned long long *)(d + L.nreg), (unsigned long long *)(d + L.roff), (uint32_t *)(d + L.cand),
+	            (bmh_alnreg_t *)(d + L.out), (long long *)(d + L.part)};
+	return BMH_OK;
+}
+
+// The window kernel, a 16-byte look at the status words, and the short chains' Smith-Watermans
+int c2r_windows(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in, const C2rWs &ws, int msl, bmh_driver_stats_t *st)
+{
 	const bmh_params_t &p = ctx->params;
 	const C2rSwRule sw{msl, ctx->dev.max_mat, ctx->wide_sw ? 1 : 0, sw_byte_gaps_wrap(p) ? 1 : 0};
-	const unsigned rb = (unsigned)((n + 63) / 64);
 	uint32_t *h = (uint32_t *)ctx->h_down.p;
 	hipStream_t s = ctx->stream;
-	BMH_HIP(ctx, hipMemsetAsync(ws.status, 0, C2R_STATUS_BYTES + sizeof(C2rPlan), s)); // the error flag starts clean on every call
-	hipLaunchKernelGGL(c2r_window_kernel, dim3(rb), dim3(64), 0, s, p, l_pac, in, ws, sw);
+	int rc;
+	hipLaunchKernelGGL(c2r_window_kernel, dim3((unsigned)((in.n_reads + 63) / 64)), dim3(64), 0, s, p, l_pac, in, ws, sw);
 	BMH_HIP(ctx, hipGetLastError());
 	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, 16, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, stream_wait(ctx, s));
@@ -593,14 +540,26 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	// The caps are given, and must stay given: in the fused call d_pool lies in ctx->d_scratch, which launch_sw's own reduction of
 	// the caps (qcap < 0) would reallocate or overwrite.  Nothing else between here and the gather touches d_scratch.
 	if (n_short && (rc = launch_sw(ctx, d_pool, ws.swt, n_short, ws.swr, BMH_MEM_SHORT_LEN - 1, BMH_MEM_SHORT_LEN - 1, 2 * BMH_MEM_SHORT_EXT + 1)))
-		return c2r_abandon(ctx, rc);
+		return abandon_call(ctx, rc);
+	return BMH_OK;
+}
+
+// The replay rounds, up to the one in which no read stops: a 16-byte look at the status words per round.  *n_tasks_: the extensions
+// requested in all.
+int c2r_rounds(bmh_ctx *ctx, const uint8_t *d_pool, const C2rIn &in, const C2rWs &ws, int lmax, bmh_driver_stats_t *st, uint32_t *n_tasks_)
+{
+	const bmh_params_t &p = ctx->params;
+	const unsigned rb = (unsigned)((in.n_reads + 63) / 64);
+	uint32_t *h = (uint32_t *)ctx->h_down.p;
+	hipStream_t s = ctx->stream;
+	int rc;
 	const int qmax = std::max(lmax, 1); // no flank is longer than its read
 	uint32_t n_done = 0, n_tasks = (uint32_t)in.tc; // round 1: the task of chain c at index c (the window kernel set the counter to tc)
 	for (;;) {
 		const bool ext = n_tasks > n_done;
 		if (ext) {
 			++st->rounds;
-			if ((rc = launch_seedext(ctx, d_pool, ws.tasks + n_done, (int64_t)(n_tasks - n_done), ws.res + n_done, qmax))) return c2r_abandon(ctx, rc);
+			if ((rc = launch_seedext(ctx, d_pool, ws.tasks + n_done, (int64_t)(n_tasks - n_done), ws.res + n_done, qmax))) return abandon_call(ctx, rc);
 			n_done = n_tasks;
 		}
 		BMH_HIP(ctx, hipMemsetAsync(&ws.status[C2R_N_STOPPED], 0, 4, s));
@@ -620,50 +579,48 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 			return BMH_E_ARG;
 		}
 	}
+	*n_tasks_ = n_tasks;
+	return BMH_OK;
+}
+
+// The driver proper, on the context's stream, the same for every caller: the two steps above, what post switches on, then the gather.
+// It returns behind c2r_place_kernel without having read the final status words: that is the tail's wait.
+int c2r_enqueue(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in, const C2rWs &ws, int lmax, int msl, bmh_driver_stats_t *st,
+                const C2rPost &post, uint32_t *n_tasks)
+{
+	const int n = in.n_reads;
+	hipStream_t s = ctx->stream;
+	int rc;
+	BMH_HIP(ctx, hipMemsetAsync(ws.status, 0, C2R_STATUS_BYTES + sizeof(C2rPlan), s)); // the error flag starts clean on every call, and the plan's ticket at 0
+	if ((rc = c2r_windows(ctx, l_pac, d_pool, in, ws, msl, st)) || (rc = c2r_rounds(ctx, d_pool, in, ws, lmax, st, n_tasks))) return rc;
 	// with the switch on: mem_sort_and_dedup on every read's arena slice, so that the gather places and downloads the survivors only
-	const bool dedup = post.dedup;
-	if (dedup && (rc = launch_region_dedup(ctx, ws.reg, in.soff, ws.nreg, n, in.ts, post.mask,
-	                                       (unsigned long long *)&ws.status[C2R_DEDUP_REMOVED], (int *)&ws.status[C2R_ERR])))
+	if (post.dedup && (rc = launch_region_dedup(ctx, ws.reg, in.soff, ws.nreg, n, in.ts, post.mask, (unsigned long long *)&ws.status[C2R_DEDUP_REMOVED],
+	                                            (int *)&ws.status[C2R_ERR])))
 		return rc;
 	// with either of its switches on: mem_test_and_remove_exact on the survivors, then mem_pestat's word per pair from what is left
-	const bool collect = post.collect, drop = post.drop;
-	if ((collect || drop) && (rc = launch_pestat_collect(ctx, ws.reg, in.soff, ws.nreg, in.len, n, in.ts, post.collect_opt ? *post.collect_opt : ctx->pestat_opt, l_pac, p.a, drop,
-	                                                     collect ? ws.cand : nullptr, (unsigned long long *)&ws.status[C2R_DROP_REMOVED],
-	                                                     (int *)&ws.status[C2R_ERR])))
+	if ((post.collect || post.drop) &&
+	    (rc = launch_pestat_collect(ctx, ws.reg, in.soff, ws.nreg, in.len, n, in.ts, post.collect_opt, l_pac, ctx->params.a, post.drop, post.collect ? ws.cand : nullptr,
+	                                (unsigned long long *)&ws.status[C2R_DROP_REMOVED], (int *)&ws.status[C2R_ERR])))
 		return rc;
-	// gather: count -> scan -> place, then the counts and the compact records
+	// gather: count -> scan -> place
 	hipLaunchKernelGGL(c2r_scan, dim3(1), dim3(1024), 0, s, (const unsigned long long *)ws.nreg, n, ws.roff);
-	hipLaunchKernelGGL(c2r_place_kernel, dim3(rb), dim3(64), 0, s, in, ws);
+	hipLaunchKernelGGL(c2r_place_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, in, ws);
 	BMH_HIP(ctx, hipGetLastError());
-	unsigned long long tr, u64s[4], removed, dropped;
-	C2rPlan plan{};
-	if (post.pairs) { // the status words, the total and the words: the one wait of the hand-off; the plan waits for the table after rescue
-		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
-		BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
-		if (b_words) BMH_HIP(ctx, hipMemcpyAsync(h + 64, ws.cand, b_words, hipMemcpyDeviceToHost, s));
-		BMH_HIP(ctx, stream_wait(ctx, s));
-		memcpy(&tr, h + 16, 8);
-	} else if (post.resident) { // the status words and the plan in one record: the one wait of the hand-off
-		if (ctx->timing) {
-			for (hipEvent_t &e : ctx->ev_plan)
-				if (!e) BMH_HIP(ctx, hipEventCreate(&e));
-			BMH_HIP(ctx, hipEventRecord(ctx->ev_plan[0], s));
-		}
-		hipLaunchKernelGGL(regs_plan_kernel, dim3(rb), dim3(64), 0, s, *post.plan_opt, n, in.ts, ws);
-		BMH_HIP(ctx, hipGetLastError());
-		if (ctx->timing) BMH_HIP(ctx, hipEventRecord(ctx->ev_plan[1], s));
-		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES + sizeof(C2rPlan), hipMemcpyDeviceToHost, s));
-		BMH_HIP(ctx, stream_wait(ctx, s));
-		memcpy(&plan, h + C2R_STATUS_BYTES / 4, sizeof(plan));
-		tr = (unsigned long long)plan.plan.total;
-		if (plan.ticket != rb || plan.plan.total < 0 || plan.plan.opool_cap < 0) tr = in.ts + 1; // cannot happen: refused below
-	} else {
-		BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
-		BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
-		BMH_HIP(ctx, stream_wait(ctx, s));
-		memcpy(&tr, h + 16, 8);
-	}
-	memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&removed, h + C2R_DEDUP_REMOVED, 8), memcpy(&dropped, h + C2R_DROP_REMOVED, 8);
+	return BMH_OK;
+}
+
+// What every tail does behind its wait, the status words in ctx->h_down and tr the total as the tail learnt it: the status check, the
+// driver's statistics and those of the switches.  *chains_in (not null): the chains before the filter, also of a refused call.
+struct C2rCounts {
+	unsigned long long tr, removed, dropped; // regions left, removed by the de-duplication, removed by drop-exact
+	float pestat_ms;
+};
+int c2r_settle(bmh_ctx *ctx, const C2rIn &in, const C2rPost &post, unsigned long long tr, uint32_t n_tasks, bmh_driver_stats_t *st, long long *chains_in, C2rCounts *c)
+{
+	const uint32_t *h = (const uint32_t *)ctx->h_down.p;
+	unsigned long long u64s[4];
+	*c = C2rCounts{tr, 0, 0, -1.f};
+	memcpy(u64s, h + C2R_EXT_TASKS, 32), memcpy(&c->removed, h + C2R_DEDUP_REMOVED, 8), memcpy(&c->dropped, h + C2R_DROP_REMOVED, 8);
 	if (chains_in) *chains_in = (long long)u64s[3];
 	if ((int)h[C2R_ERR] || tr > in.ts) {
 		ctx->last_error = "chains to regions: the region counts are inconsistent";
@@ -671,33 +628,57 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	}
 	st->ext_tasks = (int64_t)u64s[0], st->seeds_extended = (int64_t)u64s[1], st->seeds_skipped = (int64_t)u64s[2];
 	st->seeds_speculated = (int64_t)n_tasks - st->seeds_extended; // extended on the device but never used
-	if (dedup) { // (the driver's statistics are about extensions and stay what they are without the switch)
-		ctx->dedup_in = (long long)(tr + dropped + removed), ctx->dedup_out = (long long)(tr + dropped), ctx->dedup_ms = -1.f;
+	if (post.dedup) { // (the driver's statistics are about extensions and stay what they are without the switch)
+		ctx->dedup_in = (long long)(tr + c->dropped + c->removed), ctx->dedup_out = (long long)(tr + c->dropped), ctx->dedup_ms = -1.f;
 		if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->dedup_ms, ctx->ev_dedup[0], ctx->ev_dedup[1]));
 	}
-	float pestat_ms = -1.f;
-	if ((collect || drop) && ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&pestat_ms, ctx->ev_pestat[0], ctx->ev_pestat[1]));
-	if (post.pairs) { // nothing of the regions comes down and no vector is made
-		PairsPhase1 &P = *post.pairs;
-		P.regs = ResidentRegs{};
-		P.regs.roff = ws.roff, P.regs.reg = ws.out, P.regs.total = (long long)tr;
-		P.regions_in = (long long)(tr + dropped + removed), P.d2h_bytes = (long long)(C2R_STATUS_BYTES + 8 + b_words);
-		if (b_words) memcpy(P.cand.data(), h + 64, b_words);
-		if (drop) ctx->drop_exact_removed = (long long)dropped;
-		return BMH_OK;
+	if ((post.collect || post.drop) && ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&c->pestat_ms, ctx->ev_pestat[0], ctx->ev_pestat[1]));
+	if (post.drop) ctx->drop_exact_removed = (long long)c->dropped;
+	return BMH_OK;
+}
+
+// gives back the arrays of reads [0, upto) -- those this call made, not what a caller left in the .a of a read without regions
+void c2r_free_vectors(int upto, const unsigned long long *roff, bmh_alnreg_v *regs)
+{
+	for (int q = 0; q < upto; ++q)
+		if (roff[q + 1] > roff[q]) free(regs[q].a), regs[q].a = nullptr, regs[q].n = regs[q].m = 0;
+}
+
+// regs[r] receive malloc'd arrays with n == m, cut from the downloaded table; a read without regions is left as the caller gave it
+int c2r_make_vectors(bmh_ctx *ctx, int n, const unsigned long long *roff, const bmh_alnreg_t *ra, bmh_alnreg_v *regs)
+{
+	for (int r = 0; r < n; ++r) {
+		const size_t k = (size_t)(roff[r + 1] - roff[r]);
+		if (!k) continue;
+		bmh_alnreg_t *a = (bmh_alnreg_t *)malloc(k * sizeof(bmh_alnreg_t));
+		if (!a) {
+			c2r_free_vectors(r, roff, regs);
+			ctx->last_error = "chains to regions: out of host memory for the regions";
+			return BMH_E_NOMEM;
+		}
+		memcpy(a, ra + roff[r], k * sizeof(bmh_alnreg_t));
+		regs[r].a = a, regs[r].n = regs[r].m = k;
 	}
-	if (post.resident) {
-		ResidentRegs &R = *post.resident;
-		R.roff = ws.roff, R.reg = ws.out;
-		R.total = (long long)tr, R.kmax = (long long)plan.plan.kmax, R.opool_cap = (long long)plan.plan.opool_cap, R.neg = plan.plan.neg != 0;
-		bmh_reads_sam_stats_t &rs = ctx->rs;
-		rs = bmh_reads_sam_stats_t{n, (int64_t)(tr + dropped + removed), (int64_t)tr, R.kmax, R.opool_cap, (int64_t)(C2R_STATUS_BYTES + sizeof(C2rPlan)),
-		                           1, -1.f, R.neg ? 1 : 0, 0};
-		if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&rs.plan_ms, ctx->ev_plan[0], ctx->ev_plan[1]));
-		if (drop) ctx->drop_exact_removed = (long long)dropped;
-		return BMH_OK;
-	}
-	const size_t b_roff = ((size_t)n + 1) * 8 + (collect ? ((size_t)n / 2) * 4 : 0); // the words lie right behind roff[]
+	return BMH_OK;
+}
+
+// Tail 1, vectors for the host (bmh_chains2regs_device, bmh_seed_chain_regs_batch): the status words and the total in one wait, the
+// offsets -- with the insert-size words right behind them -- and the compact records in a second.
+int c2r_tail_vectors(bmh_ctx *ctx, const C2rIn &in, const C2rWs &ws, const C2rPost &post, uint32_t n_tasks, bmh_driver_stats_t *st, long long *chains_in,
+                     bmh_alnreg_v *regs)
+{
+	const int n = in.n_reads;
+	uint32_t *h = (uint32_t *)ctx->h_down.p;
+	hipStream_t s = ctx->stream;
+	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, stream_wait(ctx, s));
+	unsigned long long tr;
+	memcpy(&tr, h + 16, 8);
+	C2rCounts c;
+	int rc;
+	if ((rc = c2r_settle(ctx, in, post, tr, n_tasks, st, chains_in, &c))) return rc;
+	const size_t b_roff = ((size_t)n + 1) * 8 + (post.collect ? ((size_t)n / 2) * 4 : 0);
 	const size_t b_off = al256(b_roff + 4), b_reg = (size_t)tr * sizeof(bmh_alnreg_t);
 	if ((rc = ensure_host(ctx, ctx->h_down, b_off + b_reg + 64))) return rc;
 	uint8_t *hb = (uint8_t *)ctx->h_down.p;
@@ -705,36 +686,69 @@ int c2r_run(bmh_ctx *ctx, int64_t l_pac, const uint8_t *d_pool, const C2rIn &in,
 	if (b_reg) BMH_HIP(ctx, hipMemcpyAsync(hb + b_off, ws.out, b_reg, hipMemcpyDeviceToHost, s));
 	BMH_HIP(ctx, stream_wait(ctx, s));
 	const unsigned long long *roff = (const unsigned long long *)hb;
-	const bmh_alnreg_t *ra = (const bmh_alnreg_t *)(hb + b_off);
-	// gives back the arrays of reads [0, upto) -- those this call made, not what a caller left in the .a of a read without regions
-	auto undo = [&](int upto) {
-		for (int q = 0; q < upto; ++q)
-			if (roff[q + 1] > roff[q]) free(regs[q].a), regs[q].a = nullptr, regs[q].n = regs[q].m = 0;
-	};
-	for (int r = 0; r < n; ++r) {
-		const size_t k = (size_t)(roff[r + 1] - roff[r]);
-		if (!k) continue;
-		bmh_alnreg_t *a = (bmh_alnreg_t *)malloc(k * sizeof(bmh_alnreg_t));
-		if (!a) {
-			undo(r);
-			ctx->last_error = "chains to regions: out of host memory for the regions";
-			return BMH_E_NOMEM;
-		}
-		memcpy(a, ra + roff[r], k * sizeof(bmh_alnreg_t));
-		regs[r].a = a, regs[r].n = regs[r].m = k;
-	}
-	if (collect) { // of a successful call only (bmh_last_pestat_candidates)
+	if ((rc = c2r_make_vectors(ctx, n, roff, (const bmh_alnreg_t *)(hb + b_off), regs))) return rc;
+	if (post.collect) { // of a successful call only (bmh_last_pestat_candidates)
 		const uint32_t *w = (const uint32_t *)(hb + ((size_t)n + 1) * 8);
 		try {
 			ctx->pestat_cand.assign(w, w + n / 2);
 		} catch (const std::bad_alloc &) {
-			undo(n);
+			c2r_free_vectors(n, roff, regs);
 			ctx->last_error = "chains to regions: out of host memory for the insert-size words";
 			return BMH_E_NOMEM;
 		}
-		ctx->pestat_pairs = n / 2, ctx->pestat_ms = pestat_ms;
+		ctx->pestat_pairs = n / 2, ctx->pestat_ms = c.pestat_ms;
 	}
-	if (drop) ctx->drop_exact_removed = (long long)dropped;
+	return BMH_OK;
+}
+
+// Tail 2, resident regions with the plan (reads_regs_resident): the compact records stay in ws.out, their offsets in ws.roff -- a table
+// with in.ts records of room --, table_plan_kernel folds them into the record behind the status words, and the 128 bytes of both come
+// down in the hand-off's one wait.  *out and ctx->rs up to the hand-off are the call's.
+int c2r_tail_plan(bmh_ctx *ctx, const C2rIn &in, const C2rWs &ws, const C2rPost &post, uint32_t n_tasks, bmh_driver_stats_t *st, long long *chains_in,
+                  const bmh_sam_opt_t &o, ResidentRegs *out)
+{
+	const int n = in.n_reads;
+	uint32_t *h = (uint32_t *)ctx->h_down.p;
+	hipStream_t s = ctx->stream;
+	int rc;
+	if ((rc = launch_table_plan(ctx, o, n, ws.roff, ws.out, in.ts, nullptr, ws.part, (uint8_t *)ws.status + C2R_STATUS_BYTES, (int *)&ws.status[C2R_ERR]))) return rc;
+	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES + sizeof(C2rPlan), hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, stream_wait(ctx, s));
+	ResidentRegs R;
+	const bool whole = table_plan_read(h + C2R_STATUS_BYTES / 4, n, &R, nullptr); // (false cannot happen: refused as a total past the table)
+	C2rCounts c;
+	if ((rc = c2r_settle(ctx, in, post, whole ? (unsigned long long)R.total : in.ts + 1, n_tasks, st, chains_in, &c))) return rc;
+	R.roff = ws.roff, R.reg = ws.out, R.pair_kmax = 0; // (single-end reads: what the kernel folds over neighbours is no pair's)
+	*out = R;
+	ctx->rs = bmh_reads_sam_stats_t{n, (int64_t)(c.tr + c.dropped + c.removed), (int64_t)c.tr, R.kmax, R.opool_cap, (int64_t)(C2R_STATUS_BYTES + sizeof(C2rPlan)),
+	                                1, -1.f, R.neg ? 1 : 0, 0};
+	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ctx->rs.plan_ms, ctx->ev_plan[0], ctx->ev_plan[1]));
+	return BMH_OK;
+}
+
+// Tail 3, resident regions with the total and the words (pairs_regs_resident): no plan -- mate rescue changes the table first --, the
+// total comes down beside the status words and the insert-size words, collected into out->cand's room, behind them in the same wait.
+// ctx->rs and the context's words are left alone.
+int c2r_tail_pairs(bmh_ctx *ctx, const C2rIn &in, const C2rWs &ws, const C2rPost &post, uint32_t n_tasks, bmh_driver_stats_t *st, long long *chains_in,
+                   PairsPhase1 *out)
+{
+	const int n = in.n_reads;
+	const size_t b_words = post.collect ? out->cand.size() * 4 : 0;
+	uint32_t *h = (uint32_t *)ctx->h_down.p;
+	hipStream_t s = ctx->stream;
+	BMH_HIP(ctx, hipMemcpyAsync(h, ws.status, C2R_STATUS_BYTES, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, hipMemcpyAsync(h + 16, &ws.roff[n], 8, hipMemcpyDeviceToHost, s));
+	if (b_words) BMH_HIP(ctx, hipMemcpyAsync(h + 64, ws.cand, b_words, hipMemcpyDeviceToHost, s));
+	BMH_HIP(ctx, stream_wait(ctx, s));
+	unsigned long long tr;
+	memcpy(&tr, h + 16, 8);
+	C2rCounts c;
+	int rc;
+	if ((rc = c2r_settle(ctx, in, post, tr, n_tasks, st, chains_in, &c))) return rc;
+	out->regs = ResidentRegs{};
+	out->regs.roff = ws.roff, out->regs.reg = ws.out, out->regs.total = (long long)tr;
+	out->regions_in = (long long)(tr + c.dropped + c.removed), out->d2h_bytes = (long long)(C2R_STATUS_BYTES + 8 + b_words);
+	if (b_words) memcpy(out->cand.data(), h + 64, b_words);
 	return BMH_OK;
 }
 
@@ -745,7 +759,7 @@ void c2r_empty(bmh_ctx *ctx)
 	if (ctx->regs_drop_exact) ctx->drop_exact_removed = 0;
 }
 
-// regs NULL: a call that makes no vectors (resident mode), post being its own and not the context's switches
+// with_regs false: a call that makes no vectors (the resident tails), post being its own and not the context's switches
 int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads, int min_seed_len, const bmh_alnreg_v *regs, const char *who,
               const C2rPost &post, bool with_regs = true)
 {
@@ -761,7 +775,7 @@ int c2r_check(bmh_ctx *ctx, int64_t l_pac, int n_reads, const bmh_read_t *reads,
 		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on and n_reads is odd: reads 2p and 2p+1 are mates";
 		return BMH_E_ARG;
 	}
-	if (post.collect && (post.collect_opt ? post.collect_opt->max_ins : ctx->pestat_opt.max_ins) > BMH_PS_MAX_INS) {
+	if (post.collect && post.collect_opt.max_ins > BMH_PS_MAX_INS) {
 		ctx->last_error = std::string(who) + ": bmh_ctx_set_pestat_collect is on with max_ins >= 2^30, which the word cannot hold";
 		return BMH_E_RANGE;
 	}
@@ -794,14 +808,19 @@ int fused_check_opts(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt
 	return BMH_OK;
 }
 
+enum C2rTail { kTailVectors, kTailPlan, kTailPairs };
 struct FusedArgs {
 	const bmh_chain_opt_t *co;
 	int64_t l_pac;
 	int lmax, msl;
-	bmh_alnreg_v *regs;
 	bmh_driver_stats_t *st;
 	C2rPost post;
-	size_t bases = 0; // post.pairs: the bases of all reads
+	C2rTail tail;
+	bmh_alnreg_v *regs = nullptr;              // kTailVectors: the caller's vectors
+	const bmh_sam_opt_t *plan_opt = nullptr;   // kTailPlan: the options of the plan ...
+	ResidentRegs *resident = nullptr;          // ... and where the table and the plan are reported
+	PairsPhase1 *pairs = nullptr;              // kTailPairs: the table, the words (cand sized by the caller) and the bases
+	size_t bases = 0;                          // ... the bases of all reads
 };
 
 // The bases where nothing between here and mate rescue's last round writes: seeding's pool lies in ctx->d_scratch, which launch_sw may
@@ -842,8 +861,15 @@ int fused_cb(bmh_ctx *ctx, const DevSeedTables &t, void *user)
 	// (the chains before the filter, for bmh_chain_stats, are summed on the device and come back in the status words)
 	const C2rIn in{n, t.read_off, t.len, dc.coff, dc.soff, dc.cn, dc.seeds, dc.tc, dc.ts, dc.n_keys};
 	long long before = 0;
-	if ((rc = c2r_run(ctx, u->l_pac, t.pool, in, u->lmax, u->msl, u->regs, u->st, u->post, &before))) return rc;
-	if (u->post.pairs && (rc = bases_keep(ctx, t, u->bases, u->post.pairs))) return rc;
+	C2rWs ws;
+	uint32_t n_tasks;
+	const size_t b_words = u->tail == kTailPairs && u->post.collect ? u->pairs->cand.size() * 4 : 0; // come down behind the status record
+	if ((rc = c2r_workspace(ctx, in, b_words, &ws)) || (rc = c2r_enqueue(ctx, u->l_pac, t.pool, in, ws, u->lmax, u->msl, u->st, u->post, &n_tasks))) return rc;
+	if (u->tail == kTailVectors) rc = c2r_tail_vectors(ctx, in, ws, u->post, n_tasks, u->st, &before, u->regs);
+	else if (u->tail == kTailPlan) rc = c2r_tail_plan(ctx, in, ws, u->post, n_tasks, u->st, &before, *u->plan_opt, u->resident);
+	else rc = c2r_tail_pairs(ctx, in, ws, u->post, n_tasks, u->st, &before, u->pairs);
+	if (rc) return rc;
+	if (u->tail == kTailPairs && (rc = bases_keep(ctx, t, u->bases, u->pairs))) return rc;
 	ctx->cstats = bmh_chain_stats_t{n, before, (int64_t)dc.tc, (int64_t)dc.ts, (int64_t)dc.n_equal, dc.kernel_ms}; // of a successful call only
 	return BMH_OK;
 }
@@ -910,7 +936,11 @@ int bmh_chains2regs_device(bmh_ctx_t *ctx, int64_t l_pac, int n_reads, const bmh
 	st.pool_bytes = (int64_t)bytes + 16; // the reads and the 16 bytes of padding behind them, as the host driver counts its pool
 	const C2rIn in{n_reads, (const uint64_t *)(d + i_off), (const int *)(d + i_len), (const unsigned long long *)(d + i_coff),
 	               (const unsigned long long *)(d + i_soff), (const uint32_t *)(d + i_cn), (const bmh_seed_t *)(d + i_seed), tc, ts, nullptr};
-	rc = c2r_run(ctx, l_pac, d + i_pool, in, lmax, min_seed_len, regs, &st, c2r_post_of(ctx));
+	const C2rPost post = c2r_post_of(ctx);
+	C2rWs ws;
+	uint32_t n_tasks;
+	if (!(rc = c2r_workspace(ctx, in, 0, &ws)) && !(rc = c2r_enqueue(ctx, l_pac, d + i_pool, in, ws, lmax, min_seed_len, &st, post, &n_tasks)))
+		rc = c2r_tail_vectors(ctx, in, ws, post, n_tasks, &st, nullptr, regs);
 	ctx->dstats = st;
 	return rc;
 }
@@ -926,7 +956,7 @@ int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bm
 	ctx->dstats = st;
 	int lmax = 1;
 	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
-	FusedArgs u{co, l_pac, lmax, min_seed_len, regs, &st, c2r_post_of(ctx)};
+	FusedArgs u{co, l_pac, lmax, min_seed_len, &st, c2r_post_of(ctx), kTailVectors, regs};
 	rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
 	if (!rc && n_reads == 0) c2r_empty(ctx);
 	ctx->dstats = st;
@@ -937,9 +967,10 @@ int bmh_seed_chain_regs_batch(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bm
 
 // ---- bmh_reads_sam_device's phase 1 (api.hip): bmh_seed_chain_regs_batch with its own post-processing and the regions left resident
 
-static C2rPost reads_sam_post(const bmh_sam_opt_t *o, ResidentRegs *out)
+// a session's switches: the de-duplication at o->mask_level_redun, drop-exact with MEM_F_NO_EXACT, the words under *o where wanted
+static C2rPost session_post(const bmh_sam_opt_t *o, bool collect)
 {
-	return C2rPost{true, o->mask_level_redun, (o->flag & BMH_MEM_F_NO_EXACT) != 0, false, out, o};
+	return C2rPost{true, o->mask_level_redun, (o->flag & BMH_MEM_F_NO_EXACT) != 0, collect, *o};
 }
 
 int bmh::reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int64_t l_pac, int n_reads, const bmh_read_t *reads,
@@ -947,7 +978,7 @@ int bmh::reads_regs_check(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_chai
 {
 	int rc;
 	if (!so || !co) return BMH_E_ARG;
-	const C2rPost post{true, 0.f, false, false}; // (the context's switches are not this call's)
+	const C2rPost post{true, 0.f, false, false, {}}; // (the context's switches are not this call's)
 	if ((rc = c2r_check(ctx, l_pac, n_reads, reads, min_seed_len, nullptr, who, post, false)) || (rc = fused_check_opts(ctx, so, co, who))) return rc;
 	if (!ctx->bwt_bind) { // what seeding refuses before its upload
 		ctx->last_error = "no FM-index on the device (bmh_ctx_set_bwt)";
@@ -965,7 +996,7 @@ int bmh::reads_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_c
 	ctx->dstats = st;
 	int lmax = 1;
 	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq);
-	FusedArgs u{co, l_pac, lmax, min_seed_len, nullptr, &st, reads_sam_post(o, out)};
+	FusedArgs u{co, l_pac, lmax, min_seed_len, &st, session_post(o, false), kTailPlan, nullptr, o, out};
 	const int rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
 	ctx->dstats = st;
 	return rc;
@@ -979,8 +1010,13 @@ int bmh::pairs_regs_resident(bmh_ctx *ctx, const bmh_smem_opt_t *so, const bmh_c
 	int lmax = 1;
 	size_t bytes = 0;
 	for (int r = 0; r < n_reads; ++r) lmax = std::max(lmax, reads[r].l_seq), bytes += (size_t)reads[r].l_seq;
-	const C2rPost post{true, o->mask_level_redun, (o->flag & BMH_MEM_F_NO_EXACT) != 0, collect, &out->regs, nullptr, out, o};
-	FusedArgs u{co, l_pac, lmax, min_seed_len, nullptr, &st, post, bytes};
+	try {
+		out->cand.assign((size_t)n_reads / 2, 0u);
+	} catch (const std::bad_alloc &) {
+		ctx->last_error = "chains to regions: out of host memory for the insert-size words";
+		return BMH_E_NOMEM;
+	}
+	FusedArgs u{co, l_pac, lmax, min_seed_len, &st, session_post(o, collect), kTailPairs, nullptr, nullptr, nullptr, out, bytes};
 	const int rc = seed_tables_device(ctx, so, co->max_occ, n_reads, reads, fused_cb, &u);
 	ctx->dstats = st;
 	return rc;

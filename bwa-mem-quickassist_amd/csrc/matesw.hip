@@ -23,6 +23,7 @@
 
 #include "bmh_ctx.h"
 #include "bmh_device.h"
+#include "wave_ticket.h"
 #include "../host/matesw_core.h"
 #include "../host/matesw_table_core.h"
 
@@ -167,6 +168,7 @@ struct MtPlan { // 64 bytes: what comes down before the first round; a wave's pa
 	uint32_t ticket, rsv[3];
 };
 static_assert(sizeof(MtPlan) == 64, "plan record");
+constexpr int kMtPartWords = sizeof(MtPlan) / 8; // a wave's part: the stride of MtStage's parts, six words of it used
 
 struct MtTotal { // 16 bytes: what comes down behind the merge
 	unsigned long long total;
@@ -230,32 +232,16 @@ __global__ __launch_bounds__(64) void mt_filter_kernel(MtIn in, bmh_matesw_opt_t
 		pair[p] = rec;
 	}
 	mt_wave_fold(x);
-	uint32_t ticket = 0;
-	// The parts cross compute units inside one launch: written with agent-scope stores and released before the ticket, read with
-	// agent-scope loads behind the ticket's acquire, as regs_plan_kernel's are (chain2reg.hip)
-	if (lane == 0) {
-		long long *w = part + 8 * (size_t)blockIdx.x;
-		__hip_atomic_store(w, x.arena_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 1, x.hits_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 2, (long long)x.refusal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 3, x.refusal_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 4, x.n_act, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__hip_atomic_store(w + 5, (long long)(uint32_t)x.lmax | (long long)x.lmin << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__threadfence();
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the part has left this wave before the ticket is drawn, whatever becomes of the fence's own wait
-		ticket = atomicAdd(&plan->ticket, 1u);
-	}
-	ticket = (uint32_t)__shfl((int)ticket, 0);
-	if (ticket != gridDim.x - 1) return;
-	__threadfence();
+	// the wave's part, a ticket, and on the last wave to arrive every wave's part (wave_ticket.h)
+	const long long w[6] = {x.arena_n, x.hits_n, (long long)x.refusal, x.refusal_len, x.n_act, (long long)(uint32_t)x.lmax | (long long)x.lmin << 32};
+	if (!wave_ticket_publish<6, kMtPartWords>(part, w, &plan->ticket)) return;
 	MtPlan t = {0, 0, kMtNoRefusal, 0, 0, 1, 65535, 0, {0, 0, 0}};
 	for (unsigned b = (unsigned)lane; b < gridDim.x; b += 64) {
-		const long long *w = part + 8 * (size_t)b;
 		MtPlan y;
-		y.arena_n = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), y.hits_n = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		y.refusal = (unsigned long long)__hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		y.refusal_len = __hip_atomic_load(w + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), y.n_act = __hip_atomic_load(w + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		const long long ll = __hip_atomic_load(w + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		y.arena_n = wave_ticket_word<kMtPartWords>(part, b, 0), y.hits_n = wave_ticket_word<kMtPartWords>(part, b, 1);
+		y.refusal = (unsigned long long)wave_ticket_word<kMtPartWords>(part, b, 2);
+		y.refusal_len = wave_ticket_word<kMtPartWords>(part, b, 3), y.n_act = wave_ticket_word<kMtPartWords>(part, b, 4);
+		const long long ll = wave_ticket_word<kMtPartWords>(part, b, 5);
 		y.lmax = (int32_t)(ll & 0xffffffffll), y.lmin = (int32_t)(ll >> 32);
 		mt_merge(t, y);
 	}
@@ -456,13 +442,27 @@ __global__ __launch_bounds__(kMtScanThreads) void mt_copy_kernel(MtIn in, MtMerg
 	for (unsigned long long x = (unsigned)lane; x < n * 4; x += 64) dst4[x] = src4[x];
 }
 
+// (bmh_ctx.h) waits for what was enqueued, then reads the kernels' error flag and clears it if set; the error stays the answer
+int abandon_call(bmh_ctx *ctx, int rc)
+{
+	std::string why = std::move(ctx->last_error);
+	int e = 0;
+	(void)stream_wait(ctx, ctx->stream);
+	if (hipMemcpyAsync(ctx->h_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess && stream_wait(ctx, ctx->stream) == hipSuccess)
+		e = *ctx->h_err;
+	if (e) {
+		(void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream);
+		(void)stream_wait(ctx, ctx->stream);
+	}
+	ctx->last_error = std::move(why);
+	return rc;
+}
+
 } // namespace bmh
 
 using namespace bmh;
 
 namespace {
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct MswLayout { // [status | counts, n per pair | arena | pair records | hits | pool] is what goes up, [counts .. arena] what comes down
 	size_t status, out, arena, pair, hits, pool, state, tasks, res, total;
@@ -479,23 +479,6 @@ struct MswLayout { // [status | counts, n per pair | arena | pair records | hits
 		tasks = take(n_act * kMswTasksPerPair * sizeof(bmh_sw_task_t)), res = take(n_act * kMswTasksPerPair * sizeof(bmh_sw_result_t)), total = o;
 	}
 };
-
-// after an error inside the enqueued section: nothing of this call is left running, and the Smith-Waterman kernels' error flag is
-// clean for the next call; the error stays the answer
-int msw_abandon(bmh_ctx *ctx, int rc)
-{
-	std::string why = std::move(ctx->last_error);
-	int e = 0;
-	(void)stream_wait(ctx, ctx->stream);
-	if (hipMemcpyAsync(ctx->h_err, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess && stream_wait(ctx, ctx->stream) == hipSuccess)
-		e = *ctx->h_err;
-	if (e) {
-		(void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream);
-		(void)stream_wait(ctx, ctx->stream);
-	}
-	ctx->last_error = std::move(why);
-	return rc;
-}
 
 bmh_mt_rule_t mt_rule(const bmh_ctx *ctx)
 {
@@ -661,7 +644,7 @@ extern "C" int bmh_matesw_device(bmh_ctx_t *ctx, int64_t l_pac, int n_pairs, con
 	}();
 	if (st.rounds) st.pool_bytes = (int64_t)bytes + 16; // as the host driver counts its pool: shipped for the first round that runs Smith-Waterman
 	ctx->dstats = st;
-	if (rc) return msw_abandon(ctx, rc);
+	if (rc) return abandon_call(ctx, rc);
 	// ---- the vectors of the active pairs: grown first, so that a failure leaves every vector as it was
 	const uint8_t *hd = (const uint8_t *)ctx->h_down.p;
 	const int32_t *cnt = (const int32_t *)hd, *nsw = cnt + 2 * n_act;
@@ -844,6 +827,7 @@ int bmh::matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t
 		BMH_HIP(ctx, hipGetLastError());
 		if ((e = ev.end(2))) return e;
 		// what phase 2 must know of the table just made (table_plan_kernel, chain2reg.hip); an offset past the table's room is the total's error
+		if (plan_opt) BMH_HIP(ctx, hipMemsetAsync(d_tot + 1, 0, kTablePlanRecBytes, s)); // its ticket starts at 0
 		if (plan_opt && (e = launch_table_plan(ctx, *plan_opt, 2 * n_pairs, d_roff_out, d_reg_out, (unsigned long long)out_cap, d_nsw_out, d + o_ppart, d_tot + 1, &d_tot->err)))
 			return e;
 		BMH_HIP(ctx, hipMemcpyAsync(ctx->h_down.p, d_tot, b_tot, hipMemcpyDeviceToHost, s));
@@ -852,12 +836,12 @@ int bmh::matesw_resident(bmh_ctx *ctx, int64_t l_pac, int n_pairs, const uint8_t
 	}();
 	mt.mid_bytes += 16 * (int64_t)readbacks, mt.waits += readbacks;
 	ctx->dstats = st;
-	if (rc) return msw_abandon(ctx, rc);
+	if (rc) return abandon_call(ctx, rc);
 	mt.mid_bytes += (int64_t)b_tot, ++mt.waits; // (with the plan record behind the total where the caller asked for one)
 	const MtTotal tot = *(const MtTotal *)ctx->h_down.p;
 	if (tot.err || tot.total > out_cap) { // cannot happen
 		ctx->last_error = "mate rescue on the device: the device's counts are inconsistent";
-		return msw_abandon(ctx, BMH_E_ARG);
+		return abandon_call(ctx, BMH_E_ARG);
 	}
 	if (n_act && (rc = ev.ms(1, &mt.pack_ms))) return rc;
 	if ((rc = ev.ms(2, &mt.merge_ms))) return rc;

@@ -1,7 +1,7 @@
 /*
  * handoff_core.h -- what phase 2 must know of a batch's regions before its first launch, as ONE text for its two forms: the host's
  * walk over the caller's vectors (decide_table_sizes and oriented_cap, csrc/api.hip, also built by gcc for tests/handoff_core_main.c)
- * and regs_plan_kernel (csrc/chain2reg.hip, hipcc, one lane per read) over the regions that stay on the device between
+ * and table_plan_kernel (csrc/chain2reg.hip, hipcc, one lane per read) over the regions that stay on the device between
  * bmh_reads_sam_device's two phases.
  *   bmh_ho_log_index     the entry of the log table a region's mapQ reads (bmh_pp_mapq): its length where mapQ_coef_len is set and the
  *                        length reaches it, else 0; seedcov without mapQ_coef_len.  Negative = the refusal (log of a negative number)

@@ -1164,7 +1164,7 @@ int bmh_last_drop_exact_stats(const bmh_ctx_t *ctx, int64_t *removed);
  *       bmh_ctx_set_regs_drop_exact on exactly when o->flag has MEM_F_NO_EXACT (0x40) and bmh_ctx_set_pestat_collect off, then
  *   bmh_phase2_text_device(o, bns, pac, NULL, id0, n, seqs, regs, rg_id, text, text_off).
  *   the hand-off  the chains-to-regions driver ends behind c2r_place_kernel: the compact records and their offsets stay in its
- *                 workspace, nothing of them comes down and no vector is made.  regs_plan_kernel, one lane per read, finds what phase 2
+ *                 workspace, nothing of them comes down and no vector is made.  table_plan_kernel, one lane per read, finds what phase 2
  *                 otherwise learns by walking the vectors (host/handoff_core.h): the largest index of the log table, the negative-index
  *                 flag, the capacity of the oriented pool, the region total.  They come down in one 128-byte record with the driver's
  *                 status words: one wait where bmh_seed_chain_regs_batch has two, and as many bytes for one read as for a million.
@@ -1193,10 +1193,10 @@ int bmh_reads_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_cha
 /* Of the last bmh_reads_sam_device call on this context that got as far as the hand-off; all -1 before the first.
  *   reads                 of the batch
  *   regions_in, regions   before and after the de-duplication plus drop-exact
- *   kmax, opool_cap       what regs_plan_kernel found: the largest index of the log table (at least 1), the oriented pool's capacity
+ *   kmax, opool_cap       what table_plan_kernel found: the largest index of the log table (at least 1), the oriented pool's capacity
  *   handoff_d2h_bytes     bytes that came down between the last replay round and phase 2's upload: 128, whatever n
  *   waits_tail            host waits behind the last replay round of chains-to-regions: 1 and phase 2's (bmh_last_phase2_text_stats)
- *   plan_ms               regs_plan_kernel's milliseconds with bmh_set_kernel_timing on, else -1
+ *   plan_ms               table_plan_kernel's milliseconds with bmh_set_kernel_timing on, else -1
  *   neg_index             1 where a region asked for a negative table index (the call then returned BMH_E_RANGE), else 0 */
 typedef struct bmh_reads_sam_stats {
 	int64_t reads, regions_in, regions;
@@ -1224,7 +1224,7 @@ int bmh_last_reads_sam_stats(const bmh_ctx_t *ctx, bmh_reads_sam_stats_t *st);
  *   the barrier   the host makes the table from the words (bmh_pestat_from_candidates's arithmetic): inside the call, no wait of its own
  *   the rescue    bmh_matesw_table_device's kernels over phase 1's table where it lies, against the bases kept in a buffer of their own
  *                 (copied on the stream, device to device, from the pool seeding uploaded).  The table it leaves stays on the device
- *   the plan      table_plan_kernel, one lane per read over the table after rescue: what regs_plan_kernel finds, and the paired-end
+ *   the plan      the same table_plan_kernel, one lane per read over the table after rescue: what it finds there, and its paired-end
  *                 clause (the square of a pair's region count).  Its 64-byte record comes down with rescue's final 16-byte record
  *   phase 2       bmh_phase2_text_device's session from those numbers, the offsets and regions copied device to device
  * Nothing of the regions crosses the bus in either direction.  The bases still go up a second time, inside pass C's per-read pool.

@@ -1,6 +1,6 @@
 /*
  * handoff_core_main.c -- host/handoff_core.h as a stand-alone program, for a plain build and one under AddressSanitizer: the reduction
- * regs_plan_kernel makes over a batch's regions, in its own shape -- one read at a time into the part of its group of 64, the parts
+ * table_plan_kernel makes over a batch's regions, in its own shape -- one read at a time into the part of its group of 64, the parts
  * merged at the end -- with every read's vector in a heap block of exactly its size, so that a read one record past a vector is an
  * error the sanitizer reports.  An empty vector has no block at all: the rule must not look at it.
  *

@@ -1,4 +1,4 @@
-"""host/handoff_core.h on the CPU: the reduction regs_plan_kernel makes over a batch's regions (and decide_table_sizes and oriented_cap
+"""host/handoff_core.h on the CPU: the reduction table_plan_kernel makes over a batch's regions (and decide_table_sizes and oriented_cap
 of csrc/api.hip make over a caller's vectors), as tests/handoff_core_main.c runs it -- per read, per group of 64, merged -- against a
 plain Python restatement of the two host routines as they stood before the header (tests/handoff_ref.py), on seeded random vectors
 with every clause in them: empty vectors, sub_n negative, seedcov negative (the refusal, only without mapQ_coef_len), lengths on both
@@ -117,4 +117,4 @@ def test_api_is_built_on_the_header():
     body = api[api.index("static int decide_table_sizes("):api.index("static int decide_host_log(")]
     assert "bmh_ho_read(" in body and "bmh_ho_pair_kmax(" in body and "mapQ_coef_len" not in body and "seedcov" not in body
     assert "static size_t oriented_cap(const bmh_alnreg_t *a) { return (size_t)bmh_ho_oriented_cap(a); }" in api
-    assert "bmh_ho_read(&o, ws.out + at" in c2r
+    assert "bmh_ho_read(&o, reg + at" in c2r and c2r.count("bmh_ho_read(") == 1  # one plan kernel, for the workspace and for any table

@@ -224,6 +224,25 @@ def test_block_edges(pkg, routes, n_pairs, id0):
     assert got_n.text.count(b"\n") >= 2 * n_pairs
 
 
+def test_kernel_timing_brackets_the_plan(pkg, routes):
+    """with bmh_set_kernel_timing on, the events around the plan kernel are recorded behind mate rescue and read by this caller:
+    plan_ms is a duration, and the text is the untimed call's"""
+    r = pc.run("pe0")
+    table = routes("pe0")[1].pes
+    x = _pairs(r, _edge_order(routes)[:33])
+    c = pc.new_context(pkg)
+    try:
+        plain = call(c, x, pes0=table)
+        c.set_kernel_timing(True)
+        timed = call(c, x, pes0=table)
+    finally:
+        c.close()
+    print("plan_ms", timed.ps["plan_ms"])
+    assert plain.ps["plan_ms"] == -1 and timed.ps["plan_ms"] >= 0, (plain.ps, timed.ps)
+    assert timed.ps["n_sw"] == plain.ps["n_sw"] > 0  # rescue was live in front of the plan
+    assert timed.text == plain.text and np.array_equal(timed.text_off, plain.text_off)
+
+
 # ---------------------------------------------------------------- few or no regions, one mate unalignable
 
 def _nowhere_pairs(n_pairs, seed):

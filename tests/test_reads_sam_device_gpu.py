@@ -3,7 +3,7 @@ kernel that sorts them.  Against the compiled reference's SAM body for the fixtu
 tests/golden/pipeline_golden.npz), against the two-call composition it replaces (bmh_seed_chain_regs_batch, then
 bmh_phase2_text_device) text for text and number for number, and against the conditions a quiet download or upload of the regions
 would break: the hand-off's bytes do not depend on n, phase 2 uploads at least 64 bytes per region less than the composition and
-downloads as much.  Then the block edges of regs_plan_kernel, batches with few or no regions, -e, one context through the call and
+downloads as much.  Then the block edges of table_plan_kernel, its events in timing mode, batches with few or no regions, -e, one context through the call and
 the other route in turn, and the refusals."""
 import ctypes as C
 import types
@@ -136,6 +136,23 @@ def test_block_edges(pkg, n, id0):
     kmax, cap, total, _ = hr.plan(x.sam_opt, want.regs1)
     assert (got.rs["kmax"], got.rs["opool_cap"], got.rs["regions"]) == (kmax, cap, total)
     assert got.text.count(b"\n") >= n
+
+
+def test_kernel_timing_brackets_the_plan(pkg):
+    """with bmh_set_kernel_timing on, the events around the plan kernel are recorded and read from this caller: plan_ms is a duration,
+    and the text is the untimed call's"""
+    r = pc.run("se0")
+    x = pc.sub_run(r, r.reads[:65], r.names[:65], r.quals[:65])
+    c = pc.new_context(pkg)
+    try:
+        plain = call(c, x)
+        c.set_kernel_timing(True)
+        timed = call(c, x)
+    finally:
+        c.close()
+    print("plan_ms", timed.rs["plan_ms"])
+    assert plain.rs["plan_ms"] == -1 and timed.rs["plan_ms"] >= 0, (plain.rs, timed.rs)
+    assert timed.text == plain.text and np.array_equal(timed.text_off, plain.text_off)
 
 
 # ---------------------------------------------------------------- few or no regions
