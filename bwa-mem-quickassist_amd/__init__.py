@@ -93,6 +93,7 @@ PAIRS_SAM_STATS = np.dtype([("reads", "<i8"), ("pairs", "<i8"), ("regions_in", "
                             ("kmax", "<i8"), ("pair_kmax", "<i8"), ("opool_cap", "<i8"), ("mid_d2h_bytes", "<i8"), ("mid_h2d_bytes", "<i8"),
                             ("waits_mid", "<i4"), ("pes_given", "<i4"), ("plan_ms", "<f4"), ("neg_index", "<i4"),
                             ("rsv", "<i4", (6,))])  # bmh_pairs_sam_stats_t, 128 bytes
+PAIRS_PARKED_INFO = np.dtype([("device", "<i4"), ("reads", "<i4"), ("regions", "<i8"), ("bytes", "<i8")])  # bmh_pairs_parked_info_t, 24 bytes
 MATESW_TABLE_STATS = np.dtype([("regions_in", "<i8"), ("regions_out", "<i8"), ("arena_records", "<i8"), ("hits", "<i8"), ("mid_bytes", "<i8"),
                                ("pairs", "<i4"), ("active", "<i4"), ("waits", "<i4"), ("filter_ms", "<f4"), ("pack_ms", "<f4"),
                                ("merge_ms", "<f4")])  # bmh_matesw_table_stats_t, 64 bytes
@@ -291,6 +292,14 @@ def lib():
         L.bmh_pairs_sam_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
         L.bmh_last_pairs_sam_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_pairs_sam_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmh_pairs_sam_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        L.bmh_pairs_finish_consumed.argtypes = [C.c_void_p]
+        L.bmh_pairs_parked_free.argtypes = [C.c_void_p]
+        L.bmh_pairs_parked_free.restype = None
+        L.bmh_pairs_parked_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmh_pairs_parked_trim.argtypes = [C.c_int]
         L.bmh_last_wanted_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.bmh_region_cigar_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -319,6 +328,39 @@ def _ptr(a):
 
 def _nbytes(a):
     return a.nbytes if a is not None else 0
+
+
+class ParkedPairs:
+    """What bmh_pairs_sam_begin parked (bmh_pairs_parked_t): Context.pairs_sam_finish consumes it, free() gives its block back unfinished."""
+
+    def __init__(self, h):
+        self._h = h
+
+    def info(self):
+        """bmh_pairs_parked_info as a dict: device, reads, regions, bytes"""
+        st = np.zeros(1, dtype=PAIRS_PARKED_INFO)
+        rc = lib().bmh_pairs_parked_info(self._h, _ptr(st))
+        if rc:
+            raise BmhError(rc, lib().bmh_strerror(rc).decode())
+        return {k: st[0][k].item() for k in PAIRS_PARKED_INFO.names}
+
+    def free(self):
+        if self._h:
+            lib().bmh_pairs_parked_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def pairs_parked_trim(device=0):
+    """bmh_pairs_parked_trim: the idle parked blocks of `device` go back to the runtime"""
+    rc = lib().bmh_pairs_parked_trim(int(device))
+    if rc:
+        raise BmhError(rc, lib().bmh_strerror(rc).decode())
 
 
 class Context:
@@ -1283,8 +1325,56 @@ class Context:
         _libc.free(text)
         return data, text_off, pes_out
 
+    @staticmethod
+    def _c_seqs(seqs):
+        """(name, comment, seq, qual) tuples as a bmh_seq_t array, and what keeps its pointers alive"""
+        keep = []
+        c_seqs = (_Seq * max(len(seqs), 1))()
+        for r, (name, comment, seq, qual) in enumerate(seqs):
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+            keep.append(seq)
+            c_seqs[r] = _Seq(len(seq), name, comment, seq.ctypes.data if len(seq) else None, qual, None)
+        return c_seqs, keep
+
+    def pairs_sam_begin(self, smem_opt, chain_opt, min_seed_len, opt, refidx, seqs, collect=True):
+        """bmh_pairs_sam_begin: phase 1 of the paired-end session, its table and bases parked in a device block of their own.  Returns
+        (parked, cand): a ParkedPairs for pairs_sam_finish on any context of the same device, and the n / 2 insert-size words (None
+        with collect=False)."""
+        n = len(seqs)
+        o_in, so = np.asarray(smem_opt), np.zeros((), dtype=SMEM_OPT)
+        for k in o_in.dtype.names:
+            so[k] = o_in[k]
+        co = np.ascontiguousarray(np.asarray(chain_opt, dtype=CHAIN_OPT).reshape(()))
+        o = np.array(opt, dtype=SAM_OPT).reshape(1)
+        c_seqs, keep = self._c_seqs(seqs)
+        cand = np.zeros(n // 2, dtype=np.uint32) if collect else None
+        h = C.c_void_p(None)
+        self._check(lib().bmh_pairs_sam_begin(self._h, _ptr(so), _ptr(co), int(min_seed_len), _ptr(o), C.byref(refidx) if refidx is not None else None,
+                                              n, C.cast(c_seqs, C.c_void_p), _ptr(cand), C.cast(C.byref(h), C.c_void_p)))
+        return ParkedPairs(h.value), cand
+
+    def pairs_sam_finish(self, parked, matesw_opt, opt, refidx, pac, pes, id0, seqs, rg_id=b""):
+        """bmh_pairs_sam_finish: mate rescue, the plan and phase 2 over what pairs_sam_begin parked, under the table pes (PESTAT[4]).
+        Returns (text, text_off).  A call refused before anything ran leaves `parked` valid; past that it is consumed."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8) if pac is not None else None
+        n = len(seqs)
+        mo = np.ascontiguousarray(matesw_opt, dtype=MATESW_OPT)
+        o = np.array(opt, dtype=SAM_OPT).reshape(1)
+        c_seqs, keep = self._c_seqs(seqs)
+        text = C.c_void_p(None)
+        text_off = np.zeros(n + 1, dtype=np.int64)
+        pes = np.ascontiguousarray(pes, dtype=PESTAT)
+        rc = lib().bmh_pairs_sam_finish(self._h, parked._h, _ptr(mo), _ptr(o), C.byref(refidx) if refidx is not None else None, _ptr(pac), _ptr(pes),
+                                        C.c_int64(int(id0)), n, C.cast(c_seqs, C.c_void_p), rg_id, C.cast(C.byref(text), C.c_void_p), _ptr(text_off))
+        if lib().bmh_pairs_finish_consumed(self._h):
+            parked._h = None
+        self._check(rc)
+        data = C.string_at(text.value, int(text_off[n]))
+        _libc.free(text)
+        return data, text_off
+
     def last_pairs_sam_stats(self):
-        """bmh_last_pairs_sam_stats as a dict of PAIRS_SAM_STATS' fields: the last pairs_sam_device call on this context."""
+        """bmh_last_pairs_sam_stats as a dict of PAIRS_SAM_STATS' fields: the last pairs_sam_device or pairs_sam_finish call on this context."""
         st = np.zeros(1, dtype=PAIRS_SAM_STATS)
         self._check(lib().bmh_last_pairs_sam_stats(self._h, _ptr(st)))
         return {k: st[0][k].item() for k in PAIRS_SAM_STATS.names if k != "rsv"}

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -2670,8 +2671,10 @@ int bmh_ctx_set_refnames(bmh_ctx_t *ctx, const bmh_refidx_t *bns)
 struct SamtextPool {
 	std::vector<uint64_t> poff; // n + 1: read i's record; poff[n] = the pool's bytes
 	std::vector<int32_t> l_name, l_com;
-	int plan(int n, const bmh_seq_t *seqs)
+	bool bases = true; // false: the records hold no bases (a session whose bases are on the device already: SamtextArgs::bases)
+	int plan(int n, const bmh_seq_t *seqs, bool with_bases = true)
 	{
+		bases = with_bases;
 		const size_t nr = (size_t)n;
 		poff.resize(nr + 1), l_name.resize(nr), l_com.resize(nr);
 		size_t bytes = 0;
@@ -2680,7 +2683,7 @@ struct SamtextPool {
 			if (ln > 0x7fffffffu || lc > 0x7fffffffu) return BMH_E_ARG;
 			l_name[i] = (int32_t)ln, l_com[i] = seqs[i].comment ? (int32_t)lc : -1;
 			poff[i] = bytes;
-			bytes += samtext_read_bytes(ln, (size_t)seqs[i].l_seq, seqs[i].qual != nullptr, l_com[i]);
+			bytes += samtext_read_bytes(ln, (size_t)seqs[i].l_seq, seqs[i].qual != nullptr, l_com[i], bases);
 		}
 		poff[nr] = bytes;
 		return BMH_OK;
@@ -2693,7 +2696,7 @@ struct SamtextPool {
 			const SamtextRead h{l_name[i], s.l_seq, s.qual != nullptr, l_com[i]};
 			memcpy(b, &h, sizeof(h)), b += sizeof(h);
 			memcpy(b, s.name, (size_t)h.l_name), b += h.l_name;
-			if (s.l_seq) memcpy(b, s.seq, (size_t)s.l_seq), b += s.l_seq;
+			if (bases && s.l_seq) memcpy(b, s.seq, (size_t)s.l_seq), b += s.l_seq;
 			if (s.qual && s.l_seq) memcpy(b, s.qual, (size_t)s.l_seq), b += s.l_seq;
 			if (h.l_comment > 0) memcpy(b, s.comment, (size_t)h.l_comment);
 		}
@@ -2975,10 +2978,18 @@ static int phase2_text_check(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t 
 // One session through to the text as the host holds it: the layouts of its three blocks -- pass A's, with pass B's inputs in it, as
 // bmh_phase2_device uploads it; pass B's arrays, the overflow area of the redone regions behind them; pass C's in its fused form --
 // where the blocks lie on the device, how far the records reach, and every host buffer until the end.
+// the bases of a session's reads where an earlier call left them on the device: read i's at bases[soff[i] .. soff[i + 1]), bytes in all
+struct ResidentBases {
+	const uint8_t *bases;
+	const unsigned long long *soff;
+	size_t bytes;
+};
+
 struct Phase2TextRun {
 	bmh_ctx *ctx;
 	const char *who;
 	const ResidentRegs *res; // not NULL: the regions are on the device, see phase2_text_run
+	const ResidentBases *rb; // not NULL: so are the bases, and pass C's per-read pool goes up without them
 	Stager st;
 	Phase2Plan P;
 	SamtextBlock LT;
@@ -2990,7 +3001,12 @@ struct Phase2TextRun {
 	std::vector<Phase2TextHost> list; // the regions the host redoes, by j
 	SamtextOut O;
 	// pass C's arguments over the three blocks as they lie and reach now
-	SamtextArgs args() const { return samtext_args(ctx, dt, LT, P.Z.total, (size_t)D.n_w, cig_words, md_bytes, P.Z.n, P.pe, P.Z.l_pac, d, &P.LA, dw, &P.LB); }
+	SamtextArgs args() const
+	{
+		SamtextArgs A = samtext_args(ctx, dt, LT, P.Z.total, (size_t)D.n_w, cig_words, md_bytes, P.Z.n, P.pe, P.Z.l_pac, d, &P.LA, dw, &P.LB);
+		if (rb) A.bases = rb->bases, A.soff = rb->soff, A.bases_bytes = rb->bytes;
+		return A;
+	}
 	// size and scan again, then the look: SamtextStatus and the SamtextFused behind it
 	int look() { return samtext_size_look(ctx, who, st, args(), ctx->h_ptstat, LT.stat_bytes); }
 	const SamtextFused *fused() const { return (const SamtextFused *)((const SamtextStatus *)ctx->h_ptstat + 1); }
@@ -3021,7 +3037,7 @@ static int phase2_text_plan(Phase2TextRun &S, const bmh_sam_opt_t *o, const bmh_
 	int rc = phase2_plan(ctx, o, pes, l_pac, id0, n, reads, regs, res, total, S.P, &why);
 	if (rc) return why ? refuse(why) : rc;
 	SamtextPool pool;
-	if ((rc = pool.plan(n, seqs))) return rc;
+	if ((rc = pool.plan(n, seqs, S.rb == nullptr))) return rc;
 	S.LT = samtext_block(true, nr, total, total, l_rg, (size_t)pool.poff[nr], S.P.pe, 0, 0);
 	// (resident regions: the offsets at the block's head and the regions at the upload's tail are not the host's to send)
 	S.up_lo = res ? LA.hdr : 0, S.up_hi = res ? LA.reg : LA.up();
@@ -3175,10 +3191,11 @@ static int phase2_text_redo(Phase2TextRun &S, const bmh_refidx_t *bns, const uin
 // addresses past 32 bits), which bmh_sam_batch answers with its other routes.  Nothing of the caller's is written before the end.
 // The regions come from the caller's vectors, or -- res, regs being NULL -- from where phase 1 left them on the device with what
 // table_plan_kernel found: their offsets and records are then copied on the stream into pass A's block instead of uploaded, and
-// everything from launch_decide on is the same.
+// everything from launch_decide on is the same.  rb (bmh_pairs_sam_finish): the bases are on the device too; pass C's per-read pool is
+// packed without them, its kernels and pass B's gather read them there, and the host's redo reads seqs as ever.
 static int phase2_text_run(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes,
                            int64_t id0, int n, const bmh_seq_t *seqs, const bmh_alnreg_v *regs, const ResidentRegs *res, const char *rg_id, char **text,
-                           int64_t *text_off, bool *early)
+                           int64_t *text_off, bool *early, const ResidentBases *rb = nullptr)
 {
 	*early = false;
 	reset_phase2_text_stats(ctx);
@@ -3186,7 +3203,7 @@ static int phase2_text_run(bmh_ctx *ctx, const char *who, const bmh_sam_opt_t *o
 	int rc = phase2_text_check(ctx, who, o, bns, pac, pes, n, seqs, regs, res != nullptr, rg_id, text, text_off, reads);
 	if (rc) return rc;
 	if (n == 0) return empty_text(text, text_off);
-	Phase2TextRun S{ctx, who, res, Stager(ctx)};
+	Phase2TextRun S{ctx, who, res, rb, Stager(ctx)};
 	S.st.cnt = {&ctx->pt.h2d_bytes, &ctx->pt.d2h_bytes, &ctx->pt.waits}, S.D.stay = true;
 	if ((rc = phase2_text_plan(S, o, pes, bns->l_pac, id0, n, seqs, reads.data(), regs, rg_id, early))) return rc;
 	std::optional<GateGuard> gate; // (left around the host's redo, which enters it again through the host form)
@@ -3299,6 +3316,49 @@ int bmh_last_reads_sam_stats(const bmh_ctx_t *ctx, bmh_reads_sam_stats_t *st)
 
 static_assert(sizeof(bmh_pairs_sam_stats_t) == 128, "bmh_pairs_sam_stats_t is part of the interface");
 
+// the pair table's refusal needs the table alone: before rescue opens windows of that width
+static int pairs_table_refusal(bmh_ctx *ctx, const bmh_sam_opt_t *o, const bmh_pestat_t *pes)
+{
+	const char *why = nullptr;
+	long long kmax, n_term;
+	int64_t term_off[4];
+	const bmh_ho_plan_t none = BMH_HO_PLAN_INIT;
+	if (!decide_tables_from_plan(o, pes, none, 0, &kmax, &n_term, term_off, &why)) return BMH_OK;
+	reset_phase2_text_stats(ctx);
+	ctx->last_error = why ? why : "bmh_decide_device: the tables are out of range";
+	ctx->pt.fallbacks = 1;
+	return BMH_E_RANGE;
+}
+
+// A paired-end session from behind the barrier: mate rescue over the table `in` and the bases (pool, soff) where they lie -- the
+// context's workspaces, or a parked block --, its output table, n_sw and the plan over it in d_msw, then phase 2 from the plan's numbers:
+// nothing it ensures or launches touches d_msw.  regions_in, d2h_bytes: phase 1's; park_waits, rb: of a parked session.
+static int pairs_rescue_text(bmh_ctx *ctx, const char *who, const bmh_matesw_opt_t *mo, const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac,
+                             const bmh_pestat_t *pes, int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id, char **text, int64_t *text_off,
+                             const ResidentRegs &in, const uint8_t *pool, const unsigned long long *soff, long long regions_in, long long d2h_bytes,
+                             bool pes_given, int park_waits, const ResidentBases *rb)
+{
+	ResidentRegs R;
+	long long n_sw = 0;
+	int rc;
+	{
+		GateGuard gate;
+		BMH_HIP(ctx, hipSetDevice(ctx->device));
+		int *d_n_sw = nullptr;
+		if ((rc = matesw_resident(ctx, bns->l_pac, n >> 1, pool, soff, in, pes, mo, o->mask_level_redun, &R, &d_n_sw, o, &n_sw))) {
+			const std::string table_name = "bmh_matesw_table_device"; // the refusals speak as bmh_matesw_device's do
+			for (size_t at; (at = ctx->last_error.find(table_name)) != std::string::npos;) ctx->last_error.replace(at, table_name.size(), who);
+			return rc;
+		}
+	}
+	bmh_pairs_sam_stats_t &ps = ctx->ps;
+	ps = bmh_pairs_sam_stats_t{n, n >> 1, regions_in, in.total, R.total, n_sw, R.kmax, R.pair_kmax, R.opool_cap,
+	                           d2h_bytes + ctx->mt.mid_bytes, 0, 1 + park_waits + ctx->mt.waits, pes_given ? 1 : 0, -1.f, R.neg ? 1 : 0, {0, 0, 0, 0, 0, 0}};
+	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ps.plan_ms, ctx->ev_plan[0], ctx->ev_plan[1]));
+	bool early;
+	return phase2_text_run(ctx, who, o, bns, pac, pes, id0, n, seqs, nullptr, &R, rg_id, text, text_off, &early, rb);
+}
+
 int bmh_pairs_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_matesw_opt_t *mo,
                          const bmh_sam_opt_t *o, const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t *pes0, bmh_pestat_t pes_out[4],
                          int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id, char **text, int64_t *text_off)
@@ -3347,37 +3407,10 @@ int bmh_pairs_sam_device(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_cha
 		ctx->last_error = std::string(who) + ": the insert-size words are inconsistent";
 		return rc;
 	}
-	{ // the pair table's refusal needs the table alone: before rescue opens windows of that width
-		const char *why = nullptr;
-		long long kmax, n_term;
-		int64_t term_off[4];
-		const bmh_ho_plan_t none = BMH_HO_PLAN_INIT;
-		if (decide_tables_from_plan(o, pes, none, 0, &kmax, &n_term, term_off, &why)) {
-			reset_phase2_text_stats(ctx);
-			ctx->last_error = why ? why : "bmh_decide_device: the tables are out of range";
-			ctx->pt.fallbacks = 1;
-			return BMH_E_RANGE;
-		}
-	}
-	// ---- mate rescue over the table where it lies; its output table, n_sw and the plan over it in d_msw
-	ResidentRegs R;
-	long long n_sw = 0;
-	{
-		GateGuard gate;
-		BMH_HIP(ctx, hipSetDevice(ctx->device));
-		int *d_n_sw = nullptr;
-		if ((rc = matesw_resident(ctx, l_pac, n >> 1, P1.pool, P1.soff, P1.regs, pes, mo, o->mask_level_redun, &R, &d_n_sw, o, &n_sw))) {
-			const std::string table_name = "bmh_matesw_table_device"; // the refusals speak as bmh_matesw_device's do
-			for (size_t at; (at = ctx->last_error.find(table_name)) != std::string::npos;) ctx->last_error.replace(at, table_name.size(), who);
-			return rc;
-		}
-	}
-	bmh_pairs_sam_stats_t &ps = ctx->ps;
-	ps = bmh_pairs_sam_stats_t{n, n >> 1, P1.regions_in, P1.regs.total, R.total, n_sw, R.kmax, R.pair_kmax, R.opool_cap,
-	                           P1.d2h_bytes + ctx->mt.mid_bytes, 0, 1 + ctx->mt.waits, pes0 ? 1 : 0, -1.f, R.neg ? 1 : 0, {0, 0, 0, 0, 0, 0}};
-	if (ctx->timing) BMH_HIP(ctx, hipEventElapsedTime(&ps.plan_ms, ctx->ev_plan[0], ctx->ev_plan[1]));
-	// ---- phase 2 from the plan's numbers: nothing it ensures or launches touches d_msw
-	if ((rc = phase2_text_run(ctx, who, o, bns, pac, pes, id0, n, seqs, nullptr, &R, rg_id, text, text_off, &early))) return rc;
+	if ((rc = pairs_table_refusal(ctx, o, pes))) return rc;
+	if ((rc = pairs_rescue_text(ctx, who, mo, o, bns, pac, pes, id0, n, seqs, rg_id, text, text_off, P1.regs, P1.pool, P1.soff, P1.regions_in, P1.d2h_bytes,
+	                            pes0 != nullptr, 0, nullptr)))
+		return rc;
 	if (pes_out) memcpy(pes_out, pes, sizeof(pes));
 	return BMH_OK;
 }
@@ -3387,6 +3420,217 @@ int bmh_last_pairs_sam_stats(const bmh_ctx_t *ctx, bmh_pairs_sam_stats_t *st)
 	if (!ctx || !st) return BMH_E_ARG;
 	*st = ctx->ps;
 	return BMH_OK;
+}
+
+// ------------------------------------------------------------------ the same session cut in two at the barrier (bmh_pairs_sam_begin /
+// bmh_pairs_sam_finish): what phase 1 leaves in d_c2r and d_pbase moves into a block that no context's workspace calls touch
+
+} // extern "C"
+
+namespace {
+
+// Parked blocks, per device: taken from and given back to a list that only grows.  hipFree synchronises every stream of its device, so
+// nothing in the middle of a chunk calls it: bmh_pairs_parked_trim alone does, for the blocks idle at that moment.
+struct ParkBlock {
+	void *p = nullptr;
+	size_t cap = 0;
+};
+std::mutex g_park_mu;
+std::vector<std::pair<int, ParkBlock>> g_park_idle; // (device, block)
+
+// the smallest idle block of the device that holds `bytes`, else a new one (sized in 1 MiB steps with an eighth of room: batches of a
+// chunk are of a size, and a block a little short of the next batch would be of no use to it)
+int park_take(bmh_ctx *ctx, size_t bytes, ParkBlock *out)
+{
+	{
+		std::lock_guard<std::mutex> lock(g_park_mu);
+		size_t best = g_park_idle.size();
+		for (size_t k = 0; k < g_park_idle.size(); ++k)
+			if (g_park_idle[k].first == ctx->device && g_park_idle[k].second.cap >= bytes && (best == g_park_idle.size() || g_park_idle[k].second.cap < g_park_idle[best].second.cap))
+				best = k;
+		if (best != g_park_idle.size()) {
+			*out = g_park_idle[best].second;
+			g_park_idle.erase(g_park_idle.begin() + (long)best);
+			return BMH_OK;
+		}
+	}
+	const size_t cap = (bytes + bytes / 8 + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+	void *p = nullptr;
+	BMH_HIP(ctx, hipMalloc(&p, cap));
+	*out = ParkBlock{p, cap};
+	return BMH_OK;
+}
+
+void park_give(int device, ParkBlock &b)
+{
+	if (!b.p) return;
+	std::lock_guard<std::mutex> lock(g_park_mu);
+	g_park_idle.emplace_back(device, b);
+	b = ParkBlock{};
+}
+
+} // namespace
+
+// [roff[n + 1] | the regions | soff[n + 1] | the bases | 16 zero bytes], the last three as d_pbase holds them
+struct bmh_pairs_parked {
+	int device = 0, n = 0;
+	long long total = 0, regions_in = 0, d2h_bytes = 0;
+	ParkBlock blk;
+	size_t o_reg = 0, o_soff = 0, o_pool = 0, bases = 0, used = 0;
+	std::vector<int32_t> l_seq;
+};
+
+extern "C" {
+
+static_assert(sizeof(bmh_pairs_parked_info_t) == 24, "bmh_pairs_parked_info_t is part of the interface");
+
+int bmh_pairs_sam_begin(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_sam_opt_t *o,
+                        const bmh_refidx_t *bns, int n, const bmh_seq_t *seqs, uint32_t *cand, bmh_pairs_parked_t **parked)
+{
+	static const char *const who = "bmh_pairs_sam_begin";
+	if (!ctx || !so || !co || !o || !bns || !parked || n < 0 || (n > 0 && !seqs)) return BMH_E_ARG;
+	if (!(o->flag & BMH_MEM_F_PE)) {
+		ctx->last_error = std::string(who) + ": paired-end only (o->flag lacks BMH_MEM_F_PE; single-end reads: bmh_reads_sam_device)";
+		return BMH_E_ARG;
+	}
+	if (n & 1) {
+		ctx->last_error = std::string(who) + ": n is odd: reads 2p and 2p+1 are mates";
+		return BMH_E_ARG;
+	}
+	std::vector<bmh_read_t> reads((size_t)n);
+	for (int i = 0; i < n; ++i) reads[(size_t)i].l_seq = seqs[i].l_seq, reads[(size_t)i].seq = (const uint8_t *)seqs[i].seq;
+	int rc;
+	if ((rc = reads_regs_check(ctx, so, co, bns->l_pac, n, reads.data(), min_seed_len, who))) return rc;
+	if (cand && o->max_ins > BMH_PS_MAX_INS) {
+		ctx->last_error = std::string(who) + ": max_ins must be below 2^30 where the words are collected: the insert-size word carries the orientation above it";
+		return BMH_E_RANGE;
+	}
+	{ // the names, as phase 2 will refuse them: any table and any text pointers will do for this check
+		bmh_pestat_t any[4];
+		memset(any, 0, sizeof(any));
+		char *t = nullptr;
+		int64_t t_off = 0;
+		if ((rc = bmh_samtext_check_reads_(o, bns, any, n, seqs, &t, &t_off))) return rc;
+	}
+	std::unique_ptr<bmh_pairs_parked> K(new (std::nothrow) bmh_pairs_parked);
+	if (!K) return BMH_E_NOMEM;
+	K->device = ctx->device, K->n = n;
+	if (n == 0) { // nothing runs, nothing is parked
+		*parked = K.release();
+		return BMH_OK;
+	}
+	try {
+		K->l_seq.resize((size_t)n);
+	} catch (const std::bad_alloc &) {
+		return BMH_E_NOMEM;
+	}
+	for (int i = 0; i < n; ++i) K->l_seq[(size_t)i] = seqs[i].l_seq, K->bases += (size_t)seqs[i].l_seq;
+	PairsPhase1 P1;
+	if ((rc = pairs_regs_resident(ctx, so, co, bns->l_pac, n, reads.data(), min_seed_len, o, cand != nullptr, &P1))) return rc;
+	// ---- the move: the total is the host's only now, so the copies have a wait of their own (finish counts it in waits_mid)
+	const size_t nr1 = (size_t)n + 1, total = (size_t)P1.regs.total;
+	K->total = P1.regs.total, K->regions_in = P1.regions_in, K->d2h_bytes = P1.d2h_bytes;
+	K->o_reg = al256(nr1 * 8), K->o_soff = K->o_reg + al256(total * sizeof(bmh_alnreg_t)), K->o_pool = K->o_soff + al256(nr1 * 8);
+	K->used = K->o_pool + K->bases + 16;
+	GateGuard gate;
+	BMH_HIP(ctx, hipSetDevice(ctx->device));
+	if ((rc = park_take(ctx, K->used, &K->blk))) return rc;
+	uint8_t *d = (uint8_t *)K->blk.p;
+	hipError_t e = hipMemcpyAsync(d, P1.regs.roff, nr1 * 8, hipMemcpyDeviceToDevice, ctx->stream);
+	if (e == hipSuccess && total) e = hipMemcpyAsync(d + K->o_reg, P1.regs.reg, total * sizeof(bmh_alnreg_t), hipMemcpyDeviceToDevice, ctx->stream);
+	// (d_pbase as bases_keep laid it out: the offsets, the reads from al256 behind them, 16 zero bytes)
+	if (e == hipSuccess) e = hipMemcpyAsync(d + K->o_soff, P1.soff, K->used - K->o_soff, hipMemcpyDeviceToDevice, ctx->stream);
+	const hipError_t w = stream_wait(ctx, ctx->stream); // (also behind a failed enqueue: the block goes back idle)
+	if (e != hipSuccess || w != hipSuccess) {
+		park_give(K->device, K->blk);
+		return set_hip_error(ctx, e != hipSuccess ? e : w, "hipMemcpyAsync(parked block)");
+	}
+	if (cand) memcpy(cand, P1.cand.data(), (size_t)(n >> 1) * 4);
+	*parked = K.release();
+	return BMH_OK;
+}
+
+int bmh_pairs_sam_finish(bmh_ctx_t *ctx, bmh_pairs_parked_t *parked, const bmh_matesw_opt_t *mo, const bmh_sam_opt_t *o, const bmh_refidx_t *bns,
+                         const uint8_t *pac, const bmh_pestat_t pes[4], int64_t id0, int n, const bmh_seq_t *seqs, const char *rg_id, char **text,
+                         int64_t *text_off)
+{
+	static const char *const who = "bmh_pairs_sam_finish";
+	if (!ctx) return BMH_E_ARG;
+	ctx->park_consumed = false;
+	if (!parked || !mo || !o || !bns || !pes || !text || !text_off || n < 0 || (n > 0 && !seqs)) return BMH_E_ARG;
+	if (!(o->flag & BMH_MEM_F_PE)) {
+		ctx->last_error = std::string(who) + ": paired-end only (o->flag lacks BMH_MEM_F_PE)";
+		return BMH_E_ARG;
+	}
+	if (parked->device != ctx->device) {
+		ctx->last_error = std::string(who) + ": the parked block lies on device " + std::to_string(parked->device) + ", this context runs on device " + std::to_string(ctx->device);
+		return BMH_E_ARG;
+	}
+	if (n != parked->n) {
+		ctx->last_error = std::string(who) + ": n is " + std::to_string(n) + ", " + std::to_string(parked->n) + " reads were parked";
+		return BMH_E_ARG;
+	}
+	for (int i = 0; i < n; ++i)
+		if (seqs[i].l_seq != parked->l_seq[(size_t)i]) {
+			ctx->last_error = std::string(who) + ": read " + std::to_string(i) + " has another length than the read that was parked";
+			return BMH_E_ARG;
+		}
+	int rc;
+	std::vector<bmh_read_t> again;
+	if ((rc = phase2_text_check(ctx, who, o, bns, pac, pes, n, seqs, nullptr, true, rg_id, text, text_off, again))) return rc;
+	if (n == 0) { // nothing was parked, nothing runs
+		bool early;
+		if ((rc = phase2_text_run(ctx, who, o, bns, pac, pes, id0, 0, seqs, nullptr, nullptr, rg_id, text, text_off, &early))) return rc;
+		ctx->dstats = bmh_driver_stats_t{};
+		ctx->ps = bmh_pairs_sam_stats_t{0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, -1.f, 0, {0, 0, 0, 0, 0, 0}};
+		ctx->park_consumed = true;
+		delete parked;
+		return BMH_OK;
+	}
+	if ((rc = pairs_table_refusal(ctx, o, pes))) return rc;
+	// ---- past the refusals: the handle is this call's, whatever comes of it
+	ctx->park_consumed = true;
+	std::unique_ptr<bmh_pairs_parked> K(parked);
+	const uint8_t *d = (const uint8_t *)K->blk.p;
+	ResidentRegs in;
+	in.roff = (const unsigned long long *)d, in.reg = (const bmh_alnreg_t *)(d + K->o_reg), in.total = K->total;
+	const ResidentBases rb{d + K->o_pool, (const unsigned long long *)(d + K->o_soff), K->bases};
+	rc = pairs_rescue_text(ctx, who, mo, o, bns, pac, pes, id0, n, seqs, rg_id, text, text_off, in, rb.bases, rb.soff, K->regions_in, K->d2h_bytes, true, 1, &rb);
+	// the block goes back idle once nothing reads it: a successful session has waited for its text; behind an error the stream is drained
+	if (rc && hipSetDevice(ctx->device) == hipSuccess) (void)stream_wait(ctx, ctx->stream);
+	park_give(K->device, K->blk);
+	return rc;
+}
+
+int bmh_pairs_finish_consumed(const bmh_ctx_t *ctx) { return ctx && ctx->park_consumed ? 1 : 0; }
+
+void bmh_pairs_parked_free(bmh_pairs_parked_t *parked)
+{
+	if (!parked) return;
+	park_give(parked->device, parked->blk); // (begin left nothing in flight)
+	delete parked;
+}
+
+int bmh_pairs_parked_info(const bmh_pairs_parked_t *parked, bmh_pairs_parked_info_t *info)
+{
+	if (!parked || !info) return BMH_E_ARG;
+	*info = bmh_pairs_parked_info_t{parked->device, parked->n, (int64_t)parked->total, (int64_t)parked->used};
+	return BMH_OK;
+}
+
+int bmh_pairs_parked_trim(int device)
+{
+	std::vector<ParkBlock> gone;
+	{
+		std::lock_guard<std::mutex> lock(g_park_mu);
+		for (size_t k = g_park_idle.size(); k-- > 0;)
+			if (g_park_idle[k].first == device) gone.push_back(g_park_idle[k].second), g_park_idle.erase(g_park_idle.begin() + (long)k);
+	}
+	if (gone.empty()) return BMH_OK;
+	int rc = hipSetDevice(device) == hipSuccess ? BMH_OK : BMH_E_HIP;
+	for (ParkBlock &b : gone)
+		if (rc != BMH_OK || hipFree(b.p) != hipSuccess) rc = BMH_E_HIP;
+	return rc;
 }
 
 int bmh_driver_stats(const bmh_ctx_t *ctx, bmh_driver_stats_t *st)

@@ -205,6 +205,7 @@ struct bmh_ctx {
 	// paired-end reads to SAM text with the region table resident from phase 1 through mate rescue to phase 2 (bmh_pairs_sam_device)
 	DevBuf d_pbase;                           // the bases for the rescue: 64-bit offsets, the reads, 16 zero bytes (copied from seeding's pool)
 	bmh_pairs_sam_stats_t ps = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1.f, -1, {0, 0, 0, 0, 0, 0}}; // of the last such call (bmh_last_pairs_sam_stats)
+	bool park_consumed = false;               // the last bmh_pairs_sam_finish on this context consumed its handle (bmh_pairs_finish_consumed)
 };
 
 namespace bmh {

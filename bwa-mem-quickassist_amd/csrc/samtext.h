@@ -13,13 +13,13 @@ struct SamtextHdr { // the upload's parameter block
 static_assert(sizeof(SamtextHdr) == 144, "the header states the upload's size");
 
 // a read in the pool the host packs: this record, then name, base codes, qualities (has_qual) and comment (l_comment >= 0), the whole
-// rounded up to 8 bytes
+// rounded up to 8 bytes.  bases false: the record of a session whose bases are on the device already (SamtextArgs::bases) has none
 struct SamtextRead {
 	int32_t l_name, l_seq, has_qual, l_comment; // l_comment -1: none
 };
-constexpr size_t samtext_read_bytes(size_t l_name, size_t l_seq, bool qual, long long l_comment)
+constexpr size_t samtext_read_bytes(size_t l_name, size_t l_seq, bool qual, long long l_comment, bool bases = true)
 {
-	return (sizeof(SamtextRead) + l_name + l_seq * (qual ? 2 : 1) + (size_t)(l_comment > 0 ? l_comment : 0) + 7) & ~(size_t)7;
+	return (sizeof(SamtextRead) + l_name + l_seq * ((bases ? 1 : 0) + (qual ? 1 : 0)) + (size_t)(l_comment > 0 ? l_comment : 0) + 7) & ~(size_t)7;
 }
 
 // the only thing the host reads between launches
@@ -49,6 +49,10 @@ struct SamtextArgs {
 	const char *md;                 // md_bytes
 	const uint8_t *rpool;           // rpool_bytes
 	unsigned long long total, n_w, cig_words, md_bytes, rpool_bytes;
+	// not NULL (bmh_pairs_sam_finish): the records hold no bases, read i's are bases[soff[i] .. soff[i] + l_seq) in a pool of bases_bytes
+	const uint8_t *bases;
+	const unsigned long long *soff; // n + 1
+	unsigned long long bases_bytes;
 	const bmh_refspan_t *ref;       // the resident sequence table ...
 	const char *names;              // ... and the names: name i is names[name_off[i] .. name_off[i+1])
 	const uint64_t *name_off;

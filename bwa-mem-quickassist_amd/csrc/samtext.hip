@@ -8,7 +8,8 @@
 //   samtext_scan_kernel  one block: toff[] = exclusive 64-bit sums of size[], the total into the status word
 //   samtext_emit_kernel  one lane per read: the same composer over the same records, writing into text[toff[i] .. toff[i+1])
 // and, for the session that runs passes A, B and C without a host hop (bmh_phase2_text_device):
-//   reads_gather_kernel       one wave per read: pass B's contiguous reads pool from the per-read pool that went up for pass C
+//   reads_gather_kernel       one wave per read: pass B's contiguous reads pool from the per-read pool that went up for pass C, or,
+//                             through the same view, from the bases a parked session kept on the device
 //   phase2_text_bind_kernel   one lane per wanted region: the record's slot number becomes the slot's address in pass B's CIGAR and MD
 //                             slots, so that pass C reads them where the region kernels wrote them; the regions flagged
 //                             BMH_WANTED_HOST are listed for the host and counted.  While that count is not zero the size and scan
@@ -33,17 +34,26 @@ __device__ __forceinline__ void samtext_fail(const SamtextArgs &A, int code)
 	atomicCAS(&A.status->err, 0, code);
 }
 
-// read i as the composer sees it, from its record in the pool; false where the record does not lie in the pool
+// read i as the composer sees it, from its record in the pool; false where the record does not lie in the pool.  With A.bases the
+// record has no bases of its own: the view points at the read's in that pool, checked against soff[] and the pool's size as the record is
+// against poff[] and rpool_bytes (the branch is uniform over the launch)
 __device__ __forceinline__ bool samtext_read_view(const SamtextArgs &A, int i, bmh_st_read_t *v)
 {
 	const unsigned long long p0 = A.poff[i], p1 = A.poff[i + 1];
+	const bool own = A.bases == nullptr;
 	if (p0 > p1 || p1 > A.rpool_bytes || p1 - p0 < sizeof(SamtextRead) || (p0 & 7)) return false;
 	const SamtextRead h = *(const SamtextRead *)(A.rpool + p0);
 	if (h.l_name < 0 || h.l_seq < 0 || h.l_comment < -1) return false;
-	if (samtext_read_bytes((size_t)h.l_name, (size_t)h.l_seq, h.has_qual != 0, h.l_comment) > p1 - p0) return false;
+	if (samtext_read_bytes((size_t)h.l_name, (size_t)h.l_seq, h.has_qual != 0, h.l_comment, own) > p1 - p0) return false;
 	const char *b = (const char *)(A.rpool + p0 + sizeof(SamtextRead));
 	v->name = b, v->l_name = h.l_name, b += h.l_name;
-	v->seq = (const uint8_t *)b, v->l_seq = h.l_seq, b += h.l_seq;
+	if (own) v->seq = (const uint8_t *)b, b += h.l_seq;
+	else {
+		const unsigned long long s0 = A.soff[i], s1 = A.soff[i + 1];
+		if (s0 > s1 || s1 > A.bases_bytes || s1 - s0 != (unsigned long long)h.l_seq) return false;
+		v->seq = A.bases + s0;
+	}
+	v->l_seq = h.l_seq;
 	v->qual = h.has_qual ? b : nullptr, b += h.has_qual ? h.l_seq : 0;
 	v->comment = h.l_comment >= 0 ? b : nullptr, v->l_comment = h.l_comment >= 0 ? h.l_comment : 0, v->rsv_ = 0;
 	return true;

@@ -51,6 +51,14 @@
  *                        Needs BMH_PAC_RESIDENT not 0; needs none of the other switches and consults none of them, BMH_REGION_LONG
  *                        excepted.  A call that refuses a batch ends the run: there is no other route for it.  Paired-end chunks go
  *                        the way they go without the switch.
+ * So has a paired-end chunk:
+ *   BMH_PAIRS_SAM_DEVICE=1  the same per batch of an even number of reads, cut in two at the insert-size barrier: pass 1 parks every
+ *                        batch's region table and bases on the device (bmh_pairs_sam_begin) and brings its insert-size words down, the
+ *                        chunk's table is made from all of them, pass 2 finishes every batch from its parked block
+ *                        (bmh_pairs_sam_finish).  With -I the table is given and each batch is one bmh_pairs_sam_device.  Needs
+ *                        BMH_PAC_RESIDENT not 0; consults no other switch but BMH_REGION_LONG; independent of BMH_READS_SAM_DEVICE.
+ *                        Off for a chunk (which then goes the default way) with -P or -S, an odd or empty chunk, BMH_BATCH_EXACT=1 with an
+ *                        odd -b, max_ins >= 2^30 without -I, and more than one device in BMH_DEVICES.  Threads: BMH_PS_THREADS.
  * Run `bwa mem -b <batch>` to choose the batch size.
  * INTEGRATION.md shows the same code as a patch to bwamem.c.
  *
@@ -193,13 +201,13 @@ __attribute__((constructor)) static void qa_shim_loaded(void)
 				const char *v = buf[i + 2] ? buf + i + 2 : (i + 3 < n ? buf + i + 3 : "");
 				if (atoi(v) > 0) g_prewarm_n = atoi(v);
 			}
-		{ /* phase 2 runs -t * 3/2 threads; $BMH_P1_THREADS / $BMH_P2_THREADS / $BMH_RS_THREADS override the phases' thread counts; $BMH_PREWARM=N: N */
-			const char *v[4] = {getenv("BMH_P1_THREADS"), getenv("BMH_P2_THREADS"), getenv("BMH_RS_THREADS"), e};
+		{ /* phase 2 runs -t * 3/2 threads; $BMH_P1_THREADS / $BMH_P2_THREADS / $BMH_RS_THREADS / $BMH_PS_THREADS override the phases' thread counts; $BMH_PREWARM=N: N */
+			const char *v[5] = {getenv("BMH_P1_THREADS"), getenv("BMH_P2_THREADS"), getenv("BMH_RS_THREADS"), getenv("BMH_PS_THREADS"), e};
 			int k;
 			g_prewarm_n += g_prewarm_n / 2;
-			for (k = 0; k < 3; ++k)
+			for (k = 0; k < 4; ++k)
 				if (v[k] && atoi(v[k]) > g_prewarm_n) g_prewarm_n = atoi(v[k]);
-			if (v[3] && atoi(v[3]) > 0) g_prewarm_n = atoi(v[3]);
+			if (v[4] && atoi(v[4]) > 0) g_prewarm_n = atoi(v[4]);
 			if (g_prewarm_n > 128) g_prewarm_n = 128;
 		}
 	}
@@ -555,6 +563,28 @@ static int qa_reads_sam_device(void)
 }
 static long long g_reads_sam_cnt[6]; /* batches, reads, regions behind the de-duplication, redone on the host, lines, bytes of text */
 
+/* BMH_PAIRS_SAM_DEVICE=1: the same for a paired-end chunk (bmh_pairs_sam_begin / bmh_pairs_sam_finish around the chunk's insert-size
+ * table, or bmh_pairs_sam_device under -I: mem_process_seqs below).  Independent of BMH_READS_SAM_DEVICE; the same contradiction. */
+__attribute__((constructor)) static void qa_check_pairs_sam_device_env(void)
+{
+	const char *e = getenv("BMH_PAIRS_SAM_DEVICE"), *r = getenv("BMH_PAC_RESIDENT");
+	if (e && e[0] && strcmp(e, "0") != 0 && r && r[0] == '0') {
+		fprintf(stderr, "[bwamem_hip] fatal: BMH_PAIRS_SAM_DEVICE=1 needs the reference resident on the device: BMH_PAC_RESIDENT must not be 0\n");
+		exit(1);
+	}
+}
+static int qa_pairs_sam_device(void)
+{
+	static int on = -1;
+	if (on < 0) {
+		const char *e = getenv("BMH_PAIRS_SAM_DEVICE");
+		on = e && e[0] && strcmp(e, "0") != 0;
+	}
+	return on;
+}
+static long long g_pairs_sam_cnt[8]; /* batches, pairs, regions, regions after rescue, ksw_align2 calls, redone on the host, lines, bytes of text */
+static long long g_pairs_sam_parked; /* bytes parked at the last chunk's barrier */
+
 /* BMH_SAMTEXT_DEVICE=1: phase 2's pass C on the device (bmh_ctx_set_samtext_device on every pooled context phase 2 uses, with the
  * sequence table and the names made resident).  It reads no base of the reference, so it does not need BMH_PAC_RESIDENT. */
 static int qa_samtext_device(void)
@@ -789,6 +819,7 @@ bmh_alnreg_v mem_align1_core(const ref_mem_opt_t *opt, const void *bwt, const re
 
 #define REF_MEM_F_PE 0x2         /* bwamem.h:14 */
 #define REF_MEM_F_NO_RESCUE 0x20 /* bwamem.h:18 */
+#define REF_MEM_F_NOPAIRING 0x4  /* bwamem.h:15 */
 
 extern void kt_for(int n_threads, void (*func)(void *, int, int), void *data, int n);                       /* kthread.c */
 extern void kt_for_batch(int n_threads, void (*func)(void *, int, int, int), void *data, int n, int batch);  /* kthread_batch.c:44 */
@@ -1017,6 +1048,14 @@ typedef struct {
 	const bmh_sam_opt_t *sopt;
 } qa_reads_sam_job_t;
 
+/* a batch's text into its reads' strings (both one-session routes); the text and its offsets are freed */
+static void qa_text_to_strings(int n, ref_bseq1_t *seqs, char *text, int64_t *text_off)
+{
+	const int rc = bmh_sam_cut(n, (bmh_seq_t *)seqs, text, text_off);
+	if (rc) bmh_tls_die("the batch's SAM text could not be cut into strings", rc);
+	free(text), free(text_off);
+}
+
 static void qa_reads_sam_batch(void *data, int k, int tid)
 {
 	const qa_reads_sam_job_t *J = (const qa_reads_sam_job_t *)data;
@@ -1051,8 +1090,7 @@ static void qa_reads_sam_batch(void *data, int k, int tid)
 	bmh_last_reads_sam_stats(ctx, &rs);
 	bmh_last_phase2_text_stats(ctx, &ps);
 	bmh_pool_put(ctx);
-	if ((rc = bmh_sam_cut(hi - lo, (bmh_seq_t *)(J->seqs + lo), text, text_off))) bmh_tls_die("the batch's SAM text could not be cut into strings", rc);
-	free(text), free(text_off);
+	qa_text_to_strings(hi - lo, J->seqs + lo, text, text_off);
 	{
 		const int64_t got[6] = {1, rs.reads, rs.regions, ps.redone, ps.lines, ps.text_bytes};
 		int c;
@@ -1083,6 +1121,215 @@ static void qa_reads_sam_chunk(const ref_mem_opt_t *opt, const void *bwt, const 
 	}
 }
 
+/* ---- BMH_PAIRS_SAM_DEVICE=1, a paired-end chunk: the same, with the insert-size barrier in the middle.  The table is the whole chunk's
+ * (bwamem.c:1314-1317), so every batch's words must be down before the first batch's mate rescue: pass 1 runs bmh_pairs_sam_begin per
+ * batch, which parks the batch's region table and bases in a device block of its own; one bmh_pestat_from_candidates makes the table;
+ * pass 2 runs bmh_pairs_sam_finish per batch on whatever context the pool hands out.  With the table given (-I) there is no barrier:
+ * one pass of bmh_pairs_sam_device per batch, nothing parked. */
+typedef struct {
+	const ref_mem_opt_t *opt;
+	const void *bwt;
+	const ref_bntseq_head_t *bns;
+	const uint8_t *pac;
+	int64_t n_processed;
+	int n, batch; /* batch: even */
+	ref_bseq1_t *seqs;
+	const bmh_params_t *params;
+	const bmh_sam_opt_t *sopt;
+	const bmh_pestat_t *pes;      /* pass 2: the chunk's table; the one-pass form: the caller's */
+	uint32_t *cand;               /* pass 1: n / 2 words */
+	bmh_pairs_parked_t **parked;  /* one per batch, from pass 1 to pass 2 */
+} qa_pairs_sam_job_t;
+
+static bmh_ctx_t *qa_pairs_sam_ctx(const qa_pairs_sam_job_t *J, bmh_smem_opt_t *so, bmh_chain_opt_t *co)
+{
+	bmh_ctx_t *ctx = bmh_pool_get(J->params);
+	int rc;
+	/* what the calls need resident (BMH_PAC_RESIDENT=0 was refused when the library was loaded); contexts are pooled, so every job says it */
+	if ((rc = bmh_ctx_set_pac(ctx, J->pac, J->bns->l_pac))) bmh_tls_die(bmh_last_error(ctx), rc);
+	qa_seed_setup(ctx, J->opt, (const ref_bwt_t *)J->bwt, so);
+	qa_chain_opt(J->opt, co);
+	if ((rc = bmh_ctx_set_refidx(ctx, (const bmh_refidx_t *)J->bns)) || (rc = bmh_ctx_set_refnames(ctx, (const bmh_refidx_t *)J->bns)) ||
+	    (rc = bmh_ctx_set_region_long(ctx, qa_region_long())))
+		bmh_tls_die(bmh_last_error(ctx), rc);
+	return ctx;
+}
+
+static void qa_pairs_sam_bounds(const qa_pairs_sam_job_t *J, int k, int *lo, int *hi)
+{
+	const int64_t lo64 = (int64_t)k * J->batch, hi64 = lo64 + J->batch < J->n ? lo64 + J->batch : J->n;
+	*lo = (int)lo64, *hi = (int)hi64;
+}
+
+static void qa_pairs_sam_codes(const qa_pairs_sam_job_t *J, int lo, int hi)
+{
+	int b, i;
+	for (b = lo; b < hi; ++b) { /* bwamem.c:1093-1094 */
+		ref_bseq1_t *s = &J->seqs[b];
+		for (i = 0; i < s->l_seq; ++i) s->seq[i] = s->seq[i] < 4 ? s->seq[i] : (char)nst_nt4_table[(int)s->seq[i]];
+	}
+}
+
+/* a finished batch: its text into the reads' strings, its numbers into the run's */
+static void qa_pairs_sam_done(const qa_pairs_sam_job_t *J, bmh_ctx_t *ctx, int lo, int hi, char *text, int64_t *text_off)
+{
+	bmh_pairs_sam_stats_t ps;
+	bmh_phase2_text_stats_t pt;
+	int c;
+	bmh_last_pairs_sam_stats(ctx, &ps);
+	bmh_last_phase2_text_stats(ctx, &pt);
+	bmh_pool_put(ctx);
+	qa_text_to_strings(hi - lo, J->seqs + lo, text, text_off);
+	{
+		const int64_t got[8] = {1, ps.pairs, ps.regions, ps.regions_out, ps.n_sw, pt.redone, pt.lines, pt.text_bytes};
+		for (c = 0; c < 8; ++c) __sync_fetch_and_add(&g_pairs_sam_cnt[c], (long long)(got[c] > 0 ? got[c] : 0));
+	}
+}
+
+static void qa_pairs_sam_pass1(void *data, int k, int tid)
+{
+	const qa_pairs_sam_job_t *J = (const qa_pairs_sam_job_t *)data;
+	bmh_smem_opt_t so;
+	bmh_chain_opt_t co;
+	bmh_pairs_parked_info_t info;
+	bmh_ctx_t *ctx;
+	int lo, hi, rc;
+	(void)tid;
+	qa_pairs_sam_bounds(J, k, &lo, &hi);
+	if (hi <= lo) return;
+	qa_pairs_sam_codes(J, lo, hi);
+	ctx = qa_pairs_sam_ctx(J, &so, &co);
+	if ((rc = bmh_pairs_sam_begin(ctx, &so, &co, J->opt->min_seed_len, J->sopt, (const bmh_refidx_t *)J->bns, hi - lo, (bmh_seq_t *)(J->seqs + lo),
+	                              J->cand + (lo >> 1), &J->parked[k])))
+		bmh_tls_die(bmh_last_error(ctx), rc); /* no other route for the batch */
+	bmh_pool_put(ctx);
+	if (bmh_pairs_parked_info(J->parked[k], &info) == BMH_OK) __sync_fetch_and_add(&g_pairs_sam_parked, (long long)info.bytes);
+}
+
+static void qa_pairs_sam_pass2(void *data, int k, int tid)
+{
+	const qa_pairs_sam_job_t *J = (const qa_pairs_sam_job_t *)data;
+	bmh_smem_opt_t so;
+	bmh_chain_opt_t co;
+	bmh_matesw_opt_t mo;
+	bmh_ctx_t *ctx;
+	int64_t *text_off;
+	char *text = 0;
+	int lo, hi, rc;
+	(void)tid;
+	qa_pairs_sam_bounds(J, k, &lo, &hi);
+	if (hi <= lo) return;
+	if (!(text_off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)(hi - lo) + 1)))) bmh_tls_die("out of memory for the batch's text offsets", BMH_E_NOMEM);
+	ctx = qa_pairs_sam_ctx(J, &so, &co);
+	mo.pen_unpaired = J->opt->pen_unpaired, mo.max_matesw = J->opt->max_matesw, mo.min_seed_len = J->opt->min_seed_len, mo.rsv = 0;
+	if ((rc = bmh_pairs_sam_finish(ctx, J->parked[k], &mo, J->sopt, (const bmh_refidx_t *)J->bns, J->pac, J->pes, J->n_processed + lo, hi - lo,
+	                               (bmh_seq_t *)(J->seqs + lo), bwa_rg_id, &text, text_off)))
+		bmh_tls_die(bmh_last_error(ctx), rc);
+	J->parked[k] = 0; /* consumed */
+	qa_pairs_sam_done(J, ctx, lo, hi, text, text_off);
+}
+
+static void qa_pairs_sam_one(void *data, int k, int tid)
+{
+	const qa_pairs_sam_job_t *J = (const qa_pairs_sam_job_t *)data;
+	bmh_smem_opt_t so;
+	bmh_chain_opt_t co;
+	bmh_matesw_opt_t mo;
+	bmh_ctx_t *ctx;
+	int64_t *text_off;
+	char *text = 0;
+	int lo, hi, rc;
+	(void)tid;
+	qa_pairs_sam_bounds(J, k, &lo, &hi);
+	if (hi <= lo) return;
+	qa_pairs_sam_codes(J, lo, hi);
+	if (!(text_off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)(hi - lo) + 1)))) bmh_tls_die("out of memory for the batch's text offsets", BMH_E_NOMEM);
+	ctx = qa_pairs_sam_ctx(J, &so, &co);
+	mo.pen_unpaired = J->opt->pen_unpaired, mo.max_matesw = J->opt->max_matesw, mo.min_seed_len = J->opt->min_seed_len, mo.rsv = 0;
+	if ((rc = bmh_pairs_sam_device(ctx, &so, &co, J->opt->min_seed_len, &mo, J->sopt, (const bmh_refidx_t *)J->bns, J->pac, J->pes, 0, J->n_processed + lo,
+	                               hi - lo, (bmh_seq_t *)(J->seqs + lo), bwa_rg_id, &text, text_off)))
+		bmh_tls_die(bmh_last_error(ctx), rc);
+	qa_pairs_sam_done(J, ctx, lo, hi, text, text_off);
+}
+
+/* why a paired-end chunk keeps the default route with the switch on, or null.  A parked block is bound to its device and the pool does
+ * not pick contexts by device, so a run spread over several GPUs keeps it too. */
+static const char *qa_pairs_sam_off(const ref_mem_opt_t *opt, int n, const bmh_pestat_t *pes0)
+{
+	const char *list = getenv("BMH_DEVICES");
+	if (opt->flag & REF_MEM_F_NOPAIRING) return "-P: no pairing";
+	if (opt->flag & REF_MEM_F_NO_RESCUE) return "-S: the session always runs mate rescue";
+	if (n < 2) return "no pair";
+	if (n & 1) return "an odd number of reads";
+	if (getenv("BMH_BATCH_EXACT") && ((opt->batch_size > 0 ? opt->batch_size : 1) & 1)) return "BMH_BATCH_EXACT=1 with an odd batch size";
+	if (!pes0 && opt->max_ins >= (1 << 30)) return "max_ins >= 2^30";
+	if (list && *list) { /* distinct ordinals */
+		long first = -1;
+		const char *p = list;
+		while (*p) {
+			char *end;
+			const long v = strtol(p, &end, 10);
+			if (end == p) break;
+			if (first < 0) first = v;
+			else if (v != first) return "more than one device in BMH_DEVICES";
+			if (*end != ',') break;
+			p = end + 1;
+		}
+	}
+	return 0;
+}
+
+static void qa_pairs_sam_chunk(const ref_mem_opt_t *opt, const void *bwt, const ref_bntseq_head_t *bns, const uint8_t *pac, int64_t n_processed, int n,
+                               ref_bseq1_t *seqs, const bmh_pestat_t *pes0)
+{
+	/* threads as in the single-end route: a thread inside either call sleeps on several waits per batch */
+	const int nt = qa_threads("BMH_PS_THREADS", opt->n_threads + opt->n_threads / 2);
+	double t_[4];
+	qa_pairs_sam_job_t J;
+	bmh_pestat_t pes[4];
+	bmh_params_t p;
+	bmh_sam_opt_t so;
+	int nb;
+	t_[0] = realtime();
+	qa_sam_opt(opt, &so);
+	qa_params(opt, &p);
+	J.opt = opt, J.bwt = bwt, J.bns = bns, J.pac = pac, J.n_processed = n_processed, J.n = n, J.seqs = seqs, J.params = &p, J.sopt = &so;
+	J.batch = qa_even_batch(opt, n, nt);
+	J.batch += J.batch & 1; /* no pair straddles two batches */
+	J.pes = pes0, J.cand = 0, J.parked = 0;
+	nb = (int)(((int64_t)n + J.batch - 1) / J.batch);
+	g_pairs_sam_parked = 0;
+	if (pes0) {
+		kt_for(nt, qa_pairs_sam_one, &J, nb);
+		t_[1] = t_[2] = t_[3] = realtime();
+	} else {
+		int rc;
+		J.cand = (uint32_t *)calloc((size_t)(n >> 1), sizeof(uint32_t));
+		J.parked = (bmh_pairs_parked_t **)calloc((size_t)nb, sizeof(bmh_pairs_parked_t *));
+		if (!J.cand || !J.parked) bmh_tls_die("out of memory for the insert-size words", BMH_E_NOMEM);
+		kt_for(nt, qa_pairs_sam_pass1, &J, nb);
+		t_[1] = realtime();
+		if ((rc = bmh_pestat_from_candidates(&so, n >> 1, J.cand, pes, bwa_verbose))) bmh_tls_die("the device's insert-size words are inconsistent", rc);
+		J.pes = pes;
+		t_[2] = realtime();
+		kt_for(nt, qa_pairs_sam_pass2, &J, nb);
+		t_[3] = realtime();
+		free(J.cand), free(J.parked);
+	}
+	if (getenv("BMH_VERBOSE")) {
+		fprintf(stderr, "[bwamem_hip] paired-end reads to SAM text in one session so far: %lld batches, %lld pairs, %lld regions, %lld after rescue, %lld ksw_align2 calls, "
+		        "%lld redone on the host, %lld lines, %lld bytes, %lld bytes parked at the barrier\n",
+		        g_pairs_sam_cnt[0], g_pairs_sam_cnt[1], g_pairs_sam_cnt[2], g_pairs_sam_cnt[3], g_pairs_sam_cnt[4], g_pairs_sam_cnt[5], g_pairs_sam_cnt[6],
+		        g_pairs_sam_cnt[7], g_pairs_sam_parked);
+		if (pes0)
+			fprintf(stderr, "[bwamem_hip] chunk of %d reads: pairs to SAM text in one session per batch under the given table, %d batches of up to %d reads, %.3f s\n", n, nb,
+			        J.batch, t_[1] - t_[0]);
+		else
+			fprintf(stderr, "[bwamem_hip] chunk of %d reads: pairs to SAM text in parked sessions, %d batches of up to %d reads: pass 1 %.3f s, table %.3f s, pass 2 %.3f s\n", n,
+			        nb, J.batch, t_[1] - t_[0], t_[2] - t_[1], t_[3] - t_[2]);
+	}
+}
+
 void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntseq_head_t *bns, const uint8_t *pac,
                       int64_t n_processed, int n, ref_bseq1_t *seqs, const bmh_pestat_t *pes0)
 {
@@ -1107,6 +1354,14 @@ void mem_process_seqs(const ref_mem_opt_t *opt, const void *bwt, const ref_bntse
 			goto processed;
 		}
 		if (getenv("BMH_VERBOSE")) fprintf(stderr, "[bwamem_hip] single-end reads to SAM text in one session: off for this chunk (paired-end reads)\n");
+	}
+	if (qa_pairs_sam_device()) { /* a paired-end chunk: bases to SAM strings, the sessions parked at the insert-size barrier; nothing below runs */
+		const char *why_off = pe ? qa_pairs_sam_off(opt, n, pes0) : "single-end reads";
+		if (!why_off) {
+			qa_pairs_sam_chunk(opt, bwt, bns, pac, n_processed, n, seqs, pes0);
+			goto processed;
+		}
+		if (getenv("BMH_VERBOSE")) fprintf(stderr, "[bwamem_hip] paired-end reads to SAM text in one session: off for this chunk (%s)\n", why_off);
 	}
 	w.opt = opt, w.bwt = bwt, w.bns = bns, w.pac = pac, w.seqs = seqs;
 	w.regs = (bmh_alnreg_v *)malloc((size_t)n * sizeof(bmh_alnreg_v));

@@ -1274,6 +1274,49 @@ typedef struct bmh_pairs_sam_stats {
 } bmh_pairs_sam_stats_t; /* 128 bytes */
 int bmh_last_pairs_sam_stats(const bmh_ctx_t *ctx, bmh_pairs_sam_stats_t *st);
 
+/* ---- The same session in two calls, cut at the insert-size barrier: for a caller whose table is a whole chunk's and whose chunk is
+ * many batches (the preload shim).  bmh_pairs_sam_begin is the session's phase 1; bmh_pairs_sam_finish is its rescue, plan and phase 2
+ * under the table the caller made from every batch's words.  begin + bmh_pestat_from_candidates over the words + finish gives the
+ * bytes of bmh_pairs_sam_device with that table as pes0.
+ *   begin    the one-call form's checks up to phase 1 (BMH_MEM_F_PE, an even n, mates named alike, what phase 1 refuses, and with cand
+ *            o->max_ins below 2^30), then its phase 1, the words collected exactly when cand is given (n / 2 words, written on success
+ *            only).  What phase 1 leaves in the context's workspaces -- the table's offsets and regions, the bases' offsets, the bases
+ *            and 16 zero bytes -- is then copied on the stream, device to device, into ONE block of its own, and *parked names it.
+ *            The table's total is known only behind phase 1's wait, so the copy has a wait of its own, which the
+ *            statistics of finish count in waits_mid.  When begin
+ *            returns nothing of it is in flight, and the block stays valid whatever any context does afterwards.  n == 0 parks no
+ *            block (the handle is still made).  On any error *parked is untouched.
+ *   finish   on any context of the block's device (BMH_E_ARG with another device's).  Before anything runs, with the handle left
+ *            valid: a NULL argument, BMH_E_ARG for an n or read lengths other than the parked ones, what bmh_phase2_text_device
+ *            refuses of its arguments, and BMH_E_RANGE for a pair table past 1 << 20 entries.  Past those the handle is consumed
+ *            whatever the result: the caller must not use or free it again.  Then rescue over the parked table and bases, the plan
+ *            over its output, and phase 2 -- in which pass C's per-read pool goes up WITHOUT the bases: the kernels read them from
+ *            the parked block (h2d_bytes is smaller by the difference of the two pools), and pass B's reads pool is gathered from
+ *            there.  The host's redo of outgrown alignments reads seqs.
+ * Afterwards the bmh_last_* calls answer as after bmh_pairs_sam_device; bmh_last_pairs_sam_stats has pes_given = 1,
+ * waits_mid = 2 + bmh_last_matesw_table_stats' waits (one more than the one-call form: the copy's) and mid_d2h_bytes as in the one-call form (begin's share included).
+ * Blocks are recycled through a process-wide, mutex-guarded free list per device that only grows: neither finish nor
+ * bmh_pairs_parked_free gives memory back to the runtime (that would synchronise every stream of the device in the middle of a
+ * chunk); bmh_pairs_parked_trim does, for the blocks that are idle at that moment.
+ * bmh_pairs_parked_free(NULL) does nothing; freeing an unfinished handle returns its block to the list. */
+typedef struct bmh_pairs_parked bmh_pairs_parked_t;
+typedef struct bmh_pairs_parked_info {
+	int32_t device, reads; /* the block's device; n as parked */
+	int64_t regions, bytes; /* the parked table's records; the bytes of the block that are in use (0 for n == 0) */
+} bmh_pairs_parked_info_t; /* 24 bytes */
+int bmh_pairs_sam_begin(bmh_ctx_t *ctx, const bmh_smem_opt_t *so, const bmh_chain_opt_t *co, int min_seed_len, const bmh_sam_opt_t *o,
+                        const bmh_refidx_t *bns, int n, const bmh_seq_t *seqs, uint32_t *cand /* n / 2 words, nullable */,
+                        bmh_pairs_parked_t **parked);
+int bmh_pairs_sam_finish(bmh_ctx_t *ctx, bmh_pairs_parked_t *parked, const bmh_matesw_opt_t *mo, const bmh_sam_opt_t *o,
+                         const bmh_refidx_t *bns, const uint8_t *pac, const bmh_pestat_t pes[4], int64_t id0, int n, const bmh_seq_t *seqs,
+                         const char *rg_id, char **text, int64_t *text_off);
+/* 1 if the last bmh_pairs_sam_finish on this context consumed its handle, 0 if it left it valid (or none ran yet): for a binding that
+ * cannot tell the two from the return code */
+int bmh_pairs_finish_consumed(const bmh_ctx_t *ctx);
+void bmh_pairs_parked_free(bmh_pairs_parked_t *parked);
+int bmh_pairs_parked_info(const bmh_pairs_parked_t *parked, bmh_pairs_parked_info_t *info);
+int bmh_pairs_parked_trim(int device);
+
 #ifdef __cplusplus
 }
 #endif

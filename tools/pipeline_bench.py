@@ -73,7 +73,7 @@ def sim_pairs_fast(rng, ref, n, L, noisy_frac):
 
 def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=False, regs_device=False, dedup_device=False, matesw_device=False,
         decide_device=False, wanted_device=False, phase2_device=False, samtext_device=False, phase2_text_device=False, pestat_device=False,
-        reads_sam_device=False, more_env=None):
+        reads_sam_device=False, pairs_sam_device=False, more_env=None):
     env = dict(os.environ)
     env.pop("BMH_PESTAT_DEVICE", None)
     env.pop("BMH_CHAIN_DEVICE", None)
@@ -86,7 +86,10 @@ def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=Fals
     env.pop("BMH_SAMTEXT_DEVICE", None)
     env.pop("BMH_PHASE2_TEXT_DEVICE", None)
     env.pop("BMH_READS_SAM_DEVICE", None)
+    env.pop("BMH_PAIRS_SAM_DEVICE", None)
     if preload:
+        if pairs_sam_device:
+            env["BMH_PAIRS_SAM_DEVICE"] = "1"
         if reads_sam_device:
             env["BMH_READS_SAM_DEVICE"] = "1"
         if phase2_text_device:
@@ -137,6 +140,10 @@ def run(fa, fq, threads, batch, preload, out, ksw_dropin=True, chain_device=Fals
         one = [l for l in shim if "in one session so far" in l]
         res["reads_sam_device"] = {"chunks_in_one_session": len(one), "chunks_the_other_way": sum("in one session: off for this chunk" in l for l in shim),
                                    "so_far": one[-1] if one else None}
+    if preload and pairs_sam_device:  # likewise; the chunk lines carry the route's three spans
+        one = [l for l in shim if "paired-end reads to SAM text in one session so far" in l]
+        res["pairs_sam_device"] = {"chunks_in_one_session": len(one), "chunks_the_other_way": sum("paired-end reads to SAM text in one session: off for this chunk" in l for l in shim),
+                                   "so_far": one[-1] if one else None, "spans": [l for l in shim if "pairs to SAM text in" in l]}
     return res
 
 
@@ -195,6 +202,9 @@ def main():
     ap.add_argument("--reads-sam-device", action="store_true",
                     help="single-end reads: every batch of the DUT goes from bases to SAM text in one device session (BMH_READS_SAM_DEVICE=1); "
                          "with --pe the chunks go the way they go without it, and the run says so")
+    ap.add_argument("--pairs-sam-device", action="store_true",
+                    help="--pe: every batch of the DUT goes from bases to SAM text in one device session, parked on the device at the insert-size "
+                         "barrier (BMH_PAIRS_SAM_DEVICE=1); single-end chunks go the way they go without it")
     ap.add_argument("--pestat-device", action="store_true",
                     help="--pe: ... and answers mem_pestat's question per pair there (BMH_PESTAT_DEVICE=1); implies --regs-device --dedup-device")
     a = ap.parse_args()
@@ -205,7 +215,8 @@ def main():
 
     res = {"genome_bp": a.genome, "repeats": a.repeats, "reads": a.reads, "paired": bool(a.pe), "index_s": t_index, "chain_device": bool(a.chain_device), "regs_device": bool(a.regs_device),
            "dedup_device": bool(a.dedup_device), "matesw_device": bool(a.matesw_device), "decide_device": bool(a.decide_device), "wanted_device": bool(a.wanted_device),
-           "phase2_device": bool(a.phase2_device), "samtext_device": bool(a.samtext_device), "phase2_text_device": bool(a.phase2_text_device), "pestat_device": bool(a.pestat_device), "reads_sam_device": bool(a.reads_sam_device), "runs": []}
+           "phase2_device": bool(a.phase2_device), "samtext_device": bool(a.samtext_device), "phase2_text_device": bool(a.phase2_text_device), "pestat_device": bool(a.pestat_device), "reads_sam_device": bool(a.reads_sam_device),
+           "pairs_sam_device": bool(a.pairs_sam_device), "runs": []}
     # one untimed DUT run first: on a fresh box the first process to load the HIP runtime and the library's code objects
     # pays for reading them from disk (seconds), which has nothing to do with the pipeline
     run(fa, fq, 8, a.batch, True, os.path.join(tmp, "warm.sam"), ksw_dropin=False)
@@ -215,14 +226,14 @@ def main():
         d1 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=False, chain_device=a.chain_device, regs_device=a.regs_device,
                  dedup_device=a.dedup_device, matesw_device=a.matesw_device, decide_device=a.decide_device, wanted_device=a.wanted_device,
                  phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device,
-                 reads_sam_device=a.reads_sam_device)
+                 reads_sam_device=a.reads_sam_device, pairs_sam_device=a.pairs_sam_device)
         same1 = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         d2 = None
         if a.full:
             d2 = run(fa, fq, t, a.batch, True, os.path.join(tmp, "dut.sam"), ksw_dropin=True, chain_device=a.chain_device, regs_device=a.regs_device,
                  dedup_device=a.dedup_device, matesw_device=a.matesw_device, decide_device=a.decide_device, wanted_device=a.wanted_device,
                  phase2_device=a.phase2_device, samtext_device=a.samtext_device, phase2_text_device=a.phase2_text_device, pestat_device=a.pestat_device,
-                 reads_sam_device=a.reads_sam_device)
+                 reads_sam_device=a.reads_sam_device, pairs_sam_device=a.pairs_sam_device)
             d2["sam_identical"] = refsam == [l for l in open(os.path.join(tmp, "dut.sam")) if not l.startswith("@PG")]
         res["runs"].append({"threads": t, "batch": a.batch, "ref": r, "dut_phase1_gpu": d1, "sam_identical": same1,
                             "dut_phase1_gpu_plus_percall_global": d2})
